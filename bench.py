@@ -5,7 +5,11 @@ One "step" = one pass of the hot path (all chains, all iterations) over one batc
 events already resident in HBM.  Headline workload (BASELINE.json configs[1]): skipped-exon events,
 2 isoforms, 1000 single-end 36-bp reads, 2500 burn-in + 5000 kept iterations, lag 1, 1 chain.
 
-    python bench.py [--gpus N --steps K --warmup W] [--events E per GPU] [--K 2] [--reads 1000]
+    python bench.py [--gpus N --steps K --warmup W] [--events E per GPU] [--K 2] [--reads 1000] [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes, after the timed steps, the results of the last one (posterior samples, log scores, read
+assignments, accept counts) for a fixed, seeded sample of the events as DIR/<name>.npy, float64, under 64 MB: two builds
+run with the same arguments on the same inputs can be compared output for output.
 
 `--gpus N` (N > 1) starts N ranks itself -- one fresh process per GPU through
 `python -m torch.distributed.run`, before anything in this process touches the GPU (the reference's
@@ -41,8 +45,6 @@ import socket
 import subprocess
 import sys
 import time
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before anything initialises HIP (torch in the multi-GPU runs): docs/history.md 4.3 (iv)
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -477,6 +479,54 @@ def time_batch(batch, seed, first, steps, warmup, barrier=None):
     return time.perf_counter() - t0, kernel_ms
 
 
+# --dump-outputs: a fixed, seeded choice of events (the same for the same --events and --gpus), at most DUMP_BYTES in all
+DUMP_EVENTS = 256
+DUMP_SEED = 20251015
+DUMP_BYTES = 60 << 20
+
+
+def dump_rows(batch, first, n_global):
+    """This rank's part of the --dump-outputs sample, from the results of the batch's last launch: per chosen event in the
+    rank's shard, what a caller of the timed path receives (miso_batch_download + miso_batch_get_result)."""
+    import numpy as np
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_global, min(DUMP_EVENTS, n_global), replace=False))
+    batch.download()
+    rows = []
+    for e in pick[(pick >= first) & (pick < first + len(batch))]:
+        r = batch.result(int(e) - first)
+        rows.append((int(e), r.samples, r.loglik, r.assignment, (r.rundata.noAccepted, r.rundata.noRejected)))
+    return rows
+
+
+def write_dump(path, rows):
+    """The sample as DIR/<name>.npy, float64: events in id order while they fit DUMP_BYTES.  Isoform counts may differ
+    between events (whole-gene batches): samples are NaN beyond an event's isoforms; the assignments of all events are
+    one array, event j's at assignment[assignment_offsets[j]:assignment_offsets[j + 1]]."""
+    import numpy as np
+    rows = sorted(rows, key=lambda r: r[0])
+    kmax = max((r[1].shape[1] for r in rows), default=0)
+    keep, total = [], 0
+    for r in rows:
+        total += 8 * (r[1].shape[0] * (kmax + 1) + len(r[3]) + 4)
+        if total > DUMP_BYTES:
+            break
+        keep.append(r)
+    S = keep[0][1].shape[0] if keep else 0
+    samples = np.full((len(keep), S, kmax), np.nan)
+    for j, r in enumerate(keep):
+        samples[j, :, :r[1].shape[1]] = r[1]
+    out = {"event_id": np.array([r[0] for r in keep], np.float64),
+           "samples": samples,
+           "loglik": np.array([r[2] for r in keep], np.float64).reshape(len(keep), S),
+           "assignment": np.concatenate([np.asarray(r[3], np.float64) for r in keep] or [np.zeros(0)]),
+           "assignment_offsets": np.cumsum([0] + [len(r[3]) for r in keep]).astype(np.float64),
+           "accepted_rejected": np.array([r[4] for r in keep], np.float64).reshape(len(keep), 2)}
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return len(keep)
+
+
 def measure_clock(batch, seed, first, kernel_ms):
     """The shader clock the timed launches ran at: ONE more launch of the same batch right behind them, with the library's
     clock probe on (include/miso_amd.h miso_batch_set_clock_probe: one sleeping wavefront beside the sampler kernels that
@@ -618,7 +668,8 @@ def compact_line(full):
                                                                      "n_fail_expected", "mean_abs_dpsi", "max_abs_dpsi", "confirmed_fail")}
     if d is not None:
         out["delta_psi"]["design"] = d["design"].split(";")[0]
-    for k in ("per_rank_kernel_ms", "per_rank_elapsed_ms", "summary_ms", "compare_ms", "cpu_reference_wall_s", "stub", "full_record"):
+    for k in ("per_rank_kernel_ms", "per_rank_elapsed_ms", "summary_ms", "compare_ms", "cpu_reference_wall_s", "stub", "dumped_events",
+              "full_record"):
         if full.get(k) is not None:
             out[k] = full[k]
     if full.get("matrix"):
@@ -668,10 +719,17 @@ def main():
     ap.add_argument("--host-match", action="store_true",
                     help="compute the read x isoform compatibility on the host instead of the GPU (row f1)")
     ap.add_argument("--full-out", default="", help="where the full record goes (default gpurun_out/bench_full.json)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed for a fixed, seeded sample of the events "
+                         "(samples, log scores, read assignments, accept counts) as DIR/<name>.npy, float64, < 64 MB")
     ap.add_argument("--stub", action="store_true",
                     help="TEST ONLY (tests/test_bench_launch.py): build and shard the events on the host, skip "
                          "every GPU call; the line says \"stub\": true and its value means nothing")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.stub:
+        ap.error("--dump-outputs needs the GPU path, not --stub")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus))
@@ -749,6 +807,14 @@ def main():
         elapsed, kernel_ms = time.perf_counter() - t0, [10.0] * a.steps
     else:
         elapsed, kernel_ms = time_batch(batch, a.seed, first, a.steps, a.warmup, barrier)
+    if a.dump_outputs:
+        rows = dump_rows(batch, first, n_global)
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, rows)
+            rows = [r for p in parts for r in p]
+        if rank == 0:
+            n_dumped = write_dump(a.dump_outputs, rows)
     shard = [rank, first, last, float(costs[first:last].sum()), sum(kernel_ms) / max(len(kernel_ms), 1), 1e3 * elapsed / max(a.steps, 1)]
     if dist is not None:
         import torch
@@ -818,6 +884,8 @@ def main():
             "stream_note": streams.get("stream_note"),
             "cpu_reference_wall_s": None if cpu_wall is None else round(cpu_wall, 1),
         }
+        if a.dump_outputs:
+            out["dumped_events"] = n_dumped
         if a.stub:
             out["stub"] = True
         elif want_matrix:

@@ -21,7 +21,7 @@
 
 namespace miso {
 
-extern int g_hw_queues_in_effect;   // capi.hip: GPU_MAX_HW_QUEUES as the runtime read (or will read) it, 0 = unknown
+extern int g_hw_queues_in_effect;   // capi.hip: the host's hardware queue count as the runtime read (or will read) it, 0 = unknown
 
 template <bool PE> __global__ void sampler_wave(const KernelArgs a);
 template <int G, int MODE, int WPB> __global__ void sampler_k2(const KernelArgs a);
@@ -1756,9 +1756,9 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   // hardware queues, and a kernel waits for the one before it in its queue).
   std::vector<char> merged_into_prev(gen_runs.size(), 0);
   // (measured, 16 384 genes of 3-20 isoforms: 4 queues 290 -> 254 ms merged; 8 queues 195 ms apart, 241 ms merged --
-  // the separate launches stagger the classes' starts; capi.hip asks for 8 queues)
-  // (what is IN EFFECT, not what the environment says now: capi.hip's constructor records it; 0 = unknown -- the runtime was
-  // up before this library was loaded -- counts as the runtime's default of 4)
+  // the separate launches stagger the classes' starts; the queue count is the host's, capi.hip only records it)
+  // (what is IN EFFECT, not what the environment says now: capi.hip's constructor records it; 0 = unknown -- not set, or the
+  // runtime was up before this library was loaded -- counts as the runtime's default of 4)
   const int hwq = g_hw_queues_in_effect > 0 ? g_hw_queues_in_effect : 4;
   const bool merge_on = std::getenv("MISO_NO_PE_MERGE") == nullptr && (std::getenv("MISO_PE_MERGE") != nullptr || hwq < 8);
   auto launch_gen_run = [&](size_t ri) {

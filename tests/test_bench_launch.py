@@ -3,13 +3,14 @@ torch.distributed.run, gloo control plane), splits the global event list into co
 shards and prints ONE line with n_gpus == 2.  `--stub` keeps every GPU call out (host packing only):
 what is checked is the launcher, the sharding, the barrier / max-over-ranks and the line's shape --
 the reference's dispatcher likewise starts its own workers (misopy/miso.py:165-187, 205-214) over
-count-based chunks (cluster_utils.py:23-32)."""
+count-based chunks (cluster_utils.py:23-32).  On the GPU: `--dump-outputs` writes what the timed path computed."""
 import json
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -148,3 +149,62 @@ def test_a_failing_row_is_retried_once_and_one_confirmed_row_fails_the_process(m
     fake_delta_psi.verdicts = [False, False]
     d = bench.delta_psi_with_retry("se_k10", dict(bench.BASE_SHAPE), rows, 0, 42)
     assert d["confirmed_fail"] is True
+
+
+def test_dump_outputs_layout_and_budget(tmp_path):
+    """bench.write_dump: events in id order, samples NaN beyond an event's isoforms, the assignments of all events in one
+    array with offsets, everything float64, and no more events than fit the byte budget."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    rows = [(e, rng.random((50, k)), rng.random(50), rng.integers(0, k, n), (a, 50 - a))
+            for e, k, n, a in ((9, 2, 30, 20), (4, 5, 7, 11), (6, 3, 0, 50))]
+    assert bench.write_dump(str(tmp_path), rows) == 3
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(d) == {"event_id", "samples", "loglik", "assignment", "assignment_offsets", "accepted_rejected"}
+    assert all(v.dtype == np.float64 for v in d.values())
+    assert d["event_id"].tolist() == [4, 6, 9] and d["samples"].shape == (3, 50, 5) and d["loglik"].shape == (3, 50)
+    assert np.array_equal(d["samples"][0], rows[1][1]) and np.isnan(d["samples"][2, :, 2:]).all()
+    assert np.array_equal(d["samples"][2, :, :2], rows[0][1]) and np.array_equal(d["loglik"][1], rows[2][2])
+    assert d["assignment_offsets"].tolist() == [0, 7, 7, 37]
+    assert np.array_equal(d["assignment"][7:37], rows[0][3])
+    assert d["accepted_rejected"].tolist() == [[11, 39], [50, 0], [20, 30]]
+    big = [(e, np.zeros((5000, 10)), np.zeros(5000), np.zeros(1000, np.int32), (0, 0)) for e in range(256)]
+    n = bench.write_dump(str(tmp_path / "big"), big)
+    assert 0 < n < 256 and sum(os.path.getsize(os.path.join(tmp_path, "big", f)) for f in os.listdir(tmp_path / "big")) < 64 << 20
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_launch_s_results(tmp_path):
+    """`--dump-outputs`: the same arguments give the same arrays whatever --steps, and they are the results of the
+    headline batch's own launch, event for event."""
+    args = ["--events", "300", "--reads", "100", "--iters", "300", "--burn", "100", "--warmup", "0", "--no-matrix",
+            "--no-cpu-baseline", "--no-streams"]
+    dumps = []
+    for steps in (1, 3):
+        out_dir = tmp_path / ("steps%d" % steps)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--dump-outputs", str(out_dir),
+               "--full-out", str(tmp_path / "bench_full.json")] + args
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout + out.stderr
+        line = json.loads(out.stdout.rstrip().splitlines()[-1])
+        assert line["steps"] == steps and line["dumped_events"] == 256
+        dumps.append({f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)})
+    a, b = dumps
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["samples"].shape == (256, 200, 2) and np.allclose(a["samples"].sum(2), 1.0)
+    sys.path.insert(0, ROOT)
+    import bench
+    from miso_amd import capi
+    capi.set_device(0)
+    batch = bench.build(0, 300, dict(bench.BASE_SHAPE, reads=100, iters=300, burn=100))
+    batch.upload(0)
+    batch.launch(seed=42, first_event_id=0)
+    batch.sync()
+    batch.download()
+    off = a["assignment_offsets"].astype(int)
+    for j, e in enumerate(a["event_id"].astype(int)):
+        r = batch.result(int(e))
+        assert np.array_equal(a["samples"][j], r.samples) and np.array_equal(a["loglik"][j], r.loglik)
+        assert np.array_equal(a["assignment"][off[j]:off[j + 1]], r.assignment)
+        assert a["accepted_rejected"][j].tolist() == [r.rundata.noAccepted, r.rundata.noRejected]
