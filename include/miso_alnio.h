@@ -114,6 +114,49 @@ int miso_batch_add_events_aln(struct miso_batch *batch, int n, const struct miso
                               int given_read_len, int64_t min_reads, int n_threads, int64_t *n_reads,
                               int *event_index);
 
+/* ---- the fragment length distribution of a paired-end file (misopy/pe_utils.py:148-302) ----
+ * Intervals: n_intervals records of a GFF, GFF coordinates (1-based, inclusive): seqid[i], start[i], end[i].  A record
+ * is tagged by interval i when it is mapped (not 0x4, ref_id >= 0), its reference is named seqid[i] and its whole span
+ * lies inside: start[i] - 1 <= pos && end <= end[i] (pos 0-based, end = bam_endpos, spliced span included).  Strand
+ * is not considered.  filter_reads != 0: records with 0x200, 0x4 or 0x8, or without 0x1, do not pair
+ * (sam_utils.py:225-230).  chunk_records: records per device chunk (<= 0: the default, 4 M); device memory is bounded by
+ * it, whatever the file's size.  Both calls fail with MISO_ENODEVICE without a GPU: there is no CPU path. */
+
+/* One code per record (miso_insert_tag_records): bits 0-28 the tag, bit 29 the CIGAR is exactly one M op, bit 30 the
+ * record passes the read filter (always set when filter_reads == 0). */
+#define MISO_INSERT_TAG_MASK   0x1FFFFFFF
+#define MISO_INSERT_TAG_NONE   0x1FFFFFFF  /* no interval contains the record                      */
+#define MISO_INSERT_TAG_MULTI  0x1FFFFFFE  /* two or more do; any other tag value: the interval's index */
+#define MISO_INSERT_ONE_M      (1 << 29)
+#define MISO_INSERT_FILTER_OK  (1 << 30)
+
+typedef struct {
+  int64_t kept;          /* pairs with an insert length > 0                                         */
+  int64_t skipped;       /* pairs failing pe_utils.py:170-189 (one tag each, the same one, one M op) */
+  int64_t unpaired;      /* names whose tagged, filtered records are not exactly two                 */
+  int64_t same_strand;   /* pairs whose mates have equal 0x10                                        */
+  int64_t nonpositive;   /* pairs with an insert length <= 0 (dropped with a warning by the reference) */
+  int64_t tagged;        /* records that join the pairing (tagged and past the filter)              */
+  int64_t chunks;        /* device chunks of the record pass                                         */
+  double records_ms, grouping_ms, pairs_ms;   /* wall time of the three stages                     */
+} miso_insert_stats_t;
+
+/* The record pass alone: codes[n] (n = the file's record count) as above. */
+int miso_insert_tag_records(const miso_alnfile_t *f, int device, int filter_reads, int n_intervals,
+                            const char *const *seqid, const int64_t *start, const int64_t *end,
+                            int64_t chunk_records, int32_t *codes);
+
+/* The whole computation up to the insert lengths: tag, pair by name (strip_mate_id; groups of exactly two, the left
+ * mate the one first in the file, mates on opposite strands), then insert = right.pos + len(right's M) - left.pos for
+ * the pairs whose mates carry exactly one tag each, the same one, and a CIGAR of exactly one M op.  Out: the kept pairs
+ * as (interval index, insert) ordered by interval index, then by the left mate's position in the file.  Two-call
+ * pattern: *n_kept = number of kept pairs, at most `cap` written (arrays may be NULL when cap == 0); a caller that
+ * wants one pass gives cap = records / 2, which no file can exceed.  stats may be NULL. */
+int miso_insert_len(const miso_alnfile_t *f, int device, int filter_reads, int n_intervals,
+                    const char *const *seqid, const int64_t *start, const int64_t *end, int64_t chunk_records,
+                    int32_t *interval_out, int32_t *insert_out, int64_t cap, int64_t *n_kept,
+                    miso_insert_stats_t *stats);
+
 /* host threads the library uses by default: affinity mask capped by the cgroup CPU quota, <= 64 */
 int miso_usable_threads(void);
 

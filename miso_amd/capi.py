@@ -547,3 +547,60 @@ def selftest_philox(ctr_key6):
     out = np.zeros((len(a), 4), np.uint32)
     check(lib().miso_selftest_philox(_p(a), len(a), _p(out)))
     return out
+
+
+# ---- the fragment length distribution of a paired-end file (include/miso_alnio.h miso_insert_len) ----
+MISO_INSERT_TAG_MASK, MISO_INSERT_TAG_NONE, MISO_INSERT_TAG_MULTI = 0x1FFFFFFF, 0x1FFFFFFF, 0x1FFFFFFE
+MISO_INSERT_ONE_M, MISO_INSERT_FILTER_OK = 1 << 29, 1 << 30
+
+
+class InsertStats(C.Structure):
+    _fields_ = ([(n, C.c_int64) for n in ("kept", "skipped", "unpaired", "same_strand", "nonpositive", "tagged",
+                                          "chunks")]
+                + [(n, C.c_double) for n in ("records_ms", "grouping_ms", "pairs_ms")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _intervals(seqids, starts, ends):
+    n = len(seqids)
+    names = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else s for s in seqids])
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    if len(st) != n or len(en) != n:
+        raise ValueError("seqids, starts and ends differ in length")
+    return n, names, st, en
+
+
+_INSERT_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+
+
+def insert_tag_records(alnfile, seqids, starts, ends, device=0, filter_reads=True, chunk_records=0):
+    """The record pass alone: one MISO_INSERT_* code per record of an open alignment file (sam_utils.Samfile);
+    intervals in GFF coordinates (1-based, inclusive)."""
+    n, names, st, en = _intervals(seqids, starts, ends)
+    codes = np.zeros(max(len(alnfile), 1), np.int32)
+    L = lib()
+    L.miso_insert_tag_records.argtypes = _INSERT_ARGS + [C.c_void_p]
+    check(L.miso_insert_tag_records(alnfile._h, int(device), int(bool(filter_reads)), n, names, _p(st), _p(en),
+                                    int(chunk_records), _p(codes)))
+    return codes[:len(alnfile)]
+
+
+def insert_len(alnfile, seqids, starts, ends, device=0, filter_reads=True, chunk_records=0):
+    """Tag, pair and measure on the device (miso_insert_len).  Returns (interval index[], insert[], stats dict): the kept
+    pairs ordered by interval index, then by the left mate's place in the file."""
+    n, names, st, en = _intervals(seqids, starts, ends)
+    cap = len(alnfile) // 2          # no file holds more pairs: one call, no second pass for the size
+    iv = np.zeros(max(cap, 1), np.int32)
+    ins = np.zeros(max(cap, 1), np.int32)
+    kept = C.c_int64(0)
+    stats = InsertStats()
+    L = lib()
+    L.miso_insert_len.argtypes = _INSERT_ARGS + [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                                 C.POINTER(InsertStats)]
+    check(L.miso_insert_len(alnfile._h, int(device), int(bool(filter_reads)), n, names, _p(st), _p(en),
+                            int(chunk_records), _p(iv), _p(ins), cap, C.byref(kept), C.byref(stats)))
+    k = kept.value
+    return iv[:k].copy(), ins[:k].copy(), stats.as_dict()

@@ -451,7 +451,80 @@ std::string_view strip_mate_id(std::string_view name) {
   return name;
 }
 
+// pair_sam_reads' grouping (sam_utils.py:214-233): names through strip_mate_id, groups in order of first appearance,
+// the first two members of a group kept in the order they were added, every member counted.  `item` is what the
+// caller identifies a record by (a record index, a position in a list of records).
+struct NameGroups {
+  struct Group { int64_t r[2]; int64_t count; };
+  std::vector<Group> groups;
+  std::unordered_map<std::string_view, size_t> by_name;
+
+  static std::string_view name_of(const miso_alnfile &f, int64_t i) {
+    return strip_mate_id(std::string_view(f.names.data() + f.name_off[i], f.name_off[i + 1] - f.name_off[i]));
+  }
+  Group &add(std::string_view name, int64_t item) {
+    auto it = by_name.find(name);
+    if (it == by_name.end()) {
+      by_name.emplace(name, groups.size());
+      groups.push_back({{item, -1}, 1});
+      return groups.back();
+    }
+    Group &g = groups[it->second];
+    if (g.count < 2) g.r[g.count] = item;
+    g.count++;
+    return g;
+  }
+};
+
 }  // namespace
+
+// The whole-file form of the grouping above (pe_utils' pairing of every tagged record): records idx[0 .. n) in file
+// order, every one of them already past the read filter.  Out: the groups of exactly two as (first, second) record
+// indices in the order of their first record; *n_unpaired = groups of any other size (sam_utils.py:255-261).  Names are
+// dealt to n_threads shards by hash, each shard grouped on its own thread (a name's records all land in one shard, so
+// its group is the one a single pass would build), and the pairs come out by one scan in file order.
+int miso_aln_pair_records(const miso_alnfile_t *f, const int64_t *idx, int64_t n, int n_threads,
+                          std::vector<int64_t> &pairs, int64_t *n_unpaired) {
+  if (!f || (!idx && n > 0) || !n_unpaired) return fail(MISO_EINVAL, "miso_aln_pair_records: null argument");
+  pairs.clear();
+  try {
+    const int T = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(n_threads > 0 ? n_threads : usable_threads(),
+                                                                          n / 65536 + 1)));
+    std::vector<uint64_t> hash(static_cast<size_t>(n));
+    std::vector<int64_t> mate(static_cast<size_t>(n));   // position of the second record, at the first one's
+    std::vector<int64_t> unpaired(T, 0);
+    auto run = [&](auto &&body) {
+      std::vector<std::thread> th;
+      for (int t = 1; t < T; t++) th.emplace_back(body, t);
+      body(0);
+      for (auto &x : th) x.join();
+    };
+    run([&](int t) {
+      for (int64_t k = n * t / T; k < n * (t + 1) / T; k++) {
+        hash[k] = std::hash<std::string_view>()(NameGroups::name_of(*f, idx[k]));
+        mate[k] = -1;
+      }
+    });
+    run([&](int t) {
+      NameGroups g;
+      for (int64_t k = 0; k < n; k++)
+        if (static_cast<int>(hash[k] % static_cast<uint64_t>(T)) == t) g.add(NameGroups::name_of(*f, idx[k]), k);
+      for (const auto &q : g.groups) {
+        if (q.count == 2) mate[q.r[0]] = q.r[1];
+        else unpaired[t]++;
+      }
+    });
+    int64_t np = 0;
+    for (int64_t k = 0; k < n; k++) np += mate[k] >= 0;
+    pairs.resize(static_cast<size_t>(2 * np));
+    for (int64_t k = 0, j = 0; k < n; k++)
+      if (mate[k] >= 0) { pairs[j++] = idx[k]; pairs[j++] = idx[mate[k]]; }
+    *n_unpaired = std::accumulate(unpaired.begin(), unpaired.end(), int64_t{0});
+  } catch (const std::bad_alloc &) {
+    return fail(MISO_ENOMEM, "out of memory pairing the records by name");
+  }
+  return 0;
+}
 
 extern "C" {
 
@@ -580,30 +653,18 @@ int miso_aln_collect_reads(const miso_alnfile_t *f, int ref, int64_t start, int6
       });
     } else {
       // pair_sam_reads (sam_utils.py:207-300), names in order of first appearance
-      struct Group { int64_t r[2]; int count; };
-      std::vector<Group> groups;
-      std::unordered_map<std::string_view, size_t> by_name;
+      NameGroups ng;
       f->for_overlaps(ref, start, end, [&](int64_t i) {
         const int fl = f->flag[i];
         // QC fail, unmapped, mate unmapped or not paired: never enters the pairing (:225-230)
         if ((fl & 0x200) || (fl & 0x4) || (fl & 0x8) || !(fl & 0x1)) return;
-        const std::string_view name = strip_mate_id(
-            std::string_view(f->names.data() + f->name_off[i], f->name_off[i + 1] - f->name_off[i]));
-        auto it = by_name.find(name);
-        if (it == by_name.end()) {
-          by_name.emplace(name, groups.size());
-          groups.push_back({{i, -1}, 1});
-          return;
-        }
-        Group &g = groups[it->second];
-        if (g.count < 2) g.r[g.count] = i;
-        g.count++;
+        NameGroups::Group &g = ng.add(NameGroups::name_of(*f, i), i);
         if (g.count == 2 && strand_rule == MISO_STRAND_FIRSTSTRAND) {        // :236-248
           if ((f->flag[g.r[0]] & 0x40) && minus(g.r[0])) std::swap(g.r[0], g.r[1]);
           if ((f->flag[g.r[0]] & 0x80) && minus(g.r[0])) std::swap(g.r[0], g.r[1]);
         }
       });
-      for (const Group &g : groups) {
+      for (const NameGroups::Group &g : ng.groups) {
         if (g.count != 2) continue;                                          // :255-261
         const int64_t a = g.r[0], b = g.r[1];
         if (minus(a) == minus(b)) continue;                                  // :264-271 same strand

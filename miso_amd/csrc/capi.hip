@@ -54,6 +54,14 @@ int miso_aln_collect_reads(const miso_alnfile_t *f, int ref, int64_t start, int6
                            std::vector<int32_t> &pos_out, std::string &cig_out, int64_t *n_reads,
                            int64_t *n_strand_discarded);
 
+namespace miso {   // kernels_insert.hip
+void insert_tag_records(const miso_alnfile_t *f, int device, int filter, int n_iv, const char *const *seqid,
+                        const int64_t *start, const int64_t *end, int64_t chunk, int32_t *codes, int64_t *n_chunks);
+void insert_len(const miso_alnfile_t *f, int device, int filter, int n_iv, const char *const *seqid,
+                const int64_t *start, const int64_t *end, int64_t chunk, int32_t *iv_out, int32_t *ins_out,
+                int64_t cap, int64_t *n_kept, miso_insert_stats_t *stats);
+}  // namespace miso
+
 using namespace miso;
 
 struct miso_gene { Gene g; };
@@ -496,6 +504,24 @@ int miso_batch_add_events_aln(miso_batch_t *b, int n, const miso_gene_t *const *
       b->events.push_back(std::move(ph));
       event_index[i] = static_cast<int>(b->events.size()) - 1;
     }
+  });
+}
+
+int miso_insert_tag_records(const miso_alnfile_t *f, int device, int filter_reads, int n_intervals,
+                            const char *const *seqid, const int64_t *start, const int64_t *end,
+                            int64_t chunk_records, int32_t *codes) {
+  return guarded([&] {
+    insert_tag_records(f, device, filter_reads, n_intervals, seqid, start, end, chunk_records, codes, nullptr);
+  });
+}
+
+int miso_insert_len(const miso_alnfile_t *f, int device, int filter_reads, int n_intervals,
+                    const char *const *seqid, const int64_t *start, const int64_t *end, int64_t chunk_records,
+                    int32_t *interval_out, int32_t *insert_out, int64_t cap, int64_t *n_kept,
+                    miso_insert_stats_t *stats) {
+  return guarded([&] {
+    insert_len(f, device, filter_reads, n_intervals, seqid, start, end, chunk_records, interval_out, insert_out, cap,
+               n_kept, stats);
   });
 }
 

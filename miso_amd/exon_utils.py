@@ -1,0 +1,111 @@
+"""exon_utils --get-const-exons: the constitutive exons of a GFF3 annotation (misopy/exon_utils.py:42-83, 253-318,
+331-369), the first step of the fragment-length recipe (`pe_utils --compute-insert-len` takes the file it writes).
+
+Per gene: the exons of its first transcript whose length (end - start + 1) is at least --min-exon-size and which every
+other transcript of the gene has too (same start, end and strand).  Each is written with the attribute
+`GeneParent=<gene id>` added, to `<output dir>/<GFF basename without .gff/.gff3>.min_<N>.const_exons.gff`, in the order
+the records have in the input (the reference's order comes from a dict).
+"""
+import argparse
+import os
+import re
+import sys
+import time
+
+from miso_amd import gff_utils
+
+# GFF3 column 9: these characters are escaped inside tags and values; columns 1-8 escape tab, newline and '%'
+_ATTR_ESCAPE = re.compile(r"[\t\n\r\f\v;=%&,]")
+_COLUMN_ESCAPE = re.compile(r"[\t\n\r%]")
+
+
+def _escape(pattern, text):
+    return pattern.sub(lambda m: "%%%02X" % ord(m.group(0)), text)
+
+
+def is_exon_in_mRNA(gff_db, exon, mRNA):
+    """Does the transcript have an exon with the same start, end and strand?"""
+    return any(e.start == exon.start and e.end == exon.end and e.strand == exon.strand
+               for e in gff_db.exons_by_mRNA.get(mRNA.get_id(), []))
+
+
+def get_const_exons_from_mRNA(gff_db, mRNAs, min_size=0):
+    """The constitutive exons of one gene (its transcripts `mRNAs`, file order), GeneParent set."""
+    first = mRNAs[0]
+    gene_id = first.get_parent()
+    const = []
+    for exon in gff_db.exons_by_mRNA.get(first.get_id(), []):
+        if exon.end - exon.start + 1 < min_size:
+            continue
+        if all(is_exon_in_mRNA(gff_db, exon, m) for m in mRNAs[1:]):
+            exon.attributes["GeneParent"] = [gene_id]
+            const.append(exon)
+    return const
+
+
+def get_const_exons(gff_filename, min_size=0):
+    """Every gene's constitutive exons, in the order of the input file."""
+    gff_db = gff_utils.GFFDatabase(from_filename=gff_filename)
+    place = {id(rec): k for k, rec in enumerate(gff_db.exons)}
+    const = []
+    for mRNAs in gff_db.mRNAs_by_gene.values():
+        const.extend(get_const_exons_from_mRNA(gff_db, mRNAs, min_size=min_size))
+    return sorted(const, key=lambda rec: place[id(rec)])
+
+
+def const_exons_filename(gff_filename, output_dir, min_size):
+    basename = re.sub("[.]gff3?", "", os.path.basename(gff_filename))
+    return os.path.join(output_dir, "%s.min_%d.const_exons.gff" % (basename, min_size))
+
+
+def _field(value):
+    return "." if value is None or value == "" else str(value)
+
+
+def format_record(rec):
+    """One GFF3 line (no newline)."""
+    attrs = ";".join("%s=%s" % (_escape(_ATTR_ESCAPE, tag), ",".join(_escape(_ATTR_ESCAPE, v) for v in values))
+                     for tag, values in rec.attributes.items())
+    return "\t".join([_escape(_COLUMN_ESCAPE, rec.seqid), _escape(_COLUMN_ESCAPE, rec.source),
+                      _escape(_COLUMN_ESCAPE, rec.type), str(rec.start), str(rec.end), _field(rec.score),
+                      _field(rec.strand), _field(rec.phase), _field(attrs)])
+
+
+def write_gff(records, output_filename):
+    with open(output_filename, "w") as out:
+        out.write("##gff-version 3\n")
+        for rec in records:
+            out.write(format_record(rec) + "\n")
+
+
+def get_const_exons_by_gene(gff_filename, output_dir, min_size=0):
+    """Write the constitutive exons of `gff_filename` into output_dir; returns (records, output filename)."""
+    os.makedirs(output_dir, exist_ok=True)
+    t0 = time.time()
+    const = get_const_exons(gff_filename, min_size=min_size)
+    output_filename = const_exons_filename(gff_filename, output_dir, min_size)
+    write_gff(const, output_filename)
+    print("Constitutive exons: %d (at least %d bp) in %.2f s -> %s"
+          % (len(const), min_size, time.time() - t0, output_filename))
+    return const, output_filename
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(prog="exon_utils", description="Constitutive exons of a GFF3 annotation.")
+    parser.add_argument("--get-const-exons", dest="get_const_exons", metavar="GFF", default=None,
+                        help="Get constitutive exons from an input GFF file.")
+    parser.add_argument("--min-exon-size", dest="min_exon_size", type=int, default=20,
+                        help="Minimum size of a constitutive exon (in nucleotides). Default is 20 bp.")
+    parser.add_argument("--output-dir", dest="output_dir", default=None, help="Output directory.")
+    options = parser.parse_args(argv)
+    if options.get_const_exons is None or options.output_dir is None:
+        parser.print_help(sys.stderr)
+        return 1
+    get_const_exons_by_gene(os.path.abspath(os.path.expanduser(options.get_const_exons)),
+                            os.path.abspath(os.path.expanduser(options.output_dir)),
+                            min_size=options.min_exon_size)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
