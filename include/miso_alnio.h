@@ -157,6 +157,27 @@ int miso_insert_len(const miso_alnfile_t *f, int device, int filter_reads, int n
                     int32_t *interval_out, int32_t *insert_out, int64_t cap, int64_t *n_kept,
                     miso_insert_stats_t *stats);
 
+/* ---- per-interval read coverage (`miso --run --prefilter`, misopy/exon_utils.py:198-250) ----
+ * Intervals as for miso_insert_len (GFF coordinates, seqid[i] named exactly as the file names it; a seqid the file
+ * does not name, or start[i] > end[i], counts 0).  A record is kept when it is mapped (not 0x4, ref_id >= 0) and some
+ * interval on its reference holds its whole span (start - 1 <= pos && bam_endpos <= end; bedtools intersect -f 1); no
+ * other flag matters.  counts[i] = the kept records on interval i's reference with pos < end[i] and
+ * bam_endpos > start[i] - 1 (bedtools coverage -counts).  chunk_records: records per device chunk (<= 0: the default,
+ * 4 M); device memory is bounded by it and by n_intervals.  The counts do not depend on it or on the record order.
+ * Fails with MISO_ENODEVICE without a GPU: there is no CPU path.  stats may be NULL. */
+typedef struct {
+  int64_t kept;          /* records held whole by some interval                                             */
+  int64_t chunks;        /* device chunks of the record pass                                                */
+  double records_ms;     /* record pass: copies of the columns to the device and the kernel (device time)   */
+  double sort_ms;        /* the host tables: intervals sorted per reference, the sorted rank keys           */
+  double rank_ms;        /* rank step: prefix sums of the rank histograms and the per-interval differences  */
+  double total_ms;       /* wall time of the whole call                                                     */
+} miso_region_stats_t;
+
+int miso_region_counts(const miso_alnfile_t *f, int device, int n_intervals, const char *const *seqid,
+                       const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
+                       miso_region_stats_t *stats);
+
 /* host threads the library uses by default: affinity mask capped by the cgroup CPU quota, <= 64 */
 int miso_usable_threads(void);
 

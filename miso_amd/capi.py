@@ -604,3 +604,27 @@ def insert_len(alnfile, seqids, starts, ends, device=0, filter_reads=True, chunk
                             int(chunk_records), _p(iv), _p(ins), cap, C.byref(kept), C.byref(stats)))
     k = kept.value
     return iv[:k].copy(), ins[:k].copy(), stats.as_dict()
+
+
+# ---- per-interval read coverage (include/miso_alnio.h miso_region_counts) ----
+class RegionStats(C.Structure):
+    _fields_ = ([(n, C.c_int64) for n in ("kept", "chunks")]
+                + [(n, C.c_double) for n in ("records_ms", "sort_ms", "rank_ms", "total_ms")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def region_counts(alnfile, seqids, starts, ends, device=0, chunk_records=0):
+    """Kept records (mapped, span held whole by some interval) overlapping each interval of an open alignment file
+    (sam_utils.Samfile), intervals in GFF coordinates (1-based, inclusive), seqids spelled as the file spells them.
+    Returns (int64 counts per interval, stats dict)."""
+    n, names, st, en = _intervals(seqids, starts, ends)
+    counts = np.zeros(max(n, 1), np.int64)
+    stats = RegionStats()
+    L = lib()
+    L.miso_region_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.POINTER(RegionStats)]
+    check(L.miso_region_counts(alnfile._h, int(device), n, names, _p(st), _p(en), int(chunk_records), _p(counts),
+                               C.byref(stats)))
+    return counts[:n].copy(), stats.as_dict()

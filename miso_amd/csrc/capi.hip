@@ -62,6 +62,11 @@ void insert_len(const miso_alnfile_t *f, int device, int filter, int n_iv, const
                 int64_t cap, int64_t *n_kept, miso_insert_stats_t *stats);
 }  // namespace miso
 
+namespace miso {   // kernels_coverage.hip
+void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *const *seqid, const int64_t *start,
+                   const int64_t *end, int64_t chunk, int64_t *counts, miso_region_stats_t *stats);
+}  // namespace miso
+
 using namespace miso;
 
 struct miso_gene { Gene g; };
@@ -523,6 +528,12 @@ int miso_insert_len(const miso_alnfile_t *f, int device, int filter_reads, int n
     insert_len(f, device, filter_reads, n_intervals, seqid, start, end, chunk_records, interval_out, insert_out, cap,
                n_kept, stats);
   });
+}
+
+int miso_region_counts(const miso_alnfile_t *f, int device, int n_intervals, const char *const *seqid,
+                       const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
+                       miso_region_stats_t *stats) {
+  return guarded([&] { region_counts(f, device, n_intervals, seqid, start, end, chunk_records, counts, stats); });
 }
 
 int miso_gene_assignment_matrix(const miso_gene_t *gene, int readLength, int overHang, double *matrix, int max_cols,

@@ -43,6 +43,11 @@ def _attributes(column9):
     return out
 
 
+def parse_gff_attribs(column9):
+    """Column 9 as the index reads it: {tag: [values]} (misopy/gff_utils.py parse_gff_attribs)."""
+    return _attributes(column9)
+
+
 class GFF(object):
     """One annotation record: seqid, source, type, start, end, score, strand, phase, attributes."""
     __slots__ = ("seqid", "source", "type", "start", "end", "score", "strand", "phase", "attributes")

@@ -2,7 +2,7 @@
 
     python -m miso_amd.miso --run INDEXED_GFF_DIR ALIGNMENTS.bam --output-dir OUT --read-len 36 \
            [--paired-end MEAN SD] [--overhang-len N] [--settings-filename F] [--event-type T]
-           [-p N_GPUS] [--seed S]
+           [-p N_GPUS] [--seed S] [--prefilter]
 
 The reference's GenesDispatcher (miso.py:69-337) splits the gene list into `num_processors`
 chunks (cluster_utils.chunk_list) and runs `run_miso.py --compute-genes-from-file` on each in its
@@ -10,7 +10,13 @@ own process, one CPU core per process.  Here a chunk is a GPU: `-p N` = number o
 node (default: all visible), one child process per GPU, each sampling its contiguous chunk as GPU
 batches; no communication between them.  Every event keeps its GLOBAL index in the Philox counter
 (`--first-event-id`), so the .miso files do not depend on N.  Cluster submission (`--use-cluster`,
-SGE), `--prefilter` (bedtools) are outside the path and not provided.
+SGE) is outside the path and not provided.
+
+`--prefilter` (miso.py:379-404, run_events_analysis.py:28-68) counts the records of the alignment file that lie whole
+inside the index's genes (`genes.gff`) on the GPU instead of with bedtools (exon_utils.get_bam_gff_coverage,
+csrc/kernels_coverage.hip), in a short-lived child process: the dispatcher itself never initialises HIP.  Only the
+genes with at least min_event_reads are dispatched, each with its number in the whole gene list (a third column of the
+batch files), so a kept gene's .miso file is the one a run without --prefilter writes.
 """
 import os
 import subprocess
@@ -69,6 +75,27 @@ def visible_gpus():
         return kfd or 0
 
 
+class PrefilterError(Exception):
+    """No event passes the coverage filter, or the coverage pass failed: nothing is dispatched."""
+
+
+def _coverage_child(bam_filename, gff_filename, output_filename):
+    """The coverage pass of --prefilter, forked from the dispatcher: on GPU 0, over the alignments the dispatcher
+    decoded when it did (inherited), else over the file opened here; writes the table and exits."""
+    rc = 1
+    try:
+        from . import exon_utils, sam_utils
+        bamfile = sam_utils._PRELOADED.get(os.path.abspath(os.path.expanduser(bam_filename)))
+        exon_utils.compute_bam_gff_coverage(bam_filename, gff_filename, output_filename, bamfile=bamfile, device=0)
+        rc = 0
+    except BaseException:
+        import traceback
+        traceback.print_exc()
+    finally:
+        sys.stdout.flush(); sys.stderr.flush()
+        os._exit(rc)
+
+
 def _forked_worker(argv, log, worker_no=0, n_workers=1):
     """One worker of `miso --run`, forked from the dispatcher: output to its log file, its share of the
     host cores (the native stages -- read collection, CIGAR parsing, `.miso` formatting -- size their
@@ -105,8 +132,11 @@ class GenesDispatcher(object):
     def __init__(self, gff_dir, bam_filename, output_dir, read_len, overhang_len,
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
-                 labels=("sample1", "sample2"), summary_only=False):
+                 labels=("sample1", "sample2"), summary_only=False, prefilter=False):
         self.summary_only = bool(summary_only)
+        self.prefilter = bool(prefilter)
+        self.event_numbers = None      # --prefilter: gene id -> its number in the whole gene list
+        self.gene_samples = None       # --prefilter --compare: gene id -> the samples whose filter it passes
         self.gff_dir, self.bam_filename, self.output_dir = gff_dir, bam_filename, output_dir
         if not os.path.isfile(self.bam_filename):
             raise IOError("BAM file %s not found." % self.bam_filename)
@@ -130,8 +160,60 @@ class GenesDispatcher(object):
             raise ValueError("No genes to run on. Did you pass me the wrong path to your index "
                              "GFF directory? Or perhaps your indexed GFF directory is empty?")
 
+    def apply_prefilter(self):
+        """--prefilter (miso.py:379-404, run_events_analysis.py:28-68): keep the genes whose coverage table line passes,
+        in index order; with --compare, those passing in either sample.  Raises PrefilterError when none passes."""
+        from . import exon_utils
+        genes_gff = os.path.join(self.gff_dir, "genes.gff")
+        if not os.path.isfile(genes_gff):
+            print("WARNING: Could not find 'genes.gff' in %s - skipping prefilter stage. Please reindex your GFF file "
+                  "with the latest version to enable prefiltering." % self.gff_dir)
+            return
+        if self.compare_bam is None:
+            targets = [(self.bam_filename, self.output_dir)]
+        else:
+            targets = [(self.bam_filename, os.path.join(self.output_dir, self.labels[0])),
+                       (self.compare_bam, os.path.join(self.output_dir, self.labels[1]))]
+        min_event_reads = Settings.get_min_event_reads()
+        passing = []
+        for bam, out_dir in targets:
+            print("Prefiltering reads...")
+            table = exon_utils.get_bam_gff_coverage(bam, genes_gff, out_dir, compute=self._coverage_in_child)
+            passing.append(set(exon_utils.get_ids_passing_filter(table, min_event_reads)))
+        self.event_numbers = {g: k for k, g in enumerate(self.gene_ids)}
+        kept = [g for g in self.gene_ids if any(g in p for p in passing)]
+        if not kept:
+            raise PrefilterError("None of the events in %s appear to meet the read coverage filter. Check that your "
+                                 "BAM headers in %s match the GFF headers of indexed events."
+                                 % (self.gff_dir, ", ".join(b for b, _ in targets)))
+        print("Total of %d events pass coverage filter." % len(kept))
+        if self.compare_bam is not None:
+            self.gene_samples = {g: ",".join(str(k + 1) for k, p in enumerate(passing) if g in p) for g in kept}
+        self.gene_ids = kept
+
+    def _coverage_in_child(self, bam_filename, gff_filename, output_filename):
+        import multiprocessing
+        sys.stdout.flush()
+        p = multiprocessing.get_context("fork").Process(target=_coverage_child,
+                                                        args=(bam_filename, gff_filename, output_filename))
+        p.start()
+        p.join()
+        if p.exitcode != 0 or not os.path.isfile(output_filename):
+            raise PrefilterError("the coverage pass over %s failed (exit %s)" % (bam_filename, p.exitcode))
+
+    def _decode_once(self):
+        """Decode the alignment file(s) here, through the HIP-free reader library, for the forked children."""
+        from . import sam_utils
+        sam_utils.use_reader_library()
+        for path in (self.bam_filename, self.compare_bam):
+            if path is not None:
+                full = os.path.abspath(os.path.expanduser(path))
+                if full not in sam_utils._PRELOADED:
+                    sam_utils._PRELOADED[full] = sam_utils.Samfile(full, "rb")
+
     def output_batch_files(self):
-        """miso.py:152-186: batch-<n>_genes.txt, two columns: gene ID, indexed file."""
+        """miso.py:152-186: batch-<n>_genes.txt, two columns: gene ID, indexed file; with --prefilter a third, the
+        gene's number in the whole gene list, and with --compare a fourth, the samples whose filter it passes."""
         batches = []
         first = 0
         for batch_num, ids in enumerate(chunk_list(self.gene_ids, self.num_processors)):
@@ -141,13 +223,30 @@ class GenesDispatcher(object):
                     if gene_id not in self.gene_ids_to_gff_index:
                         print("Skipping: %s" % gene_id)
                         continue
-                    out.write("%s\t%s\n" % (gene_id, self.gene_ids_to_gff_index[gene_id]))
+                    line = "%s\t%s" % (gene_id, self.gene_ids_to_gff_index[gene_id])
+                    if self.event_numbers is not None:
+                        line += "\t%d" % self.event_numbers[gene_id]
+                    if self.gene_samples is not None:
+                        line += "\t%s" % self.gene_samples[gene_id]
+                    out.write(line + "\n")
             batches.append((fname, len(ids), first))
             first += len(ids)
         return batches
 
     def run(self):
         t_run0 = time.time()
+        fork = os.environ.get("MISO_DISPATCH", "fork") != "subprocess"
+        if self.prefilter:
+            # the coverage child inherits the one decode the workers will share (when they will share one)
+            if fork and (self.num_processors > 1 or self.compare_bam is not None):
+                try:
+                    self._decode_once()
+                except (ImportError, OSError, RuntimeError, ValueError):
+                    from . import sam_utils
+                    sam_utils._PRELOADED.clear()
+            self.apply_prefilter()
+            if os.environ.get("MISO_TIMING"):
+                print("[miso] prefilter done %.2f s after run() started" % (time.time() - t_run0))
         batches = self.output_batch_files()
         if os.environ.get("MISO_TIMING"):
             print("[miso] batch files written in %.2f s" % (time.time() - t_run0))
@@ -204,7 +303,7 @@ class GenesDispatcher(object):
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
         # index (run_miso.py:86,100); round 1 decoded the whole file in every worker (`-p 4` on one GPU was
         # slower than `-p 1`).  MISO_DISPATCH=subprocess: fresh interpreters that decode for themselves.
-        if os.environ.get("MISO_DISPATCH", "fork") == "subprocess" or not jobs:
+        if not fork or not jobs:
             return self._run_subprocesses(jobs, parts, table)
         import multiprocessing
         from . import sam_utils
@@ -218,11 +317,7 @@ class GenesDispatcher(object):
             p.start()
             return self._finish([(batch_num, p.join, lambda p=p: p.exitcode, log)], parts, table)
         try:
-            sam_utils.use_reader_library()
-            for path in (self.bam_filename, self.compare_bam):
-                if path is not None:
-                    full = os.path.abspath(os.path.expanduser(path))
-                    sam_utils._PRELOADED[full] = sam_utils.Samfile(full, "rb")
+            self._decode_once()
         except (ImportError, OSError, RuntimeError, ValueError) as e:
             # no reader library (a partial build) or the one decode failed: the workers decode for themselves
             # (the jobs are built; nothing is re-done and the process's environment is left alone)
@@ -269,7 +364,7 @@ class GenesDispatcher(object):
 def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_len=1,
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
-                          labels=("sample1", "sample2"), summary_only=False):
+                          labels=("sample1", "sample2"), summary_only=False, prefilter=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -280,7 +375,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
     return GenesDispatcher(gff_dir, bam_filename, output_dir, read_len, overhang_len,
                            settings_fname=settings_fname, paired_end=paired_end, num_proc=num_proc,
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
-                           compare_bam=compare_bam, labels=labels, summary_only=summary_only).run()
+                           compare_bam=compare_bam, labels=labels, summary_only=summary_only,
+                           prefilter=prefilter).run()
 
 
 def main(argv=None):
@@ -307,6 +403,13 @@ def main(argv=None):
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
     ap.add_argument("--labels", nargs=2, default=("sample1", "sample2"))
+    ap.add_argument("--prefilter", default=False, action="store_true",
+                    help="Prefilter events based on coverage. If given as argument, run will begin by mapping BAM "
+                         "reads to event regions (counted on the GPU), and omit events that do not meet coverage "
+                         "criteria from the run. By default, turned off. Note that events that do not meet the "
+                         "coverage criteria will not be processed regardless, but --prefilter simply does this "
+                         "filtering step at the start of the run, potentially saving computation time so that low "
+                         "coverage events will not be processed or distributed to jobs.")
     a = ap.parse_args(argv)
     settings_filename = None if a.settings_filename is None else \
         os.path.abspath(os.path.expanduser(a.settings_filename))
@@ -321,15 +424,19 @@ def main(argv=None):
         print("Error: need --read-len to compute Psi values.")
         return 1
     gff_dir, bam = (os.path.abspath(os.path.expanduser(p)) for p in a.run)
-    failed = compute_all_genes_psi(gff_dir, bam, a.read_len,
-                                   os.path.abspath(os.path.expanduser(a.output_dir)),
-                                   overhang_len=a.overhang_len or 1, paired_end=a.paired_end,
-                                   settings_fname=settings_filename, num_proc=a.num_proc,
-                                   event_type=a.event_type, seed=a.seed, summarize=a.summarize,
-                                   summary_only=a.summary_only,
-                                   compare_bam=None if a.compare is None else
-                                   os.path.abspath(os.path.expanduser(a.compare)),
-                                   labels=tuple(a.labels))
+    try:
+        failed = compute_all_genes_psi(gff_dir, bam, a.read_len,
+                                       os.path.abspath(os.path.expanduser(a.output_dir)),
+                                       overhang_len=a.overhang_len or 1, paired_end=a.paired_end,
+                                       settings_fname=settings_filename, num_proc=a.num_proc,
+                                       event_type=a.event_type, seed=a.seed, summarize=a.summarize,
+                                       summary_only=a.summary_only,
+                                       compare_bam=None if a.compare is None else
+                                       os.path.abspath(os.path.expanduser(a.compare)),
+                                       labels=tuple(a.labels), prefilter=a.prefilter)
+    except PrefilterError as err:
+        print("Error: %s" % err)
+        return 1
     if os.environ.get("MISO_TIMING"):
         print("[miso] main() %.2f s" % (time.time() - t_main0))
     return 1 if failed else 0

@@ -146,9 +146,10 @@ def _check_device(device):
 def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, read_len,
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
-                     max_events_per_launch=8192, summary_file=None, write_files=True):
+                     max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
-    reference's (gene_ids, one index file) so a whole batch file is one GPU batch."""
+    reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
+    number in the random-number counter (default first_event_id + k)."""
     os.makedirs(output_dir, exist_ok=True)
     if gene_entries is None:
         gene_entries = [(g, gff_index_filename) for g in gene_ids]
@@ -243,7 +244,7 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=output_dir)
             # every event keeps the number it has in the caller's gene list: skipped genes, chunking
             # and the number of GPUs do not change anybody's random stream
-            chunk = [ev[:4] + (first_event_id + ev[4],) for ev in chunk]
+            chunk = [ev[:4] + (_event_number(ev[4], first_event_id, event_ids),) for ev in chunk]
             tp = time.time()
             state = sampler.prepare_batch(num_iters, chunk, num_chains=num_chains, burn_in=burn_in,
                                           lag=lag, verbose=verbose)
@@ -275,6 +276,11 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     return written, info
 
 
+def _event_number(k, first_event_id, event_ids):
+    """Entry k's id in the random-number counter: its number in the whole gene list."""
+    return first_event_id + k if event_ids is None else int(event_ids[k])
+
+
 def merge_tables(parts, filename, remove=True):
     """Concatenate tab-separated tables that share a header line (per-batch / per-GPU parts)."""
     os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
@@ -298,11 +304,14 @@ def merge_tables(parts, filename, remove=True):
 def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, output_dir2,
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
-                     max_events_per_launch=4096):
+                     max_events_per_launch=4096, event_ids=None, samples=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
-    computed on the device while the samples are still in HBM."""
+    computed on the device while the samples are still in HBM.
+    event_ids[k]: as for compute_gene_psi.  samples[k] (`miso --run --compare --prefilter`): the samples whose
+    coverage filter entry k passes, "1", "2" or "1,2".  An entry is collected only in those samples; one that passes
+    in one sample only is sampled there alone (with that sample's seed) and is not compared."""
     for d in (output_dir1, output_dir2):
         os.makedirs(d, exist_ok=True)
     if device is not None:
@@ -310,10 +319,13 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         os.environ["MISO_DEVICE"] = str(int(device))
     p = Settings.get_sampler_params()
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
-    ev1, info1 = collect_gene_events(gene_entries, bam1, output_dir1, read_len, overhang_len,
-                                     paired_end=paired_end, event_type=event_type, verbose=verbose)
-    ev2, info2 = collect_gene_events(gene_entries, bam2, output_dir2, read_len, overhang_len,
-                                     paired_end=paired_end, event_type=event_type, verbose=verbose)
+    evs = []
+    for which, bam, out in (("1", bam1, output_dir1), ("2", bam2, output_dir2)):
+        ks = [k for k in range(len(gene_entries)) if samples is None or which in samples[k].split(",")]
+        ev, _ = collect_gene_events([gene_entries[k] for k in ks], bam, out, read_len, overhang_len,
+                                    paired_end=paired_end, event_type=event_type, verbose=verbose)
+        evs.append([e[:4] + (ks[e[4]],) for e in ev])        # numbered in gene_entries
+    ev1, ev2 = evs
     # pair by gene: only genes that passed the filters in BOTH samples are compared
     # (compare_miso leaves out events missing from one directory, hypothesis_test.py:262-264)
     by_no2 = {e[4]: e for e in ev2}
@@ -336,21 +348,52 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                      [b[:3] for _, b in chunk], part, num_chains=p["num_chains"],
                                      burn_in=p["burn_in"], lag=p["lag"], seed=seed,
                                      first_event_id=first_event_id + lo, verbose=verbose,
-                                     event_ids=[first_event_id + a[4] for a, _ in chunk])
+                                     event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk])
     merge_tables(parts, comparison_file)
+    if samples is not None:
+        # sample 2's stream: the seed MISOCompareBatch derives for it (pysplicingmodule.c)
+        seed2 = None if seed is None else (int(seed) ^ 0x5851F42D4C957F2D) & 0xFFFFFFFFFFFFFFFF
+        for which, ev, out, s in (("1", ev1, output_dir1, seed), ("2", ev2, output_dir2, seed2)):
+            alone = [e[:4] + (_event_number(e[4], first_event_id, event_ids),) for e in ev if samples[e[4]] == which]
+            if not alone:
+                continue
+            if paired_end:
+                params = miso.get_paired_end_sampler_params(2, mean_frag_len, frag_variance, read_len,
+                                                            overhang_len=overhang_len)
+            else:
+                params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
+            sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=out)
+            sampler.run_sampler_batch(p["num_iters"], alone, num_chains=p["num_chains"], burn_in=p["burn_in"],
+                                      lag=p["lag"], seed=s, verbose=verbose)
     return len(pairs)
 
 
 def read_genes_file(genes_filename):
     """Two-column, tab-delimited: gene ID, indexed GFF file (run_miso.py:236-250)."""
-    entries = []
+    return read_genes_file_columns(genes_filename)[0]
+
+
+def read_genes_file_columns(genes_filename):
+    """A batch file with its optional columns (`miso --run --prefilter`): 3rd the gene's number in the whole gene list,
+    4th the samples whose coverage filter it passes.  Returns (entries, numbers or None, samples or None); a column is
+    given for every line or for none."""
+    entries, numbers, samples = [], [], []
     with open(genes_filename) as genes_in:
         for line in genes_in:
             if not line.strip():
                 continue
-            gene_id, gff_filename = line.strip().split("\t")
-            entries.append((gene_id, gff_filename))
-    return entries
+            fields = line.strip().split("\t")
+            if len(fields) not in (2, 3, 4):
+                raise ValueError("%s: a batch file line has 2 to 4 columns: %r" % (genes_filename, line))
+            entries.append((fields[0], fields[1]))
+            if len(fields) > 2:
+                numbers.append(int(fields[2]))
+            if len(fields) > 3:
+                samples.append(fields[3])
+    for col in (numbers, samples):
+        if col and len(col) != len(entries):
+            raise ValueError("%s: optional columns must be given on every line" % genes_filename)
+    return entries, numbers or None, samples or None
 
 
 def main(argv=None):
@@ -384,10 +427,11 @@ def main(argv=None):
     if a.compare_genes_from_file:
         genes_filename, bam1, bam2, out1, out2, bf = (os.path.abspath(os.path.expanduser(x))
                                                      for x in a.compare_genes_from_file)
-        entries = read_genes_file(genes_filename)
+        entries, numbers, samples = read_genes_file_columns(genes_filename)
         n = compare_gene_psi(entries, bam1, bam2, out1, out2, bf, a.read_len, overhang_len,
                              paired_end=paired_end, event_type=a.event_type, seed=a.seed,
-                             first_event_id=a.first_event_id, device=a.device)
+                             first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
+                             samples=samples)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -396,10 +440,10 @@ def main(argv=None):
             if not os.path.isfile(p):
                 print("Error: %s does not exist." % p)
                 return 1
-        entries = read_genes_file(genes_filename)
+        entries, numbers, _ = read_genes_file_columns(genes_filename)
         compute_gene_psi(None, None, bam_filename, output_dir, a.read_len, overhang_len,
                          paired_end=paired_end, event_type=a.event_type, gene_entries=entries,
-                         seed=a.seed, first_event_id=a.first_event_id, device=a.device,
+                         seed=a.seed, first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
                          summary_file=a.summary_file,
                          write_files=not (a.no_miso_files and a.summary_file))
         print("Processed %d genes" % len(entries))
