@@ -5,7 +5,12 @@ One "step" = one pass of the hot path (all chains, all iterations) over one batc
 events already resident in HBM.  Headline workload (BASELINE.json configs[1]): skipped-exon events,
 2 isoforms, 1000 single-end 36-bp reads, 2500 burn-in + 5000 kept iterations, lag 1, 1 chain.
 
-    python bench.py [--gpus N --steps K --warmup W] [--events E per GPU] [--K 2] [--reads 1000] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--events E per GPU] [--K 2] [--reads 1000] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it builds and uploads the batch, runs the warm-up and the timed
+steps, writes `--dump-outputs` if asked and prints the line.  Everything else it can measure or check -- the reference's
+CPU baseline, the |delta psi| test, the roofline and the clock-probe launch behind it, rows f2 / f3, the matrix of other
+shapes and the full record -- runs only with `--full` (the `--no-*` options then leave parts of it out).
 
 `--dump-outputs DIR` writes, after the timed steps, the results of the last one (posterior samples, log scores, read
 assignments, accept counts) for a fixed, seeded sample of the events as DIR/<name>.npy, float64, under 64 MB: two builds
@@ -15,13 +20,13 @@ run with the same arguments on the same inputs can be compared output for output
 `python -m torch.distributed.run`, before anything in this process touches the GPU (the reference's
 dispatcher starts its own workers too, misopy/miso.py:165-187, 205-214) -- unless it is already
 running under a launcher (WORLD_SIZE set).  Rank 0 prints ONE compact JSON line (< 4 KB: the driver keeps the tail of
-stdout) as the LAST line of stdout and writes the full record -- every note, model detail and per-row roofline -- to
-gpurun_out/bench_full.json (`--full-out`).  The global event list
+stdout) as the LAST line of stdout; with `--full`, or wherever `--full-out` names, it also writes the full record -- every
+note, model detail and per-row roofline -- as JSON (`--full` alone: bench_out/bench_full.json).  The global event list
 (N x --events events) is split into N contiguous shards balanced by cost (sum of
 chains x iterations x reads), every event keeps its global id, there is no collective on the data
 path; ranks only meet in a gloo barrier and a max-over-ranks of the elapsed time.
 
-The line carries, besides the contract's keys:
+With `--full` the line carries, besides the contract's keys (a plain run's `roofline` is null):
   roofline            the dominant kernel against the bound that applies to it: VALU issue (VALU
                       instructions per chain-iteration and their issue cycles from the committed
                       rocprofv3 passes of this workload, profiles/valu_model.json -- a MODEL priced with
@@ -659,6 +664,8 @@ def compact_line(full):
                        "algorithmic_GBs": r.get("algorithmic_GBs"), "bytes_frac_8d": r.get("bytes_frac_8d"),
                        "profile_kernel_ms": r.get("profile_kernel_ms"),
                        "frac_source": None if r.get("frac") is None else "model: profiles/valu_model.json x this run's kernel time"}
+    if full["roofline"] is None:   # a plain run: no roofline measured
+        out["roofline"] = None
     b = full.get("cpu_baseline")
     out["cpu_baseline"] = None if b is None else {
         "value": b["value"], "unit": b["unit"], "cores": b["cores"], "kind": b["kind"], "value_1core": b["value_1core"],
@@ -707,18 +714,25 @@ def main():
     ap.add_argument("--collapsed", type=int, default=0, choices=[0, 1, 2],
                     help="single-end, opt-in: the collapsed Gibbs step (miso_batch_set_collapsed): 1 two-isoform events, 2 all")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the reference's CPU baseline and |delta psi| test, the roofline (one more "
+                         "launch with the clock probe), rows f2 / f3, the matrix of other shapes, and the full record")
     ap.add_argument("--cpu-events", type=int, default=150,
-                    help="reference events per host process (~12 s of CPU work per core at the default shape)")
-    ap.add_argument("--dpsi-events", type=int, default=128, help="events of the |delta psi| tolerance study")
-    ap.add_argument("--dpsi-seeds", type=int, default=16, help="reference seeds per event of that study")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="no reference runs at all (no cpu_baseline, no delta_psi)")
-    ap.add_argument("--no-matrix", action="store_true", help="skip the other shapes (hg19-like, K=5, K=10, defaults, paired-end)")
-    ap.add_argument("--matrix-only", default="", help="comma-separated row ids of the matrix to run (default: all)")
+                    help="--full: reference events per host process (~12 s of CPU work per core at the default shape)")
+    ap.add_argument("--dpsi-events", type=int, default=128, help="--full: events of the |delta psi| tolerance study")
+    ap.add_argument("--dpsi-seeds", type=int, default=16, help="--full: reference seeds per event of that study")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without reference runs (no cpu_baseline, no delta_psi)")
+    ap.add_argument("--no-matrix", action="store_true",
+                    help="--full without the other shapes (hg19-like, K=5, K=10, defaults, paired-end)")
+    ap.add_argument("--matrix-only", default="", help="--full: comma-separated row ids of the matrix to run (default: all)")
     ap.add_argument("--matrix-events", type=int, default=40000)
-    ap.add_argument("--no-streams", action="store_true", help="skip the device-side summaries / Bayes factors (rows f2, f3)")
+    ap.add_argument("--no-streams", action="store_true",
+                    help="--full without the device-side summaries / Bayes factors (rows f2, f3)")
     ap.add_argument("--host-match", action="store_true",
                     help="compute the read x isoform compatibility on the host instead of the GPU (row f1)")
-    ap.add_argument("--full-out", default="", help="where the full record goes (default gpurun_out/bench_full.json)")
+    ap.add_argument("--full-out", default="",
+                    help="write the full record here, with or without --full (--full alone: bench_out/bench_full.json)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last one computed for a fixed, seeded sample of the events "
                          "(samples, log scores, read assignments, accept counts) as DIR/<name>.npy, float64, < 64 MB")
@@ -751,9 +765,9 @@ def main():
 
     sh = shape_of(a, K=tuple(a.K_range) if a.K_range else a.K)
     default_shape = not a.K_range and not a.paired and a.reads_dist == "fixed"
-    want_matrix = world == 1 and default_shape and not a.no_matrix and not a.stub
+    want_matrix = a.full and world == 1 and default_shape and not a.no_matrix and not a.stub
     studies = cpu_wall = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.stub:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.stub:
         wanted = {}
         if default_shape:
             timed = [(e, 42 + e) for e in range(a.cpu_events * usable_cores())]
@@ -829,10 +843,11 @@ def main():
     rc = 0
     if rank == 0:
         avg_ms = sum(kernel_ms) / len(kernel_ms)
+        roof = None
         if a.stub:
             roof = {"bound": "valu", "achieved": None, "peak": VALU_PEAK_GCYC, "unit": "Gcycle/s", "frac": None,
                     "traffic": None}
-        else:
+        elif a.full:
             roof = roofline_for(batch, avg_ms, workload_key(n_local, sh) + ("|collapsed" if a.collapsed else ""), sh,
                                 measure_clock(batch, a.seed, first, avg_ms))
         cpu = delta = None
@@ -844,7 +859,7 @@ def main():
                 if delta.get("confirmed_fail"):
                     rc = 3
         streams = {}
-        if not a.stub and not a.no_streams and world == 1:
+        if a.full and not a.stub and not a.no_streams and world == 1:
             streams = stream_rows(batch, n_local, sh, first, a.seed, local_rank)
         kind = "paired-end" if a.paired else "skipped-exon single-end"
         rd = "hg19-like read counts (20..1e5)" if a.reads_dist == "hg19" else "%d reads" % a.reads
@@ -893,14 +908,15 @@ def main():
             out["matrix"] = run_matrix(a, local_rank, studies, sh)
             if any((r.get("delta_psi") or {}).get("confirmed_fail") for r in out["matrix"]):
                 rc = 3
-        full_path = a.full_out or os.path.join(ROOT, "gpurun_out", "bench_full.json")
-        try:
-            os.makedirs(os.path.dirname(full_path), exist_ok=True)
-            with open(full_path, "w") as f:
-                json.dump(out, f, indent=1)
-            out["full_record"] = os.path.relpath(full_path, ROOT)
-        except OSError as err:
-            print("bench.py: full record not written (%s)" % err, file=sys.stderr, flush=True)
+        full_path = a.full_out or (os.path.join(ROOT, "bench_out", "bench_full.json") if a.full else "")
+        if full_path:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
+                with open(full_path, "w") as f:
+                    json.dump(out, f, indent=1)
+                out["full_record"] = os.path.relpath(full_path, ROOT)
+            except OSError as err:
+                print("bench.py: full record not written (%s)" % err, file=sys.stderr, flush=True)
         sys.stderr.flush()
         print(json.dumps(compact_line(out), separators=(",", ":")), flush=True)   # the LAST line of stdout
     if dist is not None:

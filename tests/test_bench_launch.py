@@ -208,3 +208,38 @@ def test_dump_outputs_are_the_timed_launch_s_results(tmp_path):
         assert np.array_equal(a["samples"][j], r.samples) and np.array_equal(a["loglik"][j], r.loglik)
         assert np.array_equal(a["assignment"][off[j]:off[j + 1]], r.assignment)
         assert a["accepted_rejected"][j].tolist() == [r.rundata.noAccepted, r.rundata.noRejected]
+
+
+def test_compact_line_of_a_plain_run():
+    """A plain run (no --full) measures no roofline, no CPU baseline, no |delta psi| and no matrix: the line says null
+    for each and keeps the contract's keys."""
+    sys.path.insert(0, ROOT)
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r03_bench_default.json")))
+    full.update(roofline=None, cpu_baseline=None, delta_psi=None, summary_ms=None, compare_ms=None, cpu_reference_wall_s=None)
+    full.pop("matrix")
+    d = json.loads(json.dumps(bench.compact_line(full), separators=(",", ":")))
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["delta_psi"] is None
+    assert "matrix" not in d and "summary_ms" not in d and "full_record" not in d
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert d[k] == full[k]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """Without --full the run builds, warms up, times and prints: no roofline launch, no rows f2 / f3, no full record.
+    With --full (reference runs and matrix left out here) the roofline and rows f2 / f3 are back and the record is written."""
+    args = ["--events", "300", "--reads", "100", "--iters", "300", "--burn", "100", "--steps", "2", "--warmup", "1"]
+    lines = []
+    for extra in ([], ["--full", "--no-cpu-baseline", "--no-matrix", "--full-out", str(tmp_path / "bench_full.json")]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra, capture_output=True, text=True,
+                             timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout + out.stderr
+        lines.append(json.loads(out.stdout.rstrip().splitlines()[-1]))
+    plain, full = lines
+    assert plain["steps"] == full["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["delta_psi"] is None
+    assert "summary_ms" not in plain and "matrix" not in plain and "full_record" not in plain
+    assert full["roofline"]["bound"] == "valu" and full["roofline"]["kernel_ms"] > 0
+    assert full["summary_ms"] > 0 and full["compare_ms"] > 0 and full["cpu_baseline"] is None and "matrix" not in full
+    assert json.load(open(os.path.join(ROOT, full["full_record"])))["value"] == full["value"]
