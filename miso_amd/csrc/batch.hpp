@@ -5,9 +5,8 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
-
-#include <functional>
 
 #include "device.hpp"
 #include "host.hpp"
@@ -20,6 +19,31 @@ miso_batch *batch_new(const miso_params_t &p);
 int choose_lanes_per_chain(long chains, int max_quads, int wave_slots, int max_cpw);
 void selftest_detmath(const double *x, int n, double *e, double *l, double *s, double *q);
 void selftest_philox(const uint32_t *in6, int n, uint32_t *out4);
+
+// A device table and what it was last filled from: its host contents, or the key of the plan it was built for.  reset()
+// frees the allocation and forgets both, so that neither outlives it (the next upload may be to another device).
+template <class T> struct DevTable {
+  T *d = nullptr;
+  size_t cap = 0;                // elements allocated
+  std::vector<T> host;           // what d holds (runtime.hip put)
+  long key = -1;                 // the plan it was built for, -1 = none
+  DevTable() = default;
+  DevTable(const DevTable &) = delete;
+  DevTable &operator=(const DevTable &) = delete;
+  DevTable(DevTable &&o) noexcept : d(o.d), cap(o.cap), host(std::move(o.host)), key(o.key) { o.d = nullptr; o.cap = 0; o.key = -1; }
+  void reset() {
+    if (d) (void) hipFree(d);
+    d = nullptr; cap = 0; host.clear(); key = -1;
+  }
+};
+// chains on several workgroups (coop.hpp): which chain every workgroup works on, and the scratch they exchange through
+struct CoopTable {
+  DevTable<int32_t> tab;         // four words per workgroup
+  DevTable<uint32_t> mem;        // COOP_WORDS per chain on more than one workgroup
+  int chains = 0;                // chains on more than one workgroup
+  void reset() { tab.reset(); mem.reset(); chains = 0; }
+};
+struct GrpShape { int qs = 0, ts = 0; };   // sampler_grp's slice: class thresholds (single-end), score table (paired-end)
 }  // namespace miso
 
 struct miso_batch {
@@ -47,9 +71,8 @@ struct miso_batch {
   // rounds after the first open (KernelArgs::round_tab)
   int round_iters = 0, round_burn = 0;
   std::vector<int> round_starts;
-  miso::GrpSeg *d_grp_segs = nullptr;     // sampler_grp_all's segment table on the device (KernelArgs::grp_segs), h_grp_segs its host copy
-  std::vector<miso::GrpSeg> h_grp_segs;
-  int32_t *d_round_tab = nullptr;   // ... on the device (KernelArgs::round_tab)
+  miso::DevTable<miso::GrpSeg> grp_segs;   // sampler_grp_all's segment table (KernelArgs::grp_segs)
+  miso::DevTable<int32_t> round_tab;       // ... on the device (KernelArgs::round_tab)
   std::vector<char> went_on;      // per event: it ran a further round in the last launch's converge_rounds
   bool event_went_on(int i) const { return i < static_cast<int>(went_on.size()) && went_on[i] != 0; }
   int rounds = 1;                 // rounds the last launch took (1 = the events' own schedule sufficed)
@@ -77,16 +100,12 @@ struct miso_batch {
   std::vector<int32_t> h_slots;   // the same list on the host
   bool k2_general = false;        // paired-end, tables too wide for the two-isoform kernel's LDS: K = 2 events take sampler_grp
   bool use_delta = true;          // paired-end: MODE 2 events first in the list (fixed at upload)
-  double *d_logfact = nullptr;    // collapsed: log factorials up to the largest two-isoform event's drawing reads
-  int logfact_n = 0;
+  miso::DevTable<double> logfact; // collapsed: log factorials up to the largest event's drawing reads
   int collapsed_level = 0;        // 1: two-isoform events; 2: also the events with more isoforms (sampler_lane_k)
   bool collapsed = false;         // single-end two-isoform events: the collapsed Gibbs step (kernels_lane.hip); miso_batch_set_collapsed
   miso::LanePlan k2_plan;         // sampler_k2_multi: the runs of equal lanes per chain (runtime.hip), valid for k2_plan_key
   long k2_plan_key = -1;
-  struct K2Coop {                 // a plan's chains on several workgroups (coop.hpp): table, scratch
-    int32_t *d_tab = nullptr; uint32_t *d_mem = nullptr; int chains = 0; long key = -1;
-  };
-  K2Coop k2_coop_se, k2w_coop;
+  miso::CoopTable k2_coop_se, k2w_coop;   // the two plans' chains on several workgroups (key: the plan's wide run)
   miso::LanePlan k2w_plan;        // the same for the paired-end MODE 2 events (sampler_k2_multi<2, 4>)
   long k2w_plan_key = -1;
   int n_k2 = 0, n_gen = 0;
@@ -104,17 +123,12 @@ struct miso_batch {
     int force_G = 0;              // paired-end size bucket: at least this many lanes per chain (events several times the class's mean size)
     bool wide = false;            // paired-end size bucket: one chain per workgroup (sampler_grp<64, true, KC, true>)
     bool wave64 = false;          // paired-end size bucket: one chain per wavefront (sampler_grp<64, true, KC>)
-    // wide runs: which chain every workgroup works on, alone or as one of several (coop.hpp; runtime.hip launch_grp)
-    std::vector<int32_t> coop_tab;
-    int32_t *d_coop_tab = nullptr;
-    uint32_t *d_coop_mem = nullptr;
-    int coop_chains = 0;          // chains on more than one workgroup
+    // wide runs: which chain every workgroup works on, alone or as one of several (coop.hpp; runtime.hip wide_setup)
+    miso::CoopTable coop;
     int tuned_G = 0;              // lanes per chain picked by the first launch's trial runs
     int tuned_flat = -1;          // sampler_flat (1) or sampler_grp (0) by the first launch's trial runs, -1 = not tried
     // sampler_flat: which chains every wavefront owns (runtime.hip flat_waves; two words per wavefront)
-    std::vector<int32_t> wave_tab;
-    int32_t *d_wave_tab = nullptr;
-    long wave_key = -1;
+    miso::DevTable<int32_t> wave_tab;
     int wave_nc = 0;              // most chains of any wavefront = slices per wavefront in LDS
     int wave_wide = 0;            // chains that own a whole workgroup
     bool wave_packed = false;     // wavefronts packed by work units (events of very different sizes)
@@ -136,14 +150,47 @@ struct miso_batch {
   std::vector<std::vector<uint16_t>> kept_frags;   // paired-end: N x K fragment indices
   void resolve_pending();        // runs match_kernel for all pending events, packs them
   int lanes_per_chain = 0;        // G of the last sampler_k2 launch (0 = none)
-  std::string last_kernels;       // names of the kernels of the last launch, comma separated
-  std::vector<miso_kernel_stat_t> kernel_stats;   // miso_batch_launch_stats, filled on demand by stats_builder
+  std::string last_kernels;       // names of the kernels the last launch started, in launch order, comma separated
   // sampler_k2_multi<0, 8>, one round: the launch's wavefronts paired by estimated duration across the runs (runtime.hip)
-  std::vector<int32_t> k2_pair_tab;
-  int32_t *d_k2_pair_tab = nullptr;
+  miso::DevTable<int32_t> k2_pair_tab;
   int k2_pair_wide_blocks = 0, k2_pair_grid = 0;
-  std::vector<char> run_in_multi;                 // gen_runs launched as a segment of sampler_grp_multi (1) or sampler_grp_all (2) (last launch)
-  std::function<void()> stats_builder;            // set by launch(): the walk over events and wavefronts is not part of a launch
+  // What launch() decided, kept until the next launch: the launches follow it, launch_stats() reads it (runtime.hip)
+  struct LaunchPlan {
+    bool sampled = false;         // the kernels below ran (not MARGINAL / CLASSES, not adopted samples)
+    // this launch's sizes and switches (plan_sizes)
+    size_t lds_max = 0;           // a workgroup's LDS budget
+    size_t k2_fp = 0, k2_tab = 0, k2w_fp = 0, k2w_tab = 0, fp_plain = 0;
+    bool dense_env = true;
+    int il2 = 0;
+    long total_chains = 0;
+    size_t n_kernels = 0;
+    bool tune_runs = false;
+    int coop_max = 1;
+    // the two-isoform part (plan_k2)
+    int k2_G = 0, k2w_G = 0;      // sampler_k2's lanes per chain: MODE 0 / 1, MODE 2
+    bool k2_pair = false;         // single-end sampler_k2<G, 0, 8>
+    int k2_mix = 0, k2_mix_blocks = 0;                 // sampler_k2_mix: events of the wide part, its workgroups
+    bool k2_multi = false, k2w_multi = false, k2_narrow = false;
+    size_t k2w_multi_lds = 0;
+    bool lane_route = false, lane_ilp = false;         // collapsed: sampler_lane, sampler_lane_ilp or sampler_k2c<lane_G>
+    int lane_G = 1;
+    // the general runs, one per gen_runs entry (plan_runs, group_runs)
+    struct Run {
+      bool lane = false;          // sampler_lane_k
+      int flat_nc = 0, flat_nc_max = 0;   // sampler_flat's chains per wavefront (0: not sampler_flat)
+      int flat_ks = 0;            // ... its compile-time isoform count (0: the layout at run time)
+      bool flat_uni = false;      // ... every event of the run has flat_ks isoforms
+      int G = 64;                 // sampler_grp's lanes per chain
+      miso::GrpShape sh;
+      int group = 0;              // launched as a segment of sampler_grp_multi (1) or sampler_grp_all (2)
+      bool merge_next = false;    // one launch with the next run
+    };
+    std::vector<Run> runs;
+    bool lane_gen = false;        // some run takes sampler_lane_k
+    bool grp_all = false;         // every run in one sampler_grp_all
+    std::vector<std::pair<size_t, size_t>> multi;      // runs [r0, r1) of a class in one sampler_grp_multi
+  } plan;
+  size_t kernel_no = 0;           // kernels of the launch so far (stream_for_next)
   int wave_slots = 2048;          // resident sampler_k2 wavefronts on the device
   std::vector<miso::DevEvent> h_events;
   std::vector<unsigned char> h_out;
@@ -172,4 +219,44 @@ struct miso_batch {
   void summarize(double confidence_level, bool as_text = false);
   void adopt_samples(int n, const int *K, int S, const double *const *samples, int dev);
   void compare(miso_batch &other, double smoothing);
+  std::vector<miso_kernel_stat_t> launch_stats() const;   // miso_batch_launch_stats: one record per two-isoform part and per run
+
+  // the parts of launch() (runtime.hip)
+  void plan_sizes();
+  void plan_k2(const miso::KernelArgs &a);
+  void k2_pair_table(const std::vector<int> &nd, const miso::LaneCost &cost);
+  void plan_runs(const miso::KernelArgs &a);
+  void plan_flat(size_t ri);
+  void plan_grp(size_t ri, const miso::KernelArgs &a);
+  void group_runs();
+  void launch_planned(const miso::KernelArgs &a);
+  template <class F> int fastest(const miso::KernelArgs &a, const std::vector<int> &cand, F &&trial);
+  int slots_for(long chains) const;
+  hipStream_t stream_for_next();
+  void note_kernel(const std::string &name) { last_kernels += (last_kernels.empty() ? "" : ",") + name; }
+  std::string k2_part_name(bool wpart) const;
+  std::string run_name(size_t ri) const;
+  int fp_rows(const GenRun &run) const;
+  size_t fp_bytes_of(const GenRun &run) const;
+  miso::GrpShape grp_shape(const GenRun &run) const;
+  bool grp_fits(const GenRun &run, const miso::GrpShape &sh, int G) const;
+  GenRun joined_run(size_t r0, size_t r1) const;
+  void launch_k2(miso::KernelArgs ka, int G, hipStream_t st, bool wpart = false);
+  void launch_k2_mix(miso::KernelArgs ka, hipStream_t st);
+  void k2_coop(miso::KernelArgs &ka, const miso::LanePlan &pl, miso::CoopTable &cc, hipStream_t st);
+  void launch_k2_multi(miso::KernelArgs ka, hipStream_t st, bool wpart = false);
+  void launch_lane(miso::KernelArgs ka, hipStream_t st);
+  unsigned wide_setup(GenRun &run, long chains, hipStream_t st);
+  void launch_grp(miso::KernelArgs ka, GenRun &run, const miso::GrpShape &sh, int G, hipStream_t st);
+  void flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, int nc_max_p, long resident_p);
+  void launch_flat(miso::KernelArgs ka, size_t ri, hipStream_t st);
+  void launch_run(const miso::KernelArgs &a, size_t ri);
+  void launch_grp_all(const miso::KernelArgs &a);
+  void launch_grp_multi(const miso::KernelArgs &a, size_t r0, size_t r1);
+  template <class F> void each_coop_table(F &&f) { for (GenRun &r : gen_runs) f(r.coop); f(k2_coop_se); f(k2w_coop); }
+  template <class F> void each_table(F &&f) {   // every device table above (release())
+    f(grp_segs); f(round_tab); f(logfact); f(k2_pair_tab);
+    for (GenRun &r : gen_runs) f(r.wave_tab);
+    each_coop_table(f);
+  }
 };

@@ -834,13 +834,9 @@ int miso_batch_launch_stats(const miso_batch_t *b, miso_kernel_stat_t *stats, in
   return guarded([&] {
     need(b, "batch"); need(n_kernels, "n_kernels");
     if (!b->launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-    if (b->stats_builder) {   // the walk over events and wavefronts happens here, once, not inside every launch
-      miso_batch_t *mb = const_cast<miso_batch_t *>(b);
-      mb->stats_builder();
-      mb->stats_builder = nullptr;
-    }
-    *n_kernels = static_cast<int>(b->kernel_stats.size());
-    for (int i = 0; stats && i < max_kernels && i < *n_kernels; i++) stats[i] = b->kernel_stats[i];
+    const std::vector<miso_kernel_stat_t> ks = b->launch_stats();   // (the walk over events and wavefronts is not part of a launch)
+    *n_kernels = static_cast<int>(ks.size());
+    for (int i = 0; stats && i < max_kernels && i < *n_kernels; i++) stats[i] = ks[i];
   });
 }
 

@@ -126,31 +126,16 @@ void miso_batch::release() {
   if (d_out) (void) hipFree(d_out);
   if (d_fp) (void) hipFree(d_fp);
   if (d_slots) (void) hipFree(d_slots);
-  if (d_logfact) (void) hipFree(d_logfact);
-  if (d_k2_pair_tab) (void) hipFree(d_k2_pair_tab);
   d_slots = nullptr;
   // (the next upload may be to another device: nothing may outlive its allocation as a stale pointer or a cached plan)
-  d_logfact = nullptr; logfact_n = 0;
-  d_k2_pair_tab = nullptr; k2_pair_tab.clear(); k2_pair_grid = k2_pair_wide_blocks = 0;
+  each_table([](auto &t) { t.reset(); });
+  k2_pair_grid = k2_pair_wide_blocks = 0;
   k2_plan_key = k2w_plan_key = -1;
   if (probe_stream) { (void) hipStreamSynchronize(probe_stream); (void) hipStreamDestroy(probe_stream); probe_stream = nullptr; }
   if (d_probe) { (void) hipFree(d_probe); d_probe = nullptr; }
-  if (d_round_tab) { (void) hipFree(d_round_tab); d_round_tab = nullptr; }
-  if (d_grp_segs) { (void) hipFree(d_grp_segs); d_grp_segs = nullptr; }
   probe_armed = false;
   if (ev0) (void) hipEventDestroy(ev0);
   if (ev1) (void) hipEventDestroy(ev1);
-  for (GenRun &run : gen_runs) {
-    if (run.d_wave_tab) (void) hipFree(run.d_wave_tab);
-    if (run.d_coop_tab) (void) hipFree(run.d_coop_tab);
-    if (run.d_coop_mem) (void) hipFree(run.d_coop_mem);
-    run.d_wave_tab = nullptr; run.d_coop_tab = nullptr; run.d_coop_mem = nullptr; run.wave_key = -1;
-  }
-  for (K2Coop *cc : {&k2_coop_se, &k2w_coop}) {
-    if (cc->d_tab) (void) hipFree(cc->d_tab);
-    if (cc->d_mem) (void) hipFree(cc->d_mem);
-    *cc = K2Coop{};
-  }
   for (hipStream_t st : aux_streams) (void) hipStreamDestroy(st);
   for (hipEvent_t e : aux_done) (void) hipEventDestroy(e);
   aux_streams.clear(); aux_done.clear();
@@ -519,7 +504,7 @@ void miso_batch::upload(int dev) {
     const int kc = kc_of(e.K), bk = bucket[gen[j]];
     if (gen_runs.empty() || gen_runs.back().kc != kc || (gen_runs.back().wide ? 3 : (gen_runs.back().wave64 ? 2 : (gen_runs.back().force_G ? 1 : (gen_runs.back().small ? -1 : 0)))) != bk) {
       GenRun r; r.first = static_cast<int>(j); r.kc = kc; r.wide = bk == 3; r.wave64 = bk == 2; r.force_G = bk == 1 ? 32 : (bk == 2 ? 64 : 0); r.small = bk == -1;
-      gen_runs.push_back(r);
+      gen_runs.push_back(std::move(r));
     }
     GenRun &r = gen_runs.back();
     r.count++;
@@ -544,6 +529,156 @@ void miso_batch::upload(int dev) {
   pool_cleared = false; launched_once = false;
 }
 
+// ---- the sampler kernels' host stubs, picked by their template arguments ----
+// Only the instantiations the kernel units make (kernels_*.hip): a pointer to any other links into the library and fails
+// when it is loaded.
+template <class K> static const void *fn(K *k) { return reinterpret_cast<const void *>(k); }
+template <int MODE, int WPB> static const void *k2_kernel(int G) {
+  switch (G) {
+  case 1: return fn(&sampler_k2<1, MODE, WPB>);
+  case 2: return fn(&sampler_k2<2, MODE, WPB>);
+  case 3: return fn(&sampler_k2<3, MODE, WPB>);
+  case 4: return fn(&sampler_k2<4, MODE, WPB>);
+  case 5: return fn(&sampler_k2<5, MODE, WPB>);
+  case 6: return fn(&sampler_k2<6, MODE, WPB>);
+  case 7: return fn(&sampler_k2<7, MODE, WPB>);
+  case 8: return fn(&sampler_k2<8, MODE, WPB>);
+  case 9: return fn(&sampler_k2<9, MODE, WPB>);
+  case 10: return fn(&sampler_k2<10, MODE, WPB>);
+  case 12: return fn(&sampler_k2<12, MODE, WPB>);
+  case 16: return fn(&sampler_k2<16, MODE, WPB>);
+  case 21: return fn(&sampler_k2<21, MODE, WPB>);
+  case 32: return fn(&sampler_k2<32, MODE, WPB>);
+  case 64: return fn(&sampler_k2<64, MODE, WPB>);
+  default: MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
+  }
+}
+static const void *k2_mix_kernel(int G) {   // sampler_k2_mix<G + 1, G>
+  switch (G) {
+  case 1: return fn(&sampler_k2_mix<2, 1>);
+  case 2: return fn(&sampler_k2_mix<3, 2>);
+  case 3: return fn(&sampler_k2_mix<4, 3>);
+  case 4: return fn(&sampler_k2_mix<5, 4>);
+  case 5: return fn(&sampler_k2_mix<6, 5>);
+  case 6: return fn(&sampler_k2_mix<7, 6>);
+  default: return fn(&sampler_k2_mix<8, 7>);
+  }
+}
+static const void *k2_multi_kernel(int mode, int wpb, bool narrow) {
+  if (mode == 2) return wpb == 8 ? fn(&sampler_k2_multi<2, 8>) : fn(&sampler_k2_multi<2, 4>);
+  if (mode == 1) return fn(&sampler_k2_multi<1, 4>);
+  if (wpb == 8) return fn(&sampler_k2_multi<0, 8>);
+  if (wpb == 4) return narrow ? fn(&sampler_k2_multi<0, 4, true>) : fn(&sampler_k2_multi<0, 4>);
+  return fn(&sampler_k2_multi<0, 1>);
+}
+static const void *lane_kernel(int G, bool ilp) {   // the collapsed step: one lane per chain, or G (sampler_k2c)
+  switch (G) {
+  case 1: return ilp ? fn(&sampler_lane_ilp) : fn(&sampler_lane);
+  case 2: return fn(&sampler_k2c<2>);
+  case 4: return fn(&sampler_k2c<4>);
+  default: return fn(&sampler_k2c<8>);
+  }
+}
+template <int G, bool PE, bool WIDE = false> static const void *grp_kc(int kc) {
+  switch (kc) {
+  case 4: return fn(&sampler_grp<G, PE, 4, WIDE>);
+  case 8: return fn(&sampler_grp<G, PE, 8, WIDE>);
+  case 12: return fn(&sampler_grp<G, PE, 12, WIDE>);
+  case 16: return fn(&sampler_grp<G, PE, 16, WIDE>);
+  default: return fn(&sampler_grp<G, PE, 32, WIDE>);
+  }
+}
+static const void *grp_kernel(int G, bool pe, int kc) {   // G < 64
+  switch (G) {
+  case 2: return pe ? grp_kc<2, true>(kc) : grp_kc<2, false>(kc);
+  case 4: return pe ? grp_kc<4, true>(kc) : grp_kc<4, false>(kc);
+  case 8: return pe ? grp_kc<8, true>(kc) : grp_kc<8, false>(kc);
+  case 16: return pe ? grp_kc<16, true>(kc) : grp_kc<16, false>(kc);
+  case 32: return pe ? grp_kc<32, true>(kc) : grp_kc<32, false>(kc);
+  default: MISO_FAIL(MISO_EINVAL, "MISO_GENERAL_LANES must be 2, 4, 8, 16, 32 or 64");
+  }
+}
+static const void *grp_multi_kernel(int kc) {
+  switch (kc) {
+  case 4: return fn(&sampler_grp_multi<4>);
+  case 8: return fn(&sampler_grp_multi<8>);
+  case 12: return fn(&sampler_grp_multi<12>);
+  case 16: return fn(&sampler_grp_multi<16>);
+  default: return fn(&sampler_grp_multi<32>);
+  }
+}
+template <int KC, int KS> static const void *flat_ks_kernel(bool uni) {
+  return uni ? fn(&sampler_flat<KC, KS, true>) : fn(&sampler_flat<KC, KS, false>);
+}
+// ks: the run's largest isoform count at compile time (kc - 3 ... kc, 17 ... 20 for kc = 32), 0 = the layout at run time
+static const void *flat_kernel(int kc, int ks, bool uni) {
+  switch (kc) {
+  case 4:
+    return ks == 3 ? flat_ks_kernel<4, 3>(uni) : ks == 4 ? flat_ks_kernel<4, 4>(uni) : fn(&sampler_flat<4, 0, false>);
+  case 8:
+    return ks == 5 ? flat_ks_kernel<8, 5>(uni) : ks == 6 ? flat_ks_kernel<8, 6>(uni) : ks == 7 ? flat_ks_kernel<8, 7>(uni)
+         : ks == 8 ? flat_ks_kernel<8, 8>(uni) : fn(&sampler_flat<8, 0, false>);
+  case 12:
+    return ks == 9 ? flat_ks_kernel<12, 9>(uni) : ks == 10 ? flat_ks_kernel<12, 10>(uni) : ks == 11 ? flat_ks_kernel<12, 11>(uni)
+         : ks == 12 ? flat_ks_kernel<12, 12>(uni) : fn(&sampler_flat<12, 0, false>);
+  case 16:
+    return ks == 13 ? flat_ks_kernel<16, 13>(uni) : ks == 14 ? flat_ks_kernel<16, 14>(uni) : ks == 15 ? flat_ks_kernel<16, 15>(uni)
+         : ks == 16 ? flat_ks_kernel<16, 16>(uni) : fn(&sampler_flat<16, 0, false>);
+  default:
+    return ks == 17 ? flat_ks_kernel<32, 17>(uni) : ks == 18 ? flat_ks_kernel<32, 18>(uni) : ks == 19 ? flat_ks_kernel<32, 19>(uni)
+         : ks == 20 ? flat_ks_kernel<32, 20>(uni) : fn(&sampler_flat<32, 0, false>);
+  }
+}
+
+// Every sampler launch: the dynamic LDS the kernel may use, the launch (what the triple-chevron stub calls too), its check.
+static void launch_kernel(const void *f, unsigned grid, unsigned block, size_t lds, hipStream_t st, const KernelArgs &ka) {
+  if (lds) HIP_OK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  void *args[] = {const_cast<KernelArgs *>(&ka)};
+  (void) hipLaunchKernel(f, dim3(grid), dim3(block), args, lds, st);
+  HIP_OK(hipGetLastError());
+}
+
+// `t` holds `v` from now on, in an allocation of at least `min_n` elements; copied only when it holds something else
+template <class T> static void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n = 1) {
+  const size_t n = std::max(v.size(), min_n);
+  if (t.d && n <= t.cap && v.size() == t.host.size() && (v.empty() || std::memcmp(v.data(), t.host.data(), v.size() * sizeof(T)) == 0)) return;
+  if (!t.d || n > t.cap) {
+    if (t.d) HIP_OK(hipFree(t.d));
+    t.d = nullptr; t.cap = 0;
+    HIP_OK(hipMalloc(reinterpret_cast<void **>(&t.d), n * sizeof(T)));
+    t.cap = n;
+  }
+  if (!v.empty()) HIP_OK(hipMemcpy(t.d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  t.host = v;
+}
+
+// ---- names (last_kernels, launch_stats) ----
+static std::string k2_name(int G, bool paired, bool wpart, bool pair) {
+  return "sampler_k2<" + std::to_string(G) + (paired ? (wpart ? ", 2, 4>" : ", 1, 4>") : (pair ? ", 0, 8>" : ", 0, 4>"));
+}
+std::string miso_batch::k2_part_name(bool wpart) const {   // the kernel of the MODE 2 part (wpart) or of the other two-isoform events
+  const LaunchPlan &q = plan;
+  if (wpart) return q.k2w_multi ? "sampler_k2_multi<2, " + std::to_string(k2w_plan.wpb) + ">" : k2_name(q.k2w_G, p.paired, true, q.k2_pair);
+  if (q.lane_route) return q.lane_G == 1 ? std::string(q.lane_ilp ? "sampler_lane_ilp" : "sampler_lane") : "sampler_k2c<" + std::to_string(q.lane_G) + ">";
+  if (q.k2_multi)
+    return "sampler_k2_multi<" + std::string(p.paired ? "1, " : "0, ") + std::to_string(k2_plan.wpb) + (q.k2_narrow ? ", true>" : ">");
+  if (q.k2_mix > 0) return "sampler_k2_mix<" + std::to_string(q.k2_G + 1) + ", " + std::to_string(q.k2_G) + ">";
+  return k2_name(q.k2_G, p.paired, false, q.k2_pair);
+}
+std::string miso_batch::run_name(size_t ri) const {   // the kernel general run ri is part of
+  const GenRun &run = gen_runs[ri];
+  const LaunchPlan::Run &r = plan.runs[ri];
+  const std::string kc = std::to_string(run.kc), pe = p.paired ? "true" : "false";
+  if (r.lane) return "sampler_lane_k";
+  if (r.group == 2) return "sampler_grp_all";
+  if (r.group == 1) return "sampler_grp_multi<" + kc + ">";
+  if (run.wide) return "sampler_grp<64, true, " + kc + ", true>";
+  if (r.flat_nc > 0) return "sampler_flat<" + kc + ", " + std::to_string(r.flat_ks) + (r.flat_uni ? ", true>" : ">");
+  if (r.G == 64 && !(run.wave64 && p.paired && run.dense)) return std::string(run.kc > 64 ? "sampler_big<" : "sampler_wave<") + pe + ">";
+  return "sampler_grp<" + std::to_string(r.G) + ", " + pe + ", " + kc + ">";
+}
+
+// ---- launch(): plan the two-isoform part, plan the general runs, group them into launches, launch ----
 void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   if (!uploaded) MISO_FAIL(MISO_EINVAL, "batch not uploaded");
   HIP_OK(hipSetDevice(device));
@@ -557,11 +692,10 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   a.wide_dedup = (std::getenv("MISO_K2_WIDE_DEDUP") && std::atoi(std::getenv("MISO_K2_WIDE_DEDUP")) == 0) ? 0 : 1;   // kernels_k2.inl: a workgroup-wide chain's Metropolis-Hastings step on four of its eight wavefronts
   a.round_tab = nullptr;
   if (!round_starts.empty()) {   // a later round of stop = CONVERGENT_MEAN (converge_rounds): where the rounds after the first open
-    int32_t tab[MISO_MAX_ROUNDS];
+    std::vector<int32_t> tab(MISO_MAX_ROUNDS);
     for (int i = 0; i < MISO_MAX_ROUNDS; i++) tab[i] = i < static_cast<int>(round_starts.size()) ? round_starts[i] : -1;
-    if (!d_round_tab) HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_round_tab), sizeof(tab)));
-    HIP_OK(hipMemcpy(d_round_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-    a.round_tab = d_round_tab;
+    put(round_tab, tab);
+    a.round_tab = round_tab.d;
   }
   last_seed = seed; last_first_event_id = first_event_id;
   converged_done = false;
@@ -578,719 +712,162 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   lanes_per_chain = 0;
   last_kernels.clear();
   if (!launched_once) coop_wgs_used = 0;
-
-  // ---- algorithm = MARGINAL / CLASSES (miso.c:272-295, 788-808): Metropolis-Hastings on psi alone, no reads to reassign ----
-  // One chain per lane, every event of the batch in one launch (kernels_marginal.hip); its vectors live in LDS,
-  // [vector][isoform][lane], 64 lanes per workgroup up to 32 isoforms, 32 beyond.
-  if (!p.paired && (p.algorithm == MISO_ALGO_MARGINAL || p.algorithm == MISO_ALGO_CLASSES)) {
+  plan = LaunchPlan{};
+  kernel_no = 0;
+  // algorithm = MARGINAL / CLASSES (miso.c:272-295, 788-808): Metropolis-Hastings on psi alone, no reads to reassign
+  const bool marginal = !p.paired && (p.algorithm == MISO_ALGO_MARGINAL || p.algorithm == MISO_ALGO_CLASSES);
+  if (!marginal) {
+    plan_sizes();
+    plan_k2(a);
+    plan_runs(a);
+    group_runs();
+    plan.sampled = true;
+  }
+  HIP_OK(hipEventRecord(ev0, stream));                  // events bracket the sampler kernels only
+  if (marginal) {
+    // One chain per lane, every event of the batch in one launch (kernels_marginal.hip); its vectors live in LDS,
+    // [vector][isoform][lane], 64 lanes per workgroup up to 32 isoforms, 32 beyond.
     int ks = 2;
     for (const PackedEvent &e : events) ks = std::max(ks, e.K);
     const int lanes = ks <= 32 ? 64 : 32;
     KernelArgs ka = a;
     ka.slot_event = d_slots; ka.n_slots = n; ka.kstride = ks;
     const long chains = static_cast<long>(n) * p.noChains;
-    const size_t lds = marginal_lds_bytes(ks, lanes);
-    stats_builder = nullptr; kernel_stats.clear();
-    HIP_OK(hipEventRecord(ev0, stream));
-    if (chains > 0) {
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_marginal), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL(sampler_marginal, dim3(static_cast<unsigned>((chains + lanes - 1) / lanes)), dim3(lanes), lds, stream, ka);
-      HIP_OK(hipGetLastError());
-    }
-    HIP_OK(hipEventRecord(ev1, stream));
-    start_clock_probe();
+    if (chains > 0) launch_kernel(fn(&sampler_marginal), static_cast<unsigned>((chains + lanes - 1) / lanes), lanes, marginal_lds_bytes(ks, lanes), stream, ka);
     last_kernels = "sampler_marginal";
-    launched = true; launched_once = true; downloaded = false; summarized = false; compared = false;
-    return;
+  } else {
+    launch_planned(a);
   }
+  // kernel i > 0 went to its own stream, forked from the batch's stream: joined back into it
+  for (size_t i = 1; i < kernel_no && i <= aux_streams.size() && std::getenv("MISO_SERIAL_KERNELS") == nullptr; i++) {
+    HIP_OK(hipEventRecord(aux_done[i - 1], aux_streams[i - 1]));
+    HIP_OK(hipStreamWaitEvent(stream, aux_done[i - 1], 0));
+  }
+  HIP_OK(hipEventRecord(ev1, stream));
+  start_clock_probe();
+  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false;
+}
 
-  // ---- two-isoform events: sampler_k2<G> ----
-  const size_t k2_fp = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
-  const size_t k2_tab = p.paired ? 2 * fd.prob.size() * 4 : 0;   // per chain: int32[2 x il]
-  // (only when the batch's wavefronts fit the resident slots once: with several rounds the hardware hands
-  // out workgroups as slots free up, heaviest first, and the 4-wavefront workgroups balance better --
-  // MISO defaults, 6 chains x 40 000 events at one lane per chain: 374 ms paired, 351 ms unpaired)
-  const bool k2_pair_env = !p.paired && !(std::getenv("MISO_K2_PAIR") && std::atoi(std::getenv("MISO_K2_PAIR")) == 0);
-  bool k2_pair = k2_pair_env;
+// The launch's sizes and switches, read once per launch.
+void miso_batch::plan_sizes() {
+  LaunchPlan &q = plan;
+  // a workgroup may use half of the CU's 160 KB of LDS (two workgroups per CU)
+  // MISO_LDS_MAX_KB (experiments): a larger cap lets one workgroup per CU hold more chains per wavefront
+  q.lds_max = (std::getenv("MISO_LDS_MAX_KB") ? std::atoi(std::getenv("MISO_LDS_MAX_KB")) : 80) * 1024;
+  const int il = static_cast<int>(fd.prob.size());
+  q.k2_fp = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
+  q.k2_tab = p.paired ? 2 * fd.prob.size() * 4 : 0;   // per chain: int32[2 x il]
   // paired-end: the first n_k2w slots go to MODE 2 (no drawing read with a non-finite score), the rest to
   // MODE 1; single-end: everything is "the rest".  Both keep the event's score table (2 il int32) per chain in LDS.
   // MODE 2 reads the dense records (device.hpp pe_k2_entries): both tables with 2 il + 2 entries
-  const size_t k2w_fp = p.paired ? align_up(static_cast<size_t>(pe_k2_entries(static_cast<int>(fd.prob.size()))) * 8, 16) : 0;
-  const size_t k2w_tab = p.paired ? static_cast<size_t>(pe_k2_entries(static_cast<int>(fd.prob.size()))) * 4 : 0;
-  auto launch_k2 = [&](KernelArgs ka, int G, hipStream_t st, bool wpart = false, int sub_first = 0, int sub_count = -1) {
-    int first = wpart ? 0 : n_k2w, count = wpart ? n_k2w : n_k2 - n_k2w;
-    if (sub_count >= 0) { first += sub_first; count = sub_count; }   // a part of the list (single-end split, below)
-    const long chains = static_cast<long>(count) * p.noChains;
-    if (chains <= 0) return;
-    ka.slot_event = d_slots + first; ka.n_slots = count;
-    const int cpw = 64 / std::max(G, 1);
-    const long waves = (chains + cpw - 1) / cpw;
-    // single-end: workgroups of 8 wavefronts = one CU's resident slots; the two wavefronts of a SIMD
-    // take a heavy and a light group of chains (sampler_k2's WPB = 8).  MISO_K2_PAIR=0: the 4-wavefront
-    // workgroups in slot order (round-1 behaviour).
-    const bool pair = k2_pair;
-    ka.pair_waves = pair ? 1 : 0;
-    const unsigned grid = static_cast<unsigned>(pair ? (waves + 7) / 8 : (waves + 3) / 4);
-    const size_t k2_lds = (wpart ? k2w_fp : k2_fp) + 4 * static_cast<size_t>(cpw) * (wpart ? k2w_tab : k2_tab);
-    if (k2_lds > 160 * 1024) MISO_FAIL(MISO_UNIMPLEMENTED, "Fragment-length distribution too wide for the two-isoform paired-end kernel");
-#define MISO_K2_LAUNCH(GG)                                                                              \
-  case GG:                                                                                             \
-    if (p.paired && wpart) {                                                                           \
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_k2<GG, 2, 4>),                \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(k2_lds))); \
-      hipLaunchKernelGGL((sampler_k2<GG, 2, 4>), dim3(grid), dim3(256), k2_lds, st, ka);               \
-    } else if (p.paired) {                                                                             \
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_k2<GG, 1, 4>),                \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(k2_lds))); \
-      hipLaunchKernelGGL((sampler_k2<GG, 1, 4>), dim3(grid), dim3(256), k2_lds, st, ka);               \
-    } else if (pair) hipLaunchKernelGGL((sampler_k2<GG, 0, 8>), dim3(grid), dim3(512), 0, st, ka);     \
-    else hipLaunchKernelGGL((sampler_k2<GG, 0, 4>), dim3(grid), dim3(256), 0, st, ka);                 \
-    break;
-    switch (G) {
-      MISO_K2_LAUNCH(1) MISO_K2_LAUNCH(2) MISO_K2_LAUNCH(3) MISO_K2_LAUNCH(4) MISO_K2_LAUNCH(5)
-      MISO_K2_LAUNCH(6) MISO_K2_LAUNCH(7) MISO_K2_LAUNCH(8) MISO_K2_LAUNCH(9) MISO_K2_LAUNCH(10)
-      MISO_K2_LAUNCH(12) MISO_K2_LAUNCH(16) MISO_K2_LAUNCH(21) MISO_K2_LAUNCH(32) MISO_K2_LAUNCH(64)
-    default: MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
-    }
-#undef MISO_K2_LAUNCH
-    HIP_OK(hipGetLastError());
-  };
-
-  // ---- more than two isoforms: sampler_grp<G, PE, KC> per isoform-count class ----
-  // a workgroup may use half of the CU's 160 KB of LDS (two workgroups per CU)
-  // MISO_LDS_MAX_KB (experiments): a larger cap lets one workgroup per CU hold more chains per wavefront
-  const size_t LDS_MAX = (std::getenv("MISO_LDS_MAX_KB") ? std::atoi(std::getenv("MISO_LDS_MAX_KB")) : 80) * 1024;
-  const size_t fp_plain = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
+  q.k2w_fp = p.paired ? align_up(static_cast<size_t>(pe_k2_entries(il)) * 8, 16) : 0;
+  q.k2w_tab = p.paired ? static_cast<size_t>(pe_k2_entries(il)) * 4 : 0;
+  q.fp_plain = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
   // paired-end dense path (pe_dense): byte records, the probability table with its two extra entries, the
   // score table with rows of il + 2; MISO_NO_PE_DENSE=1 (tests, A/B): the quad loops over the plain records
-  const bool dense_env = std::getenv("MISO_NO_PE_DENSE") == nullptr;
-  const int il2 = pe_dense_il2(static_cast<int>(fd.prob.size()));
-  auto fp_rows = [&](const GenRun &run) { return (p.paired && dense_env && run.dense) ? 1 : 0; };
-  auto fp_bytes_of = [&](const GenRun &run) {
-    return fp_rows(run) ? align_up(static_cast<size_t>(il2) * 8, 16) : fp_plain;
-  };
-  struct GrpShape { int qs, ts; };
-  auto grp_shape = [&](const GenRun &run) {
-    const size_t fp_bytes = fp_bytes_of(run);
-    // single-end: per-class thresholds join the slice (class path) when every event has a class
-    // table; MISO_NO_CLASS_PATH=1 (tests): force the direct mask path of sampler_grp
-    const bool no_cls = std::getenv("MISO_NO_CLASS_PATH") != nullptr;
-    int qs = (!p.paired && !no_cls && !run.nocls && run.maxcls > 0) ? run.maxcls : 0;
-    if (qs && 4 * 2 * static_cast<size_t>(grp_slice_bytes(run.kmax, qs, 0)) > LDS_MAX) qs = 0;
-    // paired-end: the per-event score table (K x il int32) joins the slice when >= 4 chains still fit
-    int ts = p.paired ? run.kmax * (fp_rows(run) ? il2 : static_cast<int>(fd.prob.size())) : 0;
-    if (ts && fp_bytes + 4 * 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, ts)) > LDS_MAX) ts = 0;
-    return GrpShape{qs, ts};
-  };
-  auto grp_fits = [&](const GenRun &run, const GrpShape &sh, int G) {
-    const size_t fp_bytes = fp_bytes_of(run);
-    return G >= 2 && G <= 32 && !(G & (G - 1)) &&
-           fp_bytes + 4 * static_cast<size_t>(64 / G) * grp_slice_bytes(run.kmax, sh.qs, sh.ts) <= LDS_MAX;
-  };
-  // Workgroup-wide chains of a run: which chain every workgroup works on (coop.hpp), built once per batch; returns the
-  // number of workgroups.
-  auto wide_setup = [&](GenRun &run, long chains, hipStream_t st) -> unsigned {
-      // Workgroups per chain: what upload() derived from the gene's share of the batch's work (coop_n), at most
-      // COOP_MAX_N, all cooperative workgroups of the batch together at most COOP_MAX_WGS (coop.hpp: they must all be
-      // resident at once).  MISO_NO_COOP=1: one workgroup per chain; MISO_COOP_DRAWS=n: one per n drawing pairs (tests).
-      if (!run.d_coop_tab) {
-        run.coop_tab.clear(); run.coop_chains = 0;
-        const bool coop_on = coop_enabled();
-        const int per_wg = std::getenv("MISO_COOP_DRAWS") ? std::max(256, std::atoi(std::getenv("MISO_COOP_DRAWS"))) : 8192;
-        for (long c = 0; c < chains; c++) {
-          const int ev_i = h_slots[n_k2 + run.first + c / p.noChains];
-          const int nd = events[ev_i].n_draw;
-          int nw = !coop_on ? 1 : (std::getenv("MISO_COOP_DRAWS") ? std::min(COOP_MAX_N, std::max(1, (nd + per_wg - 1) / per_wg)) : coop_n[ev_i]);
-          if (nw > 1 && coop_wgs_used + nw > coop_gen_budget) nw = std::max(1, coop_gen_budget - coop_wgs_used);
-          if (nw > 1) coop_wgs_used += nw;
-          for (int r = 0; r < nw; r++) {
-            run.coop_tab.push_back(static_cast<int32_t>(c)); run.coop_tab.push_back(r); run.coop_tab.push_back(nw);
-            run.coop_tab.push_back(nw > 1 ? run.coop_chains : 0);
-          }
-          if (nw > 1) run.coop_chains++;
-        }
-        if (std::getenv("MISO_TIMING")) {
-          std::fprintf(stderr, "[miso] wide run kc=%d: %ld chains on %zu workgroups (%d on several:", run.kc, chains, run.coop_tab.size() / 4, run.coop_chains);
-          for (size_t i = 0; i < run.coop_tab.size(); i += 4)
-            if (run.coop_tab[i + 1] == 0 && run.coop_tab[i + 2] > 1)
-              std::fprintf(stderr, " %d x %d draws K=%d", run.coop_tab[i + 2], events[h_slots[n_k2 + run.first + run.coop_tab[i] / p.noChains]].n_draw,
-                           events[h_slots[n_k2 + run.first + run.coop_tab[i] / p.noChains]].K);
-          std::fprintf(stderr, ")\n");
-        }
-        HIP_OK(hipMalloc(reinterpret_cast<void **>(&run.d_coop_tab), run.coop_tab.size() * sizeof(int32_t)));
-        HIP_OK(hipMemcpy(run.d_coop_tab, run.coop_tab.data(), run.coop_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_OK(hipMalloc(reinterpret_cast<void **>(&run.d_coop_mem), std::max(1, run.coop_chains) * COOP_WORDS * sizeof(uint32_t)));
-      }
-      HIP_OK(hipMemsetAsync(run.d_coop_mem, 0, std::max(1, run.coop_chains) * COOP_WORDS * sizeof(uint32_t), st));
-      return static_cast<unsigned>(run.coop_tab.size() / 4);
-  };
-  auto launch_grp = [&](KernelArgs ka, GenRun &run, const GrpShape &sh, int G, hipStream_t st) {
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count;
-    ka.kstride = run.kmax; ka.cstride = sh.qs; ka.tstride = sh.ts;
-    const bool wave_kernel = G == 64 && !run.wide && !(run.wave64 && fp_rows(run));   // sampler_wave, not sampler_grp<64, ..>
-    ka.pe_dense = wave_kernel ? 0 : fp_rows(run);
-    ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
-    const size_t fp_bytes = wave_kernel ? fp_plain : fp_bytes_of(run);
-    if (run.wide) {   // one chain per workgroup: four slices (one per wavefront) + the reduction scratch behind them
-      ka.pe_dense = fp_rows(run);
-      if (!ka.pe_dense) MISO_FAIL(MISO_EINTERNAL, "workgroup-wide paired-end chains need the dense records");
-      const size_t lds0 = align_up(fp_bytes + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, sh.ts)), 16);
-      ka.red_off = static_cast<int32_t>(lds0);
-      const size_t lds = lds0 + 96;
-      const unsigned grid = wide_setup(run, chains, st);
-      ka.coop_tab = run.d_coop_tab; ka.coop_mem = run.d_coop_mem;
-#define MISO_GRP_WIDE(KC)                                                                                  \
-  {                                                                                                        \
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_grp<64, true, KC, true>),           \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));        \
-    hipLaunchKernelGGL((sampler_grp<64, true, KC, true>), dim3(grid), dim3(256), lds, st, ka);             \
-  }
-      switch (run.kc) {
-      case 4: MISO_GRP_WIDE(4) break;
-      case 8: MISO_GRP_WIDE(8) break;
-      case 12: MISO_GRP_WIDE(12) break;
-      case 16: MISO_GRP_WIDE(16) break;
-      default: MISO_GRP_WIDE(32) break;
-      }
-#undef MISO_GRP_WIDE
-    } else if (G == 64 && !wave_kernel) {   // a wavefront per chain, dense records (size bucket between 32 lanes and a workgroup)
-      const unsigned grid = static_cast<unsigned>((chains + 3) / 4);
-      const size_t lds = fp_bytes + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, sh.qs, sh.ts));
-#define MISO_GRP_WAVE64(KC)                                                                                \
-  {                                                                                                        \
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_grp<64, true, KC>),                 \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));        \
-    hipLaunchKernelGGL((sampler_grp<64, true, KC>), dim3(grid), dim3(256), lds, st, ka);                   \
-  }
-      switch (run.kc) {
-      case 4: MISO_GRP_WAVE64(4) break;
-      case 8: MISO_GRP_WAVE64(8) break;
-      case 12: MISO_GRP_WAVE64(12) break;
-      case 16: MISO_GRP_WAVE64(16) break;
-      default: MISO_GRP_WAVE64(32) break;
-      }
-#undef MISO_GRP_WAVE64
-    } else if (G == 64 && run.kc > 64) {   // 65 ... MISO_MAX_ISOFORMS isoforms: one wavefront = one workgroup per chain, vectors in LDS (kernels_big.hip)
-      const unsigned grid = static_cast<unsigned>(chains);
-      const size_t lds = fp_bytes + static_cast<size_t>(run.kmax) * (11 * sizeof(double) + 2 * sizeof(int));
-      if (p.paired) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_big<true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        hipLaunchKernelGGL(sampler_big<true>, dim3(grid), dim3(64), lds, st, ka);
-      } else {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_big<false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        hipLaunchKernelGGL(sampler_big<false>, dim3(grid), dim3(64), lds, st, ka);
-      }
-    } else if (G == 64) {
-      const unsigned grid = static_cast<unsigned>((chains + 3) / 4);
-      const size_t lds = fp_bytes + 4 * 64 * sizeof(int);
-      if (p.paired) hipLaunchKernelGGL(sampler_wave<true>, dim3(grid), dim3(256), lds, st, ka);
-      else hipLaunchKernelGGL(sampler_wave<false>, dim3(grid), dim3(256), lds, st, ka);
-    } else {
-      const int cpw = 64 / G;
-      const unsigned grid = static_cast<unsigned>(((chains + cpw - 1) / cpw + 3) / 4);
-      const size_t lds = fp_bytes + 4 * static_cast<size_t>(cpw) * grp_slice_bytes(run.kmax, sh.qs, sh.ts);
-#define MISO_GRP_LAUNCH_K(GG, KC)                                                                          \
-  {                                                                                                        \
-    if (p.paired) {                                                                                        \
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_grp<GG, true, KC>),               \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));      \
-      hipLaunchKernelGGL((sampler_grp<GG, true, KC>), dim3(grid), dim3(256), lds, st, ka);                 \
-    } else {                                                                                               \
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_grp<GG, false, KC>),              \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));      \
-      hipLaunchKernelGGL((sampler_grp<GG, false, KC>), dim3(grid), dim3(256), lds, st, ka);                \
-    }                                                                                                      \
-  }
-#define MISO_GRP_LAUNCH(GG)                                    \
-  case GG:                                                     \
-    switch (run.kc) {                                          \
-    case 4: MISO_GRP_LAUNCH_K(GG, 4) break;                    \
-    case 8: MISO_GRP_LAUNCH_K(GG, 8) break;                    \
-    case 12: MISO_GRP_LAUNCH_K(GG, 12) break;                  \
-    case 16: MISO_GRP_LAUNCH_K(GG, 16) break;                  \
-    default: MISO_GRP_LAUNCH_K(GG, 32) break;                  \
-    }                                                          \
-    break;
-      switch (G) {
-        MISO_GRP_LAUNCH(2) MISO_GRP_LAUNCH(4) MISO_GRP_LAUNCH(8) MISO_GRP_LAUNCH(16) MISO_GRP_LAUNCH(32)
-      default: MISO_FAIL(MISO_EINVAL, "MISO_GENERAL_LANES must be 2, 4, 8, 16, 32 or 64");
-      }
-#undef MISO_GRP_LAUNCH
-#undef MISO_GRP_LAUNCH_K
-    }
-    HIP_OK(hipGetLastError());
-  };
-
+  q.dense_env = std::getenv("MISO_NO_PE_DENSE") == nullptr;
+  q.il2 = pe_dense_il2(il);
+  // A batch with several kernels (two-isoform events + one general kernel per isoform-count class)
+  // runs them CONCURRENTLY, one stream each: every kernel then only has its share of the device to
+  // fill, so the lanes-per-chain rule sees `wave_slots x share` (one after the other, each class of
+  // a whole-gene batch -- a few thousand chains -- would be spread thin over 32 lanes per chain and
+  // still leave the GPU half empty).
+  q.total_chains = static_cast<long>(events.size()) * p.noChains;
+  q.n_kernels = (n_k2 - n_k2w > 0 ? 1 : 0) + (n_k2w > 0 ? 1 : 0) + gen_runs.size();
   // Lanes per chain, measured: the best split depends on how the batch's wavefronts fill the SIMDs
   // (chains, isoforms, reads, LDS per workgroup), so the first launch of a large single-end batch
   // with more than two isoforms times a few iterations of the rule of thumb's choice and of the next
   // larger ones on the batch itself and keeps the fastest (K=5: 58k -> 81k events/s) (the trial launches record nothing: burn-in = their length; what they leave in the
   // output pool is rewritten by the real launch).  MISO_NO_AUTOTUNE=1 keeps the rule of thumb.
   const bool tune = std::getenv("MISO_NO_AUTOTUNE") == nullptr && p.noIterations >= 2000;   // ~400 trial iterations: <= 20 % of a one-shot run
-  auto fastest = [&](const std::vector<int> &cand, auto &&trial) {
-    // per-iteration cost = slope between a short and a longer trial (set-up, launch and code-object
-    // load cancel); ~200 iterations per candidate
-    auto timed = [&](int iters, int g) {
-      KernelArgs t = a;
-      t.M = iters; t.B = iters;
-      float ms = 0;
-      HIP_OK(hipEventRecord(ev0, stream));
-      trial(t, g);
-      HIP_OK(hipEventRecord(ev1, stream));
-      HIP_OK(hipEventSynchronize(ev1));
-      HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-      return ms;
-    };
-    int best = cand[0]; float best_slope = 0;
-    for (size_t i = 0; i < cand.size(); i++) {
-      timed(4, cand[i]);
-      const float t0 = timed(32, cand[i]), t1 = timed(160, cand[i]);
-      const float slope = t1 - t0;
-      if (i == 0 || slope < best_slope) { best = cand[i]; best_slope = slope; }
-    }
-    return best;
-  };
+  q.tune_runs = tune && q.n_kernels <= 1;   // trial launches would time a kernel alone
+  // (workgroup-wide chains may use several workgroups, coop.hpp; MISO_NO_COOP=1: their own only)
+  q.coop_max = coop_enabled() ? COOP_MAX_N : 1;
+}
 
-  // A batch with several kernels (two-isoform events + one general kernel per isoform-count class)
-  // runs them CONCURRENTLY, one stream each: every kernel then only has its share of the device to
-  // fill, so the lanes-per-chain rule sees `wave_slots x share` (one after the other, each class of
-  // a whole-gene batch -- a few thousand chains -- would be spread thin over 32 lanes per chain and
-  // still leave the GPU half empty).
-  const long total_chains = static_cast<long>(n) * p.noChains;
-  const size_t n_kernels = (n_k2 - n_k2w > 0 ? 1 : 0) + (n_k2w > 0 ? 1 : 0) + gen_runs.size();
-  auto slots_for = [&](long chains) {
-    if (n_kernels <= 1 || total_chains <= 0) return wave_slots;
-    return std::max(1, static_cast<int>(static_cast<double>(wave_slots) * chains / total_chains));
+int miso_batch::slots_for(long chains) const {
+  if (plan.n_kernels <= 1 || plan.total_chains <= 0) return wave_slots;
+  return std::max(1, static_cast<int>(static_cast<double>(wave_slots) * chains / plan.total_chains));
+}
+
+// Trial launches: the candidate whose per-iteration cost is lowest -- the slope between a short and a longer trial
+// (set-up, launch and code-object load cancel); ~200 iterations per candidate
+template <class F> int miso_batch::fastest(const KernelArgs &a, const std::vector<int> &cand, F &&trial) {
+  auto timed = [&](int iters, int g) {
+    KernelArgs t = a;
+    t.M = iters; t.B = iters;
+    float ms = 0;
+    HIP_OK(hipEventRecord(ev0, stream));
+    trial(t, g);
+    HIP_OK(hipEventRecord(ev1, stream));
+    HIP_OK(hipEventSynchronize(ev1));
+    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+    return ms;
   };
-  const bool tune_runs = tune && n_kernels <= 1;   // trial launches would time a kernel alone
-  int k2_G = 0, k2w_G = 0;
+  int best = cand[0]; float best_slope = 0;
+  for (size_t i = 0; i < cand.size(); i++) {
+    timed(4, cand[i]);
+    const float t0 = timed(32, cand[i]), t1 = timed(160, cand[i]);
+    const float slope = t1 - t0;
+    if (i == 0 || slope < best_slope) { best = cand[i]; best_slope = slope; }
+  }
+  return best;
+}
+
+// ---- the two-isoform part: sampler_k2<G> and its relatives ----
+void miso_batch::plan_k2(const KernelArgs &a) {
+  LaunchPlan &q = plan;
+  const size_t LDS_MAX = q.lds_max;
+  // (only when the batch's wavefronts fit the resident slots once: with several rounds the hardware hands
+  // out workgroups as slots free up, heaviest first, and the 4-wavefront workgroups balance better --
+  // MISO defaults, 6 chains x 40 000 events at one lane per chain: 374 ms paired, 351 ms unpaired)
+  q.k2_pair = !p.paired && !(std::getenv("MISO_K2_PAIR") && std::atoi(std::getenv("MISO_K2_PAIR")) == 0);
   if (n_k2 - n_k2w > 0) {
     const long chains = static_cast<long>(n_k2 - n_k2w) * p.noChains;
     const int maxq = p.paired ? (events[k2_first_event()].n_draw + 3) / 4 : (events[k2_first_event()].n_draw + 7) / 8;   // Philox blocks
-    const int max_cpw = p.paired ? std::max<int>(1, static_cast<int>((60 * 1024 - k2_fp) / (4 * k2_tab))) : 64;
-    if (const char *env = std::getenv("MISO_LANES_PER_CHAIN")) k2_G = std::atoi(env);
-    else if (tuned_k2_G) k2_G = tuned_k2_G;
+    const int max_cpw = p.paired ? std::max<int>(1, static_cast<int>((60 * 1024 - q.k2_fp) / (4 * q.k2_tab))) : 64;
+    if (const char *env = std::getenv("MISO_LANES_PER_CHAIN")) q.k2_G = std::atoi(env);
+    else if (tuned_k2_G) q.k2_G = tuned_k2_G;
     else {
-      k2_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
-      if (tune_runs && chains >= 4096 && std::getenv("MISO_AUTOTUNE_K2") != nullptr) {   // the rule is the measured optimum
+      q.k2_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
+      if (q.tune_runs && chains >= 4096 && std::getenv("MISO_AUTOTUNE_K2") != nullptr) {   // the rule is the measured optimum
         static const int kG[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32, 64};
-        std::vector<int> cand{k2_G};
+        std::vector<int> cand{q.k2_G};
         for (int i = 0; i < 15; i++)
-          if (kG[i] == k2_G) {
+          if (kG[i] == q.k2_G) {
             for (int j : {i - 1, i + 1, i + 2})
               if (j >= 0 && j < 15 && 64 / kG[j] <= max_cpw && !(p.paired && (kG[j] & (kG[j] - 1))) &&
                   kG[j] <= std::max(1, maxq))
                 cand.push_back(kG[j]);
           }
-        if (cand.size() > 1) k2_G = fastest(cand, [&](const KernelArgs &t, int g) { launch_k2(t, g, stream); });
-        tuned_k2_G = k2_G;
+        if (cand.size() > 1) q.k2_G = fastest(a, cand, [&](const KernelArgs &t, int g) { launch_k2(t, g, stream); });
+        tuned_k2_G = q.k2_G;
       }
     }
   }
   if (n_k2w > 0) {   // MODE 2: two workgroups per CU may share the LDS (80 KB each)
     const long chains = static_cast<long>(n_k2w) * p.noChains;
     const int maxq = (events[k2_first_event()].n_draw + 3) / 4;
-    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(k2w_fp);
-    const int max_cpw = static_cast<int>(std::max<long>(1, lds_left / static_cast<long>(4 * k2w_tab)));
+    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp);
+    const int max_cpw = static_cast<int>(std::max<long>(1, lds_left / static_cast<long>(4 * q.k2w_tab)));
     if (const char *env = std::getenv("MISO_LANES_PER_CHAIN")) {
-      k2w_G = std::atoi(env);
-      if (k2w_G < 1 || k2w_G > 64) MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
-    } else k2w_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
-    while (k2w_G < 64 && static_cast<size_t>(64 / k2w_G) > static_cast<size_t>(max_cpw)) k2w_G *= 2;   // a forced choice never exceeds the LDS
+      q.k2w_G = std::atoi(env);
+      if (q.k2w_G < 1 || q.k2w_G > 64) MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
+    } else q.k2w_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
+    while (q.k2w_G < 64 && static_cast<size_t>(64 / q.k2w_G) > static_cast<size_t>(max_cpw)) q.k2w_G *= 2;   // a forced choice never exceeds the LDS
   }
-  // single-end runs whose events all have a class table go to sampler_flat (kernels_flat.inl): NC chains
-  // per wavefront, as many as fit the wavefront's share of the LDS (two workgroups of four wavefronts
-  // per CU: 20 KB each), fewer when the batch would not fill the device otherwise.
-  // MISO_NO_FLAT=1: sampler_grp as in round 1 (A/B, tests); MISO_FLAT_NC=n forces the chains per wavefront.
-  // collapsed single-end batches (miso_batch_set_collapsed): the events with three and more isoforms in ONE launch of
-  // sampler_lane_k (kernels_lane.hip), provided every one of them has its class table
-  // (level 2 only: with the classes of a five- or ten-isoform event sharing ~1000 reads the chains of small binomials
-  // cost more than the read sweep they replace -- profiles/r03_collapsed.txt; it pays from ~10^4 reads per event)
-  // The route is decided per run (ADVICE r5): a class whose events all have their class tables takes sampler_lane_k, a
-  // run without them -- or of 33 isoforms and more: several mask words, sampler_wave / sampler_big only -- keeps the
-  // per-read kernels: its events are sampled per read, i.e. equal the CPU checker's COUNTER mode
-  // (tests/test_gpu_collapsed.py).
-  std::vector<char> run_lane(gen_runs.size(), 0);
-  bool lane_gen = false;
-  if (collapsed && collapsed_level >= 2 && !p.paired && n_gen > 0)
-    for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-      run_lane[ri] = !(gen_runs[ri].nocls || gen_runs[ri].kc >= 64);
-      lane_gen |= run_lane[ri] != 0;
-    }
-  std::vector<int> flat_nc(gen_runs.size(), 0), flat_nc_max(gen_runs.size(), 0);
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-    const GenRun &run = gen_runs[ri];
-    if (run_lane[ri]) continue;
-    if (p.paired || run.nocls || run.kc >= 64 || std::getenv("MISO_NO_FLAT") != nullptr) continue;
-    const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
-    // workgroups per CU the chains per wavefront are sized for: kernels_flat.inl's register budgets -- 3 up to four isoforms
-    // and for nine to twelve (measured round 4, profiles/r04_occupancy.txt), 2 otherwise (five to eight isoforms: the kernel
-    // allows 3, sizing for 3 gained nothing); MISO_FLAT_WGS overrides
-    const int wgs = std::getenv("MISO_FLAT_WGS") ? std::max(1, std::atoi(std::getenv("MISO_FLAT_WGS"))) : flat_wgs_for(run.kc);
-    const size_t lds_wave = std::getenv("MISO_LDS_MAX_KB") ? LDS_MAX / 4 : static_cast<size_t>(160 * 1024 / (4 * wgs)) - 64;
-    const int nc_max = std::min<int>(64, static_cast<int>(lds_wave) / slice);
-    if (nc_max < 1) continue;
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    // the fewest rounds of resident wavefronts that nc_max allows, then the fewest chains per wavefront
-    // that still makes that many rounds (a 40 000-chain batch at nc_max = 17 would run 1.15 rounds = 2)
-    const long slots = std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs / 2);
-    const long rounds = std::max<long>(1, (chains + slots * nc_max - 1) / (slots * nc_max));
-    int nc = static_cast<int>(std::min<long>(nc_max, std::max<long>(1, (chains + slots * rounds - 1) / (slots * rounds))));
-    // five to eight isoforms: how the 64 lanes divide over a wavefront's chains and items matters more than the
-    // rounds -- measured on one device, 40 000 events (events/s at 5 / 6 / 7 / 8 / 10 chains per wavefront):
-    // K=6 69.4k / 67.5k / 72.2k / 77.2k / 68.6k, K=7 64.1k / 61.4k / 68.8k / 73.5k / 64.3k, K=8 55.8k / 57.1k /
-    // 52.6k / 55.1k / 54.4k; K=5: 8 -> 93.4k, 7 -> 90.3k, 10 -> 86.8k.  (Timing the candidates on the first launch
-    // was tried: a 7 % difference is inside the noise of a 200-iteration trial, the choice flipped between runs.)
-    if (run.kc == 8) nc = std::min(nc, run.kmin >= 8 ? 6 : 8);
-    if (run.kc == 4 && run.kmin >= 4) nc = std::min(nc, 8);   // four isoforms, descriptor loop: 8 -> 119.8k, 16 -> 116.1k, 13 -> 85.5k
-    if (const char *env = std::getenv("MISO_FLAT_NC")) nc = std::max(1, std::min(nc_max, std::atoi(env)));
-    flat_nc[ri] = nc; flat_nc_max[ri] = nc_max;
-  }
-  // up to twenty isoforms the kernel of the launch's largest isoform count (its slice layout at compile time,
-  // kernels_flat.inl); MISO_FLAT_NO_KS=1: the run-time layout everywhere (A/B, tests)
-  auto flat_ks = [&](const GenRun &run) {
-    const int lo = run.kc == 4 ? 3 : (run.kc == 8 ? 5 : (run.kc == 12 ? 9 : (run.kc == 16 ? 13 : 17)));
-    return (run.kc <= 32 && run.kmax >= lo && run.kmax <= std::min(run.kc, 20) && std::getenv("MISO_FLAT_NO_KS") == nullptr) ? run.kmax : 0;
-  };
-  // ... and, when every event of the launch has that count, the kernel that knows it (UNI: no per-chain `k < K` masks)
-  auto flat_uni = [&](const GenRun &run) { return flat_ks(run) > 0 && run.kmin == run.kmax && std::getenv("MISO_FLAT_NO_UNI") == nullptr; };
-  auto flat_name = [&](const GenRun &run) {
-    return "sampler_flat<" + std::to_string(run.kc) + ", " + std::to_string(flat_ks(run)) + (flat_uni(run) ? ", true>" : ">");
-  };
-  // Which chains a wavefront of sampler_flat owns (kernels_flat.inl: a.wave_tab).  Uniform batches: `nc` consecutive
-  // chains each.  When the batch's events differ widely in size -- the heaviest wavefront of the uniform rule would
-  // carry more than twice the average wavefront's work units -- the wavefronts are packed by UNITS instead: as many
-  // consecutive chains (at most nc_max: the LDS) as make about the average wavefront's units, a chain of several
-  // times that alone in a WORKGROUP (FLAT_WIDE: 256 lanes), workgroups ordered heaviest first (the hardware starts
-  // them in index order).  MISO_FLAT_PACK=0 / 1: never / always (tests, A/B).
-  // How many units per wavefront: as many as nc_max average chains have -- the scalar step costs a wavefront the same
-  // for 2 chains and for 13, so fewer, fuller wavefronts win (hg19-like read counts, 40 000 events, K = 5: 497 ms at 8
-  // average chains per wavefront, 425 ms at 13+) -- unless that leaves the device part empty: fewer wavefronts than
-  // resident slots, or a second round that is less than half full (K = 3: 3349 wavefronts on 3072 slots 286 ms,
-  // 5704 wavefronts 270 ms); then the wavefront count goes to 0.95 x one or two rounds
-  // (profiles/r03_flat_pack_sweep.txt).  A forced MISO_FLAT_NC sets the average chains per wavefront instead.
-  auto flat_waves = [&](GenRun &run, int nc, int nc_max_u, long resident_u, int nc_max_p, long resident_p) {
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    const int C = p.noChains;
-    const char *env = std::getenv("MISO_FLAT_PACK");
-    const long key = (((static_cast<long>(nc) * 4 + (env ? 1 + (std::atoi(env) != 0) : 0)) * 128 + nc_max_u) * 128 + nc_max_p) * 1024 + (std::getenv("MISO_FLAT_PACK_OV") ? 1 + std::atol(std::getenv("MISO_FLAT_PACK_OV")) % 1000 : 0);
-    if (run.wave_key == key && run.d_wave_tab) return;
-    // (round 5) what a chain costs its wavefront, in work units: its units + the scalar step and thresholds, which do not
-    // depend on the reads.  Measured per chain-iteration at eight / five chains per wavefront (profiles/r05_flat_chunks.txt):
-    // K = 5 238 VALU against 1.33 per unit, K = 10 641 against 1.96, i.e. about 30 K + 25 units -- but the wavefronts this
-    // matters for carry 14 - 18 small chains, whose flat passes and leader sections are shared by twice as many chains:
-    // 16 K + 14.  Swept on hg19-like read counts at 25 ... 300 % of the first figure: K = 3 / 4 / 6 / 8 best at 50 % (208 /
-    // 152 / 107 / 80 k events/s against 153 / 144 / 97 / 74 k at 100 %), K = 5 / 12 at 100 % (122 / 45 k against 114 / 43 k);
-    // by units alone: 151 / 112 / 55 k at K = 3 / 5 / 10.  MISO_FLAT_PACK_OV=<per cent of the rule> (0: by units alone).
-    const char *ov_env = std::getenv("MISO_FLAT_PACK_OV");
-    const long ov_pct = ov_env ? std::atol(ov_env) : 100;   // (per cent of the rule: experiments)
-    auto units_of = [&](long c) {
-      const PackedEvent &e = events[h_slots[n_k2 + run.first + c / C]];
-      return static_cast<long>(e.n_units) + (16L * e.K + 14) * ov_pct / 100;
-    };
-    long total = 0, head = 0;
-    for (long c = 0; c < chains; c++) { const long u = units_of(c); total += u; if (c < nc) head += u; }
-    long heaviest = head;   // the list is ordered by isoforms first: look at every wavefront of the uniform rule
-    for (long c = 0, sum = 0; c < chains; c++) {
-      sum += units_of(c);
-      if ((c + 1) % nc == 0 || c + 1 == chains) { heaviest = std::max(heaviest, sum); sum = 0; }
-    }
-    const double mean_wave = static_cast<double>(total) * nc / std::max<long>(1, chains);
-    const bool pack = env ? std::atoi(env) != 0 : (chains > nc && static_cast<double>(heaviest) > 2.0 * mean_wave);
-    struct W { int32_t first, n; long units; };
-    std::vector<W> waves, wides;
-    if (!pack) {
-      for (long c = 0; c < chains; c += nc) waves.push_back(W{static_cast<int32_t>(c), static_cast<int32_t>(std::min<long>(nc, chains - c)), 0});
-      run.wave_nc = nc;
-    } else {
-      // (packed launches have their own sizing: launch_flat)
-      const int nc_max = nc_max_p; const long resident = resident_p;
-      const int cap = std::min(nc_max, 255);
-      int most = 1;
-      auto pack_with = [&](double U) {
-        waves.clear(); wides.clear(); most = 1;
-        const double wide_min = std::max(3.0 * U, 2048.0);
-        for (long c = 0; c < chains;) {
-          const long u = units_of(c);
-          if (static_cast<double>(u) >= wide_min) { wides.push_back(W{static_cast<int32_t>(c), 1, u}); c++; continue; }
-          W w{static_cast<int32_t>(c), 0, 0};
-          while (c < chains && w.n < cap) {
-            const long v = units_of(c);
-            if (static_cast<double>(v) >= wide_min || (w.n > 0 && static_cast<double>(w.units + v) > 1.05 * U)) break;
-            w.units += v; w.n++; c++;
-          }
-          most = std::max(most, static_cast<int>(w.n));
-          waves.push_back(w);
-        }
-        return static_cast<long>(waves.size() + 4 * wides.size());
-      };
-      const double per_chain = static_cast<double>(total) / std::max<long>(1, chains);
-      const bool forced = std::getenv("MISO_FLAT_NC") != nullptr;
-      const long n_waves = pack_with(std::max(64.0, per_chain * (forced ? nc : cap)));
-      if (!forced && n_waves < 3 * resident / 2) {
-        // (round 6) ... and TWO rounds are aimed at from further below than one: the second round's workgroups start as the
-        // first round's end, staggered, and a count within a few per cent of two full rounds runs into a third (hg19-like read
-        // counts, K = 5, 2048 resident wavefronts: 4029 wavefronts 71.7 ms, 3793 64.6 ms, 3541 66.2 ms, 2956 -- the fullest
-        // packing -- 67.7 ms; profiles/r06_flat_pack_rounds.txt).  MISO_FLAT_ROUNDS_FRAC: the fraction of two rounds (experiments).
-        const bool two = n_waves > resident;
-        const double frac2 = std::getenv("MISO_FLAT_ROUNDS_FRAC") ? std::atof(std::getenv("MISO_FLAT_ROUNDS_FRAC")) : 0.85;
-        const double want = (two ? frac2 : 0.95) * static_cast<double>(two ? 2 * resident : resident);
-        if (static_cast<double>(n_waves) < want) {
-          // (round 5) ... and not a few wavefronts MORE than the round(s): the packing's bound is a target, the count it
-          // makes lands some per cent off, and 3110 wavefronts on 3072 slots cost a second round for 38 of them
-          // (K = 3, hg19-like read counts: 154 k events/s there, 212 k at 2960; profiles/r05_flat_chunks.txt)
-          const long target = two ? static_cast<long>((frac2 + 0.04) * 2.0 * static_cast<double>(resident)) : resident;
-          double U2 = std::max(64.0, static_cast<double>(total) / want);
-          long n2 = pack_with(U2);
-          for (int it = 0; it < 8 && n2 > target; it++) {
-            const long before = n2;
-            U2 *= static_cast<double>(n2) / (0.97 * static_cast<double>(target));
-            n2 = pack_with(U2);
-            if (n2 >= before) break;   // the chains per wavefront are at the LDS's limit: fuller wavefronts are not to be had
-          }
-        }
-      }
-      if (std::getenv("MISO_TIMING"))
-        std::fprintf(stderr, "[flat_waves] kc %d chains %ld cost/chain %.1f cap %d resident %ld first pack %ld waves -> %zu waves + %zu wide, most chains %d\n",
-                     run.kc, chains, per_chain, cap, resident, n_waves, waves.size(), wides.size(), most);
-      std::stable_sort(wides.begin(), wides.end(), [](const W &x, const W &y) { return x.units > y.units; });
-      std::stable_sort(waves.begin(), waves.end(), [](const W &x, const W &y) { return x.units > y.units; });
-      run.wave_nc = most;
-    }
-    run.wave_tab.clear();
-    for (const W &w : wides) for (int i = 0; i < 4; i++) { run.wave_tab.push_back(w.first); run.wave_tab.push_back(1 | FLAT_WIDE); }
-    for (const W &w : waves) { run.wave_tab.push_back(w.first); run.wave_tab.push_back(w.n); }
-    while ((run.wave_tab.size() / 2) % 4) { run.wave_tab.push_back(0); run.wave_tab.push_back(0); }   // padding wavefronts
-    run.wave_wide = static_cast<int>(wides.size());
-    run.wave_packed = pack;
-    if (run.d_wave_tab) (void) hipFree(run.d_wave_tab);
-    run.d_wave_tab = nullptr;
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&run.d_wave_tab), std::max<size_t>(run.wave_tab.size(), 2) * sizeof(int32_t)));
-    HIP_OK(hipMemcpy(run.d_wave_tab, run.wave_tab.data(), run.wave_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    run.wave_key = key;
-  };
-  auto launch_flat = [&](KernelArgs ka, GenRun &run, int nc, int nc_max, hipStream_t st) {
-    {
-      const long chains = static_cast<long>(run.count) * p.noChains;
-      const int wgs = std::getenv("MISO_FLAT_WGS") ? std::max(1, std::atoi(std::getenv("MISO_FLAT_WGS"))) : flat_wgs_for(run.kc);
-      // Five to eight isoforms: the kernel's registers allow three workgroups per CU; launches of like-sized events are sized for
-      // two (fuller wavefronts: K = 6 312 against 333 ms, K = 7 347 / 366), launches packed by cost for three -- more, smaller
-      // wavefronts level the heavy tail better than fuller ones amortise the scalar step (hg19-like read counts, 40 000 events:
-      // K = 5 276 -> 252 ms, K = 6 332 -> 278, K = 7 379 -> 339, K = 8 415 -> 393; profiles/r06_flat_licm.txt)
-      int wgs_p = wgs, nc_max_p = nc_max;
-      if (run.kc == 8 && std::getenv("MISO_FLAT_WGS") == nullptr && std::getenv("MISO_LDS_MAX_KB") == nullptr && std::getenv("MISO_FLAT_PACK_WGS2") == nullptr) {
-        wgs_p = 3;
-        const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
-        nc_max_p = std::max(1, std::min<int>(64, static_cast<int>(160 * 1024 / (4 * wgs_p) - 64) / slice));
-      }
-      flat_waves(run, nc, nc_max, std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs / 2),
-                 nc_max_p, std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs_p / 2));
-    }
-    ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count;
-    ka.kstride = run.kmax; ka.cstride = std::max(run.maxcls, 1); ka.tstride = 0; ka.nc = run.wave_nc;
-    ka.wave_tab = run.d_wave_tab;
-    // the descriptor read loop from four isoforms on (three: the walking loop is 2 % faster -- two thresholds per unit,
-    // little to save) and whenever a chain owns a whole workgroup; MISO_FLAT_NO_DESC=1: the walking loop everywhere
-    // (A/B, tests; not with workgroup-wide chains)
-    ka.flat_desc = ((std::getenv("MISO_FLAT_NO_DESC") == nullptr && run.kmax >= 4) || run.wave_wide > 0) ? 1 : 0;
-    // Thresholds only for the chains whose psi changed (kernels_flat.inl): the pass is one lane per (chain, class) and the
-    // Metropolis-Hastings step rejects 45 - 65 % of the proposals, but numbering the chains that accepted costs every lane
-    // a few instructions -- it pays where the thresholds weigh enough: from six isoforms on (K = 6 ... 12: + 4.5 ... 6.4 %)
-    // and for small events (hg19-like read counts at K = 5: + 5.5 %; 1000 reads per event at K = 3 ... 5: - 1 ... 2 %,
-    // profiles/r04_occupancy.txt).  MISO_FLAT_THR_SKIP=0 / 1: never / always (A/B, tests).
-    {
-      double units = 0;
-      for (int j = 0; j < run.count; j++) units += events[h_slots[n_k2 + run.first + j]].n_units;
-      const char *env = std::getenv("MISO_FLAT_THR_SKIP");
-      ka.flat_thr_skip = env ? (std::atoi(env) != 0) : (run.kmax >= 6 || units < 150.0 * run.count);
-    }
-    const unsigned grid = static_cast<unsigned>(run.wave_tab.size() / 8);
-    const size_t lds = 4 * static_cast<size_t>(run.wave_nc) * flat_layout(ka.kstride, ka.cstride).bytes;
-    // Priority by progress (device.hpp prio_by_progress) when the launch takes several rounds of like-sized wavefronts:
-    // 40 000 events x 1000 reads, K = 5 348.0 -> 334.4 ms, K = 10 649.4 -> 631.4 ms, same box; wavefronts packed by cost
-    // (hg19-like read counts) lose 1 % and keep the arbiter's own order; so do the paired-end and the two-isoform kernels
-    // (+ 0.5 ... 4 %: profiles/r06_prio_by_progress.txt).  MISO_PRIO_QUARTILES=0 / 1: never / everywhere (A/B).
-    if (std::getenv("MISO_PRIO_QUARTILES") == nullptr && !run.wave_packed && run.wave_wide == 0 &&
-        static_cast<long>(grid) * 4 > static_cast<long>(slots_for(static_cast<long>(run.count) * p.noChains)) * flat_wgs_for(run.kc) / 2)
-      ka.balance = 2;
-#define MISO_FLAT_LAUNCH_(KC, KS, UNI)                                                                  \
-  {                                                                                                     \
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_flat<KC, KS, UNI>),              \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));     \
-    hipLaunchKernelGGL((sampler_flat<KC, KS, UNI>), dim3(grid), dim3(256), lds, st, ka);                \
-  }
-#define MISO_FLAT_LAUNCH(KC, KS)                                                                        \
-  {                                                                                                     \
-    if (KS > 0 && flat_uni(run)) MISO_FLAT_LAUNCH_(KC, KS, (KS > 0)) else MISO_FLAT_LAUNCH_(KC, KS, false)  \
-  }
-    const int ksel = flat_ks(run);   // (== ka.kstride or 0)
-    switch (run.kc) {
-    case 4:
-      if (ksel == 3) MISO_FLAT_LAUNCH(4, 3) else if (ksel == 4) MISO_FLAT_LAUNCH(4, 4) else MISO_FLAT_LAUNCH(4, 0)
-      break;
-    case 8:
-      if (ksel == 5) MISO_FLAT_LAUNCH(8, 5) else if (ksel == 6) MISO_FLAT_LAUNCH(8, 6) else if (ksel == 7) MISO_FLAT_LAUNCH(8, 7)
-      else if (ksel == 8) MISO_FLAT_LAUNCH(8, 8) else MISO_FLAT_LAUNCH(8, 0)
-      break;
-    case 12:
-      if (ksel == 9) MISO_FLAT_LAUNCH(12, 9) else if (ksel == 10) MISO_FLAT_LAUNCH(12, 10) else if (ksel == 11) MISO_FLAT_LAUNCH(12, 11)
-      else if (ksel == 12) MISO_FLAT_LAUNCH(12, 12) else MISO_FLAT_LAUNCH(12, 0)
-      break;
-    case 16:
-      if (ksel == 13) MISO_FLAT_LAUNCH(16, 13) else if (ksel == 14) MISO_FLAT_LAUNCH(16, 14) else if (ksel == 15) MISO_FLAT_LAUNCH(16, 15)
-      else if (ksel == 16) MISO_FLAT_LAUNCH(16, 16) else MISO_FLAT_LAUNCH(16, 0)
-      break;
-    default:
-      if (ksel == 17) MISO_FLAT_LAUNCH(32, 17) else if (ksel == 18) MISO_FLAT_LAUNCH(32, 18) else if (ksel == 19) MISO_FLAT_LAUNCH(32, 19)
-      else if (ksel == 20) MISO_FLAT_LAUNCH(32, 20) else MISO_FLAT_LAUNCH(32, 0)
-      break;
-    }
-#undef MISO_FLAT_LAUNCH
-#undef MISO_FLAT_LAUNCH_
-    HIP_OK(hipGetLastError());
-  };
-  std::vector<int> grp_G(gen_runs.size(), 64);
-  std::vector<GrpShape> grp_sh(gen_runs.size());
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-    GenRun &run = gen_runs[ri];
-    if (run_lane[ri]) continue;
-    if (run.kc >= 64) { flat_nc[ri] = 0; grp_G[ri] = 64; grp_sh[ri] = GrpShape{0, 0}; continue; }   // more than 32 isoforms: one wavefront per chain
-    // sampler_flat or sampler_grp?  Measured on the batch's first launch like the lanes per chain below
-    // (flat wins at every isoform count of profiles/r02_flat_vs_grp_sweep.txt but 5); a small or untuned
-    // batch takes sampler_flat.
-    const bool contest = flat_nc[ri] > 0 && tune_runs && static_cast<long>(run.count) * p.noChains >= 2048 &&
-                         run.tuned_flat < 0 && std::getenv("MISO_FLAT_NC") == nullptr;
-    if (flat_nc[ri] > 0 && run.tuned_flat == 0) flat_nc[ri] = 0;
-    if (flat_nc[ri] > 0 && !contest) continue;
-    GrpShape sh = grp_sh[ri] = grp_shape(run);
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    int G = 64;
-    if (run.wide) {   // one chain per workgroup (launch_grp): the score table joins the slice when four of them fit
-      GrpShape w{0, 0};
-      w.ts = run.kmax * il2;
-      if (fp_bytes_of(run) + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, w.ts)) + 64 > LDS_MAX) w.ts = 0;
-      grp_sh[ri] = w;
-      grp_G[ri] = 64;
-      continue;
-    }
-    if (const char *env = std::getenv("MISO_GENERAL_LANES")) {
-      G = std::atoi(env);
-    } else if (const char *envc = std::getenv("MISO_GENERAL_LANES_BY_CLASS")) {   // experiments: "4:16,8:16,12:32,16:32,32:32"
-      G = 16;
-      for (const char *q = envc; q && *q;) {
-        int kc = 0, g = 0;
-        if (std::sscanf(q, "%d:%d", &kc, &g) == 2 && kc == run.kc) G = g;
-        q = std::strchr(q, ',');
-        if (q) q++;
-      }
-    } else if (run.tuned_G) {
-      G = run.tuned_G;
-      if (p.paired && sh.ts && !grp_fits(run, sh, G)) {   // chosen with the score tables in global memory (the eight-lane rule below)
-        GrpShape s0 = sh;
-        s0.ts = 0;
-        if (grp_fits(run, s0, G)) sh = grp_sh[ri] = s0;
-      }
-    } else {
-      // rule of thumb.  single-end: the per-iteration scalar step costs the same per wavefront
-      // whatever G is, so pack as many chains per wavefront as still fills the device: the smallest
-      // G whose wavefronts occupy every resident slot; a batch too small for that takes the largest.
-      // paired-end: the read loop waits on memory and more wavefronts hide it: largest G up to 16; 32 from
-      // nine isoforms on (measured, pe_dense: K=10 19.5k -> 19.9k, K=20 7.35k -> 7.57k events/s; K=5 29.9k ->
-      // 28.9k, K=3 53k -> 46k) and whenever 16 would leave the kernel's share of the device unfilled.
-      bool found = false;
-      // (a whole-gene mix -- several classes side by side -- runs 9 % faster with 32 everywhere: 14.4k -> 15.7k genes/s)
-      // (round 3, 20 000 events of one isoform count: 16 lanes beat 32 from nine isoforms on as well once the launch
-      // is more than a round and a half of wavefronts -- K = 9 21.3k -> 26.8k, K = 10 20.8k -> 26.9k, K = 12 19.1k ->
-      // 22.5k, K = 16 14.4k -> 16.6k, K = 20 10.7k -> 10.9k events/s; the mix keeps 32: 16.8k vs 14.2k genes/s;
-      // profiles/r03_pe_lanes_sweep.txt)
-      int n_classes = 0;
-      for (size_t rj = 0; rj < gen_runs.size(); rj++) if (rj == 0 || gen_runs[rj].kc != gen_runs[rj - 1].kc) n_classes++;
-      // (round 3, 8 hardware queues, 16 384 genes of 3-20 isoforms per 1500 iterations: 16 lanes up to 16 isoforms against 32
-      // everywhere -- 400 pairs per gene 120 vs 150 ms, 1000 pairs 194 vs 206 ms, hg19-like counts 176 vs 175 ms, 2500 pairs
-      // 436 vs 367 ms: small genes share the scalar step four to a wavefront, large ones want the lanes; the switch sits at a
-      // mean of 400 drawing quads per gene of the class; MISO_PE_MIX_LANES=16|32 forces)
-      const double mean_q = run.sum_q / std::max(1, run.count);
-      const char *mixl = std::getenv("MISO_PE_MIX_LANES");
-      // (round 5, same batch on one box, 7500 iterations: the 17 - 20 isoform class on 16 lanes as well -- 1000 pairs per gene
-      // 930 -> 852 ms, hg19-like pair counts 865 -> 820 ms: four chains of a wavefront share the scalar step, and the class
-      // no longer fills the device with half-efficient wavefronts for the launch's first third while the other classes
-      // wait; the bucket of "at least 32 lanes" from a need of 32 lanes instead of 24: a 20-isoform gene of 1000 pairs
-      // needs 28 by the share rule; profiles/r05_pe_mix_lanes.txt)
-      const bool mix16 = run.kc <= 32 && !run.force_G && (mixl ? std::atoi(mixl) == 16 : mean_q < 400.0);
-      const bool pe32 = p.paired && ((n_classes + (n_k2 > 0 ? 1 : 0) > 1 && !mix16) || (run.kc >= 12 && 2 * ((chains + 3) / 4) < 3 * static_cast<long>(slots_for(chains))) ||
-                                     (chains + 3) / 4 < slots_for(chains));
-      for (int g : {2, 4, 8, 16, 32}) {
-        if (p.paired && g > 16 && found && !pe32) break;
-        if (!grp_fits(run, sh, g)) continue;
-        const int cpw = 64 / g;
-        if (!found || g <= std::max(2, run.maxq)) G = g;
-        found = true;
-        if (!p.paired && (chains + cpw - 1) / cpw >= slots_for(chains)) break;
-      }
-      // Round 5, paired-end, ONE isoform-count class in the batch, five to nine isoforms, two rounds of wavefronts and more at
-      // eight lanes: EIGHT lanes per chain -- eight chains of a wavefront share the scalar step instead of four.  Rounds 2 - 4
-      // measured that slower (the read loop waited on memory and more wavefronts hid it); since the draws are ordered by
-      // fragment rows and the loop's header no longer waits for fresh gathers it wins: 40 000 events x 1000 pairs, K = 5 / 6 / 7 /
-      // 8 / 9: 45.3 -> 54.2, 41.5 -> 48.7, 40.5 -> 45.5, 38.0 -> 40.5, 30.2 -> 31.5 k events/s; K = 12: 25.7 -> 21.2 k, four lanes
-      // 33.7 k at K = 5; in a whole-gene mix, where a class is a few thousand genes, 19.2 -> 18.2 k genes/s: not there
-      // (profiles/r05_lanes_sweep.txt).  MISO_PE_LANES8=0 / 1: never / also in a mix and for the size buckets' normal run.
-      {
-        const char *l8 = std::getenv("MISO_PE_LANES8");
-        const bool single = n_classes + (n_k2 > 0 ? 1 : 0) == 1;
-        const bool want8 = l8 && std::atoi(l8) != 2 ? std::atoi(l8) != 0 : ((single || l8) && chains >= 8L * 2 * slots_for(chains));   // (2: the rule in a mix of classes too)
-        if (p.paired && want8 && G == 16 && !run.force_G && run.kmin >= 5 && run.kmax <= 9 && grp_fits(run, sh, 8)) G = 8;
-        // Three and four isoforms the same -- there the class keeps its score tables in LDS (grp_shape), which holds four
-        // chains per wavefront and no more: eight chains with the tables in global memory (an L2 line per pick) instead,
-        // K = 3 66.6 -> 78.9 k, K = 4 58.1 -> 68.0 k events/s; the tables alone are worth 2 % (16 lanes without them 65.3 /
-        // 57.0 k), four lanes lose (55.9 / 37.6 k) (profiles/r05_lanes_sweep.txt).
-        if (p.paired && want8 && G == 16 && !run.force_G && run.kmax <= 4) {
-          GrpShape sh8 = sh;
-          if (!grp_fits(run, sh8, 8)) sh8.ts = 0;
-          if (grp_fits(run, sh8, 8)) { sh = grp_sh[ri] = sh8; G = 8; }
-        }
-      }
-      if (tune_runs && chains >= 2048 && G != 64) {
-        std::vector<int> cand{G};
-        // the rule errs on the small side (tail effect when the wavefronts do not fit one round)
-        for (int g : {G * 2, G * 4})
-          if (!p.paired && grp_fits(run, sh, g) && g <= std::max(2, 2 * run.maxq)) cand.push_back(g);
-        if (cand.size() > 1)
-          G = fastest(cand, [&](const KernelArgs &t, int g) { launch_grp(t, run, sh, g, stream); });
-        run.tuned_G = G;
-      }
-    }
-    if (run.force_G && G < run.force_G && std::getenv("MISO_GENERAL_LANES") == nullptr) G = run.force_G;   // size bucket (upload)
-    if (run.small && p.paired && std::getenv("MISO_GENERAL_LANES") == nullptr && std::getenv("MISO_GENERAL_LANES_BY_CLASS") == nullptr) {   // the small genes' bucket: eight chains per wavefront, score tables in global memory
-      GrpShape sh8 = sh;
-      sh8.ts = 0;
-      if (grp_fits(run, sh8, 8)) { sh = grp_sh[ri] = sh8; G = 8; }
-    }
-    // a forced (or odd) choice never exceeds the LDS budget: fewer chains per wavefront instead
-    while (G < 64 && !grp_fits(run, sh, G)) G = (G < 2) ? 2 : ((G & (G - 1)) ? 64 : G * 2);
-    grp_G[ri] = G;
-    if (contest) {
-      const int nc = flat_nc[ri];
-      const int win = (G == 64) ? 0 : fastest({0, G}, [&](const KernelArgs &t, int g) {
-        if (g == 0) launch_flat(t, run, nc, flat_nc_max[ri], stream); else launch_grp(t, run, sh, g, stream); });
-      run.tuned_flat = win == 0 ? 1 : 0;
-      if (win != 0) flat_nc[ri] = 0;
-    }
-  }
-
-  if (k2_pair && k2_G > 0) {
-    const long waves = (static_cast<long>(n_k2 - n_k2w) * p.noChains + 64 / k2_G - 1) / (64 / k2_G);
-    k2_pair = waves <= wave_slots || std::getenv("MISO_K2_PAIR") != nullptr;
+  if (q.k2_pair && q.k2_G > 0) {
+    const long waves = (static_cast<long>(n_k2 - n_k2w) * p.noChains + 64 / q.k2_G - 1) / (64 / q.k2_G);
+    q.k2_pair = waves <= wave_slots || std::getenv("MISO_K2_PAIR") != nullptr;
   }
   // ---- single-end two-isoform events in one launch with two lane widths (sampler_k2_mix, kernels_k2.hip) ----
   // Only when the batch runs as ONE round of paired 8-wavefront workgroups (k2_pair) that does not fill the CUs:
   // the heaviest events get G + 1 lanes per chain, as many of them as still leave one CU per workgroup.
   // MISO_K2_MIX=0 switches it off (A/B), MISO_K2_SPLIT=n forces the number of events of the wide part.
-  int k2_mix = 0, k2_mix_blocks = 0;
   {
-    const int count = n_k2 - n_k2w, C = p.noChains, G = k2_G;
+    const int count = n_k2 - n_k2w, C = p.noChains, G = q.k2_G;
     const char *off = std::getenv("MISO_K2_MIX");
-    if (!p.paired && k2_pair && count > 0 && G >= 1 && G <= 7 && n_kernels <= 1 && !(off && std::atoi(off) == 0)) {
+    if (!p.paired && q.k2_pair && count > 0 && G >= 1 && G <= 7 && q.n_kernels <= 1 && !(off && std::atoi(off) == 0)) {
       const int cus = wave_slots / 8, cpwA = 64 / (G + 1), cpwB = 64 / G;
       auto blocks = [&](long chains, int cpw) { return static_cast<int>(((chains + cpw - 1) / cpw + 7) / 8); };
       auto total = [&](int y) { return blocks(static_cast<long>(y) * C, cpwA) + blocks(static_cast<long>(count - y) * C, cpwB); };
@@ -1302,36 +879,17 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
           while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (total(mid) <= cus) lo = mid; else hi = mid - 1; }
           y = lo;
         }
-        if (y > 0 && total(y) <= cus) { k2_mix = y; k2_mix_blocks = blocks(static_cast<long>(y) * C, cpwA); }
+        if (y > 0 && total(y) <= cus) { q.k2_mix = y; q.k2_mix_blocks = blocks(static_cast<long>(y) * C, cpwA); }
       }
     }
   }
-  auto k2_mix_name = [&](int G) { return "sampler_k2_mix<" + std::to_string(G + 1) + ", " + std::to_string(G) + ">"; };
-  auto launch_k2_mix = [&](KernelArgs ka, int G, hipStream_t st) {
-    const int first = n_k2w, count = n_k2 - n_k2w, C = p.noChains, cpwB = 64 / G;
-    ka.slot_event = d_slots + first; ka.n_slots = count;
-    ka.pair_waves = 1; ka.mix_slots = k2_mix; ka.mix_blocks = k2_mix_blocks;
-    const long wavesB = (static_cast<long>(count - k2_mix) * C + cpwB - 1) / cpwB;
-    const unsigned grid = static_cast<unsigned>(k2_mix_blocks + (wavesB + 7) / 8);
-    switch (G) {
-    case 1: hipLaunchKernelGGL((sampler_k2_mix<2, 1>), dim3(grid), dim3(512), 0, st, ka); break;
-    case 2: hipLaunchKernelGGL((sampler_k2_mix<3, 2>), dim3(grid), dim3(512), 0, st, ka); break;
-    case 3: hipLaunchKernelGGL((sampler_k2_mix<4, 3>), dim3(grid), dim3(512), 0, st, ka); break;
-    case 4: hipLaunchKernelGGL((sampler_k2_mix<5, 4>), dim3(grid), dim3(512), 0, st, ka); break;
-    case 5: hipLaunchKernelGGL((sampler_k2_mix<6, 5>), dim3(grid), dim3(512), 0, st, ka); break;
-    case 6: hipLaunchKernelGGL((sampler_k2_mix<7, 6>), dim3(grid), dim3(512), 0, st, ka); break;
-    default: hipLaunchKernelGGL((sampler_k2_mix<8, 7>), dim3(grid), dim3(512), 0, st, ka); break;
-    }
-    HIP_OK(hipGetLastError());
-  };
 
   // ---- single-end two-isoform events: a lane width per event (sampler_k2_multi, kernels_k2m.hip) ----
   // Default for single-end batches; MISO_K2_MULTI=0 (A/B, tests) or a forced MISO_LANES_PER_CHAIN: the
   // single-width / two-width launches above.  The plan depends on the list, the chains and this kernel's share of
   // the device only: made once per upload.  MISO_K2_COST="block,step1,step2,step3,step4" overrides the cost model,
   // MISO_K2_TARGET=x forces the bound on a wavefront's step (tests: small batches with many widths).
-  // (workgroup-wide chains may use several workgroups, coop.hpp; MISO_NO_COOP=1: their own only)
-  const int coop_max = coop_enabled() ? COOP_MAX_N : 1;
+  const int coop_max = q.coop_max;
   // All cooperative workgroups of ONE launch() -- the gene runs' (wide_setup) and the two-isoform plans' -- come out of one
   // budget of COOP_MAX_WGS (coop.hpp): the gene runs take what upload() asked for, at most 5/8 when two-isoform events are
   // in the batch too; the MODE 2 plan gets two thirds of the rest when both two-isoform kernels run, the other plan the
@@ -1348,30 +906,27 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
     coop_k2_budget = n_k2w > 0 ? left - coop_k2w_budget : left;
     if (!p.paired) coop_k2_budget = left;
   }
-  bool k2_multi = false;
-  const bool lane_route = collapsed && !p.paired && n_k2 > 0;   // miso_batch_set_collapsed
+  q.lane_route = collapsed && !p.paired && n_k2 > 0;   // miso_batch_set_collapsed
   // lanes per chain of the collapsed step: one (sampler_lane).  Sharing a chain between 2, 4 or 8 lanes (sampler_k2c:
   // the Metropolis-Hastings step's transcendentals one per lane, the binomial's rejection trials G at a time) brings more
   // wavefronts but the same instructions per wavefront -- 40 000 chains: 56.4 ms on one lane, 58.5 / 59.1 / 86.3 ms on
   // 2 / 4 / 8 (profiles/r03_collapsed.txt); MISO_COLLAPSED_LANES forces (experiments, tests)
-  int lane_G = 1;
-  if (lane_route) {
-    if (const char *f = std::getenv("MISO_COLLAPSED_LANES")) { const int g = std::atoi(f); if (g == 1 || g == 2 || g == 4 || g == 8) lane_G = g; }
+  if (q.lane_route) {
+    if (const char *f = std::getenv("MISO_COLLAPSED_LANES")) { const int g = std::atoi(f); if (g == 1 || g == 2 || g == 4 || g == 8) q.lane_G = g; }
   }
   // one chain per lane, up to two wavefronts per SIMD: the form that overlaps a chain's own work (kernels_lane.hip
   // sampler_lane_ilp); beyond, the lean one (six wavefronts per SIMD hide each other's latencies).  MISO_LANE_ILP=0 / 1 forces.
-  bool lane_ilp = false;
-  if (lane_route && lane_G == 1) {
-    lane_ilp = ((static_cast<long>(n_k2) * p.noChains + 255) / 256) * 4 <= wave_slots;
-    if (const char *env = std::getenv("MISO_LANE_ILP")) lane_ilp = std::atoi(env) != 0;
+  if (q.lane_route && q.lane_G == 1) {
+    q.lane_ilp = ((static_cast<long>(n_k2) * p.noChains + 255) / 256) * 4 <= wave_slots;
+    if (const char *env = std::getenv("MISO_LANE_ILP")) q.lane_ilp = std::atoi(env) != 0;
   }
   {
     const int count = n_k2 - n_k2w;
     const char *off = std::getenv("MISO_K2_MULTI");
     // paired-end events that keep MODE 1 (a drawing read touches a non-finite score): the same, 4-wavefront workgroups,
     // 4 ... 64 lanes as far as the chains' tables (2 il int32 each) fit the LDS, 256-lane chains
-    const long pe1_left = static_cast<long>(LDS_MAX) - static_cast<long>(k2_fp) - K2_RED_BYTES;
-    const int pe1_cpw = p.paired ? static_cast<int>(std::max<long>(0, pe1_left / static_cast<long>(4 * std::max<size_t>(k2_tab, 1)))) : 64;
+    const long pe1_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2_fp) - K2_RED_BYTES;
+    const int pe1_cpw = p.paired ? static_cast<int>(std::max<long>(0, pe1_left / static_cast<long>(4 * std::max<size_t>(q.k2_tab, 1)))) : 64;
     if (p.paired && count > 0 && pe1_cpw >= 1 && std::getenv("MISO_LANES_PER_CHAIN") == nullptr && !(off && std::atoi(off) == 0)) {
       const int resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 4);
       const long key = (static_cast<long>(resident) * 64 + p.noChains) * 256 + coop_k2_budget + (coop_max > 1 ? 0 : 200);
@@ -1385,7 +940,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
         k2_plan = plan_lanes(nd.data(), count, p.noChains, widths, 5, 4, 4, resident, pe1_cpw, cost, forced, coop_max, coop_k2_budget);
         k2_plan_key = key;
       }
-      k2_multi = k2_plan.n_segs > 0;
+      q.k2_multi = k2_plan.n_segs > 0;
     }
     if (!p.paired && count > 0 && std::getenv("MISO_LANES_PER_CHAIN") == nullptr && !(off && std::atoi(off) == 0)) {
       const int resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 8);
@@ -1407,61 +962,19 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
         if (wpb != 8 && wpb != 4 && wpb != 1) MISO_FAIL(MISO_EINVAL, "MISO_K2_WPB must be 8, 4 or 1");
         if (wpb != 8) k2_plan = plan_lanes(nd.data(), count, p.noChains, widths, 12, wpb >= 4 ? wpb : 0, wpb, resident * 8 / wpb, 64, cost, forced, coop_max, coop_k2_budget);
         k2_plan_key = key;
-        // One round, 8 wavefronts per workgroup: wavefronts w and w + 4 of a workgroup share a SIMD.  Pair the launch's
-        // wavefronts (all runs but the workgroup-wide chains') by estimated duration, the i-th heaviest with the i-th
-        // lightest ACROSS the runs: within a run the p-th heaviest + p-th lightest (a.pair_waves) give every SIMD of the
-        // run the same work, but the runs' sums differ (a run's first wavefront sits at the planner's bound, its last
-        // wherever the next width takes over) and the SIMDs of the lighter runs idle at the end (wave-slot occupancy
-        // 0.78, profiles/r03_wave_time.txt).  Measured, 40 000 events: hg19-like read counts (13 runs) 73.9 -> 71.4 ms;
-        // 1000 reads each (4 runs) 99.7 -> 100.8 ms, 3000 reads 244.6 -> 250.0 ms (few runs: their sums are close already,
-        // and the kernel with a body per run AND per wavefront is larger): used from seven runs on.
-        // MISO_K2_GLOBAL_PAIR=0 / 1: never / always (A/B, tests).
-        k2_pair_tab.clear(); k2_pair_grid = 0; k2_pair_wide_blocks = 0;
-        const char *gp = std::getenv("MISO_K2_GLOBAL_PAIR");
-        if (k2_plan.n_segs > 0 && k2_plan.rounds == 1 && wpb == 8 && (gp ? std::atoi(gp) != 0 : k2_plan.n_segs >= 7)) {
-          struct W { double cost; int32_t code; };
-          std::vector<W> ws;
-          bool ok = true, seen_narrow = false;
-          for (int sg = 0; sg < k2_plan.n_segs && ok; sg++) {
-            const int G = k2_plan.seg_lanes[sg];
-            if (G == K2_WIDE) { ok = !seen_narrow; k2_pair_wide_blocks = k2_plan.seg_block[sg + 1]; continue; }   // (wide runs come first)
-            seen_narrow = true;
-            const int cpw = 64 / G;
-            const long chains = static_cast<long>(k2_plan.seg_slot[sg + 1] - k2_plan.seg_slot[sg]) * p.noChains;
-            const long waves = (chains + cpw - 1) / cpw;
-            ok = waves < (1L << 20) && sg < 2048;
-            for (long w = 0; w < waves && ok; w++) {
-              const int first = nd[k2_plan.seg_slot[sg] + static_cast<int>((w * cpw) / p.noChains)];   // the wavefront's longest chain
-              ws.push_back(W{cost.wave_step(G, first), static_cast<int32_t>(sg << 20 | static_cast<int32_t>(w))});
-            }
-          }
-          if (ok && !ws.empty()) {
-            std::stable_sort(ws.begin(), ws.end(), [](const W &x, const W &y) { return x.cost > y.cost; });
-            const size_t N = ws.size(), Q = (N + 1) / 2, blocks = (Q + 3) / 4;
-            k2_pair_tab.assign(blocks * 8, -1);
-            for (size_t q = 0; q < Q; q++) {
-              k2_pair_tab[(q / 4) * 8 + q % 4] = ws[q].code;
-              if (N - 1 - q > q) k2_pair_tab[(q / 4) * 8 + q % 4 + 4] = ws[N - 1 - q].code;
-            }
-            k2_pair_grid = k2_pair_wide_blocks + static_cast<int>(blocks);
-            if (d_k2_pair_tab) HIP_OK(hipFree(d_k2_pair_tab));
-            HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_k2_pair_tab), k2_pair_tab.size() * sizeof(int32_t)));
-            HIP_OK(hipMemcpy(d_k2_pair_tab, k2_pair_tab.data(), k2_pair_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-          }
-        }
+        k2_pair_grid = 0; k2_pair_wide_blocks = 0;
+        if (wpb == 8) k2_pair_table(nd, cost);
       }
-      k2_multi = k2_plan.n_segs > 0;
+      q.k2_multi = k2_plan.n_segs > 0;
     }
   }
   // ---- paired-end two-isoform events of MODE 2, likewise (sampler_k2_multi<2, 4>): 4, 8, ... 64 lanes per chain as far
   // as the chains' score tables fit the workgroup's LDS, 256 lanes (the workgroup) for the largest events ----
-  bool k2w_multi = false;
-  size_t k2w_multi_lds = 0;
   {
     const char *off = std::getenv("MISO_K2_MULTI");
     if (p.paired && n_k2w > 0 && std::getenv("MISO_LANES_PER_CHAIN") == nullptr && !(off && std::atoi(off) == 0)) {
-      const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(k2w_fp) - K2_RED_BYTES;
-      const int max_cpw = static_cast<int>(std::max<long>(0, lds_left / static_cast<long>(4 * k2w_tab)));
+      const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp) - K2_RED_BYTES;
+      const int max_cpw = static_cast<int>(std::max<long>(0, lds_left / static_cast<long>(4 * q.k2w_tab)));
       const int resident = std::max(1, slots_for(static_cast<long>(n_k2w) * p.noChains) / 4);
       const long key = (static_cast<long>(resident) * 64 + p.noChains) * 256 + coop_k2w_budget + (coop_max > 1 ? 0 : 200);
       if (max_cpw >= 1 && (k2w_plan_key != key || std::getenv("MISO_K2_TARGET") || std::getenv("MISO_K2_COST") || std::getenv("MISO_COOP_MIN_QUADS") || std::getenv("MISO_K2W_WPB"))) {
@@ -1485,142 +998,913 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
         }
         k2w_plan_key = key;
       }
-      k2w_multi = max_cpw >= 1 && k2w_plan.n_segs > 0;
-      if (k2w_multi) {
+      q.k2w_multi = max_cpw >= 1 && k2w_plan.n_segs > 0;
+      if (q.k2w_multi) {
         int cpw = 1;
         for (int i = 0; i < k2w_plan.n_segs; i++)
           if (k2w_plan.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / k2w_plan.seg_lanes[i]);
-        k2w_multi_lds = align_up(k2w_fp + static_cast<size_t>(k2w_plan.wpb) * cpw * k2w_tab, 16);
+        q.k2w_multi_lds = align_up(q.k2w_fp + static_cast<size_t>(k2w_plan.wpb) * cpw * q.k2w_tab, 16);
       }
     }
   }
   // the several-rounds single-end plan has runs of one and two lanes per chain only: the kernel of three wavefronts per SIMD (kernels_k2m.inl)
-  bool k2_narrow = k2_multi && !p.paired && k2_plan.wpb == 4 && k2_plan.n_segs > 0 && std::getenv("MISO_K2_NO_NARROW") == nullptr;
-  for (int i = 0; i < k2_plan.n_segs && k2_narrow; i++) k2_narrow = k2_plan.seg_lanes[i] <= 2;
-  const std::string k2m_name = "sampler_k2_multi<" + std::string(p.paired ? "1, " : "0, ") + std::to_string(k2_plan.wpb) + (k2_narrow ? ", true>" : ">");
-  // which chain every workgroup of a plan's workgroup-wide run works on (coop.hpp); nothing to do when every chain
-  // has its workgroup to itself
-  auto k2_coop = [&](KernelArgs &ka, const LanePlan &pl, K2Coop &cc, hipStream_t st) {
-    ka.coop_tab = nullptr; ka.coop_mem = nullptr;
-    if (pl.n_segs == 0 || pl.seg_lanes[0] != K2_WIDE) return;
-    bool any = false;
-    for (int m : pl.wide_wgs) any |= m > 1;
-    if (!any) return;
-    if (cc.key != pl.seg_block[1] * 131 + static_cast<long>(pl.wide_wgs.size()) || !cc.d_tab) {
-      std::vector<int32_t> tab;
-      cc.chains = 0;
-      for (size_t e = 0; e < pl.wide_wgs.size(); e++)
-        for (int c = 0; c < p.noChains; c++) {
-          const int m = pl.wide_wgs[e];
-          for (int r = 0; r < m; r++) { tab.push_back(static_cast<int32_t>(e * p.noChains + c)); tab.push_back(r); tab.push_back(m); tab.push_back(m > 1 ? cc.chains : 0); }
-          if (m > 1) cc.chains++;
-        }
-      if (static_cast<int>(tab.size() / 4) != pl.seg_block[1]) MISO_FAIL(MISO_EINTERNAL, "lane plan and cooperative table disagree");
-      if (cc.d_tab) (void) hipFree(cc.d_tab);
-      if (cc.d_mem) (void) hipFree(cc.d_mem);
-      cc.d_tab = nullptr; cc.d_mem = nullptr;
-      HIP_OK(hipMalloc(reinterpret_cast<void **>(&cc.d_tab), tab.size() * sizeof(int32_t)));
-      HIP_OK(hipMemcpy(cc.d_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      HIP_OK(hipMalloc(reinterpret_cast<void **>(&cc.d_mem), std::max(1, cc.chains) * COOP_WORDS * sizeof(uint32_t)));
-      cc.key = pl.seg_block[1] * 131 + static_cast<long>(pl.wide_wgs.size());
-    }
-    HIP_OK(hipMemsetAsync(cc.d_mem, 0, std::max(1, cc.chains) * COOP_WORDS * sizeof(uint32_t), st));
-    ka.coop_tab = cc.d_tab; ka.coop_mem = cc.d_mem;
-  };
-  auto launch_k2_multi = [&](KernelArgs ka, hipStream_t st, bool wpart = false) {
-    k2_coop(ka, wpart ? k2w_plan : k2_plan, wpart ? k2w_coop : k2_coop_se, st);
-    if (wpart) {
-      ka.slot_event = d_slots; ka.n_slots = n_k2w;
-      ka.pair_waves = 0;
-      ka.red_off = static_cast<int32_t>(k2w_multi_lds);
-      ka.n_segs = k2w_plan.n_segs;
-      for (int i = 0; i <= k2w_plan.n_segs; i++) { ka.seg_block[i] = k2w_plan.seg_block[i]; ka.seg_slot[i] = k2w_plan.seg_slot[i]; }
-      for (int i = 0; i < k2w_plan.n_segs; i++) ka.seg_lanes[i] = k2w_plan.seg_lanes[i];
-      const int lds = static_cast<int>(k2w_multi_lds + K2_RED_BYTES);
-      const dim3 grid(static_cast<unsigned>(k2w_plan.seg_block[k2w_plan.n_segs]));
-      if (k2w_plan.wpb == 8) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_k2_multi<2, 8>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL((sampler_k2_multi<2, 8>), grid, dim3(512), lds, st, ka);
-      } else {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_k2_multi<2, 4>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        hipLaunchKernelGGL((sampler_k2_multi<2, 4>), grid, dim3(256), lds, st, ka);
-      }
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    ka.slot_event = d_slots + n_k2w; ka.n_slots = n_k2 - n_k2w;
-    ka.pair_waves = (k2_plan.rounds == 1 && k2_plan.wpb == 8) ? 1 : 0;
-    ka.red_off = 0;
-    ka.n_segs = k2_plan.n_segs;
-    for (int i = 0; i <= k2_plan.n_segs; i++) { ka.seg_block[i] = k2_plan.seg_block[i]; ka.seg_slot[i] = k2_plan.seg_slot[i]; }
-    for (int i = 0; i < k2_plan.n_segs; i++) ka.seg_lanes[i] = k2_plan.seg_lanes[i];
-    dim3 grid(static_cast<unsigned>(k2_plan.seg_block[k2_plan.n_segs]));
-    if (!p.paired && k2_plan.wpb == 8 && k2_pair_grid > 0 && !k2_pair_tab.empty()) {   // wavefronts paired across the runs
-      ka.wave_tab = d_k2_pair_tab; ka.mix_blocks = k2_pair_wide_blocks; ka.pair_waves = 0;
-      grid = dim3(static_cast<unsigned>(k2_pair_grid));
-    }
-    if (p.paired) {   // MODE 1
-      int cpw = 1;
-      for (int i = 0; i < k2_plan.n_segs; i++) if (k2_plan.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / k2_plan.seg_lanes[i]);
-      const size_t tabs = align_up(k2_fp + 4 * static_cast<size_t>(cpw) * k2_tab, 16);
-      ka.pair_waves = 0;
-      ka.red_off = static_cast<int32_t>(tabs);
-      const int lds = static_cast<int>(tabs + K2_RED_BYTES);
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_k2_multi<1, 4>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      hipLaunchKernelGGL((sampler_k2_multi<1, 4>), grid, dim3(256), lds, st, ka);
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    switch (k2_plan.wpb) {
-    case 8:
-      // the whole launch resident at once: the two wavefronts of a SIMD keep step (kernels_k2.inl k2_balance)
-      if (k2_plan.rounds == 1) ka.balance = (std::getenv("MISO_K2_BALANCE") && std::atoi(std::getenv("MISO_K2_BALANCE")) == 0) ? 0 : 1;
-      hipLaunchKernelGGL((sampler_k2_multi<0, 8>), grid, dim3(512), K2_RED_BYTES, st, ka);
-      break;
-    case 4:
-      if (k2_narrow) hipLaunchKernelGGL((sampler_k2_multi<0, 4, true>), grid, dim3(256), K2_RED_BYTES, st, ka);
-      else hipLaunchKernelGGL((sampler_k2_multi<0, 4>), grid, dim3(256), K2_RED_BYTES, st, ka);
-      break;
-    default: hipLaunchKernelGGL((sampler_k2_multi<0, 1>), grid, dim3(64), 0, st, ka); break;
-    }
-    HIP_OK(hipGetLastError());
-  };
+  q.k2_narrow = q.k2_multi && !p.paired && k2_plan.wpb == 4 && k2_plan.n_segs > 0 && std::getenv("MISO_K2_NO_NARROW") == nullptr;
+  for (int i = 0; i < k2_plan.n_segs && q.k2_narrow; i++) q.k2_narrow = k2_plan.seg_lanes[i] <= 2;
+}
 
-  auto k2_name = [&](int G, bool wpart) {
-    return "sampler_k2<" + std::to_string(G) + (p.paired ? (wpart ? ", 2, 4>" : ", 1, 4>") : (k2_pair ? ", 0, 8>" : ", 0, 4>"));
+// One round, 8 wavefronts per workgroup: wavefronts w and w + 4 of a workgroup share a SIMD.  Pair the launch's
+// wavefronts (all runs but the workgroup-wide chains') by estimated duration, the i-th heaviest with the i-th
+// lightest ACROSS the runs: within a run the p-th heaviest + p-th lightest (a.pair_waves) give every SIMD of the
+// run the same work, but the runs' sums differ (a run's first wavefront sits at the planner's bound, its last
+// wherever the next width takes over) and the SIMDs of the lighter runs idle at the end (wave-slot occupancy
+// 0.78, profiles/r03_wave_time.txt).  Measured, 40 000 events: hg19-like read counts (13 runs) 73.9 -> 71.4 ms;
+// 1000 reads each (4 runs) 99.7 -> 100.8 ms, 3000 reads 244.6 -> 250.0 ms (few runs: their sums are close already,
+// and the kernel with a body per run AND per wavefront is larger): used from seven runs on.
+// MISO_K2_GLOBAL_PAIR=0 / 1: never / always (A/B, tests).
+void miso_batch::k2_pair_table(const std::vector<int> &nd, const LaneCost &cost) {
+  const char *gp = std::getenv("MISO_K2_GLOBAL_PAIR");
+  if (!(k2_plan.n_segs > 0 && k2_plan.rounds == 1 && (gp ? std::atoi(gp) != 0 : k2_plan.n_segs >= 7))) return;
+  struct W { double cost; int32_t code; };
+  std::vector<W> ws;
+  bool ok = true, seen_narrow = false;
+  for (int sg = 0; sg < k2_plan.n_segs && ok; sg++) {
+    const int G = k2_plan.seg_lanes[sg];
+    if (G == K2_WIDE) { ok = !seen_narrow; k2_pair_wide_blocks = k2_plan.seg_block[sg + 1]; continue; }   // (wide runs come first)
+    seen_narrow = true;
+    const int cpw = 64 / G;
+    const long chains = static_cast<long>(k2_plan.seg_slot[sg + 1] - k2_plan.seg_slot[sg]) * p.noChains;
+    const long waves = (chains + cpw - 1) / cpw;
+    ok = waves < (1L << 20) && sg < 2048;
+    for (long w = 0; w < waves && ok; w++) {
+      const int first = nd[k2_plan.seg_slot[sg] + static_cast<int>((w * cpw) / p.noChains)];   // the wavefront's longest chain
+      ws.push_back(W{cost.wave_step(G, first), static_cast<int32_t>(sg << 20 | static_cast<int32_t>(w))});
+    }
+  }
+  if (!ok || ws.empty()) return;
+  std::stable_sort(ws.begin(), ws.end(), [](const W &x, const W &y) { return x.cost > y.cost; });
+  const size_t N = ws.size(), Q = (N + 1) / 2, blocks = (Q + 3) / 4;
+  std::vector<int32_t> tab(blocks * 8, -1);
+  for (size_t q = 0; q < Q; q++) {
+    tab[(q / 4) * 8 + q % 4] = ws[q].code;
+    if (N - 1 - q > q) tab[(q / 4) * 8 + q % 4 + 4] = ws[N - 1 - q].code;
+  }
+  k2_pair_grid = k2_pair_wide_blocks + static_cast<int>(blocks);
+  put(k2_pair_tab, tab);
+}
+
+void miso_batch::launch_k2(KernelArgs ka, int G, hipStream_t st, bool wpart) {
+  const int first = wpart ? 0 : n_k2w, count = wpart ? n_k2w : n_k2 - n_k2w;
+  const long chains = static_cast<long>(count) * p.noChains;
+  if (chains <= 0) return;
+  ka.slot_event = d_slots + first; ka.n_slots = count;
+  const int cpw = 64 / std::max(G, 1);
+  const long waves = (chains + cpw - 1) / cpw;
+  // single-end: workgroups of 8 wavefronts = one CU's resident slots; the two wavefronts of a SIMD
+  // take a heavy and a light group of chains (sampler_k2's WPB = 8).  MISO_K2_PAIR=0: the 4-wavefront
+  // workgroups in slot order (round-1 behaviour).
+  const bool pair = plan.k2_pair;
+  ka.pair_waves = pair ? 1 : 0;
+  const unsigned grid = static_cast<unsigned>(pair ? (waves + 7) / 8 : (waves + 3) / 4);
+  const size_t k2_lds = (wpart ? plan.k2w_fp : plan.k2_fp) + 4 * static_cast<size_t>(cpw) * (wpart ? plan.k2w_tab : plan.k2_tab);
+  if (k2_lds > 160 * 1024) MISO_FAIL(MISO_UNIMPLEMENTED, "Fragment-length distribution too wide for the two-isoform paired-end kernel");
+  const void *f = p.paired ? (wpart ? k2_kernel<2, 4>(G) : k2_kernel<1, 4>(G)) : (pair ? k2_kernel<0, 8>(G) : k2_kernel<0, 4>(G));
+  launch_kernel(f, grid, !p.paired && pair ? 512 : 256, k2_lds, st, ka);
+}
+
+void miso_batch::launch_k2_mix(KernelArgs ka, hipStream_t st) {
+  const int first = n_k2w, count = n_k2 - n_k2w, C = p.noChains, G = plan.k2_G, cpwB = 64 / G;
+  ka.slot_event = d_slots + first; ka.n_slots = count;
+  ka.pair_waves = 1; ka.mix_slots = plan.k2_mix; ka.mix_blocks = plan.k2_mix_blocks;
+  const long wavesB = (static_cast<long>(count - plan.k2_mix) * C + cpwB - 1) / cpwB;
+  launch_kernel(k2_mix_kernel(G), static_cast<unsigned>(plan.k2_mix_blocks + (wavesB + 7) / 8), 512, 0, st, ka);
+}
+
+// which chain every workgroup of a plan's workgroup-wide run works on (coop.hpp); nothing to do when every chain
+// has its workgroup to itself
+void miso_batch::k2_coop(KernelArgs &ka, const LanePlan &pl, CoopTable &cc, hipStream_t st) {
+  ka.coop_tab = nullptr; ka.coop_mem = nullptr;
+  if (pl.n_segs == 0 || pl.seg_lanes[0] != K2_WIDE) return;
+  bool any = false;
+  for (int m : pl.wide_wgs) any |= m > 1;
+  if (!any) return;
+  const long key = pl.seg_block[1] * 131 + static_cast<long>(pl.wide_wgs.size());
+  if (cc.tab.key != key || !cc.tab.d) {
+    std::vector<int32_t> tab;
+    cc.chains = 0;
+    for (size_t e = 0; e < pl.wide_wgs.size(); e++)
+      for (int c = 0; c < p.noChains; c++) {
+        const int m = pl.wide_wgs[e];
+        for (int r = 0; r < m; r++) { tab.push_back(static_cast<int32_t>(e * p.noChains + c)); tab.push_back(r); tab.push_back(m); tab.push_back(m > 1 ? cc.chains : 0); }
+        if (m > 1) cc.chains++;
+      }
+    if (static_cast<int>(tab.size() / 4) != pl.seg_block[1]) MISO_FAIL(MISO_EINTERNAL, "lane plan and cooperative table disagree");
+    put(cc.tab, tab);
+    put(cc.mem, {}, static_cast<size_t>(std::max(1, cc.chains)) * COOP_WORDS);
+    cc.tab.key = key;
+  }
+  HIP_OK(hipMemsetAsync(cc.mem.d, 0, std::max(1, cc.chains) * COOP_WORDS * sizeof(uint32_t), st));
+  ka.coop_tab = cc.tab.d; ka.coop_mem = cc.mem.d;
+}
+
+void miso_batch::launch_k2_multi(KernelArgs ka, hipStream_t st, bool wpart) {
+  const LanePlan &pl = wpart ? k2w_plan : k2_plan;
+  k2_coop(ka, pl, wpart ? k2w_coop : k2_coop_se, st);
+  ka.slot_event = d_slots + (wpart ? 0 : n_k2w); ka.n_slots = wpart ? n_k2w : n_k2 - n_k2w;
+  ka.n_segs = pl.n_segs;
+  for (int i = 0; i <= pl.n_segs; i++) { ka.seg_block[i] = pl.seg_block[i]; ka.seg_slot[i] = pl.seg_slot[i]; }
+  for (int i = 0; i < pl.n_segs; i++) ka.seg_lanes[i] = pl.seg_lanes[i];
+  unsigned grid = static_cast<unsigned>(pl.seg_block[pl.n_segs]);
+  if (wpart) {   // MODE 2
+    ka.pair_waves = 0;
+    ka.red_off = static_cast<int32_t>(plan.k2w_multi_lds);
+    launch_kernel(k2_multi_kernel(2, pl.wpb, false), grid, pl.wpb == 8 ? 512 : 256, plan.k2w_multi_lds + K2_RED_BYTES, st, ka);
+    return;
+  }
+  ka.pair_waves = (pl.rounds == 1 && pl.wpb == 8) ? 1 : 0;
+  ka.red_off = 0;
+  if (!p.paired && pl.wpb == 8 && k2_pair_grid > 0 && !k2_pair_tab.host.empty()) {   // wavefronts paired across the runs
+    ka.wave_tab = k2_pair_tab.d; ka.mix_blocks = k2_pair_wide_blocks; ka.pair_waves = 0;
+    grid = static_cast<unsigned>(k2_pair_grid);
+  }
+  if (p.paired) {   // MODE 1
+    int cpw = 1;
+    for (int i = 0; i < pl.n_segs; i++) if (pl.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / pl.seg_lanes[i]);
+    const size_t tabs = align_up(plan.k2_fp + 4 * static_cast<size_t>(cpw) * plan.k2_tab, 16);
+    ka.pair_waves = 0;
+    ka.red_off = static_cast<int32_t>(tabs);
+    launch_kernel(k2_multi_kernel(1, 4, false), grid, 256, tabs + K2_RED_BYTES, st, ka);
+    return;
+  }
+  // the whole launch resident at once: the two wavefronts of a SIMD keep step (kernels_k2.inl k2_balance)
+  if (pl.wpb == 8 && pl.rounds == 1) ka.balance = (std::getenv("MISO_K2_BALANCE") && std::atoi(std::getenv("MISO_K2_BALANCE")) == 0) ? 0 : 1;
+  const int wpb = pl.wpb == 8 || pl.wpb == 4 ? pl.wpb : 1;
+  launch_kernel(k2_multi_kernel(0, wpb, plan.k2_narrow), grid, 64 * wpb, wpb == 1 ? 0 : K2_RED_BYTES, st, ka);
+}
+
+// collapsed single-end batch: one chain per lane, no read loop (kernels_lane.hip)
+void miso_batch::launch_lane(KernelArgs ka, hipStream_t st) {
+  ka.slot_event = d_slots; ka.n_slots = n_k2; ka.pair_waves = 0;
+  ka.logfact = logfact.d; ka.tstride = static_cast<int32_t>(logfact.host.size());   // (tstride: the table's entries, for sampler_lane_ilp's LDS copy)
+  const long chains = static_cast<long>(n_k2) * p.noChains;
+  const int G = plan.lane_G;
+  unsigned grid = static_cast<unsigned>(((chains + 64 / G - 1) / (64 / G) + 3) / 4);
+  if (G == 1) {
+    grid = static_cast<unsigned>((chains + 255) / 256);
+    // fewer wavefronts than SIMDs (or than two per SIMD): spread the chains over all of them (kernels_lane.hip lane_body)
+    const long simds = wave_slots / 2, waves = (chains + 63) / 64;
+    const char *sp = std::getenv("MISO_LANE_SPREAD");   // 0: never; n: n wavefronts per SIMD (experiments)
+    const int per_simd = sp ? std::atoi(sp) : 1;
+    if (plan.lane_ilp && per_simd > 0 && waves < simds * per_simd && chains >= 64) {
+      const long target = simds * per_simd;
+      const int cpw = static_cast<int>((chains + target - 1) / target);
+      if (cpw >= 8 && cpw < 64) { ka.pair_waves = cpw; grid = static_cast<unsigned>(((chains + cpw - 1) / cpw + 3) / 4); }
+    }
+  }
+  launch_kernel(lane_kernel(G, plan.lane_ilp), grid, 256, 0, st, ka);
+}
+
+// ---- more than two isoforms: sampler_grp<G, PE, KC> per isoform-count class ----
+int miso_batch::fp_rows(const GenRun &run) const { return (p.paired && plan.dense_env && run.dense) ? 1 : 0; }
+size_t miso_batch::fp_bytes_of(const GenRun &run) const {
+  return fp_rows(run) ? align_up(static_cast<size_t>(plan.il2) * 8, 16) : plan.fp_plain;
+}
+GrpShape miso_batch::grp_shape(const GenRun &run) const {
+  const size_t fp_bytes = fp_bytes_of(run);
+  // single-end: per-class thresholds join the slice (class path) when every event has a class
+  // table; MISO_NO_CLASS_PATH=1 (tests): force the direct mask path of sampler_grp
+  const bool no_cls = std::getenv("MISO_NO_CLASS_PATH") != nullptr;
+  int qs = (!p.paired && !no_cls && !run.nocls && run.maxcls > 0) ? run.maxcls : 0;
+  if (qs && 4 * 2 * static_cast<size_t>(grp_slice_bytes(run.kmax, qs, 0)) > plan.lds_max) qs = 0;
+  // paired-end: the per-event score table (K x il int32) joins the slice when >= 4 chains still fit
+  int ts = p.paired ? run.kmax * (fp_rows(run) ? plan.il2 : static_cast<int>(fd.prob.size())) : 0;
+  if (ts && fp_bytes + 4 * 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, ts)) > plan.lds_max) ts = 0;
+  return GrpShape{qs, ts};
+}
+bool miso_batch::grp_fits(const GenRun &run, const GrpShape &sh, int G) const {
+  const size_t fp_bytes = fp_bytes_of(run);
+  return G >= 2 && G <= 32 && !(G & (G - 1)) &&
+         fp_bytes + 4 * static_cast<size_t>(64 / G) * grp_slice_bytes(run.kmax, sh.qs, sh.ts) <= plan.lds_max;
+}
+// runs [r0, r1) (consecutive in the list) as one
+miso_batch::GenRun miso_batch::joined_run(size_t r0, size_t r1) const {
+  GenRun m;
+  m.first = gen_runs[r0].first; m.count = 0; m.kc = gen_runs[r0].kc;
+  for (size_t ri = r0; ri < r1; ri++) {
+    const GenRun &run = gen_runs[ri];
+    m.count += run.count; m.kmax = std::max(m.kmax, run.kmax); m.kmin = std::min(m.kmin, run.kmin); m.maxq = std::max(m.maxq, run.maxq);
+    m.maxcls = std::max(m.maxcls, run.maxcls); m.nocls = m.nocls || run.nocls; m.dense = m.dense && run.dense;
+  }
+  return m;
+}
+
+// Workgroup-wide chains of a run: which chain every workgroup works on (coop.hpp), built once per batch; returns the
+// number of workgroups.
+unsigned miso_batch::wide_setup(GenRun &run, long chains, hipStream_t st) {
+  // Workgroups per chain: what upload() derived from the gene's share of the batch's work (coop_n), at most
+  // COOP_MAX_N, all cooperative workgroups of the batch together at most COOP_MAX_WGS (coop.hpp: they must all be
+  // resident at once).  MISO_NO_COOP=1: one workgroup per chain; MISO_COOP_DRAWS=n: one per n drawing pairs (tests).
+  CoopTable &cc = run.coop;
+  if (!cc.tab.d) {
+    std::vector<int32_t> tab;
+    cc.chains = 0;
+    const bool coop_on = coop_enabled();
+    const int per_wg = std::getenv("MISO_COOP_DRAWS") ? std::max(256, std::atoi(std::getenv("MISO_COOP_DRAWS"))) : 8192;
+    for (long c = 0; c < chains; c++) {
+      const int ev_i = h_slots[n_k2 + run.first + c / p.noChains];
+      const int nd = events[ev_i].n_draw;
+      int nw = !coop_on ? 1 : (std::getenv("MISO_COOP_DRAWS") ? std::min(COOP_MAX_N, std::max(1, (nd + per_wg - 1) / per_wg)) : coop_n[ev_i]);
+      if (nw > 1 && coop_wgs_used + nw > coop_gen_budget) nw = std::max(1, coop_gen_budget - coop_wgs_used);
+      if (nw > 1) coop_wgs_used += nw;
+      for (int r = 0; r < nw; r++) {
+        tab.push_back(static_cast<int32_t>(c)); tab.push_back(r); tab.push_back(nw);
+        tab.push_back(nw > 1 ? cc.chains : 0);
+      }
+      if (nw > 1) cc.chains++;
+    }
+    if (std::getenv("MISO_TIMING")) {
+      std::fprintf(stderr, "[miso] wide run kc=%d: %ld chains on %zu workgroups (%d on several:", run.kc, chains, tab.size() / 4, cc.chains);
+      for (size_t i = 0; i < tab.size(); i += 4)
+        if (tab[i + 1] == 0 && tab[i + 2] > 1)
+          std::fprintf(stderr, " %d x %d draws K=%d", tab[i + 2], events[h_slots[n_k2 + run.first + tab[i] / p.noChains]].n_draw,
+                       events[h_slots[n_k2 + run.first + tab[i] / p.noChains]].K);
+      std::fprintf(stderr, ")\n");
+    }
+    put(cc.tab, tab);
+    put(cc.mem, {}, static_cast<size_t>(std::max(1, cc.chains)) * COOP_WORDS);
+  }
+  HIP_OK(hipMemsetAsync(cc.mem.d, 0, std::max(1, cc.chains) * COOP_WORDS * sizeof(uint32_t), st));
+  return static_cast<unsigned>(cc.tab.host.size() / 4);
+}
+
+void miso_batch::launch_grp(KernelArgs ka, GenRun &run, const GrpShape &sh, int G, hipStream_t st) {
+  const long chains = static_cast<long>(run.count) * p.noChains;
+  ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count;
+  ka.kstride = run.kmax; ka.cstride = sh.qs; ka.tstride = sh.ts;
+  const bool wave_kernel = G == 64 && !run.wide && !(run.wave64 && fp_rows(run));   // sampler_wave, not sampler_grp<64, ..>
+  ka.pe_dense = wave_kernel ? 0 : fp_rows(run);
+  ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
+  const size_t fp_bytes = wave_kernel ? plan.fp_plain : fp_bytes_of(run);
+  if (run.wide) {   // one chain per workgroup: four slices (one per wavefront) + the reduction scratch behind them
+    ka.pe_dense = fp_rows(run);
+    if (!ka.pe_dense) MISO_FAIL(MISO_EINTERNAL, "workgroup-wide paired-end chains need the dense records");
+    const size_t lds0 = align_up(fp_bytes + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, sh.ts)), 16);
+    ka.red_off = static_cast<int32_t>(lds0);
+    const unsigned grid = wide_setup(run, chains, st);
+    ka.coop_tab = run.coop.tab.d; ka.coop_mem = run.coop.mem.d;
+    launch_kernel(grp_kc<64, true, true>(run.kc), grid, 256, lds0 + 96, st, ka);
+  } else if (G == 64 && !wave_kernel) {   // a wavefront per chain, dense records (size bucket between 32 lanes and a workgroup)
+    const size_t lds = fp_bytes + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, sh.qs, sh.ts));
+    launch_kernel(grp_kc<64, true>(run.kc), static_cast<unsigned>((chains + 3) / 4), 256, lds, st, ka);
+  } else if (G == 64 && run.kc > 64) {   // 65 ... MISO_MAX_ISOFORMS isoforms: one wavefront = one workgroup per chain, vectors in LDS (kernels_big.hip)
+    const size_t lds = fp_bytes + static_cast<size_t>(run.kmax) * (11 * sizeof(double) + 2 * sizeof(int));
+    launch_kernel(p.paired ? fn(&sampler_big<true>) : fn(&sampler_big<false>), static_cast<unsigned>(chains), 64, lds, st, ka);
+  } else if (G == 64) {
+    const size_t lds = fp_bytes + 4 * 64 * sizeof(int);
+    launch_kernel(p.paired ? fn(&sampler_wave<true>) : fn(&sampler_wave<false>), static_cast<unsigned>((chains + 3) / 4), 256, lds, st, ka);
+  } else {
+    const int cpw = 64 / G;
+    const unsigned grid = static_cast<unsigned>(((chains + cpw - 1) / cpw + 3) / 4);
+    const size_t lds = fp_bytes + 4 * static_cast<size_t>(cpw) * grp_slice_bytes(run.kmax, sh.qs, sh.ts);
+    launch_kernel(grp_kernel(G, p.paired, run.kc), grid, 256, lds, st, ka);
+  }
+}
+
+// Which chains a wavefront of sampler_flat owns (kernels_flat.inl: a.wave_tab).  Uniform batches: `nc` consecutive
+// chains each.  When the batch's events differ widely in size -- the heaviest wavefront of the uniform rule would
+// carry more than twice the average wavefront's work units -- the wavefronts are packed by UNITS instead: as many
+// consecutive chains (at most nc_max: the LDS) as make about the average wavefront's units, a chain of several
+// times that alone in a WORKGROUP (FLAT_WIDE: 256 lanes), workgroups ordered heaviest first (the hardware starts
+// them in index order).  MISO_FLAT_PACK=0 / 1: never / always (tests, A/B).
+// How many units per wavefront: as many as nc_max average chains have -- the scalar step costs a wavefront the same
+// for 2 chains and for 13, so fewer, fuller wavefronts win (hg19-like read counts, 40 000 events, K = 5: 497 ms at 8
+// average chains per wavefront, 425 ms at 13+) -- unless that leaves the device part empty: fewer wavefronts than
+// resident slots, or a second round that is less than half full (K = 3: 3349 wavefronts on 3072 slots 286 ms,
+// 5704 wavefronts 270 ms); then the wavefront count goes to 0.95 x one or two rounds
+// (profiles/r03_flat_pack_sweep.txt).  A forced MISO_FLAT_NC sets the average chains per wavefront instead.
+void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, int nc_max_p, long resident_p) {
+  const long chains = static_cast<long>(run.count) * p.noChains;
+  const int C = p.noChains;
+  const char *env = std::getenv("MISO_FLAT_PACK");
+  const long key = (((static_cast<long>(nc) * 4 + (env ? 1 + (std::atoi(env) != 0) : 0)) * 128 + nc_max_u) * 128 + nc_max_p) * 1024 + (std::getenv("MISO_FLAT_PACK_OV") ? 1 + std::atol(std::getenv("MISO_FLAT_PACK_OV")) % 1000 : 0);
+  if (run.wave_tab.key == key && run.wave_tab.d) return;
+  // (round 5) what a chain costs its wavefront, in work units: its units + the scalar step and thresholds, which do not
+  // depend on the reads.  Measured per chain-iteration at eight / five chains per wavefront (profiles/r05_flat_chunks.txt):
+  // K = 5 238 VALU against 1.33 per unit, K = 10 641 against 1.96, i.e. about 30 K + 25 units -- but the wavefronts this
+  // matters for carry 14 - 18 small chains, whose flat passes and leader sections are shared by twice as many chains:
+  // 16 K + 14.  Swept on hg19-like read counts at 25 ... 300 % of the first figure: K = 3 / 4 / 6 / 8 best at 50 % (208 /
+  // 152 / 107 / 80 k events/s against 153 / 144 / 97 / 74 k at 100 %), K = 5 / 12 at 100 % (122 / 45 k against 114 / 43 k);
+  // by units alone: 151 / 112 / 55 k at K = 3 / 5 / 10.  MISO_FLAT_PACK_OV=<per cent of the rule> (0: by units alone).
+  const char *ov_env = std::getenv("MISO_FLAT_PACK_OV");
+  const long ov_pct = ov_env ? std::atol(ov_env) : 100;   // (per cent of the rule: experiments)
+  auto units_of = [&](long c) {
+    const PackedEvent &e = events[h_slots[n_k2 + run.first + c / C]];
+    return static_cast<long>(e.n_units) + (16L * e.K + 14) * ov_pct / 100;
   };
-  // ---- what goes on the device, kernel by kernel (miso_batch_launch_stats): built on demand ----
-  const LanePlan plan_copy = k2_plan, planw_copy = k2w_plan;
-  stats_builder = [=]() {
-  kernel_stats.clear();
+  long total = 0, head = 0;
+  for (long c = 0; c < chains; c++) { const long u = units_of(c); total += u; if (c < nc) head += u; }
+  long heaviest = head;   // the list is ordered by isoforms first: look at every wavefront of the uniform rule
+  for (long c = 0, sum = 0; c < chains; c++) {
+    sum += units_of(c);
+    if ((c + 1) % nc == 0 || c + 1 == chains) { heaviest = std::max(heaviest, sum); sum = 0; }
+  }
+  const double mean_wave = static_cast<double>(total) * nc / std::max<long>(1, chains);
+  const bool pack = env ? std::atoi(env) != 0 : (chains > nc && static_cast<double>(heaviest) > 2.0 * mean_wave);
+  struct W { int32_t first, n; long units; };
+  std::vector<W> waves, wides;
+  if (!pack) {
+    for (long c = 0; c < chains; c += nc) waves.push_back(W{static_cast<int32_t>(c), static_cast<int32_t>(std::min<long>(nc, chains - c)), 0});
+    run.wave_nc = nc;
+  } else {
+    // (packed launches have their own sizing: launch_flat)
+    const int nc_max = nc_max_p; const long resident = resident_p;
+    const int cap = std::min(nc_max, 255);
+    int most = 1;
+    auto pack_with = [&](double U) {
+      waves.clear(); wides.clear(); most = 1;
+      const double wide_min = std::max(3.0 * U, 2048.0);
+      for (long c = 0; c < chains;) {
+        const long u = units_of(c);
+        if (static_cast<double>(u) >= wide_min) { wides.push_back(W{static_cast<int32_t>(c), 1, u}); c++; continue; }
+        W w{static_cast<int32_t>(c), 0, 0};
+        while (c < chains && w.n < cap) {
+          const long v = units_of(c);
+          if (static_cast<double>(v) >= wide_min || (w.n > 0 && static_cast<double>(w.units + v) > 1.05 * U)) break;
+          w.units += v; w.n++; c++;
+        }
+        most = std::max(most, static_cast<int>(w.n));
+        waves.push_back(w);
+      }
+      return static_cast<long>(waves.size() + 4 * wides.size());
+    };
+    const double per_chain = static_cast<double>(total) / std::max<long>(1, chains);
+    const bool forced = std::getenv("MISO_FLAT_NC") != nullptr;
+    const long n_waves = pack_with(std::max(64.0, per_chain * (forced ? nc : cap)));
+    if (!forced && n_waves < 3 * resident / 2) {
+      // (round 6) ... and TWO rounds are aimed at from further below than one: the second round's workgroups start as the
+      // first round's end, staggered, and a count within a few per cent of two full rounds runs into a third (hg19-like read
+      // counts, K = 5, 2048 resident wavefronts: 4029 wavefronts 71.7 ms, 3793 64.6 ms, 3541 66.2 ms, 2956 -- the fullest
+      // packing -- 67.7 ms; profiles/r06_flat_pack_rounds.txt).  MISO_FLAT_ROUNDS_FRAC: the fraction of two rounds (experiments).
+      const bool two = n_waves > resident;
+      const double frac2 = std::getenv("MISO_FLAT_ROUNDS_FRAC") ? std::atof(std::getenv("MISO_FLAT_ROUNDS_FRAC")) : 0.85;
+      const double want = (two ? frac2 : 0.95) * static_cast<double>(two ? 2 * resident : resident);
+      if (static_cast<double>(n_waves) < want) {
+        // (round 5) ... and not a few wavefronts MORE than the round(s): the packing's bound is a target, the count it
+        // makes lands some per cent off, and 3110 wavefronts on 3072 slots cost a second round for 38 of them
+        // (K = 3, hg19-like read counts: 154 k events/s there, 212 k at 2960; profiles/r05_flat_chunks.txt)
+        const long target = two ? static_cast<long>((frac2 + 0.04) * 2.0 * static_cast<double>(resident)) : resident;
+        double U2 = std::max(64.0, static_cast<double>(total) / want);
+        long n2 = pack_with(U2);
+        for (int it = 0; it < 8 && n2 > target; it++) {
+          const long before = n2;
+          U2 *= static_cast<double>(n2) / (0.97 * static_cast<double>(target));
+          n2 = pack_with(U2);
+          if (n2 >= before) break;   // the chains per wavefront are at the LDS's limit: fuller wavefronts are not to be had
+        }
+      }
+    }
+    if (std::getenv("MISO_TIMING"))
+      std::fprintf(stderr, "[flat_waves] kc %d chains %ld cost/chain %.1f cap %d resident %ld first pack %ld waves -> %zu waves + %zu wide, most chains %d\n",
+                   run.kc, chains, per_chain, cap, resident, n_waves, waves.size(), wides.size(), most);
+    std::stable_sort(wides.begin(), wides.end(), [](const W &x, const W &y) { return x.units > y.units; });
+    std::stable_sort(waves.begin(), waves.end(), [](const W &x, const W &y) { return x.units > y.units; });
+    run.wave_nc = most;
+  }
+  std::vector<int32_t> tab;
+  for (const W &w : wides) for (int i = 0; i < 4; i++) { tab.push_back(w.first); tab.push_back(1 | FLAT_WIDE); }
+  for (const W &w : waves) { tab.push_back(w.first); tab.push_back(w.n); }
+  while ((tab.size() / 2) % 4) { tab.push_back(0); tab.push_back(0); }   // padding wavefronts
+  run.wave_wide = static_cast<int>(wides.size());
+  run.wave_packed = pack;
+  put(run.wave_tab, tab, 2);
+  run.wave_tab.key = key;
+}
+
+void miso_batch::launch_flat(KernelArgs ka, size_t ri, hipStream_t st) {
+  GenRun &run = gen_runs[ri];
+  const int nc = plan.runs[ri].flat_nc, nc_max = plan.runs[ri].flat_nc_max;
+  {
+    const long chains = static_cast<long>(run.count) * p.noChains;
+    const int wgs = std::getenv("MISO_FLAT_WGS") ? std::max(1, std::atoi(std::getenv("MISO_FLAT_WGS"))) : flat_wgs_for(run.kc);
+    // Five to eight isoforms: the kernel's registers allow three workgroups per CU; launches of like-sized events are sized for
+    // two (fuller wavefronts: K = 6 312 against 333 ms, K = 7 347 / 366), launches packed by cost for three -- more, smaller
+    // wavefronts level the heavy tail better than fuller ones amortise the scalar step (hg19-like read counts, 40 000 events:
+    // K = 5 276 -> 252 ms, K = 6 332 -> 278, K = 7 379 -> 339, K = 8 415 -> 393; profiles/r06_flat_licm.txt)
+    int wgs_p = wgs, nc_max_p = nc_max;
+    if (run.kc == 8 && std::getenv("MISO_FLAT_WGS") == nullptr && std::getenv("MISO_LDS_MAX_KB") == nullptr && std::getenv("MISO_FLAT_PACK_WGS2") == nullptr) {
+      wgs_p = 3;
+      const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
+      nc_max_p = std::max(1, std::min<int>(64, static_cast<int>(160 * 1024 / (4 * wgs_p) - 64) / slice));
+    }
+    flat_waves(run, nc, nc_max, std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs / 2),
+               nc_max_p, std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs_p / 2));
+  }
+  ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count;
+  ka.kstride = run.kmax; ka.cstride = std::max(run.maxcls, 1); ka.tstride = 0; ka.nc = run.wave_nc;
+  ka.wave_tab = run.wave_tab.d;
+  // the descriptor read loop from four isoforms on (three: the walking loop is 2 % faster -- two thresholds per unit,
+  // little to save) and whenever a chain owns a whole workgroup; MISO_FLAT_NO_DESC=1: the walking loop everywhere
+  // (A/B, tests; not with workgroup-wide chains)
+  ka.flat_desc = ((std::getenv("MISO_FLAT_NO_DESC") == nullptr && run.kmax >= 4) || run.wave_wide > 0) ? 1 : 0;
+  // Thresholds only for the chains whose psi changed (kernels_flat.inl): the pass is one lane per (chain, class) and the
+  // Metropolis-Hastings step rejects 45 - 65 % of the proposals, but numbering the chains that accepted costs every lane
+  // a few instructions -- it pays where the thresholds weigh enough: from six isoforms on (K = 6 ... 12: + 4.5 ... 6.4 %)
+  // and for small events (hg19-like read counts at K = 5: + 5.5 %; 1000 reads per event at K = 3 ... 5: - 1 ... 2 %,
+  // profiles/r04_occupancy.txt).  MISO_FLAT_THR_SKIP=0 / 1: never / always (A/B, tests).
+  {
+    double units = 0;
+    for (int j = 0; j < run.count; j++) units += events[h_slots[n_k2 + run.first + j]].n_units;
+    const char *env = std::getenv("MISO_FLAT_THR_SKIP");
+    ka.flat_thr_skip = env ? (std::atoi(env) != 0) : (run.kmax >= 6 || units < 150.0 * run.count);
+  }
+  const unsigned grid = static_cast<unsigned>(run.wave_tab.host.size() / 8);
+  const size_t lds = 4 * static_cast<size_t>(run.wave_nc) * flat_layout(ka.kstride, ka.cstride).bytes;
+  // Priority by progress (device.hpp prio_by_progress) when the launch takes several rounds of like-sized wavefronts:
+  // 40 000 events x 1000 reads, K = 5 348.0 -> 334.4 ms, K = 10 649.4 -> 631.4 ms, same box; wavefronts packed by cost
+  // (hg19-like read counts) lose 1 % and keep the arbiter's own order; so do the paired-end and the two-isoform kernels
+  // (+ 0.5 ... 4 %: profiles/r06_prio_by_progress.txt).  MISO_PRIO_QUARTILES=0 / 1: never / everywhere (A/B).
+  if (std::getenv("MISO_PRIO_QUARTILES") == nullptr && !run.wave_packed && run.wave_wide == 0 &&
+      static_cast<long>(grid) * 4 > static_cast<long>(slots_for(static_cast<long>(run.count) * p.noChains)) * flat_wgs_for(run.kc) / 2)
+    ka.balance = 2;
+  launch_kernel(flat_kernel(run.kc, plan.runs[ri].flat_ks, plan.runs[ri].flat_uni), grid, 256, lds, st, ka);
+}
+
+// ---- the general runs: sampler_lane_k, sampler_flat or sampler_grp, and the lanes per chain ----
+void miso_batch::plan_runs(const KernelArgs &a) {
+  LaunchPlan &q = plan;
+  q.runs.assign(gen_runs.size(), LaunchPlan::Run{});
+  // collapsed single-end batches (miso_batch_set_collapsed): the events with three and more isoforms in ONE launch of
+  // sampler_lane_k (kernels_lane.hip), provided every one of them has its class table
+  // (level 2 only: with the classes of a five- or ten-isoform event sharing ~1000 reads the chains of small binomials
+  // cost more than the read sweep they replace -- profiles/r03_collapsed.txt; it pays from ~10^4 reads per event)
+  // The route is decided per run (ADVICE r5): a class whose events all have their class tables takes sampler_lane_k, a
+  // run without them -- or of 33 isoforms and more: several mask words, sampler_wave / sampler_big only -- keeps the
+  // per-read kernels: its events are sampled per read, i.e. equal the CPU checker's COUNTER mode
+  // (tests/test_gpu_collapsed.py).
+  if (collapsed && collapsed_level >= 2 && !p.paired && n_gen > 0)
+    for (size_t ri = 0; ri < gen_runs.size(); ri++) {
+      q.runs[ri].lane = !(gen_runs[ri].nocls || gen_runs[ri].kc >= 64);
+      q.lane_gen |= q.runs[ri].lane;
+    }
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) plan_flat(ri);
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) plan_grp(ri, a);
+}
+
+// single-end runs whose events all have a class table go to sampler_flat (kernels_flat.inl): NC chains
+// per wavefront, as many as fit the wavefront's share of the LDS (two workgroups of four wavefronts
+// per CU: 20 KB each), fewer when the batch would not fill the device otherwise.
+// MISO_NO_FLAT=1: sampler_grp as in round 1 (A/B, tests); MISO_FLAT_NC=n forces the chains per wavefront.
+void miso_batch::plan_flat(size_t ri) {
+  const GenRun &run = gen_runs[ri];
+  LaunchPlan::Run &r = plan.runs[ri];
+  // up to twenty isoforms the kernel of the launch's largest isoform count (its slice layout at compile time,
+  // kernels_flat.inl); MISO_FLAT_NO_KS=1: the run-time layout everywhere (A/B, tests)
+  const int lo = run.kc == 4 ? 3 : (run.kc == 8 ? 5 : (run.kc == 12 ? 9 : (run.kc == 16 ? 13 : 17)));
+  r.flat_ks = (run.kc <= 32 && run.kmax >= lo && run.kmax <= std::min(run.kc, 20) && std::getenv("MISO_FLAT_NO_KS") == nullptr) ? run.kmax : 0;
+  // ... and, when every event of the launch has that count, the kernel that knows it (UNI: no per-chain `k < K` masks)
+  r.flat_uni = r.flat_ks > 0 && run.kmin == run.kmax && std::getenv("MISO_FLAT_NO_UNI") == nullptr;
+  if (r.lane) return;
+  if (p.paired || run.nocls || run.kc >= 64 || std::getenv("MISO_NO_FLAT") != nullptr) return;
+  const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
+  // workgroups per CU the chains per wavefront are sized for: kernels_flat.inl's register budgets -- 3 up to four isoforms
+  // and for nine to twelve (measured round 4, profiles/r04_occupancy.txt), 2 otherwise (five to eight isoforms: the kernel
+  // allows 3, sizing for 3 gained nothing); MISO_FLAT_WGS overrides
+  const int wgs = std::getenv("MISO_FLAT_WGS") ? std::max(1, std::atoi(std::getenv("MISO_FLAT_WGS"))) : flat_wgs_for(run.kc);
+  const size_t lds_wave = std::getenv("MISO_LDS_MAX_KB") ? plan.lds_max / 4 : static_cast<size_t>(160 * 1024 / (4 * wgs)) - 64;
+  const int nc_max = std::min<int>(64, static_cast<int>(lds_wave) / slice);
+  if (nc_max < 1) return;
+  const long chains = static_cast<long>(run.count) * p.noChains;
+  // the fewest rounds of resident wavefronts that nc_max allows, then the fewest chains per wavefront
+  // that still makes that many rounds (a 40 000-chain batch at nc_max = 17 would run 1.15 rounds = 2)
+  const long slots = std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs / 2);
+  const long rounds = std::max<long>(1, (chains + slots * nc_max - 1) / (slots * nc_max));
+  int nc = static_cast<int>(std::min<long>(nc_max, std::max<long>(1, (chains + slots * rounds - 1) / (slots * rounds))));
+  // five to eight isoforms: how the 64 lanes divide over a wavefront's chains and items matters more than the
+  // rounds -- measured on one device, 40 000 events (events/s at 5 / 6 / 7 / 8 / 10 chains per wavefront):
+  // K=6 69.4k / 67.5k / 72.2k / 77.2k / 68.6k, K=7 64.1k / 61.4k / 68.8k / 73.5k / 64.3k, K=8 55.8k / 57.1k /
+  // 52.6k / 55.1k / 54.4k; K=5: 8 -> 93.4k, 7 -> 90.3k, 10 -> 86.8k.  (Timing the candidates on the first launch
+  // was tried: a 7 % difference is inside the noise of a 200-iteration trial, the choice flipped between runs.)
+  if (run.kc == 8) nc = std::min(nc, run.kmin >= 8 ? 6 : 8);
+  if (run.kc == 4 && run.kmin >= 4) nc = std::min(nc, 8);   // four isoforms, descriptor loop: 8 -> 119.8k, 16 -> 116.1k, 13 -> 85.5k
+  if (const char *env = std::getenv("MISO_FLAT_NC")) nc = std::max(1, std::min(nc_max, std::atoi(env)));
+  r.flat_nc = nc; r.flat_nc_max = nc_max;
+}
+
+void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
+  GenRun &run = gen_runs[ri];
+  LaunchPlan::Run &r = plan.runs[ri];
+  if (r.lane) return;
+  if (run.kc >= 64) { r.flat_nc = 0; r.G = 64; r.sh = GrpShape{0, 0}; return; }   // more than 32 isoforms: one wavefront per chain
+  // sampler_flat or sampler_grp?  Measured on the batch's first launch like the lanes per chain below
+  // (flat wins at every isoform count of profiles/r02_flat_vs_grp_sweep.txt but 5); a small or untuned
+  // batch takes sampler_flat.
+  const bool contest = r.flat_nc > 0 && plan.tune_runs && static_cast<long>(run.count) * p.noChains >= 2048 &&
+                       run.tuned_flat < 0 && std::getenv("MISO_FLAT_NC") == nullptr;
+  if (r.flat_nc > 0 && run.tuned_flat == 0) r.flat_nc = 0;
+  if (r.flat_nc > 0 && !contest) return;
+  GrpShape &sh = r.sh = grp_shape(run);
+  const long chains = static_cast<long>(run.count) * p.noChains;
+  int G = 64;
+  if (run.wide) {   // one chain per workgroup (launch_grp): the score table joins the slice when four of them fit
+    GrpShape w{0, 0};
+    w.ts = run.kmax * plan.il2;
+    if (fp_bytes_of(run) + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, w.ts)) + 64 > plan.lds_max) w.ts = 0;
+    r.sh = w;
+    r.G = 64;
+    return;
+  }
+  if (const char *env = std::getenv("MISO_GENERAL_LANES")) {
+    G = std::atoi(env);
+  } else if (const char *envc = std::getenv("MISO_GENERAL_LANES_BY_CLASS")) {   // experiments: "4:16,8:16,12:32,16:32,32:32"
+    G = 16;
+    for (const char *s = envc; s && *s;) {
+      int kc = 0, g = 0;
+      if (std::sscanf(s, "%d:%d", &kc, &g) == 2 && kc == run.kc) G = g;
+      s = std::strchr(s, ',');
+      if (s) s++;
+    }
+  } else if (run.tuned_G) {
+    G = run.tuned_G;
+    if (p.paired && sh.ts && !grp_fits(run, sh, G)) {   // chosen with the score tables in global memory (the eight-lane rule below)
+      GrpShape s0 = sh;
+      s0.ts = 0;
+      if (grp_fits(run, s0, G)) sh = s0;
+    }
+  } else {
+    // rule of thumb.  single-end: the per-iteration scalar step costs the same per wavefront
+    // whatever G is, so pack as many chains per wavefront as still fills the device: the smallest
+    // G whose wavefronts occupy every resident slot; a batch too small for that takes the largest.
+    // paired-end: the read loop waits on memory and more wavefronts hide it: largest G up to 16; 32 from
+    // nine isoforms on (measured, pe_dense: K=10 19.5k -> 19.9k, K=20 7.35k -> 7.57k events/s; K=5 29.9k ->
+    // 28.9k, K=3 53k -> 46k) and whenever 16 would leave the kernel's share of the device unfilled.
+    bool found = false;
+    // (a whole-gene mix -- several classes side by side -- runs 9 % faster with 32 everywhere: 14.4k -> 15.7k genes/s)
+    // (round 3, 20 000 events of one isoform count: 16 lanes beat 32 from nine isoforms on as well once the launch
+    // is more than a round and a half of wavefronts -- K = 9 21.3k -> 26.8k, K = 10 20.8k -> 26.9k, K = 12 19.1k ->
+    // 22.5k, K = 16 14.4k -> 16.6k, K = 20 10.7k -> 10.9k events/s; the mix keeps 32: 16.8k vs 14.2k genes/s;
+    // profiles/r03_pe_lanes_sweep.txt)
+    int n_classes = 0;
+    for (size_t rj = 0; rj < gen_runs.size(); rj++) if (rj == 0 || gen_runs[rj].kc != gen_runs[rj - 1].kc) n_classes++;
+    // (round 3, 8 hardware queues, 16 384 genes of 3-20 isoforms per 1500 iterations: 16 lanes up to 16 isoforms against 32
+    // everywhere -- 400 pairs per gene 120 vs 150 ms, 1000 pairs 194 vs 206 ms, hg19-like counts 176 vs 175 ms, 2500 pairs
+    // 436 vs 367 ms: small genes share the scalar step four to a wavefront, large ones want the lanes; the switch sits at a
+    // mean of 400 drawing quads per gene of the class; MISO_PE_MIX_LANES=16|32 forces)
+    const double mean_q = run.sum_q / std::max(1, run.count);
+    const char *mixl = std::getenv("MISO_PE_MIX_LANES");
+    // (round 5, same batch on one box, 7500 iterations: the 17 - 20 isoform class on 16 lanes as well -- 1000 pairs per gene
+    // 930 -> 852 ms, hg19-like pair counts 865 -> 820 ms: four chains of a wavefront share the scalar step, and the class
+    // no longer fills the device with half-efficient wavefronts for the launch's first third while the other classes
+    // wait; the bucket of "at least 32 lanes" from a need of 32 lanes instead of 24: a 20-isoform gene of 1000 pairs
+    // needs 28 by the share rule; profiles/r05_pe_mix_lanes.txt)
+    const bool mix16 = run.kc <= 32 && !run.force_G && (mixl ? std::atoi(mixl) == 16 : mean_q < 400.0);
+    const bool pe32 = p.paired && ((n_classes + (n_k2 > 0 ? 1 : 0) > 1 && !mix16) || (run.kc >= 12 && 2 * ((chains + 3) / 4) < 3 * static_cast<long>(slots_for(chains))) ||
+                                   (chains + 3) / 4 < slots_for(chains));
+    for (int g : {2, 4, 8, 16, 32}) {
+      if (p.paired && g > 16 && found && !pe32) break;
+      if (!grp_fits(run, sh, g)) continue;
+      const int cpw = 64 / g;
+      if (!found || g <= std::max(2, run.maxq)) G = g;
+      found = true;
+      if (!p.paired && (chains + cpw - 1) / cpw >= slots_for(chains)) break;
+    }
+    // Round 5, paired-end, ONE isoform-count class in the batch, five to nine isoforms, two rounds of wavefronts and more at
+    // eight lanes: EIGHT lanes per chain -- eight chains of a wavefront share the scalar step instead of four.  Rounds 2 - 4
+    // measured that slower (the read loop waited on memory and more wavefronts hid it); since the draws are ordered by
+    // fragment rows and the loop's header no longer waits for fresh gathers it wins: 40 000 events x 1000 pairs, K = 5 / 6 / 7 /
+    // 8 / 9: 45.3 -> 54.2, 41.5 -> 48.7, 40.5 -> 45.5, 38.0 -> 40.5, 30.2 -> 31.5 k events/s; K = 12: 25.7 -> 21.2 k, four lanes
+    // 33.7 k at K = 5; in a whole-gene mix, where a class is a few thousand genes, 19.2 -> 18.2 k genes/s: not there
+    // (profiles/r05_lanes_sweep.txt).  MISO_PE_LANES8=0 / 1: never / also in a mix and for the size buckets' normal run.
+    {
+      const char *l8 = std::getenv("MISO_PE_LANES8");
+      const bool single = n_classes + (n_k2 > 0 ? 1 : 0) == 1;
+      const bool want8 = l8 && std::atoi(l8) != 2 ? std::atoi(l8) != 0 : ((single || l8) && chains >= 8L * 2 * slots_for(chains));   // (2: the rule in a mix of classes too)
+      if (p.paired && want8 && G == 16 && !run.force_G && run.kmin >= 5 && run.kmax <= 9 && grp_fits(run, sh, 8)) G = 8;
+      // Three and four isoforms the same -- there the class keeps its score tables in LDS (grp_shape), which holds four
+      // chains per wavefront and no more: eight chains with the tables in global memory (an L2 line per pick) instead,
+      // K = 3 66.6 -> 78.9 k, K = 4 58.1 -> 68.0 k events/s; the tables alone are worth 2 % (16 lanes without them 65.3 /
+      // 57.0 k), four lanes lose (55.9 / 37.6 k) (profiles/r05_lanes_sweep.txt).
+      if (p.paired && want8 && G == 16 && !run.force_G && run.kmax <= 4) {
+        GrpShape sh8 = sh;
+        if (!grp_fits(run, sh8, 8)) sh8.ts = 0;
+        if (grp_fits(run, sh8, 8)) { sh = sh8; G = 8; }
+      }
+    }
+    if (plan.tune_runs && chains >= 2048 && G != 64) {
+      std::vector<int> cand{G};
+      // the rule errs on the small side (tail effect when the wavefronts do not fit one round)
+      for (int g : {G * 2, G * 4})
+        if (!p.paired && grp_fits(run, sh, g) && g <= std::max(2, 2 * run.maxq)) cand.push_back(g);
+      if (cand.size() > 1)
+        G = fastest(a, cand, [&](const KernelArgs &t, int g) { launch_grp(t, run, sh, g, stream); });
+      run.tuned_G = G;
+    }
+  }
+  if (run.force_G && G < run.force_G && std::getenv("MISO_GENERAL_LANES") == nullptr) G = run.force_G;   // size bucket (upload)
+  if (run.small && p.paired && std::getenv("MISO_GENERAL_LANES") == nullptr && std::getenv("MISO_GENERAL_LANES_BY_CLASS") == nullptr) {   // the small genes' bucket: eight chains per wavefront, score tables in global memory
+    GrpShape sh8 = sh;
+    sh8.ts = 0;
+    if (grp_fits(run, sh8, 8)) { sh = sh8; G = 8; }
+  }
+  // a forced (or odd) choice never exceeds the LDS budget: fewer chains per wavefront instead
+  while (G < 64 && !grp_fits(run, sh, G)) G = (G < 2) ? 2 : ((G & (G - 1)) ? 64 : G * 2);
+  r.G = G;
+  if (contest) {
+    const int win = (G == 64) ? 0 : fastest(a, {0, G}, [&](const KernelArgs &t, int g) {
+      if (g == 0) launch_flat(t, ri, stream); else launch_grp(t, run, sh, g, stream); });
+    run.tuned_flat = win == 0 ? 1 : 0;
+    if (win != 0) r.flat_nc = 0;
+  }
+}
+
+// ---- the general runs into launches: all in one sampler_grp_all, a class's in one sampler_grp_multi, a size bucket with
+// the run after it ----
+void miso_batch::group_runs() {
+  LaunchPlan &q = plan;
+  // Paired-end, two classes or more, every run on dense records with sixteen lanes per chain (a whole-gene batch of like-sized
+  // genes): ALL of them in one launch (sampler_grp_all, kernels_grp.inl), the segments ordered by what a workgroup costs --
+  // (quads per lane + the scalar step) x isoforms, descending: longest first across the classes.  Every segment keeps the run's
+  // own slice layout (launch_grp's).  Batches with size buckets (real pair counts) keep a launch per class
+  // (sampler_grp_multi): twenty bodies in one kernel do not compile in reasonable time (round 5: 28 minutes, 802 spilled registers).
+  // MISO_NO_PE_ALL=1: the launches per run below (A/B, tests).
+  {
+    bool all_ok = p.paired && !q.lane_gen && gen_runs.size() >= 2 && gen_runs.size() < 127 && std::getenv("MISO_NO_PE_ALL") == nullptr &&
+                  std::getenv("MISO_NO_PE_MULTI") == nullptr && std::getenv("MISO_SERIAL_KERNELS") == nullptr &&
+                  (std::getenv("MISO_GENERAL_LANES") == nullptr || std::getenv("MISO_PE_ALL") != nullptr);   // (MISO_PE_ALL=1 with MISO_GENERAL_LANES=16: tests on small batches)
+    bool two_classes = false;
+    for (size_t ri = 0; ri < gen_runs.size() && all_ok; ri++) {
+      const GenRun &run = gen_runs[ri];
+      all_ok = !q.runs[ri].lane && q.runs[ri].flat_nc == 0 && fp_rows(run) && run.kc <= 32 && !run.wide && q.runs[ri].G == 16;
+      two_classes |= run.kc != gen_runs[0].kc;
+    }
+    q.grp_all = all_ok && two_classes;
+    if (q.grp_all)
+      for (LaunchPlan::Run &r : q.runs) r.group = 2;
+  }
+  // Paired-end: the size buckets of one isoform-count class in ONE launch (sampler_grp_multi<KC>, kernels_grp.inl):
+  // segments = the class's runs in list order -- workgroup-wide chains (those on several workgroups in front), a
+  // wavefront per chain, 32 lanes, 16 lanes.  MISO_NO_PE_MULTI=1: every run its own launch (A/B, tests).
+  // When: the batch's launches outnumber the hardware queues (a whole-gene mix with real read counts: ~20 launches, 243 ->
+  // 180 ms per 1500 iterations; a single class's three or four buckets run 3 % faster side by side: 149 vs 155 ms at K = 5;
+  // profiles/r03_pe_buckets.txt).  MISO_PE_MULTI=1 forces (tests).
+  // ... or some run on 16 / 32 lanes holds several isoform counts: the multi kernel's segments keep them in wavefronts of their own
+  bool any_mixed = false;
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
+    const int G = q.runs[ri].G;
+    any_mixed |= p.paired && !gen_runs[ri].wide && (G == 16 || G == 32 || (G == 8 && gen_runs[ri].small)) && fp_rows(gen_runs[ri]) && q.runs[ri].flat_nc == 0 && gen_runs[ri].kmin != gen_runs[ri].kmax;
+  }
+  const bool multi_on = p.paired && !q.lane_gen && std::getenv("MISO_NO_PE_MULTI") == nullptr && std::getenv("MISO_GENERAL_LANES") == nullptr &&
+                        (std::getenv("MISO_PE_MULTI") != nullptr || gen_runs.size() + (n_k2 > 0 ? 1 : 0) > 8 || any_mixed);
+  for (size_t r0 = 0; multi_on && !q.grp_all && r0 < gen_runs.size();) {
+    size_t r1 = r0 + 1;
+    while (r1 < gen_runs.size() && gen_runs[r1].kc == gen_runs[r0].kc) r1++;
+    const int G0 = q.runs[r0].G;
+    bool ok = (r1 - r0 >= 2 || (r1 - r0 == 1 && gen_runs[r0].kmin != gen_runs[r0].kmax && (G0 == 16 || G0 == 32 || (G0 == 8 && gen_runs[r0].small)))) &&
+              r1 - r0 <= static_cast<size_t>(K2_MAX_SEGS);
+    for (size_t ri = r0; ri < r1 && ok; ri++) {
+      const GenRun &run = gen_runs[ri];
+      const int G = q.runs[ri].G;
+      ok = q.runs[ri].flat_nc == 0 && fp_rows(run) && (ri == r0 || run.first == gen_runs[ri - 1].first + gen_runs[ri - 1].count) &&
+           (run.wide || G == 16 || G == 32 || (G == 64 && run.wave64) || (G == 8 && run.small));
+    }
+    if (ok) {   // every segment's slices fit the workgroup's LDS
+      const GenRun m = joined_run(r0, r1);
+      const size_t fp_bytes = fp_bytes_of(m), slice = grp_slice_bytes(m.kmax, 0, grp_shape(m).ts), slice8 = grp_slice_bytes(m.kmax, 0, 0);
+      for (size_t ri = r0; ri < r1 && ok; ri++)
+        if (!gen_runs[ri].wide) ok = fp_bytes + 4 * static_cast<size_t>(64 / q.runs[ri].G) * (q.runs[ri].G == 8 ? slice8 : slice) <= q.lds_max;
+    }
+    if (ok) {
+      q.multi.emplace_back(r0, r1);
+      for (size_t ri = r0; ri < r1; ri++) q.runs[ri].group = 1;
+    }
+    r0 = r1;
+  }
+  // A size bucket whose lanes came out the same as the class's normal launch joins it: one launch (its chains stay
+  // in front: longest first), one hardware queue less to wait in (kernels of different streams share the process's
+  // hardware queues, and a kernel waits for the one before it in its queue).
+  // (measured, 16 384 genes of 3-20 isoforms: 4 queues 290 -> 254 ms merged; 8 queues 195 ms apart, 241 ms merged --
+  // the separate launches stagger the classes' starts; the queue count is the host's, capi.hip only records it)
+  // (what is IN EFFECT, not what the environment says now: capi.hip's constructor records it; 0 = unknown -- not set, or the
+  // runtime was up before this library was loaded -- counts as the runtime's default of 4)
+  const int hwq = g_hw_queues_in_effect > 0 ? g_hw_queues_in_effect : 4;
+  const bool merge_on = std::getenv("MISO_NO_PE_MERGE") == nullptr && (std::getenv("MISO_PE_MERGE") != nullptr || hwq < 8);
+  for (size_t ri = 0; merge_on && ri + 1 < gen_runs.size(); ri++) {
+    const GenRun &run = gen_runs[ri], &nx = gen_runs[ri + 1];
+    const LaunchPlan::Run &r = q.runs[ri], &rx = q.runs[ri + 1];
+    if (r.lane || r.group || (ri > 0 && q.runs[ri - 1].merge_next)) continue;
+    if (!run.wide && run.force_G && r.G != 64 && r.flat_nc == 0 && !nx.wide && !nx.force_G && nx.kc == run.kc && rx.G == r.G &&
+        rx.flat_nc == 0 && nx.first == run.first + run.count) {
+      const GenRun m = joined_run(ri, ri + 2);
+      q.runs[ri].merge_next = grp_fits(m, grp_shape(m), r.G);
+    }
+  }
+}
+
+// kernel i > 0 goes to its own stream, forked from and joined back into the batch's stream
+hipStream_t miso_batch::stream_for_next() {
+  const size_t i = kernel_no++;
+  if (i == 0 || std::getenv("MISO_SERIAL_KERNELS") != nullptr) return stream;
+  while (aux_streams.size() < i) {
+    hipStream_t st; hipEvent_t e;
+    // (numerically lower = higher priority; the range has three levels on this device: the second and third kernel
+    // of a launch at the middle one, the rest at the lowest)
+    const int n_aux = static_cast<int>(aux_streams.size());
+    const int pr = prio_hi == prio_lo ? prio_lo : std::min(prio_lo, prio_hi + 1 + n_aux / 2);
+    if (prio_hi != prio_lo) HIP_OK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, pr));
+    else HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    aux_streams.push_back(st); aux_done.push_back(e);
+  }
+  HIP_OK(hipStreamWaitEvent(aux_streams[i - 1], ev0, 0));
+  return aux_streams[i - 1];
+}
+
+// The launches, in this order (the stream and priority every kernel gets follow from it): sampler_lane_k, the
+// workgroup-wide runs (chains on several workgroups first: their workgroups must all be resident at once, coop.hpp,
+// which the idle device guarantees; what is launched after them never waits for them) -- sampler_grp_all or the
+// classes' sampler_grp_multi, then the runs of their own --, MODE 2, the other two-isoform events, the other runs.
+void miso_batch::launch_planned(const KernelArgs &a) {
+  const LaunchPlan &q = plan;
+  if (q.lane_route || q.lane_gen) {   // log factorials (miso_binomial.h) up to the largest event's drawing reads
+    size_t need = 2;
+    for (int i = 0; i < n_k2 + n_gen; i++) need = std::max<size_t>(need, events[h_slots[i]].n_draw + 2);
+    if (need > logfact.host.size()) {
+      std::vector<double> lf(need);
+      miso_logfact_fill(lf.data(), static_cast<int>(need));
+      HIP_OK(hipStreamSynchronize(stream));   // (an earlier launch of this batch may still read the old table)
+      put(logfact, lf);
+    }
+  }
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
+    if (!q.runs[ri].lane) continue;
+    const GenRun &run = gen_runs[ri];
+    const int ks = std::max(2, run.kmax);
+    KernelArgs ka = a;
+    ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count; ka.kstride = ks; ka.logfact = logfact.d;
+    const long chains = static_cast<long>(run.count) * p.noChains;
+    note_kernel(run_name(ri));
+    launch_kernel(fn(&sampler_lane_k), static_cast<unsigned>((chains + 63) / 64), 64, lanek_lds_bytes(ks), stream_for_next(), ka);
+  }
+  if (q.grp_all) launch_grp_all(a);
+  for (const auto &g : q.multi) launch_grp_multi(a, g.first, g.second);
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) if (gen_runs[ri].wide && !q.runs[ri].lane && !q.runs[ri].group) launch_run(a, ri);
+  if (n_k2w > 0) {
+    lanes_per_chain = q.k2w_multi ? k2w_plan.seg_lanes[k2w_plan.n_segs - 1] : q.k2w_G;
+    note_kernel(k2_part_name(true));
+    if (q.k2w_multi) launch_k2_multi(a, stream_for_next(), true);
+    else launch_k2(a, q.k2w_G, stream_for_next(), true);
+  }
+  if (n_k2 - n_k2w > 0) {
+    lanes_per_chain = q.lane_route ? q.lane_G : q.k2_multi ? k2_plan.seg_lanes[k2_plan.n_segs - 1] : q.k2_G;
+    note_kernel(k2_part_name(false));
+    if (q.lane_route) launch_lane(a, stream_for_next());
+    else if (q.k2_multi) launch_k2_multi(a, stream_for_next());
+    else if (q.k2_mix > 0) launch_k2_mix(a, stream_for_next());
+    else launch_k2(a, q.k2_G, stream_for_next());
+  }
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) if (!gen_runs[ri].wide && !q.runs[ri].lane && !q.runs[ri].group) launch_run(a, ri);
+}
+
+// general run ri in a launch of its own, or with the next run (merge_next); nothing when the run before took it
+void miso_batch::launch_run(const KernelArgs &a, size_t ri) {
+  const LaunchPlan::Run &r = plan.runs[ri];
+  if (ri > 0 && plan.runs[ri - 1].merge_next) return;
+  note_kernel(run_name(ri));
+  if (r.merge_next) {
+    GenRun m = joined_run(ri, ri + 2);
+    launch_grp(a, m, grp_shape(m), r.G, stream_for_next());
+  } else if (r.flat_nc > 0) {
+    launch_flat(a, ri, stream_for_next());
+  } else {
+    launch_grp(a, gen_runs[ri], r.sh, r.G, stream_for_next());
+  }
+}
+
+void miso_batch::launch_grp_all(const KernelArgs &a) {
+  struct Seg { size_t ri; int e0, e1; double cost; };
+  std::vector<Seg> segs;
+  // (a segment per isoform count, so that no wavefront carries two -- see sampler_grp_multi below; MISO_PE_ALL_ORDER=0: a segment per
+  // run, 2: heaviest / lightest alternating, 3: lightest first (A/B: 777 / 705 / 767 / 851 ms for 0 / 1 / 2 / 3))
+  const int order = std::getenv("MISO_PE_ALL_ORDER") ? std::atoi(std::getenv("MISO_PE_ALL_ORDER")) : 1;
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
+    const GenRun &run = gen_runs[ri];
+    if (order == 0) { segs.push_back(Seg{ri, 0, run.count, (static_cast<double>(run.maxq) / 16.0 + 8.0) * (run.kmax + 2)}); continue; }
+    auto cost_at = [&](int e) {
+      const PackedEvent &ev = events[h_slots[n_k2 + run.first + e]];
+      return (static_cast<double>((ev.n_draw + 3) / 4) / 16.0 + 8.0) * (ev.K + 2);
+    };
+    int e0 = 0;   // pieces: one per isoform count
+    for (int e = 1; e <= run.count; e++)
+      if (e == run.count || events[h_slots[n_k2 + run.first + e]].K != events[h_slots[n_k2 + run.first + e0]].K) { segs.push_back(Seg{ri, e0, e, cost_at(e0)}); e0 = e; }
+  }
+  std::stable_sort(segs.begin(), segs.end(), [&](const Seg &x, const Seg &y) { return x.cost > y.cost; });
+  if (order == 2) {   // heaviest, lightest, second heaviest, second lightest, ...
+    std::vector<Seg> t;
+    for (size_t i = 0, j = segs.size(); i < j;) { t.push_back(segs[i++]); if (i < j) t.push_back(segs[--j]); }
+    segs = t;
+  }
+  if (order == 3) std::reverse(segs.begin(), segs.end());   // lightest first
+  KernelArgs ka = a;
+  hipStream_t st = stream_for_next();
+  ka.slot_event = d_slots + n_k2; ka.n_slots = n_gen;
+  ka.cstride = 0; ka.pe_dense = 1; ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
+  size_t lds = 0; int blocks = 0;
+  std::vector<GrpSeg> tab;
+  for (const Seg &sg : segs) {
+    const GenRun &run = gen_runs[sg.ri];
+    const GrpShape &sh = plan.runs[sg.ri].sh;
+    const long chains = static_cast<long>(sg.e1 - sg.e0) * p.noChains;
+    GrpSeg g{};
+    g.block0 = blocks; g.slot0 = run.first + sg.e0; g.n_slots = sg.e1 - sg.e0; g.kc = run.kc;
+    g.kstride = run.kmax; g.tstride = sh.ts;
+    lds = std::max(lds, fp_bytes_of(run) + 4 * 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, sh.ts)));
+    blocks += static_cast<int>(((chains + 3) / 4 + 3) / 4);
+    tab.push_back(g);
+  }
+  GrpSeg sentinel{}; sentinel.block0 = blocks;
+  tab.push_back(sentinel);
+  if (lds > plan.lds_max) MISO_FAIL(MISO_EINTERNAL, "sampler_grp_all: a segment's slices exceed the workgroup's LDS");
+  // (uploaded when it changed: the batch's first launch, or another upload's events; the launch that read the old one has
+  // been waited for by then)
+  constexpr size_t GRP_SEGS_CAP = 256;
+  if (tab.size() > GRP_SEGS_CAP) MISO_FAIL(MISO_EINTERNAL, "sampler_grp_all: too many segments");
+  put(grp_segs, tab, GRP_SEGS_CAP);
+  ka.grp_segs = grp_segs.d; ka.n_grp_segs = static_cast<int32_t>(segs.size());
+  note_kernel("sampler_grp_all");
+  launch_kernel(fn(&sampler_grp_all), static_cast<unsigned>(blocks), 256, lds, st, ka);
+}
+
+void miso_batch::launch_grp_multi(const KernelArgs &a, size_t r0, size_t r1) {
+  const GenRun m = joined_run(r0, r1);
+  const GrpShape msh = grp_shape(m);
+  const size_t fp_bytes = fp_bytes_of(m);
+  const size_t slice = grp_slice_bytes(m.kmax, 0, msh.ts);
+  // (the small genes' segment: eight chains per wavefront, their score tables in global memory -- a tstride of its own)
+  const size_t slice8 = grp_slice_bytes(m.kmax, 0, 0);
+  KernelArgs ka = a;
+  hipStream_t st = stream_for_next();
+  ka.slot_event = d_slots + n_k2 + m.first; ka.n_slots = m.count;
+  ka.kstride = m.kmax; ka.cstride = 0; ka.tstride = msh.ts;
+  ka.pe_dense = 1; ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
+  size_t lds = 0; int blocks = 0, segs = 0;
+  // A run on 16 or 32 lanes per chain is one segment PER ISOFORM COUNT (the run's events are ordered by it): every segment starts
+  // a new workgroup, so no wavefront carries chains of two isoform counts -- such a wavefront runs both counts' read loops one after
+  // the other (kernels_grp.inl pe_fast), twice a chain's own time, and with the class's longest chains that was the launch's length
+  // (round 6, profiles/r06_mix_timeline.txt).  As far as the segments suffice; MISO_PE_NO_KSPLIT=1: a segment per run (A/B).
+  auto k_pieces = [&](const GenRun &run) {
+    std::vector<int> cuts{0};
+    for (int e = 1; e < run.count; e++)
+      if (events[h_slots[n_k2 + run.first + e]].K != events[h_slots[n_k2 + run.first + e - 1]].K) cuts.push_back(e);
+    cuts.push_back(run.count);
+    return cuts;
+  };
+  size_t want_segs = 0;
+  for (size_t ri = r0; ri < r1; ri++)
+    want_segs += (gen_runs[ri].wide || plan.runs[ri].G == 64) ? 1 : k_pieces(gen_runs[ri]).size() - 1;
+  const bool ksplit = want_segs <= static_cast<size_t>(K2_MAX_SEGS) && std::getenv("MISO_PE_NO_KSPLIT") == nullptr;
+  for (size_t ri = r0; ri < r1; ri++) {
+    GenRun &run = gen_runs[ri];
+    const long chains = static_cast<long>(run.count) * p.noChains;
+    if (run.wide) {
+      ka.seg_slot[segs] = run.first - m.first; ka.seg_block[segs] = blocks;
+      const size_t lds0 = align_up(fp_bytes + 4 * slice, 16);
+      ka.red_off = static_cast<int32_t>(lds0);
+      lds = std::max(lds, lds0 + 96);
+      blocks += static_cast<int>(wide_setup(run, chains, st));
+      ka.coop_tab = run.coop.tab.d; ka.coop_mem = run.coop.mem.d;
+      ka.seg_ts[segs] = msh.ts;
+      ka.seg_lanes[segs++] = K2_WIDE;
+    } else {
+      const int G = plan.runs[ri].G, cpw = 64 / G;
+      lds = std::max(lds, fp_bytes + 4 * static_cast<size_t>(cpw) * (G == 8 ? slice8 : slice));
+      const std::vector<int> cuts = (ksplit && G != 64) ? k_pieces(run) : std::vector<int>{0, run.count};
+      for (size_t c = 0; c + 1 < cuts.size(); c++) {
+        const long pc = static_cast<long>(cuts[c + 1] - cuts[c]) * p.noChains;
+        ka.seg_slot[segs] = run.first - m.first + cuts[c]; ka.seg_block[segs] = blocks;
+        blocks += static_cast<int>(((pc + cpw - 1) / cpw + 3) / 4);
+        ka.seg_ts[segs] = G == 8 ? 0 : msh.ts;
+        ka.seg_lanes[segs++] = G;
+      }
+    }
+  }
+  ka.seg_slot[segs] = m.count; ka.seg_block[segs] = blocks; ka.n_segs = segs;
+  note_kernel(run_name(r0));
+  launch_kernel(grp_multi_kernel(m.kc), static_cast<unsigned>(blocks), 256, lds, st, ka);
+}
+
+// ---- what the last launch put on the device, kernel by kernel (miso_batch_launch_stats): from its plan, on demand ----
+std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
+  std::vector<miso_kernel_stat_t> out;
+  if (!plan.sampled) return out;
+  const LaunchPlan &q = plan;
   auto add_stat = [&](const std::string &name, double waves, double trips, double chains, double words) {
     miso_kernel_stat_t ks{};
     std::snprintf(ks.name, sizeof ks.name, "%s", name.c_str());
     ks.waves = waves; ks.trips = trips; ks.iterations = static_cast<double>(p.noIterations) + 1.0;
     ks.chains = chains; ks.words = words;
-    kernel_stats.push_back(ks);
-  };
-  auto k2_name = [&](int G, bool wpart) {
-    return "sampler_k2<" + std::to_string(G) + (p.paired ? (wpart ? ", 2, 4>" : ", 1, 4>") : (k2_pair ? ", 0, 8>" : ", 0, 4>"));
-  };
-  auto k2_mix_name = [&](int G) { return "sampler_k2_mix<" + std::to_string(G + 1) + ", " + std::to_string(G) + ">"; };
-  // up to twenty isoforms the kernel of the launch's largest isoform count (its slice layout at compile time,
-  // kernels_flat.inl); MISO_FLAT_NO_KS=1: the run-time layout everywhere (A/B, tests)
-  auto flat_ks = [&](const GenRun &run) {
-    const int lo = run.kc == 4 ? 3 : (run.kc == 8 ? 5 : (run.kc == 12 ? 9 : (run.kc == 16 ? 13 : 17)));
-    return (run.kc <= 32 && run.kmax >= lo && run.kmax <= std::min(run.kc, 20) && std::getenv("MISO_FLAT_NO_KS") == nullptr) ? run.kmax : 0;
-  };
-  // ... and, when every event of the launch has that count, the kernel that knows it (UNI: no per-chain `k < K` masks)
-  auto flat_uni = [&](const GenRun &run) { return flat_ks(run) > 0 && run.kmin == run.kmax && std::getenv("MISO_FLAT_NO_UNI") == nullptr; };
-  auto flat_name = [&](const GenRun &run) {
-    return "sampler_flat<" + std::to_string(run.kc) + ", " + std::to_string(flat_ks(run)) + (flat_uni(run) ? ", true>" : ">");
+    out.push_back(ks);
   };
   for (int part = 0; part < 2; part++) {
     const bool wpart = part == 0;
-    const int count = wpart ? n_k2w : n_k2 - n_k2w, k2G = wpart ? k2w_G : k2_G;
+    const int count = wpart ? n_k2w : n_k2 - n_k2w, k2G = wpart ? q.k2w_G : q.k2_G;
     if (count <= 0) continue;
     // slot order = events by drawing reads, descending, each with its noChains chains
     std::vector<int> nd;
@@ -1644,12 +1928,11 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
         trips += p.paired ? 2 * t + 1 : 2 * t + (any_rem ? 1 : 0);   // counted in blocks per lane
       }
     };
-    if (!wpart && lane_route) {
+    if (!wpart && q.lane_route) {
       for (int n : nd) words += static_cast<double>(n) * C;
-      add_stat(lane_G == 1 ? std::string(lane_ilp ? "sampler_lane_ilp" : "sampler_lane") : "sampler_k2c<" + std::to_string(lane_G) + ">",
-               static_cast<double>((chains * lane_G + 63) / 64), 0.0, static_cast<double>(chains), words);
-    } else if (wpart ? k2w_multi : k2_multi) {
-      const LanePlan &pl = wpart ? planw_copy : plan_copy;
+      waves = (chains * q.lane_G + 63) / 64;
+    } else if (wpart ? q.k2w_multi : q.k2_multi) {
+      const LanePlan &pl = wpart ? k2w_plan : k2_plan;
       for (int sg = 0; sg < pl.n_segs; sg++) {
         const long c0 = static_cast<long>(pl.seg_slot[sg]) * C, c1 = static_cast<long>(pl.seg_slot[sg + 1]) * C;
         if (pl.seg_lanes[sg] == K2_WIDE) {
@@ -1664,39 +1947,37 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
           }
         } else slice(c0, c1, pl.seg_lanes[sg]);
       }
-      add_stat(wpart ? "sampler_k2_multi<2, " + std::to_string(pl.wpb) + ">" : k2m_name, static_cast<double>(waves), trips,
-               static_cast<double>(chains), words);
-    } else if (!wpart && k2_mix > 0) {
-      slice(0, static_cast<long>(k2_mix) * C, k2G + 1);
-      slice(static_cast<long>(k2_mix) * C, chains, k2G);
-      add_stat(k2_mix_name(k2G), static_cast<double>(waves), trips, static_cast<double>(chains), words);
+    } else if (!wpart && q.k2_mix > 0) {
+      slice(0, static_cast<long>(q.k2_mix) * C, k2G + 1);
+      slice(static_cast<long>(q.k2_mix) * C, chains, k2G);
     } else {
       slice(0, chains, k2G);
-      add_stat(k2_name(k2G, wpart), static_cast<double>(waves), trips, static_cast<double>(chains), words);
     }
+    add_stat(k2_part_name(wpart), static_cast<double>(waves), trips, static_cast<double>(chains), words);
   }
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
+  for (size_t ri = 0; ri < gen_runs.size() && ri < q.runs.size(); ri++) {
     const GenRun &run = gen_runs[ri];
-    if (run_lane[ri]) {
-      double words = 0;
-      for (int i = 0; i < run.count; i++) words += static_cast<double>(events[h_slots[n_k2 + run.first + i]].n_draw) * p.noChains;
-      const long chains = static_cast<long>(run.count) * p.noChains;
-      add_stat("sampler_lane_k", static_cast<double>((chains + 63) / 64), 0.0, static_cast<double>(chains), words);
-      continue;
-    }
-    const bool flat = flat_nc[ri] > 0;
-    const int G = grp_G[ri], C = p.noChains, cpw = flat ? flat_nc[ri] : std::max(1, 64 / G);
-    const bool w64 = G == 64 && run.wave64 && p.paired && run.dense;
+    const LaunchPlan::Run &r = q.runs[ri];
+    const int C = p.noChains;
     const long chains = static_cast<long>(run.count) * C;
     std::vector<const PackedEvent *> evs;   // the run's events in slot order
     for (int j = 0; j < run.count; j++) evs.push_back(&events[h_slots[n_k2 + run.first + j]]);   // the list upload made
-    const bool cls = !p.paired && grp_sh[ri].qs > 0;
     double trips = 0, words = 0;
     long waves = 0;
+    if (r.lane) {
+      for (const PackedEvent *e : evs) words += static_cast<double>(e->n_draw) * C;
+      add_stat(run_name(ri), static_cast<double>((chains + 63) / 64), 0.0, static_cast<double>(chains), words);
+      continue;
+    }
+    const bool flat = r.flat_nc > 0;
+    const int G = r.G, cpw = flat ? r.flat_nc : std::max(1, 64 / G);
+    const bool w64 = G == 64 && run.wave64 && p.paired && run.dense;
+    const bool cls = !p.paired && r.sh.qs > 0;
     if (flat) {   // the wavefronts as flat_waves laid them out
-      for (size_t w = 0; w + 1 < run.wave_tab.size(); w += 2) {
-        const int first = run.wave_tab[w], n = run.wave_tab[w + 1] & 0xFF;
-        const bool wide = (run.wave_tab[w + 1] & FLAT_WIDE) != 0;
+      const std::vector<int32_t> &tab = run.wave_tab.host;
+      for (size_t w = 0; w + 1 < tab.size(); w += 2) {
+        const int first = tab[w], n = tab[w + 1] & 0xFF;
+        const bool wide = (tab[w + 1] & FLAT_WIDE) != 0;
         if (n == 0) continue;
         long units = 0;
         for (long sl = first; sl < first + n; sl++) { units += evs[sl / C]->n_units; if (!wide || (w / 2) % 4 == 0) words += evs[sl / C]->n_draw; }
@@ -1720,358 +2001,9 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
       trips = 0; waves = 0;
       for (long sl = 0; sl < chains; sl++) { trips += 4 * ((((evs[sl / C]->n_draw + 3) / 4) + 255) / 256); waves += 4; }
     }
-    const std::string name = (ri < run_in_multi.size() && run_in_multi[ri] == 2) ? std::string("sampler_grp_all") :
-                             (ri < run_in_multi.size() && run_in_multi[ri]) ? "sampler_grp_multi<" + std::to_string(run.kc) + ">" :
-                             run.wide ? "sampler_grp<64, true, " + std::to_string(run.kc) + ", true>" :
-                             flat ? flat_name(run) : ((G == 64 && !w64) ? std::string(run.kc > 64 ? "sampler_big<" : "sampler_wave<") : "sampler_grp<" + std::to_string(G) + ", ") +
-                             (p.paired ? "true" : "false") + ((G == 64 && !w64) ? std::string(">") : ", " + std::to_string(run.kc) + ">");
-    add_stat(name, static_cast<double>(waves), trips, static_cast<double>(chains), words);
+    add_stat(run_name(ri), static_cast<double>(waves), trips, static_cast<double>(chains), words);
   }
-  };   // stats_builder
-
-  HIP_OK(hipEventRecord(ev0, stream));                  // events bracket the sampler kernels only
-  // kernel i > 0 goes to its own stream, forked from and joined back into the batch's stream
-  size_t kernel_no = 0;
-  auto stream_for_next = [&]() {
-    const size_t i = kernel_no++;
-    if (i == 0 || std::getenv("MISO_SERIAL_KERNELS") != nullptr) return stream;
-    while (aux_streams.size() < i) {
-      hipStream_t st; hipEvent_t e;
-      // (numerically lower = higher priority; the range has three levels on this device: the second and third kernel
-      // of a launch at the middle one, the rest at the lowest)
-      const int n_aux = static_cast<int>(aux_streams.size());
-      const int pr = prio_hi == prio_lo ? prio_lo : std::min(prio_lo, prio_hi + 1 + n_aux / 2);
-      if (prio_hi != prio_lo) HIP_OK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, pr));
-      else HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      aux_streams.push_back(st); aux_done.push_back(e);
-    }
-    HIP_OK(hipStreamWaitEvent(aux_streams[i - 1], ev0, 0));
-    return aux_streams[i - 1];
-  };
-  // chains on several workgroups first: their workgroups must all be resident at once (coop.hpp), which the idle
-  // device guarantees; what is launched after them never waits for them
-  // A size bucket whose lanes came out the same as the class's normal launch joins it: one launch (its chains stay
-  // in front: longest first), one hardware queue less to wait in (kernels of different streams share the process's
-  // hardware queues, and a kernel waits for the one before it in its queue).
-  std::vector<char> merged_into_prev(gen_runs.size(), 0);
-  // (measured, 16 384 genes of 3-20 isoforms: 4 queues 290 -> 254 ms merged; 8 queues 195 ms apart, 241 ms merged --
-  // the separate launches stagger the classes' starts; the queue count is the host's, capi.hip only records it)
-  // (what is IN EFFECT, not what the environment says now: capi.hip's constructor records it; 0 = unknown -- not set, or the
-  // runtime was up before this library was loaded -- counts as the runtime's default of 4)
-  const int hwq = g_hw_queues_in_effect > 0 ? g_hw_queues_in_effect : 4;
-  const bool merge_on = std::getenv("MISO_NO_PE_MERGE") == nullptr && (std::getenv("MISO_PE_MERGE") != nullptr || hwq < 8);
-  auto launch_gen_run = [&](size_t ri) {
-    GenRun &run = gen_runs[ri];
-    const int G = grp_G[ri];
-    if (merged_into_prev[ri]) return;
-    const bool wave_k = G == 64 && !(run.wave64 && p.paired && run.dense);
-    if (merge_on && !run.wide && run.force_G && G != 64 && flat_nc[ri] == 0 && ri + 1 < gen_runs.size()) {
-      const GenRun &nx = gen_runs[ri + 1];
-      if (!nx.wide && !nx.force_G && nx.kc == run.kc && grp_G[ri + 1] == G && flat_nc[ri + 1] == 0 &&
-          nx.first == run.first + run.count) {
-        GenRun m;
-        m.first = run.first; m.count = run.count + nx.count; m.kc = run.kc;
-        m.kmax = std::max(run.kmax, nx.kmax); m.kmin = std::min(run.kmin, nx.kmin); m.maxq = std::max(run.maxq, nx.maxq);
-        m.maxcls = std::max(run.maxcls, nx.maxcls); m.nocls = run.nocls || nx.nocls; m.dense = run.dense && nx.dense;
-        const GrpShape msh = grp_shape(m);
-        if (grp_fits(m, msh, G)) {
-          merged_into_prev[ri + 1] = 1;
-          last_kernels += std::string(last_kernels.empty() ? "" : ",") + "sampler_grp<" + std::to_string(G) + ", " +
-                          (p.paired ? "true" : "false") + ", " + std::to_string(run.kc) + ">";
-          launch_grp(a, m, msh, G, stream_for_next());
-          return;
-        }
-      }
-    }
-    if (flat_nc[ri] > 0) {
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + flat_name(run);
-      launch_flat(a, run, flat_nc[ri], flat_nc_max[ri], stream_for_next());
-      return;
-    }
-    last_kernels += std::string(last_kernels.empty() ? "" : ",") +
-                    (run.wide ? "sampler_grp<64, true, " + std::to_string(run.kc) + ", true>"
-                              : (wave_k ? std::string(run.kc > 64 ? "sampler_big<" : "sampler_wave<")
-                                        : "sampler_grp<" + std::to_string(G) + ", ") +
-                                    (p.paired ? "true" : "false") +
-                                    (wave_k ? std::string(">") : ", " + std::to_string(run.kc) + ">"));
-    launch_grp(a, run, grp_sh[ri], G, stream_for_next());
-  };
-  auto ensure_logfact = [&](int first, int count) {   // log factorials (miso_binomial.h) up to the largest event's drawing reads
-    int need = 2;
-    for (int i = 0; i < count; i++) need = std::max(need, events[h_slots[first + i]].n_draw + 2);
-    if (need > logfact_n) {
-      std::vector<double> lf(static_cast<size_t>(need));
-      miso_logfact_fill(lf.data(), need);
-      HIP_OK(hipStreamSynchronize(stream));   // (an earlier launch of this batch may still read the old table)
-      if (d_logfact) HIP_OK(hipFree(d_logfact));
-      HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_logfact), lf.size() * sizeof(double)));
-      HIP_OK(hipMemcpy(d_logfact, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice));
-      logfact_n = need;
-    }
-  };
-  if (lane_route || lane_gen) ensure_logfact(0, n_k2 + n_gen);
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-    if (!run_lane[ri]) continue;
-    const GenRun &run = gen_runs[ri];
-    const int ks = std::max(2, run.kmax);
-    KernelArgs ka = a;
-    ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count; ka.kstride = ks; ka.logfact = d_logfact;
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    const size_t lds = lanek_lds_bytes(ks);
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_lane_k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    last_kernels += std::string(last_kernels.empty() ? "" : ",") + "sampler_lane_k";
-    hipLaunchKernelGGL(sampler_lane_k, dim3(static_cast<unsigned>((chains + 63) / 64)), dim3(64), lds, stream_for_next(), ka);
-    HIP_OK(hipGetLastError());
-  }
-  // Paired-end: the size buckets of one isoform-count class in ONE launch (sampler_grp_multi<KC>, kernels_grp.inl):
-  // segments = the class's runs in list order -- workgroup-wide chains (those on several workgroups in front), a
-  // wavefront per chain, 32 lanes, 16 lanes.  MISO_NO_PE_MULTI=1: every run its own launch (A/B, tests).
-  std::vector<char> in_multi(gen_runs.size(), 0);
-  bool all_launched = false;
-  // Paired-end, two classes or more, every run on dense records with sixteen lanes per chain (a whole-gene batch of like-sized
-  // genes): ALL of them in one launch (sampler_grp_all, kernels_grp.inl), the segments ordered by what a workgroup costs --
-  // (quads per lane + the scalar step) x isoforms, descending: longest first across the classes.  Every segment keeps the run's
-  // own slice layout (launch_grp's).  Batches with size buckets (real pair counts) keep a launch per class
-  // (sampler_grp_multi): twenty bodies in one kernel do not compile in reasonable time (round 5: 28 minutes, 802 spilled registers).
-  // MISO_NO_PE_ALL=1: the launches per run below (A/B, tests).
-  {
-    bool all_ok = p.paired && !lane_gen && gen_runs.size() >= 2 && gen_runs.size() < 127 && std::getenv("MISO_NO_PE_ALL") == nullptr &&
-                  std::getenv("MISO_NO_PE_MULTI") == nullptr && std::getenv("MISO_SERIAL_KERNELS") == nullptr &&
-                  (std::getenv("MISO_GENERAL_LANES") == nullptr || std::getenv("MISO_PE_ALL") != nullptr);   // (MISO_PE_ALL=1 with MISO_GENERAL_LANES=16: tests on small batches)
-    bool two_classes = false;
-    for (size_t ri = 0; ri < gen_runs.size() && all_ok; ri++) {
-      const GenRun &run = gen_runs[ri];
-      const int G = grp_G[ri];
-      all_ok = !run_lane[ri] && flat_nc[ri] == 0 && fp_rows(run) && run.kc <= 32 && !run.wide && G == 16;
-      two_classes |= run.kc != gen_runs[0].kc;
-    }
-    if (all_ok && two_classes) {
-      struct Seg { size_t ri; int e0, e1; double cost; };
-      std::vector<Seg> segs;
-      // (a segment per isoform count, so that no wavefront carries two -- see sampler_grp_multi below; MISO_PE_ALL_ORDER=0: a segment per
-      // run, 2: heaviest / lightest alternating, 3: lightest first (A/B: 777 / 705 / 767 / 851 ms for 0 / 1 / 2 / 3))
-      const int order = std::getenv("MISO_PE_ALL_ORDER") ? std::atoi(std::getenv("MISO_PE_ALL_ORDER")) : 1;
-      for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-        const GenRun &run = gen_runs[ri];
-        if (order == 0) { segs.push_back(Seg{ri, 0, run.count, (static_cast<double>(run.maxq) / 16.0 + 8.0) * (run.kmax + 2)}); continue; }
-        auto cost_at = [&](int e) {
-          const PackedEvent &ev = events[h_slots[n_k2 + run.first + e]];
-          return (static_cast<double>((ev.n_draw + 3) / 4) / 16.0 + 8.0) * (ev.K + 2);
-        };
-        int e0 = 0;   // pieces: one per isoform count
-        for (int e = 1; e <= run.count; e++)
-          if (e == run.count || events[h_slots[n_k2 + run.first + e]].K != events[h_slots[n_k2 + run.first + e0]].K) { segs.push_back(Seg{ri, e0, e, cost_at(e0)}); e0 = e; }
-      }
-      std::stable_sort(segs.begin(), segs.end(), [&](const Seg &x, const Seg &y) { return x.cost > y.cost; });
-      if (order == 2) {   // heaviest, lightest, second heaviest, second lightest, ...
-        std::vector<Seg> t;
-        for (size_t i = 0, j = segs.size(); i < j;) { t.push_back(segs[i++]); if (i < j) t.push_back(segs[--j]); }
-        segs = t;
-      }
-      if (order == 3) std::reverse(segs.begin(), segs.end());   // lightest first
-      KernelArgs ka = a;
-      hipStream_t st = stream_for_next();
-      ka.slot_event = d_slots + n_k2; ka.n_slots = n_gen;
-      ka.cstride = 0; ka.pe_dense = 1; ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
-      size_t lds = 0; int blocks = 0;
-      std::vector<GrpSeg> tab;
-      for (const Seg &sg : segs) {
-        const GenRun &run = gen_runs[sg.ri];
-        const GrpShape &sh = grp_sh[sg.ri];
-        const long chains = static_cast<long>(sg.e1 - sg.e0) * p.noChains;
-        GrpSeg g{};
-        g.block0 = blocks; g.slot0 = run.first + sg.e0; g.n_slots = sg.e1 - sg.e0; g.kc = run.kc;
-        g.kstride = run.kmax; g.tstride = sh.ts;
-        lds = std::max(lds, fp_bytes_of(run) + 4 * 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, sh.ts)));
-        blocks += static_cast<int>(((chains + 3) / 4 + 3) / 4);
-        tab.push_back(g);
-        in_multi[sg.ri] = 2;
-      }
-      GrpSeg sentinel{}; sentinel.block0 = blocks;
-      tab.push_back(sentinel);
-      if (lds > LDS_MAX) MISO_FAIL(MISO_EINTERNAL, "sampler_grp_all: a segment's slices exceed the workgroup's LDS");
-      // (uploaded when it changed: the batch's first launch, or another upload's events; the launch that read the old one has
-      // been waited for by then)
-      constexpr size_t GRP_SEGS_CAP = 256;
-      if (tab.size() > GRP_SEGS_CAP) MISO_FAIL(MISO_EINTERNAL, "sampler_grp_all: too many segments");
-      if (!d_grp_segs) HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_grp_segs), GRP_SEGS_CAP * sizeof(GrpSeg)));
-      if (tab.size() != h_grp_segs.size() || std::memcmp(tab.data(), h_grp_segs.data(), tab.size() * sizeof(GrpSeg)) != 0) {
-        h_grp_segs = tab;
-        HIP_OK(hipMemcpy(d_grp_segs, h_grp_segs.data(), h_grp_segs.size() * sizeof(GrpSeg), hipMemcpyHostToDevice));
-      }
-      ka.grp_segs = d_grp_segs; ka.n_grp_segs = static_cast<int32_t>(segs.size());
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + "sampler_grp_all";
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_grp_all), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      hipLaunchKernelGGL(sampler_grp_all, dim3(static_cast<unsigned>(blocks)), dim3(256), lds, st, ka);
-      HIP_OK(hipGetLastError());
-      all_launched = true;
-    }
-  }
-  // When: the batch's launches outnumber the hardware queues (a whole-gene mix with real read counts: ~20 launches, 243 ->
-  // 180 ms per 1500 iterations; a single class's three or four buckets run 3 % faster side by side: 149 vs 155 ms at K = 5;
-  // profiles/r03_pe_buckets.txt).  MISO_PE_MULTI=1 forces (tests).
-  // ... or some run on 16 / 32 lanes holds several isoform counts: the multi kernel's segments keep them in wavefronts of their own
-  bool any_mixed = false;
-  for (size_t ri = 0; ri < gen_runs.size(); ri++)
-    any_mixed |= p.paired && !gen_runs[ri].wide && (grp_G[ri] == 16 || grp_G[ri] == 32 || (grp_G[ri] == 8 && gen_runs[ri].small)) && fp_rows(gen_runs[ri]) && flat_nc[ri] == 0 && gen_runs[ri].kmin != gen_runs[ri].kmax;
-  const bool multi_on = p.paired && !lane_gen && std::getenv("MISO_NO_PE_MULTI") == nullptr && std::getenv("MISO_GENERAL_LANES") == nullptr &&
-                        (std::getenv("MISO_PE_MULTI") != nullptr || gen_runs.size() + (n_k2 > 0 ? 1 : 0) > 8 || any_mixed);
-  for (size_t r0 = 0; multi_on && !all_launched && r0 < gen_runs.size();) {
-    size_t r1 = r0 + 1;
-    while (r1 < gen_runs.size() && gen_runs[r1].kc == gen_runs[r0].kc) r1++;
-    bool ok = (r1 - r0 >= 2 || (r1 - r0 == 1 && gen_runs[r0].kmin != gen_runs[r0].kmax && (grp_G[r0] == 16 || grp_G[r0] == 32 || (grp_G[r0] == 8 && gen_runs[r0].small)))) &&
-              r1 - r0 <= static_cast<size_t>(K2_MAX_SEGS);
-    GenRun m;
-    m.first = gen_runs[r0].first; m.count = 0; m.kc = gen_runs[r0].kc;
-    for (size_t ri = r0; ri < r1 && ok; ri++) {
-      const GenRun &run = gen_runs[ri];
-      const int G = grp_G[ri];
-      ok = flat_nc[ri] == 0 && fp_rows(run) && run.first == m.first + m.count &&
-           (run.wide || G == 16 || G == 32 || (G == 64 && run.wave64) || (G == 8 && run.small));
-      m.count += run.count; m.kmax = std::max(m.kmax, run.kmax); m.kmin = std::min(m.kmin, run.kmin);
-      m.maxq = std::max(m.maxq, run.maxq);
-    }
-    const GrpShape msh = ok ? grp_shape(m) : GrpShape{0, 0};
-    const size_t fp_bytes = fp_bytes_of(m);
-    const size_t slice = ok ? grp_slice_bytes(m.kmax, 0, msh.ts) : 0;
-    // (the small genes' segment: eight chains per wavefront, their score tables in global memory -- a tstride of its own)
-    const size_t slice8 = ok ? grp_slice_bytes(m.kmax, 0, 0) : 0;
-    for (size_t ri = r0; ri < r1 && ok; ri++)
-      if (!gen_runs[ri].wide) ok = fp_bytes + 4 * static_cast<size_t>(64 / grp_G[ri]) * (grp_G[ri] == 8 ? slice8 : slice) <= LDS_MAX;
-    if (ok) {
-      KernelArgs ka = a;
-      hipStream_t st = stream_for_next();
-      ka.slot_event = d_slots + n_k2 + m.first; ka.n_slots = m.count;
-      ka.kstride = m.kmax; ka.cstride = 0; ka.tstride = msh.ts;
-      ka.pe_dense = 1; ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
-      size_t lds = 0; int blocks = 0, segs = 0;
-      // A run on 16 or 32 lanes per chain is one segment PER ISOFORM COUNT (the run's events are ordered by it): every segment starts
-      // a new workgroup, so no wavefront carries chains of two isoform counts -- such a wavefront runs both counts' read loops one after
-      // the other (kernels_grp.inl pe_fast), twice a chain's own time, and with the class's longest chains that was the launch's length
-      // (round 6, profiles/r06_mix_timeline.txt).  As far as the segments suffice; MISO_PE_NO_KSPLIT=1: a segment per run (A/B).
-      auto k_pieces = [&](const GenRun &run) {
-        std::vector<int> cuts{0};
-        for (int e = 1; e < run.count; e++)
-          if (events[h_slots[n_k2 + run.first + e]].K != events[h_slots[n_k2 + run.first + e - 1]].K) cuts.push_back(e);
-        cuts.push_back(run.count);
-        return cuts;
-      };
-      size_t want_segs = 0;
-      for (size_t ri = r0; ri < r1; ri++)
-        want_segs += (gen_runs[ri].wide || grp_G[ri] == 64) ? 1 : k_pieces(gen_runs[ri]).size() - 1;
-      const bool ksplit = want_segs <= static_cast<size_t>(K2_MAX_SEGS) && std::getenv("MISO_PE_NO_KSPLIT") == nullptr;
-      for (size_t ri = r0; ri < r1; ri++) {
-        GenRun &run = gen_runs[ri];
-        const long chains = static_cast<long>(run.count) * p.noChains;
-        if (run.wide) {
-          ka.seg_slot[segs] = run.first - m.first; ka.seg_block[segs] = blocks;
-          const size_t lds0 = align_up(fp_bytes + 4 * slice, 16);
-          ka.red_off = static_cast<int32_t>(lds0);
-          lds = std::max(lds, lds0 + 96);
-          blocks += static_cast<int>(wide_setup(run, chains, st));
-          ka.coop_tab = run.d_coop_tab; ka.coop_mem = run.d_coop_mem;
-          ka.seg_ts[segs] = msh.ts;
-          ka.seg_lanes[segs++] = K2_WIDE;
-        } else {
-          const int G = grp_G[ri], cpw = 64 / G;
-          lds = std::max(lds, fp_bytes + 4 * static_cast<size_t>(cpw) * (G == 8 ? slice8 : slice));
-          const std::vector<int> cuts = (ksplit && G != 64) ? k_pieces(run) : std::vector<int>{0, run.count};
-          for (size_t c = 0; c + 1 < cuts.size(); c++) {
-            const long pc = static_cast<long>(cuts[c + 1] - cuts[c]) * p.noChains;
-            ka.seg_slot[segs] = run.first - m.first + cuts[c]; ka.seg_block[segs] = blocks;
-            blocks += static_cast<int>(((pc + cpw - 1) / cpw + 3) / 4);
-            ka.seg_ts[segs] = G == 8 ? 0 : msh.ts;
-            ka.seg_lanes[segs++] = G;
-          }
-        }
-        in_multi[ri] = 1;
-      }
-      ka.seg_slot[segs] = m.count; ka.seg_block[segs] = blocks; ka.n_segs = segs;
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + "sampler_grp_multi<" + std::to_string(m.kc) + ">";
-#define MISO_GRP_MULTI(KC)                                                                                   \
-  {                                                                                                          \
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sampler_grp_multi<KC>),                       \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));          \
-    hipLaunchKernelGGL((sampler_grp_multi<KC>), dim3(static_cast<unsigned>(blocks)), dim3(256), lds, st, ka); \
-  }
-      switch (m.kc) {
-      case 4: MISO_GRP_MULTI(4) break;
-      case 8: MISO_GRP_MULTI(8) break;
-      case 12: MISO_GRP_MULTI(12) break;
-      case 16: MISO_GRP_MULTI(16) break;
-      default: MISO_GRP_MULTI(32) break;
-      }
-#undef MISO_GRP_MULTI
-      HIP_OK(hipGetLastError());
-    }
-    r0 = r1;
-  }
-  run_in_multi = in_multi;
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) if (gen_runs[ri].wide && !run_lane[ri] && !in_multi[ri]) launch_gen_run(ri);
-  if (n_k2w > 0 && k2w_multi) {
-    lanes_per_chain = k2w_plan.seg_lanes[k2w_plan.n_segs - 1];
-    last_kernels = "sampler_k2_multi<2, " + std::to_string(k2w_plan.wpb) + ">";
-    launch_k2_multi(a, stream_for_next(), true);
-  } else if (n_k2w > 0) {
-    lanes_per_chain = k2w_G;
-    last_kernels = k2_name(k2w_G, true);
-    launch_k2(a, k2w_G, stream_for_next(), true);
-  }
-  if (n_k2 - n_k2w > 0) {
-    lanes_per_chain = k2_G;
-    if (lane_route) {   // collapsed single-end batch: one chain per lane, no read loop (kernels_lane.hip)
-      KernelArgs ka = a;
-      ka.slot_event = d_slots; ka.n_slots = n_k2; ka.pair_waves = 0;
-      ka.logfact = d_logfact; ka.tstride = logfact_n;   // (tstride: the table's entries, for sampler_lane_ilp's LDS copy)
-      const long chains = static_cast<long>(n_k2) * p.noChains;
-      const int G = lane_G;
-      lanes_per_chain = G;
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + (G == 1 ? std::string(lane_ilp ? "sampler_lane_ilp" : "sampler_lane") : "sampler_k2c<" + std::to_string(G) + ">");
-      const unsigned grid = static_cast<unsigned>(((chains + 64 / G - 1) / (64 / G) + 3) / 4);
-      hipStream_t st = stream_for_next();
-      switch (G) {
-      case 1: {
-        unsigned wgs = static_cast<unsigned>((chains + 255) / 256);
-        {   // fewer wavefronts than SIMDs (or than two per SIMD): spread the chains over all of them (kernels_lane.hip lane_body)
-          const long simds = wave_slots / 2, waves = (chains + 63) / 64;
-          const char *sp = std::getenv("MISO_LANE_SPREAD");   // 0: never; n: n wavefronts per SIMD (experiments)
-          const int per_simd = sp ? std::atoi(sp) : 1;
-          if (lane_ilp && per_simd > 0 && waves < simds * per_simd && chains >= 64) {
-            const long target = simds * per_simd;
-            const int cpw = static_cast<int>((chains + target - 1) / target);
-            if (cpw >= 8 && cpw < 64) { ka.pair_waves = cpw; wgs = static_cast<unsigned>(((chains + cpw - 1) / cpw + 3) / 4); }
-          }
-        }
-        if (lane_ilp) hipLaunchKernelGGL(sampler_lane_ilp, dim3(wgs), dim3(256), 0, st, ka);
-        else hipLaunchKernelGGL(sampler_lane, dim3(wgs), dim3(256), 0, st, ka);
-        break;
-      }
-      case 2: hipLaunchKernelGGL(sampler_k2c<2>, dim3(grid), dim3(256), 0, st, ka); break;
-      case 4: hipLaunchKernelGGL(sampler_k2c<4>, dim3(grid), dim3(256), 0, st, ka); break;
-      default: hipLaunchKernelGGL(sampler_k2c<8>, dim3(grid), dim3(256), 0, st, ka); break;
-      }
-      HIP_OK(hipGetLastError());
-    } else if (k2_multi) {
-      lanes_per_chain = k2_plan.seg_lanes[k2_plan.n_segs - 1];
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + k2m_name;
-      launch_k2_multi(a, stream_for_next());
-    } else if (k2_mix > 0) {
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + k2_mix_name(k2_G);
-      launch_k2_mix(a, k2_G, stream_for_next());
-    } else {
-      last_kernels += std::string(last_kernels.empty() ? "" : ",") + k2_name(k2_G, false);
-      launch_k2(a, k2_G, stream_for_next());
-    }
-  }
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) if (!gen_runs[ri].wide && !run_lane[ri] && !in_multi[ri]) launch_gen_run(ri);
-  for (size_t i = 1; i < kernel_no && i <= aux_streams.size() && std::getenv("MISO_SERIAL_KERNELS") == nullptr; i++) {
-    HIP_OK(hipEventRecord(aux_done[i - 1], aux_streams[i - 1]));
-    HIP_OK(hipStreamWaitEvent(stream, aux_done[i - 1], 0));
-  }
-  HIP_OK(hipEventRecord(ev1, stream));
-  start_clock_probe();
-  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false;
+  return out;
 }
 
 // The clock probe of this launch (clock_probe_kernel above).  First the flag's store, behind the launch's last kernel on the
@@ -2125,18 +2057,12 @@ void miso_batch::sync(float *ms) {
   read_clock_probe();
   // chains on several workgroups: did any group give up waiting for its members (coop.hpp)?
   bool gave_up = false;
-  for (const K2Coop *cc : {&k2_coop_se, &k2w_coop}) {
-    if (!cc->d_mem || cc->chains == 0) continue;
-    std::vector<uint32_t> w(static_cast<size_t>(cc->chains) * COOP_WORDS);
-    HIP_OK(hipMemcpy(w.data(), cc->d_mem, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int c = 0; c < cc->chains; c++) gave_up |= w[static_cast<size_t>(c) * COOP_WORDS + 1] != 0;
-  }
-  for (const GenRun &run : gen_runs) {
-    if (!run.d_coop_mem || run.coop_chains == 0) continue;
-    std::vector<uint32_t> w(static_cast<size_t>(run.coop_chains) * COOP_WORDS);
-    HIP_OK(hipMemcpy(w.data(), run.d_coop_mem, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int c = 0; c < run.coop_chains; c++) gave_up |= w[static_cast<size_t>(c) * COOP_WORDS + 1] != 0;
-  }
+  each_coop_table([&](const CoopTable &cc) {
+    if (!cc.mem.d || cc.chains == 0) return;
+    std::vector<uint32_t> w(static_cast<size_t>(cc.chains) * COOP_WORDS);
+    HIP_OK(hipMemcpy(w.data(), cc.mem.d, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int c = 0; c < cc.chains; c++) gave_up |= w[static_cast<size_t>(c) * COOP_WORDS + 1] != 0;
+  });
   if (!gave_up) { converge_rounds(ms); return; }
   // A chain's workgroups did not all become resident in time (a busy device: other batches, other processes).  The
   // batch must not fail for it -- the reference's workers share nothing (misopy/miso.py:165-187) --, so the launch is
@@ -2146,16 +2072,7 @@ void miso_batch::sync(float *ms) {
   const float first_ms = last_ms;
   no_coop = true; coop_retries++;
   std::fill(coop_n.begin(), coop_n.end(), 1);
-  for (GenRun &run : gen_runs) {
-    if (run.d_coop_tab) (void) hipFree(run.d_coop_tab);
-    if (run.d_coop_mem) (void) hipFree(run.d_coop_mem);
-    run.d_coop_tab = nullptr; run.d_coop_mem = nullptr; run.coop_tab.clear(); run.coop_chains = 0;
-  }
-  for (K2Coop *cc : {&k2_coop_se, &k2w_coop}) {
-    if (cc->d_tab) (void) hipFree(cc->d_tab);
-    if (cc->d_mem) (void) hipFree(cc->d_mem);
-    *cc = K2Coop{};
-  }
+  each_coop_table([](CoopTable &c) { c.reset(); });
   k2_plan_key = k2w_plan_key = -1; coop_wgs_used = 0;
   pool_cleared = false;   // (the abandoned chains left their sample columns half written)
   std::fprintf(stderr, "[miso] a chain on several workgroups gave up waiting for its workgroups after %.1f ms (busy device?): "
@@ -2355,7 +2272,7 @@ void miso_batch::adopt_samples(int n, const int *K, int Sn, const double *const 
   std::vector<unsigned char> h(out_bytes, 0);
   for (int i = 0; i < n; i++) std::memcpy(h.data() + h_events[i].off_samples, samples[i], static_cast<size_t>(Sn) * K[i] * 8);
   HIP_OK(hipMemcpy(d_out, h.data(), out_bytes, hipMemcpyHostToDevice));
-  n_k2 = n_k2w = n_gen = 0; gen_runs.clear();
+  n_k2 = n_k2w = n_gen = 0; gen_runs.clear(); plan = LaunchPlan{};
   uploaded = launched = true; downloaded = false; summarized = compared = false;
 }
 

@@ -2,6 +2,8 @@
 counts (2-20, incl. the 17-20 range of the K <= 32 kernels), read counts (0-2500), chains, lags,
 single- and paired-end, many events per launch so that several kernels (two-isoform + one per
 isoform-count class) run concurrently on their own streams."""
+import re
+
 import numpy as np
 import pytest
 
@@ -68,7 +70,10 @@ def test_random_mixed_batches_bit_exact(orc, paired, seed):
         assert np.array_equal(gpu.loglik, cpu.loglik, equal_nan=True)
         assert (gpu.assignment == cpu.assignment).all()
         assert gpu.rundata.noAccepted == cpu.accepted
-    assert "," in b.last_kernels()          # several kernels in this launch
+    # several kernels in this launch, each named once it is launched (a name's template arguments hold commas too)
+    names = re.findall(r"\w+(?:<[^>]*>)?", b.last_kernels())
+    assert len(names) > 1 and any(n.startswith("sampler_k2") for n in names), names
+    assert {k["name"] for k in b.launch_stats()["kernels"]} == set(names), names
 
 
 @pytest.mark.parametrize("level,seed", [(1, 11), (2, 12), (2, 13)])

@@ -370,21 +370,33 @@ def test_two_processes_on_one_gpu_with_cooperative_chains_in_both():
 def test_collapsed_batch_on_one_device_then_another():
     """release() between two uploads must leave nothing behind (the log-factorial table of the collapsed step, the
     cross-run pairing table and the cached plans were kept as stale pointers in round 3: use-after-free on the second
-    device).  Needs two GPUs."""
+    device; round 6: sampler_grp_all's segment table).  Needs two GPUs."""
     from miso_amd import capi
     if capi.device_count() < 2:
         pytest.skip("one GPU visible")
     orc = OrcLib()
-    evs = _events(orc, False, [300, 5000, 40, 900, 64, 2500, 150, 700])
+    se_evs = _events(orc, False, [300, 5000, 40, 900, 64, 2500, 150, 700])
+    pe_evs = []   # several isoform-count classes, sixteen lanes per chain everywhere: one sampler_grp_all
+    for j, K in enumerate([3, 6, 10, 14, 18, 4, 7, 12]):
+        exons, isoforms = se_gene(K, exlen=500 + 11 * j, gap=300)
+        g = orc.gene(flat(exons), isoforms)
+        orc.rng_seed(7300 + j)
+        rc, _, pos, cig = orc.simulate_paired_reads(g, expr_for(K), 250, 36, 250.0, 900.0)
+        assert rc == 0
+        pe_evs.append((exons, isoforms, g, pos, cig))
+    lanes16 = dict(MISO_GENERAL_LANES="16", MISO_NO_PE_BUCKETS="1", MISO_PE_ALL="1")
     kw = dict(iters=80, burn=20, lag=2, chains=2)
-    for collapsed, env in ((True, {}), (False, dict(MISO_K2_GLOBAL_PAIR="1"))):
+    for paired, collapsed, env, evs in ((False, True, {}, se_evs), (False, False, dict(MISO_K2_GLOBAL_PAIR="1"), se_evs),
+                                        (True, False, lanes16, pe_evs)):
         with _env(**env):
-            b = miso_amd.Batch(36, device_match=True, collapsed=collapsed, **kw)
+            b = miso_amd.Batch(36, paired=paired, mean=250.0 if paired else 0.0, var=900.0 if paired else 0.0,
+                               device_match=True, collapsed=collapsed, **kw)
             for exons, isoforms, g, pos, cig in evs:
                 b.add_event(miso_amd.Gene(exons, isoforms), pos, cig)
             res = []
             for dev in (0, 1, 0):
                 b.run(device=dev, seed=5, first_event_id=10)
+                assert not paired or b.last_kernels() == "sampler_grp_all", b.last_kernels()
                 res.append([b.result(i) for i in range(len(evs))])
             for i in range(len(evs)):
                 assert np.array_equal(res[0][i].samples, res[1][i].samples) and np.array_equal(res[0][i].samples, res[2][i].samples)
