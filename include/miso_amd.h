@@ -260,6 +260,44 @@ int miso_batch_get_summary(const miso_batch_t *batch, int event_index, double *m
 int miso_batch_from_samples(int n_events, const int *noiso, int n_samples, const double *const *samples, int device,
                             miso_batch_t **batch);
 
+/* The same batch straight from the files' TEXT, decoded on the device (a `.miso` file after its two header lines, or
+   the psi_vals_and_scores column of a `.miso_db` row; miso_amd/miso_db.py).  Event i's body is
+   text[offsets[i] .. offsets[i + 1]); a row is "f_1,...,f_K<TAB>g<LF>", empty lines are ignored, the last LF may be
+   missing.
+
+   miso_text_shape (host only, no device needed): per event the isoform count (commas before the first TAB of the first
+   non-empty line, plus one; 0 for a body without one) and the number of non-empty lines.  The caller groups events by
+   the latter: a batch has one n_samples.
+
+   miso_batch_from_miso_text: the sample pool is written by the decode kernel only.  status[i] == 0: event i's pool
+   region holds its n_samples x noiso[i] values, each the correctly rounded double of its decimal text (what strtod
+   gives).  status[i] != 0, a sum of the MISO_TEXT_* bits below: the event is not in the fast grammar, its pool region is
+   unspecified and its summaries must not be read; every other event is unaffected.  The fast grammar: a psi field is
+   -?digits[.digits] with at most 15 significant digits and at most 22 digits after the point (value = digits as an
+   integer / 10^decimals, one IEEE division of two exact doubles); the log-score field g is not stored but must be
+   -?digits[.digits], nan, inf or -inf; no CR, no exponent, K fields in every row, n_samples rows.
+   The text streams through the device in chunks of whole events of about chunk_bytes (<= 0: the default, 64 MiB; an
+   event larger than that is a chunk of its own), so device memory is bounded by the chunk size plus the pool.
+   MISO_ENODEVICE without a GPU: there is no CPU path.  stats may be NULL. */
+#define MISO_TEXT_EPSI 1    /* a psi field outside the fast grammar (exponent, nan, inf, > 15 digits, > 22 decimals)  */
+#define MISO_TEXT_EROW 2    /* a row with another number of fields than noiso[i], or without TAB                      */
+#define MISO_TEXT_ESCORE 4  /* a log-score field that is no plain decimal, nan, inf or -inf (a CR at the line's end)  */
+#define MISO_TEXT_ECOUNT 8  /* another number of non-empty lines than n_samples                                       */
+typedef struct {
+  int64_t chunks;        /* device chunks                                                                  */
+  int64_t decoded;       /* events with status 0                                                           */
+  int64_t not_decoded;   /* events with another status                                                     */
+  int64_t text_bytes;    /* bytes of text sent to the device                                               */
+  int64_t sample_bytes;  /* bytes of samples the pool holds (8 per psi field)                              */
+  double kernel_ms;      /* the decode kernels alone (device time, summed over the chunks)                 */
+  double decode_ms;      /* copies to the device and kernels (device time, summed over the chunks)         */
+  double total_ms;       /* wall time of the whole call                                                    */
+} miso_text_stats_t;
+int miso_text_shape(int n_events, const unsigned char *text, const int64_t *offsets, int32_t *noiso, int32_t *n_rows);
+int miso_batch_from_miso_text(int n_events, const unsigned char *text, const int64_t *offsets, const int *noiso,
+                              int n_samples, int device, int64_t chunk_bytes, miso_batch_t **batch, int32_t *status,
+                              miso_text_stats_t *stats);
+
 /* Two-sample comparison on the device (compare_miso, misopy/hypothesis_test.py:89-179, 348-380):
    `sample1` and `sample2` hold the SAME events in the same order (one batch per RNA-seq sample),
    both launched on the same device.  Per event and isoform: index-paired delta = psi1 - psi2;

@@ -104,6 +104,11 @@ def set_device(d):
     check(lib().miso_set_device(int(d)))
 
 
+def usable_threads():
+    """Host threads worth starting: the affinity mask capped by the cgroup CPU quota, at most 64 (miso_usable_threads)."""
+    return max(1, int(lib().miso_usable_threads()))
+
+
 class Gene:
     """One gene: exons as (start, end) 1-based inclusive, isoforms as tuples of exon indices
     (py2c_gene.py:10-21 builds exactly these for the reference's createGene)."""
@@ -509,6 +514,78 @@ class SamplesBatch(Batch):
         L = lib()
         L.miso_batch_from_samples.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         check(L.miso_batch_from_samples(n, _p(K), int(S), ptrs, int(device), C.byref(self.handle)))
+
+    @classmethod
+    def from_text(cls, text, offsets, noiso, n_samples, device=0, chunk_bytes=0):
+        """The same batch from the files' TEXT, decoded on the device (miso_batch_from_miso_text): event i's rows are
+        text[offsets[i]:offsets[i + 1]] (bytes / uint8 array; what follows a `.miso` file's two header lines).
+        `status` (int32 per event, 0 = decoded, else a sum of MISO_TEXT_* bits: its results must not be read) and
+        `text_stats` (dict) say how it went."""
+        buf = _text_buf(text)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        K = np.ascontiguousarray(noiso, dtype=np.int32)
+        n = len(K)
+        if len(offs) != n + 1 or (n and (offs[0] < 0 or offs[-1] > len(buf))):
+            raise ValueError("offsets must be n_events + 1 positions inside the text")
+        self = cls.__new__(cls)
+        S = int(n_samples)
+        self.params = Params(0, 36, 1, 1, S, S, 0, 1, MISO_ALGO_REASSIGN, MISO_START_AUTO, MISO_STOP_FIXEDNO, 0.0, 0.0, 4.0, 0, 0)
+        self.handle = C.c_void_p()
+        self.status = np.zeros(max(n, 1), np.int32)
+        stats = TextStats()
+        L = lib()
+        L.miso_batch_from_miso_text.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.POINTER(TextStats)]
+        check(L.miso_batch_from_miso_text(n, _p(buf), _p(offs), _p(K), S, int(device), int(chunk_bytes),
+                                          C.byref(self.handle), _p(self.status), C.byref(stats)))
+        self.status = self.status[:n]
+        self.text_stats = stats.as_dict()
+        return self
+
+    def samples(self, i):
+        """Event i's samples [S, K] as the pool holds them (downloads the pool once)."""
+        if not getattr(self, "_downloaded", False):
+            check(lib().miso_batch_download(self.handle))
+            self._downloaded = True
+        K = C.c_int()
+        check(lib().miso_batch_event_info(self.handle, i, C.byref(K), None, None, None))
+        out = np.zeros((self.params.noIterations, K.value))
+        check(lib().miso_batch_get_result(self.handle, i, _p(out), None, None, None, None, None))
+        return out
+
+
+# ---- `.miso` sample text (include/miso_amd.h miso_text_shape, miso_batch_from_miso_text) ----
+MISO_TEXT_EPSI, MISO_TEXT_EROW, MISO_TEXT_ESCORE, MISO_TEXT_ECOUNT = 1, 2, 4, 8
+
+
+class TextStats(C.Structure):
+    _fields_ = ([(n, C.c_int64) for n in ("chunks", "decoded", "not_decoded", "text_bytes", "sample_bytes")]
+                + [(n, C.c_double) for n in ("kernel_ms", "decode_ms", "total_ms")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _text_buf(text):
+    if len(text) == 0:
+        return np.zeros(1, np.uint8)[:0]
+    if isinstance(text, (bytes, bytearray, memoryview)):
+        return np.frombuffer(text, dtype=np.uint8)
+    return np.ascontiguousarray(text, dtype=np.uint8)
+
+
+def text_shape(text, offsets):
+    """(isoforms, non-empty lines) per event body text[offsets[i]:offsets[i + 1]] -- host only, no device needed."""
+    buf = _text_buf(text)
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offs) - 1
+    if n < 0 or (n and (offs[0] < 0 or offs[-1] > len(buf))):
+        raise ValueError("offsets must be n_events + 1 positions inside the text")
+    K, rows = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    L = lib()
+    L.miso_text_shape.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.miso_text_shape(n, _p(buf), _p(offs), _p(K), _p(rows)))
+    return K[:n], rows[:n]
 
 
 def simulate_reads(gene, expression, n_reads, read_len, sim_seed, mean=0.0, var=0.0, num_devs=4.0):

@@ -218,6 +218,10 @@ struct miso_batch {
   void download();
   void summarize(double confidence_level, bool as_text = false);
   void adopt_samples(int n, const int *K, int S, const double *const *samples, int dev);
+  void adopt_pool(int n, const int *K, int S, int dev);
+  // kernels_text.hip: the pool filled from `.miso` sample text by text_decode_kernel
+  void adopt_text(int n, const unsigned char *text, const int64_t *offsets, const int *K, int S, int dev, int64_t chunk_bytes,
+                  int32_t *status, miso_text_stats_t *stats);
   void compare(miso_batch &other, double smoothing);
   std::vector<miso_kernel_stat_t> launch_stats() const;   // miso_batch_launch_stats: one record per two-isoform part and per run
 

@@ -67,6 +67,10 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
                    const int64_t *end, int64_t chunk, int64_t *counts, miso_region_stats_t *stats);
 }  // namespace miso
 
+namespace miso {   // kernels_text.hip
+void text_shape(int n, const unsigned char *text, const int64_t *offsets, int32_t *noiso, int32_t *n_rows);
+}  // namespace miso
+
 using namespace miso;
 
 struct miso_gene { Gene g; };
@@ -729,6 +733,30 @@ int miso_batch_from_samples(int n_events, const int *noiso, int n_samples, const
     p.noBurnIn = 0; p.noLag = 1; p.algorithm = MISO_ALGO_REASSIGN; p.start = MISO_START_AUTO; p.stop = MISO_STOP_FIXEDNO;
     std::unique_ptr<miso_batch> b(batch_new(p));
     b->adopt_samples(n_events, noiso, n_samples, samples, device);
+    *batch = b.release();
+  });
+}
+
+int miso_text_shape(int n_events, const unsigned char *text, const int64_t *offsets, int32_t *noiso, int32_t *n_rows) {
+  return guarded([&] {
+    need(offsets, "offsets");
+    if (n_events > 0) { need(text, "text"); need(noiso, "noiso"); need(n_rows, "n_rows"); }
+    text_shape(n_events, text, offsets, noiso, n_rows);
+  });
+}
+
+int miso_batch_from_miso_text(int n_events, const unsigned char *text, const int64_t *offsets, const int *noiso,
+                              int n_samples, int device, int64_t chunk_bytes, miso_batch_t **batch, int32_t *status,
+                              miso_text_stats_t *stats) {
+  return guarded([&] {
+    need(batch, "batch"); need(offsets, "offsets");
+    if (n_events > 0) { need(text, "text"); need(noiso, "noiso"); need(status, "status"); }
+    miso_params_t p{};
+    p.readLength = 36; p.overHang = 1; p.noChains = 1; p.noIterations = n_samples; p.maxIterations = n_samples;
+    p.noBurnIn = 0; p.noLag = 1; p.algorithm = MISO_ALGO_REASSIGN; p.start = MISO_START_AUTO; p.stop = MISO_STOP_FIXEDNO;
+    if (n_samples < 1) MISO_FAIL(MISO_EINVAL, "Invalid number of events or samples");
+    std::unique_ptr<miso_batch> b(batch_new(p));
+    b->adopt_text(n_events, text, offsets, noiso, n_samples, device, chunk_bytes, status, stats);
     *batch = b.release();
   });
 }

@@ -2246,6 +2246,15 @@ void miso_batch::compare(miso_batch &other, double smoothing) {
 // and S samples in the file's layout (rows of K values).  Only the output pool exists; summarize / compare and their
 // getters work on it as on a sampled batch.
 void miso_batch::adopt_samples(int n, const int *K, int Sn, const double *const *samples, int dev) {
+  adopt_pool(n, K, Sn, dev);
+  std::vector<unsigned char> h(out_bytes, 0);
+  for (int i = 0; i < n; i++) std::memcpy(h.data() + h_events[i].off_samples, samples[i], static_cast<size_t>(Sn) * K[i] * 8);
+  HIP_OK(hipMemcpy(d_out, h.data(), out_bytes, hipMemcpyHostToDevice));
+}
+
+// The sample pool of such a batch, laid out and allocated but not filled: adopt_samples copies parsed samples into it,
+// adopt_text (kernels_text.hip) has the device decode them from the files' text.
+void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
   if (uploaded) release();
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the summaries have no CPU path");
   if (n < 0 || Sn < 1) MISO_FAIL(MISO_EINVAL, "Invalid number of events or samples");
@@ -2269,9 +2278,6 @@ void miso_batch::adopt_samples(int n, const int *K, int Sn, const double *const 
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_events), std::max<size_t>(n, 1) * sizeof(DevEvent)));
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
-  std::vector<unsigned char> h(out_bytes, 0);
-  for (int i = 0; i < n; i++) std::memcpy(h.data() + h_events[i].off_samples, samples[i], static_cast<size_t>(Sn) * K[i] * 8);
-  HIP_OK(hipMemcpy(d_out, h.data(), out_bytes, hipMemcpyHostToDevice));
   n_k2 = n_k2w = n_gen = 0; gen_runs.clear(); plan = LaunchPlan{};
   uploaded = launched = true; downloaded = false; summarized = compared = false;
 }

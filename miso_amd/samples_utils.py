@@ -1,33 +1,96 @@
 """misopy/samples_utils.py (`summarize_miso --summarize-samples`) and misopy/hypothesis_test.py
-(`compare_miso --compare-samples`) over EXISTING directories of `.miso` files, for Python 3 and the GPU.
+(`compare_miso --compare-samples`) over EXISTING MISO output, for Python 3 and the GPU.
 
     python -m miso_amd.samples_utils --summarize-samples SAMPLES_DIR OUTPUT_DIR
     python -m miso_amd.samples_utils --compare-samples SAMPLES_DIR1 SAMPLES_DIR2 OUTPUT_DIR
 
-The reference walks the samples directory (chromosome sub-directories of `<event>.miso`, samples_utils.py:263-329),
-parses every file's "%.4f" rows and computes per event the posterior mean and Chen-Shao interval
-(credible_intervals.py:4-72); compare_miso pairs the events present in both directories and adds the Savage-Dickey
-Bayes factor (hypothesis_test.py:89-179, 186-345).  Here the files are parsed on the host cores (numpy, one
-process per core) and the numbers come from the same device kernels that serve a live run (summarize_kernel,
-compare_kernel through `miso_batch_from_samples`): the samples are what the files hold, so the summaries equal the
-reference's on the same files (bounds bit for bit; see tests/test_gpu_summary.py, tests/test_gpu_compare.py).
-Out of scope as in the reference's own optional paths: compressed-ID maps (`--use-compressed`), zipped / SQLite
-`.miso_db` inputs (miso_pack).
+The reference walks the samples directory (chromosome sub-directories of `<event>.miso`, or their packed form
+`<chrom>.miso_db`, samples_utils.py:263-411), parses every event's "%.4f" rows and computes per event the posterior
+mean and Chen-Shao interval (credible_intervals.py:4-72); compare_miso pairs the events present in both directories and
+adds the Savage-Dickey Bayes factor (hypothesis_test.py:89-179, 186-345).  Here the directory's content decides what is
+read: `.miso` files, `.miso_db` databases (miso_amd/miso_pack.py, miso_amd/miso_db.py) or both, each event once (a
+file beats a row of the same name).  The numbers come from the same device kernels that serve a live run
+(summarize_kernel, compare_kernel); the samples get to the device in one of two ways, MISO_TEXT_DECODE=device|host or
+the `decoder` argument:
+
+  device  the events' text is uploaded as it is and decoded by text_decode_kernel straight into the samples pool
+          (capi.SamplesBatch.from_text).  An event outside the decoder's grammar (an exponent, `nan` as a value, a
+          ragged row; include/miso_amd.h) is reported by its status and goes through the host parser in a batch of its
+          own; `last_decode_stats` says how many did.
+  host    every event is parsed on the host cores (numpy, a thread per core) and copied to the device
+          (capi.SamplesBatch).
+
+Both give the same doubles for the same text -- the correctly rounded value of every decimal -- so the tables are
+byte-identical (tests/test_gpu_miso_text.py), and equal to the reference's on the same files (bounds bit for bit; see
+tests/test_gpu_summary.py, tests/test_gpu_compare.py).  Out of scope as in the reference's own optional paths:
+compressed-ID maps (`--use-compressed`), zipped outputs (miso_zip).
 """
 import glob
 import os
 import sys
+import time
 
 import numpy as np
 
-from . import capi, compare, summary
+from . import capi, compare, miso_db, summary
+
+# The default decoder: `device`, because it is the faster one end to end (profiles/miso_text.txt: a tree of
+# 40 000 default-settings events, tools/miso_text_bench.py).  MISO_TEXT_DECODE overrides it, the functions' `decoder`
+# argument overrides both.
+DEFAULT_DECODER = "device"
+# text of one device batch: bounds the host copy that joins the events' bodies into one buffer
+TEXT_BATCH_BYTES = 1 << 30
+# what the last summarize / compare did: events decoded on the device, events left to the host parser (their names),
+# the decode kernels' time and bytes (capi.TextStats summed over the batches), wall seconds per stage
+last_decode_stats = {}
+
+
+def _decoder(decoder):
+    d = decoder or os.environ.get("MISO_TEXT_DECODE") or DEFAULT_DECODER
+    if d not in ("host", "device"):
+        raise ValueError("MISO_TEXT_DECODE / decoder must be `host` or `device`, not %r" % (d,))
+    return d
 
 
 def get_samples_dir_filenames(samples_dir):
-    """samples_utils.py:90-127: every `.miso` file below samples_dir (chromosome sub-directories), sorted."""
-    direct = glob.glob(os.path.join(samples_dir, "*.miso"))
-    nested = glob.glob(os.path.join(samples_dir, "*", "*.miso"))
-    return sorted(direct + nested)
+    """samples_utils.py:351-411: every `.miso` file and every `.miso_db` database of samples_dir, each looked for in the
+    directory itself and one level down (chromosome sub-directories), sorted: files first."""
+    found = []
+    for ext in (".miso", miso_db.MISO_DB_EXT):
+        direct = glob.glob(os.path.join(samples_dir, "*" + ext))
+        nested = glob.glob(os.path.join(samples_dir, "*", "*" + ext))
+        found.append(sorted(f for f in direct + nested if os.path.isfile(f) and not os.path.basename(f).startswith(".")))
+    if found[0] and found[1]:
+        print("WARNING: Directory %s has both *.miso and *.miso_db files" % samples_dir)
+    return found[0] + found[1]
+
+
+def list_events(samples_dir):
+    """(files, rows): the `.miso` paths, and per database the event names to take from it.  Each event once: a row whose
+    event is also a file is left out (the file wins), and so is a row whose name an earlier database had."""
+    names = get_samples_dir_filenames(samples_dir)
+    files = [f for f in names if not miso_db.is_miso_db_fname(f)]
+    seen = {miso_db.strip_miso_ext(os.path.basename(f)) for f in files}
+    rows = {}
+    for dbf in names[len(files):]:
+        with miso_db.MISODatabase(dbf) as db:
+            mine = [n for n in dict.fromkeys(db.get_all_event_names()) if n not in seen]
+        seen.update(mine)
+        rows[dbf] = mine
+    return files, rows
+
+
+def _header_fields(header):
+    line = header.split("\n", 1)[0]
+    return dict(kv.split("=", 1) for kv in line[1:].split("\t") if "=" in kv)
+
+
+def _parse_rows(body):
+    first = body.split("\n", 1)[0]
+    K = first.split("\t")[0].count(",") + 1
+    flat = np.array(body.replace("\t", ",").replace("\n", ",").strip(",").split(","), dtype=np.float64)
+    rows = flat.reshape(-1, K + 1)
+    return np.ascontiguousarray(rows[:, :K])
 
 
 def parse_miso_file(path):
@@ -45,26 +108,155 @@ def parse_miso_file(path):
     return os.path.basename(path)[:-len(".miso")], np.ascontiguousarray(rows[:, :K]), fields
 
 
-def _parse_or_skip(path):
-    """A file that cannot be parsed (a header without sample rows, a truncated write) costs the run that event, not the
-    directory: the reference skips what it cannot load (samples_utils.py:282-292 `Skipping ...`)."""
+def parse_miso_text(name, header, rows):
+    """parse_miso_file's twin for a packed event: a `.miso_db` row's (event_name, header, psi_vals_and_scores)."""
+    return name, _parse_rows(rows), _header_fields(header)
+
+
+class _Event:
+    """One event's text as read: `header` (str, the two header lines) and `body` (bytes, the rows)."""
+    __slots__ = ("name", "header", "body", "where", "K", "S")
+
+    def __init__(self, name, header, body, where):
+        self.name, self.header, self.body, self.where, self.K, self.S = name, header, body, where, 0, 0
+
+    def parse(self):
+        return parse_miso_text(self.name, self.header, self.body.decode())
+
+
+def _parse_or_skip(ev):
+    """An event that cannot be parsed (a header without sample rows, a truncated write) costs the run that event, not the
+    directory: the reference skips what it cannot load (samples_utils.py:282-292 `Skipping ...`).  ev: a path or an
+    _Event."""
     try:
-        return parse_miso_file(path)
+        return parse_miso_file(ev) if isinstance(ev, str) else ev.parse()
     except (ValueError, IndexError, OSError) as err:
-        print("Skipping %s: %s" % (os.path.basename(path), err))
+        print("Skipping %s: %s" % (os.path.basename(ev) if isinstance(ev, str) else ev.where, err))
         return None
 
 
-def _load_all(paths, processes=None):
-    """Every file parsed on the host cores, in THREADS: the parsing is numpy's C code (the GIL is released where the
-    time goes) and a thread pool never forks a process that has already initialised the GPU runtime -- the caller may
-    have summarised another directory on the device a moment ago."""
-    if len(paths) < 64:
-        return [e for e in (_parse_or_skip(p) for p in paths) if e is not None]
+def _threads(processes=None):
+    """(not the affinity mask alone: under a CPU quota it names many more cores than the process may use)"""
+    return processes or capi.usable_threads()
+
+
+def _pool_map(fn, items, processes=None):
+    """fn over items in THREADS: the work is C code that releases the GIL (numpy's parser, file reads, SQLite) and a
+    thread pool never forks a process that has already initialised the GPU runtime -- the caller may have summarised
+    another directory on the device a moment ago."""
+    if len(items) < 64:
+        return [fn(x) for x in items]
     from concurrent.futures import ThreadPoolExecutor
-    n = processes or max(1, len(os.sched_getaffinity(0)))
+    n = _threads(processes)
     with ThreadPoolExecutor(n) as pool:
-        return [e for e in pool.map(_parse_or_skip, paths, chunksize=max(1, len(paths) // (8 * n))) if e is not None]
+        return list(pool.map(fn, items, chunksize=max(1, len(items) // (8 * n))))
+
+
+def _load_all(paths, processes=None):
+    """Every file (or _Event) parsed on the host cores."""
+    return [e for e in _pool_map(_parse_or_skip, paths, processes) if e is not None]
+
+
+def _read_file(path):
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+    except OSError as err:
+        print("Skipping %s: %s" % (os.path.basename(path), err))
+        return None
+    cut = data.find(b"\n")
+    cut = data.find(b"\n", cut + 1) if cut >= 0 else -1
+    if cut < 0:
+        print("Skipping %s: no sample rows" % os.path.basename(path))
+        return None
+    return _Event(os.path.basename(path)[:-len(".miso")], data[:cut + 1].decode(errors="replace"), data[cut + 1:], path)
+
+
+def _read_db(job):
+    """One database's wanted rows: one SELECT, the text as bytes (no decode / encode round trip)."""
+    dbf, wanted = job
+    wanted = set(wanted)
+    out = {}
+    with miso_db.MISODatabase(dbf, text_factory=bytes) as db:
+        for name, rows, header in db:
+            name = name.decode()
+            if name in wanted and name not in out:
+                out[name] = _Event(name, header.decode(errors="replace"), rows, "%s:%s" % (dbf, name))
+    return list(out.values())
+
+
+def _read_events(files, rows):
+    """The events' text: files and databases read side by side, nothing parsed yet."""
+    evs = [e for e in _pool_map(_read_file, files) if e is not None]
+    for part in _pool_map(_read_db, [(dbf, names) for dbf, names in rows.items() if names]):
+        evs.extend(part)
+    return evs
+
+
+def _text_batches(items, size_of):
+    """items in runs of at most TEXT_BATCH_BYTES of text (at least one item each)."""
+    run, n = [], 0
+    for it in items:
+        sz = size_of(it)
+        if run and n + sz > TEXT_BATCH_BYTES:
+            yield run
+            run, n = [], 0
+        run.append(it)
+        n += sz
+    if run:
+        yield run
+
+
+def _joined(evs):
+    offs = np.zeros(len(evs) + 1, np.int64)
+    np.cumsum([len(e.body) for e in evs], out=offs[1:])
+    return b"".join(e.body for e in evs), offs
+
+
+def _shape(evs):
+    """Isoforms and rows of every event's text (capi.text_shape: host threads, no device)."""
+    for run in _text_batches(evs, lambda e: len(e.body)):
+        text, offs = _joined(run)
+        K, S = capi.text_shape(text, offs)
+        for e, k, s in zip(run, K, S):
+            e.K, e.S = int(k), int(s)
+
+
+def _device_ok(e):
+    return 1 <= e.K <= capi.MISO_MAX_ISOFORMS and e.S >= 1
+
+
+class _Stats:
+    def __init__(self, decoder):
+        self.clock = time.perf_counter
+        self.d = {"decoder": decoder, "device_events": 0, "fallback_events": [], "chunks": 0, "text_bytes": 0,
+                  "sample_bytes": 0, "kernel_ms": 0.0, "decode_ms": 0.0, "stage_s": {}}
+        self.t = self.clock()
+
+    def stage(self, name):
+        now = self.clock()
+        self.d["stage_s"][name] = self.d["stage_s"].get(name, 0.0) + now - self.t
+        self.t = now
+
+    def add(self, batch, evs):
+        st = batch.text_stats
+        for k in ("chunks", "text_bytes", "sample_bytes", "kernel_ms", "decode_ms"):
+            self.d[k] += st[k]
+        self.d["device_events"] += int(st["decoded"])
+        self.d["fallback_events"] += [e.name for e, s in zip(evs, batch.status) if s and e.name not in self.d["fallback_events"]]
+
+    def done(self):
+        global last_decode_stats
+        n = self.d["device_events"] + len(self.d["fallback_events"])
+        self.d["fallback_share"] = len(self.d["fallback_events"]) / n if n else 0.0
+        last_decode_stats = self.d
+
+
+def _text_batch(evs, S, device, stats):
+    text, offs = _joined(evs)
+    b = capi.SamplesBatch.from_text(text, offs, [e.K for e in evs], S, device=device)
+    stats.add(b, evs)
+    return b
 
 
 def _by_sample_count(events):
@@ -74,39 +266,92 @@ def _by_sample_count(events):
     return groups
 
 
-def summarize_sampler_results(samples_dir, summary_filename, confidence_level=0.95, device=0):
-    """samples_utils.py:263-329: one summary row per `.miso` file of samples_dir."""
-    events = _load_all(get_samples_dir_filenames(samples_dir))
-    rows = []
+def _summarize_parsed(events, confidence_level, device, rows, stats):
+    """Summary rows of host-parsed events (name, samples [S, K], header dict)."""
     for S, group in sorted(_by_sample_count(events).items()):
         lo, _ = summary.credible_interval_ranks(S, confidence_level)
         if lo <= 0:                                      # the reference asserts both ranks > 0
             print("Skipping %d events with only %d samples" % (len(group), S))
             continue
         b = capi.SamplesBatch([g[1] for g in group], device=device)
+        stats.stage("decode")
         b.summarize(confidence_level)                     # the files' values ARE the samples here
         for i, (name, _, hdr) in enumerate(group):
             rows.append((name,) + tuple(b.summary(i)) + (hdr,))
+        stats.stage("summarize")
+
+
+def summarize_sampler_results(samples_dir, summary_filename, confidence_level=0.95, device=0, decoder=None):
+    """samples_utils.py:263-329: one summary row per event of samples_dir (`.miso` files and `.miso_db` rows)."""
+    decoder = _decoder(decoder)
+    stats = _Stats(decoder)
+    files, dbrows = list_events(samples_dir)
+    rows = []
+    if decoder == "host":
+        evs = _read_events([], dbrows)
+        stats.stage("read")
+        events = _load_all(files + evs)
+        stats.stage("parse")
+        _summarize_parsed(events, confidence_level, device, rows, stats)
+    else:
+        evs = _read_events(files, dbrows)
+        stats.stage("read")
+        _shape(evs)
+        stats.stage("shape")
+        left = [e for e in evs if not _device_ok(e)]
+        groups = {}
+        for e in evs:
+            if _device_ok(e):
+                groups.setdefault(e.S, []).append(e)
+        for S, group in sorted(groups.items()):
+            lo, _ = summary.credible_interval_ranks(S, confidence_level)
+            if lo <= 0:
+                print("Skipping %d events with only %d samples" % (len(group), S))
+                continue
+            for run in _text_batches(group, lambda e: len(e.body)):
+                b = _text_batch(run, S, device, stats)
+                stats.stage("decode")
+                b.summarize(confidence_level)
+                for i, e in enumerate(run):
+                    if b.status[i]:
+                        left.append(e)
+                    else:
+                        rows.append((e.name,) + tuple(b.summary(i)) + (_header_fields(e.header),))
+                stats.stage("summarize")
+        # what the device decoder did not take: through the host parser, in batches of their own
+        stats.d["fallback_events"] += [e.name for e in left if e.name not in stats.d["fallback_events"]]
+        _summarize_parsed(_load_all(left), confidence_level, device, rows, stats)
     rows.sort(key=lambda r: r[0])
     os.makedirs(os.path.dirname(os.path.abspath(summary_filename)), exist_ok=True)
-    return summary.write_summary(summary_filename, rows)
+    n = summary.write_summary(summary_filename, rows)
+    stats.stage("write")
+    stats.done()
+    return n
 
 
-def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_level=0.95, smoothing=0.3,
-                              sample_labels=None, device=0):
-    """hypothesis_test.py:186-345: events present in BOTH directories (262-264), `<l1>_vs_<l2>.miso_bf`."""
-    l1, l2 = sample_labels or (os.path.basename(os.path.normpath(sample1_dir)), os.path.basename(os.path.normpath(sample2_dir)))
-    f1 = {os.path.basename(p): p for p in get_samples_dir_filenames(sample1_dir)}
-    f2 = {os.path.basename(p): p for p in get_samples_dir_filenames(sample2_dir)}
-    common = sorted(set(f1) & set(f2))
-    print("Given %d events in %s and %d in %s: %d in both" % (len(f1), sample1_dir, len(f2), sample2_dir, len(common)))
-    ev1 = {e[0]: e for e in _load_all([f1[c] for c in common])}
-    ev2 = {e[0]: e for e in _load_all([f2[c] for c in common])}
-    both = sorted(set(ev1) & set(ev2))                    # (a file that could not be parsed drops its event from the pairing)
-    ev1, ev2 = [ev1[n] for n in both], [ev2[n] for n in both]
-    rows = []
+def _sources(samples_dir):
+    """event name -> where it is: a `.miso` path, or (database, name)."""
+    files, dbrows = list_events(samples_dir)
+    src = {os.path.basename(p)[:-len(".miso")]: p for p in files}
+    for dbf, names in dbrows.items():
+        for n in names:
+            src.setdefault(n, (dbf, n))
+    return src
+
+
+def _read_named(src, names):
+    files = [src[n] for n in names if isinstance(src[n], str)]
+    dbrows = {}
+    for n in names:
+        if not isinstance(src[n], str):
+            dbrows.setdefault(src[n][0], []).append(n)
+    return files, dbrows
+
+
+def _compare_parsed(pairs, confidence_level, smoothing, device, rows):
+    """Comparison rows of host-parsed pairs ((name, samples, header), (name, samples, header))."""
     groups = {}
-    for a, b2 in zip(ev1, ev2):
+    for a, b2 in pairs:
         if a[1].shape != b2[1].shape:
             print("Skipping %s: the two samples differ in isoforms or sample count" % a[0])
             continue
@@ -122,11 +367,77 @@ def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_l
         for i, (a, c) in enumerate(group):
             _, _, bf, _ = b1.comparison(i)
             rows.append((a[0], tuple(b1.summary(i)), tuple(b2.summary(i)), bf, a[2], c[2]))
+
+
+def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_level=0.95, smoothing=0.3,
+                              sample_labels=None, device=0, decoder=None):
+    """hypothesis_test.py:186-345: events present in BOTH directories (262-264), `<l1>_vs_<l2>.miso_bf`."""
+    decoder = _decoder(decoder)
+    stats = _Stats(decoder)
+    l1, l2 = sample_labels or (os.path.basename(os.path.normpath(sample1_dir)), os.path.basename(os.path.normpath(sample2_dir)))
+    f1, f2 = _sources(sample1_dir), _sources(sample2_dir)
+    common = sorted(set(f1) & set(f2))
+    print("Given %d events in %s and %d in %s: %d in both" % (len(f1), sample1_dir, len(f2), sample2_dir, len(common)))
+    rows = []
+    if decoder == "host":
+        sides = []
+        for src in (f1, f2):
+            files, dbrows = _read_named(src, common)
+            sides.append({e[0]: e for e in _load_all(files + _read_events([], dbrows))})
+        ev1, ev2 = sides
+        both = sorted(set(ev1) & set(ev2))                # (an event that could not be parsed drops out of the pairing)
+        stats.stage("read+parse")
+        _compare_parsed([(ev1[n], ev2[n]) for n in both], confidence_level, smoothing, device, rows)
+    else:
+        sides = []
+        for src in (f1, f2):
+            evs = _read_events(*_read_named(src, common))
+            _shape(evs)
+            sides.append({e.name: e for e in evs})
+        ev1, ev2 = sides
+        both = sorted(set(ev1) & set(ev2))
+        stats.stage("read+shape")
+        left, groups = [], {}
+        for n in both:
+            a, c = ev1[n], ev2[n]
+            if not (_device_ok(a) and _device_ok(c)):
+                left.append((a, c))
+            elif (a.K, a.S) != (c.K, c.S):
+                print("Skipping %s: the two samples differ in isoforms or sample count" % n)
+            else:
+                groups.setdefault(a.S, []).append((a, c))
+        for S, group in sorted(groups.items()):
+            lo, _ = summary.credible_interval_ranks(S, confidence_level)
+            if lo <= 0 or S < 2:
+                continue
+            for run in _text_batches(group, lambda p: len(p[0].body) + len(p[1].body)):
+                b1 = _text_batch([p[0] for p in run], S, device, stats)
+                b2 = _text_batch([p[1] for p in run], S, device, stats)
+                b1.summarize(confidence_level); b2.summarize(confidence_level)
+                b1.compare(b2, smoothing)
+                for i, (a, c) in enumerate(run):
+                    if b1.status[i] or b2.status[i]:
+                        left.append((a, c))
+                        continue
+                    _, _, bf, _ = b1.comparison(i)
+                    rows.append((a.name, tuple(b1.summary(i)), tuple(b2.summary(i)), bf, _header_fields(a.header),
+                                 _header_fields(c.header)))
+        stats.stage("decode+compare")
+        # pairs with a side the device decoder did not take: both sides through the host parser
+        for a, c in left:
+            for e in (a, c):
+                if e.name not in stats.d["fallback_events"]:
+                    stats.d["fallback_events"].append(e.name)
+        parsed = [(_parse_or_skip(a), _parse_or_skip(c)) for a, c in left]
+        _compare_parsed([p for p in parsed if p[0] is not None and p[1] is not None], confidence_level, smoothing,
+                        device, rows)
     rows.sort(key=lambda r: r[0])
     name = "%s_vs_%s" % (l1, l2)
     out = os.path.join(output_dir, name, "bayes-factors", name + ".miso_bf")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     compare.write_comparison(out, rows)
+    stats.stage("write")
+    stats.done()
     return out, len(rows)
 
 
