@@ -392,6 +392,43 @@ int miso_selftest_detmath(const double *x, int n, double *out_exp, double *out_l
                           double *out_sqrt, double *out_qnorm);
 int miso_selftest_philox(const uint32_t *ctr_key6, int n, uint32_t *out4);
 
+/* The device functions the sampler kernels are built from, one element per thread over host arrays (test-only surface,
+   tests/test_gpu_primitives.py).  Element i runs on thread i of 256-thread workgroups: elements 64 w .. 64 w + 63 share a
+   wavefront, which is what the routines that choose a route per wavefront see. */
+enum { MISO_SELFTEST_EXP_N = 0,   /* csrc/detmath_n.hpp det_exp_n<width>, width 1, 2, 3 or 5 */
+       MISO_SELFTEST_LOG_N,       /* det_log_n<width> */
+       MISO_SELFTEST_EXP_T,       /* det_exp_t, det_log_t, det_sqrt_pos: width 1 */
+       MISO_SELFTEST_LOG_T,
+       MISO_SELFTEST_SQRT_POS };
+/* out[i * width + j] = routine(x[(i + j * stride) % n]): the `width` interleaved arguments of one call differ; the
+   coefficient tables come from registers, loaded as the kernels load them */
+int miso_selftest_detmath_n(int routine, int width, const double *x, int n, int stride, double *out);
+/* The draw thresholds: out[i] = #{32-bit words u : the reference's test holds for rnd = fl(fl(u 2^-32) T[i]) against
+   c[i]}, 0 .. 2^32 -- `rnd < c` (LT) or `!(rnd > c)` (LE).  Exact for every finite c >= 0, T >= 0. */
+enum { MISO_SELFTEST_K2_THRESHOLD = 0,      /* kernels_k2.inl k2_threshold(c, T): route chosen per wavefront */
+       MISO_SELFTEST_K2_THRESHOLD_EXACT,    /* k2_threshold_exact */
+       MISO_SELFTEST_FLAT_LT,               /* kernels_flat.inl: estimate and choice between flat_threshold and */
+       MISO_SELFTEST_FLAT_LE,               /*   flat_threshold_fast as sampler_flat's threshold pass makes them */
+       MISO_SELFTEST_FLAT_GENERAL_LT,       /* flat_threshold itself */
+       MISO_SELFTEST_FLAT_GENERAL_LE,
+       MISO_SELFTEST_FLAT_FAST_LT,          /* flat_threshold_fast itself: the caller keeps to its precondition */
+       MISO_SELFTEST_FLAT_FAST_LE,          /*   (T in [1e-280, 1e280], 2 <= c (2^32 / T) <= 2^32 - 3) */
+       MISO_SELFTEST_DRAW_LT,               /* kernels_grp.inl draw_threshold<false>, estimate as sampler_grp forms it */
+       MISO_SELFTEST_DRAW_LE };             /* draw_threshold<true> */
+int miso_selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out);
+/* kernels_flat.inl count_below: out[i] = D[i] + #{j < 4 : w4[4 i + j] < T[i]} */
+int miso_selftest_count_below(const int32_t *D, const uint32_t *w4, const uint32_t *T, int n, int32_t *out);
+/* One paired-end read's draw per element (kernels_grp.inl): K = 2 .. 10 isoforms, f[i K + k] the read's index into
+   fp_rep[il2] for isoform k (il2 - 2 = incompatible; fp_rep[il2 - 2] must be -0.0), psi[i K + k], rule_le[i]: 1 =
+   `!(rnd > c)`, 0 = `rnd < c` then the second isoform; word[i] the uniform.  out[i (K + 1) ...] = { the dense read
+   loop's pick (pe_all_tests) or -1 where that loop leaves the read to pe_pick_exact, over[K - 1] (1 where the read
+   passed over isoform k), pe_pick_exact's pick }. */
+int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const double *fp_rep, int il2,
+                          const uint32_t *rule_le, const uint32_t *word, int n, int32_t *out);
+/* kernels_k2.inl binomial_coop<G>, G = 1, 2, 4, 8 lanes per chain: `count` draws of Binomial(n, p) from the word streams
+   (seed, event_id, chain 0, iteration i, MISO_SITE_COUNTS), i = 0 .. count - 1 */
+int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,8 +10,15 @@
  * construction.  Every file that includes this header MUST be compiled with -ffp-contract=off
  * (the only fused operations are the explicit fma() calls below).
  *
- * Accuracy (checked in tests/test_detmath.py against libm over 10^6 points each):
- * exp, log <= 2 ulp; sqrt <= 1 ulp; qnorm as AS241 (about 1e-16 relative).
+ * Accuracy, asserted in tests/test_detmath.py against mpmath at 200 bits on random sets over each routine's range and
+ * on the places where a routine changes behaviour (error in ulps of the double nearest the exact value):
+ *   exp    <= 2 ulp asserted; worst measured 0.867 ulp (a subnormal result), 0.863 ulp among normal results
+ *   log    <= 2 ulp asserted; worst measured 0.834 ulp
+ *   sqrt   correctly rounded (bit-equal to the IEEE square root) on every point tried: 0.5 ulp
+ *   qnorm  worst measured relative error against the exact quantile 8.0e-16 (far lower tail, p ~ 2^-590; 6.5e-16 for
+ *          p >= 1e-30) -- AS241's own error: the same algorithm with libm's log and sqrt measures the same on the same
+ *          points, the two are bit-equal for |p - 0.5| <= 0.425, and the assertion is "libm variant's worst + 2 ulp"
+ * (tests/test_gpu_primitives.py then shows the device bit-equal to the host on the same points.)
  *
  *   miso_det_exp   range reduction x = k ln2 + r, |r| <= ln2/2, degree-13 Taylor (Horner, fma)
  *   miso_det_log   x = 2^e m, m in [sqrt(1/2), sqrt(2)), s = f/(2+f), atanh series in s^2

@@ -611,6 +611,70 @@ def selftest_detmath(x):
     return outs
 
 
+# ---- the samplers' device functions, one element per thread (include/miso_amd.h MISO_SELFTEST_*; tests/test_gpu_primitives.py) ----
+SELFTEST_EXP_N, SELFTEST_LOG_N, SELFTEST_EXP_T, SELFTEST_LOG_T, SELFTEST_SQRT_POS = range(5)
+(SELFTEST_K2_THRESHOLD, SELFTEST_K2_THRESHOLD_EXACT, SELFTEST_FLAT_LT, SELFTEST_FLAT_LE, SELFTEST_FLAT_GENERAL_LT,
+ SELFTEST_FLAT_GENERAL_LE, SELFTEST_FLAT_FAST_LT, SELFTEST_FLAT_FAST_LE, SELFTEST_DRAW_LT, SELFTEST_DRAW_LE) = range(10)
+
+
+def selftest_detmath_n(fn, x, width=1, stride=0):
+    """csrc/detmath_n.hpp routine `fn` at `width` arguments per call: out[i, j] = f(x[(i + j * stride) % n])"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros((len(x), width), np.float64)
+    check(lib().miso_selftest_detmath_n(int(fn), int(width), _p(x), len(x), int(stride), _p(out)))
+    return out
+
+
+def selftest_threshold(routine, c, T):
+    """#{32-bit words u for which the reference's draw test holds} as threshold routine `routine` counts it; element i
+    runs on thread i (64 consecutive elements share a wavefront)"""
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    if c.shape != T.shape or c.ndim != 1:
+        raise ValueError("c and T: two vectors of one length")
+    out = np.zeros(len(c), np.uint64)
+    check(lib().miso_selftest_threshold(int(routine), _p(c), _p(T), len(c), _p(out)))
+    return out
+
+
+def selftest_count_below(D, words4, T):
+    """kernels_flat.inl count_below: D + (w0 < T) + (w1 < T) + (w2 < T) + (w3 < T) per element"""
+    D = np.ascontiguousarray(D, dtype=np.int32)
+    w = np.ascontiguousarray(words4, dtype=np.uint32).reshape(len(D), 4)
+    T = np.ascontiguousarray(T, dtype=np.uint32)
+    if len(T) != len(D):
+        raise ValueError("D, words4 and T differ in length")
+    out = np.zeros(len(D), np.int32)
+    check(lib().miso_selftest_count_below(_p(D), _p(w), _p(T), len(D), _p(out)))
+    return out
+
+
+def selftest_pe_pick(frag, psi, fp_rep, rule_le, words):
+    """One paired-end read's draw per element, as the dense read loop makes it (kernels_grp.inl pe_all_tests) and as
+    pe_pick_exact does.  frag: n x K fragment indices into fp_rep, len(fp_rep) - 2 = incompatible (fp_rep there: -0.0);
+    psi: n x K; rule_le: 1 = `!(rnd > c)`, 0 = `rnd < c`, then the second isoform.
+    Returns (dense pick or -1 where the loop hands the read to pe_pick_exact, over[n, K - 1], pe_pick_exact's pick)."""
+    frag = np.ascontiguousarray(frag, dtype=np.uint8)
+    psi = np.ascontiguousarray(psi, dtype=np.float64)
+    fp = np.ascontiguousarray(fp_rep, dtype=np.float64)
+    rule = np.ascontiguousarray(rule_le, dtype=np.uint32)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    n, K = frag.shape
+    if psi.shape != (n, K) or len(rule) != n or len(words) != n:
+        raise ValueError("frag, psi: n x K; rule_le, words: n")
+    out = np.zeros((n, K + 1), np.int32)
+    check(lib().miso_selftest_pe_pick(K, _p(frag), _p(psi), _p(fp), len(fp), _p(rule), _p(words), n, _p(out)))
+    return out[:, 0].copy(), out[:, 1:K].copy(), out[:, K].copy()
+
+
+def selftest_binomial(G, n, p, count, seed=1, event_id=0):
+    """`count` draws of Binomial(n, p) by kernels_k2.inl binomial_coop<G> (chain 0, iterations 0 .. count - 1)"""
+    out = np.zeros(count, np.int32)
+    check(lib().miso_selftest_binomial(int(G), C.c_uint64(seed), C.c_uint32(event_id), C.c_int32(n), C.c_double(p),
+                                       int(count), _p(out)))
+    return out
+
+
 def selftest_convergent_mean(samples, chains):
     """samples: S x K (row i from chain i % chains) -> True if stop=CONVERGENT_MEAN would stop (miso.c:556-636)"""
     a = np.ascontiguousarray(samples, dtype=np.float64)

@@ -19,6 +19,13 @@ miso_batch *batch_new(const miso_params_t &p);
 int choose_lanes_per_chain(long chains, int max_quads, int wave_slots, int max_cpw);
 void selftest_detmath(const double *x, int n, double *e, double *l, double *s, double *q);
 void selftest_philox(const uint32_t *in6, int n, uint32_t *out4);
+// kernels_selftest.hip
+void selftest_detmath_n(int fn, int width, const double *x, int n, int stride, double *out);
+void selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out);
+void selftest_count_below(const int32_t *D, const uint32_t *w4, const uint32_t *T, int n, int32_t *out);
+void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double *fp_rep, int il2, const uint32_t *rule_le,
+                      const uint32_t *word, int n, int32_t *out);
+void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
 
 // A device table and what it was last filled from: its host contents, or the key of the plan it was built for.  reset()
 // frees the allocation and forgets both, so that neither outlives it (the next upload may be to another device).

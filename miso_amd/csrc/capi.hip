@@ -979,5 +979,21 @@ int miso_selftest_detmath(const double *x, int n, double *out_exp, double *out_l
 int miso_selftest_philox(const uint32_t *ctr_key6, int n, uint32_t *out4) {
   return guarded([&] { selftest_philox(ctr_key6, n, out4); });
 }
+int miso_selftest_detmath_n(int routine, int width, const double *x, int n, int stride, double *out) {
+  return guarded([&] { selftest_detmath_n(routine, width, x, n, stride, out); });
+}
+int miso_selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out) {
+  return guarded([&] { selftest_threshold(routine, c, T, n, out); });
+}
+int miso_selftest_count_below(const int32_t *D, const uint32_t *w4, const uint32_t *T, int n, int32_t *out) {
+  return guarded([&] { selftest_count_below(D, w4, T, n, out); });
+}
+int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const double *fp_rep, int il2,
+                          const uint32_t *rule_le, const uint32_t *word, int n, int32_t *out) {
+  return guarded([&] { selftest_pe_pick(K, f, psi, fp_rep, il2, rule_le, word, n, out); });
+}
+int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out) {
+  return guarded([&] { selftest_binomial(G, seed, event_id, n, p, count, out); });
+}
 
 }  // extern "C"

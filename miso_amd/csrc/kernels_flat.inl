@@ -81,10 +81,15 @@ __device__ __forceinline__ double flat_threshold(bool le, double c, double T, do
   const double t0 = __builtin_floor(est);
   const int n = fthr_pred(le, t0 - 1.0, c, T) + fthr_pred(le, t0, c, T) + fthr_pred(le, t0 + 1.0, c, T);
   double t = t0 - 1.0 + static_cast<double>(n);
-  if (!fthr_pred(le, t0 - 2.0, c, T) || fthr_pred(le, t0 + 2.0, c, T)) {  // exact fallback, rarely taken
-    t = t0;
-    for (int g = 0; g < 4096 && t > 0.0 && !fthr_pred(le, t - 1.0, c, T); g++) t = t - 1.0;
-    for (int g = 0; g < 4096 && t < 4294967296.0 && fthr_pred(le, t, c, T); g++) t = t + 1.0;
+  if (!fthr_pred(le, t0 - 2.0, c, T) || fthr_pred(le, t0 + 2.0, c, T)) {
+    // est is not next to the boundary (2^32 / T overflowed, T subnormal or 0, c == T == 0): bisection on u over [0, 2^32],
+    // at most 33 tests, exact for every finite c >= 0, T >= 0 (the test is monotone in u).  Every u < lo passes, hi does not.
+    double lo = 0.0, hi = 4294967296.0;
+    for (int g = 0; g < 33 && lo < hi; g++) {
+      const double mid = __builtin_floor((lo + hi) * 0.5);
+      if (fthr_pred(le, mid, c, T)) lo = mid + 1.0; else hi = mid;
+    }
+    t = lo;
   }
   return t < 0.0 ? 0.0 : t;
 }

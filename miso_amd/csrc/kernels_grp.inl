@@ -199,17 +199,22 @@ template <bool LE> __device__ __forceinline__ bool thr_pred(int64_t u, double c,
   const double rnd = static_cast<double>(static_cast<uint32_t>(u)) * (1.0 / 4294967296.0) * T;
   return LE ? !(rnd > c) : (rnd < c);
 }
-// `est` only seeds the search (any value gives the exact threshold; a good one makes it short)
+// `est` only seeds the search: next to the boundary, three tests (and two that guard them) give the count; anywhere else
+// -- 2^32 / T overflowed, T subnormal or 0 -- a bisection on u over [0, 2^32] does, in at most 33 tests.  Exact for every
+// finite c >= 0, T >= 0 whatever est is, because the test is monotone in u.
 template <bool LE> __device__ __forceinline__ uint64_t draw_threshold(double c, double T, double est) {
   est = (est > 0.0) ? est : 0.0;                      // also maps NaN to 0
   est = (est > 4294967296.0) ? 4294967296.0 : est;
   const int64_t t0 = static_cast<int64_t>(est);
   const int n = thr_pred<LE>(t0 - 1, c, T) + thr_pred<LE>(t0, c, T) + thr_pred<LE>(t0 + 1, c, T);
   int64_t t = t0 - 1 + n;
-  if (!thr_pred<LE>(t0 - 2, c, T) || thr_pred<LE>(t0 + 2, c, T)) {  // exact fallback, rarely taken
-    t = t0;
-    for (int g = 0; g < 4096 && t > 0 && !thr_pred<LE>(t - 1, c, T); g++) t--;
-    for (int g = 0; g < 4096 && t < 4294967296ll && thr_pred<LE>(t, c, T); g++) t++;
+  if (!thr_pred<LE>(t0 - 2, c, T) || thr_pred<LE>(t0 + 2, c, T)) {  // rarely taken: every u < lo passes, hi does not
+    int64_t lo = 0, hi = 4294967296ll;
+    for (int g = 0; g < 33 && lo < hi; g++) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (thr_pred<LE>(mid, c, T)) lo = mid + 1; else hi = mid;
+    }
+    t = lo;
   }
   return static_cast<uint64_t>(t < 0 ? 0 : t);
 }

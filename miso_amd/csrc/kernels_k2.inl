@@ -124,10 +124,16 @@ __device__ __forceinline__ uint64_t k2_threshold_exact(double p0, double T) {
   // t0 - 1 + (number of true tests among t0-1, t0, t0+1); the two outer tests guard that claim.
   const int n = k2_pred(t0 - 1, p0, T) + k2_pred(t0, p0, T) + k2_pred(t0 + 1, p0, T);
   int64_t t = t0 - 1 + n;
-  if (!k2_pred(t0 - 2, p0, T) || k2_pred(t0 + 2, p0, T)) {  // never taken for finite psi; exact fallback
-    t = t0 < 0 ? 0 : (t0 > 4294967296ll ? 4294967296ll : t0);
-    for (int g = 0; g < 4096 && t > 0 && !k2_pred(t - 1, p0, T); g++) t--;
-    for (int g = 0; g < 4096 && t < 4294967296ll && k2_pred(t, p0, T); g++) t++;
+  if (!k2_pred(t0 - 2, p0, T) || k2_pred(t0 + 2, p0, T)) {
+    // The estimate is not next to the boundary (T subnormal or so small that the quotient overflows, T = 0, non-finite
+    // psi): bisection on u over [0, 2^32], at most 33 tests -- exact for every finite p0 >= 0, T >= 0, because the test is
+    // monotone in u.  Every u < lo passes, hi does not.
+    int64_t lo = 0, hi = 4294967296ll;
+    for (int g = 0; g < 33 && lo < hi; g++) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (k2_pred(mid, p0, T)) lo = mid + 1; else hi = mid;
+    }
+    t = lo;
   }
   t = t < 0 ? 0 : t;
   return static_cast<uint64_t>(t);

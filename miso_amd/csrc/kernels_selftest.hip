@@ -1,0 +1,283 @@
+// kernels_selftest.hip -- the device functions the samplers are built from, callable one element per thread over host
+// arrays (include/miso_amd.h miso_selftest_*; tests/test_gpu_primitives.py).  This unit includes the samplers' .inl files
+// for their anonymous-namespace routines and instantiates none of their kernels: test-only surface, no sampler's code
+// changes with it.  One thread per element, 256 threads per workgroup, bounded work per thread.
+#include "kernels_k2.inl"
+#include "kernels_flat.inl"
+#include "kernels_grp.inl"
+
+#include <vector>
+
+#include "host.hpp"
+
+#pragma clang fp contract(off)
+
+namespace miso {
+
+namespace {
+
+// argument j of element i is point (i + j stride) mod n: a mix-up between the interleaved chains of det_*_n shows
+template <int N, bool LOG> __device__ __forceinline__ void st_detmath_n(const double *x, int n, int stride, int i, double *out,
+                                                                         const double (&te)[12], const double (&tl)[12]) {
+  double in[N], o[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) in[j] = x[static_cast<int>((static_cast<long long>(i) + static_cast<long long>(j) * stride) % n)];
+  if (LOG) det_log_n<N>(in, o, tl);
+  else det_exp_n<N>(in, o, te);
+#pragma unroll
+  for (int j = 0; j < N; j++) out[static_cast<size_t>(i) * N + j] = o[j];
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) selftest_detmath_n_kernel(int fn, int width, const double *x, int n, int stride, double *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double te[12], tl[12];
+  det_tables_to_registers(te, tl);
+  if (i >= n) return;
+  switch (fn * 8 + width) {
+  case MISO_SELFTEST_EXP_N * 8 + 1: st_detmath_n<1, false>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_EXP_N * 8 + 2: st_detmath_n<2, false>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_EXP_N * 8 + 3: st_detmath_n<3, false>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_EXP_N * 8 + 5: st_detmath_n<5, false>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_LOG_N * 8 + 1: st_detmath_n<1, true>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_LOG_N * 8 + 2: st_detmath_n<2, true>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_LOG_N * 8 + 3: st_detmath_n<3, true>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_LOG_N * 8 + 5: st_detmath_n<5, true>(x, n, stride, i, out, te, tl); break;
+  case MISO_SELFTEST_EXP_T * 8 + 1: out[i] = det_exp_t(x[i], te); break;
+  case MISO_SELFTEST_LOG_T * 8 + 1: out[i] = det_log_t(x[i], tl); break;
+  case MISO_SELFTEST_SQRT_POS * 8 + 1: out[i] = det_sqrt_pos(x[i]); break;
+  default: break;
+  }
+}
+
+// Element order = thread order: elements 64 w .. 64 w + 63 share a wavefront, so the caller decides what a wavefront-uniform
+// choice of route (__all / __any) sees.  Threads behind the last element carry an input that every fast route accepts.
+__global__ void __launch_bounds__(256) selftest_threshold_kernel(int routine, const double *c_in, const double *T_in, int n, uint64_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool on = i < n;
+  const double c = on ? c_in[i] : 0.5, T = on ? T_in[i] : 1.0;
+  uint64_t t = 0;
+  switch (routine) {
+  case MISO_SELFTEST_K2_THRESHOLD: t = k2_threshold(c, T); break;
+  case MISO_SELFTEST_K2_THRESHOLD_EXACT: t = k2_threshold_exact(c, T); break;
+  case MISO_SELFTEST_FLAT_LT:
+  case MISO_SELFTEST_FLAT_LE: {   // as sampler_flat's threshold pass forms the estimate and chooses the routine
+    const bool le = routine == MISO_SELFTEST_FLAT_LE;
+    const double inv = 4294967296.0 / T;
+    const bool tnormal = T >= 1e-280 && T <= 1e280;
+    const double est = c * inv;
+    double r;
+    if (__any(on && !(tnormal && est >= 2.0 && est <= 4294967293.0))) r = flat_threshold(le, c, T, est);
+    else r = flat_threshold_fast(le, c, T, est);
+    t = static_cast<uint64_t>(r);
+    break;
+  }
+  case MISO_SELFTEST_FLAT_GENERAL_LT:
+  case MISO_SELFTEST_FLAT_GENERAL_LE:
+    t = static_cast<uint64_t>(flat_threshold(routine == MISO_SELFTEST_FLAT_GENERAL_LE, c, T, c * (4294967296.0 / T)));
+    break;
+  case MISO_SELFTEST_FLAT_FAST_LT:
+  case MISO_SELFTEST_FLAT_FAST_LE:   // (the caller keeps to the routine's precondition)
+    t = static_cast<uint64_t>(flat_threshold_fast(routine == MISO_SELFTEST_FLAT_FAST_LE, c, T, c * (4294967296.0 / T)));
+    break;
+  case MISO_SELFTEST_DRAW_LT: t = draw_threshold<false>(c, T, c * (4294967296.0 / T)); break;   // est as sampler_grp forms it
+  case MISO_SELFTEST_DRAW_LE: t = draw_threshold<true>(c, T, c * (4294967296.0 / T)); break;
+  default: break;
+  }
+  if (on) out[i] = t;
+}
+
+__global__ void __launch_bounds__(256) selftest_count_below_kernel(const int32_t *D0, const uint32_t *w4, const uint32_t *T, int n, int32_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int D = D0[i];
+  const uint32_t *w = w4 + 4 * static_cast<size_t>(i);
+  count_below(D, w[0], w[1], w[2], w[3], T[i]);
+  out[i] = D;
+}
+
+namespace {
+
+// One read's draw as pe_dense makes it.  The lines between the record's bytes and pe_all_tests are RESTATED from pe_dense's
+// body (cumulative weights from -0.0, rnd, the rule's adjustment, "not exact here"): lifting them into a helper both call
+// would touch every paired-end sampler's code.  The table offsets are the isoform numbers, so fsel is the pick.
+template <int KK>
+__device__ __forceinline__ void st_pe_pick(const uint8_t *f, const double *psi, const double *fp_rep, int il2, uint32_t rule_le,
+                                           uint32_t word, int32_t *out) {
+  uint32_t pk[KK]; int64_t cb[KK];
+  int over[KK - 1];
+#pragma unroll
+  for (int k = 0; k < KK - 1; k++) over[k] = 0;
+  double T = -0.0;
+#pragma unroll
+  for (int k = 0; k < KK; k++) {
+    pk[k] = static_cast<uint32_t>(k);
+    T = T + psi[k] * fp_rep[f[k]];
+    cb[k] = __double_as_longlong(T);
+  }
+  const double rnd = miso_u01(word) * T;
+  const bool ok = rnd < T;
+  int64_t rb = __double_as_longlong(rnd) - static_cast<int64_t>(rule_le & 1u);
+  rb = ok ? rb : INT64_MIN;
+  uint32_t fsel = pk[0];
+  pe_all_tests<KK>(rb, cb, pk, fsel, over);
+  out[0] = ok ? static_cast<int32_t>(fsel) : -1;
+#pragma unroll
+  for (int k = 0; k < KK - 1; k++) out[1 + k] = over[k];
+  out[KK] = pe_pick_exact(f, KK, il2, psi, fp_rep, (rule_le & 1u) == 0, word);
+}
+
+}  // namespace
+
+// f: n x KK fragment indices (il2 - 2 = incompatible, whose fp_rep entry is -0.0), psi: n x KK, fp_rep: il2 entries, rule:
+// 1 = `!(rnd > c)`, 0 = `rnd < c` then unconditional; out: n x (KK + 1) = {dense pick or -1 where pe_dense would hand the read
+// to pe_pick_exact, over[KK - 1], pe_pick_exact's pick}
+__global__ void __launch_bounds__(256) selftest_pe_pick_kernel(int KK, const uint8_t *f, const double *psi, const double *fp_rep, int il2,
+                                                               const uint32_t *rule_le, const uint32_t *word, int n, int32_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t *fi = f + static_cast<size_t>(i) * KK;
+  const double *pi = psi + static_cast<size_t>(i) * KK;
+  int32_t *o = out + static_cast<size_t>(i) * (KK + 1);
+  switch (KK) {
+  case 2: st_pe_pick<2>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 3: st_pe_pick<3>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 4: st_pe_pick<4>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 5: st_pe_pick<5>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 6: st_pe_pick<6>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 7: st_pe_pick<7>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 8: st_pe_pick<8>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 9: st_pe_pick<9>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  case 10: st_pe_pick<10>(fi, pi, fp_rep, il2, rule_le[i], word[i], o); break;
+  default: break;
+  }
+}
+
+// draw i of chain 0 (iteration i) by the G lanes [G i, G i + G) of the grid: all lanes of a chain call binomial_coop together;
+// the lanes behind the last draw repeat it and store nothing
+template <int G>
+__global__ void __launch_bounds__(256) selftest_binomial_kernel(uint64_t seed, uint32_t event_id, int32_t n, double p, int count,
+                                                                const double *lf, int32_t *out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int sub = t % G, lane = threadIdx.x & 63;
+  const int i = min(t / G, count - 1);
+  const int32_t y = binomial_coop<G>(seed, event_id, 0u, static_cast<uint32_t>(i), n, p, lf, sub, lane - sub);
+  if (t / G < count && sub == 0) out[i] = y;
+}
+
+#define ST_HIP_OK(call)                                                                    \
+  do {                                                                                     \
+    hipError_t e_ = (call);                                                                \
+    if (e_ != hipSuccess)                                                                  \
+      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
+  } while (0)
+
+namespace {
+
+// device copies of host arrays for one launch, freed on every way out
+struct StBuffers {
+  std::vector<void *> ptrs;
+  ~StBuffers() { for (void *p : ptrs) (void) hipFree(p); }
+  template <class T> T *in(const T *host, size_t count) {
+    T *d = out<T>(count);
+    if (count) ST_HIP_OK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
+  template <class T> T *out(size_t count) {
+    void *d = nullptr;
+    ST_HIP_OK(hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(T)));
+    ptrs.push_back(d);
+    return static_cast<T *>(d);
+  }
+  template <class T> void back(T *host, const T *dev, size_t count) {
+    ST_HIP_OK(hipGetLastError());
+    ST_HIP_OK(hipDeviceSynchronize());
+    if (count) ST_HIP_OK(hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost));
+  }
+};
+
+void st_need_device(int n) {
+  if (n < 0) MISO_FAIL(MISO_EINVAL, "negative element count");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device");
+}
+dim3 st_grid(size_t threads) { return dim3(static_cast<unsigned>((threads + 255) / 256)); }
+
+}  // namespace
+
+void selftest_detmath_n(int fn, int width, const double *x, int n, int stride, double *out) {
+  const bool wide = fn == MISO_SELFTEST_EXP_N || fn == MISO_SELFTEST_LOG_N;
+  if (wide ? !(width == 1 || width == 2 || width == 3 || width == 5)
+           : !((fn == MISO_SELFTEST_EXP_T || fn == MISO_SELFTEST_LOG_T || fn == MISO_SELFTEST_SQRT_POS) && width == 1))
+    MISO_FAIL(MISO_EINVAL, "no such detmath_n routine / width");
+  if (stride < 0) MISO_FAIL(MISO_EINVAL, "negative stride");
+  st_need_device(n);
+  if (n == 0) return;
+  StBuffers b;
+  const double *dx = b.in(x, static_cast<size_t>(n));
+  double *dout = b.out<double>(static_cast<size_t>(n) * width);
+  hipLaunchKernelGGL(selftest_detmath_n_kernel, st_grid(n), dim3(256), 0, 0, fn, width, dx, n, stride, dout);
+  b.back(out, dout, static_cast<size_t>(n) * width);
+}
+
+void selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out) {
+  if (routine < 0 || routine > MISO_SELFTEST_DRAW_LE) MISO_FAIL(MISO_EINVAL, "no such threshold routine");
+  st_need_device(n);
+  if (n == 0) return;
+  StBuffers b;
+  const double *dc = b.in(c, static_cast<size_t>(n)), *dT = b.in(T, static_cast<size_t>(n));
+  uint64_t *dout = b.out<uint64_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_threshold_kernel, st_grid(n), dim3(256), 0, 0, routine, dc, dT, n, dout);
+  b.back(out, dout, static_cast<size_t>(n));
+}
+
+void selftest_count_below(const int32_t *D, const uint32_t *w4, const uint32_t *T, int n, int32_t *out) {
+  st_need_device(n);
+  if (n == 0) return;
+  StBuffers b;
+  const int32_t *dD = b.in(D, static_cast<size_t>(n));
+  const uint32_t *dw = b.in(w4, 4 * static_cast<size_t>(n)), *dT = b.in(T, static_cast<size_t>(n));
+  int32_t *dout = b.out<int32_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_count_below_kernel, st_grid(n), dim3(256), 0, 0, dD, dw, dT, n, dout);
+  b.back(out, dout, static_cast<size_t>(n));
+}
+
+void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double *fp_rep, int il2, const uint32_t *rule_le,
+                      const uint32_t *word, int n, int32_t *out) {
+  if (KK < 2 || KK > 10) MISO_FAIL(MISO_EINVAL, "isoforms: 2 .. 10");
+  if (il2 < 3 || il2 > 256) MISO_FAIL(MISO_EINVAL, "fragment table: 3 .. 256 entries");
+  st_need_device(n);
+  const size_t nk = static_cast<size_t>(n) * KK;
+  for (size_t i = 0; i < nk; i++) if (f[i] >= il2) MISO_FAIL(MISO_EINVAL, "fragment index outside the table");
+  if (n == 0) return;
+  StBuffers b;
+  const uint8_t *df = b.in(f, nk);
+  const double *dpsi = b.in(psi, nk), *dfp = b.in(fp_rep, static_cast<size_t>(il2));
+  const uint32_t *drule = b.in(rule_le, static_cast<size_t>(n)), *dword = b.in(word, static_cast<size_t>(n));
+  int32_t *dout = b.out<int32_t>(static_cast<size_t>(n) * (KK + 1));
+  hipLaunchKernelGGL(selftest_pe_pick_kernel, st_grid(n), dim3(256), 0, 0, KK, df, dpsi, dfp, il2, drule, dword, n, dout);
+  b.back(out, dout, static_cast<size_t>(n) * (KK + 1));
+}
+
+void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out) {
+  if (!(G == 1 || G == 2 || G == 4 || G == 8)) MISO_FAIL(MISO_EINVAL, "lanes per chain: 1, 2, 4, 8");
+  if (n < 0 || n > (1 << 24)) MISO_FAIL(MISO_EINVAL, "n: 0 .. 2^24");
+  st_need_device(count);
+  if (count == 0) return;
+  std::vector<double> lf(static_cast<size_t>(n) + 2);
+  miso_logfact_fill(lf.data(), static_cast<int32_t>(lf.size()));   // as miso_batch::upload builds the batch's table
+  StBuffers b;
+  const double *dlf = b.in(lf.data(), lf.size());
+  int32_t *dout = b.out<int32_t>(static_cast<size_t>(count));
+  const dim3 grid = st_grid(static_cast<size_t>(count) * G);
+  switch (G) {
+  case 1: hipLaunchKernelGGL(selftest_binomial_kernel<1>, grid, dim3(256), 0, 0, seed, event_id, n, p, count, dlf, dout); break;
+  case 2: hipLaunchKernelGGL(selftest_binomial_kernel<2>, grid, dim3(256), 0, 0, seed, event_id, n, p, count, dlf, dout); break;
+  case 4: hipLaunchKernelGGL(selftest_binomial_kernel<4>, grid, dim3(256), 0, 0, seed, event_id, n, p, count, dlf, dout); break;
+  default: hipLaunchKernelGGL(selftest_binomial_kernel<8>, grid, dim3(256), 0, 0, seed, event_id, n, p, count, dlf, dout); break;
+  }
+  b.back(out, dout, static_cast<size_t>(count));
+}
+
+}  // namespace miso

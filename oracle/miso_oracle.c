@@ -151,6 +151,8 @@ double orc_qnorm_det(double p) { return as241(p, &MATH_DET); }
 double orc_det_exp(double x) { return miso_det_exp(x); }
 double orc_det_log(double x) { return miso_det_log(x); }
 double orc_det_sqrt(double x) { return miso_det_sqrt(x); }
+/* the header's own quantile routine (what the kernels call; as241() above carries its own copy of the tables) */
+double orc_det_qnorm(double p) { return miso_det_qnorm(p); }
 /* log factorials for miso_binomial (include/miso_binomial.h), grown on demand */
 static double *g_lf = NULL; static int g_lf_n = 0;
 static const double *logfact(int n) { /* at least n + 1 entries */
@@ -172,6 +174,8 @@ void orc_binomial(uint64_t seed, uint32_t event_id, int32_t n, double p, int cou
     out[i] = miso_binomial(&us, n, p, logfact(n));
   }
 }
+/* test hook: the first n entries of the log-factorial table (log 0! .. log (n-1)!) as miso_logfact_fill builds it */
+void orc_logfact(int n, double *out) { miso_logfact_fill(out, n); }
 void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                 uint32_t *out4) {
   miso_u32x4 o = miso_philox4x32(c0, c1, c2, c3, k0, k1);

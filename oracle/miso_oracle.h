@@ -117,7 +117,9 @@ double orc_qnorm_det(double p);
 double orc_det_exp(double x);
 double orc_det_log(double x);
 double orc_det_sqrt(double x);
+double orc_det_qnorm(double p);
 void orc_binomial(uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
+void orc_logfact(int n, double *out);
 void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                 uint32_t *out4);
 void orc_philox_r(int rounds, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

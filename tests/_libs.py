@@ -254,7 +254,7 @@ class OrcLib(_Base):
         super().__init__(path or ensure_oracle_built())
         L = self.lib
         for name in ("orc_qnorm_libm", "orc_qnorm_det", "orc_det_exp", "orc_det_log",
-                     "orc_det_sqrt"):
+                     "orc_det_sqrt", "orc_det_qnorm"):
             getattr(L, name).restype = C.c_double
             getattr(L, name).argtypes = [C.c_double]
 
@@ -285,6 +285,12 @@ class OrcLib(_Base):
         """`count` draws of include/miso_binomial.h's Binomial(n, p) (word streams of iterations 0 .. count-1)."""
         out = np.zeros(count, np.int32)
         self.lib.orc_binomial(C.c_uint64(seed), C.c_uint32(event_id), C.c_int32(n), C.c_double(p), C.c_int(count), _p(out))
+        return out
+
+    def logfact(self, n):
+        """log 0! .. log (n-1)! as include/miso_binomial.h's miso_logfact_fill builds the binomial's table"""
+        out = np.zeros(n)
+        self.lib.orc_logfact(C.c_int(n), _p(out))
         return out
 
     def _opts(self, mode, seed, event_id, per_read_sums):
