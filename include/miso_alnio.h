@@ -178,6 +178,58 @@ int miso_region_counts(const miso_alnfile_t *f, int device, int n_intervals, con
                        const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
                        miso_region_stats_t *stats);
 
+/* ---- per-base read density and junction counts of many regions (sashimi_plot, misopy/sashimi_plot/plot_utils/
+ * plot_gene.py:48-57, 398-444 readsToWiggle_pysam) ----
+ * Regions: n_regions triples (seqid[i], tx_start[i], tx_end[i]) in the numbers a GFF gives (1-based, inclusive); seqid[i]
+ * is matched exactly against the file's reference names.  Record coordinates: pos 0-based, bam_endpos as above.  The
+ * reference mixes the two systems and so does this call:
+ *   1. a record is fetched for a region when it is on its reference and pos < tx_end && bam_endpos > tx_start; no flag
+ *      matters;
+ *   2. a fetched record without a CIGAR, or with more than one N op, adds nothing; I and D do not disqualify;
+ *   3. its aligned positions are the reference positions of its M, =, X ops (D and N advance the reference; I, S, H, P do
+ *      not); qlen = the sum of its M, I, =, X lengths; a record without aligned positions adds nothing;
+ *   4. depth[x - tx_start] counts the records with an aligned position x, tx_start <= x <= tx_end; every such position
+ *      weighs 1 / qlen in wiggle;
+ *   5. two consecutive aligned positions x, y of one record with y > x + 1 (an N or a D between them) and
+ *      tx_start <= x <= tx_end give leftss = x + 1, rightss = y + 1; when tx_start < leftss < tx_end and
+ *      tx_start < rightss < tx_end the junction (leftss, rightss) of that region counts one more;
+ *   6. a region whose seqid the file does not name, or with tx_start > tx_end: all zero, no junction, no error;
+ *   7. regions may overlap, nest and repeat: each is computed as if alone.
+ * Out: region i owns L_i = max(0, tx_end[i] - tx_start[i] + 1) consecutive entries of depth and wiggle, the regions one
+ * after the other in the order given (out_cap = entries the two arrays hold, at least the sum of the L_i).
+ * wiggle[b] = the sum over the distinct qlen values q, ascending, of depth_q[b] / q in double, depth_q the depth from
+ * records of that qlen: exact integer counts first, so the value does not depend on the record order, the chunk size or
+ * the grouping (the reference adds 1. / qlen into a float32 array in file order).  Junctions: (region, leftss, rightss,
+ * count) sorted by region, leftss, rightss; two-call pattern: *n_jxn = their number, at most jxn_cap written (arrays may
+ * be NULL when jxn_cap == 0).
+ * chunk_records: records per device chunk (<= 0: 4 M).  accum_bytes: device bytes for the accumulators of one group of
+ * regions (<= 0: 1 GiB); the regions are processed in groups that fit (a region larger than the budget is a group of its
+ * own), one pass over the records per group.  qlen up to 65535; a fetched record beyond fails with MISO_EINVAL and names
+ * it.  Fails with MISO_ENODEVICE without a GPU: there is no CPU path.  stats may be NULL. */
+typedef struct {
+  int64_t fetched;           /* records fetched by at least one region                                            */
+  int64_t skipped_multi_n;   /* of those: more than one N op                                                     */
+  int64_t skipped_no_cigar;  /* of those: no CIGAR                                                               */
+  int64_t with_indel;        /* of those, not skipped: an I or a D op                                            */
+  int64_t qlen_classes;      /* distinct qlen among the fetched, not skipped records with an aligned position     */
+  int64_t chunks;            /* device chunks of one pass over the records                                       */
+  int64_t groups;            /* region groups = passes over the records after the mark pass                      */
+  int64_t junction_retries;  /* group passes repeated because the junction list had to grow                      */
+  double tables_ms;          /* host tables: all regions, then each group's                                      */
+  double mark_ms;            /* mark pass: copies of the columns and the kernel (device time)                    */
+  double records_ms;         /* group passes: copies of the columns and the kernel (device time)                 */
+  double scan_ms;            /* scan and finish kernels (device time)                                            */
+  double junction_ms;        /* junction keys back, sorted and counted on the host                               */
+  double copy_ms;            /* depth and wiggle back and into the caller's arrays                               */
+  double total_ms;           /* wall time of the whole call                                                      */
+} miso_density_stats_t;
+
+int miso_region_densities(const miso_alnfile_t *f, int device, int n_regions, const char *const *seqid,
+                          const int64_t *tx_start, const int64_t *tx_end, int64_t chunk_records, int64_t accum_bytes,
+                          int32_t *depth, double *wiggle, int64_t out_cap, int32_t *jxn_region, int64_t *jxn_left,
+                          int64_t *jxn_right, int64_t *jxn_count, int64_t jxn_cap, int64_t *n_jxn,
+                          miso_density_stats_t *stats);
+
 /* host threads the library uses by default: affinity mask capped by the cgroup CPU quota, <= 64 */
 int miso_usable_threads(void);
 

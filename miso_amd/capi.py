@@ -769,3 +769,48 @@ def region_counts(alnfile, seqids, starts, ends, device=0, chunk_records=0):
     check(L.miso_region_counts(alnfile._h, int(device), n, names, _p(st), _p(en), int(chunk_records), _p(counts),
                                C.byref(stats)))
     return counts[:n].copy(), stats.as_dict()
+
+
+# ---- per-base read density and junction counts (include/miso_alnio.h miso_region_densities) ----
+class DensityStats(C.Structure):
+    _fields_ = ([(n, C.c_int64) for n in ("fetched", "skipped_multi_n", "skipped_no_cigar", "with_indel", "qlen_classes",
+                                          "chunks", "groups", "junction_retries")]
+                + [(n, C.c_double) for n in ("tables_ms", "mark_ms", "records_ms", "scan_ms", "junction_ms", "copy_ms",
+                                             "total_ms")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def region_densities(alnfile, seqids, starts, ends, device=0, chunk_records=0, accum_bytes=0):
+    """Read density and junctions of every region (seqid, tx_start, tx_end), GFF numbers, of an open alignment file
+    (sam_utils.Samfile) in one device pass; seqids spelled as the file spells them.  Returns (depth, wiggle, junctions,
+    stats): per region an int32 array and a float64 array of tx_end - tx_start + 1 entries (empty when
+    tx_start > tx_end) and a list of (leftss, rightss, count) sorted by the splice sites; stats as a dict."""
+    n, names, st, en = _intervals(seqids, starts, ends)
+    lens = np.maximum(en - st + 1, 0) if n else np.zeros(0, np.int64)
+    off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+    total = int(off[-1])
+    depth = np.zeros(max(total, 1), np.int32)
+    wiggle = np.zeros(max(total, 1), np.float64)
+    stats = DensityStats()
+    found = C.c_int64(0)
+    L = lib()
+    L.miso_region_densities.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+                                        + [C.c_int64, C.POINTER(C.c_int64), C.POINTER(DensityStats)])
+    cap = 1 << 16
+    while True:
+        jr, jl = np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+        jrt, jc = np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        check(L.miso_region_densities(alnfile._h, int(device), n, names, _p(st), _p(en), int(chunk_records),
+                                      int(accum_bytes), _p(depth), _p(wiggle), total, _p(jr), _p(jl), _p(jrt), _p(jc),
+                                      cap, C.byref(found), C.byref(stats)))
+        if found.value <= cap:
+            break
+        cap = found.value            # the list did not fit: once more, with room for all of it
+    junctions = [[] for _ in range(n)]
+    for k in range(found.value):
+        junctions[jr[k]].append((int(jl[k]), int(jrt[k]), int(jc[k])))
+    return ([depth[off[i]:off[i + 1]].copy() for i in range(n)], [wiggle[off[i]:off[i + 1]].copy() for i in range(n)],
+            junctions, stats.as_dict())

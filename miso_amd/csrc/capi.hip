@@ -67,6 +67,13 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
                    const int64_t *end, int64_t chunk, int64_t *counts, miso_region_stats_t *stats);
 }  // namespace miso
 
+namespace miso {   // kernels_density.hip
+void region_densities(const miso_alnfile_t *f, int device, int n_regions, const char *const *seqid, const int64_t *start,
+                      const int64_t *end, int64_t chunk, int64_t accum_bytes, int32_t *depth, double *wiggle,
+                      int64_t out_cap, int32_t *jxn_region, int64_t *jxn_left, int64_t *jxn_right, int64_t *jxn_count,
+                      int64_t jxn_cap, int64_t *n_jxn, miso_density_stats_t *stats);
+}  // namespace miso
+
 namespace miso {   // kernels_text.hip
 void text_shape(int n, const unsigned char *text, const int64_t *offsets, int32_t *noiso, int32_t *n_rows);
 }  // namespace miso
@@ -538,6 +545,17 @@ int miso_region_counts(const miso_alnfile_t *f, int device, int n_intervals, con
                        const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
                        miso_region_stats_t *stats) {
   return guarded([&] { region_counts(f, device, n_intervals, seqid, start, end, chunk_records, counts, stats); });
+}
+
+int miso_region_densities(const miso_alnfile_t *f, int device, int n_regions, const char *const *seqid,
+                          const int64_t *tx_start, const int64_t *tx_end, int64_t chunk_records, int64_t accum_bytes,
+                          int32_t *depth, double *wiggle, int64_t out_cap, int32_t *jxn_region, int64_t *jxn_left,
+                          int64_t *jxn_right, int64_t *jxn_count, int64_t jxn_cap, int64_t *n_jxn,
+                          miso_density_stats_t *stats) {
+  return guarded([&] {
+    region_densities(f, device, n_regions, seqid, tx_start, tx_end, chunk_records, accum_bytes, depth, wiggle, out_cap,
+                     jxn_region, jxn_left, jxn_right, jxn_count, jxn_cap, n_jxn, stats);
+  });
 }
 
 int miso_gene_assignment_matrix(const miso_gene_t *gene, int readLength, int overHang, double *matrix, int max_cols,
