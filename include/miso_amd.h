@@ -428,6 +428,9 @@ int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const doub
 /* kernels_k2.inl binomial_coop<G>, G = 1, 2, 4, 8 lanes per chain: `count` draws of Binomial(n, p) from the word streams
    (seed, event_id, chain 0, iteration i, MISO_SITE_COUNTS), i = 0 .. count - 1 */
 int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
+/* csrc/text_digits.hpp text_digits, the rounding of summarize_as_text: out[i] = x[i] x 10^4 rounded to the nearest integer,
+   ties to even, on the exact product -- the digits of "%.4f" of x[i], sign included.  Finite |x[i]| < 2^38. */
+int miso_selftest_text_digits(const double *x, int n, int64_t *out);
 
 #ifdef __cplusplus
 }

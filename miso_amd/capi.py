@@ -675,6 +675,16 @@ def selftest_binomial(G, n, p, count, seed=1, event_id=0):
     return out
 
 
+def selftest_text_digits(x):
+    """csrc/text_digits.hpp text_digits per element: the digits of "%.4f" % x[i] as a signed integer (x 10^4, ties to even)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError("x: one vector")
+    out = np.zeros(len(x), np.int64)
+    check(lib().miso_selftest_text_digits(_p(x), len(x), _p(out)))
+    return out
+
+
 def selftest_convergent_mean(samples, chains):
     """samples: S x K (row i from chain i % chains) -> True if stop=CONVERGENT_MEAN would stop (miso.c:556-636)"""
     a = np.ascontiguousarray(samples, dtype=np.float64)

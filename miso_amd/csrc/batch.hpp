@@ -26,6 +26,7 @@ void selftest_count_below(const int32_t *D, const uint32_t *w4, const uint32_t *
 void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double *fp_rep, int il2, const uint32_t *rule_le,
                       const uint32_t *word, int n, int32_t *out);
 void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
+void selftest_text_digits(const double *x, int n, int64_t *out);
 
 // A device table and what it was last filled from: its host contents, or the key of the plan it was built for.  reset()
 // frees the allocation and forgets both, so that neither outlives it (the next upload may be to another device).

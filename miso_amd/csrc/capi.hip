@@ -1013,5 +1013,8 @@ int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const doub
 int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out) {
   return guarded([&] { selftest_binomial(G, seed, event_id, n, p, count, out); });
 }
+int miso_selftest_text_digits(const double *x, int n, int64_t *out) {
+  return guarded([&] { selftest_text_digits(x, n, out); });
+}
 
 }  // extern "C"

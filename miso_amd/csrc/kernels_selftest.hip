@@ -1,7 +1,8 @@
 // kernels_selftest.hip -- the device functions the samplers are built from, callable one element per thread over host
 // arrays (include/miso_amd.h miso_selftest_*; tests/test_gpu_primitives.py).  This unit includes the samplers' .inl files
 // for their anonymous-namespace routines and instantiates none of their kernels: test-only surface, no sampler's code
-// changes with it.  One thread per element, 256 threads per workgroup, bounded work per thread.
+// changes with it.  One thread per element, 256 threads per workgroup, bounded work per thread.  Also here: the summaries'
+// "%.4f" rounding (text_digits.hpp, shared with kernels_summary.hip; tests/test_gpu_text_digits.py).
 #include "kernels_k2.inl"
 #include "kernels_flat.inl"
 #include "kernels_grp.inl"
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "host.hpp"
+#include "text_digits.hpp"
 
 #pragma clang fp contract(off)
 
@@ -95,6 +97,11 @@ __global__ void __launch_bounds__(256) selftest_count_below_kernel(const int32_t
   const uint32_t *w = w4 + 4 * static_cast<size_t>(i);
   count_below(D, w[0], w[1], w[2], w[3], T[i]);
   out[i] = D;
+}
+
+__global__ void __launch_bounds__(256) selftest_text_digits_kernel(const double *x, int n, int64_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = text_digits(x[i]);
 }
 
 namespace {
@@ -258,6 +265,16 @@ void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double 
   int32_t *dout = b.out<int32_t>(static_cast<size_t>(n) * (KK + 1));
   hipLaunchKernelGGL(selftest_pe_pick_kernel, st_grid(n), dim3(256), 0, 0, KK, df, dpsi, dfp, il2, drule, dword, n, dout);
   b.back(out, dout, static_cast<size_t>(n) * (KK + 1));
+}
+
+void selftest_text_digits(const double *x, int n, int64_t *out) {
+  st_need_device(n);
+  if (n == 0) return;
+  StBuffers b;
+  const double *dx = b.in(x, static_cast<size_t>(n));
+  int64_t *dout = b.out<int64_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_text_digits_kernel, st_grid(n), dim3(256), 0, 0, dx, n, dout);
+  b.back(out, dout, static_cast<size_t>(n));
 }
 
 void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out) {

@@ -15,11 +15,15 @@
 
 #include "device.hpp"
 #include "miso_detmath.h"
+#include "text_digits.hpp"
 
 namespace miso {
 
+// (every NaN gets the largest key, whatever its sign bit: numpy's sort -- the reference's, credible_intervals.py:53 --
+// puts NaN behind +inf; the bit pattern alone would put a sign-bit NaN in front of -inf)
 __device__ __forceinline__ uint64_t order_key(double x) {
   const uint64_t u = __double_as_longlong(x);
+  if (x != x) return ~0ull;
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 __device__ __forceinline__ double key_value(uint64_t k) {
@@ -29,23 +33,8 @@ __device__ __forceinline__ double key_value(uint64_t k) {
 
 constexpr int SUMMARY_CACHE = 32;   // samples per thread held in registers (S <= 8192)
 
-// TEXT: summarise what summarize_miso READS, not what the sampler computed: the reference's summaries come from the
-// `.miso` file (samples_utils.py:130-262 -> credible_intervals.py), where every sample is the text "%.4f" of psi.
-// k = psi x 10^4 rounded to the nearest integer, ties to even, decided on the EXACT product (fma gives the rounding
-// error of the multiplication), which is what a correctly rounded "%.4f" prints; the value read back is the double
-// nearest to k / 10^4 = the correctly rounded quotient.  The mean is then the exact integer sum of the k over
-// S x 10^4 (correctly rounded; numpy's pairwise float sum of the same values agrees to the last bit or two).
-__device__ __forceinline__ long long text_digits(double v) {
-  const double p = v * 10000.0;
-  const double e = __builtin_fma(v, 10000.0, -p);        // v x 10^4 = p + e exactly
-  double r = __builtin_rint(p);                          // nearest, ties to even
-  const double d = (p - r) + e;                          // exact: both terms are tiny and on a common grid
-  if (d > 0.5) r = r + 1.0; else if (d < -0.5) r = r - 1.0;
-  else if (d == 0.5 && (static_cast<long long>(r) & 1)) r = r + 1.0;     // a tie decided against an odd r
-  else if (d == -0.5 && (static_cast<long long>(r) & 1)) r = r - 1.0;
-  return static_cast<long long>(r);
-}
-
+// TEXT: summarise what summarize_miso READS, not what the sampler computed: every sample as "%.4f" prints it
+// (text_digits.hpp text_digits).
 template <bool CACHED, bool TEXT>
 __device__ __forceinline__ void summarize_column(const double *x, int K, int S, int rank_lo, int rank_hi,
                                                  double *o) {
@@ -56,7 +45,7 @@ __device__ __forceinline__ void summarize_column(const double *x, int K, int S, 
   long long iacc = 0;
   auto as_read = [&](double v) {   // TEXT: the sample as the `.miso` file hands it on
     if (!TEXT) return v;
-    if (!(v == v) || v - v != 0.0) { s_nonfinite = 1; return v; }     // "nan" / "inf" stay what they are
+    if (!text_rounds(v)) { s_nonfinite = 1; return v; }     // "nan" / "inf" / an integer of 16 digits stay what they are
     const long long k = text_digits(v);
     iacc += k;
     return static_cast<double>(k) / 10000.0;
@@ -144,7 +133,7 @@ __device__ __forceinline__ void summarize_column(const double *x, int K, int S, 
     } else {
       for (int s = t; s < S; s += 256) {
         const double vq = x[static_cast<size_t>(s) * K];
-        const uint64_t key = order_key((TEXT && vq == vq && vq - vq == 0.0) ? static_cast<double>(text_digits(vq)) / 10000.0 : vq);
+        const uint64_t key = order_key((TEXT && text_rounds(vq)) ? static_cast<double>(text_digits(vq)) / 10000.0 : vq);
         const uint64_t km = key & mask;
         const unsigned bin = static_cast<unsigned>(key >> (8 * byte)) & 0xFFu;
         if (km == p0) atomicAdd(&hist2[0][bin], 1u);

@@ -39,7 +39,7 @@ def test_header_declares_the_path():
     for must in ("miso_create_gene", "miso_run", "miso_run_paired", "miso_batch_create",
                  "miso_batch_add_event", "miso_batch_launch", "miso_batch_get_result",
                  "miso_match_iso", "miso_match_iso_paired", "miso_last_error", "miso_aln_open",
-                 "miso_aln_fetch", "miso_aln_parse_reads"):
+                 "miso_aln_fetch", "miso_aln_parse_reads", "miso_selftest_text_digits"):
         assert must in names
 
 
