@@ -308,6 +308,24 @@ int miso_batch_compare(miso_batch_t *sample1, miso_batch_t *sample2, double smoo
 int miso_batch_get_comparison(const miso_batch_t *sample1, int event_index, double *mean1, double *mean2,
                               double *bayes_factor, double *density_at_0);   /* noiso doubles each */
 
+/* Every pair of two groups of samples (biological replicates) in one device pass.  group1[i], group2[j]: batches that
+   hold the SAME events in the same order with the same n_samples, on the same device (what miso_batch_compare requires of
+   its two); n1, n2 >= 1.  out: n1 * n2 * tot doubles, tot = sum over events of 4 * noiso; pair (i, j), event e, isoform k
+   at ((i * n2 + j) * tot + off[e] + 4 * k), off[e] = 4 * (isoforms of the events before e): mean1, mean2, bayes_factor,
+   density_at_0 -- bit for bit what miso_batch_compare(group1[i], group2[j], smoothing) + miso_batch_get_comparison give.
+   One launch serves all pairs: a workgroup per (event, isoform) reads the n1 + n2 sample columns once into LDS and takes
+   every pair from there.  staging says which columns: MISO_STAGE_AUTO picks by what fits beside the reduction buffers
+   (both groups, else the smaller group, else none: the columns then come from global memory, same bits);
+   the other values force one (tools/compare_groups_bench.py measures them; one that does not fit is MISO_EINVAL).
+   kernel_ms (may be NULL): the kernel's time.  Errors as miso_batch_compare, naming the group and index of the batch
+   at fault; MISO_ENODEVICE without a GPU. */
+#define MISO_STAGE_AUTO 0
+#define MISO_STAGE_BOTH 1
+#define MISO_STAGE_SMALLER 2
+#define MISO_STAGE_NONE 3
+int miso_batch_compare_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2,
+                              double smoothing, int staging, double *out, int64_t out_len, float *kernel_ms);
+
 /* device_match batches: kernel time of the matching launch done by miso_batch_upload, and (tests:
    want_counts_trace batches only) the kernel's output for event i in the layout of
    miso_match_iso[_paired]: match noiso x n_reads, fragmentLength likewise or NULL. */

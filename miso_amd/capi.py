@@ -554,6 +554,56 @@ class SamplesBatch(Batch):
         return out
 
 
+# ---- every pair of two groups of samples (include/miso_amd.h miso_batch_compare_groups) ----
+MISO_STAGE_AUTO, MISO_STAGE_BOTH, MISO_STAGE_SMALLER, MISO_STAGE_NONE = 0, 1, 2, 3
+STAGING = {"auto": MISO_STAGE_AUTO, "both": MISO_STAGE_BOTH, "smaller": MISO_STAGE_SMALLER, "none": MISO_STAGE_NONE}
+
+
+class GroupComparison:
+    """What compare_groups computed: comparison(i, j, event) is Batch.comparison(event)'s tuple for the pair
+    (batches1[i], batches2[j]); `kernel_ms` the kernel's time."""
+
+    def __init__(self, out, n2, noiso, kernel_ms):
+        self.noiso = np.asarray(noiso, dtype=np.int64)
+        self.offs = np.concatenate([[0], np.cumsum(4 * self.noiso)])
+        self.out = out.reshape(-1, n2, int(self.offs[-1]))
+        self.kernel_ms = kernel_ms
+
+    def comparison(self, i, j, event):
+        """(mean1[K], mean2[K], bayes_factor[K], density_at_0[K]) of `event` for the pair (i, j)."""
+        if not 0 <= event < len(self.noiso):
+            raise IndexError("event %d of %d" % (event, len(self.noiso)))
+        q = self.out[i, j, self.offs[event]:self.offs[event + 1]].reshape(-1, 4)
+        return q[:, 0].copy(), q[:, 1].copy(), q[:, 2].copy(), q[:, 3].copy()
+
+
+def compare_groups(batches1, batches2, smoothing=0.3, staging="auto", noiso=None):
+    """Every pair (batches1[i], batches2[j]) in one device pass: the batches hold the same events in the same order with
+    the same number of samples, on one device.  Bit for bit what batches1[i].compare(batches2[j], smoothing) gives.
+    staging: which sample columns a workgroup keeps in LDS (`auto`, `both`, `smaller`, `none`).  noiso: the
+    events' isoform counts where the caller knows them (else asked of the first batch, event by event)."""
+    b1, b2 = list(batches1), list(batches2)
+    L = lib()
+    L.miso_batch_compare_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                            C.c_int64, C.POINTER(C.c_float)]
+    h1 = (C.c_void_p * max(len(b1), 1))(*[b.handle for b in b1])
+    h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
+    if noiso is not None:
+        noiso = [int(k) for k in noiso]
+    else:
+        noiso = []
+    if not noiso and b1 and len(b1[0]):
+        K = C.c_int()
+        for e in range(len(b1[0])):
+            check(L.miso_batch_event_info(b1[0].handle, e, C.byref(K), None, None, None))
+            noiso.append(K.value)
+    out = np.zeros(len(b1) * len(b2) * 4 * int(sum(noiso)))
+    ms = C.c_float(0.0)
+    check(L.miso_batch_compare_groups(h1, len(b1), h2, len(b2), C.c_double(smoothing), STAGING[staging], _p(out),
+                                      out.size, C.byref(ms)))
+    return GroupComparison(out, len(b2), noiso, float(ms.value))
+
+
 # ---- `.miso` sample text (include/miso_amd.h miso_text_shape, miso_batch_from_miso_text) ----
 MISO_TEXT_EPSI, MISO_TEXT_EROW, MISO_TEXT_ESCORE, MISO_TEXT_ECOUNT = 1, 2, 4, 8
 

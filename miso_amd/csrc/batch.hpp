@@ -27,6 +27,10 @@ void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double 
                       const uint32_t *word, int n, int32_t *out);
 void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
 void selftest_text_digits(const double *x, int n, int64_t *out);
+// kernels_compare_groups.hip
+int compare_groups_staging(int n1, int n2, int S, size_t budget);
+void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
+                    int64_t out_len, float *kernel_ms);
 
 // A device table and what it was last filled from: its host contents, or the key of the plan it was built for.  reset()
 // frees the allocation and forgets both, so that neither outlives it (the next upload may be to another device).

@@ -823,6 +823,14 @@ int miso_batch_get_comparison(const miso_batch_t *b, int i, double *mean1, doubl
   });
 }
 
+int miso_batch_compare_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, double smoothing,
+                              int staging, double *out, int64_t out_len, float *kernel_ms) {
+  return guarded([&] {
+    need(group1, "group1"); need(group2, "group2");
+    compare_groups(group1, n1, group2, n2, smoothing, staging, out, out_len, kernel_ms);
+  });
+}
+
 int miso_batch_last_match_ms(const miso_batch_t *b, float *ms) {
   return guarded([&] { need(b, "batch"); need(ms, "ms"); *ms = b->match_ms; });
 }

@@ -3,6 +3,7 @@
 
     python -m miso_amd.samples_utils --summarize-samples SAMPLES_DIR OUTPUT_DIR
     python -m miso_amd.samples_utils --compare-samples SAMPLES_DIR1 SAMPLES_DIR2 OUTPUT_DIR
+    python -m miso_amd.samples_utils --compare-groups DIR[,DIR...] DIR[,DIR...] OUTPUT_DIR [--group-labels L[,L...] L[,L...]]
 
 The reference walks the samples directory (chromosome sub-directories of `<event>.miso`, or their packed form
 `<chrom>.miso_db`, samples_utils.py:263-411), parses every event's "%.4f" rows and computes per event the posterior
@@ -24,6 +25,10 @@ Both give the same doubles for the same text -- the correctly rounded value of e
 byte-identical (tests/test_gpu_miso_text.py), and equal to the reference's on the same files (bounds bit for bit; see
 tests/test_gpu_summary.py, tests/test_gpu_compare.py).  Out of scope as in the reference's own optional paths:
 compressed-ID maps (`--use-compressed`), zipped outputs (miso_zip).
+
+`--compare-groups` is `--compare-samples` for biological replicates (what filter_events --votes reads): every pair of the
+two groups gets the file the pairwise call writes, byte for byte, but every tree is read once, every sample decoded and
+summarised once per chunk of events, and all pairs of a chunk come out of one launch (capi.compare_groups).
 """
 import glob
 import os
@@ -441,12 +446,251 @@ def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_l
     return out, len(rows)
 
 
+# ---- replicate groups: every pair of two groups of sample directories in one device pass per chunk of events ----
+# text of one group chunk, all samples together (what TEXT_BATCH_BYTES is to the two samples of a pair)
+GROUP_TEXT_BYTES = TEXT_BATCH_BYTES
+
+
+def group_labels(dirs1, dirs2, labels1=None, labels2=None):
+    """The two groups' labels (default: the directories' base names), checked before anything is read: as many labels as
+    directories, and no two pairs with the same `<l1>_vs_<l2>` (they would write the same file)."""
+    out = []
+    for which, dirs, labels in ((1, dirs1, labels1), (2, dirs2, labels2)):
+        if not dirs:
+            raise ValueError("group %d has no sample directory" % which)
+        if labels is None:
+            labels = [os.path.basename(os.path.normpath(d)) for d in dirs]
+        labels = list(labels)
+        if len(labels) != len(dirs):
+            raise ValueError("group %d has %d directories and %d labels" % (which, len(dirs), len(labels)))
+        out.append(labels)
+    seen = {}
+    for i, a in enumerate(out[0]):
+        for j, c in enumerate(out[1]):
+            name = "%s_vs_%s" % (a, c)
+            if name in seen:
+                raise ValueError("pairs %r and %r would both write %s: give distinct --group-labels" % (seen[name], (i, j), name))
+            seen[name] = (i, j)
+    return out[0], out[1]
+
+
+def plan_group_comparison(listings1, listings2, chunk_bytes=None):
+    """Which events of two groups of samples go where -- host only, nothing is read or decoded here.
+
+    listingsN: per sample of group N an iterable of (name, K, S, decodable[, text_bytes]): an event the sample has, its
+    isoforms and sample rows, whether the device route can take it (for text: 1 <= K <= MISO_MAX_ISOFORMS and S >= 1) and
+    the size of its text (0 when left out).  Only events that at least one sample of EACH group has take part: the
+    others are in no pair.  Returns a dict:
+
+      chunks      [{"S", "present1", "present2", "names", "K", "bytes"}]: the events of the group route, i.e. those whose
+                  samples all agree on (K, S) and are all decodable.  One chunk = one launch of the group kernel over the
+                  samples that HAVE its events (present1 / present2: indices into the groups; a sample that lacks an
+                  event is masked out of that event's pairs by not being in its chunk); events in name order, all with S
+                  rows, their text over all present samples within chunk_bytes (at least one event a chunk).
+      pair_route  names of events whose samples disagree on (K, S): every pair that has one goes the pairwise route (which
+                  prints its `Skipping ...` line where the pair itself disagrees).
+      fallback    names of events some sample cannot hand to the device route: every pair through the host parser.
+      pairs_of    name -> [(i, j)] for the events of pair_route and fallback: the pairs whose two samples have it."""
+    if chunk_bytes is None:
+        chunk_bytes = GROUP_TEXT_BYTES
+    have = ({}, {})                                       # name -> {sample index: (K, S, decodable, bytes)}
+    for side, listings in enumerate((listings1, listings2)):
+        for i, listing in enumerate(listings):
+            for rec in listing:
+                name, K, S, ok = rec[:4]
+                nbytes = rec[4] if len(rec) > 4 else 0
+                have[side].setdefault(name, {})[i] = (int(K), int(S), bool(ok), int(nbytes))
+    plan = {"chunks": [], "pair_route": [], "fallback": [], "pairs_of": {}}
+    classes = {}
+    for name in sorted(set(have[0]) & set(have[1])):
+        recs = list(have[0][name].values()) + list(have[1][name].values())
+        if not all(r[2] for r in recs):
+            where = plan["fallback"]
+        elif len({r[:2] for r in recs}) > 1:
+            where = plan["pair_route"]
+        else:
+            key = (recs[0][1], tuple(sorted(have[0][name])), tuple(sorted(have[1][name])))
+            classes.setdefault(key, []).append((name, recs[0][0], sum(r[3] for r in recs)))
+            continue
+        where.append(name)
+        plan["pairs_of"][name] = [(i, j) for i in sorted(have[0][name]) for j in sorted(have[1][name])]
+    for (S, p1, p2), evs in sorted(classes.items()):
+        run, n = [], 0
+        for ev in evs + [None]:
+            if ev is None or (run and n + ev[2] > chunk_bytes):
+                if run:
+                    plan["chunks"].append({"S": S, "present1": p1, "present2": p2, "names": [e[0] for e in run],
+                                           "K": [e[1] for e in run], "bytes": n})
+                run, n = [], 0
+            if ev is not None:
+                run.append(ev)
+                n += ev[2]
+    return plan
+
+
+class _TextSample:
+    """One sample directory for the group pass, decoder = device: its events' text, read once."""
+
+    def __init__(self, src, names):
+        evs = _read_events(*_read_named(src, names))
+        _shape(evs)
+        self.ev = {e.name: e for e in evs}
+        self.parsed = {}
+
+    def listing(self):
+        return [(e.name, e.K, e.S, _device_ok(e), len(e.body)) for e in self.ev.values()]
+
+    def batch(self, names, S, device, stats):
+        return _text_batch([self.ev[n] for n in names], S, device, stats)
+
+    def header(self, name):
+        return _header_fields(self.ev[name].header)
+
+    def parse(self, name):
+        if name not in self.parsed:
+            self.parsed[name] = _parse_or_skip(self.ev[name])
+        return self.parsed[name]
+
+
+class _ParsedSample:
+    """The same, decoder = host: every event parsed on the host cores, once."""
+
+    def __init__(self, src, names):
+        files, dbrows = _read_named(src, names)
+        self.ev = {e[0]: e for e in _load_all(files + _read_events([], dbrows))}
+
+    def listing(self):
+        return [(n, a.shape[1], a.shape[0], True, a.nbytes) for n, a, _ in self.ev.values()]
+
+    def batch(self, names, S, device, stats):
+        b = capi.SamplesBatch([self.ev[n][1] for n in names], device=device)
+        b.status = np.zeros(len(names), np.int32)
+        return b
+
+    def header(self, name):
+        return self.ev[name][2]
+
+    def parse(self, name):
+        return self.ev[name]
+
+
+def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=None, confidence_level=0.95, smoothing=0.3,
+                             device=0, decoder=None):
+    """compare_miso for replicates: every pair (dirs1[i], dirs2[j]) as output_samples_comparison writes it -- the same
+    `<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf`, byte for byte -- with every tree listed and read once, every
+    sample's text decoded and summarised once, and all pairs of a chunk of events in one launch
+    (capi.compare_groups).  plan_group_comparison decides which events take that route.  Returns [(path, n_rows)] in
+    row-major pair order."""
+    labels1, labels2 = group_labels(dirs1, dirs2, labels1, labels2)
+    decoder = _decoder(decoder)
+    stats = _Stats(decoder)
+    n1, n2 = len(dirs1), len(dirs2)
+    stats.d.update({"samples": n1 + n2, "pairs": n1 * n2, "group_events": 0, "pair_route_events": [], "group_chunks": 0,
+                    "compare_kernel_ms": 0.0})
+    srcs = [[_sources(d) for d in dirs] for dirs in (dirs1, dirs2)]
+    stats.stage("list")
+    # a sample reads the events that some sample of the other group has too: the others are in no pair
+    others = [set().union(*srcs[1 - g]) for g in (0, 1)]
+    make = _ParsedSample if decoder == "host" else _TextSample
+    samples = [[make(src, sorted(set(src) & others[g])) for src in srcs[g]] for g in (0, 1)]
+    stats.stage("read+parse" if decoder == "host" else "read+shape")
+    plan = plan_group_comparison([s.listing() for s in samples[0]], [s.listing() for s in samples[1]])
+    stats.stage("plan")
+    rows = {(i, j): [] for i in range(n1) for j in range(n2)}
+    routed = {name: "fallback" for name in plan["fallback"]}
+    routed.update({name: "pair" for name in plan["pair_route"]})
+    pairs_of = dict(plan["pairs_of"])
+
+    for ch in plan["chunks"]:
+        S, names, K = ch["S"], ch["names"], ch["K"]
+        lo, _ = summary.credible_interval_ranks(S, confidence_level)
+        if lo <= 0 or S < 2:                              # as the pairwise route: no interval, no comparison
+            continue
+        present = (ch["present1"], ch["present2"])
+        batches = [[samples[g][i].batch(names, S, device, stats) for i in present[g]] for g in (0, 1)]
+        stats.stage("decode")
+        summ = []
+        for g in (0, 1):
+            for b in batches[g]:
+                b.summarize(confidence_level)
+            summ.append([b.summaries(range(len(names)), K) for b in batches[g]])
+        stats.stage("summarize")
+        cmp = capi.compare_groups(batches[0], batches[1], smoothing, noiso=K)
+        stats.d["compare_kernel_ms"] += cmp.kernel_ms
+        stats.d["group_chunks"] += 1
+        stats.stage("compare")
+        bad = np.zeros(len(names), bool)
+        for g in (0, 1):
+            for b in batches[g]:
+                bad |= np.asarray(b.status) != 0
+        hdrs = [[[None if bad[e] else samples[g][i].header(n) for e, n in enumerate(names)] for i in present[g]]
+                for g in (0, 1)]
+        for a, i in enumerate(present[0]):
+            for c, j in enumerate(present[1]):
+                bf = cmp.out[a, c]
+                out = rows[(i, j)]
+                for e, name in enumerate(names):
+                    if not bad[e]:
+                        out.append((name, summ[0][a][e], summ[1][c][e], bf[cmp.offs[e] + 2:cmp.offs[e + 1]:4],
+                                    hdrs[0][a][e], hdrs[1][c][e]))
+        for e, name in enumerate(names):
+            if bad[e]:                                    # outside the device decoder's grammar in some sample
+                routed[name] = "fallback"
+                pairs_of[name] = [(i, j) for i in present[0] for j in present[1]]
+        stats.d["group_events"] += int((~bad).sum())
+        del batches, cmp
+        stats.stage("rows")
+
+    # what the group route did not take, pair by pair as output_samples_comparison does it: through the host parser
+    # (the same doubles as the device decoder's), _compare_parsed prints the `Skipping ...` of a pair that disagrees
+    left = {}
+    for name in sorted(routed):
+        for pair in pairs_of[name]:
+            left.setdefault(pair, []).append(name)
+    for (i, j), names in sorted(left.items()):
+        parsed = [(samples[0][i].parse(n), samples[1][j].parse(n)) for n in names]
+        _compare_parsed([p for p in parsed if p[0] is not None and p[1] is not None], confidence_level, smoothing, device,
+                        rows[(i, j)])
+    stats.d["fallback_events"] = sorted(n for n, r in routed.items() if r == "fallback")
+    stats.d["pair_route_events"] = sorted(n for n, r in routed.items() if r == "pair")
+    stats.stage("pairwise")
+
+    written = []
+    for i in range(n1):
+        for j in range(n2):
+            name = "%s_vs_%s" % (labels1[i], labels2[j])
+            out = os.path.join(output_dir, name, "bayes-factors", name + ".miso_bf")
+            os.makedirs(os.path.dirname(out), exist_ok=True)
+            rows[(i, j)].sort(key=lambda r: r[0])
+            compare.write_comparison(out, rows[(i, j)])
+            written.append((out, len(rows[(i, j)])))
+    stats.stage("write")
+    stats.done()
+    return written
+
+
+def parse_group_args(compare_groups, group_labels_arg=None):
+    """`--compare-groups DIR[,DIR...] DIR[,DIR...] OUTPUT_DIR [--group-labels L[,L...] L[,L...]]` ->
+    (dirs1, dirs2, output_dir, labels1, labels2); the labels are checked (group_labels) before anything is read."""
+    g1, g2, out_dir = compare_groups
+    split = lambda v: [x for x in v.split(",") if x]  # noqa: E731
+    dirs1, dirs2 = ([os.path.abspath(os.path.expanduser(p)) for p in split(g)] for g in (g1, g2))
+    l1 = l2 = None
+    if group_labels_arg:
+        l1, l2 = (split(v) for v in group_labels_arg)
+    l1, l2 = group_labels(dirs1, dirs2, l1, l2)
+    return dirs1, dirs2, os.path.abspath(os.path.expanduser(out_dir)), l1, l2
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="summarize_miso / compare_miso over directories of .miso files")
     ap.add_argument("--summarize-samples", nargs=2, metavar=("SAMPLES_DIR", "OUTPUT_DIR"))
     ap.add_argument("--compare-samples", nargs=3, metavar=("SAMPLES_DIR1", "SAMPLES_DIR2", "OUTPUT_DIR"))
     ap.add_argument("--comparison-labels", nargs=2, default=None)
+    ap.add_argument("--compare-groups", nargs=3, metavar=("DIR[,DIR...]", "DIR[,DIR...]", "OUTPUT_DIR"),
+                    help="every pair of two groups of sample directories (replicates), one .miso_bf per pair")
+    ap.add_argument("--group-labels", nargs=2, default=None, metavar=("L[,L...]", "L[,L...]"))
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.summarize_samples:
@@ -459,7 +703,16 @@ def main(argv=None):
         d1, d2, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.compare_samples)
         out, n = output_samples_comparison(d1, d2, out_dir, sample_labels=a.comparison_labels, device=a.device)
         print("Compared %d events into %s" % (n, out))
-    if not a.summarize_samples and not a.compare_samples:
+    if a.compare_groups:
+        try:
+            dirs1, dirs2, out_dir, l1, l2 = parse_group_args(a.compare_groups, a.group_labels)
+        except ValueError as err:
+            ap.error(str(err))
+        for out, n in output_group_comparisons(dirs1, dirs2, out_dir, l1, l2, device=a.device):
+            print("Compared %d events into %s" % (n, out))
+    elif a.group_labels:
+        ap.error("--group-labels goes with --compare-groups")
+    if not a.summarize_samples and not a.compare_samples and not a.compare_groups:
         ap.print_help()
     return 0
 
