@@ -410,14 +410,23 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   const int nfq = PE ? n_draw >> 2 : n_draw >> 3, rem = PE ? n_draw & 3 : n_draw & 7;
   // trips of the Gibbs loop (UQ quads per lane per trip); must be wave-uniform
   constexpr int UQ = PE ? 2 : MISO_K2_UQ;
-  int trips = (nfq + UQ * GE - 1) / (UQ * GE);
-  int any_rem = rem;
+  // single-end: the partial block is block number nfq of the stride, worked on by the lane whose stride reaches it
+  const int nblk = PE ? nfq : nfq + (rem != 0 ? 1 : 0);
+  int trips = (nblk + UQ * GE - 1) / (UQ * GE);
+  // single-end: the trips in which EVERY block of every lane of the wavefront is a full block of its chain -- the read
+  // loop's steady part, which tests no range (n_draw does not change between iterations: found once, here).  Lanes
+  // beyond the wavefront's last chain shadow lane 0 of that chain.
+  int full_trips = ((sub < nfq) ? (nfq - 1 - sub) / GE + 1 : 0) / UQ;
   for (int off = 32; off >= 1; off >>= 1) {
     trips = max(trips, __shfl_xor(trips, off));
-    any_rem |= __shfl_xor(any_rem, off);
+    full_trips = min(full_trips, __shfl_xor(full_trips, off));
   }
   trips = __builtin_amdgcn_readfirstlane(trips);     // wave-uniform by construction: say so
-  any_rem = __builtin_amdgcn_readfirstlane(any_rem);
+  full_trips = __builtin_amdgcn_readfirstlane(full_trips);
+  // the halves of the partial block's word w that are NOT reads of the chain (rem = 0: all of them)
+  uint32_t part_inv[4];
+#pragma unroll
+  for (int w = 0; w < 4; w++) part_inv[w] = (2 * w < rem ? 0u : 0xFFFFu) | (2 * w + 1 < rem ? 0u : 0xFFFF0000u);
 
   double *samples = reinterpret_cast<double *>(a.out_pool + E.off_samples);
   double *loglik = reinterpret_cast<double *>(a.out_pool + E.off_loglik);
@@ -641,18 +650,9 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     const uint64_t t = k2_threshold(cur.x0, (0.0 + cur.x0) + cur.x1);
     const uint32_t th = static_cast<uint32_t>(t >> 16), tl = static_cast<uint32_t>(t) & 0xFFFFu;   // th <= 65536
     const uint32_t n0r0 = rng.p1hi ^ iter ^ k0;
-    int d0 = 0, amb_n = 0; uint32_t amb_t = 0; bool amb_p = false;   // trips of this lane with a high half on the threshold, the last of them; the partial block
+    int d0 = 0, amb_n = 0; uint32_t amb_t = 0;   // trips of this lane with a high half on the threshold, the last of them
     PROF_T(g1);
     PROF_ADD(pf_thr, g0, g1);
-    auto halves = [&](const miso_u32x4 &u, int nh, int &below, int &equal) __attribute__((always_inline)) {
-      below = 0; equal = 0;
-#pragma unroll
-      for (int h = 0; h < 8; h++) {
-        const uint32_t x = (h & 1) ? (u.v[h >> 1] >> 16) : (u.v[h >> 1] & 0xFFFFu);
-        below += (h < nh && x < th) ? 1 : 0;
-        equal |= (h < nh && x == th) ? 1 : 0;
-      }
-    };
     // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask):
     //   below: saturating th - x is non-zero iff x < th; min(.., 1) is the count;   equal: x ^ th is zero iff x == th,
     // kept as the running minimum over the trip's words and tested once per trip (a 32-bit word has a zero half iff
@@ -663,55 +663,63 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // VALU per 16 reads, 74.6 ms; this form, 108 VALU but no lane masks, 71.0 ms; MISO defaults 235.9 -> 219.1 ms,
     // hg19-like read counts 66.4 -> 59.4 ms; the equal test once per trip instead of once per block: 70.9 -> 69.3 ms,
     // defaults 219.5 -> 207.9 ms; profiles/r04_lazy_low_bits.txt)
+    // The loop has two parts.  STEADY: the wavefront's first full_trips trips, in which every block of every lane is a
+    // full block of its chain -- no range test, every word's count goes straight into the packed accumulator.  TAIL: the
+    // remaining trips (one or two unless chains of very different sizes share the wavefront), in which a block is a full
+    // one (q < nfq), the chain's partial block (q == nfq: the halves >= rem are not reads) or beyond the chain: the
+    // halves that are not reads are masked out of the count AND out of the equal test, so the partial block needs no
+    // generator call of its own and a block beyond the chain never flags a trip.
     const uint32_t thc = th > 0xFFFFu ? 0xFFFFu : th;
     const uint32_t T2 = thc | (thc << 16), one2 = 0x00010001u;
     uint32_t accv = 0;
+    auto trip = [&](int j, auto masked) __attribute__((always_inline)) {
+      constexpr bool MASKED = decltype(masked)::value;
+      miso_u32x4 u[UQ];
+#pragma unroll
+      for (int i = 0; i < UQ; i++)
+        u[i] = philox_gibbs(rng, static_cast<uint32_t>(sub + (UQ * j + i) * GE), n0r0);
+      uint32_t m = 0;   // the trip's running minimum of x ^ th, both halves
+#pragma unroll
+      for (int i = 0; i < UQ; i++) {
+        const int q = sub + (UQ * j + i) * GE;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+          uint32_t d;
+          asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(T2), "v"(u[i].v[w]));
+          asm("v_pk_min_u16 %0, %1, %2" : "=v"(d) : "v"(d), "v"(one2));
+          uint32_t y = u[i].v[w] ^ T2;
+          if (MASKED) {
+            const uint32_t inv = (q < nfq) ? 0u : (q == nfq ? part_inv[w] : 0xFFFFFFFFu);
+            d &= ~inv;
+            y |= inv;
+          }
+          asm("v_pk_add_u16 %0, %1, %2" : "=v"(accv) : "v"(accv), "v"(d));
+          if (i == 0 && w == 0) { m = y; continue; }
+          asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(m), "v"(y));
+        }
+      }
+      if (((m - 0x00010001u) & ~m & 0x80008000u) != 0u) { amb_t = static_cast<uint32_t>(j); amb_n++; }
+    };
     // (the two 16-bit counters of a lane take 4 per block each: emptied every 16000 blocks, which only a chain of more
     // than 10^5 reads forced onto a single lane ever reaches)
     constexpr int CHUNK = 16000 / UQ;
-    for (int j0 = 0; j0 < trips; j0 += CHUNK) {
-      const int j1 = min(trips, j0 + CHUNK);
-      for (int j = j0; j < j1; j++) {
-        miso_u32x4 u[UQ];
-#pragma unroll
-        for (int i = 0; i < UQ; i++)
-          u[i] = philox_gibbs(rng, static_cast<uint32_t>(sub + (UQ * j + i) * GE), n0r0);
-        uint32_t m = u[0].v[0] ^ T2;   // the trip's running minimum of x ^ th, both halves (blocks beyond the chain's
-                                       // last included: a flag too many only costs the look behind the loop)
-#pragma unroll
-        for (int i = 0; i < UQ; i++) {
-          const int q = sub + (UQ * j + i) * GE;
-          uint32_t c = 0;
-#pragma unroll
-          for (int w = 0; w < 4; w++) {
-            uint32_t d;
-            asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(T2), "v"(u[i].v[w]));
-            asm("v_pk_min_u16 %0, %1, %2" : "=v"(d) : "v"(d), "v"(one2));
-            asm("v_pk_add_u16 %0, %1, %2" : "=v"(c) : "v"(c), "v"(d));
-            if (i == 0 && w == 0) continue;
-            const uint32_t y = u[i].v[w] ^ T2;
-            asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(m), "v"(y));
-          }
-          uint32_t cm = (q < nfq) ? c : 0u;
-          asm("v_pk_add_u16 %0, %1, %2" : "=v"(accv) : "v"(accv), "v"(cm));
-        }
-        if (((m - 0x00010001u) & ~m & 0x80008000u) != 0u) { amb_t = static_cast<uint32_t>(j); amb_n++; }
-      }
+    for (int j0 = 0; j0 < full_trips; j0 += CHUNK) {
+      const int j1 = min(full_trips, j0 + CHUNK);
+      for (int j = j0; j < j1; j++) trip(j, std::false_type{});
       d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
       accv = 0;
     }
-    if (th > 0xFFFFu) d0 = (sub < nfq) ? 8 * ((nfq - 1 - sub) / GE + 1) : 0;
-    if (any_rem) {  // the partial block, owned by one lane of the group
-      const miso_u32x4 u = philox_gibbs(rng, static_cast<uint32_t>(nfq), n0r0);
-      int cp, eq;
-      halves(u, rem, cp, eq);
-      const bool mine = sub == (nfq % GE);
-      d0 += mine ? cp : 0;
-      amb_p = mine && eq;
+    for (int j0 = full_trips; j0 < trips; j0 += CHUNK) {
+      const int j1 = min(trips, j0 + CHUNK);
+      for (int j = j0; j < j1; j++) trip(j, std::true_type{});
+      d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
+      accv = 0;
     }
-    if (!lane_used) { d0 = 0; amb_n = 0; amb_p = false; }
+    // t = 2^32: every read of the lane's full blocks and, for its owner, of the partial block
+    if (th > 0xFFFFu) d0 = ((sub < nfq) ? 8 * ((nfq - 1 - sub) / GE + 1) : 0) + ((sub == nfq % GE) ? rem : 0);
+    if (!lane_used) { d0 = 0; amb_n = 0; }
     const bool settle_all = a.pe_force_exact != 0;   // tests: every lane takes the rescan below at every step
-    if (tl != 0 && __builtin_expect(settle_all || __any(amb_n != 0 || amb_p), 0)) {
+    if (tl != 0 && __builtin_expect(settle_all || __any(amb_n != 0), 0)) {
       // the reads whose high half sits ON the threshold: their low halves decide (one wavefront step in four at 1000
       // reads and 16 chains per wavefront; two Philox blocks then)
       auto settle = [&](uint32_t q) {
@@ -723,20 +731,20 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
           more += (miso_block_half(hi, h) == th && miso_block_half(lo, h) < tl) ? 1 : 0;
         return more;
       };
-      // a full block of this lane: its low halves if one of its high halves is on the threshold
+      // a block of this lane: its low halves if one of its high halves is on the threshold (the partial block: settle()
+      // counts nothing when none of its rem high halves is)
       auto look = [&](int q) {
-        if (q >= nfq) return 0;
+        if (q >= nblk) return 0;
+        if (q == nfq) return settle(static_cast<uint32_t>(q));
         const miso_u32x4 hi = miso_philox4x32(static_cast<uint32_t>(q), iter, c2_gibbs, event_id, k0, k1);
         bool on = false;
         for (int h = 0; h < 8; h++) on |= miso_block_half(hi, h) == th;
         return on ? settle(static_cast<uint32_t>(q)) : 0;
       };
-      // the partial block (its owner only; settle() counts nothing when no high half is on the threshold)
-      if (lane_used && rem != 0 && sub == (nfq % GE) && (amb_p || settle_all)) d0 += settle(static_cast<uint32_t>(nfq));
-      if (amb_n == 1 && !settle_all) {        // the full blocks: one trip's ...
+      if (amb_n == 1 && !settle_all) {        // one trip's blocks ...
         for (int i = 0; i < UQ; i++) d0 += look(sub + (UQ * static_cast<int>(amb_t) + i) * GE);
       } else if ((amb_n > 1 || settle_all) && lane_used) {   // ... or, with several such trips, all of the lane's
-        for (int q = sub; q < nfq; q += GE) d0 += look(q);
+        for (int q = sub; q < nblk; q += GE) d0 += look(q);
       }
     }
     PROF_T(g2);

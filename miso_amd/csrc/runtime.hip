@@ -1918,14 +1918,14 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
     auto slice = [&](long c0, long c1, int G) {   // chains [c0, c1) of the list with G lanes per chain
       const int cpw = 64 / G;
       for (long s0 = c0; s0 < c1; s0 += cpw, waves++) {
-        int mx = 0, any_rem = 0;
+        int mx = 0;   // blocks of the wavefront's largest chain (single-end: the partial block is one of the stride's)
         for (long sl = s0; sl < std::min(c1, s0 + cpw); sl++) {
           const int n = nd[sl / C];
-          mx = std::max(mx, n >> bshift); any_rem |= n & ((1 << bshift) - 1);
+          mx = std::max(mx, (n >> bshift) + ((!p.paired && (n & ((1 << bshift) - 1))) ? 1 : 0));
           words += n;
         }
         const int t = (mx + 2 * G - 1) / (2 * G);             // trips of two Philox blocks per lane
-        trips += p.paired ? 2 * t + 1 : 2 * t + (any_rem ? 1 : 0);   // counted in blocks per lane
+        trips += p.paired ? 2 * t + 1 : 2 * t;                // counted in blocks per lane
       }
     };
     if (!wpart && q.lane_route) {
@@ -1941,8 +1941,8 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
             const size_t we = static_cast<size_t>(c / C - pl.seg_slot[sg]);
             const int m = we < pl.wide_wgs.size() ? pl.wide_wgs[we] : 1;     // workgroups of the chain (coop.hpp)
             const int wl = 64 * pl.wpb * m;
-            const int t = ((n >> bshift) + 2 * wl - 1) / (2 * wl);
-            trips += pl.wpb * m * (p.paired ? 2 * t + 1 : 2 * t + ((n & 7) ? 1 : 0));
+            const int t = ((n >> bshift) + ((!p.paired && (n & 7)) ? 1 : 0) + 2 * wl - 1) / (2 * wl);
+            trips += pl.wpb * m * (p.paired ? 2 * t + 1 : 2 * t);
             words += n; waves += pl.wpb * m;
           }
         } else slice(c0, c1, pl.seg_lanes[sg]);
