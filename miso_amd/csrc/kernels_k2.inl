@@ -413,16 +413,23 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   // single-end: the partial block is block number nfq of the stride, worked on by the lane whose stride reaches it
   const int nblk = PE ? nfq : nfq + (rem != 0 ? 1 : 0);
   int trips = (nblk + UQ * GE - 1) / (UQ * GE);
-  // single-end: the trips in which EVERY block of every lane of the wavefront is a full block of its chain -- the read
-  // loop's steady part, which tests no range (n_draw does not change between iterations: found once, here).  Lanes
-  // beyond the wavefront's last chain shadow lane 0 of that chain.
+  // single-end: lane `sub` owns blocks sub + k GE, k = 0, 1, ... (stride position k); npos = the positions the wavefront's
+  // longest chain needs.  full_trips = the trips in which EVERY block of every lane of the wavefront is a full block of
+  // its chain -- the read loop's steady part, which tests no range (n_draw does not change between iterations: found once,
+  // here).  Lanes beyond the wavefront's last chain shadow lane 0 of that chain.
+  int npos = PE ? 0 : (nblk + GE - 1) / GE;
   int full_trips = ((sub < nfq) ? (nfq - 1 - sub) / GE + 1 : 0) / UQ;
   for (int off = 32; off >= 1; off >>= 1) {
     trips = max(trips, __shfl_xor(trips, off));
+    if (!PE) npos = max(npos, __shfl_xor(npos, off));
     full_trips = min(full_trips, __shfl_xor(full_trips, off));
   }
   trips = __builtin_amdgcn_readfirstlane(trips);     // wave-uniform by construction: say so
+  if (!PE) npos = __builtin_amdgcn_readfirstlane(npos);
   full_trips = __builtin_amdgcn_readfirstlane(full_trips);
+  // single-end: behind the steady trips, masked trips of UQ positions while UQ remain, then masked steps of ONE position:
+  // uq_trips = steady and masked trips together; positions UQ uq_trips .. npos - 1 are single steps
+  const int uq_trips = npos / UQ;
   // the halves of the partial block's word w that are NOT reads of the chain (rem = 0: all of them)
   uint32_t part_inv[4];
 #pragma unroll
@@ -650,7 +657,8 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     const uint64_t t = k2_threshold(cur.x0, (0.0 + cur.x0) + cur.x1);
     const uint32_t th = static_cast<uint32_t>(t >> 16), tl = static_cast<uint32_t>(t) & 0xFFFFu;   // th <= 65536
     const uint32_t n0r0 = rng.p1hi ^ iter ^ k0;
-    int d0 = 0, amb_n = 0; uint32_t amb_t = 0;   // trips of this lane with a high half on the threshold, the last of them
+    // trips and single steps of this lane with a high half on the threshold; the stride position the last of them began at
+    int d0 = 0, amb_n = 0; uint32_t amb_t = 0;
     PROF_T(g1);
     PROF_ADD(pf_thr, g0, g1);
     // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask):
@@ -663,25 +671,29 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // VALU per 16 reads, 74.6 ms; this form, 108 VALU but no lane masks, 71.0 ms; MISO defaults 235.9 -> 219.1 ms,
     // hg19-like read counts 66.4 -> 59.4 ms; the equal test once per trip instead of once per block: 70.9 -> 69.3 ms,
     // defaults 219.5 -> 207.9 ms; profiles/r04_lazy_low_bits.txt)
-    // The loop has two parts.  STEADY: the wavefront's first full_trips trips, in which every block of every lane is a
-    // full block of its chain -- no range test, every word's count goes straight into the packed accumulator.  TAIL: the
-    // remaining trips (one or two unless chains of very different sizes share the wavefront), in which a block is a full
-    // one (q < nfq), the chain's partial block (q == nfq: the halves >= rem are not reads) or beyond the chain: the
-    // halves that are not reads are masked out of the count AND out of the equal test, so the partial block needs no
-    // generator call of its own and a block beyond the chain never flags a trip.
+    // The loop has three parts.  STEADY: the wavefront's first full_trips trips of UQ stride positions, in which every
+    // block of every lane is a full block of its chain -- no range test, every word's count goes straight into the packed
+    // accumulator.  TAIL: masked trips of UQ positions while at least UQ remain for the wavefront's longest chain (none or
+    // one unless chains of very different sizes share the wavefront), then masked steps of ONE position for the fewer
+    // than UQ left -- a wavefront whose longest lane ends on an odd block count no longer pays a whole trip for one block.
+    // Masked: a block is a full one (q < nfq), the chain's partial block (q == nfq: the halves >= rem are not reads) or
+    // beyond the chain: the halves that are not reads are masked out of the count AND out of the equal test, so the
+    // partial block needs no generator call of its own and a block beyond the chain never flags a trip or a step.
     const uint32_t thc = th > 0xFFFFu ? 0xFFFFu : th;
     const uint32_t T2 = thc | (thc << 16), one2 = 0x00010001u;
     uint32_t accv = 0;
-    auto trip = [&](int j, auto masked) __attribute__((always_inline)) {
+    // NB blocks of the lane from stride position k on: a trip (NB = UQ) or a single step (NB = 1)
+    auto trip = [&](int k, auto masked, auto blocks) __attribute__((always_inline)) {
       constexpr bool MASKED = decltype(masked)::value;
-      miso_u32x4 u[UQ];
+      constexpr int NB = decltype(blocks)::value;
+      miso_u32x4 u[NB];
 #pragma unroll
-      for (int i = 0; i < UQ; i++)
-        u[i] = philox_gibbs(rng, static_cast<uint32_t>(sub + (UQ * j + i) * GE), n0r0);
+      for (int i = 0; i < NB; i++)
+        u[i] = philox_gibbs(rng, static_cast<uint32_t>(sub + (k + i) * GE), n0r0);
       uint32_t m = 0;   // the trip's running minimum of x ^ th, both halves
 #pragma unroll
-      for (int i = 0; i < UQ; i++) {
-        const int q = sub + (UQ * j + i) * GE;
+      for (int i = 0; i < NB; i++) {
+        const int q = sub + (k + i) * GE;
 #pragma unroll
         for (int w = 0; w < 4; w++) {
           uint32_t d;
@@ -698,20 +710,28 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
           asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(m), "v"(y));
         }
       }
-      if (((m - 0x00010001u) & ~m & 0x80008000u) != 0u) { amb_t = static_cast<uint32_t>(j); amb_n++; }
+      // the flag: the stride position the flagged trip or step began at (a single step: k >= UQ * uq_trips)
+      if (((m - 0x00010001u) & ~m & 0x80008000u) != 0u) { amb_t = static_cast<uint32_t>(k); amb_n++; }
     };
+    const std::integral_constant<int, UQ> whole{};
+    const std::integral_constant<int, 1> single{};
     // (the two 16-bit counters of a lane take 4 per block each: emptied every 16000 blocks, which only a chain of more
     // than 10^5 reads forced onto a single lane ever reaches)
     constexpr int CHUNK = 16000 / UQ;
     for (int j0 = 0; j0 < full_trips; j0 += CHUNK) {
       const int j1 = min(full_trips, j0 + CHUNK);
-      for (int j = j0; j < j1; j++) trip(j, std::false_type{});
+      for (int j = j0; j < j1; j++) trip(UQ * j, std::false_type{}, whole);
       d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
       accv = 0;
     }
-    for (int j0 = full_trips; j0 < trips; j0 += CHUNK) {
-      const int j1 = min(trips, j0 + CHUNK);
-      for (int j = j0; j < j1; j++) trip(j, std::true_type{});
+    for (int j0 = full_trips; j0 < uq_trips; j0 += CHUNK) {
+      const int j1 = min(uq_trips, j0 + CHUNK);
+      for (int j = j0; j < j1; j++) trip(UQ * j, std::true_type{}, whole);
+      d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
+      accv = 0;
+    }
+    if (UQ * uq_trips < npos) {   // fewer than UQ positions left: one block per lane at a time
+      for (int k = UQ * uq_trips; k < npos; k++) trip(k, std::true_type{}, single);
       d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
       accv = 0;
     }
@@ -741,8 +761,9 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
         for (int h = 0; h < 8; h++) on |= miso_block_half(hi, h) == th;
         return on ? settle(static_cast<uint32_t>(q)) : 0;
       };
-      if (amb_n == 1 && !settle_all) {        // one trip's blocks ...
-        for (int i = 0; i < UQ; i++) d0 += look(sub + (UQ * static_cast<int>(amb_t) + i) * GE);
+      if (amb_n == 1 && !settle_all) {        // one trip's blocks, or one single step's block ...
+        const int k = static_cast<int>(amb_t), nb = k < UQ * uq_trips ? UQ : 1;
+        for (int i = 0; i < nb; i++) d0 += look(sub + (k + i) * GE);
       } else if ((amb_n > 1 || settle_all) && lane_used) {   // ... or, with several such trips, all of the lane's
         for (int q = sub; q < nblk; q += GE) d0 += look(q);
       }

@@ -20,17 +20,19 @@ namespace miso {
 struct LaneCost {
   double step[5] = {0, 0, 0, 0, 0};   // index 1..4 = lanes cooperating on the scalar step
   double block = 48;
-  int uq = 2;              // blocks per lane and trip of the read loop (trips are whole)
-  bool paired = false;     // paired-end loop: 2 x trips + 1 blocks; single-end: uq x trips, the partial block one of the stride's
+  int uq = 2;              // blocks per lane and trip of the read loop (paired-end: trips are whole)
+  bool paired = false;     // paired-end loop: 2 x trips + 1 blocks; single-end: one block per stride position, the partial block among them
   int coop_min_quads = 8;  // a chain on several workgroups keeps at least this many blocks per lane (tests lower it)
   int draws = 4;           // draws per Philox block: four words; single-end EIGHT half-words (miso_philox.h, lazy low bits)
-  // exact: what the kernels' loops do (trips are whole; single-end: a partial block is block number nfq of the lanes'
-  // stride -- it takes a slot of the last trip, and a trip of its own only when the full blocks fill the last one)
+  // exact: what the kernels' loops do (paired-end: trips are whole; single-end: a partial block is block number nfq of the
+  // lanes' stride, and the loop ends with steps of one block per lane for the fewer than uq stride positions its trips
+  // leave: as many blocks per lane as the chain has stride positions)
   double blocks_per_lane(int lanes, int n_draw) const {
     const int nfq = n_draw / draws;
     const int nblk = paired ? nfq : nfq + ((n_draw % draws) ? 1 : 0);
+    if (!paired) return static_cast<double>((nblk + lanes - 1) / lanes);
     const int trips = (nblk + uq * lanes - 1) / (uq * lanes);
-    return paired ? 2.0 * trips + 1.0 : static_cast<double>(uq) * trips;
+    return 2.0 * trips + 1.0;
   }
   double wave_step(int lanes, int n_draw) const {   // lanes = lanes striding over the chain's draws (K2_WIDE: 64 x wpb)
     return step[lanes >= 4 ? 4 : lanes] + block * blocks_per_lane(lanes, n_draw);
@@ -49,7 +51,8 @@ struct LaneCost {
 // than the 52 / 115 measured in round 3)
 // (single-end since the lazy low bits: a block is EIGHT reads -- 27 generator instructions + 5 per word for the packed
 // below / equal arithmetic + the loop's share: 97 `v_*` instructions per two blocks in the loop's steady part, 125 in its
-// masked tail trips, 103 before the loop was split -- counted between the loop's header and its backward branch
+// masked tail trips (a masked step of one block per lane ends the loop where the stride positions are odd), 103 before
+// the loop was split -- counted between the loop's header and its backward branch
 // (docs/history.md; round 4's "108" for that loop counted the trip's `s_nop`s and the chunk loop's share as well); the
 // launch time hardly moves between 44 and 96,
 // profiles/r04_lazy_low_bits.txt: `block` stays as fitted)

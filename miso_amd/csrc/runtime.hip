@@ -1924,8 +1924,8 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
           mx = std::max(mx, (n >> bshift) + ((!p.paired && (n & ((1 << bshift) - 1))) ? 1 : 0));
           words += n;
         }
-        const int t = (mx + 2 * G - 1) / (2 * G);             // trips of two Philox blocks per lane
-        trips += p.paired ? 2 * t + 1 : 2 * t;                // counted in blocks per lane
+        const int t = (mx + 2 * G - 1) / (2 * G);             // paired-end: trips of two Philox blocks per lane
+        trips += p.paired ? 2 * t + 1 : (mx + G - 1) / G;     // counted in blocks per lane (single-end: stride positions)
       }
     };
     if (!wpart && q.lane_route) {
@@ -1942,7 +1942,8 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
             const int m = we < pl.wide_wgs.size() ? pl.wide_wgs[we] : 1;     // workgroups of the chain (coop.hpp)
             const int wl = 64 * pl.wpb * m;
             const int t = ((n >> bshift) + ((!p.paired && (n & 7)) ? 1 : 0) + 2 * wl - 1) / (2 * wl);
-            trips += pl.wpb * m * (p.paired ? 2 * t + 1 : 2 * t);
+            const int nb = (n >> bshift) + ((!p.paired && (n & 7)) ? 1 : 0);
+            trips += pl.wpb * m * (p.paired ? 2 * t + 1 : (nb + wl - 1) / wl);
             words += n; waves += pl.wpb * m;
           }
         } else slice(c0, c1, pl.seg_lanes[sg]);

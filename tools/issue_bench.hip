@@ -170,6 +170,83 @@ __global__ void k_ds_read_b64(uint32_t *out, int n, uint32_t seed, unsigned long
   if (threadIdx.x == 0 && blockIdx.x == 0) *cyc = t1 - t0;
 }
 
+// ---- rows for the two-isoform sampler's step (profiles/issue_costs_k2.txt) ----
+// One asm statement per loop trip: PRE (what sets up the trip: the compare that writes the mask, well ahead of its readers)
+// followed by 8 x 8 instructions under test.  %0..%7 chains, a 64-bit scalar scratch (a lane mask) and a 32-bit one (a
+// read lane), vcc declared as clobbered.  PRE is one instruction in 65: not counted.
+#define DEF_KERNEL_32M(NAME, PRE, ASM)                                                       \
+  __global__ void NAME(uint32_t *out, int n, uint32_t seed, unsigned long long *cyc) {       \
+    uint32_t r0 = threadIdx.x + seed, r1 = r0 * 3 + 1, r2 = r0 * 5 + 2, r3 = r0 * 7 + 3,     \
+             r4 = r0 * 11 + 4, r5 = r0 * 13 + 5, r6 = r0 * 17 + 6, r7 = r0 * 19 + 7;         \
+    const uint32_t a = seed | 1u, b = seed * 0x9E3779B9u;                                    \
+    uint64_t sm; uint32_t ss;                                                                \
+    const unsigned long long t0 = __builtin_readcyclecounter();                              \
+    for (int i = 0; i < n; i++) {                                                            \
+      asm volatile(PRE REP8(ASM) REP8(ASM) REP8(ASM) REP8(ASM) REP8(ASM) REP8(ASM) REP8(ASM) REP8(ASM) \
+                   : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "=&s"(sm), "=&s"(ss) \
+                   : "v"(a), "v"(b) : "vcc");                                                \
+    }                                                                                        \
+    const unsigned long long t1 = __builtin_readcyclecounter();                              \
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r0 ^ r1 ^ r2 ^ r3 ^ r4 ^ r5 ^ r6 ^ r7;      \
+    if (threadIdx.x == 0 && blockIdx.x == 0) *cyc = t1 - t0;                                 \
+  }
+// operands: %0..%7 chains, %8 = the 64-bit scalar scratch, %9 = the 32-bit one, %10 = a, %11 = b
+#define P_NONE ""
+#define P_CMP_VCC "v_cmp_le_u32 vcc, %0, %10\n s_nop 4\n"
+#define P_CMP_SGPR "v_cmp_le_u32_e64 %8, %0, %10\n s_nop 4\n"
+#define M_CNDMASK_E32(i) "v_cndmask_b32_e32 %" #i ", %" #i ", %10, vcc\n"
+#define M_CNDMASK_E64(i) "v_cndmask_b32_e64 %" #i ", %" #i ", %10, %8\n"
+#define M_BFI(i) "v_bfi_b32 %" #i ", %10, %11, %" #i "\n"
+#define M_PK_SUB_CLAMP(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n"
+#define M_PK_MIN(i) "v_pk_min_u16 %" #i ", %" #i ", %10\n"
+#define M_PK_ADD(i) "v_pk_add_u16 %" #i ", %" #i ", %10\n"
+// v_readlane_b32 into a scalar, the s_nop the compiler puts behind it, and a VALU reader of that scalar (two instructions
+// and a nop per entry: per_trip counts the pair as ONE)
+#define M_READLANE_NOP(i) "v_readlane_b32 %9, %" #i ", 3\n s_nop 0\n v_add_u32 %" #i ", %9, %" #i "\n"
+DEF_KERNEL_32M(k_cndmask_e32_m, P_CMP_VCC, M_CNDMASK_E32)
+DEF_KERNEL_32M(k_cndmask_e64_m, P_CMP_SGPR, M_CNDMASK_E64)
+DEF_KERNEL_32M(k_bfi, P_NONE, M_BFI)
+DEF_KERNEL_32M(k_pk_sub_clamp, P_NONE, M_PK_SUB_CLAMP)
+DEF_KERNEL_32M(k_pk_min, P_NONE, M_PK_MIN)
+DEF_KERNEL_32M(k_pk_add, P_NONE, M_PK_ADD)
+DEF_KERNEL_32M(k_readlane_nop, P_NONE, M_READLANE_NOP)
+
+// ds_bpermute_b32 round trip: eight independent permutes in flight, one wait, the results feed the next eight (addresses
+// within the wavefront: 4 x lane)
+__global__ void k_ds_bpermute(uint32_t *out, int n, uint32_t seed, unsigned long long *cyc) {
+  uint32_t r0 = threadIdx.x + seed, r1 = r0 * 3 + 1, r2 = r0 * 5 + 2, r3 = r0 * 7 + 3,
+           r4 = r0 * 11 + 4, r5 = r0 * 13 + 5, r6 = r0 * 17 + 6, r7 = r0 * 19 + 7;
+  const uint32_t addr = ((threadIdx.x + 1) & 63) * 4;
+  const unsigned long long t0 = __builtin_readcyclecounter();
+  for (int i = 0; i < n; i++) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      asm volatile("ds_bpermute_b32 %0, %8, %0\n ds_bpermute_b32 %1, %8, %1\n ds_bpermute_b32 %2, %8, %2\n ds_bpermute_b32 %3, %8, %3\n"
+                   "ds_bpermute_b32 %4, %8, %4\n ds_bpermute_b32 %5, %8, %5\n ds_bpermute_b32 %6, %8, %6\n ds_bpermute_b32 %7, %8, %7\n"
+                   "s_waitcnt lgkmcnt(0)\n"
+                   : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7)
+                   : "v"(addr));
+    }
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  out[blockIdx.x * blockDim.x + threadIdx.x] = r0 ^ r1 ^ r2 ^ r3 ^ r4 ^ r5 ^ r6 ^ r7;
+  if (threadIdx.x == 0 && blockIdx.x == 0) *cyc = t1 - t0;
+}
+// one permute at a time: issue, wait, use -- the latency a dependent reader sees
+__global__ void k_ds_bpermute_serial(uint32_t *out, int n, uint32_t seed, unsigned long long *cyc) {
+  uint32_t r0 = threadIdx.x + seed;
+  const uint32_t addr = ((threadIdx.x + 1) & 63) * 4;
+  const unsigned long long t0 = __builtin_readcyclecounter();
+  for (int i = 0; i < n; i++) {
+#pragma unroll
+    for (int u = 0; u < 64; u++)
+      asm volatile("ds_bpermute_b32 %0, %1, %0\n s_waitcnt lgkmcnt(0)\n" : "+v"(r0) : "v"(addr));
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  out[blockIdx.x * blockDim.x + threadIdx.x] = r0;
+  if (threadIdx.x == 0 && blockIdx.x == 0) *cyc = t1 - t0;
+}
+
 typedef void (*kern_t)(uint32_t *, int, uint32_t, unsigned long long *);
 struct Entry { const char *name; kern_t k; int per_trip; };
 
@@ -192,6 +269,11 @@ int main() {
     {"v_rcp_f64", k_rcp_f64, 64}, {"v_div_scale_f64", k_div_scale_f64, 64}, {"v_div_fmas_f64", k_div_fmas_f64, 64},
     {"v_div_fixup_f64", k_div_fixup_f64, 64},
     {"ds_read_b32 (8 + wait)", k_ds_read_b32, 64}, {"ds_read_b64 (8 + wait)", k_ds_read_b64, 64},
+    // the two-isoform sampler's step (profiles/issue_costs_k2.txt); "v_cndmask_b32" above reads a vcc nobody wrote or declared
+    {"v_cndmask e32, vcc set", k_cndmask_e32_m, 64}, {"v_cndmask e64, sgpr mask", k_cndmask_e64_m, 64},
+    {"v_bfi_b32", k_bfi, 64}, {"v_pk_sub_u16 clamp", k_pk_sub_clamp, 64}, {"v_pk_min_u16", k_pk_min, 64},
+    {"v_pk_add_u16", k_pk_add, 64}, {"v_readlane+s_nop+v_add", k_readlane_nop, 64},
+    {"ds_bpermute (8 + wait)", k_ds_bpermute, 64}, {"ds_bpermute, one + wait", k_ds_bpermute_serial, 64},
   };
   const int n = 2000;
   printf("%-24s %28s %28s %28s\n", "", "1 wave/SIMD", "2 waves/SIMD", "4 waves/SIMD");
