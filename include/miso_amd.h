@@ -356,7 +356,14 @@ int miso_batch_coop_retries(const miso_batch_t *batch, int *n);
    the summaries and the file writer see a batch of noSamples samples per event, as the reference returns them.
    rundata.noAccepted / noRejected count the last round (paired-end: all rounds), as the reference's do.
    *rounds = rounds the slowest event of the last launch took (1: every event converged on its own schedule, and
-   always with MISO_STOP_FIXEDNO). */
+   always with MISO_STOP_FIXEDNO).
+   The rounds have no limit of their own, as in the reference: an event goes on until it converges or its schedule
+   reaches maxIterations.  The one limit is the device's 32-bit iteration counter.  The device keeps no chain state
+   between launches and runs round r from the chain's first iteration, so the iterations of ALL rounds through the next
+   one must stay within INT32_MAX (2^31 - 1); an event that would pass that keeps the samples of its last round, where
+   the reference would go on.  The kept window doubles with every round, so this is reached before round 32 whatever
+   the schedule; with 5000 / 500 (window 4500) round 18 is the first that does not fit, 2.4 x 10^9 iterations from the
+   chain's start. */
 int miso_batch_rounds(const miso_batch_t *batch, int *rounds);
 
 /* Measurement: what the last launch put on the device, kernel by kernel (bench.py's VALU roofline

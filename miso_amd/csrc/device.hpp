@@ -83,7 +83,7 @@ struct ChainStats {
 
 constexpr int FLAT_WIDE = 0x100;  // sampler_flat wave_tab: the workgroup's four wavefronts share ONE chain
 constexpr int K2_MAX_SEGS = 16;
-constexpr int MISO_MAX_ROUNDS = 8;   // stop = CONVERGENT_MEAN: rounds a device launch can reproduce (every round at least doubles the kept window)
+constexpr int MISO_MAX_ROUNDS = 32;  // stop = CONVERGENT_MEAN: entries of KernelArgs::round_tab.  No limit of its own: every round doubles the kept window, so the 32-bit iteration counter ends the rounds (runtime.hip converge_rounds) before the 32nd
 constexpr int K2_WIDE = 512;   // seg_lanes value: one chain per workgroup
 constexpr int K2_RED_BYTES = 2 * 8 * 16 + 16 + 16;   // two buffers x (up to) 8 wavefronts x {int64 score sum, int count, int bad} + the barrier's flag + the psi a workgroup-wide chain's first four wavefronts publish (kernels_k2.inl)
 

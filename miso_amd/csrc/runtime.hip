@@ -2095,8 +2095,10 @@ void miso_batch::sync(float *ms) {
 // proposal terms in a round's first ratio" (miso.c:866): the kernels are told where the later rounds open
 // (KernelArgs::round_tab, device.hpp RoundOpen).  The CPU checker's counter mode continues its chains like the
 // reference and addresses the draws by the chain's own iteration number: equal bit for bit (tests/test_gpu_convergent.py).
-// The next round is a batch of its own (only the unconverged events; its sync() recurses).  A launch reproduces at most
-// MISO_MAX_ROUNDS rounds (every round at least doubles the kept window: 2^7 x the first); beyond that the last stands.
+// The next round is a batch of its own (only the unconverged events; its sync() recurses).  The rounds have no limit of
+// their own, as in the reference (`while (1)`): they end when the iterations from the chain's start through the next round
+// no longer fit the kernels' 32-bit counter, and then the last round stands.  The kept window doubles with every round
+// (N' - B' = 2 (N - B)), so that is before round MISO_MAX_ROUNDS = 32, the size of the table of round starts.
 void miso_batch::converge_rounds(float *ms) {
   // once per launch: a second sync() must not test the samples the further rounds have already put in place (they might
   // pass now and reset the accept counts' bookkeeping, or fail and run the rounds -- and the paired-end sums -- twice)
@@ -2107,7 +2109,6 @@ void miso_batch::converge_rounds(float *ms) {
   // this round's own schedule, the reference's (noIterations, noBurnIn): the batch's for the first round
   const int N = round_iters > 0 ? round_iters : p.noIterations, B = round_iters > 0 ? round_burn : p.noBurnIn;
   if (p.stop != MISO_STOP_CONVERGENT_MEAN || p.maxIterations <= N || events.empty()) return;
-  if (static_cast<int>(round_starts.size()) >= MISO_MAX_ROUNDS - 1) return;
   const int S0 = S(), C = p.noChains;
   if (S0 < C) return;                        // fewer kept samples than chains: nothing to assess
   std::vector<unsigned char> out(out_bytes);
@@ -2119,6 +2120,8 @@ void miso_batch::converge_rounds(float *ms) {
   if (again.empty()) return;
   const int64_t N2 = 3LL * N - 2LL * B, total = static_cast<int64_t>(p.noIterations) + N2;
   if (total > INT32_MAX) return;             // (the kernels count iterations in 32 bits)
+  if (static_cast<int>(round_starts.size()) >= MISO_MAX_ROUNDS - 1)   // (a window of >= 1 iteration doubled 31 times is past INT32_MAX)
+    MISO_FAIL(MISO_EINTERNAL, "stop = CONVERGENT_MEAN: more rounds than the table of round starts holds");
   miso_params_t p2 = p;
   p2.noIterations = static_cast<int>(total); p2.noBurnIn = p.noIterations + N;   // miso.c:921-923, behind what has been run
   p2.want_counts_trace = 0; p2.device_match = 0;

@@ -7,6 +7,7 @@ tests/golden/*_convergent.npz: outputs of the reference itself)."""
 import numpy as np
 import pytest
 
+import _convergent_cases as cc
 import _golden
 import miso_amd
 from miso_amd import capi
@@ -142,3 +143,53 @@ def test_batch_where_some_events_converge_and_some_do_not(orc, paired):
     assert b.rounds() == rounds
     for e in range(len(cases)):
         assert np.array_equal(b.result(e).samples, first[e])
+
+
+def _batch_equal(orc, name):
+    """the named batch of tests/_convergent_cases.py on the device, every event against the checker's run of it alone"""
+    c = cc.case(orc, name)
+    cpu, rounds = c.reference(orc), c.rounds(orc)
+    b = cc.run_device(c)
+    wrong = []
+    for i, r in enumerate(cpu):
+        try:
+            _equal(b.result(i), r)
+        except AssertionError as err:
+            wrong.append((i, c.events[i].K, c.events[i].n, rounds[i], str(err).split("\n")[0]))
+    print(name, "rounds", rounds, "device", b.rounds(), b.last_kernels())
+    assert not wrong, "%s: events that differ from the checker (index, isoforms, reads, checker's rounds): %r; rounds of all events %r" % (name, wrong, rounds)
+    assert b.rounds() == max(rounds), (name, b.rounds(), rounds)
+    return b
+
+
+@pytest.mark.parametrize("name", cc.DEEP_NAMES)
+def test_deep_rounds_bit_exact_against_the_checker(orc, name):
+    """Schedules of one and two kept iterations (10 / 9 and 8 / 6, two chains, max_iters 10^7) on events of 2, 3 and 5
+    isoforms and 0 ... 300 reads: 4 to 10 rounds on the checker (tests/test_convergent_cases.py), which like the reference
+    (miso.c:845 `while (1)`) has no limit of its own.  The device reproduces every round the 32-bit iteration counter
+    allows (include/miso_amd.h miso_batch_rounds); it used to hand back the eighth round's samples for the events that
+    take nine and more."""
+    _batch_equal(orc, name)
+
+
+@pytest.mark.parametrize("name", cc.LAG_NAMES)
+def test_lag_that_does_not_divide_the_kept_window(orc, name):
+    """noSamples = C (N - B) / lag rows with fewer filled (miso.c:728, 882-893: quirk C8, the trailing rows stay 0): the last
+    noSamples of a later round (miso.c:976-983) include that round's unfilled rows."""
+    c = cc.case(orc, name)
+    b = _batch_equal(orc, name)
+    S0 = c.kw["chains"] * (c.kw["iters"] - c.kw["burn"]) // c.kw["lag"]
+    for i, r in enumerate(c.rounds(orc)):
+        if r >= 2:                    # the zero rows the checker returns are the device's too (and they are there)
+            empty = cc.unfilled_rows(c.kw, r)
+            assert not b.result(i).samples[S0 - empty:].any(), (name, i, r)
+            assert b.result(i).samples[:S0 - empty].all(), (name, i, r)
+
+
+@pytest.mark.parametrize("name", cc.EDGE_NAMES)
+def test_schedule_edges(orc, name):
+    """burn = 0; burn = iters (no kept sample: both sides stop after one round); max_iters on either side of
+    `maxIterations <= noIterations` (miso.c:908) in the second round; two and six chains."""
+    b = _batch_equal(orc, name)
+    if name.endswith("burn_is_iters"):
+        assert b.rounds() == 1 and b.result(0).samples.shape[0] == 0
