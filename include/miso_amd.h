@@ -428,6 +428,13 @@ enum { MISO_SELFTEST_EXP_N = 0,   /* csrc/detmath_n.hpp det_exp_n<width>, width 
 /* out[i * width + j] = routine(x[(i + j * stride) % n]): the `width` interleaved arguments of one call differ; the
    coefficient tables come from registers, loaded as the kernels load them */
 int miso_selftest_detmath_n(int routine, int width, const double *x, int n, int stride, double *out);
+/* The exp / log of the two-isoform Metropolis-Hastings step as its kernel calls them (csrc/detmath_n.hpp det_exp_r /
+   det_log_r): the wavefront's test, then the routine without special cases or the full one.  out[i] = the value,
+   route[i] = the route element i's wavefront took (MISO_SELFTEST_ROUTE_*); force_full != 0: the full routine at every
+   call, as MISO_K2_FULL_MATH does in the sampler.  Threads behind the last element carry an argument inside the domain. */
+enum { MISO_SELFTEST_EXP_R = 0, MISO_SELFTEST_LOG_R };
+enum { MISO_SELFTEST_ROUTE_FAST = 0, MISO_SELFTEST_ROUTE_FULL };
+int miso_selftest_detmath_routed(int routine, int force_full, const double *x, int n, double *out, int32_t *route);
 /* The draw thresholds: out[i] = #{32-bit words u : the reference's test holds for rnd = fl(fl(u 2^-32) T[i]) against
    c[i]}, 0 .. 2^32 -- `rnd < c` (LT) or `!(rnd > c)` (LE).  Exact for every finite c >= 0, T >= 0. */
 enum { MISO_SELFTEST_K2_THRESHOLD = 0,      /* kernels_k2.inl k2_threshold(c, T): route chosen per wavefront */

@@ -675,6 +675,21 @@ def selftest_detmath_n(fn, x, width=1, stride=0):
     return out
 
 
+SELFTEST_EXP_R, SELFTEST_LOG_R = range(2)
+SELFTEST_ROUTE_FAST, SELFTEST_ROUTE_FULL = range(2)
+
+
+def selftest_detmath_routed(fn, x, force_full=False):
+    """csrc/detmath_n.hpp det_exp_r / det_log_r, the Metropolis-Hastings step's exp / log with the route chosen per
+    wavefront: (values, route of each element's wavefront); element i runs on thread i (64 consecutive elements share a
+    wavefront)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(len(x), np.float64)
+    route = np.full(len(x), -1, np.int32)
+    check(lib().miso_selftest_detmath_routed(int(fn), int(bool(force_full)), _p(x), len(x), _p(out), _p(route)))
+    return out, route
+
+
 def selftest_threshold(routine, c, T):
     """#{32-bit words u for which the reference's draw test holds} as threshold routine `routine` counts it; element i
     runs on thread i (64 consecutive elements share a wavefront)"""

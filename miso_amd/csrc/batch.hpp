@@ -21,6 +21,7 @@ void selftest_detmath(const double *x, int n, double *e, double *l, double *s, d
 void selftest_philox(const uint32_t *in6, int n, uint32_t *out4);
 // kernels_selftest.hip
 void selftest_detmath_n(int fn, int width, const double *x, int n, int stride, double *out);
+void selftest_detmath_routed(int fn, int force_full, const double *x, int n, double *out, int32_t *route);
 void selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out);
 void selftest_count_below(const int32_t *D, const uint32_t *w4, const uint32_t *T, int n, int32_t *out);
 void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double *fp_rep, int il2, const uint32_t *rule_le,

@@ -1008,6 +1008,9 @@ int miso_selftest_philox(const uint32_t *ctr_key6, int n, uint32_t *out4) {
 int miso_selftest_detmath_n(int routine, int width, const double *x, int n, int stride, double *out) {
   return guarded([&] { selftest_detmath_n(routine, width, x, n, stride, out); });
 }
+int miso_selftest_detmath_routed(int routine, int force_full, const double *x, int n, double *out, int32_t *route) {
+  return guarded([&] { selftest_detmath_routed(routine, force_full, x, n, out, route); });
+}
 int miso_selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out) {
   return guarded([&] { selftest_threshold(routine, c, T, n, out); });
 }

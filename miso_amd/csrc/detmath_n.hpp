@@ -139,5 +139,85 @@ __device__ __forceinline__ double det_log_t(double x, const double (&tl)[12]) {
   return o[0];
 }
 
+// ---- the Metropolis-Hastings step's exp / log without the special cases, where none applies ----
+// det_exp_fast / det_log_fast are det_exp_n<1> / det_log_n<1> statement for statement, less the selects whose condition is
+// false on the routine's domain: identities, not approximations -- on the domain the result has the full routine's bits
+// (tests/test_gpu_fast_detmath.py).  det_exp_r / det_log_r choose the route per wavefront.
+//
+// det_exp_fast: |x| <= 700 (a NaN fails the compare).
+//   * xm = (x != x) ? 0 : x               x is not a NaN
+//   * xm = (xm > 710) ? 710 : xm          x <= 700
+//   * xm = (xm < -746) ? -746 : xm        x >= -700: so xm == x
+//   * res = (x > 709.78...) ? +inf : res  x <= 700
+//   * res = (x < -745.2) ? 0 : res        x >= -700
+//   * res = (x != x) ? x : res            x is not a NaN
+//   k = floor(x log2(e) + 0.5) lies in [-1010, 1010], so k1, k2 lie in [-505, 505] and miso_pow2i's argument is in range.
+__device__ __forceinline__ double det_exp_fast(double x, const double (&te)[12]) {
+  const double LOG2E = 1.4426950408889634074;
+  const double LN2_HI = 6.93147180369123816490e-01;
+  const double LN2_LO = 1.90821492927058770002e-10;
+  const double kd = __builtin_floor(x * LOG2E + 0.5);
+  const int k = static_cast<int>(kd);
+  double r = miso_fma(-kd, LN2_HI, x);
+  r = miso_fma(-kd, LN2_LO, r);
+  double p = te[0];
+#pragma unroll
+  for (int i = 1; i < 12; i++) p = miso_fma(p, r, te[i]);
+  p = miso_fma(p, r, 1.0);
+  p = miso_fma(p, r, 1.0);
+  const int k1 = k / 2, k2 = k - k1;
+  return p * miso_pow2i(k1) * miso_pow2i(k2);
+}
+
+// det_log_fast: x positive, normal and finite (class "positive normal").
+//   * sub = (bits >> 52) == 0             the exponent field of a normal number is not 0: sub == 0, so xs == x and e takes no -54
+//   * res = (bits == +inf) ? x : res      x is finite
+//   * res = (x == 0) ? -inf : res         x is normal, not 0
+//   * res = (x < 0) ? NaN : res           x is positive
+//   * res = (x != x) ? x : res            x is not a NaN
+//   The `big` select (m > sqrt 2) belongs to the ordinary path and stays.
+__device__ __forceinline__ double det_log_fast(double x, const double (&tl)[12]) {
+  const double LN2_HI = 6.93147180369123816490e-01;
+  const double LN2_LO = 1.90821492927058770002e-10;
+  const double SQRT2 = 1.41421356237309504880;
+  const uint64_t u = miso_d2u(x);
+  int e = static_cast<int>((u >> 52) & 0x7FF) - 1023;
+  double m = miso_u2d((u & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull);
+  const int big = m > SQRT2;
+  m = big ? m * 0.5 : m;
+  e += big ? 1 : 0;
+  const double f = m - 1.0;
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  const double ed = static_cast<double>(e);
+  double q = tl[0];
+#pragma unroll
+  for (int i = 1; i < 12; i++) q = miso_fma(q, z, tl[i]);
+  const double R = z * q;
+  return miso_fma(ed, LN2_HI, f - (s * (f - R) - ed * LN2_LO));
+}
+
+// The route, per wavefront: the fast routine when EVERY active lane's argument is in its domain (one compare; its lane mask
+// is tested on the scalar side), the full routine for the whole wavefront otherwise.  force_full (0 or 1, wave-uniform:
+// KernelArgs::k2_full_math, tests) sends every call down the full route.  Call in wave-uniform control flow only.
+// full: whether the wavefront took the full route (tests, MISO_K2_ROUTE_COUNT).
+__device__ __forceinline__ double det_exp_r(double x, const double (&te)[12], uint64_t force_full, bool &full) {
+  const uint64_t outside = __builtin_amdgcn_ballot_w64(!(__builtin_fabs(x) <= 700.0));
+  full = (outside | force_full) != 0;
+  if (!full) return det_exp_fast(x, te);
+  return det_exp_t(x, te);
+}
+__device__ __forceinline__ double det_log_r(double x, const double (&tl)[12], uint64_t force_full, bool &full) {
+  // every class but "positive normal" (0x100): NaNs, infinities, negatives, zeros, subnormals.  Written as the one
+  // instruction it is: the ballot of __builtin_amdgcn_class compiles to three (compare, select 0 / 1, compare).
+  // The compare reads EXEC implicitly: an inactive lane's bit is 0, so it counts as inside the domain, as in a ballot.
+  // (Not volatile: device inline assembly is convergent, and every caller is in wave-uniform control flow.)
+  uint64_t outside;
+  asm("v_cmp_class_f64_e64 %0, %1, %2" : "=s"(outside) : "v"(x), "s"(0x3FF & ~0x100));
+  full = (outside | force_full) != 0;
+  if (!full) return det_log_fast(x, tl);
+  return det_log_t(x, tl);
+}
+
 }  // namespace
 }  // namespace miso

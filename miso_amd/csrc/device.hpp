@@ -145,6 +145,7 @@ struct KernelArgs {
   int32_t seg_slot[K2_MAX_SEGS + 1];
   int32_t seg_lanes[K2_MAX_SEGS];
   int32_t seg_ts[K2_MAX_SEGS];   // sampler_grp_multi: the segment's tstride (eight chains of a wavefront keep their score tables in global memory)
+  int32_t k2_full_math;     // tests: the two-isoform Metropolis-Hastings step's exp / log through the full routines at every call (detmath_n.hpp det_exp_r / det_log_r).  Last, so that no other field moves
 };
 
 #ifdef __HIPCC__

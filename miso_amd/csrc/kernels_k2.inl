@@ -43,6 +43,15 @@
 #define MISO_K2_UQ 2   // Philox blocks in flight per lane in the single-end read loop
 #endif
 
+// diagnostic build (-DMISO_K2_ROUTE_COUNT, with MISO_K2_TAB_REGS 1): ChainStats::hw_id carries, instead of the hardware id, how
+// many of its wavefront's exp / log calls took the full route (high half-word, saturating) and how many calls there were
+// in units of 256 (low half-word) -- tools/k2_route_share.py
+#ifdef MISO_K2_ROUTE_COUNT
+#define ROUTE_COUNT(full) (rc_calls++, rc_full += (full) ? 1u : 0u)
+#else
+#define ROUTE_COUNT(full) ((void) (full))
+#endif
+
 #ifdef MISO_K2_PROFILE
 #define PROF_T(var) const uint64_t var = __builtin_readcyclecounter()
 #define PROF_ADD(acc, t0, t1) acc += (t1) - (t0)
@@ -819,10 +828,16 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   };
   // alpha' = alpha + sd z, psi' = logit_inv(alpha') (miso.c:449-471)
 #if MISO_K2_TAB_REGS
+#ifdef MISO_K2_ROUTE_COUNT
+  uint32_t rc_calls = 0, rc_full = 0;
+#endif
   double TE[12], TL[12];
   det_tables_to_registers(TE, TL);
-  auto k2_exp = [&](double v) { return det_exp_t(v, TE); };
-  auto k2_log = [&](double v) { return det_log_t(v, TL); };
+  // the routines without their special cases where no active lane's argument needs one (detmath_n.hpp det_exp_r / det_log_r:
+  // a wave-uniform choice, every call site is in wave-uniform control flow); MISO_K2_FULL_MATH: the full routines always
+  const uint64_t full_math = a.k2_full_math != 0;
+  auto k2_exp = [&](double v) { bool full; const double y = det_exp_r(v, TE, full_math, full); ROUTE_COUNT(full); return y; };
+  auto k2_log = [&](double v) { bool full; const double y = det_log_r(v, TL, full_math, full); ROUTE_COUNT(full); return y; };
 #else
   auto k2_exp = [](double v) { return miso_det_exp(v); };
   auto k2_log = [](double v) { return miso_det_log(v); };
@@ -1015,6 +1030,9 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     st->counts_hash = hash;
     st->accepted = accepted;
     st->hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID, all 32 bits
+#if defined(MISO_K2_ROUTE_COUNT) && MISO_K2_TAB_REGS
+    st->hw_id = (min(rc_full, 0xFFFFu) << 16) | min(rc_calls >> 8, 0xFFFFu);
+#endif
 #ifdef MISO_K2_WAVETIME
     uint64_t wt_t1;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wt_t1) : : "memory");

@@ -53,6 +53,23 @@ __global__ void __launch_bounds__(256) selftest_detmath_n_kernel(int fn, int wid
   }
 }
 
+// det_exp_r / det_log_r as the two-isoform kernel's k2_exp / k2_log call them.  Element order = thread order; every thread of a
+// wavefront with an element stays active through the call (the route is the wavefront's), the ones behind the last element
+// with an argument both fast routes accept.
+__global__ void __launch_bounds__(256) selftest_detmath_routed_kernel(int fn, int force_full, const double *x, int n, double *out, int32_t *route) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double te[12], tl[12];
+  det_tables_to_registers(te, tl);
+  const bool on = i < n;
+  const double v = on ? x[i] : 1.0;
+  const uint64_t force = force_full != 0;
+  bool full = false;
+  double y;
+  if (fn == MISO_SELFTEST_LOG_R) y = det_log_r(v, tl, force, full);
+  else y = det_exp_r(v, te, force, full);
+  if (on) { out[i] = y; route[i] = full ? MISO_SELFTEST_ROUTE_FULL : MISO_SELFTEST_ROUTE_FAST; }
+}
+
 // Element order = thread order: elements 64 w .. 64 w + 63 share a wavefront, so the caller decides what a wavefront-uniform
 // choice of route (__all / __any) sees.  Threads behind the last element carry an input that every fast route accepts.
 __global__ void __launch_bounds__(256) selftest_threshold_kernel(int routine, const double *c_in, const double *T_in, int n, uint64_t *out) {
@@ -226,6 +243,19 @@ void selftest_detmath_n(int fn, int width, const double *x, int n, int stride, d
   double *dout = b.out<double>(static_cast<size_t>(n) * width);
   hipLaunchKernelGGL(selftest_detmath_n_kernel, st_grid(n), dim3(256), 0, 0, fn, width, dx, n, stride, dout);
   b.back(out, dout, static_cast<size_t>(n) * width);
+}
+
+void selftest_detmath_routed(int fn, int force_full, const double *x, int n, double *out, int32_t *route) {
+  if (fn != MISO_SELFTEST_EXP_R && fn != MISO_SELFTEST_LOG_R) MISO_FAIL(MISO_EINVAL, "no such routed detmath routine");
+  st_need_device(n);
+  if (n == 0) return;
+  StBuffers b;
+  const double *dx = b.in(x, static_cast<size_t>(n));
+  double *dout = b.out<double>(static_cast<size_t>(n));
+  int32_t *droute = b.out<int32_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_detmath_routed_kernel, st_grid(n), dim3(256), 0, 0, fn, force_full, dx, n, dout, droute);
+  b.back(out, dout, static_cast<size_t>(n));
+  b.back(route, droute, static_cast<size_t>(n));
 }
 
 void selftest_threshold(int routine, const double *c, const double *T, int n, uint64_t *out) {

@@ -701,6 +701,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   converged_done = false;
   if (probe_armed) { HIP_OK(hipStreamSynchronize(probe_stream)); probe_armed = false; }   // (a launch nobody waited for)
   a.pe_force_exact = std::getenv("MISO_K2_SETTLE_ALL") != nullptr;   // tests (kernels_k2.inl: the rescan for high halves on the threshold)
+  a.k2_full_math = std::getenv("MISO_K2_FULL_MATH") != nullptr;   // tests (detmath_n.hpp: the step's exp / log with their special cases at every call)
   if (const char *env = std::getenv("MISO_COOP_MAX_POLLS")) a.coop_max_polls = static_cast<uint32_t>(std::max(1L, std::atol(env)));   // tests
   // Trailing sample columns stay 0 (miso.c:661, quirk C8) -- they exist only when the lag does not divide the kept
   // iterations; otherwise the kernels overwrite every sample, log score, pick and statistic of the pool, and clearing

@@ -196,6 +196,12 @@ __global__ void k_ds_read_b64(uint32_t *out, int n, uint32_t seed, unsigned long
 #define P_CMP_SGPR "v_cmp_le_u32_e64 %8, %0, %10\n s_nop 4\n"
 #define M_CNDMASK_E32(i) "v_cndmask_b32_e32 %" #i ", %" #i ", %10, vcc\n"
 #define M_CNDMASK_E64(i) "v_cndmask_b32_e64 %" #i ", %" #i ", %10, %8\n"
+// the e64 encoding with VCC as its mask: is the e32 row's cost the encoding's or VCC's?
+#define M_CNDMASK_E64_VCC(i) "v_cndmask_b32_e64 %" #i ", %" #i ", %10, vcc\n"
+// a select whose scalar-pair mask was written by a compare two instructions earlier: compare, one instruction the select
+// does not depend on, select (of a and b, so that only the mask ties it to what came before); three instructions per
+// entry, per_trip counts all three
+#define M_CMP_NEAR_CNDMASK(i) "v_cmp_le_u32_e64 %8, %" #i ", %10\n v_add_u32 %" #i ", %" #i ", %11\n v_cndmask_b32_e64 %" #i ", %10, %11, %8\n"
 #define M_BFI(i) "v_bfi_b32 %" #i ", %10, %11, %" #i "\n"
 #define M_PK_SUB_CLAMP(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n"
 #define M_PK_MIN(i) "v_pk_min_u16 %" #i ", %" #i ", %10\n"
@@ -205,6 +211,8 @@ __global__ void k_ds_read_b64(uint32_t *out, int n, uint32_t seed, unsigned long
 #define M_READLANE_NOP(i) "v_readlane_b32 %9, %" #i ", 3\n s_nop 0\n v_add_u32 %" #i ", %9, %" #i "\n"
 DEF_KERNEL_32M(k_cndmask_e32_m, P_CMP_VCC, M_CNDMASK_E32)
 DEF_KERNEL_32M(k_cndmask_e64_m, P_CMP_SGPR, M_CNDMASK_E64)
+DEF_KERNEL_32M(k_cndmask_e64_vcc, P_CMP_VCC, M_CNDMASK_E64_VCC)
+DEF_KERNEL_32M(k_cmp_near_cndmask, P_NONE, M_CMP_NEAR_CNDMASK)
 DEF_KERNEL_32M(k_bfi, P_NONE, M_BFI)
 DEF_KERNEL_32M(k_pk_sub_clamp, P_NONE, M_PK_SUB_CLAMP)
 DEF_KERNEL_32M(k_pk_min, P_NONE, M_PK_MIN)
@@ -271,6 +279,7 @@ int main() {
     {"ds_read_b32 (8 + wait)", k_ds_read_b32, 64}, {"ds_read_b64 (8 + wait)", k_ds_read_b64, 64},
     // the two-isoform sampler's step (profiles/issue_costs_k2.txt); "v_cndmask_b32" above reads a vcc nobody wrote or declared
     {"v_cndmask e32, vcc set", k_cndmask_e32_m, 64}, {"v_cndmask e64, sgpr mask", k_cndmask_e64_m, 64},
+    {"v_cndmask e64, vcc mask", k_cndmask_e64_vcc, 64}, {"cmp e64, add, cndmask e64", k_cmp_near_cndmask, 192},
     {"v_bfi_b32", k_bfi, 64}, {"v_pk_sub_u16 clamp", k_pk_sub_clamp, 64}, {"v_pk_min_u16", k_pk_min, 64},
     {"v_pk_add_u16", k_pk_add, 64}, {"v_readlane+s_nop+v_add", k_readlane_nop, 64},
     {"ds_bpermute (8 + wait)", k_ds_bpermute, 64}, {"ds_bpermute, one + wait", k_ds_bpermute_serial, 64},
