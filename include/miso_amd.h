@@ -253,6 +253,20 @@ int miso_batch_summarize_as_text(miso_batch_t *batch, double confidence_level);
 int miso_batch_get_summary(const miso_batch_t *batch, int event_index, double *mean, double *ci_low,
                            double *ci_high);
 
+/* Chain diagnostics on the device, from the samples of the last launch (same preconditions as miso_batch_summarize;
+   DESIGN.md 14): per (event, isoform) column the split R-hat of its chains, the effective sample size and Monte-Carlo
+   standard error of the psi mean, and the lag at which Geyer's initial monotone sequence was cut.  Sample column s
+   belongs to chain s % noChains; each chain's n = S div noChains draws are split into their first and last h = n div 2.
+   noChains = 0: the batch's own chains -- MISO_EINVAL for a batch of adopted samples (miso_batch_from_samples,
+   miso_batch_from_miso_text), which has none; any other value is used as given (1 .. 2048).  h < 4: MISO_EINVAL
+   "Too few samples per chain for diagnostics", before any launch.  A column that is constant or holds a NaN or an
+   infinity gets rhat = ess = mcse = NaN and lag = 0.  rhat / ess / mcse / lag: noiso doubles each. */
+int miso_batch_diagnose(miso_batch_t *batch, int noChains);
+int miso_batch_get_diagnostics(const miso_batch_t *batch, int event_index, double *rhat, double *ess, double *mcse,
+                               double *lag);
+/* Kernel time (HIP events) of the last miso_batch_summarize[_as_text] and miso_batch_diagnose of this batch, ms; 0 before. */
+int miso_batch_pass_ms(const miso_batch_t *batch, float *summarize_ms, float *diagnose_ms);
+
 /* Samples that were produced elsewhere -- parsed `.miso` files: summarize_miso and compare_miso work on directories of
    them (misopy/samples_utils.py:263-329, hypothesis_test.py:186-345).  Event i has noiso[i] isoforms and n_samples
    samples in the file's layout (samples[i]: n_samples rows of noiso[i] values).  The batch lives on `device` and

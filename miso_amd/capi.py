@@ -300,6 +300,42 @@ class Batch:
             check(f(h, int(i), C.c_void_p(base[0] + o), C.c_void_p(base[1] + o), C.c_void_p(base[2] + o)))
         return [(buf[0, offs[j]:offs[j + 1]], buf[1, offs[j]:offs[j + 1]], buf[2, offs[j]:offs[j + 1]]) for j in range(len(indices))]
 
+    def diagnose(self, chains=None):
+        """Device-side chain diagnostics of every event (no sample download; miso_batch_diagnose): split
+        R-hat, effective sample size, Monte-Carlo standard error of the psi mean.  chains: how many chains the sample
+        columns interleave (column s is chain s % chains); None = the batch's own, which a batch of adopted samples
+        does not have."""
+        check(lib().miso_batch_diagnose(self.handle, C.c_int(0 if chains is None else int(chains))))
+
+    def diagnostics(self, i):
+        """(rhat[K], ess[K], mcse[K], lag[K]) of event i after diagnose(); lag as integers."""
+        K = C.c_int()
+        check(lib().miso_batch_event_info(self.handle, i, C.byref(K), None, None, None))
+        r, e, m, l = (np.zeros(K.value) for _ in range(4))
+        check(lib().miso_batch_get_diagnostics(self.handle, i, _p(r), _p(e), _p(m), _p(l)))
+        return r, e, m, l.astype(np.int64)
+
+    def diagnostics_many(self, indices, noiso):
+        """[(rhat[K], ess[K], mcse[K], lag[K])] of the given events after diagnose(): diagnostics() for many events, as
+        summaries() is summary()'s."""
+        offs = np.concatenate([[0], np.cumsum(np.asarray(noiso, dtype=np.int64))])
+        buf = np.zeros((4, int(offs[-1])))
+        base = [buf[r].ctypes.data for r in range(4)]
+        f = lib().miso_batch_get_diagnostics
+        h = self.handle
+        for j, i in enumerate(indices):
+            o = 8 * int(offs[j])
+            check(f(h, int(i), *(C.c_void_p(base[r] + o) for r in range(4))))
+        lag = buf[3].astype(np.int64)
+        return [(buf[0, offs[j]:offs[j + 1]], buf[1, offs[j]:offs[j + 1]], buf[2, offs[j]:offs[j + 1]], lag[offs[j]:offs[j + 1]])
+                for j in range(len(indices))]
+
+    def pass_ms(self):
+        """(summarize_ms, diagnose_ms): kernel time of the last summarize() and diagnose() of this batch (HIP events)."""
+        a, b = C.c_float(0), C.c_float(0)
+        check(lib().miso_batch_pass_ms(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def compare(self, other, smoothing=0.3):
         """Two-sample comparison with `other` (same events, same order) on the device."""
         check(lib().miso_batch_compare(self.handle, other.handle, C.c_double(smoothing)))
@@ -499,7 +535,8 @@ class Batch:
 
 class SamplesBatch(Batch):
     """Posterior samples produced elsewhere (parsed `.miso` files) on the device: summarize(), summary(i),
-    compare(other), comparison(i) as on a sampled batch (miso_batch_from_samples)."""
+    compare(other), comparison(i), diagnose(chains), diagnostics(i), diagnostics_many() as on a sampled batch
+    (miso_batch_from_samples); diagnose() needs its `chains` here, the samples carry no chain count."""
 
     def __init__(self, samples, device=0):
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in samples]     # each [S, K]

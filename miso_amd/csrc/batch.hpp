@@ -59,6 +59,9 @@ struct CoopTable {
 struct GrpShape { int qs = 0, ts = 0; };   // sampler_grp's slice: class thresholds (single-end), score table (paired-end)
 }  // namespace miso
 
+// diagnose(): chains at most (three doubles of LDS per split sequence)
+constexpr int DIAG_MAX_CHAINS = 2048;
+
 struct miso_batch {
   miso_params_t p{};
   miso::FragmentDist fd;                 // paired only
@@ -212,6 +215,12 @@ struct miso_batch {
   bool summarized = false;
   std::vector<double> h_compare;        // per event: K x {mean1, mean2, bayes factor, posterior density at 0}
   bool compared = false;
+  std::vector<double> h_diag;           // per event: K x {rhat, ess, mcse, lag} (kernels_diagnose.hip)
+  std::vector<uint64_t> h_diag_off;     // offsets (in doubles) into h_diag
+  bool diagnosed = false;
+  float summarize_ms = 0.f, diagnose_ms = 0.f;   // kernel time of the last summarize / diagnose pass
+  hipEvent_t pass_ev0 = nullptr, pass_ev1 = nullptr;   // bracket that pass; made by the first one
+  bool adopted = false;                 // samples produced elsewhere (adopt_pool): p.noChains says nothing about them
   uint64_t in_bytes = 0, out_bytes = 0;
   float last_ms = 0.f;
 
@@ -230,6 +239,7 @@ struct miso_batch {
   void sync(float *ms);
   void download();
   void summarize(double confidence_level, bool as_text = false);
+  void diagnose(int noChains);
   void adopt_samples(int n, const int *K, int S, const double *const *samples, int dev);
   void adopt_pool(int n, const int *K, int S, int dev);
   // kernels_text.hip: the pool filled from `.miso` sample text by text_decode_kernel

@@ -801,6 +801,33 @@ int miso_batch_get_summary(const miso_batch_t *b, int i, double *mean, double *c
   });
 }
 
+int miso_batch_diagnose(miso_batch_t *b, int noChains) {
+  return guarded([&] { need(b, "batch"); b->diagnose(noChains); });
+}
+
+int miso_batch_get_diagnostics(const miso_batch_t *b, int i, double *rhat, double *ess, double *mcse, double *lag) {
+  return guarded([&] {
+    need(b, "batch");
+    const PackedEvent &e = event_at(b, i);
+    if (!b->diagnosed) MISO_FAIL(MISO_EINVAL, "miso_batch_diagnose has not run");
+    const double *s = b->h_diag.data() + b->h_diag_off[i];
+    for (int k = 0; k < e.K; k++) {
+      if (rhat) rhat[k] = s[4 * k];
+      if (ess) ess[k] = s[4 * k + 1];
+      if (mcse) mcse[k] = s[4 * k + 2];
+      if (lag) lag[k] = s[4 * k + 3];
+    }
+  });
+}
+
+int miso_batch_pass_ms(const miso_batch_t *b, float *summarize_ms, float *diagnose_ms) {
+  return guarded([&] {
+    need(b, "batch");
+    if (summarize_ms) *summarize_ms = b->summarize_ms;
+    if (diagnose_ms) *diagnose_ms = b->diagnose_ms;
+  });
+}
+
 int miso_batch_compare(miso_batch_t *a, miso_batch_t *b, double smoothing) {
   return guarded([&] { need(a, "batch"); need(b, "batch"); a->compare(*b, smoothing); });
 }

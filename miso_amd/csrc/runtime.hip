@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "batch.hpp"
+#include "compare_column.hpp"
 #include "coop.hpp"
 #include "miso_binomial.h"
 
@@ -40,6 +41,7 @@ __global__ void compare_kernel(const DevEvent *, const unsigned char *, const De
 __global__ void match_kernel(const MatchEvent *, const int2 *, const int *, const int *, const int *, const int *,
                              const int *, const int *, const int *, int, int, int, int, int, uint32_t *, uint16_t *);
 __global__ void summarize_kernel(const DevEvent *, const unsigned char *, int, int, int, int, const uint64_t *, double *, int);
+__global__ void diagnose_kernel(const DevEvent *, const unsigned char *, int, int, int, int, double, int, const uint64_t *, double *);
 template <int G, bool PE, int KC, bool WIDE = false> __global__ void sampler_grp(const KernelArgs a);
 template <int KC> __global__ void sampler_grp_multi(const KernelArgs a);
 __global__ void sampler_grp_all(const KernelArgs a);   // kernels_grp_all.hip
@@ -136,11 +138,13 @@ void miso_batch::release() {
   probe_armed = false;
   if (ev0) (void) hipEventDestroy(ev0);
   if (ev1) (void) hipEventDestroy(ev1);
+  if (pass_ev0) (void) hipEventDestroy(pass_ev0);
+  if (pass_ev1) (void) hipEventDestroy(pass_ev1);
   for (hipStream_t st : aux_streams) (void) hipStreamDestroy(st);
   for (hipEvent_t e : aux_done) (void) hipEventDestroy(e);
   aux_streams.clear(); aux_done.clear();
   if (stream) (void) hipStreamDestroy(stream);
-  d_events = nullptr; d_in = d_out = nullptr; d_fp = nullptr; ev0 = ev1 = nullptr; stream = nullptr;
+  d_events = nullptr; d_in = d_out = nullptr; d_fp = nullptr; ev0 = ev1 = pass_ev0 = pass_ev1 = nullptr; stream = nullptr;
   uploaded = launched = downloaded = false;
 }
 
@@ -746,7 +750,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   }
   HIP_OK(hipEventRecord(ev1, stream));
   start_clock_probe();
-  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false;
+  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; diagnosed = false;
 }
 
 // The launch's sizes and switches, read once per launch.
@@ -2180,6 +2184,26 @@ void miso_batch::converge_rounds(float *ms) {
   last_kernels += "," + next->last_kernels;
 }
 
+// The kernel time of a reduction pass over the resident samples (miso_batch_pass_ms), on the batch's pass_ev0 / pass_ev1,
+// made by its first pass: ev0 / ev1 bracket the sampler kernels and sync() reads them later.
+namespace {
+struct PassTimer {
+  hipStream_t st;
+  hipEvent_t &a, &b;
+  PassTimer(hipStream_t s, hipEvent_t &e0, hipEvent_t &e1) : st(s), a(e0), b(e1) {
+    if (!a) HIP_OK(hipEventCreate(&a));
+    if (!b) HIP_OK(hipEventCreate(&b));
+    HIP_OK(hipEventRecord(a, st));
+  }
+  void stop() { HIP_OK(hipEventRecord(b, st)); }
+  float ms() {   // after the stream has been synchronised
+    float v = 0.f;
+    HIP_OK(hipEventElapsedTime(&v, a, b));
+    return v;
+  }
+};
+}  // namespace
+
 // Posterior mean and Chen-Shao credible interval of every isoform, computed where the samples are
 // (credible_intervals.py:31-55: order statistics int(round(alpha/2 n)) - 1 and
 // int(round((1 - alpha/2) n)) - 1, Python-2 rounding = half away from zero).
@@ -2204,13 +2228,59 @@ void miso_batch::summarize(double confidence_level, bool as_text) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_sum), off * sizeof(double)));
   HIP_OK(hipMemcpyAsync(d_off, h_sum_off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  PassTimer timer(stream, pass_ev0, pass_ev1);
   hipLaunchKernelGGL(summarize_kernel, dim3(n, kmax), dim3(256), 0, stream, d_events, d_out, n, Sn, lo, hi,
                      d_off, d_sum, as_text ? 1 : 0);
   HIP_OK(hipGetLastError());
+  timer.stop();
   HIP_OK(hipMemcpyAsync(h_summary.data(), d_sum, off * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
   (void) hipFree(d_off); (void) hipFree(d_sum);
+  summarize_ms = timer.ms();
   summarized = true;
+}
+
+// Chain diagnostics of every (event, isoform) column, computed where the samples are (kernels_diagnose.hip):
+// split R-hat, effective sample size, Monte-Carlo standard error of the mean and the lag at which Geyer's sequence was cut.
+// noChains = 0: the batch's own chains; an adopted batch has none to offer.
+void miso_batch::diagnose(int noChains) {
+  if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (noChains < 0) MISO_FAIL(MISO_EINVAL, "Invalid number of chains");
+  if (noChains == 0 && adopted) MISO_FAIL(MISO_EINVAL, "Adopted samples have no chain count of their own: give noChains");
+  const int C = noChains ? noChains : p.noChains;
+  const int Sn = S();
+  const int n_draws = Sn / C, h = n_draws / 2;
+  if (h < 4) MISO_FAIL(MISO_EINVAL, "Too few samples per chain for diagnostics");
+  // (the per-sequence scratch of a workgroup: three doubles per sequence in LDS)
+  if (C > DIAG_MAX_CHAINS) MISO_FAIL(MISO_EINVAL, "Too many chains for diagnostics");
+  // as summarize(): under CONVERGENT_MEAN the launch is finished once sync() has run its further rounds
+  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  HIP_OK(hipSetDevice(device));
+  const int n = static_cast<int>(events.size());
+  const int M = 2 * C, N = M * h;
+  h_diag_off.assign(n, 0);
+  uint64_t off = 0; int kmax = 1;
+  for (int i = 0; i < n; i++) { h_diag_off[i] = off; off += 4 * events[i].K; kmax = std::max(kmax, events[i].K); }
+  h_diag.assign(off, 0.0);
+  if (n == 0) { diagnosed = true; return; }
+  const bool cached = N <= 256 * miso::SUMMARY_CACHE;
+  const size_t dyn = (static_cast<size_t>(cached ? N : 0) + 3 * static_cast<size_t>(M)) * sizeof(double);
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(diagnose_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             static_cast<int>(dyn)));
+  uint64_t *d_off = nullptr; double *d_diag = nullptr;
+  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
+  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_diag), off * sizeof(double)));
+  HIP_OK(hipMemcpyAsync(d_off, h_diag_off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  PassTimer timer(stream, pass_ev0, pass_ev1);
+  hipLaunchKernelGGL(diagnose_kernel, dim3(n, kmax), dim3(256), dyn, stream, d_events, d_out, n, C, n_draws, h,
+                     std::log10(static_cast<double>(N)), cached ? 1 : 0, d_off, d_diag);
+  HIP_OK(hipGetLastError());
+  timer.stop();
+  HIP_OK(hipMemcpyAsync(h_diag.data(), d_diag, off * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  (void) hipFree(d_off); (void) hipFree(d_diag);
+  diagnose_ms = timer.ms();
+  diagnosed = true;
 }
 
 // Two-sample comparison of this batch (sample 1) with `other` (sample 2), event by event and
@@ -2284,7 +2354,7 @@ void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
   n_k2 = n_k2w = n_gen = 0; gen_runs.clear(); plan = LaunchPlan{};
-  uploaded = launched = true; downloaded = false; summarized = compared = false;
+  uploaded = launched = true; downloaded = false; summarized = compared = diagnosed = false; adopted = true;
 }
 
 void miso_batch::download() {

@@ -132,8 +132,10 @@ class GenesDispatcher(object):
     def __init__(self, gff_dir, bam_filename, output_dir, read_len, overhang_len,
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
-                 labels=("sample1", "sample2"), summary_only=False, prefilter=False):
+                 labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False):
         self.summary_only = bool(summary_only)
+        self.diagnostics = bool(diagnostics)
+        self.diag_tables = []          # --diagnostics: [(table, its per-worker parts)], one per output directory (run)
         self.prefilter = bool(prefilter)
         self.event_numbers = None      # --prefilter: gene id -> its number in the whole gene list
         self.gene_samples = None       # --prefilter --compare: gene id -> the samples whose filter it passes
@@ -264,6 +266,13 @@ class GenesDispatcher(object):
             table = None
         if table is not None:
             os.makedirs(os.path.dirname(table), exist_ok=True)
+        self.diag_tables = []
+        if self.diagnostics:
+            # one table per directory of `.miso` files: the output directory, or with --compare each label's
+            for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
+                label = os.path.basename(os.path.normpath(d))
+                self.diag_tables.append((os.path.join(d, "summary", label + ".miso_diag"), []))
+                os.makedirs(os.path.dirname(self.diag_tables[-1][0]), exist_ok=True)
         for batch_num, (fname, size, first) in enumerate(batches):
             if size == 0:
                 continue
@@ -273,6 +282,11 @@ class GenesDispatcher(object):
             if self.compare_bam is not None:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compare-genes-from-file", fname,
                        self.bam_filename, self.compare_bam, out1, out2, part]
+                if self.diag_tables:
+                    dparts = ["%s.gpu%d" % (t, batch_num) for t, _ in self.diag_tables]
+                    for (_, plist), dp in zip(self.diag_tables, dparts):
+                        plist.append(dp)
+                    cmd += ["--diagnostics-files"] + dparts
             else:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compute-genes-from-file", fname,
                        self.bam_filename, self.output_dir]
@@ -280,6 +294,9 @@ class GenesDispatcher(object):
                     cmd += ["--summary-file", part]
                     if self.summary_only:
                         cmd += ["--no-miso-files"]
+                if self.diag_tables:
+                    self.diag_tables[0][1].append("%s.gpu%d" % (self.diag_tables[0][0], batch_num))
+                    cmd += ["--diagnostics-file", self.diag_tables[0][1][-1]]
             # more chunks than GPUs (-p above the GPU count) share the GPUs round robin
             cmd += ["--read-len", str(self.read_len), "--device", str(batch_num % self.n_gpus),
                     "--first-event-id", str(first)]
@@ -358,13 +375,17 @@ class GenesDispatcher(object):
             from .run_miso import merge_tables
             merge_tables(parts, table)
             print("Wrote %s" % table)
+        for diag_table, diag_parts in self.diag_tables:
+            from .run_miso import merge_tables
+            merge_tables(diag_parts, diag_table)
+            print("Wrote %s" % diag_table)
         return failed
 
 
 def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_len=1,
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
-                          labels=("sample1", "sample2"), summary_only=False, prefilter=False):
+                          labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -376,7 +397,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            settings_fname=settings_fname, paired_end=paired_end, num_proc=num_proc,
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
-                           prefilter=prefilter).run()
+                           prefilter=prefilter, diagnostics=diagnostics).run()
 
 
 def main(argv=None):
@@ -399,6 +420,10 @@ def main(argv=None):
     ap.add_argument("--summary-only", action="store_true",
                     help="--summarize without the per-event .miso files: the run's product is the summary table alone "
                          "(what summarize_miso needs of a .miso file is its mean and credible interval, samples_utils.py:263-329)")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="also write OUT/summary/<OUT>.miso_diag: per event the split R-hat of its chains, the effective "
+                         "sample size and the Monte-Carlo standard error of the Psi mean, computed on the GPU during the run; "
+                         "with --compare one table per label: OUT/<label>/summary/<label>.miso_diag")
     ap.add_argument("--compare", metavar="BAM2", default=None,
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
@@ -433,7 +458,7 @@ def main(argv=None):
                                        summary_only=a.summary_only,
                                        compare_bam=None if a.compare is None else
                                        os.path.abspath(os.path.expanduser(a.compare)),
-                                       labels=tuple(a.labels), prefilter=a.prefilter)
+                                       labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

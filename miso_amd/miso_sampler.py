@@ -25,6 +25,7 @@ import capi  # noqa: E402  (miso_amd/capi.py: the batch object behind run_sample
 
 capi.InternalError = pysplicing.InternalError   # one exception type for callers of this module
 import summary  # noqa: E402  (miso_amd/summary.py)
+import diagnostics  # noqa: E402  (miso_amd/diagnostics.py)
 import compare  # noqa: E402  (miso_amd/compare.py)
 
 
@@ -161,7 +162,7 @@ class MISOSampler:
     def run_sampler_batch(self, num_iters, events, num_chains=6, burn_in=1000, lag=2,
                           start_cond=pysplicing.MISO_START_AUTO,
                           stop_cond=pysplicing.MISO_STOP_FIXEDNO, seed=None, first_event_id=0,
-                          verbose=False, summary_file=None, confidence_level=0.95, threads=0):
+                          verbose=False, summary_file=None, confidence_level=0.95, threads=0, diagnostics_file=None):
         """events: list of (reads, gene, output_file[, prior_params[, event_id]]); `reads` is the
         reference's (positions 0-based, cigars) pair or an AlnRegion; event_id pins the event's
         random stream (default: first_event_id + its position among the events actually sampled).  Same per-event skip rules as run_sampler
@@ -171,13 +172,14 @@ class MISOSampler:
         Returns the list of written file names (None for skipped events).
         summary_file: also write the `summarize_miso` table (samples_utils.py:263-329) for the
         events of this batch, from means / credible intervals computed on the device.
+        diagnostics_file: also write the chain diagnostics table (diagnostics.py) of these events.
         = prepare_batch (host: skip rules, reads into the batch) + finish_batch (GPU + files); a caller
         with several batches can overlap one's finish with the next one's prepare (run_miso.py)."""
         state = self.prepare_batch(num_iters, events, num_chains=num_chains, burn_in=burn_in, lag=lag,
                                    start_cond=start_cond, stop_cond=stop_cond, verbose=verbose)
         return self.finish_batch(state, seed=seed, first_event_id=first_event_id, verbose=verbose,
                                  summary_file=summary_file, confidence_level=confidence_level,
-                                 threads=threads)
+                                 threads=threads, diagnostics_file=diagnostics_file)
 
     def prepare_batch(self, num_iters, events, num_chains=6, burn_in=1000, lag=2,
                       start_cond=pysplicing.MISO_START_AUTO, stop_cond=pysplicing.MISO_STOP_FIXEDNO,
@@ -306,7 +308,7 @@ class MISOSampler:
         return (batch, slots, written, int(num_iters), int(burn_in), int(lag))
 
     def finish_batch(self, state, seed=None, first_event_id=0, verbose=False, summary_file=None,
-                     confidence_level=0.95, threads=0, write_files=True):
+                     confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None):
         """Launch, then the event's outputs.  write_files=False (with a summary_file): no per-event `.miso` file --
         the posterior means and credible intervals that `summarize_miso` would compute from those files
         (samples_utils.py:263-329) come from the device, summarised from the four-decimal text the file WOULD hold.
@@ -314,7 +316,7 @@ class MISOSampler:
         launch beside this one's outputs."""
         self.launch_batch(state, seed=seed, first_event_id=first_event_id)
         return self.output_batch(state, verbose=verbose, summary_file=summary_file, confidence_level=confidence_level,
-                                 threads=threads, write_files=write_files)
+                                 threads=threads, write_files=write_files, diagnostics_file=diagnostics_file)
 
     def launch_batch(self, state, seed=None, first_event_id=0):
         """Upload, sample, download (native code, the interpreter lock released throughout)."""
@@ -344,10 +346,12 @@ class MISOSampler:
                    ",".join(str(iso.genomic_end) for iso in gene.isoforms)))
 
     def output_batch(self, state, verbose=False, summary_file=None, confidence_level=0.95, threads=0,
-                     write_files=True):
+                     write_files=True, diagnostics_file=None):
         """The `.miso` files and / or the summary table of a launched batch.  The header's run-dependent fields are
         formatted natively for the whole batch (miso_batch_header_fields); miso_header() below is the same line field
-        by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte)."""
+        by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte).
+        diagnostics_file: the chain diagnostics table of the written events (diagnostics.py), from the full-precision
+        samples resident on the device; nothing else changes with it."""
         batch, slots, written, num_iters, burn_in, lag = state
         if not slots:
             return written
@@ -362,6 +366,12 @@ class MISOSampler:
         sums = None
         if summary_file is not None:
             sums = batch.summaries([idx for _, idx, _, _ in slots], [len(gene.isoforms) for _, _, gene, _ in slots])
+        diags, diag_rows = None, []
+        if diagnostics_file is not None:
+            batch.diagnose()
+            diags = batch.diagnostics_many([idx for _, idx, _, _ in slots], [len(gene.isoforms) for _, _, gene, _ in slots])
+            n_chains = int(batch.params.noChains)
+            n_samples = n_chains * (num_iters - burn_in) // lag
         for j, ((i, idx, gene, out), (unassigned, pa, counts, assigned)) in enumerate(zip(slots, fields)):
             if unassigned:                                                # miso_sampler.py:352-354
                 if verbose:
@@ -382,11 +392,15 @@ class MISOSampler:
                 hdr = {"isoforms": head[len("#isoforms="):head.index("\texon_lens=")], "counts": counts, "assigned_counts": assigned}
                 hdr.update(kv.split("=", 1) for kv in tail.rstrip("\n").split("\t"))
                 rows.append((name,) + tuple(sums[j]) + (hdr,))
+            if diagnostics_file is not None:
+                diag_rows.append((os.path.basename(out)[:-len(".miso")],) + tuple(diags[j]) + (n_samples, n_chains))
         t2 = time.time()
         if write_files:
             batch.write_miso_files(idxs, paths, headers, threads)
         if summary_file is not None:
             summary.write_summary(summary_file, rows)
+        if diagnostics_file is not None:
+            diagnostics.write_diagnostics(diagnostics_file, diag_rows)
         if timing:
             print("[miso] batch of %d events: headers %.2f s, .miso files / table %.2f s"
                   % (len(slots), t2 - t1, time.time() - t2))
@@ -395,7 +409,8 @@ class MISOSampler:
     # -- two RNA-seq samples over the same events + Bayes factors (compare_miso) ----------------
     def run_comparison_batch(self, num_iters, events1, events2, comparison_file, num_chains=6,
                              burn_in=1000, lag=2, seed=None, seed2=None, first_event_id=0,
-                             confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None):
+                             confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
+                             diagnostics_files=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -403,7 +418,9 @@ class MISOSampler:
         compare_miso leaves out events missing from one directory (hypothesis_test.py:262-264).
         event_ids[i] (optional): event i's id in the random-number counter -- its number in the caller's
         full event list -- so that skipped events and chunking change nobody's random stream; default
-        first_event_id + position among the events that are run."""
+        first_event_id + position among the events that are run.
+        diagnostics_files (optional): (file1, file2), the chain diagnostics table (diagnostics.py) of each sample's
+        written events, from the samples resident on the device."""
         if len(events1) != len(events2):
             raise ValueError("the two samples must list the same events")
         keep = []
@@ -414,6 +431,7 @@ class MISOSampler:
                 keep.append((i, e1[1], p1, p2))
         written = [None] * len(events1)
         rows = []
+        diag_rows = ([], [])
         if keep:
             self.params.update(iters=num_iters, burn_in=burn_in, lag=lag)
             kw = dict(seed=seed if seed is not None else random.getrandbits(64), seed2=seed2,
@@ -422,18 +440,30 @@ class MISOSampler:
                 kw["paired"] = (float(self.mean_frag_len), float(self.frag_variance), 4.0)
             if event_ids is not None:
                 kw["event_ids"] = tuple(int(event_ids[p[0]]) for p in keep)
-            r1, r2, cmp = pysplicing.MISOCompareBatch(
+            if diagnostics_files is not None:
+                kw["diagnostics"] = True
+            res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),
                 int(self.params["overhang_len"]), int(num_chains), **kw)
-            for (i, gene, p1, p2), a, b, c in zip(keep, r1, r2, cmp):
+            r1, r2, cmp = res[:3]
+            n_samples = int(num_chains) * (int(num_iters) - int(burn_in)) // int(lag)
+            for j, ((i, gene, p1, p2), a, b, c) in enumerate(zip(keep, r1, r2, cmp)):
                 f1 = self._finish(a, gene, p1[4], num_iters, burn_in, lag, verbose)
                 f2 = self._finish(b, gene, p2[4], num_iters, burn_in, lag, verbose)
                 written[i] = (f1, f2)
+                if diagnostics_files is not None:
+                    for which, f in enumerate((f1, f2)):
+                        if f is not None:
+                            diag_rows[which].append((os.path.basename(f)[:-len(".miso")],) + tuple(res[3][which][j])
+                                                    + (n_samples, int(num_chains)))
                 if f1 is not None and f2 is not None:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
         compare.write_comparison(comparison_file, rows)
+        if diagnostics_files is not None:
+            for f, drows in zip(diagnostics_files, diag_rows):
+                diagnostics.write_diagnostics(f, drows)
         return written
 
     # -- shared pieces -------------------------------------------------------------------------

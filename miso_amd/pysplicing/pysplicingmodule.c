@@ -414,6 +414,24 @@ static PyObject *results_list(miso_batch_t *b, Py_ssize_t n, double conf) {
   return out;
 }
 
+/* chain diagnostics of a finished batch: per event (rhat, ess, mcse, lag), noiso values each */
+static PyObject *diagnostics_list(miso_batch_t *b, Py_ssize_t n) {
+  Py_ssize_t i; int rc;
+  PyObject *out;
+  if (n > 0 && (rc = miso_batch_diagnose(b, 0))) return raise_miso(rc);
+  out = PyList_New(n);
+  for (i = 0; out && i < n; i++) {
+    int K; double r[MISO_MAX_ISOFORMS], e[MISO_MAX_ISOFORMS], m[MISO_MAX_ISOFORMS], l[MISO_MAX_ISOFORMS];
+    PyObject *t;
+    if ((rc = miso_batch_event_info(b, (int) i, &K, NULL, NULL, NULL)) ||
+        (rc = miso_batch_get_diagnostics(b, (int) i, r, e, m, l))) { raise_miso(rc); Py_CLEAR(out); break; }
+    t = Py_BuildValue("(NNNN)", from_doubles(r, K), from_doubles(e, K), from_doubles(m, K), from_doubles(l, K));
+    if (!t) { Py_CLEAR(out); break; }
+    PyList_SET_ITEM(out, i, t);
+  }
+  return out;
+}
+
 static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seedobj,
                               unsigned int first_event_id, PyObject *summaryobj) {
   double conf; miso_batch_t *b; PyObject *out = NULL; Py_ssize_t n;
@@ -434,17 +452,18 @@ static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seed
 static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
-                           "summary", "smoothing", "paired", "event_ids", NULL};
+                           "summary", "smoothing", "paired", "event_ids", "diagnostics", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
-  PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL;
+  PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL;
+  int diagnostics = 0;
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
   int start = MISO_START_AUTO, stop = MISO_STOP_FIXEDNO, rc;
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOO", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOp", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
-                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj)) return NULL;
+                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics)) return NULL;
   if (seedobj && seedobj != Py_None) { seed = PyLong_AsUnsignedLongLongMask(seedobj); if (PyErr_Occurred()) return NULL; }
   else if (default_seed(&seed)) return NULL;
   /* the two samples must not share random numbers: identical draws would correlate the chains */
@@ -488,9 +507,18 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     if (!t) goto done;
     PyList_SET_ITEM(cmp, i, t);
   }
-  out = Py_BuildValue("(OOO)", r1, r2, cmp);
+  /* diagnostics=True: a fourth element, per sample the events' (rhat, ess, mcse, lag) (miso_batch_diagnose) */
+  if (diagnostics) {
+    PyObject *d1 = diagnostics_list(b1, n), *d2 = d1 ? diagnostics_list(b2, n) : NULL;
+    if (d2) dg = PyTuple_Pack(2, d1, d2);
+    Py_XDECREF(d1); Py_XDECREF(d2);
+    if (!dg) goto done;
+    out = Py_BuildValue("(OOOO)", r1, r2, cmp, dg);
+  } else {
+    out = Py_BuildValue("(OOO)", r1, r2, cmp);
+  }
 done:
-  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp);
+  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg);
   if (b1) miso_batch_destroy(b1);
   if (b2) miso_batch_destroy(b2);
   return out;

@@ -146,10 +146,12 @@ def _check_device(device):
 def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, read_len,
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
-                     max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None):
+                     max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
+                     diagnostics_file=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
-    number in the random-number counter (default first_event_id + k)."""
+    number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
+    diagnostics table of this run (diagnostics.py), per launch from the resident samples, merged like the summary parts."""
     os.makedirs(output_dir, exist_ok=True)
     if gene_entries is None:
         gene_entries = [(g, gff_index_filename) for g in gene_ids]
@@ -226,6 +228,7 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     threading.Thread(target=producer, daemon=True).start()
     written = []
     summary_parts = []
+    diag_parts = []
     with ThreadPoolExecutor(1) as gpu, ThreadPoolExecutor(1) as out:
         in_flight = []       # output futures, oldest first: at most two batches behind the one being prepared
         while True:
@@ -254,11 +257,15 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             part = None if summary_file is None else "%s.part%06d" % (summary_file, lo)
             if part:
                 summary_parts.append(part)
+            dpart = None if diagnostics_file is None else "%s.part%06d" % (diagnostics_file, lo)
+            if dpart:
+                diag_parts.append(dpart)
             launched = gpu.submit(sampler.launch_batch, state, seed=seed, first_event_id=first_event_id + lo)
 
-            def outputs(sampler=sampler, state=state, launched=launched, part=part):
+            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart):
                 launched.result()
-                return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files)
+                return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files,
+                                            diagnostics_file=dpart)
             in_flight.append(out.submit(outputs))
         for f in in_flight:
             written += f.result()
@@ -267,6 +274,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     t1 = t0 + t_collect[0]
     if summary_file is not None:
         merge_tables(summary_parts, summary_file)
+    if diagnostics_file is not None:
+        merge_tables(diag_parts, diagnostics_file)
     t2 = time.time()
     if verbose:
         print("Collected %d events in %.2f s (beside the decoding / sampling), batches prepared in %.2f s, whole run %.2f s"
@@ -304,14 +313,16 @@ def merge_tables(parts, filename, remove=True):
 def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, output_dir2,
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
-                     max_events_per_launch=4096, event_ids=None, samples=None):
+                     max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
     computed on the device while the samples are still in HBM.
     event_ids[k]: as for compute_gene_psi.  samples[k] (`miso --run --compare --prefilter`): the samples whose
     coverage filter entry k passes, "1", "2" or "1,2".  An entry is collected only in those samples; one that passes
-    in one sample only is sampled there alone (with that sample's seed) and is not compared."""
+    in one sample only is sampled there alone (with that sample's seed) and is not compared.
+    diagnostics_files: (file1, file2), each sample's chain diagnostics table (diagnostics.py), parts merged like the
+    comparison's."""
     for d in (output_dir1, output_dir2):
         os.makedirs(d, exist_ok=True)
     if device is not None:
@@ -331,6 +342,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     by_no2 = {e[4]: e for e in ev2}
     pairs = [(a, by_no2[a[4]]) for a in ev1 if a[4] in by_no2]
     parts = []
+    diag_parts = ([], [])
     if paired_end:
         mean_frag_len = int(paired_end[0])
         frag_variance = np.power(int(paired_end[1]), 2)
@@ -344,11 +356,17 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=output_dir1)
         part = "%s.part%06d" % (comparison_file, lo)
         parts.append(part)
+        dparts = None
+        if diagnostics_files is not None:
+            dparts = tuple("%s.part%06d" % (f, lo) for f in diagnostics_files)
+            for which in (0, 1):
+                diag_parts[which].append(dparts[which])
         sampler.run_comparison_batch(p["num_iters"], [a[:3] for a, _ in chunk],
                                      [b[:3] for _, b in chunk], part, num_chains=p["num_chains"],
                                      burn_in=p["burn_in"], lag=p["lag"], seed=seed,
                                      first_event_id=first_event_id + lo, verbose=verbose,
-                                     event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk])
+                                     event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
+                                     diagnostics_files=dparts)
     merge_tables(parts, comparison_file)
     if samples is not None:
         # sample 2's stream: the seed MISOCompareBatch derives for it (pysplicingmodule.c)
@@ -363,8 +381,15 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             else:
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
             sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=out)
+            dpart = None
+            if diagnostics_files is not None:
+                dpart = "%s.alone" % diagnostics_files[int(which) - 1]
+                diag_parts[int(which) - 1].append(dpart)
             sampler.run_sampler_batch(p["num_iters"], alone, num_chains=p["num_chains"], burn_in=p["burn_in"],
-                                      lag=p["lag"], seed=s, verbose=verbose)
+                                      lag=p["lag"], seed=s, verbose=verbose, diagnostics_file=dpart)
+    if diagnostics_files is not None:
+        for which in (0, 1):
+            merge_tables(diag_parts[which], diagnostics_files[which])
     return len(pairs)
 
 
@@ -406,6 +431,10 @@ def main(argv=None):
                     help="sample both RNA-seq samples and write the Bayes-factor table")
     ap.add_argument("--summary-file", default=None,
                     help="also write the summarize_miso table of this run (device-side summaries)")
+    ap.add_argument("--diagnostics-file", default=None,
+                    help="also write the chain diagnostics table of this run (split R-hat, ESS, MCSE; device-side)")
+    ap.add_argument("--diagnostics-files", nargs=2, default=None, metavar=("FILE1", "FILE2"),
+                    help="with --compare-genes-from-file: the chain diagnostics table of each sample")
     ap.add_argument("--no-miso-files", action="store_true",
                     help="with --summary-file: only the table, no per-event .miso files")
     ap.add_argument("--paired-end", nargs=2, type=float, metavar=("MEAN", "SD"))
@@ -424,6 +453,12 @@ def main(argv=None):
         return 1
     overhang_len = a.overhang_len if a.overhang_len is not None else 1
     paired_end = tuple(a.paired_end) if a.paired_end else None
+    if a.diagnostics_file and not a.compute_genes_from_file:
+        print("Error: --diagnostics-file goes with --compute-genes-from-file.")
+        return 1
+    if a.diagnostics_files and not a.compare_genes_from_file:
+        print("Error: --diagnostics-files goes with --compare-genes-from-file.")
+        return 1
     if a.compare_genes_from_file:
         genes_filename, bam1, bam2, out1, out2, bf = (os.path.abspath(os.path.expanduser(x))
                                                      for x in a.compare_genes_from_file)
@@ -431,7 +466,7 @@ def main(argv=None):
         n = compare_gene_psi(entries, bam1, bam2, out1, out2, bf, a.read_len, overhang_len,
                              paired_end=paired_end, event_type=a.event_type, seed=a.seed,
                              first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
-                             samples=samples)
+                             samples=samples, diagnostics_files=a.diagnostics_files)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -445,7 +480,8 @@ def main(argv=None):
                          paired_end=paired_end, event_type=a.event_type, gene_entries=entries,
                          seed=a.seed, first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
                          summary_file=a.summary_file,
-                         write_files=not (a.no_miso_files and a.summary_file))
+                         write_files=not (a.no_miso_files and a.summary_file),
+                         diagnostics_file=a.diagnostics_file)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")

@@ -3,6 +3,7 @@
 
     python -m miso_amd.samples_utils --summarize-samples SAMPLES_DIR OUTPUT_DIR
     python -m miso_amd.samples_utils --compare-samples SAMPLES_DIR1 SAMPLES_DIR2 OUTPUT_DIR
+    python -m miso_amd.samples_utils --diagnose-samples SAMPLES_DIR OUTPUT_DIR [--num-chains C]
     python -m miso_amd.samples_utils --compare-groups DIR[,DIR...] DIR[,DIR...] OUTPUT_DIR [--group-labels L[,L...] L[,L...]]
 
 The reference walks the samples directory (chromosome sub-directories of `<event>.miso`, or their packed form
@@ -26,6 +27,9 @@ byte-identical (tests/test_gpu_miso_text.py), and equal to the reference's on th
 tests/test_gpu_summary.py, tests/test_gpu_compare.py).  Out of scope as in the reference's own optional paths:
 compressed-ID maps (`--use-compressed`), zipped outputs (miso_zip).
 
+`--diagnose-samples` has no reference counterpart: the chain diagnostics (split R-hat, effective sample size, Monte-Carlo
+standard error; diagnostics.py) of the files' four-decimal values, through the same readers and decoders.
+
 `--compare-groups` is `--compare-samples` for biological replicates (what filter_events --votes reads): every pair of the
 two groups gets the file the pairwise call writes, byte for byte, but every tree is read once, every sample decoded and
 summarised once per chunk of events, and all pairs of a chunk come out of one launch (capi.compare_groups).
@@ -37,7 +41,8 @@ import time
 
 import numpy as np
 
-from . import capi, compare, miso_db, summary
+from . import capi, compare, diagnostics, miso_db, summary
+from .settings import Settings
 
 # The default decoder: `device`, because it is the faster one end to end (profiles/miso_text.txt: a tree of
 # 40 000 default-settings events, tools/miso_text_bench.py).  MISO_TEXT_DECODE overrides it, the functions' `decoder`
@@ -329,6 +334,85 @@ def summarize_sampler_results(samples_dir, summary_filename, confidence_level=0.
     rows.sort(key=lambda r: r[0])
     os.makedirs(os.path.dirname(os.path.abspath(summary_filename)), exist_ok=True)
     n = summary.write_summary(summary_filename, rows)
+    stats.stage("write")
+    stats.done()
+    return n
+
+
+def _diagnosable(S, num_chains, n_events):
+    if (S // num_chains) // 2 >= 4:
+        return True
+    print("Skipping %d events with only %d samples for %d chains" % (n_events, S, num_chains))
+    return False
+
+
+def _diagnose_rows(b, names, headers, Ks, S, num_chains, rows, status=None):
+    b.diagnose(num_chains)
+    diags = b.diagnostics_many(range(len(names)), Ks)
+    for i, (name, hdr) in enumerate(zip(names, headers)):
+        if status is not None and status[i]:
+            continue
+        warn = diagnostics.header_mismatch(name, hdr, S, num_chains)
+        if warn:
+            print(warn)
+        rows.append((name,) + tuple(diags[i]) + (S, num_chains))
+
+
+def _diagnose_parsed(events, num_chains, device, rows, stats):
+    """Diagnostics rows of host-parsed events (name, samples [S, K], header dict)."""
+    for S, group in sorted(_by_sample_count(events).items()):
+        if not _diagnosable(S, num_chains, len(group)):
+            continue
+        b = capi.SamplesBatch([g[1] for g in group], device=device)
+        stats.stage("decode")
+        _diagnose_rows(b, [g[0] for g in group], [g[2] for g in group], [g[1].shape[1] for g in group], S, num_chains, rows)
+        stats.stage("diagnose")
+
+
+def diagnose_sampler_results(samples_dir, diag_filename, num_chains=None, device=0, decoder=None):
+    """One diagnostics row per event of samples_dir (`.miso` files and `.miso_db` rows): what the files' four-decimal
+    values say about their chains.  num_chains: the chains the rows interleave (row s is chain s % num_chains), default
+    the settings' num_chains; an event whose header disagrees with its row count is named and diagnosed all the same."""
+    if num_chains is None:
+        num_chains = int(Settings.get_sampler_params()["num_chains"])
+    num_chains = int(num_chains)
+    if num_chains < 1:
+        raise ValueError("--num-chains must be at least 1")
+    decoder = _decoder(decoder)
+    stats = _Stats(decoder)
+    files, dbrows = list_events(samples_dir)
+    rows = []
+    if decoder == "host":
+        evs = _read_events([], dbrows)
+        stats.stage("read")
+        events = _load_all(files + evs)
+        stats.stage("parse")
+        _diagnose_parsed(events, num_chains, device, rows, stats)
+    else:
+        evs = _read_events(files, dbrows)
+        stats.stage("read")
+        _shape(evs)
+        stats.stage("shape")
+        left = [e for e in evs if not _device_ok(e)]
+        groups = {}
+        for e in evs:
+            if _device_ok(e):
+                groups.setdefault(e.S, []).append(e)
+        for S, group in sorted(groups.items()):
+            if not _diagnosable(S, num_chains, len(group)):
+                continue
+            for run in _text_batches(group, lambda e: len(e.body)):
+                b = _text_batch(run, S, device, stats)
+                stats.stage("decode")
+                _diagnose_rows(b, [e.name for e in run], [_header_fields(e.header) for e in run], [e.K for e in run], S,
+                               num_chains, rows, status=b.status)
+                left += [e for i, e in enumerate(run) if b.status[i]]
+                stats.stage("diagnose")
+        stats.d["fallback_events"] += [e.name for e in left if e.name not in stats.d["fallback_events"]]
+        _diagnose_parsed(_load_all(left), num_chains, device, rows, stats)
+    rows.sort(key=lambda r: r[0])
+    os.makedirs(os.path.dirname(os.path.abspath(diag_filename)), exist_ok=True)
+    n = diagnostics.write_diagnostics(diag_filename, rows)
     stats.stage("write")
     stats.done()
     return n
@@ -687,6 +771,10 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="summarize_miso / compare_miso over directories of .miso files")
     ap.add_argument("--summarize-samples", nargs=2, metavar=("SAMPLES_DIR", "OUTPUT_DIR"))
     ap.add_argument("--compare-samples", nargs=3, metavar=("SAMPLES_DIR1", "SAMPLES_DIR2", "OUTPUT_DIR"))
+    ap.add_argument("--diagnose-samples", nargs=2, metavar=("SAMPLES_DIR", "OUTPUT_DIR"),
+                    help="chain diagnostics (split R-hat, ESS, MCSE) of every event: OUTPUT_DIR/summary/<name>.miso_diag")
+    ap.add_argument("--num-chains", type=int, default=None,
+                    help="with --diagnose-samples: chains the sample rows interleave (default: the settings' num_chains, 6)")
     ap.add_argument("--comparison-labels", nargs=2, default=None)
     ap.add_argument("--compare-groups", nargs=3, metavar=("DIR[,DIR...]", "DIR[,DIR...]", "OUTPUT_DIR"),
                     help="every pair of two groups of sample directories (replicates), one .miso_bf per pair")
@@ -699,6 +787,14 @@ def main(argv=None):
         fname = os.path.join(out_dir, "summary", label + ".miso_summary")
         n = summarize_sampler_results(samples_dir, fname, device=a.device)
         print("Summarized %d events into %s" % (n, fname))
+    if a.diagnose_samples:
+        samples_dir, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.diagnose_samples)
+        label = os.path.basename(os.path.normpath(samples_dir))
+        fname = os.path.join(out_dir, "summary", label + ".miso_diag")
+        n = diagnose_sampler_results(samples_dir, fname, num_chains=a.num_chains, device=a.device)
+        print("Diagnosed %d events into %s" % (n, fname))
+    elif a.num_chains is not None:
+        ap.error("--num-chains goes with --diagnose-samples")
     if a.compare_samples:
         d1, d2, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.compare_samples)
         out, n = output_samples_comparison(d1, d2, out_dir, sample_labels=a.comparison_labels, device=a.device)
@@ -712,7 +808,7 @@ def main(argv=None):
             print("Compared %d events into %s" % (n, out))
     elif a.group_labels:
         ap.error("--group-labels goes with --compare-groups")
-    if not a.summarize_samples and not a.compare_samples and not a.compare_groups:
+    if not a.summarize_samples and not a.compare_samples and not a.compare_groups and not a.diagnose_samples:
         ap.print_help()
     return 0
 
