@@ -150,6 +150,10 @@ typedef struct miso_params {
                                 0: on the host, at miso_batch_add_event */
 } miso_params_t;
 
+/* Paired-end: the fragment-length distribution (the lengths max(readLength, normalMean - numDevs * sd) ..
+   normalMean + numDevs * sd, sd = sqrt(normalVar), both truncated to integers) may hold at most 65535 lengths: a
+   pair's fragment length is kept as a 16-bit index into it and 0xFFFF stands for "none".  A wider one is
+   MISO_UNIMPLEMENTED. */
 int miso_batch_create(const miso_params_t *params, miso_batch_t **batch);
 void miso_batch_destroy(miso_batch_t *batch);
 

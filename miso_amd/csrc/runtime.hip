@@ -2374,7 +2374,13 @@ miso_batch *batch_new(const miso_params_t &p) {
   validate_params(p);
   auto b = std::make_unique<miso_batch>();
   b->p = p;
-  if (p.paired) b->fd = normal_fragment(p.normalMean, p.normalVar, p.numDevs, p.readLength);
+  if (p.paired) {
+    b->fd = normal_fragment(p.normalMean, p.normalVar, p.numDevs, p.readLength);
+    // a fragment length is kept as a uint16_t index into fd.prob, FRAG_NONE = none (host.cpp pack_event, match_kernel):
+    // every index has to stay below it
+    if (b->fd.prob.size() > FRAG_NONE)
+      MISO_FAIL(MISO_UNIMPLEMENTED, "Fragment-length distribution wider than 65535 lengths");
+  }
   return b.release();
 }
 

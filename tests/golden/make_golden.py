@@ -248,6 +248,68 @@ def atp2b1_case(R):
          chains=2, pos=pos, cigars=np.array(cig), **pack_result(r))
 
 
+def match_adversarial(R):
+    """tests/_match_cases.py through splicing_matchIso / splicing_matchIso_paired: OUTPUTS only (the inputs are
+    regenerated from the seed and pinned by their SHA-256).  match/adversarial.npz: a subdirectory, because
+    _golden.names() opens every *.npz next to this file.  Match matrices [N, K] bit-packed along K, fragment lengths
+    [pairs, K] as int16.  "shifted" is not stored, it must equal "tangled"; of a wide gene the tangled isoforms' columns
+    must equal "tangled" too, and what is stored is the rest: (read, isoform) of every filler entry that is set, with its
+    fragment length (_match_cases.Golden puts the matrix together again)."""
+    import _match_cases as mc
+    out = {}
+
+    def filler_part(name, m, base, fl=None):
+        K = m.shape[1]
+        slots = mc.tangled_slots(K)
+        assert np.array_equal((fl if fl is not None else m)[:, slots], base)
+        rest = np.setdiff1d(np.arange(K), slots)
+        sub = np.zeros_like(m, dtype=bool)
+        sub[:, rest] = m[:, rest] != 0
+        idx = np.argwhere(sub).astype(np.int32)
+        return idx, (None if fl is None else fl[sub].astype(np.int16))
+
+    pos, cig, _ = mc.single_reads()
+    for ov in mc.OVERHANGS:
+        for rl in mc.READ_LENS:
+            base = None
+            for name in mc.gene_names(False):
+                exons, isoforms = mc.gene(name)
+                p = pos + (mc.SHIFT if name == "shifted" else 0)
+                rc, m = R.match_iso(R.gene(flat(exons), isoforms), p, cig, rl, overhang=ov)
+                assert rc == 0 and np.isin(m, (0.0, 1.0)).all()
+                if name == "tangled":
+                    base = m
+                    assert np.array_equal(m, mc.model_match(exons, isoforms, pos, cig, rl, ov))
+                if name == "shifted":
+                    assert np.array_equal(m, base)
+                elif name == "tangled":
+                    out[mc.se_key(name, ov, rl)] = np.packbits(m.astype(np.uint8), axis=1)
+                else:
+                    out[mc.se_key(name, ov, rl) + "_filler"], _ = filler_part(name, m, base)
+    for mean, var in mc.MEAN_VARS:
+        for rl in mc.READ_LENS:
+            pos, cig, _ = mc.paired_reads(mean, var, rl)
+            for ov in mc.OVERHANGS:
+                base = None
+                for name in mc.gene_names(True):
+                    exons, isoforms = mc.gene(name)
+                    p = pos + (mc.SHIFT if name == "shifted" else 0)
+                    rc, m, fl = R.match_iso_paired(R.gene(flat(exons), isoforms), p, cig, rl, mean, var, overhang=ov)
+                    assert rc == 0 and np.array_equal(m != 0, fl >= 0) and fl.max() < 32768
+                    if name == "tangled":
+                        base = fl
+                    key = mc.pe_key(name, ov, rl, mean, var)
+                    if name == "shifted":
+                        assert np.array_equal(fl, base)
+                    elif name == "tangled":
+                        out[key + "_match"] = np.packbits((m != 0).astype(np.uint8), axis=1)
+                        out[key + "_fraglen"] = fl.astype(np.int16)
+                    else:
+                        out[key + "_filler"], out[key + "_filler_len"] = filler_part(name, m, base, fl)
+    os.makedirs(os.path.join(HERE, "match"), exist_ok=True)
+    save(os.path.join("match", "adversarial"), kind="match_adversarial", digest=mc.inputs_digest(), **out)
+
+
 def main():
     if not RefLib.available():
         sys.exit("oracle/_ref/libmiso_ref.so missing: run `make -C oracle ref` first")
@@ -256,6 +318,9 @@ def main():
     saved = os.dup(1)
     os.dup2(devnull, 1)  # the reference prints "no chains: %d" (miso.c:837)
     try:
+        if sys.argv[1:] == ["match"]:        # only tests/golden/match/adversarial.npz (the others are unchanged)
+            match_adversarial(R)
+            return
         if sys.argv[1:] == ["assignment"]:   # likewise
             assignment_matrix_case(R)
             return
@@ -289,6 +354,7 @@ def main():
         marginal_cases(R)
         assignment_matrix_case(R)
         as_cases(R)
+        match_adversarial(R)
     finally:
         os.dup2(saved, 1)
     print("done")

@@ -63,8 +63,8 @@ def test_device_match_batch_equals_host_path(paired, orc):
     for K, n, sd in specs:
         exons, isoforms = se_gene(K, exlen=500, gap=300) if paired else se_gene(K)
         G = capi.Gene(exons, isoforms)
-        keep.append(G)
         _, pos, cig = capi.simulate_reads(G, expr_for(K), n, 36, sd, 250.0 if paired else 0.0, 900.0 if paired else 0.0)
+        keep.append((G, pos, cig))
         assert dev.add_event(G, pos, cig) == host.add_event(G, pos, cig)
         og = orc.gene(flat(exons), isoforms)
         if not paired and n:
@@ -72,7 +72,12 @@ def test_device_match_batch_equals_host_path(paired, orc):
     dev.run(seed=5); host.run(seed=5)
     for i, (K, n, sd) in enumerate(specs):
         m, fl = dev.device_match_of(i)
-        G = keep[i]
+        G, pos, cig = keep[i]
+        if paired:
+            hm, hfl = G.match_iso_paired(pos, cig, 36, 250.0, 900.0)
+            assert np.array_equal(m, hm) and np.array_equal(fl, hfl)
+        else:
+            assert fl is None and np.array_equal(m, G.match_iso(pos, cig, 36))
         a, b = dev.result(i, trace=True), host.result(i, trace=True)
         assert np.array_equal(a.samples, b.samples) and np.array_equal(a.loglik, b.loglik)
         assert np.array_equal(a.assignment, b.assignment) and np.array_equal(a.counts_hash, b.counts_hash)
