@@ -204,6 +204,31 @@ int miso_batch_set_event_id(miso_batch_t *batch, int event_index, uint32_t event
    ~1000 reads spread over the classes of a five- or ten-isoform event it is slower than the per-read sweep
    (profiles/r03_collapsed.txt).  Before miso_batch_launch; MISO_EINVAL for paired-end. */
 int miso_batch_set_collapsed(miso_batch_t *batch, int on);
+/* Single-end batches, algorithm = MISO_ALGO_REASSIGN: on != 0 selects the EXACT-POSTERIOR mode for the eligible
+   two-isoform events (csrc/kernels_exact.hip).  With x = psi_0 the reference's joint score summed
+   over the reads' assignments is a density of one variable,
+       log p(x) = (n10 + h0 - 1) log x + (n01 + h1 - 1) log(1 - x) - n log(x e0 + (1 - x) e1) + const
+   (n10 / n01 reads compatible with isoform 0 / 1 only, n all reads with a compatible isoform, e the effective lengths,
+   h the Dirichlet hyperparameters).  An eligible event -- two isoforms, both effective lengths > 0, both
+   hyperparameters >= 1 (miso_exact_eligible) -- runs no chain: the density is tabulated once on a grid in logit space
+   and the event's noSamples rows are INDEPENDENT draws from it, row s by inverting the CDF at the uniform of
+   (seed, event id, sample s, MISO_SITE_EXACT).  What such an event returns: samples as ever (row order = sample
+   index); logLik[s] = the MARGINAL score log p at the sample with the Dirichlet normaliser, not a joint score with an
+   assignment; assignment = one per-read reassignment from the last sample's psi, drawn as algorithm = MARGINAL draws
+   its one (Gibbs words of chain 0, MISO_ITER_INIT); rundata accepted = noSamples, rejected = 0; under stop =
+   CONVERGENT_MEAN it is done after the first round.  Every other event of the batch runs through the sampler kernels,
+   bit-identical to the same event in a batch without the mode.  May be combined with miso_batch_set_collapsed: exact
+   takes the eligible events, collapsed the rest it would have taken.  Before miso_batch_launch; MISO_EINVAL for
+   paired-end batches and for algorithm != MISO_ALGO_REASSIGN. */
+int miso_batch_set_exact(miso_batch_t *batch, int on);
+/* the eligibility rule on its own (host arithmetic, no device): eff_len / hyper: noiso doubles each */
+int miso_exact_eligible(int paired, int noiso, const double *eff_len, const double *hyper, int *eligible);
+/* After miso_batch_sync: posterior mean and the quantiles (1 - confidence_level) / 2 and 1 - (1 - confidence_level) / 2
+   of an event the exact mode took, from the grid itself: no Monte-Carlo error.  mean / ci_low / ci_high: two doubles
+   each (isoform 0, isoform 1; isoform 1's from 1 - x computed on its own, so a value near 0 keeps its relative
+   precision).  *was_exact = 0 and the outputs untouched for an event that ran the sampler. */
+int miso_batch_get_exact_summary(miso_batch_t *batch, int event_index, double *mean, double *ci_low, double *ci_high,
+                                 double confidence_level, int *was_exact);
 int miso_batch_upload(miso_batch_t *batch, int device);
 /* enqueue the sampler kernels for every event on the batch's stream; returns immediately */
 int miso_batch_launch(miso_batch_t *batch, uint64_t seed, uint32_t first_event_id);
@@ -478,6 +503,11 @@ int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const doub
 /* kernels_k2.inl binomial_coop<G>, G = 1, 2, 4, 8 lanes per chain: `count` draws of Binomial(n, p) from the word streams
    (seed, event_id, chain 0, iteration i, MISO_SITE_COUNTS), i = 0 .. count - 1 */
 int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
+/* kernels_exact.hip, the posterior stage alone, one wavefront per element: stats7[7 i ...] = {n10, n01, n, e0, e1, h0, h1}
+   (n = all reads with a compatible isoform).  out8[8 i ...] = {mean of x, mean of 1 - x, window low, window high (logit
+   space), the normalising sum F[G], the mode (logit space), the grid step, the log density at the mode as tabulated};
+   icdf[(i n_prob + j) 2 ...] = {x, 1 - x} at the inverse CDF of prob[j] (0 < prob < 1). */
+int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf);
 /* csrc/text_digits.hpp text_digits, the rounding of summarize_as_text: out[i] = x[i] x 10^4 rounded to the nearest integer,
    ties to even, on the exact product -- the digits of "%.4f" of x[i], sign included.  Finite |x[i]| < 2^38. */
 int miso_selftest_text_digits(const double *x, int n, int64_t *out);

@@ -22,6 +22,9 @@
  *                           half-word r (block r/8, half r%8; half h = bits 16 (h & 1) .. + 15 of word h / 2)
  *                           is the HIGH half of the read's 32-bit uniform and the same half-word of site
  *   site MISO_SITE_GIBBS_LOW (4)  its LOW half
+ *   site MISO_SITE_EXACT (5): the exact-posterior mode of single-end two-isoform events (miso_batch_set_exact,
+ *                           csrc/kernels_exact.hip) -- no chain, no iteration: ctr = (sample index s, 0, site, event_id),
+ *                           word 0 of that block = the uniform that sample s inverts the posterior's CDF at
  *   iteration = m for the main loop (miso.c:847), MISO_ITER_INIT for the set-up draws
  *   (initial proposal miso.c:834 and initial assignment miso.c:841).
  *
@@ -66,6 +69,7 @@
 #define MISO_SITE_MH    0u
 #define MISO_SITE_GIBBS 2u
 #define MISO_SITE_GIBBS_LOW 4u   /* (3 = MISO_SITE_COUNTS, miso_binomial.h) */
+#define MISO_SITE_EXACT 5u       /* exact-posterior mode: one word per sample (header comment); no existing draw moves */
 #define MISO_ITER_INIT  0xFFFFFFFFu
 
 #define MISO_PHILOX_M0 0xD2511F53u

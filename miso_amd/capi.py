@@ -198,9 +198,11 @@ class Batch:
     def __init__(self, read_len, iters=5000, burn=500, lag=10, chains=6, overhang=1, paired=False,
                  mean=0.0, var=0.0, num_devs=4.0, start=MISO_START_AUTO, stop=MISO_STOP_FIXEDNO,
                  algo=MISO_ALGO_REASSIGN, max_iters=100000, counts_trace=False, device_match=False,
-                 collapsed=False):
+                 collapsed=False, exact=False):
         """collapsed (single-end): the two-isoform events draw their assignment COUNTS directly (one exact binomial
-        per iteration instead of one uniform per read; miso_batch_set_collapsed in include/miso_amd.h)."""
+        per iteration instead of one uniform per read; miso_batch_set_collapsed in include/miso_amd.h).
+        exact (single-end, algo = REASSIGN): the eligible two-isoform events run no chain, their samples are independent
+        draws from the posterior of psi itself, tabulated once per event (miso_batch_set_exact in include/miso_amd.h)."""
         self.params = Params(int(paired), read_len, overhang, chains, iters, max_iters, burn, lag,
                              algo, start, stop, mean, var, num_devs, int(counts_trace),
                              int(device_match))
@@ -209,6 +211,9 @@ class Batch:
         self.collapsed = int(collapsed)     # True / 1: two-isoform events; 2: events of any isoform count
         if collapsed:
             check(lib().miso_batch_set_collapsed(self.handle, int(collapsed)))
+        self.exact = bool(exact)
+        if exact:
+            check(lib().miso_batch_set_exact(self.handle, 1))
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -286,6 +291,15 @@ class Batch:
         m, lo, hi = (np.zeros(K.value) for _ in range(3))
         check(lib().miso_batch_get_summary(self.handle, i, _p(m), _p(lo), _p(hi)))
         return m, lo, hi
+
+    def exact_summary(self, i, confidence_level=0.95):
+        """(mean[2], ci_low[2], ci_high[2]) of event i from the exact mode's grid -- no Monte-Carlo error -- after sync();
+        None for an event that ran the sampler (miso_batch_get_exact_summary)."""
+        m, lo, hi = (np.zeros(2) for _ in range(3))
+        was = C.c_int(0)
+        check(lib().miso_batch_get_exact_summary(self.handle, int(i), _p(m), _p(lo), _p(hi), C.c_double(confidence_level),
+                                                 C.byref(was)))
+        return (m, lo, hi) if was.value else None
 
     def summaries(self, indices, noiso):
         """[(mean[K], ci_low[K], ci_high[K])] of the given events after summarize() -- summary() for many events without its
@@ -775,6 +789,18 @@ def selftest_binomial(G, n, p, count, seed=1, event_id=0):
     check(lib().miso_selftest_binomial(int(G), C.c_uint64(seed), C.c_uint32(event_id), C.c_int32(n), C.c_double(p),
                                        int(count), _p(out)))
     return out
+
+
+def selftest_exact(stats7, probs):
+    """csrc/kernels_exact.hip, the posterior stage alone: stats7[i] = (n10, n01, n, e0, e1, h0, h1) -> (out8 [n, 8] = mean of x,
+    mean of 1 - x, window low / high, normalising sum, mode, grid step, log density at the mode; icdf [n, len(probs), 2] =
+    (x, 1 - x) at the inverse CDF of every probability) -- include/miso_amd.h miso_selftest_exact"""
+    st = np.ascontiguousarray(stats7, dtype=np.float64).reshape(-1, 7)
+    pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    out8 = np.zeros((len(st), 8))
+    icdf = np.zeros((len(st), len(pr), 2))
+    check(lib().miso_selftest_exact(_p(st), len(st), _p(pr), len(pr), _p(out8), _p(icdf)))
+    return out8, icdf
 
 
 def selftest_text_digits(x):

@@ -28,6 +28,12 @@ void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double 
                       const uint32_t *word, int n, int32_t *out);
 void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
 void selftest_text_digits(const double *x, int n, int64_t *out);
+// kernels_exact.hip: the exact-posterior mode's posterior stage on its own (miso_selftest_exact, exact summaries)
+void exact_probe_run(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st = nullptr);
+// the exact-posterior mode takes such an event (include/miso_amd.h miso_exact_eligible)
+inline bool exact_eligible(bool paired, int K, const double *eff, const double *hyper) {
+  return !paired && K == 2 && eff[0] > 0 && eff[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1;
+}
 // kernels_compare_groups.hip
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
@@ -119,6 +125,18 @@ struct miso_batch {
   miso::DevTable<double> logfact; // collapsed: log factorials up to the largest event's drawing reads
   int collapsed_level = 0;        // 1: two-isoform events; 2: also the events with more isoforms (sampler_lane_k)
   bool collapsed = false;         // single-end two-isoform events: the collapsed Gibbs step (kernels_lane.hip); miso_batch_set_collapsed
+  // the exact-posterior mode (miso_batch_set_exact; kernels_exact.hip): its events leave the sampler's lists
+  bool exact = false;
+  bool slots_exact = false;       // the mode the launch lists were last built for (build_slots)
+  std::vector<char> is_exact;     // per event: the exact kernel takes it
+  int n_exact = 0;                // ... their number: the launch lists are [two-isoform | other | exact]
+  miso::DevTable<double> exact_eff;   // e0, e1 of every event of the exact list
+  std::vector<double> exact_sums; // exact_summaries(): per event of the exact list {mean, ci_low, ci_high} x 2 isoforms
+  double exact_sums_level = -1.0; // ... the confidence level they were made for
+  bool event_exact(int i) const { return i >= 0 && i < static_cast<int>(is_exact.size()) && is_exact[i] != 0; }
+  void build_slots();
+  void launch_exact(const miso::KernelArgs &a);
+  void exact_summaries(double confidence_level);
   miso::LanePlan k2_plan;         // sampler_k2_multi: the runs of equal lanes per chain (runtime.hip), valid for k2_plan_key
   long k2_plan_key = -1;
   miso::CoopTable k2_coop_se, k2w_coop;   // the two plans' chains on several workgroups (key: the plan's wide run)
@@ -227,7 +245,7 @@ struct miso_batch {
   int k2_first_event() const {  // the k2 event with the most drawing reads (list is sorted)
     int best = -1;
     for (size_t i = 0; i < events.size(); i++)
-      if (events[i].K == 2 && !k2_general && (best < 0 || events[i].n_draw > events[best].n_draw))
+      if (events[i].K == 2 && !k2_general && !event_exact(static_cast<int>(i)) && (best < 0 || events[i].n_draw > events[best].n_draw))
         best = static_cast<int>(i);
     return best;
   }
@@ -282,7 +300,7 @@ struct miso_batch {
   void launch_grp_multi(const miso::KernelArgs &a, size_t r0, size_t r1);
   template <class F> void each_coop_table(F &&f) { for (GenRun &r : gen_runs) f(r.coop); f(k2_coop_se); f(k2w_coop); }
   template <class F> void each_table(F &&f) {   // every device table above (release())
-    f(grp_segs); f(round_tab); f(logfact); f(k2_pair_tab);
+    f(grp_segs); f(round_tab); f(logfact); f(k2_pair_tab); f(exact_eff);
     for (GenRun &r : gen_runs) f(r.wave_tab);
     each_coop_table(f);
   }

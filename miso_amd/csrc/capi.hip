@@ -404,6 +404,7 @@ int miso_batch_get_result(const miso_batch_t *b, int i, double *samples, double 
       for (int c = 0; c < b->p.noChains; c++) acc += st[c].accepted;
       // (stop = CONVERGENT_MEAN: the counts of the last round, paired-end of all rounds -- batch.hpp iters_counted)
       fill_rundata(*b, e.K, acc, b->iters_counted.empty() ? b->p.noIterations : b->iters_counted[i], rundata);
+      if (b->event_exact(i)) rundata->noRejected = 0;   // the exact mode: noSamples independent draws, none rejected
     }
   });
 }
@@ -680,6 +681,7 @@ int miso_batch_header_fields(const miso_batch_t *b, int n, const int *event_inde
           for (int c = 0; c < b->p.noChains; c++) acc += st[c].accepted;
           miso_rundata_t rd;
           fill_rundata(*b, e.K, static_cast<int>(acc), b->iters_counted.empty() ? b->p.noIterations : b->iters_counted[i], &rd);
+          if (b->event_exact(i)) rd.noRejected = 0;
           const double pa = static_cast<double>(rd.noAccepted) / static_cast<double>(rd.noAccepted + rd.noRejected) * 100.0;
           std::snprintf(num, sizeof num, "%.2f", pa);
           ln += num; ln += '\t';
@@ -951,6 +953,44 @@ int miso_batch_set_collapsed(miso_batch_t *b, int on) {
   });
 }
 
+int miso_batch_set_exact(miso_batch_t *b, int on) {
+  return guarded([&] {
+    need(b, "batch");
+    if (on && b->p.paired) MISO_FAIL(MISO_EINVAL, "the exact-posterior mode takes single-end events only");
+    if (on && b->p.algorithm != MISO_ALGO_REASSIGN) MISO_FAIL(MISO_EINVAL, "the exact-posterior mode is the posterior of algorithm = REASSIGN only");
+    b->exact = on != 0;   // (the launch lists follow at the upload, or at the next launch: runtime.hip build_slots)
+  });
+}
+
+int miso_exact_eligible(int paired, int noiso, const double *eff_len, const double *hyper, int *eligible) {
+  return guarded([&] {
+    need(eff_len, "eff_len"); need(hyper, "hyper"); need(eligible, "eligible");
+    *eligible = (noiso == 2 && exact_eligible(paired != 0, noiso, eff_len, hyper)) ? 1 : 0;
+  });
+}
+
+int miso_batch_get_exact_summary(miso_batch_t *b, int i, double *mean, double *ci_low, double *ci_high, double confidence_level,
+                                 int *was_exact) {
+  return guarded([&] {
+    need(b, "batch"); need(was_exact, "was_exact");
+    (void) event_at(b, i);
+    if (!b->launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+    *was_exact = b->event_exact(i) ? 1 : 0;
+    if (!*was_exact) return;
+    b->exact_summaries(confidence_level);
+    int j = 0;   // the event's place in the exact list
+    const int first = b->n_k2 + b->n_gen;
+    while (j < b->n_exact && b->h_slots[first + j] != i) j++;
+    if (j >= b->n_exact) MISO_FAIL(MISO_EINTERNAL, "an exact event is missing from its launch list");
+    const double *r = &b->exact_sums[static_cast<size_t>(j) * 6];
+    for (int k = 0; k < 2; k++) {
+      if (mean) mean[k] = r[k];
+      if (ci_low) ci_low[k] = r[2 + k];
+      if (ci_high) ci_high[k] = r[4 + k];
+    }
+  });
+}
+
 int miso_batch_get_placement(const miso_batch_t *b, int i, uint32_t *hw_id) {
   return guarded([&] {
     need(b, "batch"); need(hw_id, "hw_id");
@@ -1050,6 +1090,13 @@ int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const doub
 }
 int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out) {
   return guarded([&] { selftest_binomial(G, seed, event_id, n, p, count, out); });
+}
+int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf) {
+  return guarded([&] {
+    if (n > 0) need(stats7, "stats7");
+    if (n_prob > 0) need(prob, "prob");
+    exact_probe_run(stats7, n, prob, n_prob, out8, icdf);
+  });
 }
 int miso_selftest_text_digits(const double *x, int n, int64_t *out) {
   return guarded([&] { selftest_text_digits(x, n, out); });

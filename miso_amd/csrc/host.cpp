@@ -432,6 +432,7 @@ PackedEvent pack_event_masks(const miso_params_t &p, const FragmentDist *fd, int
       const int l = isolen[k] - p.readLength + 1 - 2 * (noexons[k] - 1) * (ov - 1);
       const int eff = l > 0 ? l : 0;
       e.consts[k] = std::log(static_cast<double>(eff));
+      e.eff.push_back(static_cast<double>(eff));
       e.consts[K + k] = -std::log(static_cast<double>(l));
       // miso.c:800-808: the marginal algorithm's match matrix is divided by the effective length where that is not 0
       if (marginal && eff != 0) invlen[k] = 1.0 / eff;

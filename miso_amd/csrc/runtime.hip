@@ -34,6 +34,7 @@ __global__ void sampler_lane_ilp(const KernelArgs a);   // ... the form for at m
 template <int G> __global__ void sampler_k2c(const KernelArgs a);   // ... G lanes per chain (k2_body COLLAPSED)
 __global__ void sampler_lane_k(const KernelArgs a); // ... three and more isoforms (vectors in LDS)
 __global__ void sampler_marginal(const KernelArgs a); // kernels_marginal.hip: algorithm = MARGINAL, one chain per lane
+__global__ void exact_sample(const KernelArgs a, const double *eff, int S);   // kernels_exact.hip: the exact-posterior mode, one wavefront per event
 constexpr int LANEK_VECTORS = 9;
 inline size_t lanek_lds_bytes(int ks) { return static_cast<size_t>(LANEK_VECTORS) * ks * 64 * 8 + static_cast<size_t>(ks) * 64 * 4; }
 __global__ void compare_kernel(const DevEvent *, const unsigned char *, const DevEvent *, const unsigned char *, int, int,
@@ -297,6 +298,8 @@ void miso_batch::resolve_pending() {
                  secs(T0, T1), match_ms, secs(T1, T2), nthreads, secs(T2, now()));
 }
 
+template <class T> static void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n = 1);
+
 void miso_batch::upload(int dev) {
   if (uploaded && dev == device) return;
   if (uploaded) release();
@@ -421,14 +424,38 @@ void miso_batch::upload(int dev) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(d_in, h_in.data(), in_bytes, hipMemcpyHostToDevice));
+  build_slots();
+  if (p.paired) {
+    HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_fp), fd.prob.size() * 8));
+    HIP_OK(hipMemcpy(d_fp, fd.prob.data(), fd.prob.size() * 8, hipMemcpyHostToDevice));
+  }
+  uploaded = true;
+  pool_cleared = false; launched_once = false;
+}
+
+// The launch lists of the uploaded events: [two-isoform events | the other events by class | the exact mode's events].
+// Made by upload(), and again by launch() when miso_batch_set_exact was called in between.
+void miso_batch::build_slots() {
+  const int n = static_cast<int>(events.size());
   // launch lists: two-isoform events (single- or paired-end) go to sampler_k2, ordered by their
   // number of drawing reads so the chains sharing a wavefront loop equally long
   // (paired-end with a fragment-length distribution so wide that one chain's tables do not fit a CU's LDS -- sd beyond
   // ~400 -- : the two-isoform events take the general kernel, whose tables may stay in global memory, like the
   // reference, which takes any sd, miso_paired.c:299-308; MISO_K2_GENERAL=1 forces it: tests)
   k2_general = p.paired && (48 * fd.prob.size() + 64 > 150 * 1024 || std::getenv("MISO_K2_GENERAL") != nullptr);
-  std::vector<int32_t> k2, gen;
-  for (int i = 0; i < n; i++) ((events[i].K == 2 && !k2_general) ? k2 : gen).push_back(i);
+  // (the exact-posterior mode, miso_batch_set_exact: its eligible events leave both lists for one of their own)
+  std::vector<int32_t> k2, gen, ex;
+  is_exact.assign(n, 0);
+  if (exact && !p.paired && p.algorithm == MISO_ALGO_REASSIGN)
+    for (int i = 0; i < n; i++) {
+      if (events[i].K != 2) continue;
+      // (every single-end event is packed with its effective lengths, host.cpp pack_event_masks: one without them came
+      // by a route that forgot them, and must not fall back to the sampler in silence)
+      if (events[i].eff.size() != 2 || events[i].hyper.size() != 2)
+        MISO_FAIL(MISO_EINTERNAL, "exact-posterior mode: a two-isoform event was packed without its effective lengths");
+      is_exact[i] = exact_eligible(false, 2, events[i].eff.data(), events[i].hyper.data());
+    }
+  for (int i = 0; i < n; i++) (is_exact[i] ? ex : (events[i].K == 2 && !k2_general) ? k2 : gen).push_back(i);
   // (paired-end: the events sampler_k2's MODE 2 can take come first, MISO_NO_PE_DELTA=1 sends all to MODE 1)
   use_delta = std::getenv("MISO_NO_PE_DELTA") == nullptr;   // fixed here: the slot order depends on it
   // (Round 5 tried ordering a collapsed batch's list by the binomial's likely regime -- inversion below n min(p, q) = 10, BTRS
@@ -521,16 +548,16 @@ void miso_batch::upload(int dev) {
     if (!e.paired || e.draw_dense.empty() || e.K == 2) r.dense = false;   // (K = 2: draw_dense holds sampler_k2's records)
   }
   n_k2 = static_cast<int>(k2.size()); n_gen = static_cast<int>(gen.size());
+  n_exact = static_cast<int>(ex.size());
   k2.insert(k2.end(), gen.begin(), gen.end());
+  k2.insert(k2.end(), ex.begin(), ex.end());
   h_slots = k2;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_slots), std::max<size_t>(n, 1) * sizeof(int32_t)));
+  std::vector<double> eff2;
+  for (int i : ex) { eff2.push_back(events[i].eff[0]); eff2.push_back(events[i].eff[1]); }
+  put(exact_eff, eff2);
+  slots_exact = exact; exact_sums.clear(); exact_sums_level = -1.0;
+  if (!d_slots) HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_slots), std::max<size_t>(n, 1) * sizeof(int32_t)));
   if (n) HIP_OK(hipMemcpy(d_slots, k2.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (p.paired) {
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_fp), fd.prob.size() * 8));
-    HIP_OK(hipMemcpy(d_fp, fd.prob.data(), fd.prob.size() * 8, hipMemcpyHostToDevice));
-  }
-  uploaded = true;
-  pool_cleared = false; launched_once = false;
 }
 
 // ---- the sampler kernels' host stubs, picked by their template arguments ----
@@ -643,7 +670,7 @@ static void launch_kernel(const void *f, unsigned grid, unsigned block, size_t l
 }
 
 // `t` holds `v` from now on, in an allocation of at least `min_n` elements; copied only when it holds something else
-template <class T> static void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n = 1) {
+template <class T> static void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n) {
   const size_t n = std::max(v.size(), min_n);
   if (t.d && n <= t.cap && v.size() == t.host.size() && (v.empty() || std::memcmp(v.data(), t.host.data(), v.size() * sizeof(T)) == 0)) return;
   if (!t.d || n > t.cap) {
@@ -686,6 +713,11 @@ std::string miso_batch::run_name(size_t ri) const {   // the kernel general run 
 void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   if (!uploaded) MISO_FAIL(MISO_EINVAL, "batch not uploaded");
   HIP_OK(hipSetDevice(device));
+  if (slots_exact != exact) {   // miso_batch_set_exact after the upload: the launch lists anew
+    HIP_OK(hipStreamSynchronize(stream));
+    for (GenRun &r : gen_runs) { r.wave_tab.reset(); r.coop.reset(); }
+    build_slots();
+  }
   const int n = static_cast<int>(events.size());
   KernelArgs a{};
   a.events = d_events; a.in_pool = d_in; a.out_pool = d_out; a.frag_prob = d_fp;
@@ -742,6 +774,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
     last_kernels = "sampler_marginal";
   } else {
     launch_planned(a);
+    if (n_exact > 0) launch_exact(a);
   }
   // kernel i > 0 went to its own stream, forked from the batch's stream: joined back into it
   for (size_t i = 1; i < kernel_no && i <= aux_streams.size() && std::getenv("MISO_SERIAL_KERNELS") == nullptr; i++) {
@@ -777,7 +810,7 @@ void miso_batch::plan_sizes() {
   // fill, so the lanes-per-chain rule sees `wave_slots x share` (one after the other, each class of
   // a whole-gene batch -- a few thousand chains -- would be spread thin over 32 lanes per chain and
   // still leave the GPU half empty).
-  q.total_chains = static_cast<long>(events.size()) * p.noChains;
+  q.total_chains = static_cast<long>(n_k2 + n_gen) * p.noChains;   // (the exact mode's events are not the samplers')
   q.n_kernels = (n_k2 - n_k2w > 0 ? 1 : 0) + (n_k2w > 0 ? 1 : 0) + gen_runs.size();
   // Lanes per chain, measured: the best split depends on how the batch's wavefronts fill the SIMDs
   // (chains, isoforms, reads, LDS per workgroup), so the first launch of a large single-end batch
@@ -1768,6 +1801,47 @@ void miso_batch::launch_planned(const KernelArgs &a) {
   for (size_t ri = 0; ri < gen_runs.size(); ri++) if (!gen_runs[ri].wide && !q.runs[ri].lane && !q.runs[ri].group) launch_run(a, ri);
 }
 
+// The exact-posterior mode's events (kernels_exact.hip): one wavefront each, no chains; the launch's last kernel, on the
+// next of its streams (the batch's own when the samplers' plan is empty).
+void miso_batch::launch_exact(const KernelArgs &a) {
+  KernelArgs ka = a;
+  ka.slot_event = d_slots + n_k2 + n_gen; ka.n_slots = n_exact;
+  note_kernel("exact_sample");
+  const double *eff = exact_eff.d;
+  int Sn = S();
+  void *args[] = {&ka, &eff, &Sn};
+  (void) hipLaunchKernel(fn(&exact_sample), dim3(static_cast<unsigned>(n_exact)), dim3(64), args, 0, stream_for_next());
+  HIP_OK(hipGetLastError());
+}
+
+// Posterior mean and the two quantiles of every event the exact mode took, from the grid itself (exact_probe): made once
+// per confidence level, for all of them.
+void miso_batch::exact_summaries(double confidence_level) {
+  if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (!(confidence_level > 0 && confidence_level < 1)) MISO_FAIL(MISO_EINVAL, "Invalid confidence level");
+  if (exact_sums_level == confidence_level && exact_sums.size() == static_cast<size_t>(n_exact) * 6) return;
+  HIP_OK(hipSetDevice(device));
+  const double alpha = 1 - confidence_level;
+  const double prob[2] = {alpha / 2, 1 - alpha / 2};
+  std::vector<double> st(static_cast<size_t>(n_exact) * 7), out8(static_cast<size_t>(n_exact) * 8), q(static_cast<size_t>(n_exact) * 4);
+  for (int j = 0; j < n_exact; j++) {
+    const PackedEvent &e = events[h_slots[n_k2 + n_gen + j]];
+    double *r = &st[static_cast<size_t>(j) * 7];
+    r[0] = e.base_count[0]; r[1] = e.base_count[1]; r[2] = e.base_count[0] + e.base_count[1] + e.n_draw;
+    r[3] = e.eff[0]; r[4] = e.eff[1]; r[5] = e.hyper[0]; r[6] = e.hyper[1];
+  }
+  exact_probe_run(st.data(), n_exact, prob, 2, out8.data(), q.data(), stream);
+  exact_sums.assign(static_cast<size_t>(n_exact) * 6, 0.0);
+  for (int j = 0; j < n_exact; j++) {
+    double *r = &exact_sums[static_cast<size_t>(j) * 6];
+    const double *lo = &q[static_cast<size_t>(j) * 4], *hi = lo + 2;   // {x, 1 - x} at the low and at the high quantile
+    r[0] = out8[static_cast<size_t>(j) * 8]; r[1] = out8[static_cast<size_t>(j) * 8 + 1];
+    r[2] = lo[0]; r[3] = hi[1];
+    r[4] = hi[0]; r[5] = lo[1];
+  }
+  exact_sums_level = confidence_level;
+}
+
 // general run ri in a launch of its own, or with the next run (merge_next); nothing when the run before took it
 void miso_batch::launch_run(const KernelArgs &a, size_t ri) {
   const LaunchPlan::Run &r = plan.runs[ri];
@@ -1913,7 +1987,10 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
     if (count <= 0) continue;
     // slot order = events by drawing reads, descending, each with its noChains chains
     std::vector<int> nd;
-    for (const PackedEvent &e : events) if (e.K == 2 && !k2_general && (use_delta && e.pe_delta && !e.draw_dense.empty()) == wpart) nd.push_back(e.n_draw);
+    for (size_t i = 0; i < events.size(); i++) {
+      const PackedEvent &e = events[i];
+      if (e.K == 2 && !k2_general && !event_exact(static_cast<int>(i)) && (use_delta && e.pe_delta && !e.draw_dense.empty()) == wpart) nd.push_back(e.n_draw);
+    }
     std::sort(nd.begin(), nd.end(), [](int x, int y) { return x > y; });
     const int C = p.noChains;
     const long chains = static_cast<long>(count) * C;
@@ -2008,6 +2085,10 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
       for (long sl = 0; sl < chains; sl++) { trips += 4 * ((((evs[sl / C]->n_draw + 3) / 4) + 255) / 256); waves += 4; }
     }
     add_stat(run_name(ri), static_cast<double>(waves), trips, static_cast<double>(chains), words);
+  }
+  if (n_exact > 0) {   // one wavefront per event, no chains: `chains` counts the events, `words` their sample uniforms
+    add_stat("exact_sample", static_cast<double>(n_exact), 0.0, static_cast<double>(n_exact), static_cast<double>(n_exact) * S());
+    out.back().iterations = 1.0;
   }
   return out;
 }
@@ -2120,7 +2201,8 @@ void miso_batch::converge_rounds(float *ms) {
   HIP_OK(hipMemcpy(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost));
   std::vector<int> again;
   for (size_t i = 0; i < events.size(); i++)
-    if (!convergent_mean(reinterpret_cast<const double *>(out.data() + h_events[i].off_samples), events[i].K, C, S0))
+    if (!event_exact(static_cast<int>(i)) &&   // (independent draws from the posterior itself: done after the first round)
+        !convergent_mean(reinterpret_cast<const double *>(out.data() + h_events[i].off_samples), events[i].K, C, S0))
       again.push_back(static_cast<int>(i));
   if (again.empty()) return;
   const int64_t N2 = 3LL * N - 2LL * B, total = static_cast<int64_t>(p.noIterations) + N2;

@@ -132,8 +132,9 @@ class GenesDispatcher(object):
     def __init__(self, gff_dir, bam_filename, output_dir, read_len, overhang_len,
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
-                 labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False):
+                 labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False):
         self.summary_only = bool(summary_only)
+        self.exact = bool(exact)       # --exact: handed on to every worker
         self.diagnostics = bool(diagnostics)
         self.diag_tables = []          # --diagnostics: [(table, its per-worker parts)], one per output directory (run)
         self.prefilter = bool(prefilter)
@@ -311,6 +312,8 @@ class GenesDispatcher(object):
                 cmd += ["--event-type", self.event_type]
             if self.seed is not None:
                 cmd += ["--seed", str(self.seed)]
+            if self.exact:
+                cmd += ["--exact"]
             log = os.path.join(self.batch_logs_dir, "batch-%d-%s.log"
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
@@ -385,7 +388,7 @@ class GenesDispatcher(object):
 def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_len=1,
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
-                          labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False):
+                          labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -397,7 +400,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            settings_fname=settings_fname, paired_end=paired_end, num_proc=num_proc,
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
-                           prefilter=prefilter, diagnostics=diagnostics).run()
+                           prefilter=prefilter, diagnostics=diagnostics, exact=exact).run()
 
 
 def main(argv=None):
@@ -424,6 +427,10 @@ def main(argv=None):
                     help="also write OUT/summary/<OUT>.miso_diag: per event the split R-hat of its chains, the effective "
                          "sample size and the Monte-Carlo standard error of the Psi mean, computed on the GPU during the run; "
                          "with --compare one table per label: OUT/<label>/summary/<label>.miso_diag")
+    ap.add_argument("--exact", action="store_true",
+                    help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
+                         "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
+                         "other events are sampled as always.  Also the settings key `exact` under [sampler].")
     ap.add_argument("--compare", metavar="BAM2", default=None,
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
@@ -458,7 +465,8 @@ def main(argv=None):
                                        summary_only=a.summary_only,
                                        compare_bam=None if a.compare is None else
                                        os.path.abspath(os.path.expanduser(a.compare)),
-                                       labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics)
+                                       labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics,
+                                       exact=a.exact)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

@@ -195,7 +195,10 @@ class MISOSampler:
                            device_match=True,
                            # opt-in, single-end: the collapsed Gibbs step (include/miso_amd.h miso_batch_set_collapsed);
                            # params["collapsed"] or MISO_COLLAPSED=1|2 in the environment
-                           collapsed=0 if self.paired_end else int(self.params.get("collapsed", os.environ.get("MISO_COLLAPSED", 0)) or 0))
+                           collapsed=0 if self.paired_end else int(self.params.get("collapsed", os.environ.get("MISO_COLLAPSED", 0)) or 0),
+                           # opt-in, single-end: the exact-posterior mode of the eligible two-isoform events (include/miso_amd.h
+                           # miso_batch_set_exact); params["exact"] or MISO_EXACT=1 in the environment
+                           exact=False if self.paired_end else bool(int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0)))
         written = [None] * len(events)
         slots = []
         from sam_utils import STRAND_RULES
@@ -442,6 +445,8 @@ class MISOSampler:
                 kw["event_ids"] = tuple(int(event_ids[p[0]]) for p in keep)
             if diagnostics_files is not None:
                 kw["diagnostics"] = True
+            if not self.paired_end and int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
+                kw["exact"] = True          # the exact-posterior mode, as in prepare_batch
             res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),

@@ -28,6 +28,8 @@
  *   MISOBatch / MISOPairedBatch(events, ...)  many events per GPU launch; events is a tuple of
  *                   (gff, readpos, readcigar[, hyperp]); returns a list of 6-tuples;
  *   first_event_id  global index of the first event (sharding a run over GPUs).
+ *   exact=True      MISOBatch / MISOCompareBatch: the eligible single-end two-isoform events run no chain, their
+ *                   samples are independent draws from the tabulated posterior of psi (miso_batch_set_exact).
  * The functions of the module that are not on the sampler path raise NotImplementedError.
  * The reference's stdout side effect `printf("no chains: %d\n")` (miso.c:837) is not reproduced.
  */
@@ -376,11 +378,12 @@ static int parse_level(PyObject *obj, double *conf) {
   return 0;
 }
 
-/* a new batch holding `events` = ((gff, readpos, readcigar[, hyperp]), ...) */
-static miso_batch_t *fill_batch(PyObject *events, miso_params_t *p) {
+/* a new batch holding `events` = ((gff, readpos, readcigar[, hyperp]), ...); exact: miso_batch_set_exact */
+static miso_batch_t *fill_batch(PyObject *events, miso_params_t *p, int exact) {
   miso_batch_t *b = NULL; Py_ssize_t i, n; int rc;
   if (!PyTuple_Check(events)) { PyErr_SetString(PyExc_TypeError, "Need a tuple"); return NULL; }
   if ((rc = miso_batch_create(p, &b))) { raise_miso(rc); return NULL; }
+  if (exact && (rc = miso_batch_set_exact(b, 1))) { raise_miso(rc); miso_batch_destroy(b); return NULL; }
   n = PyTuple_Size(events);
   for (i = 0; i < n; i++) {
     PyObject *ev = PyTuple_GET_ITEM(events, i);
@@ -433,13 +436,13 @@ static PyObject *diagnostics_list(miso_batch_t *b, Py_ssize_t n) {
 }
 
 static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seedobj,
-                              unsigned int first_event_id, PyObject *summaryobj) {
+                              unsigned int first_event_id, PyObject *summaryobj, int exact) {
   double conf; miso_batch_t *b; PyObject *out = NULL; Py_ssize_t n;
   unsigned long long seed;
   if (seedobj && seedobj != Py_None) { seed = PyLong_AsUnsignedLongLongMask(seedobj); if (PyErr_Occurred()) return NULL; }
   else if (default_seed(&seed)) return NULL;
   if (parse_level(summaryobj, &conf)) return NULL;
-  if (!(b = fill_batch(events, p))) return NULL;
+  if (!(b = fill_batch(events, p, exact))) return NULL;
   n = PyTuple_Size(events);
   if (n == 0 || !run_batch(b, seed, first_event_id)) out = results_list(b, n, conf);
   miso_batch_destroy(b);
@@ -452,18 +455,18 @@ static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seed
 static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
-                           "summary", "smoothing", "paired", "event_ids", "diagnostics", NULL};
+                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL;
-  int diagnostics = 0;
+  int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
   int start = MISO_START_AUTO, stop = MISO_STOP_FIXEDNO, rc;
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOp", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOpp", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
-                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics)) return NULL;
+                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact)) return NULL;
   if (seedobj && seedobj != Py_None) { seed = PyLong_AsUnsignedLongLongMask(seedobj); if (PyErr_Occurred()) return NULL; }
   else if (default_seed(&seed)) return NULL;
   /* the two samples must not share random numbers: identical draws would correlate the chains */
@@ -478,8 +481,8 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   if (!PyTuple_Check(ev1) || !PyTuple_Check(ev2)) { PyErr_SetString(PyExc_TypeError, "Need a tuple"); return NULL; }
   n = PyTuple_Size(ev1);
   if (PyTuple_Size(ev2) != n) { PyErr_SetString(PyExc_ValueError, "the two samples must list the same events"); return NULL; }
-  if (!(b1 = fill_batch(ev1, &p))) goto done;
-  if (!(b2 = fill_batch(ev2, &p))) goto done;
+  if (!(b1 = fill_batch(ev1, &p, exact))) goto done;
+  if (!(b2 = fill_batch(ev2, &p, exact))) goto done;
   /* event_ids: every event's id in the Philox counter (its number in the caller's full event list), so
      that events dropped by the caller's skip rules, the chunking and the number of GPUs change nobody's
      random stream -- as miso_batch_set_event_id does for MISOBatch's callers */
@@ -526,16 +529,17 @@ done:
 
 static PyObject *py_miso_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events", "readLength", "noIterations", "noBurnIn", "noLag", "overhang",
-                           "no_chains", "start", "stop", "algo", "seed", "first_event_id", "summary", NULL};
+                           "no_chains", "start", "stop", "algo", "seed", "first_event_id", "summary", "exact", NULL};
   PyObject *events, *seedobj = NULL, *summaryobj = NULL;
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
   int start = MISO_START_AUTO, stop = MISO_STOP_FIXEDNO, algo = MISO_ALGO_REASSIGN;
+  int exact = 0;   /* exact=True: the eligible two-isoform events take the exact-posterior mode (miso_batch_set_exact) */
   unsigned int first = 0; miso_params_t p;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "Oi|iiiiiiii$OIO", kwlist, &events, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "Oi|iiiiiiii$OIOp", kwlist, &events, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &algo, &seedobj,
-                                   &first, &summaryobj)) return NULL;
+                                   &first, &summaryobj, &exact)) return NULL;
   fill_params(&p, 0, readLength, overhang, chains, iters, burn, lag, algo, start, stop, 0, 0, 0);
-  return batch_common(events, &p, seedobj, first, summaryobj);
+  return batch_common(events, &p, seedobj, first, summaryobj, exact);
 }
 
 static PyObject *py_miso_paired_batch(PyObject *self, PyObject *args, PyObject *kw) {
@@ -551,7 +555,7 @@ static PyObject *py_miso_paired_batch(PyObject *self, PyObject *args, PyObject *
                                    &stop, &seedobj, &first, &summaryobj)) return NULL;
   fill_params(&p, 1, readLength, overhang, chains, iters, burn, lag, MISO_ALGO_REASSIGN, start, stop,
               mean, var, devs);
-  return batch_common(events, &p, seedobj, first, summaryobj);
+  return batch_common(events, &p, seedobj, first, summaryobj, 0);
 }
 
 /* ---- simulateReads / simulatePairedReads (pysplicing.c:280-330, 462-520) ---- */

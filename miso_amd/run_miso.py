@@ -147,11 +147,13 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
-                     diagnostics_file=None):
+                     diagnostics_file=None, exact=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
-    diagnostics table of this run (diagnostics.py), per launch from the resident samples, merged like the summary parts."""
+    diagnostics table of this run (diagnostics.py), per launch from the resident samples, merged like the summary parts.
+    exact: single-end two-isoform events take the exact-posterior mode (None: the settings' `exact` key)."""
+    exact = Settings.get_exact() if exact is None else bool(exact)
     os.makedirs(output_dir, exist_ok=True)
     if gene_entries is None:
         gene_entries = [(g, gff_index_filename) for g in gene_ids]
@@ -244,6 +246,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                                                             overhang_len=overhang_len)
             else:
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
+                if exact:
+                    params["exact"] = 1     # miso_sampler.py prepare_batch
             sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=output_dir)
             # every event keeps the number it has in the caller's gene list: skipped genes, chunking
             # and the number of GPUs do not change anybody's random stream
@@ -313,7 +317,7 @@ def merge_tables(parts, filename, remove=True):
 def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, output_dir2,
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
-                     max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None):
+                     max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -328,6 +332,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     if device is not None:
         _check_device(device)
         os.environ["MISO_DEVICE"] = str(int(device))
+    exact = Settings.get_exact() if exact is None else bool(exact)
     p = Settings.get_sampler_params()
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
     evs = []
@@ -353,6 +358,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                                         overhang_len=overhang_len)
         else:
             params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
+            if exact:
+                params["exact"] = 1     # miso_sampler.py prepare_batch
         sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=output_dir1)
         part = "%s.part%06d" % (comparison_file, lo)
         parts.append(part)
@@ -380,6 +387,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                                             overhang_len=overhang_len)
             else:
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
+                if exact:
+                    params["exact"] = 1     # miso_sampler.py prepare_batch
             sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=out)
             dpart = None
             if diagnostics_files is not None:
@@ -437,6 +446,9 @@ def main(argv=None):
                     help="with --compare-genes-from-file: the chain diagnostics table of each sample")
     ap.add_argument("--no-miso-files", action="store_true",
                     help="with --summary-file: only the table, no per-event .miso files")
+    ap.add_argument("--exact", action="store_true",
+                    help="single-end two-isoform events: independent draws from the exact posterior of Psi instead of chains "
+                         "(also the settings key `exact`)")
     ap.add_argument("--paired-end", nargs=2, type=float, metavar=("MEAN", "SD"))
     ap.add_argument("--read-len", type=int)
     ap.add_argument("--overhang-len", type=int)
@@ -453,6 +465,7 @@ def main(argv=None):
         return 1
     overhang_len = a.overhang_len if a.overhang_len is not None else 1
     paired_end = tuple(a.paired_end) if a.paired_end else None
+    exact = bool(a.exact) or Settings.get_exact()       # the flag, or `exact = True` under [sampler] of the settings file
     if a.diagnostics_file and not a.compute_genes_from_file:
         print("Error: --diagnostics-file goes with --compute-genes-from-file.")
         return 1
@@ -466,7 +479,7 @@ def main(argv=None):
         n = compare_gene_psi(entries, bam1, bam2, out1, out2, bf, a.read_len, overhang_len,
                              paired_end=paired_end, event_type=a.event_type, seed=a.seed,
                              first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
-                             samples=samples, diagnostics_files=a.diagnostics_files)
+                             samples=samples, diagnostics_files=a.diagnostics_files, exact=exact)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -481,7 +494,7 @@ def main(argv=None):
                          seed=a.seed, first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
                          summary_file=a.summary_file,
                          write_files=not (a.no_miso_files and a.summary_file),
-                         diagnostics_file=a.diagnostics_file)
+                         diagnostics_file=a.diagnostics_file, exact=exact)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")
@@ -489,7 +502,7 @@ def main(argv=None):
                                                   for p in a.compute_gene_psi[1:])
         compute_gene_psi(gene_ids, gff_filename, bam_filename, output_dir, a.read_len,
                          overhang_len, paired_end=paired_end, event_type=a.event_type,
-                         seed=a.seed, first_event_id=a.first_event_id, device=a.device)
+                         seed=a.seed, first_event_id=a.first_event_id, device=a.device, exact=exact)
     else:
         ap.print_help()
     return 0

@@ -54,6 +54,19 @@ class Settings(object):
                 "lag": table["lag"], "num_iters": table["num_iters"]}
 
     @classmethod
+    def get_exact(cls, default_exact=False):
+        """`exact = True` under [sampler]: single-end two-isoform events take the exact-posterior mode (miso --run --exact)."""
+        value = cls.global_settings.get("exact", default_exact)
+        if isinstance(value, str):       # not a Python literal: the usual spellings, anything else is an error
+            low = value.strip().lower()
+            if low in ("true", "yes", "on", "1"):
+                return True
+            if low in ("false", "no", "off", "0", ""):
+                return False
+            raise ValueError("Error: Invalid exact parameter %s (True or False)" % value)
+        return bool(value)
+
+    @classmethod
     def get_min_event_reads(cls, default_min_reads=20):
         return cls.global_settings.get("min_event_reads", default_min_reads)
 
