@@ -351,6 +351,27 @@ int miso_batch_compare(miso_batch_t *sample1, miso_batch_t *sample2, double smoo
 int miso_batch_get_comparison(const miso_batch_t *sample1, int event_index, double *mean1, double *mean2,
                               double *bayes_factor, double *density_at_0);   /* noiso doubles each */
 
+/* The comparison of two batches that both ran with the exact-posterior mode (miso_batch_set_exact), without a draw
+   (csrc/kernels_exact_compare.hip).  Preconditions and errors as miso_batch_compare: both synced,
+   same device, the same events in the same order.  An event pair is EXACT-COMPARABLE when the exact mode took the event
+   in both batches and its two effective lengths are bit-equal in both; every other pair gets was_exact = 0 and nothing
+   else.  For a comparable pair the product of the two posteriors is a posterior of the same family (pooled counts,
+   hyperparameters h1 + h2 - 1), so the posterior density of delta = psi_1 - psi_2 at 0 is a ratio of three normalisers of
+   the mode's own tables: log_density_at_0 = log Z12 - log Z1 - log Z2.  The Savage-Dickey Bayes factor is the prior
+   density of delta at 0 (from the hyperparameters, std::lgamma on the host; 1 at h = (1, 1)) over it:
+   log10_bayes_factor is uncapped, bayes_factor = min(exp(log BF), 1e12); no "peaked on the null" rule applies.
+   z: n_z points in (-1, 1), 0 <= n_z <= 8: cdf[j] = P(psi_1 - psi_2 <= z[j]), the trapezoid sum over the narrower
+   posterior's 2049 grid points of its density times the other posterior's tabulated CDF at the shifted argument.
+   mean1 / mean2: the grid means of psi_0.  No Monte-Carlo error, no dependence on the seed.  MISO_EINVAL when either
+   batch lacks the exact mode, n_z is outside [0, 8] or a z outside (-1, 1); MISO_ENODEVICE without a GPU.  Results are
+   stored in sample1; the launch appears in miso_batch_last_kernels as exact_compare. */
+int miso_batch_compare_exact(miso_batch_t *sample1, miso_batch_t *sample2, const double *z, int n_z);
+int miso_batch_get_exact_comparison(const miso_batch_t *sample1, int event_index, double *mean1, double *mean2,
+                                    double *log_density_at_0, double *bayes_factor, double *log10_bayes_factor,
+                                    double *cdf /* n_z */, int *was_exact);
+/* Kernel time (HIP events) of the last miso_batch_compare and miso_batch_compare_exact stored in this batch, ms; 0 before. */
+int miso_batch_compare_ms(const miso_batch_t *sample1, float *compare_ms, float *exact_compare_ms);
+
 /* Every pair of two groups of samples (biological replicates) in one device pass.  group1[i], group2[j]: batches that
    hold the SAME events in the same order with the same n_samples, on the same device (what miso_batch_compare requires of
    its two); n1, n2 >= 1.  out: n1 * n2 * tot doubles, tot = sum over events of 4 * noiso; pair (i, j), event e, isoform k
@@ -508,6 +529,11 @@ int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, d
    space), the normalising sum F[G], the mode (logit space), the grid step, the log density at the mode as tabulated};
    icdf[(i n_prob + j) 2 ...] = {x, 1 - x} at the inverse CDF of prob[j] (0 < prob < 1). */
 int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf);
+/* kernels_exact_compare.hip on caller-given statistics, one wavefront per pair: stats7_1 / stats7_2 in miso_selftest_exact's
+   layout (sample 1, sample 2).  out[(5 + n_z) i ...] = {mean1, mean2, log_density_at_0, bayes_factor, log10_bayes_factor,
+   cdf at z[0 .. n_z)} as miso_batch_get_exact_comparison returns them.  MISO_EINVAL when a pair's e0, e1 differ between
+   its samples (bit-wise), when a pair is not eligible for the exact mode, n_z is outside [0, 8] or a z outside (-1, 1). */
+int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, int n, const double *z, int n_z, double *out);
 /* csrc/text_digits.hpp text_digits, the rounding of summarize_as_text: out[i] = x[i] x 10^4 rounded to the nearest integer,
    ties to even, on the exact product -- the digits of "%.4f" of x[i], sign included.  Finite |x[i]| < 2^38. */
 int miso_selftest_text_digits(const double *x, int n, int64_t *out);

@@ -362,6 +362,29 @@ class Batch:
         check(lib().miso_batch_get_comparison(self.handle, i, _p(m1), _p(m2), _p(bf), _p(dens)))
         return m1, m2, bf, dens
 
+    def compare_exact(self, other, z=()):
+        """The exact comparison with `other` (same events, same order; both batches exact=True) on the device, without a
+        draw: Bayes factor and P(psi_1 - psi_2 <= z) for every z (at most 8, each in (-1, 1)) from the two posteriors'
+        tables (miso_batch_compare_exact in include/miso_amd.h)."""
+        zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+        check(lib().miso_batch_compare_exact(self.handle, other.handle, _p(zz), C.c_int(len(zz))))
+        self._exact_nz = len(zz)
+
+    def exact_comparison(self, i):
+        """(mean1, mean2, log_density_at_0, bayes_factor, log10_bayes_factor, cdf[n_z]) of event i after compare_exact();
+        None when the pair is not exact-comparable (miso_batch_get_exact_comparison)."""
+        v = [C.c_double(0.0) for _ in range(5)]
+        cdf = np.zeros(getattr(self, "_exact_nz", 0))
+        was = C.c_int(0)
+        check(lib().miso_batch_get_exact_comparison(self.handle, int(i), *[C.byref(x) for x in v], _p(cdf), C.byref(was)))
+        return tuple(x.value for x in v) + (cdf,) if was.value else None
+
+    def compare_ms(self):
+        """(kernel ms of the last compare(), of the last compare_exact()) stored in this batch"""
+        a, b = C.c_float(0), C.c_float(0)
+        check(lib().miso_batch_compare_ms(self.handle, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     def add_event_aln(self, gene, alnfile, chrom, start, end, strand_rule=0, target_strand=None,
                       read_len=None, min_reads=0, hyper=None):
         """One event straight from an open alignment file (sam_utils.Samfile) -- fetch, pairing and
@@ -801,6 +824,20 @@ def selftest_exact(stats7, probs):
     icdf = np.zeros((len(st), len(pr), 2))
     check(lib().miso_selftest_exact(_p(st), len(st), _p(pr), len(pr), _p(out8), _p(icdf)))
     return out8, icdf
+
+
+def selftest_exact_compare(stats7_1, stats7_2, z=()):
+    """csrc/kernels_exact_compare.hip on caller-given statistics: stats7_i[j] = (n10, n01, n, e0, e1, h0, h1) of pair j in
+    sample i -> out [n, 5 + len(z)] = mean1, mean2, log density of psi_1 - psi_2 at 0, Bayes factor (capped), log10 Bayes
+    factor, P(psi_1 - psi_2 <= z) -- include/miso_amd.h miso_selftest_exact_compare"""
+    s1 = np.ascontiguousarray(stats7_1, dtype=np.float64).reshape(-1, 7)
+    s2 = np.ascontiguousarray(stats7_2, dtype=np.float64).reshape(-1, 7)
+    if len(s1) != len(s2):
+        raise ValueError("stats7_1, stats7_2: one row per pair each")
+    zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+    out = np.zeros((len(s1), 5 + len(zz)))
+    check(lib().miso_selftest_exact_compare(_p(s1), _p(s2), C.c_int(len(s1)), _p(zz), C.c_int(len(zz)), _p(out)))
+    return out
 
 
 def selftest_text_digits(x):

@@ -55,3 +55,60 @@ def write_comparison(filename, rows):
             f.write(comparison_line(*row) + "\n")
             n += 1
     return n
+
+
+# ---- the exact comparison's table, `<label1>_vs_<label2>.miso_bf_exact` beside the `.miso_bf` ----
+DEFAULT_DELTA_THRESHOLDS = (0.1, 0.2)
+MAX_DELTA_THRESHOLDS = 4            # two points of the CDF each, miso_batch_compare_exact takes eight
+
+
+def check_delta_thresholds(thresholds):
+    """the thresholds as floats; ValueError unless there are 1 .. 4 of them, each inside (0, 1)"""
+    t = [float(x) for x in thresholds]
+    if not 1 <= len(t) <= MAX_DELTA_THRESHOLDS:
+        raise ValueError("Error: between 1 and %d delta psi thresholds, got %d" % (MAX_DELTA_THRESHOLDS, len(t)))
+    for x in t:
+        if not 0.0 < x < 1.0:
+            raise ValueError("Error: delta psi threshold %r outside (0, 1)" % x)
+    return t
+
+
+def delta_points(thresholds):
+    """where the exact comparison evaluates the CDF of psi_1 - psi_2: (t, -t) of every threshold"""
+    return tuple(z for t in check_delta_thresholds(thresholds) for z in (t, -t))
+
+
+def exact_header_fields(thresholds):
+    return HEADER_FIELDS + ["exact", "log10_bayes_factor"] + ["prob_abs_diff_ge_%g" % t for t in thresholds]
+
+
+def exact_comparison_line(event_name, summary1, summary2, bayes_factors, header1, header2, exact, thresholds):
+    """exact = None: the event's `.miso_bf` line, then exact = 0 and NA.  Otherwise (mean1, mean2, log_density_at_0,
+    bayes_factor, log10_bayes_factor, cdf at delta_points(thresholds), grid summary of sample 1, of sample 2) as
+    pysplicing.MISOCompareBatch(exact_compare=) returns it: means, bounds and difference from the grid as %.4f, the capped
+    Bayes factor as %.2f, P(|psi_1 - psi_2| >= t) = 1 - H(t) + H(-t) per threshold."""
+    if exact is None:
+        return "\t".join([comparison_line(event_name, summary1, summary2, bayes_factors, header1, header2), "0", "NA"]
+                         + ["NA"] * len(thresholds))
+    mean1, mean2, _, bf, log10_bf, cdf, (m1, lo1, hi1), (m2, lo2, hi2) = exact
+    f = [event_name, "%.4f" % m1[0], "%.4f" % lo1[0], "%.4f" % hi1[0], "%.4f" % m2[0], "%.4f" % lo2[0], "%.4f" % hi2[0],
+         "%.4f" % (mean1 - mean2), "%.2f" % min(bf, MAX_BF), header1["isoforms"],
+         header1["counts"], header1["assigned_counts"], header2["counts"], header2["assigned_counts"]]
+    for key in ("chrom", "strand", "mRNA_starts", "mRNA_ends"):
+        f.append(header1.get(key, "NA"))
+    f += ["1", "%.4f" % log10_bf]
+    f += ["%.4f" % ((1.0 - cdf[2 * j]) + cdf[2 * j + 1]) for j in range(len(thresholds))]
+    return "\t".join(f)
+
+
+def write_exact_comparison(filename, rows, thresholds):
+    """rows: iterable of (event_name, summary1, summary2, bayes_factors, header1, header2, exact) -- write_comparison's
+    row and the event's exact comparison, or None where the pair was not exact-comparable."""
+    thresholds = check_delta_thresholds(thresholds)
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(exact_header_fields(thresholds)) + "\n")
+        for row in rows:
+            f.write(exact_comparison_line(*row, thresholds=thresholds) + "\n")
+            n += 1
+    return n

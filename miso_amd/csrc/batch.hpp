@@ -30,6 +30,10 @@ void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, doubl
 void selftest_text_digits(const double *x, int n, int64_t *out);
 // kernels_exact.hip: the exact-posterior mode's posterior stage on its own (miso_selftest_exact, exact summaries)
 void exact_probe_run(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st = nullptr);
+// kernels_exact_compare.hip: pairs of such posteriors compared (miso_batch_compare_exact, miso_selftest_exact_compare);
+// out: 5 + n_z doubles per pair
+void exact_compare_run(const double *stats7_1, const double *stats7_2, int n, const double *z, int n_z, double *out,
+                       hipStream_t st = nullptr, float *ms = nullptr);
 // the exact-posterior mode takes such an event (include/miso_amd.h miso_exact_eligible)
 inline bool exact_eligible(bool paired, int K, const double *eff, const double *hyper) {
   return !paired && K == 2 && eff[0] > 0 && eff[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1;
@@ -137,6 +141,14 @@ struct miso_batch {
   void build_slots();
   void launch_exact(const miso::KernelArgs &a);
   void exact_summaries(double confidence_level);
+  void exact_stats7(int event, double *r) const;   // {n10, n01, n, e0, e1, h0, h1} of an event of the exact list
+  // miso_batch_compare_exact (this batch is sample 1): per event 5 + exact_cmp_nz doubles, and whether the pair was comparable
+  std::vector<double> h_exact_cmp;
+  std::vector<char> exact_cmp_ok;
+  int exact_cmp_nz = 0;
+  bool exact_compared = false;
+  float compare_ms = 0.f, exact_compare_ms = 0.f;   // kernel time of the last compare / compare_exact
+  void compare_exact(miso_batch &other, const double *z, int n_z);
   miso::LanePlan k2_plan;         // sampler_k2_multi: the runs of equal lanes per chain (runtime.hip), valid for k2_plan_key
   long k2_plan_key = -1;
   miso::CoopTable k2_coop_se, k2w_coop;   // the two plans' chains on several workgroups (key: the plan's wide run)

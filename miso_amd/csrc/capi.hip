@@ -852,6 +852,40 @@ int miso_batch_get_comparison(const miso_batch_t *b, int i, double *mean1, doubl
   });
 }
 
+int miso_batch_compare_exact(miso_batch_t *a, miso_batch_t *b, const double *z, int n_z) {
+  return guarded([&] {
+    need(a, "batch"); need(b, "batch");
+    if (n_z > 0) need(z, "z");
+    a->compare_exact(*b, z, n_z);
+  });
+}
+
+int miso_batch_get_exact_comparison(const miso_batch_t *b, int i, double *mean1, double *mean2, double *log_density_at_0,
+                                    double *bayes_factor, double *log10_bayes_factor, double *cdf, int *was_exact) {
+  return guarded([&] {
+    need(b, "batch"); need(was_exact, "was_exact");
+    (void) event_at(b, i);
+    if (!b->exact_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_exact has not run");
+    *was_exact = b->exact_cmp_ok[i] ? 1 : 0;
+    if (!*was_exact) return;
+    const double *r = &b->h_exact_cmp[static_cast<size_t>(i) * (5 + b->exact_cmp_nz)];
+    if (mean1) *mean1 = r[0];
+    if (mean2) *mean2 = r[1];
+    if (log_density_at_0) *log_density_at_0 = r[2];
+    if (bayes_factor) *bayes_factor = r[3];
+    if (log10_bayes_factor) *log10_bayes_factor = r[4];
+    if (cdf) for (int k = 0; k < b->exact_cmp_nz; k++) cdf[k] = r[5 + k];
+  });
+}
+
+int miso_batch_compare_ms(const miso_batch_t *b, float *compare_ms, float *exact_compare_ms) {
+  return guarded([&] {
+    need(b, "batch");
+    if (compare_ms) *compare_ms = b->compare_ms;
+    if (exact_compare_ms) *exact_compare_ms = b->exact_compare_ms;
+  });
+}
+
 int miso_batch_compare_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, double smoothing,
                               int staging, double *out, int64_t out_len, float *kernel_ms) {
   return guarded([&] {
@@ -1096,6 +1130,13 @@ int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_p
     if (n > 0) need(stats7, "stats7");
     if (n_prob > 0) need(prob, "prob");
     exact_probe_run(stats7, n, prob, n_prob, out8, icdf);
+  });
+}
+int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, int n, const double *z, int n_z, double *out) {
+  return guarded([&] {
+    if (n > 0) { need(stats7_1, "stats7_1"); need(stats7_2, "stats7_2"); need(out, "out"); }
+    if (n_z > 0) need(z, "z");
+    exact_compare_run(stats7_1, stats7_2, n, z, n_z, out);
   });
 }
 int miso_selftest_text_digits(const double *x, int n, int64_t *out) {

@@ -783,7 +783,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   }
   HIP_OK(hipEventRecord(ev1, stream));
   start_clock_probe();
-  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; diagnosed = false;
+  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; exact_compared = false; diagnosed = false;
 }
 
 // The launch's sizes and switches, read once per launch.
@@ -1814,6 +1814,13 @@ void miso_batch::launch_exact(const KernelArgs &a) {
   HIP_OK(hipGetLastError());
 }
 
+// the statistics of an event of the exact list as exact_probe and exact_compare take them
+void miso_batch::exact_stats7(int event, double *r) const {
+  const PackedEvent &e = events[event];
+  r[0] = e.base_count[0]; r[1] = e.base_count[1]; r[2] = e.base_count[0] + e.base_count[1] + e.n_draw;
+  r[3] = e.eff[0]; r[4] = e.eff[1]; r[5] = e.hyper[0]; r[6] = e.hyper[1];
+}
+
 // Posterior mean and the two quantiles of every event the exact mode took, from the grid itself (exact_probe): made once
 // per confidence level, for all of them.
 void miso_batch::exact_summaries(double confidence_level) {
@@ -1824,12 +1831,7 @@ void miso_batch::exact_summaries(double confidence_level) {
   const double alpha = 1 - confidence_level;
   const double prob[2] = {alpha / 2, 1 - alpha / 2};
   std::vector<double> st(static_cast<size_t>(n_exact) * 7), out8(static_cast<size_t>(n_exact) * 8), q(static_cast<size_t>(n_exact) * 4);
-  for (int j = 0; j < n_exact; j++) {
-    const PackedEvent &e = events[h_slots[n_k2 + n_gen + j]];
-    double *r = &st[static_cast<size_t>(j) * 7];
-    r[0] = e.base_count[0]; r[1] = e.base_count[1]; r[2] = e.base_count[0] + e.base_count[1] + e.n_draw;
-    r[3] = e.eff[0]; r[4] = e.eff[1]; r[5] = e.hyper[0]; r[6] = e.hyper[1];
-  }
+  for (int j = 0; j < n_exact; j++) exact_stats7(h_slots[n_k2 + n_gen + j], &st[static_cast<size_t>(j) * 7]);
   exact_probe_run(st.data(), n_exact, prob, 2, out8.data(), q.data(), stream);
   exact_sums.assign(static_cast<size_t>(n_exact) * 6, 0.0);
   for (int j = 0; j < n_exact; j++) {
@@ -2389,13 +2391,55 @@ void miso_batch::compare(miso_batch &other, double smoothing) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_cmp), tot * sizeof(double)));
   HIP_OK(hipMemcpyAsync(d_off, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  PassTimer timer(stream, pass_ev0, pass_ev1);
   hipLaunchKernelGGL(compare_kernel, dim3(n, kmax), dim3(256), 0, stream, d_events, d_out, other.d_events,
                      other.d_out, n, Sn, smoothing, d_off, d_cmp);
   HIP_OK(hipGetLastError());
+  timer.stop();
   HIP_OK(hipMemcpyAsync(h_compare.data(), d_cmp, tot * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
   (void) hipFree(d_off); (void) hipFree(d_cmp);
+  compare_ms = timer.ms();
   compared = true;
+}
+
+// The exact comparison of this batch (sample 1) with `other` (sample 2): the pairs both batches' exact mode took, with
+// bit-equal effective lengths, go to exact_compare (kernels_exact_compare.hip); every other pair is marked not comparable.
+void miso_batch::compare_exact(miso_batch &other, const double *z, int n_z) {
+  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
+  if (events.size() != other.events.size() || S() != other.S())
+    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
+  if (!exact || !other.exact || slots_exact != exact || other.slots_exact != other.exact)
+    MISO_FAIL(MISO_EINVAL, "Both batches to compare exactly must have run with the exact-posterior mode");
+  if (n_z < 0 || n_z > 8) MISO_FAIL(MISO_EINVAL, "The number of delta psi points must lie in [0, 8]");
+  const int n = static_cast<int>(events.size());
+  for (int i = 0; i < n; i++)
+    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+  std::vector<int> list;
+  std::vector<double> s1, s2;
+  exact_cmp_ok.assign(n, 0);
+  for (int i = 0; i < n; i++) {
+    if (!event_exact(i) || !other.event_exact(i)) continue;
+    if (std::memcmp(events[i].eff.data(), other.events[i].eff.data(), 2 * sizeof(double)) != 0) continue;
+    list.push_back(i);
+    s1.resize(s1.size() + 7); s2.resize(s2.size() + 7);
+    exact_stats7(i, &s1[s1.size() - 7]); other.exact_stats7(i, &s2[s2.size() - 7]);
+  }
+  const size_t w = 5 + static_cast<size_t>(n_z);
+  std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
+  HIP_OK(hipSetDevice(device));
+  HIP_OK(hipStreamSynchronize(other.stream));
+  // (validates z, and fails with MISO_ENODEVICE without a device, also when no pair is comparable)
+  exact_compare_run(s1.data(), s2.data(), static_cast<int>(list.size()), z, n_z, got.data(), stream, &exact_compare_ms);
+  h_exact_cmp.assign(static_cast<size_t>(n) * w, 0.0);
+  for (size_t j = 0; j < list.size(); j++) {
+    std::memcpy(&h_exact_cmp[list[j] * w], &got[j * w], w * sizeof(double));
+    exact_cmp_ok[list[j]] = 1;
+  }
+  exact_cmp_nz = n_z;
+  if (!list.empty()) note_kernel("exact_compare");
+  exact_compared = true;
 }
 
 // A batch that holds posterior samples produced elsewhere -- parsed `.miso` files (summarize_miso / compare_miso
@@ -2436,7 +2480,7 @@ void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
   n_k2 = n_k2w = n_gen = 0; gen_runs.clear(); plan = LaunchPlan{};
-  uploaded = launched = true; downloaded = false; summarized = compared = diagnosed = false; adopted = true;
+  uploaded = launched = true; downloaded = false; summarized = compared = exact_compared = diagnosed = false; adopted = true;
 }
 
 void miso_batch::download() {

@@ -132,9 +132,14 @@ class GenesDispatcher(object):
     def __init__(self, gff_dir, bam_filename, output_dir, read_len, overhang_len,
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
-                 labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False):
+                 labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
+                 exact_compare=False, delta_thresholds=None):
         self.summary_only = bool(summary_only)
         self.exact = bool(exact)       # --exact: handed on to every worker
+        # --exact-compare: beside the `.miso_bf` table the exact comparison's `.miso_bf_exact` (compare.py), merged like a
+        # diagnostics table; delta_thresholds: its thresholds (None: the workers' default)
+        self.exact_compare = bool(exact_compare)
+        self.delta_thresholds = None if delta_thresholds is None else [float(t) for t in delta_thresholds]
         self.diagnostics = bool(diagnostics)
         self.diag_tables = []          # --diagnostics: [(table, its per-worker parts)], one per output directory (run)
         self.prefilter = bool(prefilter)
@@ -268,12 +273,14 @@ class GenesDispatcher(object):
         if table is not None:
             os.makedirs(os.path.dirname(table), exist_ok=True)
         self.diag_tables = []
+        xtable = []                    # --exact-compare: [(table, its per-worker parts)], merged with the diagnostics tables
         if self.diagnostics:
             # one table per directory of `.miso` files: the output directory, or with --compare each label's
             for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
                 label = os.path.basename(os.path.normpath(d))
                 self.diag_tables.append((os.path.join(d, "summary", label + ".miso_diag"), []))
                 os.makedirs(os.path.dirname(self.diag_tables[-1][0]), exist_ok=True)
+        n_diag = len(self.diag_tables)
         for batch_num, (fname, size, first) in enumerate(batches):
             if size == 0:
                 continue
@@ -283,7 +290,14 @@ class GenesDispatcher(object):
             if self.compare_bam is not None:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compare-genes-from-file", fname,
                        self.bam_filename, self.compare_bam, out1, out2, part]
-                if self.diag_tables:
+                if self.exact_compare:
+                    if not xtable:
+                        xtable.append((table + "_exact", []))
+                    xtable[0][1].append("%s.gpu%d" % (xtable[0][0], batch_num))
+                    cmd += ["--exact-comparison-file", xtable[0][1][-1]]
+                    if self.delta_thresholds is not None:
+                        cmd += ["--delta-psi-thresholds"] + ["%r" % t for t in self.delta_thresholds]
+                if n_diag:
                     dparts = ["%s.gpu%d" % (t, batch_num) for t, _ in self.diag_tables]
                     for (_, plist), dp in zip(self.diag_tables, dparts):
                         plist.append(dp)
@@ -318,6 +332,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
+        self.diag_tables += xtable
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -388,7 +403,8 @@ class GenesDispatcher(object):
 def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_len=1,
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
-                          labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False):
+                          labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
+                          exact_compare=False, delta_thresholds=None):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -400,7 +416,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            settings_fname=settings_fname, paired_end=paired_end, num_proc=num_proc,
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
-                           prefilter=prefilter, diagnostics=diagnostics, exact=exact).run()
+                           prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare,
+                           delta_thresholds=delta_thresholds).run()
 
 
 def main(argv=None):
@@ -431,6 +448,12 @@ def main(argv=None):
                     help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
                          "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
                          "other events are sampled as always.  Also the settings key `exact` under [sampler].")
+    ap.add_argument("--exact-compare", action="store_true",
+                    help="with --compare and the exact mode: also write OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf_exact -- "
+                         "for the events the exact mode took in both samples the Bayes factor and P(|delta Psi| >= T) come from the "
+                         "two posteriors' tables, without sampling error and whatever the seed; the .miso_bf table is unchanged")
+    ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
+                    help="the thresholds T of --exact-compare, each in (0, 1), at most four (default 0.1 0.2)")
     ap.add_argument("--compare", metavar="BAM2", default=None,
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
@@ -446,6 +469,21 @@ def main(argv=None):
     settings_filename = None if a.settings_filename is None else \
         os.path.abspath(os.path.expanduser(a.settings_filename))
     Settings.load(settings_filename)
+    if a.exact_compare:     # argument errors, before any work
+        if a.compare is None:
+            ap.error("--exact-compare goes with --compare")
+        if a.paired_end is not None:
+            ap.error("--exact-compare: the exact-posterior mode takes single-end events only")
+        if not (a.exact or Settings.get_exact()):
+            ap.error("--exact-compare needs the exact-posterior mode (--exact, or `exact = True` in the settings)")
+    if a.delta_psi_thresholds is not None:
+        if not a.exact_compare:
+            ap.error("--delta-psi-thresholds goes with --exact-compare")
+        from . import compare
+        try:
+            compare.check_delta_thresholds(a.delta_psi_thresholds)
+        except ValueError as err:
+            ap.error(str(err))
     if a.run is None:
         ap.print_help()
         return 0
@@ -466,7 +504,8 @@ def main(argv=None):
                                        compare_bam=None if a.compare is None else
                                        os.path.abspath(os.path.expanduser(a.compare)),
                                        labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics,
-                                       exact=a.exact)
+                                       exact=a.exact, exact_compare=a.exact_compare,
+                                       delta_thresholds=a.delta_psi_thresholds)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

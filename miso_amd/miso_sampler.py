@@ -413,7 +413,7 @@ class MISOSampler:
     def run_comparison_batch(self, num_iters, events1, events2, comparison_file, num_chains=6,
                              burn_in=1000, lag=2, seed=None, seed2=None, first_event_id=0,
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
-                             diagnostics_files=None):
+                             diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -423,7 +423,15 @@ class MISOSampler:
         full event list -- so that skipped events and chunking change nobody's random stream; default
         first_event_id + position among the events that are run.
         diagnostics_files (optional): (file1, file2), the chain diagnostics table (diagnostics.py) of each sample's
-        written events, from the samples resident on the device."""
+        written events, from the samples resident on the device.
+        exact_comparison_file (optional; the exact-posterior mode only): the `.miso_bf_exact` table of the exact comparison
+        (compare.write_exact_comparison) with P(|delta psi| >= t) for every t of delta_thresholds (default 0.1, 0.2)."""
+        xthr = None
+        if exact_comparison_file is not None:
+            if self.paired_end or not int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
+                raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
+            xthr = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
+        xrows = []
         if len(events1) != len(events2):
             raise ValueError("the two samples must list the same events")
         keep = []
@@ -447,6 +455,8 @@ class MISOSampler:
                 kw["diagnostics"] = True
             if not self.paired_end and int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
                 kw["exact"] = True          # the exact-posterior mode, as in prepare_batch
+            if xthr is not None:
+                kw["exact_compare"] = compare.delta_points(xthr)
             res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),
@@ -465,7 +475,11 @@ class MISOSampler:
                 if f1 is not None and f2 is not None:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
+                    if xthr is not None:
+                        xrows.append(rows[-1] + (res[-1][j],))
         compare.write_comparison(comparison_file, rows)
+        if xthr is not None:
+            compare.write_exact_comparison(exact_comparison_file, xrows, xthr)
         if diagnostics_files is not None:
             for f, drows in zip(diagnostics_files, diag_rows):
                 diagnostics.write_diagnostics(f, drows)

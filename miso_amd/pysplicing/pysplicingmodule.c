@@ -30,6 +30,8 @@
  *   first_event_id  global index of the first event (sharding a run over GPUs).
  *   exact=True      MISOBatch / MISOCompareBatch: the eligible single-end two-isoform events run no chain, their
  *                   samples are independent draws from the tabulated posterior of psi (miso_batch_set_exact).
+ *   exact_compare=(z, ...)  MISOCompareBatch with exact=True: the exact comparison (miso_batch_compare_exact) at these
+ *                   delta psi points, appended as the LAST element of the result.
  * The functions of the module that are not on the sampler path raise NotImplementedError.
  * The reference's stdout side effect `printf("no chains: %d\n")` (miso.c:837) is not reproduced.
  */
@@ -455,18 +457,31 @@ static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seed
 static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
-                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", NULL};
+                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
-  PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL;
+  PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL, *xcobj = NULL, *xc = NULL;
+  double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
   int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
   int start = MISO_START_AUTO, stop = MISO_STOP_FIXEDNO, rc;
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOpp", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppO", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
-                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact)) return NULL;
+                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj)) return NULL;
+  if (xcobj == Py_None) xcobj = NULL;
+  if (xcobj) {
+    Py_ssize_t nz;
+    if (!exact) { PyErr_SetString(PyExc_ValueError, "exact_compare requires exact=True"); return NULL; }
+    if (!PyTuple_Check(xcobj) || (nz = PyTuple_Size(xcobj)) > 8) {
+      PyErr_SetString(PyExc_ValueError, "exact_compare must be a tuple of at most 8 delta psi points"); return NULL;
+    }
+    for (n_xz = 0; n_xz < (int) nz; n_xz++) {
+      xz[n_xz] = PyFloat_AsDouble(PyTuple_GET_ITEM(xcobj, n_xz));
+      if (PyErr_Occurred()) return NULL;
+    }
+  }
   if (seedobj && seedobj != Py_None) { seed = PyLong_AsUnsignedLongLongMask(seedobj); if (PyErr_Occurred()) return NULL; }
   else if (default_seed(&seed)) return NULL;
   /* the two samples must not share random numbers: identical draws would correlate the chains */
@@ -520,8 +535,35 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   } else {
     out = Py_BuildValue("(OOO)", r1, r2, cmp);
   }
+  /* exact_compare=(z, ...): a last element, per event None (not exact-comparable) or (mean1, mean2, log_density_at_0,
+     bayes_factor, log10_bayes_factor, cdf at every z, sample 1's and sample 2's grid summary (mean, ci_low, ci_high)) */
+  if (out && xcobj) {
+    PyObject *one, *all;
+    if (n > 0 && (rc = miso_batch_compare_exact(b1, b2, xz, n_xz))) { raise_miso(rc); Py_CLEAR(out); goto done; }
+    if (!(xc = PyList_New(n))) { Py_CLEAR(out); goto done; }
+    for (i = 0; i < n; i++) {
+      double v[5], cdf[8], s[2][6]; int was = 0, w1 = 0, w2 = 0;
+      PyObject *t;
+      if ((rc = miso_batch_get_exact_comparison(b1, (int) i, v, v + 1, v + 2, v + 3, v + 4, cdf, &was))) {
+        raise_miso(rc); Py_CLEAR(out); goto done;
+      }
+      if (!was) { Py_INCREF(Py_None); PyList_SET_ITEM(xc, i, Py_None); continue; }
+      if ((rc = miso_batch_get_exact_summary(b1, (int) i, s[0], s[0] + 2, s[0] + 4, conf, &w1)) ||
+          (rc = miso_batch_get_exact_summary(b2, (int) i, s[1], s[1] + 2, s[1] + 4, conf, &w2))) {
+        raise_miso(rc); Py_CLEAR(out); goto done;
+      }
+      t = Py_BuildValue("(dddddN(NNN)(NNN))", v[0], v[1], v[2], v[3], v[4], from_doubles(cdf, n_xz),
+                        from_doubles(s[0], 2), from_doubles(s[0] + 2, 2), from_doubles(s[0] + 4, 2),
+                        from_doubles(s[1], 2), from_doubles(s[1] + 2, 2), from_doubles(s[1] + 4, 2));
+      if (!t) { Py_CLEAR(out); goto done; }
+      PyList_SET_ITEM(xc, i, t);
+    }
+    one = PyTuple_Pack(1, xc);
+    all = one ? PySequence_Concat(out, one) : NULL;
+    Py_XDECREF(one); Py_DECREF(out); out = all;
+  }
 done:
-  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg);
+  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc);
   if (b1) miso_batch_destroy(b1);
   if (b2) miso_batch_destroy(b2);
   return out;

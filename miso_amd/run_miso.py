@@ -317,7 +317,8 @@ def merge_tables(parts, filename, remove=True):
 def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, output_dir2,
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
-                     max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None):
+                     max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
+                     exact_comparison_file=None, delta_thresholds=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -326,13 +327,17 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     coverage filter entry k passes, "1", "2" or "1,2".  An entry is collected only in those samples; one that passes
     in one sample only is sampled there alone (with that sample's seed) and is not compared.
     diagnostics_files: (file1, file2), each sample's chain diagnostics table (diagnostics.py), parts merged like the
-    comparison's."""
+    comparison's.
+    exact_comparison_file (the exact mode only): the `.miso_bf_exact` table of the exact comparison (compare.py
+    write_exact_comparison), parts merged like the comparison's; delta_thresholds: its thresholds t of P(|delta psi| >= t)."""
     for d in (output_dir1, output_dir2):
         os.makedirs(d, exist_ok=True)
     if device is not None:
         _check_device(device)
         os.environ["MISO_DEVICE"] = str(int(device))
     exact = Settings.get_exact() if exact is None else bool(exact)
+    if exact_comparison_file is not None and (paired_end or not exact):
+        raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
     p = Settings.get_sampler_params()
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
     evs = []
@@ -347,6 +352,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     by_no2 = {e[4]: e for e in ev2}
     pairs = [(a, by_no2[a[4]]) for a in ev1 if a[4] in by_no2]
     parts = []
+    xparts = []
     diag_parts = ([], [])
     if paired_end:
         mean_frag_len = int(paired_end[0])
@@ -368,13 +374,20 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             dparts = tuple("%s.part%06d" % (f, lo) for f in diagnostics_files)
             for which in (0, 1):
                 diag_parts[which].append(dparts[which])
+        xpart = None
+        if exact_comparison_file is not None:
+            xpart = "%s.part%06d" % (exact_comparison_file, lo)
+            xparts.append(xpart)
         sampler.run_comparison_batch(p["num_iters"], [a[:3] for a, _ in chunk],
                                      [b[:3] for _, b in chunk], part, num_chains=p["num_chains"],
                                      burn_in=p["burn_in"], lag=p["lag"], seed=seed,
                                      first_event_id=first_event_id + lo, verbose=verbose,
                                      event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
-                                     diagnostics_files=dparts)
+                                     diagnostics_files=dparts, exact_comparison_file=xpart,
+                                     delta_thresholds=delta_thresholds)
     merge_tables(parts, comparison_file)
+    if exact_comparison_file is not None:
+        merge_tables(xparts, exact_comparison_file)
     if samples is not None:
         # sample 2's stream: the seed MISOCompareBatch derives for it (pysplicingmodule.c)
         seed2 = None if seed is None else (int(seed) ^ 0x5851F42D4C957F2D) & 0xFFFFFFFFFFFFFFFF
@@ -449,6 +462,11 @@ def main(argv=None):
     ap.add_argument("--exact", action="store_true",
                     help="single-end two-isoform events: independent draws from the exact posterior of Psi instead of chains "
                          "(also the settings key `exact`)")
+    ap.add_argument("--exact-comparison-file", default=None, metavar="F",
+                    help="with --compare-genes-from-file and the exact mode: also write the exact comparison's table "
+                         "(Bayes factors and P(|delta psi| >= T) from the posteriors' tables, no sampling error)")
+    ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
+                    help="the thresholds T of --exact-comparison-file, each in (0, 1), at most four (default 0.1 0.2)")
     ap.add_argument("--paired-end", nargs=2, type=float, metavar=("MEAN", "SD"))
     ap.add_argument("--read-len", type=int)
     ap.add_argument("--overhang-len", type=int)
@@ -472,6 +490,16 @@ def main(argv=None):
     if a.diagnostics_files and not a.compare_genes_from_file:
         print("Error: --diagnostics-files goes with --compare-genes-from-file.")
         return 1
+    if a.exact_comparison_file is not None:
+        if not a.compare_genes_from_file or paired_end or not exact:
+            print("Error: --exact-comparison-file goes with --compare-genes-from-file and the exact mode (single-end).")
+            return 1
+    if a.delta_psi_thresholds is not None:
+        try:
+            miso.compare.check_delta_thresholds(a.delta_psi_thresholds)
+        except ValueError as err:
+            print(err)
+            return 1
     if a.compare_genes_from_file:
         genes_filename, bam1, bam2, out1, out2, bf = (os.path.abspath(os.path.expanduser(x))
                                                      for x in a.compare_genes_from_file)
@@ -479,7 +507,10 @@ def main(argv=None):
         n = compare_gene_psi(entries, bam1, bam2, out1, out2, bf, a.read_len, overhang_len,
                              paired_end=paired_end, event_type=a.event_type, seed=a.seed,
                              first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
-                             samples=samples, diagnostics_files=a.diagnostics_files, exact=exact)
+                             samples=samples, diagnostics_files=a.diagnostics_files, exact=exact,
+                             exact_comparison_file=(os.path.abspath(os.path.expanduser(a.exact_comparison_file))
+                                                    if a.exact_comparison_file else None),
+                             delta_thresholds=a.delta_psi_thresholds)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
