@@ -260,6 +260,11 @@ int miso_selftest_format(const double *x, int n, int decimals, char *out, int st
  * miso.c:556-636): samples = noSamples columns of noiso values, column i from chain i % noChains; *stop = 1 converged.
  * Host arithmetic, no device needed. */
 int miso_selftest_convergent_mean(const double *samples, int noiso, int noChains, int noSamples, int *stop);
+/* tests: the planner's MISO_* tuning knobs as the next upload or launch would read them now (csrc/knobs.hpp Knobs::from_env):
+ * one "NAME=value" line per knob that is set -- a switch as 1, a number as parsed and clamped, a list with commas --
+ * NUL-terminated, cut at `cap` bytes.  Returns the bytes the whole text needs (buf may be NULL), -1 out of memory.
+ * No device needed. */
+int miso_selftest_knobs(char *buf, int cap);
 /* parity instrumentation: FNV-1a over every chain's per-iteration assignment counts
    (counts_hash: noChains words) and, if want_counts_trace, the counts themselves
    ((noIterations+1) x noChains x noiso int32, row m = counts the MH step of iteration m saw,

@@ -858,6 +858,16 @@ def selftest_convergent_mean(samples, chains):
     return bool(stop.value)
 
 
+def selftest_knobs():
+    """{name: value text} of the MISO_* tuning knobs that are set, as the planner would read them now (csrc/knobs.hpp)"""
+    need = lib().miso_selftest_knobs(None, 0)
+    if need < 0:
+        raise MemoryError("miso_selftest_knobs")
+    buf = C.create_string_buffer(need)
+    lib().miso_selftest_knobs(buf, need)
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
 def selftest_philox(ctr_key6):
     a = np.ascontiguousarray(ctr_key6, dtype=np.uint32).reshape(-1, 6)
     out = np.zeros((len(a), 4), np.uint32)

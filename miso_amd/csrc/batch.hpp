@@ -10,6 +10,7 @@
 
 #include "device.hpp"
 #include "host.hpp"
+#include "knobs.hpp"
 #include "plan.hpp"
 
 namespace miso {
@@ -74,6 +75,7 @@ constexpr int DIAG_MAX_CHAINS = 2048;
 
 struct miso_batch {
   miso_params_t p{};
+  miso::Knobs knobs;                     // the MISO_* environment as resolve_pending() / upload() / launch() last found it (knobs.hpp)
   miso::FragmentDist fd;                 // paired only
   std::vector<miso::PackedEvent> events;
   std::vector<int64_t> event_ids;        // per event: explicit Philox event id, -1 = first_event_id + index
@@ -105,7 +107,7 @@ struct miso_batch {
   int prio_lo = 0, prio_hi = 0;   // the device's stream priority range as this batch uses it (equal: priorities off)
   bool converged_done = false;    // stop = CONVERGENT_MEAN: this launch's further rounds have run (sync() is idempotent; launch() clears it)
   void converge_rounds(float *ms);
-  bool coop_enabled() const;      // chains may use several workgroups (coop.hpp): not after a time-out, not with MISO_NO_COOP=1
+  bool coop_enabled() const;      // chains may use several workgroups (coop.hpp): not after a time-out, not with knobs.no_coop
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // the shader clock of a launch (miso_batch_set_clock_probe; runtime.hip clock_probe_kernel)
@@ -281,12 +283,19 @@ struct miso_batch {
   // the parts of launch() (runtime.hip)
   void plan_sizes();
   void plan_k2(const miso::KernelArgs &a);
+  // a part of the two-isoform list as plan_lanes takes it: slots [first, first + count), the lanes per chain a run may have,
+  // the wavefronts of a workgroup-wide chain's and of the other workgroups, the workgroups resident at once, the chains per
+  // wavefront the LDS allows, the part's share of the cooperative workgroups
+  struct K2Part { int first, count; const int *widths; int n_widths; int wide_wpb = 0, wpb = 0, resident = 1, max_cpw = 64, coop_budget = 0; };
+  miso::LanePlan k2_lanes(const K2Part &pt, const std::vector<int> &nd, const miso::LaneCost &cost) const;
+  bool plan_k2_lanes(const K2Part &pt, bool forced, miso::LaneCost &cost, std::vector<int> &nd, miso::LanePlan &pl, long &pl_key);
   void k2_pair_table(const std::vector<int> &nd, const miso::LaneCost &cost);
   void plan_runs(const miso::KernelArgs &a);
+  int flat_wgs(int kc) const;
   void plan_flat(size_t ri);
   void plan_grp(size_t ri, const miso::KernelArgs &a);
   void group_runs();
-  void launch_planned(const miso::KernelArgs &a);
+  void launch_planned(const miso::KernelArgs &a, const miso::KernelArgs &k2a);
   template <class F> int fastest(const miso::KernelArgs &a, const std::vector<int> &cand, F &&trial);
   int slots_for(long chains) const;
   hipStream_t stream_for_next();

@@ -579,6 +579,14 @@ int miso_selftest_convergent_mean(const double *samples, int noiso, int noChains
   });
 }
 
+int miso_selftest_knobs(char *buf, int cap) {
+  try {
+    const std::string s = Knobs::from_env().dump();
+    if (buf && cap > 0) { std::snprintf(buf, static_cast<size_t>(cap), "%s", s.c_str()); }
+    return static_cast<int>(s.size()) + 1;
+  } catch (...) { return -1; }
+}
+
 int miso_batch_rounds(const miso_batch_t *b, int *rounds) {
   return guarded([&] { need(b, "batch"); need(rounds, "rounds"); *rounds = b->rounds; });
 }

@@ -120,7 +120,7 @@ int choose_lanes_per_chain(long chains, int max_quads, int wave_slots, int max_c
 
 using namespace miso;
 
-bool miso_batch::coop_enabled() const { return !no_coop && std::getenv("MISO_NO_COOP") == nullptr; }
+bool miso_batch::coop_enabled() const { return !no_coop && !knobs.no_coop; }
 
 void miso_batch::release() {
   if (device >= 0) (void) hipSetDevice(device);
@@ -155,7 +155,8 @@ void miso_batch::release() {
 // packs them (the same pack_event, fed with the match matrix those outputs stand for).
 void miso_batch::resolve_pending() {
   if (pending.empty()) return;
-  const bool timing = std::getenv("MISO_TIMING") != nullptr;
+  knobs = Knobs::from_env();
+  const bool timing = knobs.timing;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<double>(b - a).count(); };
@@ -306,12 +307,13 @@ void miso_batch::upload(int dev) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the sampler has no CPU path");
   device = dev;
   HIP_OK(hipSetDevice(dev));
+  knobs = Knobs::from_env();
   resolve_pending();
   {   // the reference's proposal density overflows beyond about 85 isoforms (miso.c:97-122: linear domain):
       // such a chain accepts its first proposal and nothing after -- bit-equal to the reference, not a posterior
     int wide = 0, kmax = 0;
     for (const PackedEvent &e : events) if (e.K > 80) { wide++; kmax = std::max(kmax, e.K); }
-    if (wide > 0 && std::getenv("MISO_QUIET") == nullptr)
+    if (wide > 0 && !knobs.quiet)
       std::fprintf(stderr, "[miso] warning: %d gene(s) of more than 80 isoforms (up to %d): as in the reference, the proposal density "
                            "(miso.c:97-122, linear domain) overflows beyond about 85 isoforms and the chains stop accepting after "
                            "their first iteration; the samples equal the reference's and are not a posterior\n", wide, kmax);
@@ -399,7 +401,7 @@ void miso_batch::upload(int dev) {
     hipDeviceProp_t prop;
     HIP_OK(hipGetDeviceProperties(&prop, dev));
     wave_slots = prop.multiProcessorCount * 4 * 2;  // CUs x SIMDs x resident sampler_k2 waves
-    if (const char *env = std::getenv("MISO_WAVE_SLOTS")) wave_slots = std::max(64, std::atoi(env));   // experiments: what the planners take as resident
+    if (knobs.wave_slots.set) wave_slots = knobs.wave_slots.v;
   }
   {
     // The batch's own stream carries its FIRST kernel -- the longest-running class of a whole-gene batch (runs are
@@ -407,13 +409,12 @@ void miso_batch::upload(int dev) {
     // priority (launch: stream_for_next), so that whenever a slot frees up the dispatcher takes a workgroup of the longest
     // class still waiting: longest first ACROSS the classes without one kernel holding all their bodies (that kernel was
     // built: 28 minutes of compilation, 800 spilled registers -- tools/experiments/grp_all/).  MEASURED, round 5, and OFF
-    // unless MISO_STREAM_PRIO=1: 16 384 genes of 3 - 20 isoforms x 1000 pairs 922 ms with against 917 ms without, hg19-like
+    // unless knobs.stream_prio: 16 384 genes of 3 - 20 isoforms x 1000 pairs 922 ms with against 917 ms without, hg19-like
     // pair counts 958 against 865 ms (the chains on several workgroups sit in the high-priority kernel and everything else
     // waits behind them) -- profiles/r05_stream_priorities.txt.
     int lo = 0, hi = 0;
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = hi = 0; (void) hipGetLastError(); }
-    const char *env = std::getenv("MISO_STREAM_PRIO");
-    prio_lo = lo; prio_hi = (env && std::atoi(env) != 0) ? hi : lo;
+    prio_lo = lo; prio_hi = knobs.stream_prio.on() ? hi : lo;
     if (prio_hi != prio_lo) HIP_OK(hipStreamCreateWithPriority(&stream, hipStreamDefault, prio_hi));
     else HIP_OK(hipStreamCreate(&stream));
   }
@@ -441,8 +442,8 @@ void miso_batch::build_slots() {
   // number of drawing reads so the chains sharing a wavefront loop equally long
   // (paired-end with a fragment-length distribution so wide that one chain's tables do not fit a CU's LDS -- sd beyond
   // ~400 -- : the two-isoform events take the general kernel, whose tables may stay in global memory, like the
-  // reference, which takes any sd, miso_paired.c:299-308; MISO_K2_GENERAL=1 forces it: tests)
-  k2_general = p.paired && (48 * fd.prob.size() + 64 > 150 * 1024 || std::getenv("MISO_K2_GENERAL") != nullptr);
+  // reference, which takes any sd, miso_paired.c:299-308; or knobs.k2_general)
+  k2_general = p.paired && (48 * fd.prob.size() + 64 > 150 * 1024 || knobs.k2_general);
   // (the exact-posterior mode, miso_batch_set_exact: its eligible events leave both lists for one of their own)
   std::vector<int32_t> k2, gen, ex;
   is_exact.assign(n, 0);
@@ -456,8 +457,8 @@ void miso_batch::build_slots() {
       is_exact[i] = exact_eligible(false, 2, events[i].eff.data(), events[i].hyper.data());
     }
   for (int i = 0; i < n; i++) (is_exact[i] ? ex : (events[i].K == 2 && !k2_general) ? k2 : gen).push_back(i);
-  // (paired-end: the events sampler_k2's MODE 2 can take come first, MISO_NO_PE_DELTA=1 sends all to MODE 1)
-  use_delta = std::getenv("MISO_NO_PE_DELTA") == nullptr;   // fixed here: the slot order depends on it
+  // (paired-end: the events sampler_k2's MODE 2 can take come first)
+  use_delta = !knobs.no_pe_delta;   // fixed here: the slot order depends on it
   // (Round 5 tried ordering a collapsed batch's list by the binomial's likely regime -- inversion below n min(p, q) = 10, BTRS
   // above: a wavefront that holds chains of both runs both -- and measured nothing once the inversion had lost its division:
   // 50.3 - 50.8 ms against 50.1 - 50.6 ms, profiles/r05_sampler_lane_ilp.txt.)
@@ -476,21 +477,18 @@ void miso_batch::build_slots() {
   // wavefront of its own (sampler_grp<64, true, KC>); beyond: one chain per workgroup (256 lanes, kernels_grp.inl WIDE
   // -- its four wavefronts each repeat the chain's Metropolis-Hastings step, so only where the read loop dominates);
   // beyond 384: several workgroups (coop.hpp), one per 256 lanes needed.  Never more lanes than the gene has pairs of
-  // quads.  Thresholds measured: profiles/r03_pe_buckets.txt.  MISO_NO_PE_BUCKETS=1: one launch per class as before
-  // (A/B, tests); MISO_PE_T_WAVE / MISO_PE_T_WIDE: the two thresholds (experiments, tests).
+  // quads.  Thresholds measured: profiles/r03_pe_buckets.txt (knobs.no_pe_buckets, pe_t_wave, pe_t_wide).
   // (64: 33 ... MISO_MAX_ISOFORMS isoforms -- sampler_wave only, lane k = isoform k; the reference has no limit, miso.c:696)
   // (256: 65 ... MISO_MAX_ISOFORMS isoforms -- sampler_big, the chain's vectors in LDS, kernels_big.hip)
   auto kc_of = [](int K) { return K <= 4 ? 4 : (K <= 8 ? 8 : (K <= 12 ? 12 : (K <= 16 ? 16 : (K <= 32 ? 32 : (K <= 64 ? 64 : 256))))); };
   std::vector<int> bucket(n, 0);   // 0 normal, 1 at least 32 lanes, 2 a wavefront, 3 workgroup-wide (coop_n[event] workgroups)
   coop_n.assign(n, 1);
-  if (p.paired && std::getenv("MISO_NO_PE_BUCKETS") == nullptr) {
+  if (p.paired && !knobs.no_pe_buckets) {
     double W = 0;
     for (int i : gen) W += static_cast<double>((events[i].n_draw + 3) / 4) * events[i].K;
     const double device_lanes = 2048.0 * 64.0;
-    const double share_factor = std::getenv("MISO_PE_SHARE") ? std::atof(std::getenv("MISO_PE_SHARE")) : 2.0;
-    const double t_wave = std::getenv("MISO_PE_T_WAVE") ? std::atof(std::getenv("MISO_PE_T_WAVE")) : 64.0;
-    const double t_wide = std::getenv("MISO_PE_T_WIDE") ? std::atof(std::getenv("MISO_PE_T_WIDE")) : 256.0;
-    const bool dense_ok = std::getenv("MISO_NO_PE_DENSE") == nullptr;
+    const double share_factor = knobs.pe_share.v, t_wave = knobs.pe_t_wave.v, t_wide = knobs.pe_t_wide.v;
+    const bool dense_ok = !knobs.no_pe_dense;
     const bool coop_on = coop_enabled();
     // "at least 32 lanes" from a need of 24 lanes in a batch with a heavy tail (some gene needs a wavefront or more), from 32
     // in a batch of like-sized genes, where a 20-isoform gene of 1000 pairs needs 28 by the share rule and runs better on
@@ -498,7 +496,7 @@ void miso_batch::build_slots() {
     // profiles/r05_pe_mix_lanes.txt)
     double max_need = 0.0;
     for (int i : gen) max_need = std::max(max_need, W > 0 ? share_factor * device_lanes * (static_cast<double>((events[i].n_draw + 3) / 4) * events[i].K) / W : 0.0);
-    const double t_32 = std::getenv("MISO_PE_T_32") ? std::atof(std::getenv("MISO_PE_T_32")) : (max_need > t_wave ? 24.0 : 32.0);
+    const double t_32 = knobs.pe_t_32.set ? knobs.pe_t_32.v : (max_need > t_wave ? 24.0 : 32.0);
     for (int i : gen) {
       const PackedEvent &e = events[i];
       const int nq = (e.n_draw + 3) / 4;
@@ -513,9 +511,8 @@ void miso_batch::build_slots() {
     }
     // (round 6) ... and the SMALL genes of a batch of several classes: eight lanes per chain -- a gene of a hundred pairs is all
     // scalar step, which eight chains of a wavefront share instead of four (16 384 genes of 3 - 8 isoforms x 100 / 250 / 500 pairs:
-    // 198.5 -> 147.4, 237.3 -> 190.3, 306.2 -> 291.8 ms; profiles/r06_small_genes.txt).  MISO_PE_T_SMALL: drawing quads up to which
-    // (0: none; experiments, tests).
-    const int t_small = std::getenv("MISO_PE_T_SMALL") ? std::atoi(std::getenv("MISO_PE_T_SMALL")) : 96;
+    // 198.5 -> 147.4, 237.3 -> 190.3, 306.2 -> 291.8 ms; profiles/r06_small_genes.txt).
+    const int t_small = knobs.pe_t_small.v;
     bool classes2 = false;
     for (int i : gen) classes2 |= kc_of(events[i].K) != kc_of(events[gen[0]].K);
     if (classes2 && t_small > 0 && dense_ok)
@@ -713,6 +710,7 @@ std::string miso_batch::run_name(size_t ri) const {   // the kernel general run 
 void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   if (!uploaded) MISO_FAIL(MISO_EINVAL, "batch not uploaded");
   HIP_OK(hipSetDevice(device));
+  knobs = Knobs::from_env();
   if (slots_exact != exact) {   // miso_batch_set_exact after the upload: the launch lists anew
     HIP_OK(hipStreamSynchronize(stream));
     for (GenRun &r : gen_runs) { r.wave_tab.reset(); r.coop.reset(); }
@@ -724,8 +722,8 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   a.il = static_cast<int>(fd.prob.size()); a.n_events = n;
   a.C = p.noChains; a.M = p.noIterations; a.B = p.noBurnIn; a.lag = p.noLag;
   a.start = p.start; a.first_event_id = first_event_id; a.seed = seed;
-  a.balance = (std::getenv("MISO_PRIO_QUARTILES") && std::atoi(std::getenv("MISO_PRIO_QUARTILES")) != 0) ? 2 : 0;   // experiment: device.hpp prio_by_progress
-  a.wide_dedup = (std::getenv("MISO_K2_WIDE_DEDUP") && std::atoi(std::getenv("MISO_K2_WIDE_DEDUP")) == 0) ? 0 : 1;   // kernels_k2.inl: a workgroup-wide chain's Metropolis-Hastings step on four of its eight wavefronts
+  a.balance = knobs.prio_quartiles.on() ? 2 : 0;   // device.hpp prio_by_progress
+  a.wide_dedup = knobs.k2_wide_dedup.off() ? 0 : 1;
   a.round_tab = nullptr;
   if (!round_starts.empty()) {   // a later round of stop = CONVERGENT_MEAN (converge_rounds): where the rounds after the first open
     std::vector<int32_t> tab(MISO_MAX_ROUNDS);
@@ -736,9 +734,12 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   last_seed = seed; last_first_event_id = first_event_id;
   converged_done = false;
   if (probe_armed) { HIP_OK(hipStreamSynchronize(probe_stream)); probe_armed = false; }   // (a launch nobody waited for)
-  a.pe_force_exact = std::getenv("MISO_K2_SETTLE_ALL") != nullptr;   // tests (kernels_k2.inl: the rescan for high halves on the threshold)
-  a.k2_full_math = std::getenv("MISO_K2_FULL_MATH") != nullptr;   // tests (detmath_n.hpp: the step's exp / log with their special cases at every call)
-  if (const char *env = std::getenv("MISO_COOP_MAX_POLLS")) a.coop_max_polls = static_cast<uint32_t>(std::max(1L, std::atol(env)));   // tests
+  a.k2_full_math = knobs.k2_full_math;
+  if (knobs.coop_max_polls.set) a.coop_max_polls = static_cast<uint32_t>(knobs.coop_max_polls.v);
+  // (one word, two readers: the general paired-end kernels' exact scan, the two-isoform kernels' rescan -- device.hpp)
+  a.pe_force_exact = knobs.pe_force_exact;
+  KernelArgs k2a = a;                    // what the two-isoform part is planned and launched with
+  k2a.pe_force_exact = knobs.k2_settle_all;
   // Trailing sample columns stay 0 (miso.c:661, quirk C8) -- they exist only when the lag does not divide the kept
   // iterations; otherwise the kernels overwrite every sample, log score, pick and statistic of the pool, and clearing
   // 4.8 GB per launch (0.75 ms of the headline's 102 ms step) is for the first launch only.
@@ -755,7 +756,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   const bool marginal = !p.paired && (p.algorithm == MISO_ALGO_MARGINAL || p.algorithm == MISO_ALGO_CLASSES);
   if (!marginal) {
     plan_sizes();
-    plan_k2(a);
+    plan_k2(k2a);
     plan_runs(a);
     group_runs();
     plan.sampled = true;
@@ -773,11 +774,11 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
     if (chains > 0) launch_kernel(fn(&sampler_marginal), static_cast<unsigned>((chains + lanes - 1) / lanes), lanes, marginal_lds_bytes(ks, lanes), stream, ka);
     last_kernels = "sampler_marginal";
   } else {
-    launch_planned(a);
+    launch_planned(a, k2a);
     if (n_exact > 0) launch_exact(a);
   }
   // kernel i > 0 went to its own stream, forked from the batch's stream: joined back into it
-  for (size_t i = 1; i < kernel_no && i <= aux_streams.size() && std::getenv("MISO_SERIAL_KERNELS") == nullptr; i++) {
+  for (size_t i = 1; i < kernel_no && i <= aux_streams.size() && !knobs.serial_kernels; i++) {
     HIP_OK(hipEventRecord(aux_done[i - 1], aux_streams[i - 1]));
     HIP_OK(hipStreamWaitEvent(stream, aux_done[i - 1], 0));
   }
@@ -790,8 +791,8 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
 void miso_batch::plan_sizes() {
   LaunchPlan &q = plan;
   // a workgroup may use half of the CU's 160 KB of LDS (two workgroups per CU)
-  // MISO_LDS_MAX_KB (experiments): a larger cap lets one workgroup per CU hold more chains per wavefront
-  q.lds_max = (std::getenv("MISO_LDS_MAX_KB") ? std::atoi(std::getenv("MISO_LDS_MAX_KB")) : 80) * 1024;
+  // (knobs.lds_max_kb: a larger cap lets one workgroup per CU hold more chains per wavefront)
+  q.lds_max = knobs.lds_max_kb.v * 1024;
   const int il = static_cast<int>(fd.prob.size());
   q.k2_fp = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
   q.k2_tab = p.paired ? 2 * fd.prob.size() * 4 : 0;   // per chain: int32[2 x il]
@@ -802,8 +803,8 @@ void miso_batch::plan_sizes() {
   q.k2w_tab = p.paired ? static_cast<size_t>(pe_k2_entries(il)) * 4 : 0;
   q.fp_plain = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
   // paired-end dense path (pe_dense): byte records, the probability table with its two extra entries, the
-  // score table with rows of il + 2; MISO_NO_PE_DENSE=1 (tests, A/B): the quad loops over the plain records
-  q.dense_env = std::getenv("MISO_NO_PE_DENSE") == nullptr;
+  // score table with rows of il + 2
+  q.dense_env = !knobs.no_pe_dense;
   q.il2 = pe_dense_il2(il);
   // A batch with several kernels (two-isoform events + one general kernel per isoform-count class)
   // runs them CONCURRENTLY, one stream each: every kernel then only has its share of the device to
@@ -816,10 +817,10 @@ void miso_batch::plan_sizes() {
   // (chains, isoforms, reads, LDS per workgroup), so the first launch of a large single-end batch
   // with more than two isoforms times a few iterations of the rule of thumb's choice and of the next
   // larger ones on the batch itself and keeps the fastest (K=5: 58k -> 81k events/s) (the trial launches record nothing: burn-in = their length; what they leave in the
-  // output pool is rewritten by the real launch).  MISO_NO_AUTOTUNE=1 keeps the rule of thumb.
-  const bool tune = std::getenv("MISO_NO_AUTOTUNE") == nullptr && p.noIterations >= 2000;   // ~400 trial iterations: <= 20 % of a one-shot run
+  // output pool is rewritten by the real launch).
+  const bool tune = !knobs.no_autotune && p.noIterations >= 2000;   // ~400 trial iterations: <= 20 % of a one-shot run
   q.tune_runs = tune && q.n_kernels <= 1;   // trial launches would time a kernel alone
-  // (workgroup-wide chains may use several workgroups, coop.hpp; MISO_NO_COOP=1: their own only)
+  // (workgroup-wide chains may use several workgroups, coop.hpp)
   q.coop_max = coop_enabled() ? COOP_MAX_N : 1;
 }
 
@@ -853,22 +854,49 @@ template <class F> int miso_batch::fastest(const KernelArgs &a, const std::vecto
 }
 
 // ---- the two-isoform part: sampler_k2<G> and its relatives ----
+// lanes per chain a run of sampler_k2_multi may have: single-end, paired-end
+static constexpr int K2_WIDTHS_SE[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 32, 64}, K2_WIDTHS_PE[] = {4, 8, 16, 32, 64};
+
+// plan_lanes for a part of the two-isoform list (batch.hpp K2Part) under this launch's knobs: knobs.k2_target forces the
+// bound on a wavefront's step
+LanePlan miso_batch::k2_lanes(const K2Part &pt, const std::vector<int> &nd, const LaneCost &cost) const {
+  return plan_lanes(nd.data(), pt.count, p.noChains, pt.widths, pt.n_widths, pt.wide_wpb, pt.wpb, pt.resident, pt.max_cpw, cost,
+                    knobs.k2_target.v, plan.coop_max, pt.coop_budget);
+}
+
+// The lane plan of one part into `pl`, unless `pl` still holds the one made for the same key: the resident workgroups, the
+// chains and the cooperative budget.  A knob the key does not carry (knobs.replan_k2(), the caller's `forced`) plans anew
+// at every launch.  `cost`: the part's cost model, here overridden by knobs.k2_cost and knobs.coop_min_quads.  True when
+// it planned: `nd` then holds the slots' drawing reads, for what the caller plans further.
+bool miso_batch::plan_k2_lanes(const K2Part &pt, bool forced, LaneCost &cost, std::vector<int> &nd, LanePlan &pl, long &pl_key) {
+  const long key = (static_cast<long>(pt.resident) * 64 + p.noChains) * 256 + pt.coop_budget + (plan.coop_max > 1 ? 0 : 200);
+  if (pl_key == key && !forced && !knobs.replan_k2()) return false;
+  double *const c[5] = {&cost.block, &cost.step[1], &cost.step[2], &cost.step[3], &cost.step[4]};
+  for (size_t i = 0; i < knobs.k2_cost.size(); i++) *c[i] = knobs.k2_cost[i];
+  if (knobs.coop_min_quads.set) cost.coop_min_quads = knobs.coop_min_quads.v;
+  nd.resize(pt.count);
+  for (int i = 0; i < pt.count; i++) nd[i] = events[h_slots[pt.first + i]].n_draw;
+  pl = k2_lanes(pt, nd, cost);
+  pl_key = key;
+  return true;
+}
+
 void miso_batch::plan_k2(const KernelArgs &a) {
   LaunchPlan &q = plan;
   const size_t LDS_MAX = q.lds_max;
   // (only when the batch's wavefronts fit the resident slots once: with several rounds the hardware hands
   // out workgroups as slots free up, heaviest first, and the 4-wavefront workgroups balance better --
   // MISO defaults, 6 chains x 40 000 events at one lane per chain: 374 ms paired, 351 ms unpaired)
-  q.k2_pair = !p.paired && !(std::getenv("MISO_K2_PAIR") && std::atoi(std::getenv("MISO_K2_PAIR")) == 0);
+  q.k2_pair = !p.paired && !knobs.k2_pair.off();
   if (n_k2 - n_k2w > 0) {
     const long chains = static_cast<long>(n_k2 - n_k2w) * p.noChains;
     const int maxq = p.paired ? (events[k2_first_event()].n_draw + 3) / 4 : (events[k2_first_event()].n_draw + 7) / 8;   // Philox blocks
     const int max_cpw = p.paired ? std::max<int>(1, static_cast<int>((60 * 1024 - q.k2_fp) / (4 * q.k2_tab))) : 64;
-    if (const char *env = std::getenv("MISO_LANES_PER_CHAIN")) q.k2_G = std::atoi(env);
+    if (knobs.lanes_per_chain.set) q.k2_G = knobs.lanes_per_chain.v;
     else if (tuned_k2_G) q.k2_G = tuned_k2_G;
     else {
       q.k2_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
-      if (q.tune_runs && chains >= 4096 && std::getenv("MISO_AUTOTUNE_K2") != nullptr) {   // the rule is the measured optimum
+      if (q.tune_runs && chains >= 4096 && knobs.autotune_k2) {   // the rule is the measured optimum
         static const int kG[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32, 64};
         std::vector<int> cand{q.k2_G};
         for (int i = 0; i < 15; i++)
@@ -888,30 +916,29 @@ void miso_batch::plan_k2(const KernelArgs &a) {
     const int maxq = (events[k2_first_event()].n_draw + 3) / 4;
     const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp);
     const int max_cpw = static_cast<int>(std::max<long>(1, lds_left / static_cast<long>(4 * q.k2w_tab)));
-    if (const char *env = std::getenv("MISO_LANES_PER_CHAIN")) {
-      q.k2w_G = std::atoi(env);
+    if (knobs.lanes_per_chain.set) {
+      q.k2w_G = knobs.lanes_per_chain.v;
       if (q.k2w_G < 1 || q.k2w_G > 64) MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
     } else q.k2w_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
     while (q.k2w_G < 64 && static_cast<size_t>(64 / q.k2w_G) > static_cast<size_t>(max_cpw)) q.k2w_G *= 2;   // a forced choice never exceeds the LDS
   }
   if (q.k2_pair && q.k2_G > 0) {
     const long waves = (static_cast<long>(n_k2 - n_k2w) * p.noChains + 64 / q.k2_G - 1) / (64 / q.k2_G);
-    q.k2_pair = waves <= wave_slots || std::getenv("MISO_K2_PAIR") != nullptr;
+    q.k2_pair = waves <= wave_slots || knobs.k2_pair.set;
   }
   // ---- single-end two-isoform events in one launch with two lane widths (sampler_k2_mix, kernels_k2.hip) ----
   // Only when the batch runs as ONE round of paired 8-wavefront workgroups (k2_pair) that does not fill the CUs:
   // the heaviest events get G + 1 lanes per chain, as many of them as still leave one CU per workgroup.
-  // MISO_K2_MIX=0 switches it off (A/B), MISO_K2_SPLIT=n forces the number of events of the wide part.
+  // (knobs.k2_mix switches it off, knobs.k2_split forces the number of events of the wide part.)
   {
     const int count = n_k2 - n_k2w, C = p.noChains, G = q.k2_G;
-    const char *off = std::getenv("MISO_K2_MIX");
-    if (!p.paired && q.k2_pair && count > 0 && G >= 1 && G <= 7 && q.n_kernels <= 1 && !(off && std::atoi(off) == 0)) {
+    if (!p.paired && q.k2_pair && count > 0 && G >= 1 && G <= 7 && q.n_kernels <= 1 && !knobs.k2_mix.off()) {
       const int cus = wave_slots / 8, cpwA = 64 / (G + 1), cpwB = 64 / G;
       auto blocks = [&](long chains, int cpw) { return static_cast<int>(((chains + cpw - 1) / cpw + 7) / 8); };
       auto total = [&](int y) { return blocks(static_cast<long>(y) * C, cpwA) + blocks(static_cast<long>(count - y) * C, cpwB); };
       if (total(0) < cus && blocks(static_cast<long>(count) * C, cpwB) * 8 >= wave_slots / 2) {
         int y = 0;
-        if (const char *env = std::getenv("MISO_K2_SPLIT")) y = std::max(0, std::min(count - 1, std::atoi(env)));
+        if (knobs.k2_split.set) y = std::max(0, std::min(count - 1, knobs.k2_split.v));
         else {
           int lo = 0, hi = count - 1;          // total(y) grows with y: the largest y that still fits
           while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (total(mid) <= cus) lo = mid; else hi = mid - 1; }
@@ -923,10 +950,9 @@ void miso_batch::plan_k2(const KernelArgs &a) {
   }
 
   // ---- single-end two-isoform events: a lane width per event (sampler_k2_multi, kernels_k2m.hip) ----
-  // Default for single-end batches; MISO_K2_MULTI=0 (A/B, tests) or a forced MISO_LANES_PER_CHAIN: the
-  // single-width / two-width launches above.  The plan depends on the list, the chains and this kernel's share of
-  // the device only: made once per upload.  MISO_K2_COST="block,step1,step2,step3,step4" overrides the cost model,
-  // MISO_K2_TARGET=x forces the bound on a wavefront's step (tests: small batches with many widths).
+  // Default for single-end batches; knobs.k2_multi off or a forced knobs.lanes_per_chain: the single-width / two-width
+  // launches above.  The plan depends on the list, the chains and this kernel's share of the device only: made once per
+  // upload (plan_k2_lanes).
   const int coop_max = q.coop_max;
   // All cooperative workgroups of ONE launch() -- the gene runs' (wide_setup) and the two-isoform plans' -- come out of one
   // budget of COOP_MAX_WGS (coop.hpp): the gene runs take what upload() asked for, at most 5/8 when two-isoform events are
@@ -936,7 +962,7 @@ void miso_batch::plan_k2(const KernelArgs &a) {
   {
     long want = 0;
     for (int i = 0; i < n_gen; i++) { const int ev_i = h_slots[n_k2 + i]; if (coop_n[ev_i] > 1) want += static_cast<long>(coop_n[ev_i]) * p.noChains; }
-    if (std::getenv("MISO_COOP_DRAWS") && p.paired && n_gen > 0) want = COOP_MAX_WGS;   // (tests: the table decides chain by chain)
+    if (knobs.coop_draws.set && p.paired && n_gen > 0) want = COOP_MAX_WGS;   // (the table decides chain by chain)
     const long cap = n_k2 > 0 ? COOP_MAX_WGS * 5 / 8 : COOP_MAX_WGS;
     coop_gen_budget = coop_max > 1 ? static_cast<int>(std::min(want, cap)) : 0;
     const int left = COOP_MAX_WGS - coop_gen_budget;
@@ -948,58 +974,47 @@ void miso_batch::plan_k2(const KernelArgs &a) {
   // lanes per chain of the collapsed step: one (sampler_lane).  Sharing a chain between 2, 4 or 8 lanes (sampler_k2c:
   // the Metropolis-Hastings step's transcendentals one per lane, the binomial's rejection trials G at a time) brings more
   // wavefronts but the same instructions per wavefront -- 40 000 chains: 56.4 ms on one lane, 58.5 / 59.1 / 86.3 ms on
-  // 2 / 4 / 8 (profiles/r03_collapsed.txt); MISO_COLLAPSED_LANES forces (experiments, tests)
-  if (q.lane_route) {
-    if (const char *f = std::getenv("MISO_COLLAPSED_LANES")) { const int g = std::atoi(f); if (g == 1 || g == 2 || g == 4 || g == 8) q.lane_G = g; }
+  // 2 / 4 / 8 (profiles/r03_collapsed.txt); knobs.collapsed_lanes forces
+  if (q.lane_route && knobs.collapsed_lanes.set) {
+    const int g = knobs.collapsed_lanes.v;
+    if (g == 1 || g == 2 || g == 4 || g == 8) q.lane_G = g;
   }
   // one chain per lane, up to two wavefronts per SIMD: the form that overlaps a chain's own work (kernels_lane.hip
-  // sampler_lane_ilp); beyond, the lean one (six wavefronts per SIMD hide each other's latencies).  MISO_LANE_ILP=0 / 1 forces.
+  // sampler_lane_ilp); beyond, the lean one (six wavefronts per SIMD hide each other's latencies); knobs.lane_ilp forces.
   if (q.lane_route && q.lane_G == 1) {
     q.lane_ilp = ((static_cast<long>(n_k2) * p.noChains + 255) / 256) * 4 <= wave_slots;
-    if (const char *env = std::getenv("MISO_LANE_ILP")) q.lane_ilp = std::atoi(env) != 0;
+    if (knobs.lane_ilp.set) q.lane_ilp = knobs.lane_ilp.v != 0;
   }
+  const bool multi = !knobs.lanes_per_chain.set && !knobs.k2_multi.off();
+  std::vector<int> nd;
   {
     const int count = n_k2 - n_k2w;
-    const char *off = std::getenv("MISO_K2_MULTI");
     // paired-end events that keep MODE 1 (a drawing read touches a non-finite score): the same, 4-wavefront workgroups,
     // 4 ... 64 lanes as far as the chains' tables (2 il int32 each) fit the LDS, 256-lane chains
     const long pe1_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2_fp) - K2_RED_BYTES;
     const int pe1_cpw = p.paired ? static_cast<int>(std::max<long>(0, pe1_left / static_cast<long>(4 * std::max<size_t>(q.k2_tab, 1)))) : 64;
-    if (p.paired && count > 0 && pe1_cpw >= 1 && std::getenv("MISO_LANES_PER_CHAIN") == nullptr && !(off && std::atoi(off) == 0)) {
-      const int resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 4);
-      const long key = (static_cast<long>(resident) * 64 + p.noChains) * 256 + coop_k2_budget + (coop_max > 1 ? 0 : 200);
-      if (k2_plan_key != key || std::getenv("MISO_K2_TARGET") || std::getenv("MISO_K2_COST") || std::getenv("MISO_COOP_MIN_QUADS")) {
-        static const int widths[] = {4, 8, 16, 32, 64};
-        LaneCost cost = k2_cost_paired();
-        if (const char *env = std::getenv("MISO_COOP_MIN_QUADS")) cost.coop_min_quads = std::max(1, std::atoi(env));
-        std::vector<int> nd(count);
-        for (int i = 0; i < count; i++) nd[i] = events[h_slots[n_k2w + i]].n_draw;
-        const double forced = std::getenv("MISO_K2_TARGET") ? std::atof(std::getenv("MISO_K2_TARGET")) : 0.0;
-        k2_plan = plan_lanes(nd.data(), count, p.noChains, widths, 5, 4, 4, resident, pe1_cpw, cost, forced, coop_max, coop_k2_budget);
-        k2_plan_key = key;
-      }
+    if (p.paired && count > 0 && pe1_cpw >= 1 && multi) {
+      K2Part pt{n_k2w, count, K2_WIDTHS_PE, 5};
+      pt.wide_wpb = pt.wpb = 4; pt.max_cpw = pe1_cpw; pt.coop_budget = coop_k2_budget;
+      pt.resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 4);
+      LaneCost cost = k2_cost_paired();
+      plan_k2_lanes(pt, false, cost, nd, k2_plan, k2_plan_key);
       q.k2_multi = k2_plan.n_segs > 0;
     }
-    if (!p.paired && count > 0 && std::getenv("MISO_LANES_PER_CHAIN") == nullptr && !(off && std::atoi(off) == 0)) {
-      const int resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 8);
-      const long key = (static_cast<long>(resident) * 64 + p.noChains) * 256 + coop_k2_budget + (coop_max > 1 ? 0 : 200);
-      if (k2_plan_key != key || std::getenv("MISO_K2_TARGET") || std::getenv("MISO_K2_COST") || std::getenv("MISO_COOP_MIN_QUADS") || std::getenv("MISO_K2_WPB")) {
-        static const int widths[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 32, 64};
-        LaneCost cost = k2_cost_single();
-        if (const char *env = std::getenv("MISO_K2_COST"))
-          std::sscanf(env, "%lf,%lf,%lf,%lf,%lf", &cost.block, &cost.step[1], &cost.step[2], &cost.step[3], &cost.step[4]);
-        if (const char *env = std::getenv("MISO_COOP_MIN_QUADS")) cost.coop_min_quads = std::max(1, std::atoi(env));
-        std::vector<int> nd(count);
-        for (int i = 0; i < count; i++) nd[i] = events[h_slots[n_k2w + i]].n_draw;
-        const double forced = std::getenv("MISO_K2_TARGET") ? std::atof(std::getenv("MISO_K2_TARGET")) : 0.0;
-        k2_plan = plan_lanes(nd.data(), count, p.noChains, widths, 12, 8, 8, resident, 64, cost, forced, coop_max, coop_k2_budget);
+    if (!p.paired && count > 0 && multi) {
+      K2Part pt{n_k2w, count, K2_WIDTHS_SE, 12};
+      pt.wide_wpb = pt.wpb = 8; pt.max_cpw = 64; pt.coop_budget = coop_k2_budget;
+      pt.resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 8);
+      LaneCost cost = k2_cost_single();
+      if (knobs.k2_wpb.set && knobs.k2_wpb.v != 8 && knobs.k2_wpb.v != 4 && knobs.k2_wpb.v != 1) MISO_FAIL(MISO_EINVAL, "MISO_K2_WPB must be 8, 4 or 1");
+      if (plan_k2_lanes(pt, knobs.k2_wpb.set, cost, nd, k2_plan, k2_plan_key)) {
         // several rounds: smaller workgroups (a workgroup starts when ALL its wavefronts' slots are free; with 8 the
         // slots of early finishers idle: MISO defaults on 40 000 events 425 ms, with 4: see profiles/r03_k2_multi_ab.txt)
-        int wpb = k2_plan.rounds == 1 ? 8 : 4;
-        if (const char *env = std::getenv("MISO_K2_WPB")) wpb = std::atoi(env);
-        if (wpb != 8 && wpb != 4 && wpb != 1) MISO_FAIL(MISO_EINVAL, "MISO_K2_WPB must be 8, 4 or 1");
-        if (wpb != 8) k2_plan = plan_lanes(nd.data(), count, p.noChains, widths, 12, wpb >= 4 ? wpb : 0, wpb, resident * 8 / wpb, 64, cost, forced, coop_max, coop_k2_budget);
-        k2_plan_key = key;
+        const int wpb = knobs.k2_wpb.set ? knobs.k2_wpb.v : (k2_plan.rounds == 1 ? 8 : 4);
+        if (wpb != 8) {
+          pt.wide_wpb = wpb >= 4 ? wpb : 0; pt.wpb = wpb; pt.resident = pt.resident * 8 / wpb;
+          k2_plan = k2_lanes(pt, nd, cost);
+        }
         k2_pair_grid = 0; k2_pair_wide_blocks = 0;
         if (wpb == 8) k2_pair_table(nd, cost);
       }
@@ -1008,45 +1023,32 @@ void miso_batch::plan_k2(const KernelArgs &a) {
   }
   // ---- paired-end two-isoform events of MODE 2, likewise (sampler_k2_multi<2, 4>): 4, 8, ... 64 lanes per chain as far
   // as the chains' score tables fit the workgroup's LDS, 256 lanes (the workgroup) for the largest events ----
-  {
-    const char *off = std::getenv("MISO_K2_MULTI");
-    if (p.paired && n_k2w > 0 && std::getenv("MISO_LANES_PER_CHAIN") == nullptr && !(off && std::atoi(off) == 0)) {
-      const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp) - K2_RED_BYTES;
-      const int max_cpw = static_cast<int>(std::max<long>(0, lds_left / static_cast<long>(4 * q.k2w_tab)));
-      const int resident = std::max(1, slots_for(static_cast<long>(n_k2w) * p.noChains) / 4);
-      const long key = (static_cast<long>(resident) * 64 + p.noChains) * 256 + coop_k2w_budget + (coop_max > 1 ? 0 : 200);
-      if (max_cpw >= 1 && (k2w_plan_key != key || std::getenv("MISO_K2_TARGET") || std::getenv("MISO_K2_COST") || std::getenv("MISO_COOP_MIN_QUADS") || std::getenv("MISO_K2W_WPB"))) {
-        static const int widths[] = {4, 8, 16, 32, 64};
-        LaneCost cost = k2_cost_paired();
-        if (const char *env = std::getenv("MISO_K2_COST"))
-          std::sscanf(env, "%lf,%lf,%lf,%lf,%lf", &cost.block, &cost.step[1], &cost.step[2], &cost.step[3], &cost.step[4]);
-        if (const char *env = std::getenv("MISO_COOP_MIN_QUADS")) cost.coop_min_quads = std::max(1, std::atoi(env));
-        std::vector<int> nd(n_k2w);
-        for (int i = 0; i < n_k2w; i++) nd[i] = events[h_slots[i]].n_draw;
-        const double forced = std::getenv("MISO_K2_TARGET") ? std::atof(std::getenv("MISO_K2_TARGET")) : 0.0;
-        k2w_plan = plan_lanes(nd.data(), n_k2w, p.noChains, widths, 5, 4, 4, resident, max_cpw, cost, forced, coop_max, coop_k2w_budget);
-        // The widest a chain can be is its workgroup: 256 lanes with 4 wavefronts, 512 with 8 (one workgroup per CU,
-        // twice the LDS each: the same chains per CU).  8-wavefront workgroups lose ~19 % when the launch runs in
-        // several rounds (a workgroup starts when ALL its slots are free), so they are taken only when the largest
-        // events would otherwise outlast the launch (hg19-like read counts: 218 ms -> 175 ms; uniform: 217 ms -> 259 ms, not taken; profiles/r03_pe_k2_wpb.txt).
-        {
-          const LanePlan p8 = plan_lanes(nd.data(), n_k2w, p.noChains, widths, 5, 8, 8, std::max(1, resident / 2), max_cpw, cost, forced, coop_max, coop_k2w_budget);
-          const char *env = std::getenv("MISO_K2W_WPB");
-          if (env ? std::atoi(env) == 8 : 1.2 * p8.est < k2w_plan.est) k2w_plan = p8;
-        }
-        k2w_plan_key = key;
-      }
-      q.k2w_multi = max_cpw >= 1 && k2w_plan.n_segs > 0;
-      if (q.k2w_multi) {
-        int cpw = 1;
-        for (int i = 0; i < k2w_plan.n_segs; i++)
-          if (k2w_plan.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / k2w_plan.seg_lanes[i]);
-        q.k2w_multi_lds = align_up(q.k2w_fp + static_cast<size_t>(k2w_plan.wpb) * cpw * q.k2w_tab, 16);
-      }
+  if (p.paired && n_k2w > 0 && multi) {
+    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp) - K2_RED_BYTES;
+    const int max_cpw = static_cast<int>(std::max<long>(0, lds_left / static_cast<long>(4 * q.k2w_tab)));
+    K2Part pt{0, n_k2w, K2_WIDTHS_PE, 5};
+    pt.wide_wpb = pt.wpb = 4; pt.max_cpw = max_cpw; pt.coop_budget = coop_k2w_budget;
+    pt.resident = std::max(1, slots_for(static_cast<long>(n_k2w) * p.noChains) / 4);
+    LaneCost cost = k2_cost_paired();
+    if (max_cpw >= 1 && plan_k2_lanes(pt, knobs.k2w_wpb.set, cost, nd, k2w_plan, k2w_plan_key)) {
+      // The widest a chain can be is its workgroup: 256 lanes with 4 wavefronts, 512 with 8 (one workgroup per CU,
+      // twice the LDS each: the same chains per CU).  8-wavefront workgroups lose ~19 % when the launch runs in
+      // several rounds (a workgroup starts when ALL its slots are free), so they are taken only when the largest
+      // events would otherwise outlast the launch (hg19-like read counts: 218 ms -> 175 ms; uniform: 217 ms -> 259 ms, not taken; profiles/r03_pe_k2_wpb.txt).
+      pt.wide_wpb = pt.wpb = 8; pt.resident = std::max(1, pt.resident / 2);
+      const LanePlan p8 = k2_lanes(pt, nd, cost);
+      if (knobs.k2w_wpb.set ? knobs.k2w_wpb.v == 8 : 1.2 * p8.est < k2w_plan.est) k2w_plan = p8;
+    }
+    q.k2w_multi = max_cpw >= 1 && k2w_plan.n_segs > 0;
+    if (q.k2w_multi) {
+      int cpw = 1;
+      for (int i = 0; i < k2w_plan.n_segs; i++)
+        if (k2w_plan.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / k2w_plan.seg_lanes[i]);
+      q.k2w_multi_lds = align_up(q.k2w_fp + static_cast<size_t>(k2w_plan.wpb) * cpw * q.k2w_tab, 16);
     }
   }
   // the several-rounds single-end plan has runs of one and two lanes per chain only: the kernel of three wavefronts per SIMD (kernels_k2m.inl)
-  q.k2_narrow = q.k2_multi && !p.paired && k2_plan.wpb == 4 && k2_plan.n_segs > 0 && std::getenv("MISO_K2_NO_NARROW") == nullptr;
+  q.k2_narrow = q.k2_multi && !p.paired && k2_plan.wpb == 4 && k2_plan.n_segs > 0 && !knobs.k2_no_narrow;
   for (int i = 0; i < k2_plan.n_segs && q.k2_narrow; i++) q.k2_narrow = k2_plan.seg_lanes[i] <= 2;
 }
 
@@ -1057,11 +1059,10 @@ void miso_batch::plan_k2(const KernelArgs &a) {
 // wherever the next width takes over) and the SIMDs of the lighter runs idle at the end (wave-slot occupancy
 // 0.78, profiles/r03_wave_time.txt).  Measured, 40 000 events: hg19-like read counts (13 runs) 73.9 -> 71.4 ms;
 // 1000 reads each (4 runs) 99.7 -> 100.8 ms, 3000 reads 244.6 -> 250.0 ms (few runs: their sums are close already,
-// and the kernel with a body per run AND per wavefront is larger): used from seven runs on.
-// MISO_K2_GLOBAL_PAIR=0 / 1: never / always (A/B, tests).
+// and the kernel with a body per run AND per wavefront is larger): used from seven runs on (knobs.k2_global_pair).
 void miso_batch::k2_pair_table(const std::vector<int> &nd, const LaneCost &cost) {
-  const char *gp = std::getenv("MISO_K2_GLOBAL_PAIR");
-  if (!(k2_plan.n_segs > 0 && k2_plan.rounds == 1 && (gp ? std::atoi(gp) != 0 : k2_plan.n_segs >= 7))) return;
+  const Opt<int> &gp = knobs.k2_global_pair;
+  if (!(k2_plan.n_segs > 0 && k2_plan.rounds == 1 && (gp.set ? gp.v != 0 : k2_plan.n_segs >= 7))) return;
   struct W { double cost; int32_t code; };
   std::vector<W> ws;
   bool ok = true, seen_narrow = false;
@@ -1098,7 +1099,7 @@ void miso_batch::launch_k2(KernelArgs ka, int G, hipStream_t st, bool wpart) {
   const int cpw = 64 / std::max(G, 1);
   const long waves = (chains + cpw - 1) / cpw;
   // single-end: workgroups of 8 wavefronts = one CU's resident slots; the two wavefronts of a SIMD
-  // take a heavy and a light group of chains (sampler_k2's WPB = 8).  MISO_K2_PAIR=0: the 4-wavefront
+  // take a heavy and a light group of chains (sampler_k2's WPB = 8); knobs.k2_pair off: the 4-wavefront
   // workgroups in slot order (round-1 behaviour).
   const bool pair = plan.k2_pair;
   ka.pair_waves = pair ? 1 : 0;
@@ -1174,7 +1175,7 @@ void miso_batch::launch_k2_multi(KernelArgs ka, hipStream_t st, bool wpart) {
     return;
   }
   // the whole launch resident at once: the two wavefronts of a SIMD keep step (kernels_k2.inl k2_balance)
-  if (pl.wpb == 8 && pl.rounds == 1) ka.balance = (std::getenv("MISO_K2_BALANCE") && std::atoi(std::getenv("MISO_K2_BALANCE")) == 0) ? 0 : 1;
+  if (pl.wpb == 8 && pl.rounds == 1) ka.balance = knobs.k2_balance.off() ? 0 : 1;
   const int wpb = pl.wpb == 8 || pl.wpb == 4 ? pl.wpb : 1;
   launch_kernel(k2_multi_kernel(0, wpb, plan.k2_narrow), grid, 64 * wpb, wpb == 1 ? 0 : K2_RED_BYTES, st, ka);
 }
@@ -1190,8 +1191,7 @@ void miso_batch::launch_lane(KernelArgs ka, hipStream_t st) {
     grid = static_cast<unsigned>((chains + 255) / 256);
     // fewer wavefronts than SIMDs (or than two per SIMD): spread the chains over all of them (kernels_lane.hip lane_body)
     const long simds = wave_slots / 2, waves = (chains + 63) / 64;
-    const char *sp = std::getenv("MISO_LANE_SPREAD");   // 0: never; n: n wavefronts per SIMD (experiments)
-    const int per_simd = sp ? std::atoi(sp) : 1;
+    const int per_simd = knobs.lane_spread.v;
     if (plan.lane_ilp && per_simd > 0 && waves < simds * per_simd && chains >= 64) {
       const long target = simds * per_simd;
       const int cpw = static_cast<int>((chains + target - 1) / target);
@@ -1208,10 +1208,8 @@ size_t miso_batch::fp_bytes_of(const GenRun &run) const {
 }
 GrpShape miso_batch::grp_shape(const GenRun &run) const {
   const size_t fp_bytes = fp_bytes_of(run);
-  // single-end: per-class thresholds join the slice (class path) when every event has a class
-  // table; MISO_NO_CLASS_PATH=1 (tests): force the direct mask path of sampler_grp
-  const bool no_cls = std::getenv("MISO_NO_CLASS_PATH") != nullptr;
-  int qs = (!p.paired && !no_cls && !run.nocls && run.maxcls > 0) ? run.maxcls : 0;
+  // single-end: per-class thresholds join the slice (class path) when every event has a class table
+  int qs = (!p.paired && !knobs.no_class_path && !run.nocls && run.maxcls > 0) ? run.maxcls : 0;
   if (qs && 4 * 2 * static_cast<size_t>(grp_slice_bytes(run.kmax, qs, 0)) > plan.lds_max) qs = 0;
   // paired-end: the per-event score table (K x il int32) joins the slice when >= 4 chains still fit
   int ts = p.paired ? run.kmax * (fp_rows(run) ? plan.il2 : static_cast<int>(fd.prob.size())) : 0;
@@ -1240,17 +1238,17 @@ miso_batch::GenRun miso_batch::joined_run(size_t r0, size_t r1) const {
 unsigned miso_batch::wide_setup(GenRun &run, long chains, hipStream_t st) {
   // Workgroups per chain: what upload() derived from the gene's share of the batch's work (coop_n), at most
   // COOP_MAX_N, all cooperative workgroups of the batch together at most COOP_MAX_WGS (coop.hpp: they must all be
-  // resident at once).  MISO_NO_COOP=1: one workgroup per chain; MISO_COOP_DRAWS=n: one per n drawing pairs (tests).
+  // resident at once).  knobs.no_coop: one workgroup per chain; knobs.coop_draws: one per n drawing pairs.
   CoopTable &cc = run.coop;
   if (!cc.tab.d) {
     std::vector<int32_t> tab;
     cc.chains = 0;
     const bool coop_on = coop_enabled();
-    const int per_wg = std::getenv("MISO_COOP_DRAWS") ? std::max(256, std::atoi(std::getenv("MISO_COOP_DRAWS"))) : 8192;
+    const int per_wg = knobs.coop_draws.v;
     for (long c = 0; c < chains; c++) {
       const int ev_i = h_slots[n_k2 + run.first + c / p.noChains];
       const int nd = events[ev_i].n_draw;
-      int nw = !coop_on ? 1 : (std::getenv("MISO_COOP_DRAWS") ? std::min(COOP_MAX_N, std::max(1, (nd + per_wg - 1) / per_wg)) : coop_n[ev_i]);
+      int nw = !coop_on ? 1 : (knobs.coop_draws.set ? std::min(COOP_MAX_N, std::max(1, (nd + per_wg - 1) / per_wg)) : coop_n[ev_i]);
       if (nw > 1 && coop_wgs_used + nw > coop_gen_budget) nw = std::max(1, coop_gen_budget - coop_wgs_used);
       if (nw > 1) coop_wgs_used += nw;
       for (int r = 0; r < nw; r++) {
@@ -1259,7 +1257,7 @@ unsigned miso_batch::wide_setup(GenRun &run, long chains, hipStream_t st) {
       }
       if (nw > 1) cc.chains++;
     }
-    if (std::getenv("MISO_TIMING")) {
+    if (knobs.timing) {
       std::fprintf(stderr, "[miso] wide run kc=%d: %ld chains on %zu workgroups (%d on several:", run.kc, chains, tab.size() / 4, cc.chains);
       for (size_t i = 0; i < tab.size(); i += 4)
         if (tab[i + 1] == 0 && tab[i + 2] > 1)
@@ -1280,7 +1278,6 @@ void miso_batch::launch_grp(KernelArgs ka, GenRun &run, const GrpShape &sh, int 
   ka.kstride = run.kmax; ka.cstride = sh.qs; ka.tstride = sh.ts;
   const bool wave_kernel = G == 64 && !run.wide && !(run.wave64 && fp_rows(run));   // sampler_wave, not sampler_grp<64, ..>
   ka.pe_dense = wave_kernel ? 0 : fp_rows(run);
-  ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
   const size_t fp_bytes = wave_kernel ? plan.fp_plain : fp_bytes_of(run);
   if (run.wide) {   // one chain per workgroup: four slices (one per wavefront) + the reduction scratch behind them
     ka.pe_dense = fp_rows(run);
@@ -1312,18 +1309,19 @@ void miso_batch::launch_grp(KernelArgs ka, GenRun &run, const GrpShape &sh, int 
 // carry more than twice the average wavefront's work units -- the wavefronts are packed by UNITS instead: as many
 // consecutive chains (at most nc_max: the LDS) as make about the average wavefront's units, a chain of several
 // times that alone in a WORKGROUP (FLAT_WIDE: 256 lanes), workgroups ordered heaviest first (the hardware starts
-// them in index order).  MISO_FLAT_PACK=0 / 1: never / always (tests, A/B).
+// them in index order); knobs.flat_pack: never / always.
 // How many units per wavefront: as many as nc_max average chains have -- the scalar step costs a wavefront the same
 // for 2 chains and for 13, so fewer, fuller wavefronts win (hg19-like read counts, 40 000 events, K = 5: 497 ms at 8
 // average chains per wavefront, 425 ms at 13+) -- unless that leaves the device part empty: fewer wavefronts than
 // resident slots, or a second round that is less than half full (K = 3: 3349 wavefronts on 3072 slots 286 ms,
 // 5704 wavefronts 270 ms); then the wavefront count goes to 0.95 x one or two rounds
-// (profiles/r03_flat_pack_sweep.txt).  A forced MISO_FLAT_NC sets the average chains per wavefront instead.
+// (profiles/r03_flat_pack_sweep.txt).  A forced knobs.flat_nc sets the average chains per wavefront instead.
 void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, int nc_max_p, long resident_p) {
   const long chains = static_cast<long>(run.count) * p.noChains;
   const int C = p.noChains;
-  const char *env = std::getenv("MISO_FLAT_PACK");
-  const long key = (((static_cast<long>(nc) * 4 + (env ? 1 + (std::atoi(env) != 0) : 0)) * 128 + nc_max_u) * 128 + nc_max_p) * 1024 + (std::getenv("MISO_FLAT_PACK_OV") ? 1 + std::atol(std::getenv("MISO_FLAT_PACK_OV")) % 1000 : 0);
+  const Opt<int> &fpack = knobs.flat_pack;
+  const long ov_pct = knobs.flat_pack_ov.v;   // (per cent of the rule below)
+  const long key = (((static_cast<long>(nc) * 4 + (fpack.set ? 1 + (fpack.v != 0) : 0)) * 128 + nc_max_u) * 128 + nc_max_p) * 1024 + (knobs.flat_pack_ov.set ? 1 + ov_pct % 1000 : 0);
   if (run.wave_tab.key == key && run.wave_tab.d) return;
   // (round 5) what a chain costs its wavefront, in work units: its units + the scalar step and thresholds, which do not
   // depend on the reads.  Measured per chain-iteration at eight / five chains per wavefront (profiles/r05_flat_chunks.txt):
@@ -1331,9 +1329,7 @@ void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, 
   // matters for carry 14 - 18 small chains, whose flat passes and leader sections are shared by twice as many chains:
   // 16 K + 14.  Swept on hg19-like read counts at 25 ... 300 % of the first figure: K = 3 / 4 / 6 / 8 best at 50 % (208 /
   // 152 / 107 / 80 k events/s against 153 / 144 / 97 / 74 k at 100 %), K = 5 / 12 at 100 % (122 / 45 k against 114 / 43 k);
-  // by units alone: 151 / 112 / 55 k at K = 3 / 5 / 10.  MISO_FLAT_PACK_OV=<per cent of the rule> (0: by units alone).
-  const char *ov_env = std::getenv("MISO_FLAT_PACK_OV");
-  const long ov_pct = ov_env ? std::atol(ov_env) : 100;   // (per cent of the rule: experiments)
+  // by units alone: 151 / 112 / 55 k at K = 3 / 5 / 10.
   auto units_of = [&](long c) {
     const PackedEvent &e = events[h_slots[n_k2 + run.first + c / C]];
     return static_cast<long>(e.n_units) + (16L * e.K + 14) * ov_pct / 100;
@@ -1346,7 +1342,7 @@ void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, 
     if ((c + 1) % nc == 0 || c + 1 == chains) { heaviest = std::max(heaviest, sum); sum = 0; }
   }
   const double mean_wave = static_cast<double>(total) * nc / std::max<long>(1, chains);
-  const bool pack = env ? std::atoi(env) != 0 : (chains > nc && static_cast<double>(heaviest) > 2.0 * mean_wave);
+  const bool pack = fpack.set ? fpack.v != 0 : (chains > nc && static_cast<double>(heaviest) > 2.0 * mean_wave);
   struct W { int32_t first, n; long units; };
   std::vector<W> waves, wides;
   if (!pack) {
@@ -1375,15 +1371,15 @@ void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, 
       return static_cast<long>(waves.size() + 4 * wides.size());
     };
     const double per_chain = static_cast<double>(total) / std::max<long>(1, chains);
-    const bool forced = std::getenv("MISO_FLAT_NC") != nullptr;
+    const bool forced = knobs.flat_nc.set;
     const long n_waves = pack_with(std::max(64.0, per_chain * (forced ? nc : cap)));
     if (!forced && n_waves < 3 * resident / 2) {
       // (round 6) ... and TWO rounds are aimed at from further below than one: the second round's workgroups start as the
       // first round's end, staggered, and a count within a few per cent of two full rounds runs into a third (hg19-like read
       // counts, K = 5, 2048 resident wavefronts: 4029 wavefronts 71.7 ms, 3793 64.6 ms, 3541 66.2 ms, 2956 -- the fullest
-      // packing -- 67.7 ms; profiles/r06_flat_pack_rounds.txt).  MISO_FLAT_ROUNDS_FRAC: the fraction of two rounds (experiments).
+      // packing -- 67.7 ms; profiles/r06_flat_pack_rounds.txt): knobs.flat_rounds_frac.
       const bool two = n_waves > resident;
-      const double frac2 = std::getenv("MISO_FLAT_ROUNDS_FRAC") ? std::atof(std::getenv("MISO_FLAT_ROUNDS_FRAC")) : 0.85;
+      const double frac2 = knobs.flat_rounds_frac.v;
       const double want = (two ? frac2 : 0.95) * static_cast<double>(two ? 2 * resident : resident);
       if (static_cast<double>(n_waves) < want) {
         // (round 5) ... and not a few wavefronts MORE than the round(s): the packing's bound is a target, the count it
@@ -1400,7 +1396,7 @@ void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, 
         }
       }
     }
-    if (std::getenv("MISO_TIMING"))
+    if (knobs.timing)
       std::fprintf(stderr, "[flat_waves] kc %d chains %ld cost/chain %.1f cap %d resident %ld first pack %ld waves -> %zu waves + %zu wide, most chains %d\n",
                    run.kc, chains, per_chain, cap, resident, n_waves, waves.size(), wides.size(), most);
     std::stable_sort(wides.begin(), wides.end(), [](const W &x, const W &y) { return x.units > y.units; });
@@ -1417,18 +1413,23 @@ void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, 
   run.wave_tab.key = key;
 }
 
+// Workgroups per CU a run of sampler_flat is sized for: kernels_flat.inl's register budgets -- 3 up to four isoforms and for
+// nine to twelve (measured round 4, profiles/r04_occupancy.txt), 2 otherwise (five to eight isoforms: the kernel allows 3,
+// sizing for 3 gained nothing) -- unless knobs.flat_wgs says otherwise.
+int miso_batch::flat_wgs(int kc) const { return knobs.flat_wgs.set ? knobs.flat_wgs.v : flat_wgs_for(kc); }
+
 void miso_batch::launch_flat(KernelArgs ka, size_t ri, hipStream_t st) {
   GenRun &run = gen_runs[ri];
   const int nc = plan.runs[ri].flat_nc, nc_max = plan.runs[ri].flat_nc_max;
   {
     const long chains = static_cast<long>(run.count) * p.noChains;
-    const int wgs = std::getenv("MISO_FLAT_WGS") ? std::max(1, std::atoi(std::getenv("MISO_FLAT_WGS"))) : flat_wgs_for(run.kc);
+    const int wgs = flat_wgs(run.kc);
     // Five to eight isoforms: the kernel's registers allow three workgroups per CU; launches of like-sized events are sized for
     // two (fuller wavefronts: K = 6 312 against 333 ms, K = 7 347 / 366), launches packed by cost for three -- more, smaller
     // wavefronts level the heavy tail better than fuller ones amortise the scalar step (hg19-like read counts, 40 000 events:
     // K = 5 276 -> 252 ms, K = 6 332 -> 278, K = 7 379 -> 339, K = 8 415 -> 393; profiles/r06_flat_licm.txt)
     int wgs_p = wgs, nc_max_p = nc_max;
-    if (run.kc == 8 && std::getenv("MISO_FLAT_WGS") == nullptr && std::getenv("MISO_LDS_MAX_KB") == nullptr && std::getenv("MISO_FLAT_PACK_WGS2") == nullptr) {
+    if (run.kc == 8 && !knobs.flat_wgs.set && !knobs.lds_max_kb.set && !knobs.flat_pack_wgs2) {
       wgs_p = 3;
       const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
       nc_max_p = std::max(1, std::min<int>(64, static_cast<int>(160 * 1024 / (4 * wgs_p) - 64) / slice));
@@ -1440,27 +1441,25 @@ void miso_batch::launch_flat(KernelArgs ka, size_t ri, hipStream_t st) {
   ka.kstride = run.kmax; ka.cstride = std::max(run.maxcls, 1); ka.tstride = 0; ka.nc = run.wave_nc;
   ka.wave_tab = run.wave_tab.d;
   // the descriptor read loop from four isoforms on (three: the walking loop is 2 % faster -- two thresholds per unit,
-  // little to save) and whenever a chain owns a whole workgroup; MISO_FLAT_NO_DESC=1: the walking loop everywhere
-  // (A/B, tests; not with workgroup-wide chains)
-  ka.flat_desc = ((std::getenv("MISO_FLAT_NO_DESC") == nullptr && run.kmax >= 4) || run.wave_wide > 0) ? 1 : 0;
+  // little to save) and whenever a chain owns a whole workgroup
+  ka.flat_desc = ((!knobs.flat_no_desc && run.kmax >= 4) || run.wave_wide > 0) ? 1 : 0;
   // Thresholds only for the chains whose psi changed (kernels_flat.inl): the pass is one lane per (chain, class) and the
   // Metropolis-Hastings step rejects 45 - 65 % of the proposals, but numbering the chains that accepted costs every lane
   // a few instructions -- it pays where the thresholds weigh enough: from six isoforms on (K = 6 ... 12: + 4.5 ... 6.4 %)
   // and for small events (hg19-like read counts at K = 5: + 5.5 %; 1000 reads per event at K = 3 ... 5: - 1 ... 2 %,
-  // profiles/r04_occupancy.txt).  MISO_FLAT_THR_SKIP=0 / 1: never / always (A/B, tests).
+  // profiles/r04_occupancy.txt); knobs.flat_thr_skip: never / always.
   {
     double units = 0;
     for (int j = 0; j < run.count; j++) units += events[h_slots[n_k2 + run.first + j]].n_units;
-    const char *env = std::getenv("MISO_FLAT_THR_SKIP");
-    ka.flat_thr_skip = env ? (std::atoi(env) != 0) : (run.kmax >= 6 || units < 150.0 * run.count);
+    ka.flat_thr_skip = knobs.flat_thr_skip.set ? (knobs.flat_thr_skip.v != 0) : (run.kmax >= 6 || units < 150.0 * run.count);
   }
   const unsigned grid = static_cast<unsigned>(run.wave_tab.host.size() / 8);
   const size_t lds = 4 * static_cast<size_t>(run.wave_nc) * flat_layout(ka.kstride, ka.cstride).bytes;
   // Priority by progress (device.hpp prio_by_progress) when the launch takes several rounds of like-sized wavefronts:
   // 40 000 events x 1000 reads, K = 5 348.0 -> 334.4 ms, K = 10 649.4 -> 631.4 ms, same box; wavefronts packed by cost
   // (hg19-like read counts) lose 1 % and keep the arbiter's own order; so do the paired-end and the two-isoform kernels
-  // (+ 0.5 ... 4 %: profiles/r06_prio_by_progress.txt).  MISO_PRIO_QUARTILES=0 / 1: never / everywhere (A/B).
-  if (std::getenv("MISO_PRIO_QUARTILES") == nullptr && !run.wave_packed && run.wave_wide == 0 &&
+  // (+ 0.5 ... 4 %: profiles/r06_prio_by_progress.txt); knobs.prio_quartiles set: never here / everywhere (launch()).
+  if (!knobs.prio_quartiles.set && !run.wave_packed && run.wave_wide == 0 &&
       static_cast<long>(grid) * 4 > static_cast<long>(slots_for(static_cast<long>(run.count) * p.noChains)) * flat_wgs_for(run.kc) / 2)
     ka.balance = 2;
   launch_kernel(flat_kernel(run.kc, plan.runs[ri].flat_ks, plan.runs[ri].flat_uni), grid, 256, lds, st, ka);
@@ -1490,24 +1489,21 @@ void miso_batch::plan_runs(const KernelArgs &a) {
 // single-end runs whose events all have a class table go to sampler_flat (kernels_flat.inl): NC chains
 // per wavefront, as many as fit the wavefront's share of the LDS (two workgroups of four wavefronts
 // per CU: 20 KB each), fewer when the batch would not fill the device otherwise.
-// MISO_NO_FLAT=1: sampler_grp as in round 1 (A/B, tests); MISO_FLAT_NC=n forces the chains per wavefront.
+// (knobs.no_flat: sampler_grp as in round 1; knobs.flat_nc forces the chains per wavefront.)
 void miso_batch::plan_flat(size_t ri) {
   const GenRun &run = gen_runs[ri];
   LaunchPlan::Run &r = plan.runs[ri];
   // up to twenty isoforms the kernel of the launch's largest isoform count (its slice layout at compile time,
-  // kernels_flat.inl); MISO_FLAT_NO_KS=1: the run-time layout everywhere (A/B, tests)
+  // kernels_flat.inl)
   const int lo = run.kc == 4 ? 3 : (run.kc == 8 ? 5 : (run.kc == 12 ? 9 : (run.kc == 16 ? 13 : 17)));
-  r.flat_ks = (run.kc <= 32 && run.kmax >= lo && run.kmax <= std::min(run.kc, 20) && std::getenv("MISO_FLAT_NO_KS") == nullptr) ? run.kmax : 0;
+  r.flat_ks = (run.kc <= 32 && run.kmax >= lo && run.kmax <= std::min(run.kc, 20) && !knobs.flat_no_ks) ? run.kmax : 0;
   // ... and, when every event of the launch has that count, the kernel that knows it (UNI: no per-chain `k < K` masks)
-  r.flat_uni = r.flat_ks > 0 && run.kmin == run.kmax && std::getenv("MISO_FLAT_NO_UNI") == nullptr;
+  r.flat_uni = r.flat_ks > 0 && run.kmin == run.kmax && !knobs.flat_no_uni;
   if (r.lane) return;
-  if (p.paired || run.nocls || run.kc >= 64 || std::getenv("MISO_NO_FLAT") != nullptr) return;
+  if (p.paired || run.nocls || run.kc >= 64 || knobs.no_flat) return;
   const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
-  // workgroups per CU the chains per wavefront are sized for: kernels_flat.inl's register budgets -- 3 up to four isoforms
-  // and for nine to twelve (measured round 4, profiles/r04_occupancy.txt), 2 otherwise (five to eight isoforms: the kernel
-  // allows 3, sizing for 3 gained nothing); MISO_FLAT_WGS overrides
-  const int wgs = std::getenv("MISO_FLAT_WGS") ? std::max(1, std::atoi(std::getenv("MISO_FLAT_WGS"))) : flat_wgs_for(run.kc);
-  const size_t lds_wave = std::getenv("MISO_LDS_MAX_KB") ? plan.lds_max / 4 : static_cast<size_t>(160 * 1024 / (4 * wgs)) - 64;
+  const int wgs = flat_wgs(run.kc);
+  const size_t lds_wave = knobs.lds_max_kb.set ? plan.lds_max / 4 : static_cast<size_t>(160 * 1024 / (4 * wgs)) - 64;
   const int nc_max = std::min<int>(64, static_cast<int>(lds_wave) / slice);
   if (nc_max < 1) return;
   const long chains = static_cast<long>(run.count) * p.noChains;
@@ -1523,7 +1519,7 @@ void miso_batch::plan_flat(size_t ri) {
   // was tried: a 7 % difference is inside the noise of a 200-iteration trial, the choice flipped between runs.)
   if (run.kc == 8) nc = std::min(nc, run.kmin >= 8 ? 6 : 8);
   if (run.kc == 4 && run.kmin >= 4) nc = std::min(nc, 8);   // four isoforms, descriptor loop: 8 -> 119.8k, 16 -> 116.1k, 13 -> 85.5k
-  if (const char *env = std::getenv("MISO_FLAT_NC")) nc = std::max(1, std::min(nc_max, std::atoi(env)));
+  if (knobs.flat_nc.set) nc = std::max(1, std::min(nc_max, knobs.flat_nc.v));
   r.flat_nc = nc; r.flat_nc_max = nc_max;
 }
 
@@ -1536,7 +1532,7 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
   // (flat wins at every isoform count of profiles/r02_flat_vs_grp_sweep.txt but 5); a small or untuned
   // batch takes sampler_flat.
   const bool contest = r.flat_nc > 0 && plan.tune_runs && static_cast<long>(run.count) * p.noChains >= 2048 &&
-                       run.tuned_flat < 0 && std::getenv("MISO_FLAT_NC") == nullptr;
+                       run.tuned_flat < 0 && !knobs.flat_nc.set;
   if (r.flat_nc > 0 && run.tuned_flat == 0) r.flat_nc = 0;
   if (r.flat_nc > 0 && !contest) return;
   GrpShape &sh = r.sh = grp_shape(run);
@@ -1550,16 +1546,11 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
     r.G = 64;
     return;
   }
-  if (const char *env = std::getenv("MISO_GENERAL_LANES")) {
-    G = std::atoi(env);
-  } else if (const char *envc = std::getenv("MISO_GENERAL_LANES_BY_CLASS")) {   // experiments: "4:16,8:16,12:32,16:32,32:32"
+  if (knobs.general_lanes.set) {
+    G = knobs.general_lanes.v;
+  } else if (knobs.general_lanes_by_class_set) {
     G = 16;
-    for (const char *s = envc; s && *s;) {
-      int kc = 0, g = 0;
-      if (std::sscanf(s, "%d:%d", &kc, &g) == 2 && kc == run.kc) G = g;
-      s = std::strchr(s, ',');
-      if (s) s++;
-    }
+    for (const auto &c : knobs.general_lanes_by_class) if (c.first == run.kc) G = c.second;
   } else if (run.tuned_G) {
     G = run.tuned_G;
     if (p.paired && sh.ts && !grp_fits(run, sh, G)) {   // chosen with the score tables in global memory (the eight-lane rule below)
@@ -1585,15 +1576,14 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
     // (round 3, 8 hardware queues, 16 384 genes of 3-20 isoforms per 1500 iterations: 16 lanes up to 16 isoforms against 32
     // everywhere -- 400 pairs per gene 120 vs 150 ms, 1000 pairs 194 vs 206 ms, hg19-like counts 176 vs 175 ms, 2500 pairs
     // 436 vs 367 ms: small genes share the scalar step four to a wavefront, large ones want the lanes; the switch sits at a
-    // mean of 400 drawing quads per gene of the class; MISO_PE_MIX_LANES=16|32 forces)
+    // mean of 400 drawing quads per gene of the class; knobs.pe_mix_lanes forces)
     const double mean_q = run.sum_q / std::max(1, run.count);
-    const char *mixl = std::getenv("MISO_PE_MIX_LANES");
     // (round 5, same batch on one box, 7500 iterations: the 17 - 20 isoform class on 16 lanes as well -- 1000 pairs per gene
     // 930 -> 852 ms, hg19-like pair counts 865 -> 820 ms: four chains of a wavefront share the scalar step, and the class
     // no longer fills the device with half-efficient wavefronts for the launch's first third while the other classes
     // wait; the bucket of "at least 32 lanes" from a need of 32 lanes instead of 24: a 20-isoform gene of 1000 pairs
     // needs 28 by the share rule; profiles/r05_pe_mix_lanes.txt)
-    const bool mix16 = run.kc <= 32 && !run.force_G && (mixl ? std::atoi(mixl) == 16 : mean_q < 400.0);
+    const bool mix16 = run.kc <= 32 && !run.force_G && (knobs.pe_mix_lanes.set ? knobs.pe_mix_lanes.v == 16 : mean_q < 400.0);
     const bool pe32 = p.paired && ((n_classes + (n_k2 > 0 ? 1 : 0) > 1 && !mix16) || (run.kc >= 12 && 2 * ((chains + 3) / 4) < 3 * static_cast<long>(slots_for(chains))) ||
                                    (chains + 3) / 4 < slots_for(chains));
     for (int g : {2, 4, 8, 16, 32}) {
@@ -1610,11 +1600,11 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
     // fragment rows and the loop's header no longer waits for fresh gathers it wins: 40 000 events x 1000 pairs, K = 5 / 6 / 7 /
     // 8 / 9: 45.3 -> 54.2, 41.5 -> 48.7, 40.5 -> 45.5, 38.0 -> 40.5, 30.2 -> 31.5 k events/s; K = 12: 25.7 -> 21.2 k, four lanes
     // 33.7 k at K = 5; in a whole-gene mix, where a class is a few thousand genes, 19.2 -> 18.2 k genes/s: not there
-    // (profiles/r05_lanes_sweep.txt).  MISO_PE_LANES8=0 / 1: never / also in a mix and for the size buckets' normal run.
+    // (profiles/r05_lanes_sweep.txt).  knobs.pe_lanes8 = 0 / 1: never / also in a mix and for the size buckets' normal run.
     {
-      const char *l8 = std::getenv("MISO_PE_LANES8");
+      const Opt<int> &l8 = knobs.pe_lanes8;
       const bool single = n_classes + (n_k2 > 0 ? 1 : 0) == 1;
-      const bool want8 = l8 && std::atoi(l8) != 2 ? std::atoi(l8) != 0 : ((single || l8) && chains >= 8L * 2 * slots_for(chains));   // (2: the rule in a mix of classes too)
+      const bool want8 = l8.set && l8.v != 2 ? l8.v != 0 : ((single || l8.set) && chains >= 8L * 2 * slots_for(chains));   // (2: the rule in a mix of classes too)
       if (p.paired && want8 && G == 16 && !run.force_G && run.kmin >= 5 && run.kmax <= 9 && grp_fits(run, sh, 8)) G = 8;
       // Three and four isoforms the same -- there the class keeps its score tables in LDS (grp_shape), which holds four
       // chains per wavefront and no more: eight chains with the tables in global memory (an L2 line per pick) instead,
@@ -1636,8 +1626,8 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
       run.tuned_G = G;
     }
   }
-  if (run.force_G && G < run.force_G && std::getenv("MISO_GENERAL_LANES") == nullptr) G = run.force_G;   // size bucket (upload)
-  if (run.small && p.paired && std::getenv("MISO_GENERAL_LANES") == nullptr && std::getenv("MISO_GENERAL_LANES_BY_CLASS") == nullptr) {   // the small genes' bucket: eight chains per wavefront, score tables in global memory
+  if (run.force_G && G < run.force_G && !knobs.general_lanes.set) G = run.force_G;   // size bucket (upload)
+  if (run.small && p.paired && !knobs.general_lanes.set && !knobs.general_lanes_by_class_set) {   // the small genes' bucket: eight chains per wavefront, score tables in global memory
     GrpShape sh8 = sh;
     sh8.ts = 0;
     if (grp_fits(run, sh8, 8)) { sh = sh8; G = 8; }
@@ -1662,11 +1652,9 @@ void miso_batch::group_runs() {
   // (quads per lane + the scalar step) x isoforms, descending: longest first across the classes.  Every segment keeps the run's
   // own slice layout (launch_grp's).  Batches with size buckets (real pair counts) keep a launch per class
   // (sampler_grp_multi): twenty bodies in one kernel do not compile in reasonable time (round 5: 28 minutes, 802 spilled registers).
-  // MISO_NO_PE_ALL=1: the launches per run below (A/B, tests).
   {
-    bool all_ok = p.paired && !q.lane_gen && gen_runs.size() >= 2 && gen_runs.size() < 127 && std::getenv("MISO_NO_PE_ALL") == nullptr &&
-                  std::getenv("MISO_NO_PE_MULTI") == nullptr && std::getenv("MISO_SERIAL_KERNELS") == nullptr &&
-                  (std::getenv("MISO_GENERAL_LANES") == nullptr || std::getenv("MISO_PE_ALL") != nullptr);   // (MISO_PE_ALL=1 with MISO_GENERAL_LANES=16: tests on small batches)
+    bool all_ok = p.paired && !q.lane_gen && gen_runs.size() >= 2 && gen_runs.size() < 127 && !knobs.no_pe_all &&
+                  !knobs.no_pe_multi && !knobs.serial_kernels && (!knobs.general_lanes.set || knobs.pe_all);
     bool two_classes = false;
     for (size_t ri = 0; ri < gen_runs.size() && all_ok; ri++) {
       const GenRun &run = gen_runs[ri];
@@ -1679,18 +1667,18 @@ void miso_batch::group_runs() {
   }
   // Paired-end: the size buckets of one isoform-count class in ONE launch (sampler_grp_multi<KC>, kernels_grp.inl):
   // segments = the class's runs in list order -- workgroup-wide chains (those on several workgroups in front), a
-  // wavefront per chain, 32 lanes, 16 lanes.  MISO_NO_PE_MULTI=1: every run its own launch (A/B, tests).
+  // wavefront per chain, 32 lanes, 16 lanes.
   // When: the batch's launches outnumber the hardware queues (a whole-gene mix with real read counts: ~20 launches, 243 ->
   // 180 ms per 1500 iterations; a single class's three or four buckets run 3 % faster side by side: 149 vs 155 ms at K = 5;
-  // profiles/r03_pe_buckets.txt).  MISO_PE_MULTI=1 forces (tests).
+  // profiles/r03_pe_buckets.txt); knobs.pe_multi forces.
   // ... or some run on 16 / 32 lanes holds several isoform counts: the multi kernel's segments keep them in wavefronts of their own
   bool any_mixed = false;
   for (size_t ri = 0; ri < gen_runs.size(); ri++) {
     const int G = q.runs[ri].G;
     any_mixed |= p.paired && !gen_runs[ri].wide && (G == 16 || G == 32 || (G == 8 && gen_runs[ri].small)) && fp_rows(gen_runs[ri]) && q.runs[ri].flat_nc == 0 && gen_runs[ri].kmin != gen_runs[ri].kmax;
   }
-  const bool multi_on = p.paired && !q.lane_gen && std::getenv("MISO_NO_PE_MULTI") == nullptr && std::getenv("MISO_GENERAL_LANES") == nullptr &&
-                        (std::getenv("MISO_PE_MULTI") != nullptr || gen_runs.size() + (n_k2 > 0 ? 1 : 0) > 8 || any_mixed);
+  const bool multi_on = p.paired && !q.lane_gen && !knobs.no_pe_multi && !knobs.general_lanes.set &&
+                        (knobs.pe_multi || gen_runs.size() + (n_k2 > 0 ? 1 : 0) > 8 || any_mixed);
   for (size_t r0 = 0; multi_on && !q.grp_all && r0 < gen_runs.size();) {
     size_t r1 = r0 + 1;
     while (r1 < gen_runs.size() && gen_runs[r1].kc == gen_runs[r0].kc) r1++;
@@ -1723,7 +1711,7 @@ void miso_batch::group_runs() {
   // (what is IN EFFECT, not what the environment says now: capi.hip's constructor records it; 0 = unknown -- not set, or the
   // runtime was up before this library was loaded -- counts as the runtime's default of 4)
   const int hwq = g_hw_queues_in_effect > 0 ? g_hw_queues_in_effect : 4;
-  const bool merge_on = std::getenv("MISO_NO_PE_MERGE") == nullptr && (std::getenv("MISO_PE_MERGE") != nullptr || hwq < 8);
+  const bool merge_on = !knobs.no_pe_merge && (knobs.pe_merge || hwq < 8);
   for (size_t ri = 0; merge_on && ri + 1 < gen_runs.size(); ri++) {
     const GenRun &run = gen_runs[ri], &nx = gen_runs[ri + 1];
     const LaunchPlan::Run &r = q.runs[ri], &rx = q.runs[ri + 1];
@@ -1739,7 +1727,7 @@ void miso_batch::group_runs() {
 // kernel i > 0 goes to its own stream, forked from and joined back into the batch's stream
 hipStream_t miso_batch::stream_for_next() {
   const size_t i = kernel_no++;
-  if (i == 0 || std::getenv("MISO_SERIAL_KERNELS") != nullptr) return stream;
+  if (i == 0 || knobs.serial_kernels) return stream;
   while (aux_streams.size() < i) {
     hipStream_t st; hipEvent_t e;
     // (numerically lower = higher priority; the range has three levels on this device: the second and third kernel
@@ -1759,7 +1747,7 @@ hipStream_t miso_batch::stream_for_next() {
 // workgroup-wide runs (chains on several workgroups first: their workgroups must all be resident at once, coop.hpp,
 // which the idle device guarantees; what is launched after them never waits for them) -- sampler_grp_all or the
 // classes' sampler_grp_multi, then the runs of their own --, MODE 2, the other two-isoform events, the other runs.
-void miso_batch::launch_planned(const KernelArgs &a) {
+void miso_batch::launch_planned(const KernelArgs &a, const KernelArgs &k2a) {
   const LaunchPlan &q = plan;
   if (q.lane_route || q.lane_gen) {   // log factorials (miso_binomial.h) up to the largest event's drawing reads
     size_t need = 2;
@@ -1787,16 +1775,16 @@ void miso_batch::launch_planned(const KernelArgs &a) {
   if (n_k2w > 0) {
     lanes_per_chain = q.k2w_multi ? k2w_plan.seg_lanes[k2w_plan.n_segs - 1] : q.k2w_G;
     note_kernel(k2_part_name(true));
-    if (q.k2w_multi) launch_k2_multi(a, stream_for_next(), true);
-    else launch_k2(a, q.k2w_G, stream_for_next(), true);
+    if (q.k2w_multi) launch_k2_multi(k2a, stream_for_next(), true);
+    else launch_k2(k2a, q.k2w_G, stream_for_next(), true);
   }
   if (n_k2 - n_k2w > 0) {
     lanes_per_chain = q.lane_route ? q.lane_G : q.k2_multi ? k2_plan.seg_lanes[k2_plan.n_segs - 1] : q.k2_G;
     note_kernel(k2_part_name(false));
-    if (q.lane_route) launch_lane(a, stream_for_next());
-    else if (q.k2_multi) launch_k2_multi(a, stream_for_next());
-    else if (q.k2_mix > 0) launch_k2_mix(a, stream_for_next());
-    else launch_k2(a, q.k2_G, stream_for_next());
+    if (q.lane_route) launch_lane(k2a, stream_for_next());
+    else if (q.k2_multi) launch_k2_multi(k2a, stream_for_next());
+    else if (q.k2_mix > 0) launch_k2_mix(k2a, stream_for_next());
+    else launch_k2(k2a, q.k2_G, stream_for_next());
   }
   for (size_t ri = 0; ri < gen_runs.size(); ri++) if (!gen_runs[ri].wide && !q.runs[ri].lane && !q.runs[ri].group) launch_run(a, ri);
 }
@@ -1862,9 +1850,8 @@ void miso_batch::launch_run(const KernelArgs &a, size_t ri) {
 void miso_batch::launch_grp_all(const KernelArgs &a) {
   struct Seg { size_t ri; int e0, e1; double cost; };
   std::vector<Seg> segs;
-  // (a segment per isoform count, so that no wavefront carries two -- see sampler_grp_multi below; MISO_PE_ALL_ORDER=0: a segment per
-  // run, 2: heaviest / lightest alternating, 3: lightest first (A/B: 777 / 705 / 767 / 851 ms for 0 / 1 / 2 / 3))
-  const int order = std::getenv("MISO_PE_ALL_ORDER") ? std::atoi(std::getenv("MISO_PE_ALL_ORDER")) : 1;
+  // (a segment per isoform count, so that no wavefront carries two -- see sampler_grp_multi below; knobs.pe_all_order: other orders)
+  const int order = knobs.pe_all_order.v;
   for (size_t ri = 0; ri < gen_runs.size(); ri++) {
     const GenRun &run = gen_runs[ri];
     if (order == 0) { segs.push_back(Seg{ri, 0, run.count, (static_cast<double>(run.maxq) / 16.0 + 8.0) * (run.kmax + 2)}); continue; }
@@ -1886,7 +1873,7 @@ void miso_batch::launch_grp_all(const KernelArgs &a) {
   KernelArgs ka = a;
   hipStream_t st = stream_for_next();
   ka.slot_event = d_slots + n_k2; ka.n_slots = n_gen;
-  ka.cstride = 0; ka.pe_dense = 1; ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
+  ka.cstride = 0; ka.pe_dense = 1;
   size_t lds = 0; int blocks = 0;
   std::vector<GrpSeg> tab;
   for (const Seg &sg : segs) {
@@ -1924,12 +1911,12 @@ void miso_batch::launch_grp_multi(const KernelArgs &a, size_t r0, size_t r1) {
   hipStream_t st = stream_for_next();
   ka.slot_event = d_slots + n_k2 + m.first; ka.n_slots = m.count;
   ka.kstride = m.kmax; ka.cstride = 0; ka.tstride = msh.ts;
-  ka.pe_dense = 1; ka.pe_force_exact = std::getenv("MISO_PE_FORCE_EXACT") != nullptr;
+  ka.pe_dense = 1;
   size_t lds = 0; int blocks = 0, segs = 0;
   // A run on 16 or 32 lanes per chain is one segment PER ISOFORM COUNT (the run's events are ordered by it): every segment starts
   // a new workgroup, so no wavefront carries chains of two isoform counts -- such a wavefront runs both counts' read loops one after
   // the other (kernels_grp.inl pe_fast), twice a chain's own time, and with the class's longest chains that was the launch's length
-  // (round 6, profiles/r06_mix_timeline.txt).  As far as the segments suffice; MISO_PE_NO_KSPLIT=1: a segment per run (A/B).
+  // (round 6, profiles/r06_mix_timeline.txt).  As far as the segments suffice (knobs.pe_no_ksplit: a segment per run).
   auto k_pieces = [&](const GenRun &run) {
     std::vector<int> cuts{0};
     for (int e = 1; e < run.count; e++)
@@ -1940,7 +1927,7 @@ void miso_batch::launch_grp_multi(const KernelArgs &a, size_t r0, size_t r1) {
   size_t want_segs = 0;
   for (size_t ri = r0; ri < r1; ri++)
     want_segs += (gen_runs[ri].wide || plan.runs[ri].G == 64) ? 1 : k_pieces(gen_runs[ri]).size() - 1;
-  const bool ksplit = want_segs <= static_cast<size_t>(K2_MAX_SEGS) && std::getenv("MISO_PE_NO_KSPLIT") == nullptr;
+  const bool ksplit = want_segs <= static_cast<size_t>(K2_MAX_SEGS) && !knobs.pe_no_ksplit;
   for (size_t ri = r0; ri < r1; ri++) {
     GenRun &run = gen_runs[ri];
     const long chains = static_cast<long>(run.count) * p.noChains;
