@@ -542,6 +542,11 @@ int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, 
 /* csrc/text_digits.hpp text_digits, the rounding of summarize_as_text: out[i] = x[i] x 10^4 rounded to the nearest integer,
    ties to even, on the exact product -- the digits of "%.4f" of x[i], sign included.  Finite |x[i]| < 2^38. */
 int miso_selftest_text_digits(const double *x, int n, int64_t *out);
+/* csrc/k2_flag.hpp, the trip flag of the single-end two-isoform read loop: element i is one lane, its trips the pairs
+   start[i] .. start[i + 1] - 1 (start[0] = 0, n + 1 offsets) of m (a trip's running minimum) and k (its stride position,
+   < 2^24), noted in order by k2_flag_note.  k2_flag_read's answer: code[i] = 0 no flagged trip, 1 exactly one, at pos[i],
+   2 more than one (or one trip with two bits: see the header). */
+int miso_selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *start, int n, int32_t *code, uint32_t *pos);
 
 #ifdef __cplusplus
 }

@@ -850,6 +850,20 @@ def selftest_text_digits(x):
     return out
 
 
+def selftest_k2_flag(m, k, start):
+    """csrc/k2_flag.hpp on the device, one lane per element: trips start[i] .. start[i + 1] - 1 of (running minimum m, stride
+    position k) noted in order; returns (code, pos): 0 none / 1 exactly one flagged trip, at pos / 2 more than one"""
+    m = np.ascontiguousarray(m, dtype=np.uint32)
+    k = np.ascontiguousarray(k, dtype=np.uint32)
+    start = np.ascontiguousarray(start, dtype=np.int32)
+    if m.shape != k.shape or m.ndim != 1 or start.ndim != 1 or len(start) < 1 or start[0] != 0 or start[-1] != len(m):
+        raise ValueError("m, k: two vectors of one length; start: offsets from 0 to len(m)")
+    n = len(start) - 1
+    code, pos = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    check(lib().miso_selftest_k2_flag(_p(m), _p(k), _p(start), n, _p(code), _p(pos)))
+    return code, pos
+
+
 def selftest_convergent_mean(samples, chains):
     """samples: S x K (row i from chain i % chains) -> True if stop=CONVERGENT_MEAN would stop (miso.c:556-636)"""
     a = np.ascontiguousarray(samples, dtype=np.float64)

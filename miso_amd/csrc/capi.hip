@@ -1150,5 +1150,13 @@ int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, 
 int miso_selftest_text_digits(const double *x, int n, int64_t *out) {
   return guarded([&] { selftest_text_digits(x, n, out); });
 }
+int miso_selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *start, int n, int32_t *code, uint32_t *pos) {
+  return guarded([&] {
+    need(start, "start");
+    if (n > 0) { need(code, "code"); need(pos, "pos"); }
+    if (n > 0 && start[n] > 0) { need(m, "m"); need(k, "k"); }
+    selftest_k2_flag(m, k, start, n, code, pos);
+  });
+}
 
 }  // extern "C"

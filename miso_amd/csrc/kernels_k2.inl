@@ -33,6 +33,7 @@
 #include "coop.hpp"
 #include "miso_binomial.h"
 #include "detmath_n.hpp"
+#include "k2_flag.hpp"
 
 #pragma clang fp contract(off)
 
@@ -442,7 +443,7 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   // the halves of the partial block's word w that are NOT reads of the chain (rem = 0: all of them)
   uint32_t part_inv[4];
 #pragma unroll
-  for (int w = 0; w < 4; w++) part_inv[w] = (2 * w < rem ? 0u : 0xFFFFu) | (2 * w + 1 < rem ? 0u : 0xFFFF0000u);
+  for (int w = 0; w < 4; w++) part_inv[w] = k2_part_inv(rem, w);
 
   double *samples = reinterpret_cast<double *>(a.out_pool + E.off_samples);
   double *loglik = reinterpret_cast<double *>(a.out_pool + E.off_loglik);
@@ -666,8 +667,9 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     const uint64_t t = k2_threshold(cur.x0, (0.0 + cur.x0) + cur.x1);
     const uint32_t th = static_cast<uint32_t>(t >> 16), tl = static_cast<uint32_t>(t) & 0xFFFFu;   // th <= 65536
     const uint32_t n0r0 = rng.p1hi ^ iter ^ k0;
-    // trips and single steps of this lane with a high half on the threshold; the stride position the last of them began at
-    int d0 = 0, amb_n = 0; uint32_t amb_t = 0;
+    // trips and single steps of this lane with a high half on the threshold, and the stride position the one began at where
+    // there is exactly one (k2_flag.hpp: two sums, no compare and no select on the loop's path)
+    int d0 = 0; K2Flag amb;
     PROF_T(g1);
     PROF_ADD(pf_thr, g0, g1);
     // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask):
@@ -676,6 +678,10 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // (m - 0x00010001) & ~m & 0x80008000).  th = 65536 (t = 2^32: every read picks isoform 0) does not fit a half:
     // counted in closed form behind the loop.
     // (inline assembly: written with vector types the compiler recognises the idiom and goes back to one compare per half.
+    // Two words' operations share ONE statement, interleaved so that none reads the result of the one before it: behind a
+    // statement of its own the compiler pads with an s_nop 0 whenever the next instruction reads what the statement wrote --
+    // it assumes a destination-forwarding hazard it cannot see into -- and these operations have none: inside a statement
+    // the hardware's ordinary interlocks apply.
     // Measured, same box, 40 000 events x 1000 reads: one SDWA compare per half into a lane mask + add-with-carry, 110
     // VALU per 16 reads, 74.6 ms; this form, 108 VALU but no lane masks, 71.0 ms; MISO defaults 235.9 -> 219.1 ms,
     // hg19-like read counts 66.4 -> 59.4 ms; the equal test once per trip instead of once per block: 70.9 -> 69.3 ms,
@@ -704,23 +710,40 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
       for (int i = 0; i < NB; i++) {
         const int q = sub + (k + i) * GE;
 #pragma unroll
-        for (int w = 0; w < 4; w++) {
-          uint32_t d;
-          asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(d) : "v"(T2), "v"(u[i].v[w]));
-          asm("v_pk_min_u16 %0, %1, %2" : "=v"(d) : "v"(d), "v"(one2));
-          uint32_t y = u[i].v[w] ^ T2;
-          if (MASKED) {
-            const uint32_t inv = (q < nfq) ? 0u : (q == nfq ? part_inv[w] : 0xFFFFFFFFu);
-            d &= ~inv;
-            y |= inv;
+        for (int w = 0; w < 4; w += 2) {   // two words per statement, interleaved: no packed operation reads its predecessor's result
+          const uint32_t ua = u[i].v[w], ub = u[i].v[w + 1];
+          uint32_t da, db, ya = ua ^ T2, yb = ub ^ T2;
+          const bool first = i == 0 && w == 0;   // m = min(ya, yb) instead of min(m, ya, yb)
+          if (!MASKED) {
+            if (first)
+              asm("v_pk_sub_u16 %0, %4, %5 clamp\n\tv_pk_sub_u16 %1, %4, %6 clamp\n\t"
+                  "v_pk_min_u16 %0, %0, %7\n\tv_pk_min_u16 %1, %1, %7\n\t"
+                  "v_pk_add_u16 %2, %2, %0\n\tv_pk_min_u16 %3, %8, %9\n\tv_pk_add_u16 %2, %2, %1"
+                  : "=&v"(da), "=&v"(db), "+v"(accv), "=&v"(m) : "v"(T2), "v"(ua), "v"(ub), "v"(one2), "v"(ya), "v"(yb));
+            else
+              asm("v_pk_sub_u16 %0, %4, %5 clamp\n\tv_pk_sub_u16 %1, %4, %6 clamp\n\t"
+                  "v_pk_min_u16 %0, %0, %7\n\tv_pk_min_u16 %1, %1, %7\n\t"
+                  "v_pk_add_u16 %2, %2, %0\n\tv_pk_min_u16 %3, %3, %8\n\tv_pk_add_u16 %2, %2, %1\n\tv_pk_min_u16 %3, %3, %9"
+                  : "=&v"(da), "=&v"(db), "+v"(accv), "+v"(m) : "v"(T2), "v"(ua), "v"(ub), "v"(one2), "v"(ya), "v"(yb));
+          } else {   // the masks go between the counts and the sums: two statements
+            asm("v_pk_sub_u16 %0, %2, %3 clamp\n\tv_pk_sub_u16 %1, %2, %4 clamp\n\t"
+                "v_pk_min_u16 %0, %0, %5\n\tv_pk_min_u16 %1, %1, %5"
+                : "=&v"(da), "=&v"(db) : "v"(T2), "v"(ua), "v"(ub), "v"(one2));
+            const uint32_t inva = (q < nfq) ? 0u : (q == nfq ? part_inv[w] : 0xFFFFFFFFu);
+            const uint32_t invb = (q < nfq) ? 0u : (q == nfq ? part_inv[w + 1] : 0xFFFFFFFFu);
+            da &= ~inva; ya |= inva;
+            db &= ~invb; yb |= invb;
+            if (first)
+              asm("v_pk_add_u16 %0, %0, %2\n\tv_pk_min_u16 %1, %4, %5\n\tv_pk_add_u16 %0, %0, %3"
+                  : "+v"(accv), "=&v"(m) : "v"(da), "v"(db), "v"(ya), "v"(yb));
+            else
+              asm("v_pk_add_u16 %0, %0, %2\n\tv_pk_min_u16 %1, %1, %4\n\tv_pk_add_u16 %0, %0, %3\n\tv_pk_min_u16 %1, %1, %5"
+                  : "+v"(accv), "+v"(m) : "v"(da), "v"(db), "v"(ya), "v"(yb));
           }
-          asm("v_pk_add_u16 %0, %1, %2" : "=v"(accv) : "v"(accv), "v"(d));
-          if (i == 0 && w == 0) { m = y; continue; }
-          asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(m), "v"(y));
         }
       }
       // the flag: the stride position the flagged trip or step began at (a single step: k >= UQ * uq_trips)
-      if (((m - 0x00010001u) & ~m & 0x80008000u) != 0u) { amb_t = static_cast<uint32_t>(k); amb_n++; }
+      k2_flag_note(amb, m, static_cast<uint32_t>(k));
     };
     const std::integral_constant<int, UQ> whole{};
     const std::integral_constant<int, 1> single{};
@@ -746,9 +769,12 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     }
     // t = 2^32: every read of the lane's full blocks and, for its owner, of the partial block
     if (th > 0xFFFFu) d0 = ((sub < nfq) ? 8 * ((nfq - 1 - sub) / GE + 1) : 0) + ((sub == nfq % GE) ? rem : 0);
-    if (!lane_used) { d0 = 0; amb_n = 0; }
+    if (!lane_used) { d0 = 0; amb = K2Flag{}; }
     const bool settle_all = a.pe_force_exact != 0;   // tests: every lane takes the rescan below at every step
-    if (tl != 0 && __builtin_expect(settle_all || __any(amb_n != 0), 0)) {
+    uint32_t amb_t = 0;
+    // (a position beyond the flag's 24-bit multiply -- a lane walking more than 1.3e8 reads -- is not trusted: rescan)
+    const int amb_n = (npos <= K2_FLAG_MAX_POS || amb.n == 0) ? k2_flag_read(amb, amb_t) : static_cast<int>(K2_FLAG_MANY);
+    if (tl != 0 && __builtin_expect(settle_all || __any(amb_n != K2_FLAG_NONE), 0)) {
       // the reads whose high half sits ON the threshold: their low halves decide (one wavefront step in four at 1000
       // reads and 16 chains per wavefront; two Philox blocks then)
       auto settle = [&](uint32_t q) {
@@ -770,10 +796,10 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
         for (int h = 0; h < 8; h++) on |= miso_block_half(hi, h) == th;
         return on ? settle(static_cast<uint32_t>(q)) : 0;
       };
-      if (amb_n == 1 && !settle_all) {        // one trip's blocks, or one single step's block ...
+      if (amb_n == K2_FLAG_ONE && !settle_all) {        // one trip's blocks, or one single step's block ...
         const int k = static_cast<int>(amb_t), nb = k < UQ * uq_trips ? UQ : 1;
         for (int i = 0; i < nb; i++) d0 += look(sub + (k + i) * GE);
-      } else if ((amb_n > 1 || settle_all) && lane_used) {   // ... or, with several such trips, all of the lane's
+      } else if ((amb_n == K2_FLAG_MANY || settle_all) && lane_used) {   // ... or, with several such trips, all of the lane's
         for (int q = sub; q < nblk; q += GE) d0 += look(q);
       }
     }

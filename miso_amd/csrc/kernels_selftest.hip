@@ -116,6 +116,18 @@ __global__ void __launch_bounds__(256) selftest_count_below_kernel(const int32_t
   out[i] = D;
 }
 
+// k2_flag.hpp: element i is one lane's read loop, its trips the pairs start[i] .. start[i + 1] - 1 of (m, k)
+__global__ void __launch_bounds__(256) selftest_k2_flag_kernel(const uint32_t *m, const uint32_t *k, const int32_t *start, int n,
+                                                               int32_t *code, uint32_t *pos) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  K2Flag f;
+  for (int j = start[i]; j < start[i + 1]; j++) k2_flag_note(f, m[j], k[j]);
+  uint32_t p = 0;
+  code[i] = k2_flag_read(f, p);
+  pos[i] = p;
+}
+
 __global__ void __launch_bounds__(256) selftest_text_digits_kernel(const double *x, int n, int64_t *out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = text_digits(x[i]);
@@ -295,6 +307,22 @@ void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double 
   int32_t *dout = b.out<int32_t>(static_cast<size_t>(n) * (KK + 1));
   hipLaunchKernelGGL(selftest_pe_pick_kernel, st_grid(n), dim3(256), 0, 0, KK, df, dpsi, dfp, il2, drule, dword, n, dout);
   b.back(out, dout, static_cast<size_t>(n) * (KK + 1));
+}
+
+void selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *start, int n, int32_t *code, uint32_t *pos) {
+  st_need_device(n);
+  if (n == 0) return;
+  if (start[0] != 0) MISO_FAIL(MISO_EINVAL, "start[0] must be 0");
+  for (int i = 0; i < n; i++) if (start[i + 1] < start[i]) MISO_FAIL(MISO_EINVAL, "start must not decrease");
+  const size_t total = static_cast<size_t>(start[n]);
+  StBuffers b;
+  const uint32_t *dm = b.in(m, total), *dk = b.in(k, total);
+  const int32_t *dstart = b.in(start, static_cast<size_t>(n) + 1);
+  int32_t *dcode = b.out<int32_t>(static_cast<size_t>(n));
+  uint32_t *dpos = b.out<uint32_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_k2_flag_kernel, st_grid(n), dim3(256), 0, 0, dm, dk, dstart, n, dcode, dpos);
+  b.back(code, dcode, static_cast<size_t>(n));
+  b.back(pos, dpos, static_cast<size_t>(n));
 }
 
 void selftest_text_digits(const double *x, int n, int64_t *out) {

@@ -209,6 +209,15 @@ __global__ void k_ds_read_b64(uint32_t *out, int n, uint32_t seed, unsigned long
 // v_readlane_b32 into a scalar, the s_nop the compiler puts behind it, and a VALU reader of that scalar (two instructions
 // and a nop per entry: per_trip counts the pair as ONE)
 #define M_READLANE_NOP(i) "v_readlane_b32 %9, %" #i ", 3\n s_nop 0\n v_add_u32 %" #i ", %9, %" #i "\n"
+// the read loop's trip flag as arithmetic: the population count with its addend
+#define M_BCNT(i) "v_bcnt_u32_b32 %" #i ", %" #i ", %10\n"
+// two DEPENDENT packed operations back to back, and the same with the s_nop 0 the compiler pads a separate asm statement
+// with: the difference of the two rows is what the nop costs (two instructions per entry, per_trip counts both)
+#define M_PK_DEP(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n v_pk_min_u16 %" #i ", %" #i ", %11\n"
+#define M_PK_DEP_NOP(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n s_nop 0\n v_pk_min_u16 %" #i ", %" #i ", %11\n"
+DEF_KERNEL_32M(k_bcnt, P_NONE, M_BCNT)
+DEF_KERNEL_32M(k_pk_dep, P_NONE, M_PK_DEP)
+DEF_KERNEL_32M(k_pk_dep_nop, P_NONE, M_PK_DEP_NOP)
 DEF_KERNEL_32M(k_cndmask_e32_m, P_CMP_VCC, M_CNDMASK_E32)
 DEF_KERNEL_32M(k_cndmask_e64_m, P_CMP_SGPR, M_CNDMASK_E64)
 DEF_KERNEL_32M(k_cndmask_e64_vcc, P_CMP_VCC, M_CNDMASK_E64_VCC)
@@ -282,6 +291,7 @@ int main() {
     {"v_cndmask e64, vcc mask", k_cndmask_e64_vcc, 64}, {"cmp e64, add, cndmask e64", k_cmp_near_cndmask, 192},
     {"v_bfi_b32", k_bfi, 64}, {"v_pk_sub_u16 clamp", k_pk_sub_clamp, 64}, {"v_pk_min_u16", k_pk_min, 64},
     {"v_pk_add_u16", k_pk_add, 64}, {"v_readlane+s_nop+v_add", k_readlane_nop, 64},
+    {"v_bcnt_u32_b32", k_bcnt, 64}, {"pk_sub, pk_min dependent", k_pk_dep, 128}, {"pk_sub, s_nop 0, pk_min", k_pk_dep_nop, 128},
     {"ds_bpermute (8 + wait)", k_ds_bpermute, 64}, {"ds_bpermute, one + wait", k_ds_bpermute_serial, 64},
   };
   const int n = 2000;
