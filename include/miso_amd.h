@@ -229,6 +229,29 @@ int miso_exact_eligible(int paired, int noiso, const double *eff_len, const doub
    precision).  *was_exact = 0 and the outputs untouched for an event that ran the sampler. */
 int miso_batch_get_exact_summary(miso_batch_t *batch, int event_index, double *mean, double *ci_low, double *ci_high,
                                  double confidence_level, int *was_exact);
+/* Paired-end batches, algorithm = MISO_ALGO_REASSIGN: on != 0 selects the exact-posterior mode of the eligible
+   PAIRED-END two-isoform events (csrc/kernels_exact_paired.hip); a switch of its own, apart from
+   miso_batch_set_exact.  Summed over the pairs' assignments the law of x = psi_0 under the reference's paired chain
+   (miso_paired.c:24-174) is
+       log p(x) = (n10 + h0 - 1) log x + (n01 + h1 - 1) log(1 - x) + sum_i log(x m0_i + (1 - x) m1_i)
+                  - n log(x A0 + (1 - x) A1) + const
+   (n10 / n01 pairs compatible with isoform 0 / 1 only; the sum over the pairs compatible with both, m their
+   fragment-length probabilities under the two isoforms; n all pairs with a compatible isoform; A_k = exp(assscores_k),
+   miso_paired.c:403-419).  An eligible event -- two isoforms, A0, A1 > 0, both hyperparameters >= 1, no pair on a
+   non-finite score entry (miso_exact_paired_eligible) -- runs no chain: one wavefront tabulates the density (which may
+   have SEVERAL modes) and row s of the samples inverts the CDF at the uniform of (seed, event id, sample s,
+   MISO_SITE_EXACT).  logLik[s] = log p at the sample with the Dirichlet normaliser and without psi-free constants: the
+   MARGINAL log density, not the reference's joint score -- the additive terms of quirk C5 are absent by construction;
+   assignment = one reassignment of the pairs from the last row's psi by the paired pick rule
+   U (psi0 m0 + psi1 m1) < psi0 m0, on the words of the paired sampler's initial reassignment of chain 0 (MISO_SITE_GIBBS,
+   MISO_ITER_INIT); accepted = noSamples, rejected = 0; done after round one under stop = CONVERGENT_MEAN;
+   miso_batch_get_exact_summary serves these events too.  Every other event runs through the sampler kernels,
+   bit-identical to the same event in a batch without the mode.  Before miso_batch_launch; MISO_EINVAL for single-end
+   batches and for algorithm != MISO_ALGO_REASSIGN. */
+int miso_batch_set_exact_paired(miso_batch_t *batch, int on);
+/* the eligibility rule on its own (host arithmetic): A = exp(assscores), hyper: noiso doubles each; any_bad != 0: a pair
+   of the event touches a non-finite score entry */
+int miso_exact_paired_eligible(int noiso, const double *A, const double *hyper, int any_bad, int *eligible);
 int miso_batch_upload(miso_batch_t *batch, int device);
 /* enqueue the sampler kernels for every event on the batch's stream; returns immediately */
 int miso_batch_launch(miso_batch_t *batch, uint64_t seed, uint32_t first_event_id);
@@ -534,6 +557,13 @@ int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, d
    space), the normalising sum F[G], the mode (logit space), the grid step, the log density at the mode as tabulated};
    icdf[(i n_prob + j) 2 ...] = {x, 1 - x} at the inverse CDF of prob[j] (0 < prob < 1). */
 int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf);
+/* kernels_exact_paired.hip, the posterior stage alone, one wavefront per element: stats6[6 i ...] = {n10, n01, A0, A1, h0, h1};
+   the element's drawing pairs are m[2 r], m[2 r + 1] = (m0, m1) for r in [offs[i], offs[i + 1]) (offs: n + 1 ascending
+   entries from 0; every m inside [2^-63, 1]: sixteen factors multiply without underflow).  out8[8 i ...] = {mean of x, mean of 1 - x, window
+   low, window high (logit space), the normalising sum F[G], gref (the largest log density the last window pass met),
+   the grid step, log F[G] + gref}; icdf as miso_selftest_exact. */
+int miso_selftest_exact_paired(const double *stats6, const double *m, const int64_t *offs, int n, const double *prob,
+                               int n_prob, double *out8, double *icdf);
 /* kernels_exact_compare.hip on caller-given statistics, one wavefront per pair: stats7_1 / stats7_2 in miso_selftest_exact's
    layout (sample 1, sample 2).  out[(5 + n_z) i ...] = {mean1, mean2, log_density_at_0, bayes_factor, log10_bayes_factor,
    cdf at z[0 .. n_z)} as miso_batch_get_exact_comparison returns them.  MISO_EINVAL when a pair's e0, e1 differ between

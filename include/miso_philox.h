@@ -25,6 +25,8 @@
  *   site MISO_SITE_EXACT (5): the exact-posterior mode of single-end two-isoform events (miso_batch_set_exact,
  *                           csrc/kernels_exact.hip) -- no chain, no iteration: ctr = (sample index s, 0, site, event_id),
  *                           word 0 of that block = the uniform that sample s inverts the posterior's CDF at
+ *                           (the same address in the paired-end mode, miso_batch_set_exact_paired,
+ *                           csrc/kernels_exact_paired.hip: an event is single-end or paired-end, never both)
  *   iteration = m for the main loop (miso.c:847), MISO_ITER_INIT for the set-up draws
  *   (initial proposal miso.c:834 and initial assignment miso.c:841).
  *

@@ -198,11 +198,13 @@ class Batch:
     def __init__(self, read_len, iters=5000, burn=500, lag=10, chains=6, overhang=1, paired=False,
                  mean=0.0, var=0.0, num_devs=4.0, start=MISO_START_AUTO, stop=MISO_STOP_FIXEDNO,
                  algo=MISO_ALGO_REASSIGN, max_iters=100000, counts_trace=False, device_match=False,
-                 collapsed=False, exact=False):
+                 collapsed=False, exact=False, exact_paired=False):
         """collapsed (single-end): the two-isoform events draw their assignment COUNTS directly (one exact binomial
         per iteration instead of one uniform per read; miso_batch_set_collapsed in include/miso_amd.h).
         exact (single-end, algo = REASSIGN): the eligible two-isoform events run no chain, their samples are independent
-        draws from the posterior of psi itself, tabulated once per event (miso_batch_set_exact in include/miso_amd.h)."""
+        draws from the posterior of psi itself, tabulated once per event (miso_batch_set_exact in include/miso_amd.h).
+        exact_paired (paired-end, algo = REASSIGN): the same for the eligible paired-end two-isoform events, a switch of its
+        own (miso_batch_set_exact_paired in include/miso_amd.h)."""
         self.params = Params(int(paired), read_len, overhang, chains, iters, max_iters, burn, lag,
                              algo, start, stop, mean, var, num_devs, int(counts_trace),
                              int(device_match))
@@ -214,6 +216,15 @@ class Batch:
         self.exact = bool(exact)
         if exact:
             check(lib().miso_batch_set_exact(self.handle, 1))
+        self.exact_paired = bool(exact_paired)
+        if exact_paired:
+            check(lib().miso_batch_set_exact_paired(self.handle, 1))
+
+    def set_exact_paired(self, on=True):
+        """Switch the paired-end exact-posterior mode on or off, also after the upload: the next launch makes its lists anew
+        (miso_batch_set_exact_paired)."""
+        check(lib().miso_batch_set_exact_paired(self.handle, int(bool(on))))
+        self.exact_paired = bool(on)
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -823,6 +834,26 @@ def selftest_exact(stats7, probs):
     out8 = np.zeros((len(st), 8))
     icdf = np.zeros((len(st), len(pr), 2))
     check(lib().miso_selftest_exact(_p(st), len(st), _p(pr), len(pr), _p(out8), _p(icdf)))
+    return out8, icdf
+
+
+def selftest_exact_paired(stats6, pairs, probs):
+    """csrc/kernels_exact_paired.hip, the posterior stage alone: stats6[i] = (n10, n01, A0, A1, h0, h1), pairs[i] = the
+    element's drawing pairs [(m0, m1), ...] -> (out8 [n, 8] = mean of x, mean of 1 - x, window low / high, normalising sum,
+    gref, grid step, log of the normalising sum + gref; icdf [n, len(probs), 2]) -- include/miso_amd.h miso_selftest_exact_paired"""
+    st = np.ascontiguousarray(stats6, dtype=np.float64).reshape(-1, 6)
+    if len(pairs) != len(st):
+        raise ValueError("one list of pairs per element")
+    rows = [np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 2) for q in pairs]
+    offs = np.zeros(len(st) + 1, np.int64)
+    offs[1:] = np.cumsum([len(r) for r in rows])
+    m = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 2)))
+    if len(m) == 0:
+        m = np.zeros((1, 2))           # (a valid pointer; no element reads it)
+    pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    out8 = np.zeros((len(st), 8))
+    icdf = np.zeros((len(st), len(pr), 2))
+    check(lib().miso_selftest_exact_paired(_p(st), _p(m), _p(offs), len(st), _p(pr), len(pr), _p(out8), _p(icdf)))
     return out8, icdf
 
 

@@ -40,6 +40,18 @@ void exact_compare_run(const double *stats7_1, const double *stats7_2, int n, co
 inline bool exact_eligible(bool paired, int K, const double *eff, const double *hyper) {
   return !paired && K == 2 && eff[0] > 0 && eff[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1;
 }
+// kernels_exact_paired.hip: the paired-end exact-posterior mode (miso_batch_set_exact_paired).  Its posterior stage on its
+// own: ka != null -- the events of ka's list, A2 their A0, A1 on the device (exact summaries); otherwise caller-given
+// statistics and pairs (miso_selftest_exact_paired)
+void exact_paired_probe_run(const KernelArgs *ka, const double *A2, const double *stats6, const double *m, const int64_t *offs,
+                            int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st = nullptr);
+const void *exact_paired_sample_fn();   // the kernel exact_paired_sample(KernelArgs, const double *A2, int S)
+// sixteen pair factors, each at least the smallest fragment-length probability, must multiply to a normal number
+constexpr double EXACT_PAIRED_MIN_PROB = 1.0 / 9223372036854775808.0;   // 2^-63
+// the paired mode takes such an event (include/miso_amd.h miso_exact_paired_eligible); A = exp(assscores)
+inline bool exact_paired_eligible(int K, const double *A, const double *hyper, bool any_bad) {
+  return K == 2 && A[0] > 0 && A[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1 && !any_bad;
+}
 // kernels_compare_groups.hip
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
@@ -134,6 +146,9 @@ struct miso_batch {
   bool collapsed = false;         // single-end two-isoform events: the collapsed Gibbs step (kernels_lane.hip); miso_batch_set_collapsed
   // the exact-posterior mode (miso_batch_set_exact; kernels_exact.hip): its events leave the sampler's lists
   bool exact = false;
+  bool exact_paired = false;      // ... of paired-end batches (miso_batch_set_exact_paired; kernels_exact_paired.hip): the same lists,
+                                  // exact_eff holds A0, A1 (a batch is single-end or paired-end: at most one of the two is set)
+  bool exact_any() const { return exact || exact_paired; }
   bool slots_exact = false;       // the mode the launch lists were last built for (build_slots)
   std::vector<char> is_exact;     // per event: the exact kernel takes it
   int n_exact = 0;                // ... their number: the launch lists are [two-isoform | other | exact]

@@ -1004,6 +1004,22 @@ int miso_batch_set_exact(miso_batch_t *b, int on) {
   });
 }
 
+int miso_batch_set_exact_paired(miso_batch_t *b, int on) {
+  return guarded([&] {
+    need(b, "batch");
+    if (on && !b->p.paired) MISO_FAIL(MISO_EINVAL, "the paired exact-posterior mode takes paired-end events only");
+    if (on && b->p.algorithm != MISO_ALGO_REASSIGN) MISO_FAIL(MISO_EINVAL, "the exact-posterior mode is the posterior of algorithm = REASSIGN only");
+    b->exact_paired = on != 0;   // (the launch lists follow at the upload, or at the next launch: runtime.hip build_slots)
+  });
+}
+
+int miso_exact_paired_eligible(int noiso, const double *A, const double *hyper, int any_bad, int *eligible) {
+  return guarded([&] {
+    need(A, "A"); need(hyper, "hyper"); need(eligible, "eligible");
+    *eligible = (noiso == 2 && exact_paired_eligible(noiso, A, hyper, any_bad != 0)) ? 1 : 0;
+  });
+}
+
 int miso_exact_eligible(int paired, int noiso, const double *eff_len, const double *hyper, int *eligible) {
   return guarded([&] {
     need(eff_len, "eff_len"); need(hyper, "hyper"); need(eligible, "eligible");
@@ -1145,6 +1161,14 @@ int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, 
     if (n > 0) { need(stats7_1, "stats7_1"); need(stats7_2, "stats7_2"); need(out, "out"); }
     if (n_z > 0) need(z, "z");
     exact_compare_run(stats7_1, stats7_2, n, z, n_z, out);
+  });
+}
+int miso_selftest_exact_paired(const double *stats6, const double *m, const int64_t *offs, int n, const double *prob, int n_prob,
+                               double *out8, double *icdf) {
+  return guarded([&] {
+    if (n > 0) { need(stats6, "stats6"); need(offs, "offs"); if (offs[n] > 0) need(m, "m"); }
+    if (n_prob > 0) need(prob, "prob");
+    exact_paired_probe_run(nullptr, nullptr, stats6, m, offs, n, prob, n_prob, out8, icdf);
   });
 }
 int miso_selftest_text_digits(const double *x, int n, int64_t *out) {

@@ -448,6 +448,7 @@ PackedEvent pack_event_masks(const miso_params_t &p, const FragmentDist *fd, int
       }
     }
     for (int k = 0; k < K; k++) e.consts[k] = std::log(ass[k]);
+    e.eff = ass;
     e.sfix_table.resize(static_cast<size_t>(K) * il);
     for (size_t i = 0; i < e.sfix_table.size(); i++) {
       const double s = isoscore_tab[i];

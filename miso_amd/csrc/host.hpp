@@ -89,7 +89,8 @@ struct PackedEvent {
   bool paired = false;
   std::vector<double> hyper;            // K
   std::vector<double> consts;           // 3K+5 doubles, layout in device.hpp
-  std::vector<double> eff;              // single-end: K effective lengths, 0 where not positive (miso.c:136-138) -- the exact mode's e_k
+  std::vector<double> eff;              // single-end: K effective lengths, 0 where not positive (miso.c:136-138) -- the exact mode's e_k;
+                                        // paired-end: A_k = exp(assscores_k) (miso_paired.c:403-419) -- the paired exact mode's
   std::vector<int32_t> base_count;      // K
   int64_t base_sfix = 0;                // paired: sum of fixed reads' scores, 2^-26 fixed point
   int32_t base_bad = 0;                 // paired: a fixed read has a non-finite score

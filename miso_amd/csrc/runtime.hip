@@ -456,6 +456,20 @@ void miso_batch::build_slots() {
         MISO_FAIL(MISO_EINTERNAL, "exact-posterior mode: a two-isoform event was packed without its effective lengths");
       is_exact[i] = exact_eligible(false, 2, events[i].eff.data(), events[i].hyper.data());
     }
+  // (the paired-end mode, miso_batch_set_exact_paired: A0, A1 in the place of the effective lengths; no pair of the event
+  // on a non-finite score entry -- base_bad the fixed pairs, pe_delta the drawing ones; the batch's smallest
+  // fragment-length probability at least 2^-63, so that sixteen factors multiply to a normal number; indices in 16 bits)
+  if (exact_paired && p.paired && p.algorithm == MISO_ALGO_REASSIGN) {
+    double fp_min = 1.0;
+    for (double v : fd.prob) fp_min = std::min(fp_min, v);
+    const bool batch_ok = !fd.prob.empty() && fp_min >= EXACT_PAIRED_MIN_PROB && fd.prob.size() <= 0xFFFFu;
+    for (int i = 0; i < n && batch_ok; i++) {
+      if (events[i].K != 2) continue;
+      if (events[i].eff.size() != 2 || events[i].hyper.size() != 2)
+        MISO_FAIL(MISO_EINTERNAL, "paired exact-posterior mode: a two-isoform event was packed without its A0, A1");
+      is_exact[i] = exact_paired_eligible(2, events[i].eff.data(), events[i].hyper.data(), events[i].base_bad != 0 || !events[i].pe_delta);
+    }
+  }
   for (int i = 0; i < n; i++) (is_exact[i] ? ex : (events[i].K == 2 && !k2_general) ? k2 : gen).push_back(i);
   // (paired-end: the events sampler_k2's MODE 2 can take come first)
   use_delta = !knobs.no_pe_delta;   // fixed here: the slot order depends on it
@@ -552,7 +566,7 @@ void miso_batch::build_slots() {
   std::vector<double> eff2;
   for (int i : ex) { eff2.push_back(events[i].eff[0]); eff2.push_back(events[i].eff[1]); }
   put(exact_eff, eff2);
-  slots_exact = exact; exact_sums.clear(); exact_sums_level = -1.0;
+  slots_exact = exact_any(); exact_sums.clear(); exact_sums_level = -1.0;
   if (!d_slots) HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_slots), std::max<size_t>(n, 1) * sizeof(int32_t)));
   if (n) HIP_OK(hipMemcpy(d_slots, k2.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
 }
@@ -711,7 +725,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   if (!uploaded) MISO_FAIL(MISO_EINVAL, "batch not uploaded");
   HIP_OK(hipSetDevice(device));
   knobs = Knobs::from_env();
-  if (slots_exact != exact) {   // miso_batch_set_exact after the upload: the launch lists anew
+  if (slots_exact != exact_any()) {   // miso_batch_set_exact / _paired after the upload: the launch lists anew
     HIP_OK(hipStreamSynchronize(stream));
     for (GenRun &r : gen_runs) { r.wave_tab.reset(); r.coop.reset(); }
     build_slots();
@@ -1794,11 +1808,11 @@ void miso_batch::launch_planned(const KernelArgs &a, const KernelArgs &k2a) {
 void miso_batch::launch_exact(const KernelArgs &a) {
   KernelArgs ka = a;
   ka.slot_event = d_slots + n_k2 + n_gen; ka.n_slots = n_exact;
-  note_kernel("exact_sample");
+  note_kernel(p.paired ? "exact_paired_sample" : "exact_sample");
   const double *eff = exact_eff.d;
   int Sn = S();
   void *args[] = {&ka, &eff, &Sn};
-  (void) hipLaunchKernel(fn(&exact_sample), dim3(static_cast<unsigned>(n_exact)), dim3(64), args, 0, stream_for_next());
+  (void) hipLaunchKernel(p.paired ? exact_paired_sample_fn() : fn(&exact_sample), dim3(static_cast<unsigned>(n_exact)), dim3(64), args, 0, stream_for_next());
   HIP_OK(hipGetLastError());
 }
 
@@ -1819,8 +1833,16 @@ void miso_batch::exact_summaries(double confidence_level) {
   const double alpha = 1 - confidence_level;
   const double prob[2] = {alpha / 2, 1 - alpha / 2};
   std::vector<double> st(static_cast<size_t>(n_exact) * 7), out8(static_cast<size_t>(n_exact) * 8), q(static_cast<size_t>(n_exact) * 4);
-  for (int j = 0; j < n_exact; j++) exact_stats7(h_slots[n_k2 + n_gen + j], &st[static_cast<size_t>(j) * 7]);
-  exact_probe_run(st.data(), n_exact, prob, 2, out8.data(), q.data(), stream);
+  if (p.paired) {   // the pairs' records are on the device: the events of the exact list themselves
+    KernelArgs ka{};
+    ka.events = d_events; ka.in_pool = d_in; ka.out_pool = d_out; ka.frag_prob = d_fp;
+    ka.il = static_cast<int32_t>(fd.prob.size());
+    ka.slot_event = d_slots + n_k2 + n_gen; ka.n_slots = n_exact;
+    exact_paired_probe_run(&ka, exact_eff.d, nullptr, nullptr, nullptr, n_exact, prob, 2, out8.data(), q.data(), stream);
+  } else {
+    for (int j = 0; j < n_exact; j++) exact_stats7(h_slots[n_k2 + n_gen + j], &st[static_cast<size_t>(j) * 7]);
+    exact_probe_run(st.data(), n_exact, prob, 2, out8.data(), q.data(), stream);
+  }
   exact_sums.assign(static_cast<size_t>(n_exact) * 6, 0.0);
   for (int j = 0; j < n_exact; j++) {
     double *r = &exact_sums[static_cast<size_t>(j) * 6];
@@ -2076,7 +2098,7 @@ std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
     add_stat(run_name(ri), static_cast<double>(waves), trips, static_cast<double>(chains), words);
   }
   if (n_exact > 0) {   // one wavefront per event, no chains: `chains` counts the events, `words` their sample uniforms
-    add_stat("exact_sample", static_cast<double>(n_exact), 0.0, static_cast<double>(n_exact), static_cast<double>(n_exact) * S());
+    add_stat(p.paired ? "exact_paired_sample" : "exact_sample", static_cast<double>(n_exact), 0.0, static_cast<double>(n_exact), static_cast<double>(n_exact) * S());
     out.back().iterations = 1.0;
   }
   return out;

@@ -133,7 +133,8 @@ class GenesDispatcher(object):
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
-                 exact_compare=False, delta_thresholds=None):
+                 exact_compare=False, delta_thresholds=None, exact_paired=False):
+        self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
         self.summary_only = bool(summary_only)
         self.exact = bool(exact)       # --exact: handed on to every worker
         # --exact-compare: beside the `.miso_bf` table the exact comparison's `.miso_bf_exact` (compare.py), merged like a
@@ -328,6 +329,8 @@ class GenesDispatcher(object):
                 cmd += ["--seed", str(self.seed)]
             if self.exact:
                 cmd += ["--exact"]
+            if self.exact_paired:
+                cmd += ["--exact-paired"]
             log = os.path.join(self.batch_logs_dir, "batch-%d-%s.log"
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
@@ -404,7 +407,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
-                          exact_compare=False, delta_thresholds=None):
+                          exact_compare=False, delta_thresholds=None, exact_paired=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -416,7 +419,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            settings_fname=settings_fname, paired_end=paired_end, num_proc=num_proc,
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
-                           prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare,
+                           prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
                            delta_thresholds=delta_thresholds).run()
 
 
@@ -448,6 +451,11 @@ def main(argv=None):
                     help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
                          "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
                          "other events are sampled as always.  Also the settings key `exact` under [sampler].")
+    ap.add_argument("--exact-paired", action="store_true",
+                    help="with --paired-end: paired-end two-isoform events run no chains -- the posterior of Psi, a product over "
+                         "the event's read pairs, is tabulated once per event on the GPU and the .miso file's samples are "
+                         "independent draws from it (percent_accept=100); other events are sampled as always.  Also the "
+                         "settings key `exact_paired` under [sampler].")
     ap.add_argument("--exact-compare", action="store_true",
                     help="with --compare and the exact mode: also write OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf_exact -- "
                          "for the events the exact mode took in both samples the Bayes factor and P(|delta Psi| >= T) come from the "
@@ -469,7 +477,9 @@ def main(argv=None):
     settings_filename = None if a.settings_filename is None else \
         os.path.abspath(os.path.expanduser(a.settings_filename))
     Settings.load(settings_filename)
-    if a.exact_compare:     # argument errors, before any work
+    if a.exact_paired and a.paired_end is None:     # argument errors, before any work
+        ap.error("--exact-paired goes with --paired-end")
+    if a.exact_compare:
         if a.compare is None:
             ap.error("--exact-compare goes with --compare")
         if a.paired_end is not None:
@@ -504,7 +514,7 @@ def main(argv=None):
                                        compare_bam=None if a.compare is None else
                                        os.path.abspath(os.path.expanduser(a.compare)),
                                        labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics,
-                                       exact=a.exact, exact_compare=a.exact_compare,
+                                       exact=a.exact, exact_compare=a.exact_compare, exact_paired=a.exact_paired,
                                        delta_thresholds=a.delta_psi_thresholds)
     except PrefilterError as err:
         print("Error: %s" % err)

@@ -24,6 +24,9 @@ import pysplicing  # noqa: E402  (miso_amd/pysplicing)
 import capi  # noqa: E402  (miso_amd/capi.py: the batch object behind run_sampler_batch)
 
 capi.InternalError = pysplicing.InternalError   # one exception type for callers of this module
+
+# the environment variable that asks for the paired-end exact-posterior mode (MISOSampler.exact_paired)
+EXACT_PAIRED_ENV = "MISO_EXACT_PAIRED"
 import summary  # noqa: E402  (miso_amd/summary.py)
 import diagnostics  # noqa: E402  (miso_amd/diagnostics.py)
 import compare  # noqa: E402  (miso_amd/compare.py)
@@ -181,6 +184,13 @@ class MISOSampler:
                                  summary_file=summary_file, confidence_level=confidence_level,
                                  threads=threads, diagnostics_file=diagnostics_file)
 
+    def exact_paired(self):
+        """the paired-end exact-posterior mode is asked for: params["exact_paired"], else MISO_EXACT_PAIRED=1; never on a
+        single-end run"""
+        if not self.paired_end:
+            return False
+        return bool(int(self.params.get("exact_paired", os.environ.get(EXACT_PAIRED_ENV, 0)) or 0))
+
     def prepare_batch(self, num_iters, events, num_chains=6, burn_in=1000, lag=2,
                       start_cond=pysplicing.MISO_START_AUTO, stop_cond=pysplicing.MISO_STOP_FIXEDNO,
                       verbose=False):
@@ -198,7 +208,10 @@ class MISOSampler:
                            collapsed=0 if self.paired_end else int(self.params.get("collapsed", os.environ.get("MISO_COLLAPSED", 0)) or 0),
                            # opt-in, single-end: the exact-posterior mode of the eligible two-isoform events (include/miso_amd.h
                            # miso_batch_set_exact); params["exact"] or MISO_EXACT=1 in the environment
-                           exact=False if self.paired_end else bool(int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0)))
+                           exact=False if self.paired_end else bool(int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0)),
+                           # opt-in, paired-end: the exact-posterior mode of the eligible paired-end two-isoform events, a switch
+                           # of its own (miso_batch_set_exact_paired); params["exact_paired"] or MISO_EXACT_PAIRED=1
+                           exact_paired=self.exact_paired())
         written = [None] * len(events)
         slots = []
         from sam_utils import STRAND_RULES
@@ -455,6 +468,8 @@ class MISOSampler:
                 kw["diagnostics"] = True
             if not self.paired_end and int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
                 kw["exact"] = True          # the exact-posterior mode, as in prepare_batch
+            if self.exact_paired():
+                kw["exact_paired"] = True   # ... and the paired-end one
             if xthr is not None:
                 kw["exact_compare"] = compare.delta_points(xthr)
             res = pysplicing.MISOCompareBatch(

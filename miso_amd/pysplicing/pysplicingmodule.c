@@ -30,6 +30,8 @@
  *   first_event_id  global index of the first event (sharding a run over GPUs).
  *   exact=True      MISOBatch / MISOCompareBatch: the eligible single-end two-isoform events run no chain, their
  *                   samples are independent draws from the tabulated posterior of psi (miso_batch_set_exact).
+ *                   MISOPairedBatch(exact=True) / MISOCompareBatch(paired=..., exact_paired=True): the same for the
+ *                   eligible paired-end two-isoform events (miso_batch_set_exact_paired).
  *   exact_compare=(z, ...)  MISOCompareBatch with exact=True: the exact comparison (miso_batch_compare_exact) at these
  *                   delta psi points, appended as the LAST element of the result.
  * The functions of the module that are not on the sampler path raise NotImplementedError.
@@ -380,12 +382,15 @@ static int parse_level(PyObject *obj, double *conf) {
   return 0;
 }
 
-/* a new batch holding `events` = ((gff, readpos, readcigar[, hyperp]), ...); exact: miso_batch_set_exact */
+/* a new batch holding `events` = ((gff, readpos, readcigar[, hyperp]), ...); exact: 1 miso_batch_set_exact, 2
+   miso_batch_set_exact_paired */
 static miso_batch_t *fill_batch(PyObject *events, miso_params_t *p, int exact) {
   miso_batch_t *b = NULL; Py_ssize_t i, n; int rc;
   if (!PyTuple_Check(events)) { PyErr_SetString(PyExc_TypeError, "Need a tuple"); return NULL; }
   if ((rc = miso_batch_create(p, &b))) { raise_miso(rc); return NULL; }
-  if (exact && (rc = miso_batch_set_exact(b, 1))) { raise_miso(rc); miso_batch_destroy(b); return NULL; }
+  if (exact && (rc = exact == 2 ? miso_batch_set_exact_paired(b, 1) : miso_batch_set_exact(b, 1))) {
+    raise_miso(rc); miso_batch_destroy(b); return NULL;
+  }
   n = PyTuple_Size(events);
   for (i = 0; i < n; i++) {
     PyObject *ev = PyTuple_GET_ITEM(events, i);
@@ -457,19 +462,21 @@ static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seed
 static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
-                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", NULL};
+                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL, *xcobj = NULL, *xc = NULL;
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
   int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
+  int exact_paired = 0;             /* exact_paired=True (with paired=): miso_batch_set_exact_paired */
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
   int start = MISO_START_AUTO, stop = MISO_STOP_FIXEDNO, rc;
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppO", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOp", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
-                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj)) return NULL;
+                                   &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
+                                   &exact_paired)) return NULL;
   if (xcobj == Py_None) xcobj = NULL;
   if (xcobj) {
     Py_ssize_t nz;
@@ -496,8 +503,8 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   if (!PyTuple_Check(ev1) || !PyTuple_Check(ev2)) { PyErr_SetString(PyExc_TypeError, "Need a tuple"); return NULL; }
   n = PyTuple_Size(ev1);
   if (PyTuple_Size(ev2) != n) { PyErr_SetString(PyExc_ValueError, "the two samples must list the same events"); return NULL; }
-  if (!(b1 = fill_batch(ev1, &p, exact))) goto done;
-  if (!(b2 = fill_batch(ev2, &p, exact))) goto done;
+  if (!(b1 = fill_batch(ev1, &p, exact_paired ? 2 : exact))) goto done;
+  if (!(b2 = fill_batch(ev2, &p, exact_paired ? 2 : exact))) goto done;
   /* event_ids: every event's id in the Philox counter (its number in the caller's full event list), so
      that events dropped by the caller's skip rules, the chunking and the number of GPUs change nobody's
      random stream -- as miso_batch_set_event_id does for MISOBatch's callers */
@@ -587,17 +594,18 @@ static PyObject *py_miso_batch(PyObject *self, PyObject *args, PyObject *kw) {
 static PyObject *py_miso_paired_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events", "readLength", "normalMean", "normalVar", "numDevs",
                            "noIterations", "noBurnIn", "noLag", "overhang", "no_chains", "start",
-                           "stop", "seed", "first_event_id", "summary", NULL};
+                           "stop", "seed", "first_event_id", "summary", "exact", NULL};
   PyObject *events, *seedobj = NULL, *summaryobj = NULL;
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
   int start = MISO_START_AUTO, stop = MISO_STOP_FIXEDNO;
+  int exact = 0;   /* exact=True: the eligible two-isoform events take the paired exact-posterior mode (miso_batch_set_exact_paired) */
   double mean, var, devs; unsigned int first = 0; miso_params_t p;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "Oiddd|iiiiiii$OIO", kwlist, &events, &readLength, &mean,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "Oiddd|iiiiiii$OIOp", kwlist, &events, &readLength, &mean,
                                    &var, &devs, &iters, &burn, &lag, &overhang, &chains, &start,
-                                   &stop, &seedobj, &first, &summaryobj)) return NULL;
+                                   &stop, &seedobj, &first, &summaryobj, &exact)) return NULL;
   fill_params(&p, 1, readLength, overhang, chains, iters, burn, lag, MISO_ALGO_REASSIGN, start, stop,
               mean, var, devs);
-  return batch_common(events, &p, seedobj, first, summaryobj, 0);
+  return batch_common(events, &p, seedobj, first, summaryobj, exact ? 2 : 0);
 }
 
 /* ---- simulateReads / simulatePairedReads (pysplicing.c:280-330, 462-520) ---- */

@@ -147,13 +147,16 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
-                     diagnostics_file=None, exact=None):
+                     diagnostics_file=None, exact=None, exact_paired=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
     diagnostics table of this run (diagnostics.py), per launch from the resident samples, merged like the summary parts.
-    exact: single-end two-isoform events take the exact-posterior mode (None: the settings' `exact` key)."""
+    exact: single-end two-isoform events take the exact-posterior mode (None: the settings' `exact` key).
+    exact_paired: the same switch for the paired-end two-isoform events of a --paired-end run (None: the settings'
+    `exact_paired` key); nothing on a single-end run."""
     exact = Settings.get_exact() if exact is None else bool(exact)
+    exact_paired = Settings.get_exact_paired() if exact_paired is None else bool(exact_paired)
     os.makedirs(output_dir, exist_ok=True)
     if gene_entries is None:
         gene_entries = [(g, gff_index_filename) for g in gene_ids]
@@ -244,6 +247,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             if paired_end:
                 params = miso.get_paired_end_sampler_params(2, mean_frag_len, frag_variance, read_len,
                                                             overhang_len=overhang_len)
+                if exact_paired:
+                    params["exact_paired"] = 1     # miso_sampler.py prepare_batch
             else:
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
                 if exact:
@@ -318,7 +323,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
-                     exact_comparison_file=None, delta_thresholds=None):
+                     exact_comparison_file=None, delta_thresholds=None, exact_paired=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -336,6 +341,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         _check_device(device)
         os.environ["MISO_DEVICE"] = str(int(device))
     exact = Settings.get_exact() if exact is None else bool(exact)
+    exact_paired = Settings.get_exact_paired() if exact_paired is None else bool(exact_paired)
     if exact_comparison_file is not None and (paired_end or not exact):
         raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
     p = Settings.get_sampler_params()
@@ -362,6 +368,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         if paired_end:
             params = miso.get_paired_end_sampler_params(2, mean_frag_len, frag_variance, read_len,
                                                         overhang_len=overhang_len)
+            if exact_paired:
+                params["exact_paired"] = 1     # miso_sampler.py prepare_batch
         else:
             params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
             if exact:
@@ -398,6 +406,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             if paired_end:
                 params = miso.get_paired_end_sampler_params(2, mean_frag_len, frag_variance, read_len,
                                                             overhang_len=overhang_len)
+                if exact_paired:
+                    params["exact_paired"] = 1     # miso_sampler.py prepare_batch
             else:
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
                 if exact:
@@ -462,6 +472,9 @@ def main(argv=None):
     ap.add_argument("--exact", action="store_true",
                     help="single-end two-isoform events: independent draws from the exact posterior of Psi instead of chains "
                          "(also the settings key `exact`)")
+    ap.add_argument("--exact-paired", action="store_true",
+                    help="with --paired-end: paired-end two-isoform events draw independently from the exact posterior of Psi "
+                         "instead of running chains (also the settings key `exact_paired`)")
     ap.add_argument("--exact-comparison-file", default=None, metavar="F",
                     help="with --compare-genes-from-file and the exact mode: also write the exact comparison's table "
                          "(Bayes factors and P(|delta psi| >= T) from the posteriors' tables, no sampling error)")
@@ -484,6 +497,9 @@ def main(argv=None):
     overhang_len = a.overhang_len if a.overhang_len is not None else 1
     paired_end = tuple(a.paired_end) if a.paired_end else None
     exact = bool(a.exact) or Settings.get_exact()       # the flag, or `exact = True` under [sampler] of the settings file
+    if a.exact_paired and not paired_end:
+        ap.error("--exact-paired goes with --paired-end")
+    exact_paired = bool(paired_end) and (bool(a.exact_paired) or Settings.get_exact_paired())
     if a.diagnostics_file and not a.compute_genes_from_file:
         print("Error: --diagnostics-file goes with --compute-genes-from-file.")
         return 1
@@ -510,7 +526,7 @@ def main(argv=None):
                              samples=samples, diagnostics_files=a.diagnostics_files, exact=exact,
                              exact_comparison_file=(os.path.abspath(os.path.expanduser(a.exact_comparison_file))
                                                     if a.exact_comparison_file else None),
-                             delta_thresholds=a.delta_psi_thresholds)
+                             delta_thresholds=a.delta_psi_thresholds, exact_paired=exact_paired)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -525,7 +541,7 @@ def main(argv=None):
                          seed=a.seed, first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
                          summary_file=a.summary_file,
                          write_files=not (a.no_miso_files and a.summary_file),
-                         diagnostics_file=a.diagnostics_file, exact=exact)
+                         diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")
@@ -533,7 +549,8 @@ def main(argv=None):
                                                   for p in a.compute_gene_psi[1:])
         compute_gene_psi(gene_ids, gff_filename, bam_filename, output_dir, a.read_len,
                          overhang_len, paired_end=paired_end, event_type=a.event_type,
-                         seed=a.seed, first_event_id=a.first_event_id, device=a.device, exact=exact)
+                         seed=a.seed, first_event_id=a.first_event_id, device=a.device, exact=exact,
+                         exact_paired=exact_paired)
     else:
         ap.print_help()
     return 0

@@ -67,6 +67,20 @@ class Settings(object):
         return bool(value)
 
     @classmethod
+    def get_exact_paired(cls, default_exact_paired=False):
+        """`exact_paired = True` under [sampler]: paired-end two-isoform events take the exact-posterior mode
+        (miso --run --paired-end M SD --exact-paired); the spellings of get_exact."""
+        value = cls.global_settings.get("exact_paired", default_exact_paired)
+        if isinstance(value, str):
+            low = value.strip().lower()
+            if low in ("true", "yes", "on", "1"):
+                return True
+            if low in ("false", "no", "off", "0", ""):
+                return False
+            raise ValueError("Error: Invalid exact_paired parameter %s (True or False)" % value)
+        return bool(value)
+
+    @classmethod
     def get_min_event_reads(cls, default_min_reads=20):
         return cls.global_settings.get("min_event_reads", default_min_reads)
 
