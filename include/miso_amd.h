@@ -397,7 +397,17 @@ int miso_batch_compare_exact(miso_batch_t *sample1, miso_batch_t *sample2, const
 int miso_batch_get_exact_comparison(const miso_batch_t *sample1, int event_index, double *mean1, double *mean2,
                                     double *log_density_at_0, double *bayes_factor, double *log10_bayes_factor,
                                     double *cdf /* n_z */, int *was_exact);
-/* Kernel time (HIP events) of the last miso_batch_compare and miso_batch_compare_exact stored in this batch, ms; 0 before. */
+/* The same comparison for two PAIRED-END batches that both ran with miso_batch_set_exact_paired
+   (csrc/kernels_exact_paired_compare.hip).  Preconditions and errors as miso_batch_compare_exact; an
+   event is comparable when the paired exact mode took it in both batches (nothing has to be equal between the samples:
+   each has its own A = exp(assscores), its own pairs).  The product of the two posteriors is tabulated as a density of
+   its own over both samples' resident pair records -- pooled exponents, hyperparameters h1 + h2 - 1, both pair sums, both
+   denominators --, and log_density_at_0, the Bayes factor and cdf follow as above.  MISO_EINVAL when either batch is
+   single-end or lacks the paired exact mode.  Results are stored in sample1 in the place of miso_batch_compare_exact's and
+   read through miso_batch_get_exact_comparison; the launch appears in miso_batch_last_kernels as exact_paired_compare. */
+int miso_batch_compare_exact_paired(miso_batch_t *sample1, miso_batch_t *sample2, const double *z, int n_z);
+/* Kernel time (HIP events) of the last miso_batch_compare and of the last miso_batch_compare_exact or
+   miso_batch_compare_exact_paired stored in this batch, ms; 0 before. */
 int miso_batch_compare_ms(const miso_batch_t *sample1, float *compare_ms, float *exact_compare_ms);
 
 /* Every pair of two groups of samples (biological replicates) in one device pass.  group1[i], group2[j]: batches that
@@ -569,6 +579,12 @@ int miso_selftest_exact_paired(const double *stats6, const double *m, const int6
    cdf at z[0 .. n_z)} as miso_batch_get_exact_comparison returns them.  MISO_EINVAL when a pair's e0, e1 differ between
    its samples (bit-wise), when a pair is not eligible for the exact mode, n_z is outside [0, 8] or a z outside (-1, 1). */
 int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, int n, const double *z, int n_z, double *out);
+/* kernels_exact_paired_compare.hip on caller-given elements, one wavefront per pair: stats6_s, m_s, offs_s in
+   miso_selftest_exact_paired's layout, sample s = 1, 2 (the two samples' pair lists are independent of each other).
+   out[(5 + n_z) i ...] as miso_selftest_exact_compare's.  MISO_EINVAL when an element is not eligible for the paired exact
+   mode, a probability lies outside [2^-63, 1], n_z is outside [0, 8] or a z outside (-1, 1). */
+int miso_selftest_exact_paired_compare(const double *stats6_1, const double *m_1, const int64_t *offs_1, const double *stats6_2,
+                                       const double *m_2, const int64_t *offs_2, int n, const double *z, int n_z, double *out);
 /* csrc/text_digits.hpp text_digits, the rounding of summarize_as_text: out[i] = x[i] x 10^4 rounded to the nearest integer,
    ties to even, on the exact product -- the digits of "%.4f" of x[i], sign included.  Finite |x[i]| < 2^38. */
 int miso_selftest_text_digits(const double *x, int n, int64_t *out);

@@ -381,9 +381,17 @@ class Batch:
         check(lib().miso_batch_compare_exact(self.handle, other.handle, _p(zz), C.c_int(len(zz))))
         self._exact_nz = len(zz)
 
+    def compare_exact_paired(self, other, z=()):
+        """compare_exact() for two paired-end batches that both ran with exact_paired=True: the product of the two
+        posteriors is tabulated over both samples' resident pairs (miso_batch_compare_exact_paired in include/miso_amd.h).
+        The results take compare_exact()'s place: exact_comparison(i) reads them."""
+        zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+        check(lib().miso_batch_compare_exact_paired(self.handle, other.handle, _p(zz), C.c_int(len(zz))))
+        self._exact_nz = len(zz)
+
     def exact_comparison(self, i):
-        """(mean1, mean2, log_density_at_0, bayes_factor, log10_bayes_factor, cdf[n_z]) of event i after compare_exact();
-        None when the pair is not exact-comparable (miso_batch_get_exact_comparison)."""
+        """(mean1, mean2, log_density_at_0, bayes_factor, log10_bayes_factor, cdf[n_z]) of event i after compare_exact() or
+        compare_exact_paired(); None when the pair is not exact-comparable (miso_batch_get_exact_comparison)."""
         v = [C.c_double(0.0) for _ in range(5)]
         cdf = np.zeros(getattr(self, "_exact_nz", 0))
         was = C.c_int(0)
@@ -391,7 +399,7 @@ class Batch:
         return tuple(x.value for x in v) + (cdf,) if was.value else None
 
     def compare_ms(self):
-        """(kernel ms of the last compare(), of the last compare_exact()) stored in this batch"""
+        """(kernel ms of the last compare(), of the last compare_exact() or compare_exact_paired()) stored in this batch"""
         a, b = C.c_float(0), C.c_float(0)
         check(lib().miso_batch_compare_ms(self.handle, C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
@@ -855,6 +863,35 @@ def selftest_exact_paired(stats6, pairs, probs):
     icdf = np.zeros((len(st), len(pr), 2))
     check(lib().miso_selftest_exact_paired(_p(st), _p(m), _p(offs), len(st), _p(pr), len(pr), _p(out8), _p(icdf)))
     return out8, icdf
+
+
+def _pair_lists(stats6, pairs):
+    """(stats6 [n, 6], m [*, 2], offs [n + 1]) of miso_selftest_exact_paired's layout"""
+    st = np.ascontiguousarray(stats6, dtype=np.float64).reshape(-1, 6)
+    if len(pairs) != len(st):
+        raise ValueError("one list of pairs per element")
+    rows = [np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 2) for q in pairs]
+    offs = np.zeros(len(st) + 1, np.int64)
+    offs[1:] = np.cumsum([len(r) for r in rows])
+    m = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 2)))
+    if len(m) == 0:
+        m = np.zeros((1, 2))           # (a valid pointer; no element reads it)
+    return st, m, offs
+
+
+def selftest_exact_paired_compare(stats6_1, pairs_1, stats6_2, pairs_2, z=()):
+    """csrc/kernels_exact_paired_compare.hip on caller-given elements: stats6_s[j] = (n10, n01, A0, A1, h0, h1) and
+    pairs_s[j] = [(m0, m1), ...] of pair j in sample s -> out [n, 5 + len(z)] as selftest_exact_compare's --
+    include/miso_amd.h miso_selftest_exact_paired_compare"""
+    s1, m1, o1 = _pair_lists(stats6_1, pairs_1)
+    s2, m2, o2 = _pair_lists(stats6_2, pairs_2)
+    if len(s1) != len(s2):
+        raise ValueError("stats6_1, stats6_2: one row per pair each")
+    zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+    out = np.zeros((len(s1), 5 + len(zz)))
+    check(lib().miso_selftest_exact_paired_compare(_p(s1), _p(m1), _p(o1), _p(s2), _p(m2), _p(o2), C.c_int(len(s1)),
+                                                   _p(zz), C.c_int(len(zz)), _p(out)))
+    return out
 
 
 def selftest_exact_compare(stats7_1, stats7_2, z=()):

@@ -52,6 +52,24 @@ constexpr double EXACT_PAIRED_MIN_PROB = 1.0 / 9223372036854775808.0;   // 2^-63
 inline bool exact_paired_eligible(int K, const double *A, const double *hyper, bool any_bad) {
   return K == 2 && A[0] > 0 && A[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1 && !any_bad;
 }
+// kernels_exact_paired_compare.hip: pairs of such posteriors compared (miso_batch_compare_exact_paired,
+// miso_selftest_exact_paired_compare).  One sample's side of the n pairs, as the host driver takes it: stats6 (host) =
+// {n10, n01, A0, A1, h0, h1} per pair, and the drawing pairs EITHER as caller-given probabilities m / offs (host, the
+// selftest's layout) OR -- m == null -- as the records of a resident batch (device pointers), pair i being event list[i]
+struct ExactPairedCmpInput {
+  const double *stats6;
+  const double *m; const int64_t *offs;
+  const DevEvent *events; const unsigned char *in_pool; const double *frag_prob; int il;
+};
+// ... and as the kernel takes it (every pointer on the device)
+struct ExactPairedCmpSide {
+  const double *stats6;
+  const double *mm; const int64_t *offs;
+  const DevEvent *events; const unsigned char *in_pool; const double *frag_prob; int il;
+};
+// out: 5 + n_z doubles per pair, as exact_compare_run's
+void exact_paired_compare_run(const ExactPairedCmpInput &in1, const ExactPairedCmpInput &in2, const int32_t *list, int n, const double *z,
+                              int n_z, double *out, hipStream_t st = nullptr, float *ms = nullptr);
 // kernels_compare_groups.hip
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
@@ -165,8 +183,9 @@ struct miso_batch {
   std::vector<char> exact_cmp_ok;
   int exact_cmp_nz = 0;
   bool exact_compared = false;
-  float compare_ms = 0.f, exact_compare_ms = 0.f;   // kernel time of the last compare / compare_exact
+  float compare_ms = 0.f, exact_compare_ms = 0.f;   // kernel time of the last compare / compare_exact or compare_exact_paired
   void compare_exact(miso_batch &other, const double *z, int n_z);
+  void compare_exact_paired(miso_batch &other, const double *z, int n_z);   // miso_batch_compare_exact_paired: the same stores
   miso::LanePlan k2_plan;         // sampler_k2_multi: the runs of equal lanes per chain (runtime.hip), valid for k2_plan_key
   long k2_plan_key = -1;
   miso::CoopTable k2_coop_se, k2w_coop;   // the two plans' chains on several workgroups (key: the plan's wide run)

@@ -868,12 +868,20 @@ int miso_batch_compare_exact(miso_batch_t *a, miso_batch_t *b, const double *z, 
   });
 }
 
+int miso_batch_compare_exact_paired(miso_batch_t *a, miso_batch_t *b, const double *z, int n_z) {
+  return guarded([&] {
+    need(a, "batch"); need(b, "batch");
+    if (n_z > 0) need(z, "z");
+    a->compare_exact_paired(*b, z, n_z);
+  });
+}
+
 int miso_batch_get_exact_comparison(const miso_batch_t *b, int i, double *mean1, double *mean2, double *log_density_at_0,
                                     double *bayes_factor, double *log10_bayes_factor, double *cdf, int *was_exact) {
   return guarded([&] {
     need(b, "batch"); need(was_exact, "was_exact");
     (void) event_at(b, i);
-    if (!b->exact_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_exact has not run");
+    if (!b->exact_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_exact / miso_batch_compare_exact_paired has not run");
     *was_exact = b->exact_cmp_ok[i] ? 1 : 0;
     if (!*was_exact) return;
     const double *r = &b->h_exact_cmp[static_cast<size_t>(i) * (5 + b->exact_cmp_nz)];
@@ -1161,6 +1169,20 @@ int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, 
     if (n > 0) { need(stats7_1, "stats7_1"); need(stats7_2, "stats7_2"); need(out, "out"); }
     if (n_z > 0) need(z, "z");
     exact_compare_run(stats7_1, stats7_2, n, z, n_z, out);
+  });
+}
+int miso_selftest_exact_paired_compare(const double *stats6_1, const double *m_1, const int64_t *offs_1, const double *stats6_2,
+                                       const double *m_2, const int64_t *offs_2, int n, const double *z, int n_z, double *out) {
+  return guarded([&] {
+    if (n > 0) { need(stats6_1, "stats6_1"); need(stats6_2, "stats6_2"); need(offs_1, "offs_1"); need(offs_2, "offs_2"); need(out, "out"); }
+    if (n > 0 && offs_1[0] == 0 && offs_1[n] > 0) need(m_1, "m_1");
+    if (n > 0 && offs_2[0] == 0 && offs_2[n] > 0) need(m_2, "m_2");
+    if (n_z > 0) need(z, "z");
+    // (an element without a pair still takes the caller-given route: a placeholder stands for the empty list)
+    static const double none[2] = {1.0, 1.0};
+    const ExactPairedCmpInput in1{stats6_1, m_1 ? m_1 : none, offs_1, nullptr, nullptr, nullptr, 0};
+    const ExactPairedCmpInput in2{stats6_2, m_2 ? m_2 : none, offs_2, nullptr, nullptr, nullptr, 0};
+    exact_paired_compare_run(in1, in2, nullptr, n, z, n_z, out);
   });
 }
 int miso_selftest_exact_paired(const double *stats6, const double *m, const int64_t *offs, int n, const double *prob, int n_prob,

@@ -1,6 +1,7 @@
 // exact_paired.hpp -- the paired-end exact-posterior mode's device functions (the scheme is described in
-// kernels_exact_paired.hip, its only user).  Built on exact_posterior.hpp, which it leaves as it is: ExactStats / exact_point
-// with e = A give the pair-free part of the density, exact_invert the inverse of the table.  -ffp-contract=off.
+// kernels_exact_paired.hip; kernels_exact_paired_compare.hip, DESIGN.md 18, tabulates the product of two such densities with
+// them).  Built on exact_posterior.hpp, which it leaves as it is: ExactStats / exact_point with e = A give the pair-free part
+// of the density, exact_invert the inverse of the table.  -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,17 +84,49 @@ __device__ __forceinline__ void exact_pair_logsum(const ExactPairs &p, double *m
   }
 }
 
+// A density has one segment -- one sample's statistics and pairs (s, p below; kernels_exact_paired.hip) -- or two: the
+// product of two samples' densities of one event (kernels_exact_paired_compare.hip), whose second segment
+// brings its own denominator term and its own pair sum:
+//     g12 = ((((0 - lin) - c L) - n1 ld1) - n2 ld2) + (P1 + P2),   c = (a + b) - (n1 + n2),
+// s then holding the pooled exponents and that c, with n and e0, e1 of sample 1.  Each sample's pairs go in their own
+// blocks of sixteen, sample 1 first.  ExactOneSegment adds nothing, and the code is what it was without the parameter.
+struct ExactOneSegment {
+  __device__ __forceinline__ void point(double, const ExactPoint &, double &) const {}
+  template <int NP>
+  __device__ __forceinline__ void pairs(double *, int, const double (&)[NP], const double (&)[NP], double (&)[NP]) const {}
+};
+struct ExactSecondSegment {
+  double n, e0, e1;   // sample 2's pair count and A0, A1
+  ExactPairs p;       // ... and drawing pairs
+  __device__ __forceinline__ void point(double t, const ExactPoint &pt, double &g) const {
+    const double E = miso_det_exp(-pt.at);
+    const double Ee0 = E * e0, Ee1 = E * e1;
+    const double den = t >= 0.0 ? e0 + Ee1 : Ee0 + e1;
+    g = g - n * miso_det_log(den);
+  }
+  template <int NP>
+  __device__ __forceinline__ void pairs(double *mbuf, int lane, const double (&x)[NP], const double (&y)[NP], double (&P)[NP]) const {
+    double P2[NP];
+    exact_pair_logsum<NP>(p, mbuf, lane, x, y, P2);
+#pragma unroll
+    for (int j = 0; j < NP; j++) P[j] = P[j] + P2[j];
+  }
+};
+
 // g, x, 1 - x at the lane's NP logit-space points
-template <int NP>
+template <int NP, class Seg2 = ExactOneSegment>
 __device__ __forceinline__ void exact_paired_eval(const ExactStats &s, const ExactPairs &p, double *mbuf, int lane,
-                                                  const double (&t)[NP], double (&g)[NP], double (&x)[NP], double (&y)[NP]) {
+                                                  const double (&t)[NP], double (&g)[NP], double (&x)[NP], double (&y)[NP],
+                                                  const Seg2 &seg2 = Seg2()) {
 #pragma unroll
   for (int j = 0; j < NP; j++) {
     const ExactPoint pt = exact_point(s, t[j]);
     x[j] = pt.x; y[j] = pt.y; g[j] = pt.g;
+    seg2.point(t[j], pt, g[j]);
   }
   double P[NP];
   exact_pair_logsum<NP>(p, mbuf, lane, x, y, P);
+  seg2.template pairs<NP>(mbuf, lane, x, y, P);
 #pragma unroll
   for (int j = 0; j < NP; j++) g[j] = g[j] + P[j];
 }
@@ -101,8 +134,9 @@ __device__ __forceinline__ void exact_paired_eval(const ExactStats &s, const Exa
 // Steps 1 - 2: the window [tL, tR] and gref (in T.gmax; T.tm is the window's middle, nothing is made of it).
 // c8 = (n + h0 + h1) / 32: g'' >= -4 c8 everywhere, so between two grid points d apart g exceeds the larger of the two by
 // at most c8 d^2.  red: 64 doubles, redi: 128 ints of LDS.
+template <class Seg2 = ExactOneSegment>
 __device__ __forceinline__ ExactTable exact_paired_window(const ExactStats &s, double c8, const ExactPairs &p, double *mbuf,
-                                                          double *red, int *redi, int lane) {
+                                                          double *red, int *redi, int lane, const Seg2 &seg2 = Seg2()) {
   ExactTable T;
   double lo = -EXACT_T_MODE, hi = EXACT_T_MODE, gref = 0.0;
   constexpr int NPTS = 64 * EXP_PASS_PTS;
@@ -111,7 +145,7 @@ __device__ __forceinline__ ExactTable exact_paired_window(const ExactStats &s, d
     double t[EXP_PASS_PTS], g[EXP_PASS_PTS], x[EXP_PASS_PTS], y[EXP_PASS_PTS];
 #pragma unroll
     for (int j = 0; j < EXP_PASS_PTS; j++) t[j] = lo + d * static_cast<double>(EXP_PASS_PTS * lane + j);
-    exact_paired_eval<EXP_PASS_PTS>(s, p, mbuf, lane, t, g, x, y);
+    exact_paired_eval<EXP_PASS_PTS>(s, p, mbuf, lane, t, g, x, y, seg2);
     double m = g[0];
 #pragma unroll
     for (int j = 1; j < EXP_PASS_PTS; j++) m = g[j] > m ? g[j] : m;
@@ -148,8 +182,10 @@ __device__ __forceinline__ ExactTable exact_paired_window(const ExactStats &s, d
 }
 
 // Step 3: the table on the window.  F, f: EXACT_PAD doubles of LDS each, red: 256, fext: 2 (f at the points -1 and G + 1).
+template <class Seg2 = ExactOneSegment>
 __device__ __forceinline__ ExactTable exact_paired_table(const ExactStats &s, ExactTable T, const ExactPairs &p, double *mbuf,
-                                                         double *F, double *f, double *fext, double *red, int lane) {
+                                                         double *F, double *f, double *fext, double *red, int lane,
+                                                         const Seg2 &seg2 = Seg2()) {
   const double h = T.h, h24 = h / 24.0;
   const int i0 = EXACT_CELLS * lane;
   double ax = 0.0, ay = 0.0, af = 0.0;
@@ -158,7 +194,7 @@ __device__ __forceinline__ ExactTable exact_paired_table(const ExactStats &s, Ex
     double t[EXP_TAB_PTS], g[EXP_TAB_PTS], x[EXP_TAB_PTS], y[EXP_TAB_PTS];
 #pragma unroll
     for (int j = 0; j < EXP_TAB_PTS; j++) t[j] = T.tL + h * static_cast<double>(i0 + EXP_TAB_PTS * sw + j);
-    exact_paired_eval<EXP_TAB_PTS>(s, p, mbuf, lane, t, g, x, y);
+    exact_paired_eval<EXP_TAB_PTS>(s, p, mbuf, lane, t, g, x, y, seg2);
 #pragma unroll
     for (int j = 0; j < EXP_TAB_PTS; j++) {
       const int i = i0 + EXP_TAB_PTS * sw + j;
@@ -174,7 +210,7 @@ __device__ __forceinline__ ExactTable exact_paired_table(const ExactStats &s, Ex
     const int i = lane == 0 ? -1 : (lane == 1 ? EXACT_G + 1 : EXACT_G);
     double t[1], g[1], x[1], y[1];
     t[0] = T.tL + h * static_cast<double>(i);
-    exact_paired_eval<1>(s, p, mbuf, lane, t, g, x, y);
+    exact_paired_eval<1>(s, p, mbuf, lane, t, g, x, y, seg2);
     const double fi = miso_det_exp(g[0] - T.gmax);
     if (lane == 63) {
       f[exact_idx(EXACT_G)] = fi;

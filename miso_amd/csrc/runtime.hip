@@ -2451,6 +2451,49 @@ void miso_batch::compare_exact(miso_batch &other, const double *z, int n_z) {
   exact_compared = true;
 }
 
+// The exact comparison of two paired-end batches (this one is sample 1): the events both batches' paired exact mode took go
+// to exact_paired_compare (kernels_exact_paired_compare.hip), which reads both batches' resident pair records; every other
+// event is marked not comparable.  The results take compare_exact's place (h_exact_cmp, read by the same getter).
+void miso_batch::compare_exact_paired(miso_batch &other, const double *z, int n_z) {
+  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
+  if (events.size() != other.events.size() || S() != other.S())
+    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
+  if (!p.paired || !other.p.paired || !exact_paired || !other.exact_paired || slots_exact != exact_paired || other.slots_exact != other.exact_paired)
+    MISO_FAIL(MISO_EINVAL, "Both batches to compare exactly must be paired-end and have run with the paired exact-posterior mode");
+  if (n_z < 0 || n_z > 8) MISO_FAIL(MISO_EINVAL, "The number of delta psi points must lie in [0, 8]");
+  const int n = static_cast<int>(events.size());
+  for (int i = 0; i < n; i++)
+    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+  std::vector<int32_t> list;
+  std::vector<double> s1, s2;
+  exact_cmp_ok.assign(n, 0);
+  auto stats6 = [](const PackedEvent &e, std::vector<double> &s) {
+    s.insert(s.end(), {static_cast<double>(e.base_count[0]), static_cast<double>(e.base_count[1]), e.eff[0], e.eff[1], e.hyper[0], e.hyper[1]});
+  };
+  for (int i = 0; i < n; i++) {
+    if (!event_exact(i) || !other.event_exact(i)) continue;
+    list.push_back(i);
+    stats6(events[i], s1); stats6(other.events[i], s2);
+  }
+  const size_t w = 5 + static_cast<size_t>(n_z);
+  std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
+  HIP_OK(hipSetDevice(device));
+  HIP_OK(hipStreamSynchronize(other.stream));
+  const ExactPairedCmpInput in1{s1.data(), nullptr, nullptr, d_events, d_in, d_fp, static_cast<int>(fd.prob.size())};
+  const ExactPairedCmpInput in2{s2.data(), nullptr, nullptr, other.d_events, other.d_in, other.d_fp, static_cast<int>(other.fd.prob.size())};
+  // (validates z, and fails with MISO_ENODEVICE without a device, also when no event is comparable)
+  exact_paired_compare_run(in1, in2, list.data(), static_cast<int>(list.size()), z, n_z, got.data(), stream, &exact_compare_ms);
+  h_exact_cmp.assign(static_cast<size_t>(n) * w, 0.0);
+  for (size_t j = 0; j < list.size(); j++) {
+    std::memcpy(&h_exact_cmp[list[j] * w], &got[j * w], w * sizeof(double));
+    exact_cmp_ok[list[j]] = 1;
+  }
+  exact_cmp_nz = n_z;
+  if (!list.empty()) note_kernel("exact_paired_compare");
+  exact_compared = true;
+}
+
 // A batch that holds posterior samples produced elsewhere -- parsed `.miso` files (summarize_miso / compare_miso
 // work on directories of them, misopy/samples_utils.py:263-329, hypothesis_test.py:186-345): event i has K[i] isoforms
 // and S samples in the file's layout (rows of K values).  Only the output pool exists; summarize / compare and their

@@ -137,7 +137,7 @@ class GenesDispatcher(object):
         self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
         self.summary_only = bool(summary_only)
         self.exact = bool(exact)       # --exact: handed on to every worker
-        # --exact-compare: beside the `.miso_bf` table the exact comparison's `.miso_bf_exact` (compare.py), merged like a
+        # --exact-compare / --exact-paired-compare: beside the `.miso_bf` table the exact comparison's `.miso_bf_exact` (compare.py), merged like a
         # diagnostics table; delta_thresholds: its thresholds (None: the workers' default)
         self.exact_compare = bool(exact_compare)
         self.delta_thresholds = None if delta_thresholds is None else [float(t) for t in delta_thresholds]
@@ -460,8 +460,13 @@ def main(argv=None):
                     help="with --compare and the exact mode: also write OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf_exact -- "
                          "for the events the exact mode took in both samples the Bayes factor and P(|delta Psi| >= T) come from the "
                          "two posteriors' tables, without sampling error and whatever the seed; the .miso_bf table is unchanged")
+    ap.add_argument("--exact-paired-compare", action="store_true",
+                    help="with --compare, --paired-end and the paired exact mode: also write the .miso_bf_exact table of "
+                         "--exact-compare for the events the paired exact mode took in both samples -- the product of the two "
+                         "posteriors is tabulated over both samples' read pairs; the .miso files and the .miso_bf table are unchanged")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
-                    help="the thresholds T of --exact-compare, each in (0, 1), at most four (default 0.1 0.2)")
+                    help="the thresholds T of --exact-compare / --exact-paired-compare, each in (0, 1), at most four "
+                         "(default 0.1 0.2)")
     ap.add_argument("--compare", metavar="BAM2", default=None,
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
@@ -486,8 +491,16 @@ def main(argv=None):
             ap.error("--exact-compare: the exact-posterior mode takes single-end events only")
         if not (a.exact or Settings.get_exact()):
             ap.error("--exact-compare needs the exact-posterior mode (--exact, or `exact = True` in the settings)")
+    if a.exact_paired_compare:
+        if a.compare is None:
+            ap.error("--exact-paired-compare goes with --compare")
+        if a.paired_end is None:
+            ap.error("--exact-paired-compare goes with --paired-end")
+        if not (a.exact_paired or Settings.get_exact_paired()):
+            ap.error("--exact-paired-compare needs the paired exact-posterior mode (--exact-paired, or `exact_paired = True` "
+                     "in the settings)")
     if a.delta_psi_thresholds is not None:
-        if not a.exact_compare:
+        if not (a.exact_compare or a.exact_paired_compare):
             ap.error("--delta-psi-thresholds goes with --exact-compare")
         from . import compare
         try:
@@ -514,7 +527,8 @@ def main(argv=None):
                                        compare_bam=None if a.compare is None else
                                        os.path.abspath(os.path.expanduser(a.compare)),
                                        labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics,
-                                       exact=a.exact, exact_compare=a.exact_compare, exact_paired=a.exact_paired,
+                                       exact=a.exact, exact_compare=a.exact_compare or a.exact_paired_compare,
+                                       exact_paired=a.exact_paired,
                                        delta_thresholds=a.delta_psi_thresholds)
     except PrefilterError as err:
         print("Error: %s" % err)

@@ -438,10 +438,14 @@ class MISOSampler:
         diagnostics_files (optional): (file1, file2), the chain diagnostics table (diagnostics.py) of each sample's
         written events, from the samples resident on the device.
         exact_comparison_file (optional; the exact-posterior mode only): the `.miso_bf_exact` table of the exact comparison
-        (compare.write_exact_comparison) with P(|delta psi| >= t) for every t of delta_thresholds (default 0.1, 0.2)."""
+        (compare.write_exact_comparison) with P(|delta psi| >= t) for every t of delta_thresholds (default 0.1, 0.2).  A
+        paired-end sampler with the paired exact mode compares through MISOCompareBatch(exact_paired_compare=)."""
         xthr = None
         if exact_comparison_file is not None:
-            if self.paired_end or not int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
+            if self.paired_end:
+                if not self.exact_paired():
+                    raise ValueError("the exact comparison of paired-end samples needs the paired exact-posterior mode")
+            elif not int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
                 raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
             xthr = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
         xrows = []
@@ -471,7 +475,7 @@ class MISOSampler:
             if self.exact_paired():
                 kw["exact_paired"] = True   # ... and the paired-end one
             if xthr is not None:
-                kw["exact_compare"] = compare.delta_points(xthr)
+                kw["exact_paired_compare" if self.paired_end else "exact_compare"] = compare.delta_points(xthr)
             res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),

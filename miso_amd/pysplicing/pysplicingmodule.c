@@ -32,6 +32,8 @@
  *                   samples are independent draws from the tabulated posterior of psi (miso_batch_set_exact).
  *                   MISOPairedBatch(exact=True) / MISOCompareBatch(paired=..., exact_paired=True): the same for the
  *                   eligible paired-end two-isoform events (miso_batch_set_exact_paired).
+ *   exact_paired_compare=(z, ...)  MISOCompareBatch with paired= and exact_paired=True: the same through
+ *                   miso_batch_compare_exact_paired, appended as the LAST element of the result.
  *   exact_compare=(z, ...)  MISOCompareBatch with exact=True: the exact comparison (miso_batch_compare_exact) at these
  *                   delta psi points, appended as the LAST element of the result.
  * The functions of the module that are not on the sampler path raise NotImplementedError.
@@ -462,9 +464,11 @@ static PyObject *batch_common(PyObject *events, miso_params_t *p, PyObject *seed
 static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject *kw) {
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
-                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired", NULL};
+                           "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired",
+                           "exact_paired_compare", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL, *xcobj = NULL, *xc = NULL;
+  PyObject *xpobj = NULL;   /* exact_paired_compare=(z, ...): the same through miso_batch_compare_exact_paired */
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
   int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
   int exact_paired = 0;             /* exact_paired=True (with paired=): miso_batch_set_exact_paired */
@@ -473,16 +477,24 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOp", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpO", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
                                    &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
-                                   &exact_paired)) return NULL;
+                                   &exact_paired, &xpobj)) return NULL;
   if (xcobj == Py_None) xcobj = NULL;
+  if (xpobj == Py_None) xpobj = NULL;
+  if (xpobj) {
+    if (xcobj) { PyErr_SetString(PyExc_ValueError, "exact_compare and exact_paired_compare exclude each other"); return NULL; }
+    if (!exact_paired) { PyErr_SetString(PyExc_ValueError, "exact_paired_compare requires exact_paired=True"); return NULL; }
+    xcobj = xpobj;
+  }
   if (xcobj) {
     Py_ssize_t nz;
-    if (!exact) { PyErr_SetString(PyExc_ValueError, "exact_compare requires exact=True"); return NULL; }
+    if (!xpobj && !exact) { PyErr_SetString(PyExc_ValueError, "exact_compare requires exact=True"); return NULL; }
     if (!PyTuple_Check(xcobj) || (nz = PyTuple_Size(xcobj)) > 8) {
-      PyErr_SetString(PyExc_ValueError, "exact_compare must be a tuple of at most 8 delta psi points"); return NULL;
+      PyErr_SetString(PyExc_ValueError, xpobj ? "exact_paired_compare must be a tuple of at most 8 delta psi points"
+                                             : "exact_compare must be a tuple of at most 8 delta psi points");
+      return NULL;
     }
     for (n_xz = 0; n_xz < (int) nz; n_xz++) {
       xz[n_xz] = PyFloat_AsDouble(PyTuple_GET_ITEM(xcobj, n_xz));
@@ -546,7 +558,9 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
      bayes_factor, log10_bayes_factor, cdf at every z, sample 1's and sample 2's grid summary (mean, ci_low, ci_high)) */
   if (out && xcobj) {
     PyObject *one, *all;
-    if (n > 0 && (rc = miso_batch_compare_exact(b1, b2, xz, n_xz))) { raise_miso(rc); Py_CLEAR(out); goto done; }
+    if (n > 0 && (rc = xpobj ? miso_batch_compare_exact_paired(b1, b2, xz, n_xz) : miso_batch_compare_exact(b1, b2, xz, n_xz))) {
+      raise_miso(rc); Py_CLEAR(out); goto done;
+    }
     if (!(xc = PyList_New(n))) { Py_CLEAR(out); goto done; }
     for (i = 0; i < n; i++) {
       double v[5], cdf[8], s[2][6]; int was = 0, w1 = 0, w2 = 0;

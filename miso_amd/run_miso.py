@@ -342,7 +342,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         os.environ["MISO_DEVICE"] = str(int(device))
     exact = Settings.get_exact() if exact is None else bool(exact)
     exact_paired = Settings.get_exact_paired() if exact_paired is None else bool(exact_paired)
-    if exact_comparison_file is not None and (paired_end or not exact):
+    if exact_comparison_file is not None and paired_end and not exact_paired:
+        raise ValueError("the exact comparison of paired-end samples needs the paired exact-posterior mode")
+    if exact_comparison_file is not None and not paired_end and not exact:
         raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
     p = Settings.get_sampler_params()
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
@@ -507,7 +509,11 @@ def main(argv=None):
         print("Error: --diagnostics-files goes with --compare-genes-from-file.")
         return 1
     if a.exact_comparison_file is not None:
-        if not a.compare_genes_from_file or paired_end or not exact:
+        if paired_end and a.compare_genes_from_file:
+            if not exact_paired:
+                print("Error: --exact-comparison-file with --paired-end needs the paired exact mode (--exact-paired).")
+                return 1
+        elif not a.compare_genes_from_file or paired_end or not exact:
             print("Error: --exact-comparison-file goes with --compare-genes-from-file and the exact mode (single-end).")
             return 1
     if a.delta_psi_thresholds is not None:
