@@ -593,6 +593,21 @@ int miso_selftest_text_digits(const double *x, int n, int64_t *out);
    < 2^24), noted in order by k2_flag_note.  k2_flag_read's answer: code[i] = 0 no flagged trip, 1 exactly one, at pos[i],
    2 more than one (or one trip with two bits: see the header). */
 int miso_selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *start, int n, int32_t *code, uint32_t *pos);
+/* csrc/k2_count.hpp, the per-word arithmetic of the same loop as the device issues it (the assembly statements): element i
+   is one lane, its generator words u[start[i]] .. u[start[i + 1] - 1] (start[0] = 0, n + 1 offsets, an even number of words
+   each: two per statement) against the high-half threshold th[i] (0 .. 65536).  masked[i] != 0: the tail's statements, inv =
+   per word the halves that are not reads (0xFFFF each); 0: the steady trips' statements, inv must be 0.  acc[i] = the two
+   16-bit sums of c = 2 below + on side by side, o[i] = the OR of c (bit 0 of a half: a read on the threshold). */
+int miso_selftest_k2_count(const uint32_t *th, const int32_t *start, const uint32_t *u, const uint32_t *inv, const int32_t *masked,
+                           int n, uint32_t *acc, uint32_t *o);
+/* csrc/kernels_k2.inl k2_finish_lane, what a lane of the same loop does BEHIND it (the settle path, the finishing expression,
+   the th = 0xFFFF rule and recount, the t = 2^32 closed form), with a caller-given threshold: element i is a chain on one lane
+   with n_draw[i] (0 .. 2^20) drawing reads at iteration iter[i] of (seed, event_id[i], chain[i]); its sum and flag are made by
+   k2_count.hpp's plain functions over its generator blocks.  out[i] = the number of its reads whose 32-bit uniform
+   (include/miso_philox.h miso_split_word) is below t[i] (0 .. 2^32).  settle_all != 0: every lane rescans, as under
+   MISO_K2_SETTLE_ALL. */
+int miso_selftest_k2_finish(uint64_t seed, const uint32_t *event_id, const uint32_t *chain, const uint32_t *iter, const int32_t *n_draw,
+                            const uint64_t *t, int settle_all, int n, int32_t *out);
 
 #ifdef __cplusplus
 }

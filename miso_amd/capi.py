@@ -932,6 +932,42 @@ def selftest_k2_flag(m, k, start):
     return code, pos
 
 
+def selftest_k2_count(th, start, u, inv, masked):
+    """csrc/k2_count.hpp's assembly statements on the device, one lane per element: words start[i] .. start[i + 1] - 1 of u
+    (an even number), two per statement, against high-half threshold th[i]; masked[i] != 0: the tail's form, inv = the halves
+    that are not reads; 0: the steady trips' form (inv must be 0).  Returns (acc, o): the packed sums and the flag word"""
+    th = np.ascontiguousarray(th, dtype=np.uint32)
+    u = np.ascontiguousarray(u, dtype=np.uint32)
+    inv = np.ascontiguousarray(inv, dtype=np.uint32)
+    masked = np.ascontiguousarray(masked, dtype=np.int32)
+    start = np.ascontiguousarray(start, dtype=np.int32)
+    if (u.shape != inv.shape or u.ndim != 1 or start.ndim != 1 or len(start) < 1 or start[0] != 0 or start[-1] != len(u)
+            or th.shape != (len(start) - 1,) or masked.shape != th.shape):
+        raise ValueError("u, inv: two vectors of one length; start: offsets from 0 to len(u); th, masked: one per sequence")
+    n = len(start) - 1
+    acc, o = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    check(lib().miso_selftest_k2_count(_p(th), _p(start), _p(u), _p(inv), _p(masked), n, _p(acc), _p(o)))
+    return acc, o
+
+
+def selftest_k2_finish(seed, event_id, chain, iteration, n_draw, t, settle_all=False):
+    """csrc/kernels_k2.inl k2_finish_lane on the device, one single-lane chain per element: the number of the chain's n_draw[i]
+    drawing reads at iteration[i] whose uniform is below the caller's threshold t[i] (0 .. 2^32), through the read loop's sum
+    and flag, the settle path and the finishing expression -- include/miso_amd.h miso_selftest_k2_finish"""
+    event_id = np.ascontiguousarray(event_id, dtype=np.uint32)
+    chain = np.ascontiguousarray(chain, dtype=np.uint32)
+    iteration = np.ascontiguousarray(iteration, dtype=np.uint32)
+    n_draw = np.ascontiguousarray(n_draw, dtype=np.int32)
+    t = np.ascontiguousarray(t, dtype=np.uint64)
+    n = len(t)
+    if any(a.shape != (n,) for a in (event_id, chain, iteration, n_draw)):
+        raise ValueError("event_id, chain, iteration, n_draw, t: one entry per element")
+    out = np.zeros(n, np.int32)
+    check(lib().miso_selftest_k2_finish(C.c_uint64(seed), _p(event_id), _p(chain), _p(iteration), _p(n_draw), _p(t),
+                                        C.c_int(int(bool(settle_all))), C.c_int(n), _p(out)))
+    return out
+
+
 def selftest_convergent_mean(samples, chains):
     """samples: S x K (row i from chain i % chains) -> True if stop=CONVERGENT_MEAN would stop (miso.c:556-636)"""
     a = np.ascontiguousarray(samples, dtype=np.float64)

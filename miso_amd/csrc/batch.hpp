@@ -30,6 +30,10 @@ void selftest_pe_pick(int KK, const uint8_t *f, const double *psi, const double 
 void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
 void selftest_text_digits(const double *x, int n, int64_t *out);
 void selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *start, int n, int32_t *code, uint32_t *pos);
+void selftest_k2_finish(uint64_t seed, const uint32_t *event_id, const uint32_t *chain, const uint32_t *iter, const int32_t *n_draw,
+                        const uint64_t *t, int settle_all, int n, int32_t *out);
+void selftest_k2_count(const uint32_t *th, const int32_t *start, const uint32_t *u, const uint32_t *inv, const int32_t *masked, int n,
+                       uint32_t *acc, uint32_t *o);
 // kernels_exact.hip: the exact-posterior mode's posterior stage on its own (miso_selftest_exact, exact summaries)
 void exact_probe_run(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st = nullptr);
 // kernels_exact_compare.hip: pairs of such posteriors compared (miso_batch_compare_exact, miso_selftest_exact_compare);

@@ -1204,5 +1204,21 @@ int miso_selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *s
     selftest_k2_flag(m, k, start, n, code, pos);
   });
 }
+int miso_selftest_k2_count(const uint32_t *th, const int32_t *start, const uint32_t *u, const uint32_t *inv, const int32_t *masked,
+                           int n, uint32_t *acc, uint32_t *o) {
+  return guarded([&] {
+    need(start, "start");
+    if (n > 0) { need(th, "th"); need(masked, "masked"); need(acc, "acc"); need(o, "o"); }
+    if (n > 0 && start[n] > 0) { need(u, "u"); need(inv, "inv"); }
+    selftest_k2_count(th, start, u, inv, masked, n, acc, o);
+  });
+}
+int miso_selftest_k2_finish(uint64_t seed, const uint32_t *event_id, const uint32_t *chain, const uint32_t *iter, const int32_t *n_draw,
+                            const uint64_t *t, int settle_all, int n, int32_t *out) {
+  return guarded([&] {
+    if (n > 0) { need(event_id, "event_id"); need(chain, "chain"); need(iter, "iter"); need(n_draw, "n_draw"); need(t, "t"); need(out, "out"); }
+    selftest_k2_finish(seed, event_id, chain, iter, n_draw, t, settle_all, n, out);
+  });
+}
 
 }  // extern "C"

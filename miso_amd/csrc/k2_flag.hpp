@@ -36,12 +36,17 @@ K2_FLAG_FN uint32_t k2_mul24(uint32_t a, uint32_t b) {
 #endif
 }
 
-// note the trip or single step that began at stride position k (k < 2^24) and whose running minimum is m
-K2_FLAG_FN void k2_flag_note(K2Flag &f, uint32_t m, uint32_t k) {
-  const uint32_t z = (m - 0x00010001u) & ~m & 0x80008000u;
+// note the trip or single step that began at stride position k (k < 2^24) and whose flag word is z: at most two bits, non-zero
+// iff a read of the trip sits on the threshold (the read loop's z: k2_count.hpp k2_count_flag)
+K2_FLAG_FN void k2_flag_note_z(K2Flag &f, uint32_t z, uint32_t k) {
   const uint32_t c = static_cast<uint32_t>(__builtin_popcount(z));
   f.n += c;
   f.s += k2_mul24(c, k);
+}
+
+// the same from a running minimum m of x ^ th
+K2_FLAG_FN void k2_flag_note(K2Flag &f, uint32_t m, uint32_t k) {
+  k2_flag_note_z(f, (m - 0x00010001u) & ~m & 0x80008000u, k);
 }
 
 enum { K2_FLAG_NONE = 0, K2_FLAG_ONE = 1, K2_FLAG_MANY = 2 };

@@ -34,6 +34,7 @@
 #include "miso_binomial.h"
 #include "detmath_n.hpp"
 #include "k2_flag.hpp"
+#include "k2_count.hpp"
 
 #pragma clang fp contract(off)
 
@@ -163,6 +164,72 @@ __device__ __forceinline__ uint64_t k2_threshold(double p0, double T) {
   const bool q1 = pred(q0 ? t0 + 1.0 : t0 - 1.0);
   const double t = q0 ? (q1 ? t0 + 2.0 : t0 + 1.0) : (q1 ? t0 : t0 - 1.0);
   return static_cast<uint64_t>(t);
+}
+
+// Behind the single-end read loop (k2_body gibbs(); kernels_selftest.hip runs it on its own): a lane's reads on isoform 0
+// from A, the sum of its words' c (k2_count.hpp), and its flag.  The lane is `sub` of the GE lanes striding over the chain's
+// nblk blocks (nfq full ones and, where rem != 0, the partial block of rem reads, block number nfq); npos stride positions,
+// the first uq_trips * UQ of them in trips of UQ, the rest single steps.  draw(q, low) is block q of the step's high
+// (low = false) or low half-words.  All lanes of the wavefront call it together (one wave-wide vote).
+template <int UQ, class Draw>
+__device__ __forceinline__ int k2_finish_lane(int d0, K2Flag amb, uint32_t th, uint32_t tl, int sub, int GE, int nfq, int rem,
+                                              int nblk, int npos, int uq_trips, bool lane_used, bool settle_all, Draw draw) {
+  {
+    // the lane's reads: those of its full blocks and, for its owner, of the partial block (the same at every step: the
+    // compiler keeps it; asking for it only where th >= 0xFFFF measured slower, 51.78 against 51.58 ms)
+    const int n_lane = ((sub < nfq) ? 8 * ((nfq - 1 - sub) / GE + 1) : 0) + ((sub == nfq % GE) ? rem : 0);
+    // t = 2^32: every one of them; the loop's sums mean nothing and no trip is flagged
+    const bool closed = th > 0xFFFFu;
+    if (closed || !lane_used) amb = K2Flag{};
+    // (settle_all -- tests: every lane takes the rescan below at every step)
+    uint32_t amb_t = 0;
+    // (a position beyond the flag's 24-bit multiply -- a lane walking more than 1.3e8 reads -- is not trusted: rescan)
+    const int amb_n = (npos <= K2_FLAG_MAX_POS || amb.n == 0) ? k2_flag_read(amb, amb_t) : static_cast<int>(K2_FLAG_MANY);
+    // th = 0xFFFF: a lane that is flagged (a half of 0xFFFE) or whose sum is short (a half of 0xFFFF) counts its reads directly
+    const bool top = th == K2_COUNT_TOP && lane_used;
+    const bool recount = top && (settle_all || !k2_count_top_clean(d0, amb.n, n_lane));
+    int on = 0, more = 0;   // the lane's reads ON the threshold, and those of them whose low half is below tl
+    if (__builtin_expect(settle_all || __any(amb_n != K2_FLAG_NONE || recount), 0)) {
+      // the reads whose high half sits ON the threshold: their low halves decide (one wavefront step in four at 1000
+      // reads and 16 chains per wavefront; two Philox blocks then).  A flagged lane comes here whatever tl is: E is needed.
+      // A block of this lane: how many of its reads' high halves are on the threshold, and the low halves of those
+      // (the partial block: its rem reads only); DIRECT (th = 0xFFFF): the block's count itself, read by read.
+      // (`direct` is summed for every block looked at though only the th = 0xFFFF recount reads it: one compare and one add
+      // per half on a cold path, against a second copy of look() in every lane layout's body.)
+      int direct = 0;
+      auto look = [&](int q) {
+        if (q >= nblk) return;
+        const miso_u32x4 hi = draw(q, false);
+        const int nh = (q == nfq) ? rem : 8;
+        int e = 0;
+        // (all eight halves by their constant numbers, those beyond nh masked: a loop to nh indexes the block's words
+        // by a variable and branches per half, on a path the step of a workgroup-wide chain waits for nearly every time)
+#pragma unroll
+        for (int h = 0; h < 8; h++) {
+          const uint32_t x = miso_block_half(hi, h);
+          e += (h < nh && x == th) ? 1 : 0;
+          direct += (h < nh && x < th) ? 1 : 0;
+        }
+        on += e;
+        if (e == 0) return;   // (tl == 0 takes no path of its own: nothing is below a low half of 0)
+        const miso_u32x4 lo = draw(q, true);
+#pragma unroll
+        for (int h = 0; h < 8; h++)
+          more += (h < nh && miso_block_half(hi, h) == th && miso_block_half(lo, h) < tl) ? 1 : 0;
+      };
+      if (amb_n == K2_FLAG_ONE && !settle_all && !recount) {        // one trip's blocks, or one single step's block ...
+        const int k = static_cast<int>(amb_t), nb = k < UQ * uq_trips ? UQ : 1;
+        for (int i = 0; i < nb; i++) look(sub + (k + i) * GE);
+      } else if ((amb_n == K2_FLAG_MANY || settle_all || recount) && lane_used && !closed) {   // ... or all of the lane's
+        for (int q = sub; q < nblk; q += GE) look(q);
+      }
+      if (recount) { d0 = 2 * direct; on = 0; }   // (as A of a lane with nothing on the threshold; `more` as counted)
+    }
+    d0 = k2_count_finish(d0, on, more);
+    if (closed) d0 = n_lane;
+    if (!lane_used) d0 = 0;
+  }
+  return d0;
 }
 
 // value held by lane J of the caller's quad (v_mov_b32 with DPP quad_perm, full rate)
@@ -672,16 +739,21 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     int d0 = 0; K2Flag amb;
     PROF_T(g1);
     PROF_ADD(pf_thr, g0, g1);
-    // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask):
-    //   below: saturating th - x is non-zero iff x < th; min(.., 1) is the count;   equal: x ^ th is zero iff x == th,
-    // kept as the running minimum over the trip's words and tested once per trip (a 32-bit word has a zero half iff
-    // (m - 0x00010001) & ~m & 0x80008000).  th = 65536 (t = 2^32: every read picks isoform 0) does not fit a half:
-    // counted in closed form behind the loop.
+    // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask), FOUR
+    // operations per word (k2_count.hpp): with P = th + 1 in both halves the saturating P - x is 0 iff x > th, 1 iff
+    // x == th and >= 2 iff x < th; c = min(.., 2) classifies the half three ways.  accv += c with a plain 32-bit add
+    // (per half 2 * below + on; the halves never carry: CHUNK below) and o |= c with a plain 32-bit or: bit 0 of a half of
+    // o says that a read of the trip sits ON the threshold, tested once per trip (z = o & 0x00010001).  Behind the loop
+    // the lane holds A = 2 below + E and d0 = (A - E) / 2 + more; E and more are 0 unless a trip was flagged.
+    // th = 0xFFFF: P does not fit a half; the loop runs with P = 0xFFFF and the lane finishes by k2_count.hpp's rule.
+    // th = 65536 (t = 2^32: every read picks isoform 0): counted in closed form behind the loop.
     // (inline assembly: written with vector types the compiler recognises the idiom and goes back to one compare per half.
     // Two words' operations share ONE statement, interleaved so that none reads the result of the one before it: behind a
     // statement of its own the compiler pads with an s_nop 0 whenever the next instruction reads what the statement wrote --
     // it assumes a destination-forwarding hazard it cannot see into -- and these operations have none: inside a statement
     // the hardware's ordinary interlocks apply.
+    // Before the three-way form: five operations per word -- the count from min(sat(th - x), 1) with a packed add, the
+    // equal test as a running packed minimum of x ^ th: 96 `v_*` per steady trip against 87 now, docs/history.md.
     // Measured, same box, 40 000 events x 1000 reads: one SDWA compare per half into a lane mask + add-with-carry, 110
     // VALU per 16 reads, 74.6 ms; this form, 108 VALU but no lane masks, 71.0 ms; MISO defaults 235.9 -> 219.1 ms,
     // hg19-like read counts 66.4 -> 59.4 ms; the equal test once per trip instead of once per block: 70.9 -> 69.3 ms,
@@ -694,8 +766,7 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // Masked: a block is a full one (q < nfq), the chain's partial block (q == nfq: the halves >= rem are not reads) or
     // beyond the chain: the halves that are not reads are masked out of the count AND out of the equal test, so the
     // partial block needs no generator call of its own and a block beyond the chain never flags a trip or a step.
-    const uint32_t thc = th > 0xFFFFu ? 0xFFFFu : th;
-    const uint32_t T2 = thc | (thc << 16), one2 = 0x00010001u;
+    const uint32_t P2 = k2_count_p(th), two2 = K2_COUNT_TWO;
     uint32_t accv = 0;
     // NB blocks of the lane from stride position k on: a trip (NB = UQ) or a single step (NB = 1)
     auto trip = [&](int k, auto masked, auto blocks) __attribute__((always_inline)) {
@@ -705,104 +776,57 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
 #pragma unroll
       for (int i = 0; i < NB; i++)
         u[i] = philox_gibbs(rng, static_cast<uint32_t>(sub + (k + i) * GE), n0r0);
-      uint32_t m = 0;   // the trip's running minimum of x ^ th, both halves
+      uint32_t o = 0;   // the trip's OR of c, both halves
 #pragma unroll
       for (int i = 0; i < NB; i++) {
         const int q = sub + (k + i) * GE;
 #pragma unroll
         for (int w = 0; w < 4; w += 2) {   // two words per statement, interleaved: no packed operation reads its predecessor's result
           const uint32_t ua = u[i].v[w], ub = u[i].v[w + 1];
-          uint32_t da, db, ya = ua ^ T2, yb = ub ^ T2;
-          const bool first = i == 0 && w == 0;   // m = min(ya, yb) instead of min(m, ya, yb)
           if (!MASKED) {
-            if (first)
-              asm("v_pk_sub_u16 %0, %4, %5 clamp\n\tv_pk_sub_u16 %1, %4, %6 clamp\n\t"
-                  "v_pk_min_u16 %0, %0, %7\n\tv_pk_min_u16 %1, %1, %7\n\t"
-                  "v_pk_add_u16 %2, %2, %0\n\tv_pk_min_u16 %3, %8, %9\n\tv_pk_add_u16 %2, %2, %1"
-                  : "=&v"(da), "=&v"(db), "+v"(accv), "=&v"(m) : "v"(T2), "v"(ua), "v"(ub), "v"(one2), "v"(ya), "v"(yb));
-            else
-              asm("v_pk_sub_u16 %0, %4, %5 clamp\n\tv_pk_sub_u16 %1, %4, %6 clamp\n\t"
-                  "v_pk_min_u16 %0, %0, %7\n\tv_pk_min_u16 %1, %1, %7\n\t"
-                  "v_pk_add_u16 %2, %2, %0\n\tv_pk_min_u16 %3, %3, %8\n\tv_pk_add_u16 %2, %2, %1\n\tv_pk_min_u16 %3, %3, %9"
-                  : "=&v"(da), "=&v"(db), "+v"(accv), "+v"(m) : "v"(T2), "v"(ua), "v"(ub), "v"(one2), "v"(ya), "v"(yb));
-          } else {   // the masks go between the counts and the sums: two statements
-            asm("v_pk_sub_u16 %0, %2, %3 clamp\n\tv_pk_sub_u16 %1, %2, %4 clamp\n\t"
-                "v_pk_min_u16 %0, %0, %5\n\tv_pk_min_u16 %1, %1, %5"
-                : "=&v"(da), "=&v"(db) : "v"(T2), "v"(ua), "v"(ub), "v"(one2));
+            if (i == 0 && w == 0) k2_count_pair<true>(accv, o, P2, two2, ua, ub);   // o = c_a | c_b instead of o | c_a | c_b
+            else k2_count_pair<false>(accv, o, P2, two2, ua, ub);
+          } else {   // the halves that are not reads count nothing and flag nothing: one mask on c per word
             const uint32_t inva = (q < nfq) ? 0u : (q == nfq ? part_inv[w] : 0xFFFFFFFFu);
             const uint32_t invb = (q < nfq) ? 0u : (q == nfq ? part_inv[w + 1] : 0xFFFFFFFFu);
-            da &= ~inva; ya |= inva;
-            db &= ~invb; yb |= invb;
-            if (first)
-              asm("v_pk_add_u16 %0, %0, %2\n\tv_pk_min_u16 %1, %4, %5\n\tv_pk_add_u16 %0, %0, %3"
-                  : "+v"(accv), "=&v"(m) : "v"(da), "v"(db), "v"(ya), "v"(yb));
-            else
-              asm("v_pk_add_u16 %0, %0, %2\n\tv_pk_min_u16 %1, %1, %4\n\tv_pk_add_u16 %0, %0, %3\n\tv_pk_min_u16 %1, %1, %5"
-                  : "+v"(accv), "+v"(m) : "v"(da), "v"(db), "v"(ya), "v"(yb));
+            if (i == 0 && w == 0) k2_count_pair_masked<true>(accv, o, P2, two2, ua, ub, inva, invb);
+            else k2_count_pair_masked<false>(accv, o, P2, two2, ua, ub, inva, invb);
           }
         }
       }
       // the flag: the stride position the flagged trip or step began at (a single step: k >= UQ * uq_trips)
-      k2_flag_note(amb, m, static_cast<uint32_t>(k));
+      k2_flag_note_z(amb, k2_count_flag(o), static_cast<uint32_t>(k));
     };
     const std::integral_constant<int, UQ> whole{};
     const std::integral_constant<int, 1> single{};
-    // (the two 16-bit counters of a lane take 4 per block each: emptied every 16000 blocks, which only a chain of more
-    // than 10^5 reads forced onto a single lane ever reaches)
-    constexpr int CHUNK = 16000 / UQ;
+    // (the two 16-bit counters of a lane take up to 8 per block each -- four words of at most 2 -- and hold K2_COUNT_MAX_BLOCKS
+    // = 8191 blocks: emptied every 8000 blocks, which only a chain of more than 6 10^4 reads forced onto a single lane ever
+    // reaches.  d0 is A, the sum of c, until the loop is through.)
+    constexpr int CHUNK = 8000 / UQ;
+    static_assert(CHUNK * UQ <= K2_COUNT_MAX_BLOCKS, "the packed counters would carry");
     for (int j0 = 0; j0 < full_trips; j0 += CHUNK) {
       const int j1 = min(full_trips, j0 + CHUNK);
       for (int j = j0; j < j1; j++) trip(UQ * j, std::false_type{}, whole);
-      d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
+      d0 += k2_count_sum(accv);
       accv = 0;
     }
     for (int j0 = full_trips; j0 < uq_trips; j0 += CHUNK) {
       const int j1 = min(uq_trips, j0 + CHUNK);
       for (int j = j0; j < j1; j++) trip(UQ * j, std::true_type{}, whole);
-      d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
+      d0 += k2_count_sum(accv);
       accv = 0;
     }
-    if (UQ * uq_trips < npos) {   // fewer than UQ positions left: one block per lane at a time
+    if (UQ * uq_trips < npos) {   // fewer than UQ positions left: one block per lane at a time (fewer than UQ: no chunks)
       for (int k = UQ * uq_trips; k < npos; k++) trip(k, std::true_type{}, single);
-      d0 += static_cast<int>(accv & 0xFFFFu) + static_cast<int>(accv >> 16);
+      d0 += k2_count_sum(accv);
       accv = 0;
     }
-    // t = 2^32: every read of the lane's full blocks and, for its owner, of the partial block
-    if (th > 0xFFFFu) d0 = ((sub < nfq) ? 8 * ((nfq - 1 - sub) / GE + 1) : 0) + ((sub == nfq % GE) ? rem : 0);
-    if (!lane_used) { d0 = 0; amb = K2Flag{}; }
-    const bool settle_all = a.pe_force_exact != 0;   // tests: every lane takes the rescan below at every step
-    uint32_t amb_t = 0;
-    // (a position beyond the flag's 24-bit multiply -- a lane walking more than 1.3e8 reads -- is not trusted: rescan)
-    const int amb_n = (npos <= K2_FLAG_MAX_POS || amb.n == 0) ? k2_flag_read(amb, amb_t) : static_cast<int>(K2_FLAG_MANY);
-    if (tl != 0 && __builtin_expect(settle_all || __any(amb_n != K2_FLAG_NONE), 0)) {
-      // the reads whose high half sits ON the threshold: their low halves decide (one wavefront step in four at 1000
-      // reads and 16 chains per wavefront; two Philox blocks then)
-      auto settle = [&](uint32_t q) {
-        const miso_u32x4 hi = miso_philox4x32(q, iter, c2_gibbs, event_id, k0, k1);
-        const miso_u32x4 lo = miso_philox4x32(q, iter, MISO_SITE_GIBBS_LOW | (chain << 8), event_id, k0, k1);
-        const int nh = (static_cast<int>(q) == nfq) ? rem : 8;
-        int more = 0;
-        for (int h = 0; h < nh; h++)
-          more += (miso_block_half(hi, h) == th && miso_block_half(lo, h) < tl) ? 1 : 0;
-        return more;
-      };
-      // a block of this lane: its low halves if one of its high halves is on the threshold (the partial block: settle()
-      // counts nothing when none of its rem high halves is)
-      auto look = [&](int q) {
-        if (q >= nblk) return 0;
-        if (q == nfq) return settle(static_cast<uint32_t>(q));
-        const miso_u32x4 hi = miso_philox4x32(static_cast<uint32_t>(q), iter, c2_gibbs, event_id, k0, k1);
-        bool on = false;
-        for (int h = 0; h < 8; h++) on |= miso_block_half(hi, h) == th;
-        return on ? settle(static_cast<uint32_t>(q)) : 0;
-      };
-      if (amb_n == K2_FLAG_ONE && !settle_all) {        // one trip's blocks, or one single step's block ...
-        const int k = static_cast<int>(amb_t), nb = k < UQ * uq_trips ? UQ : 1;
-        for (int i = 0; i < nb; i++) d0 += look(sub + (k + i) * GE);
-      } else if ((amb_n == K2_FLAG_MANY || settle_all) && lane_used) {   // ... or, with several such trips, all of the lane's
-        for (int q = sub; q < nblk; q += GE) d0 += look(q);
-      }
-    }
+    // behind the loop: the lane's reads on isoform 0 from its sum and its flag (k2_finish_lane above)
+    d0 = k2_finish_lane<UQ>(d0, amb, th, tl, sub, GE, nfq, rem, nblk, npos, uq_trips, lane_used, a.pe_force_exact != 0,
+                            [&](int q, bool low) {
+                              return miso_philox4x32(static_cast<uint32_t>(q), iter, low ? (MISO_SITE_GIBBS_LOW | (chain << 8)) : c2_gibbs,
+                                                     event_id, k0, k1);
+                            });
     PROF_T(g2);
     PROF_ADD(pf_loop, g1, g2);
     if (POW2) {

@@ -128,6 +128,61 @@ __global__ void __launch_bounds__(256) selftest_k2_flag_kernel(const uint32_t *m
   pos[i] = p;
 }
 
+// k2_count.hpp's assembly statements: element i is one lane, its words u[start[i]] .. u[start[i + 1] - 1] (an even number) taken
+// two per statement as the read loop takes them, the first pair in the form that starts o; masked[i]: the tail's form with inv
+__global__ void __launch_bounds__(256) selftest_k2_count_kernel(const uint32_t *th, const int32_t *start, const uint32_t *u,
+                                                                const uint32_t *inv, const int32_t *masked, int n, uint32_t *acc_out,
+                                                                uint32_t *o_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t P = k2_count_p(th[i]), two = K2_COUNT_TWO;
+  uint32_t acc = 0, o = 0;
+  const int j0 = start[i], j1 = start[i + 1];
+  if (masked[i]) {
+    if (j0 < j1) k2_count_pair_masked<true>(acc, o, P, two, u[j0], u[j0 + 1], inv[j0], inv[j0 + 1]);
+    for (int j = j0 + 2; j < j1; j += 2) k2_count_pair_masked<false>(acc, o, P, two, u[j], u[j + 1], inv[j], inv[j + 1]);
+  } else {
+    if (j0 < j1) k2_count_pair<true>(acc, o, P, two, u[j0], u[j0 + 1]);
+    for (int j = j0 + 2; j < j1; j += 2) k2_count_pair<false>(acc, o, P, two, u[j], u[j + 1]);
+  }
+  acc_out[i] = acc;
+  o_out[i] = o;
+}
+
+// kernels_k2.inl k2_finish_lane, the code behind the single-end read loop, with a caller-given threshold t: element i is a
+// chain on ONE lane (GE = 1) of n_draw[i] reads at iteration iter[i]; its sum and flag come from k2_count.hpp's plain functions
+// over its blocks, in trips of two blocks and a single step as the loop takes them.  out[i] = the reads with uniform below t[i].
+__global__ void __launch_bounds__(64) selftest_k2_finish_kernel(uint64_t seed, const uint32_t *event_id, const uint32_t *chain,
+                                                                 const uint32_t *iter, const int32_t *n_draw, const uint64_t *t,
+                                                                 int settle_all, int n, int32_t *out) {
+  const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool used = i0 < n;
+  const int i = used ? i0 : n - 1;   // (every lane of the wavefront goes through the wave-wide vote)
+  constexpr int UQ = 2;
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+  const uint32_t ev = event_id[i], ch = chain[i], it = iter[i];
+  const uint32_t th = static_cast<uint32_t>(t[i] >> 16), tl = static_cast<uint32_t>(t[i]) & 0xFFFFu;
+  const int nfq = n_draw[i] >> 3, rem = n_draw[i] & 7, nblk = nfq + (rem != 0 ? 1 : 0), npos = nblk, uq_trips = npos / UQ;
+  auto draw = [&](int q, bool low) {
+    return miso_philox4x32(static_cast<uint32_t>(q), it, (low ? MISO_SITE_GIBBS_LOW : MISO_SITE_GIBBS) | (ch << 8), ev, k0, k1);
+  };
+  const uint32_t P = k2_count_p(th);
+  int A = 0; K2Flag amb;
+  for (int k = 0; k < npos;) {
+    const int nb = k < UQ * uq_trips ? UQ : 1;
+    uint32_t acc = 0, o = 0;
+    for (int b = 0; b < nb; b++) {
+      const miso_u32x4 u = draw(k + b, false);
+      for (int w = 0; w < 4; w++) k2_count_step(acc, o, P, u.v[w], (k + b) < nfq ? 0u : k2_part_inv(rem, w));
+    }
+    A += k2_count_sum(acc);
+    k2_flag_note_z(amb, k2_count_flag(o), static_cast<uint32_t>(k));
+    k += nb;
+  }
+  const int d0 = k2_finish_lane<UQ>(A, amb, th, tl, 0, 1, nfq, rem, nblk, npos, uq_trips, used, settle_all != 0, draw);
+  if (used) out[i] = d0;
+}
+
 __global__ void __launch_bounds__(256) selftest_text_digits_kernel(const double *x, int n, int64_t *out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = text_digits(x[i]);
@@ -323,6 +378,44 @@ void selftest_k2_flag(const uint32_t *m, const uint32_t *k, const int32_t *start
   hipLaunchKernelGGL(selftest_k2_flag_kernel, st_grid(n), dim3(256), 0, 0, dm, dk, dstart, n, dcode, dpos);
   b.back(code, dcode, static_cast<size_t>(n));
   b.back(pos, dpos, static_cast<size_t>(n));
+}
+
+void selftest_k2_count(const uint32_t *th, const int32_t *start, const uint32_t *u, const uint32_t *inv, const int32_t *masked, int n,
+                       uint32_t *acc, uint32_t *o) {
+  st_need_device(n);
+  if (n == 0) return;
+  if (start[0] != 0) MISO_FAIL(MISO_EINVAL, "start[0] must be 0");
+  for (int i = 0; i < n; i++) {
+    if (start[i + 1] < start[i] || ((start[i + 1] - start[i]) & 1)) MISO_FAIL(MISO_EINVAL, "start must not decrease; two words per statement");
+    if (th[i] > 65536u) MISO_FAIL(MISO_EINVAL, "th: 0 .. 65536");
+    if (!masked[i]) for (int j = start[i]; j < start[i + 1]; j++) if (inv[j] != 0) MISO_FAIL(MISO_EINVAL, "the steady form has no masks");
+  }
+  const size_t total = static_cast<size_t>(start[n]);
+  StBuffers b;
+  const uint32_t *dth = b.in(th, static_cast<size_t>(n)), *du = b.in(u, total), *dinv = b.in(inv, total);
+  const int32_t *dstart = b.in(start, static_cast<size_t>(n) + 1), *dmasked = b.in(masked, static_cast<size_t>(n));
+  uint32_t *dacc = b.out<uint32_t>(static_cast<size_t>(n)), *do_ = b.out<uint32_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_k2_count_kernel, st_grid(n), dim3(256), 0, 0, dth, dstart, du, dinv, dmasked, n, dacc, do_);
+  b.back(acc, dacc, static_cast<size_t>(n));
+  b.back(o, do_, static_cast<size_t>(n));
+}
+
+void selftest_k2_finish(uint64_t seed, const uint32_t *event_id, const uint32_t *chain, const uint32_t *iter, const int32_t *n_draw,
+                        const uint64_t *t, int settle_all, int n, int32_t *out) {
+  st_need_device(n);
+  if (n == 0) return;
+  for (int i = 0; i < n; i++) {
+    if (n_draw[i] < 0 || n_draw[i] > (1 << 20)) MISO_FAIL(MISO_EINVAL, "n_draw: 0 .. 2^20");
+    if (t[i] > 4294967296ull) MISO_FAIL(MISO_EINVAL, "t: 0 .. 2^32");
+    if (chain[i] >= (1u << 24)) MISO_FAIL(MISO_EINVAL, "chain: below 2^24");
+  }
+  StBuffers b;
+  const uint32_t *dev = b.in(event_id, static_cast<size_t>(n)), *dch = b.in(chain, static_cast<size_t>(n)), *dit = b.in(iter, static_cast<size_t>(n));
+  const int32_t *dn = b.in(n_draw, static_cast<size_t>(n));
+  const uint64_t *dt = b.in(t, static_cast<size_t>(n));
+  int32_t *dout = b.out<int32_t>(static_cast<size_t>(n));
+  hipLaunchKernelGGL(selftest_k2_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, seed, dev, dch, dit, dn, dt, settle_all, n, dout);
+  b.back(out, dout, static_cast<size_t>(n));
 }
 
 void selftest_text_digits(const double *x, int n, int64_t *out) {

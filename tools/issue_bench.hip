@@ -215,6 +215,16 @@ __global__ void k_ds_read_b64(uint32_t *out, int n, uint32_t seed, unsigned long
 // with: the difference of the two rows is what the nop costs (two instructions per entry, per_trip counts both)
 #define M_PK_DEP(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n v_pk_min_u16 %" #i ", %" #i ", %11\n"
 #define M_PK_DEP_NOP(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n s_nop 0\n v_pk_min_u16 %" #i ", %" #i ", %11\n"
+// the read loop's three-way count (csrc/k2_count.hpp): plain 32-bit or / and, and the four operations of one generator word
+// -- sub clamp, min, add, or -- chained through ONE register: each reads the result of the one before it (four instructions
+// per entry, per_trip counts all four).  That is STRICTER than the loop, where the add and the or both read the min's result
+// and write two other registers: the row is an upper bound for the word, not its cost in the loop.
+#define M_OR(i) "v_or_b32 %" #i ", %" #i ", %10\n"
+#define M_AND(i) "v_and_b32 %" #i ", %" #i ", %10\n"
+#define M_COUNT_WORD(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n v_pk_min_u16 %" #i ", %" #i ", %11\n v_add_u32 %" #i ", %" #i ", %10\n v_or_b32 %" #i ", %" #i ", %11\n"
+DEF_KERNEL_32M(k_or, P_NONE, M_OR)
+DEF_KERNEL_32M(k_and, P_NONE, M_AND)
+DEF_KERNEL_32M(k_count_word, P_NONE, M_COUNT_WORD)
 DEF_KERNEL_32M(k_bcnt, P_NONE, M_BCNT)
 DEF_KERNEL_32M(k_pk_dep, P_NONE, M_PK_DEP)
 DEF_KERNEL_32M(k_pk_dep_nop, P_NONE, M_PK_DEP_NOP)
@@ -292,6 +302,7 @@ int main() {
     {"v_bfi_b32", k_bfi, 64}, {"v_pk_sub_u16 clamp", k_pk_sub_clamp, 64}, {"v_pk_min_u16", k_pk_min, 64},
     {"v_pk_add_u16", k_pk_add, 64}, {"v_readlane+s_nop+v_add", k_readlane_nop, 64},
     {"v_bcnt_u32_b32", k_bcnt, 64}, {"pk_sub, pk_min dependent", k_pk_dep, 128}, {"pk_sub, s_nop 0, pk_min", k_pk_dep_nop, 128},
+    {"v_or_b32", k_or, 64}, {"v_and_b32", k_and, 64}, {"pk_sub, pk_min, add, or", k_count_word, 256},
     {"ds_bpermute (8 + wait)", k_ds_bpermute, 64}, {"ds_bpermute, one + wait", k_ds_bpermute_serial, 64},
   };
   const int n = 2000;
