@@ -36,6 +36,7 @@ void selftest_k2_count(const uint32_t *th, const int32_t *start, const uint32_t 
                        uint32_t *acc, uint32_t *o);
 // kernels_exact.hip: the exact-posterior mode's posterior stage on its own (miso_selftest_exact, exact summaries)
 void exact_probe_run(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st = nullptr);
+void exact_check_prob(const double *prob, int n_prob);   // MISO_EINVAL unless every probability lies inside (0, 1)
 // kernels_exact_compare.hip: pairs of such posteriors compared (miso_batch_compare_exact, miso_selftest_exact_compare);
 // out: 5 + n_z doubles per pair
 void exact_compare_run(const double *stats7_1, const double *stats7_2, int n, const double *z, int n_z, double *out,
@@ -56,6 +57,9 @@ constexpr double EXACT_PAIRED_MIN_PROB = 1.0 / 9223372036854775808.0;   // 2^-63
 inline bool exact_paired_eligible(int K, const double *A, const double *hyper, bool any_bad) {
   return K == 2 && A[0] > 0 && A[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1 && !any_bad;
 }
+// n elements given by a caller: MISO_EINVAL unless every row of stats6 is eligible and -- offs != null: caller-given pairs --
+// the offsets start at 0 and ascend and the probabilities m lie in [2^-63, 1]; returns the number of caller-given pairs
+int64_t exact_paired_check(const double *stats6, const double *m, const int64_t *offs, int n);
 // kernels_exact_paired_compare.hip: pairs of such posteriors compared (miso_batch_compare_exact_paired,
 // miso_selftest_exact_paired_compare).  One sample's side of the n pairs, as the host driver takes it: stats6 (host) =
 // {n10, n01, A0, A1, h0, h1} per pair, and the drawing pairs EITHER as caller-given probabilities m / offs (host, the

@@ -1,7 +1,8 @@
 // exact_paired.hpp -- the paired-end exact-posterior mode's device functions (the scheme is described in
 // kernels_exact_paired.hip; kernels_exact_paired_compare.hip, DESIGN.md 18, tabulates the product of two such densities with
 // them).  Built on exact_posterior.hpp, which it leaves as it is: ExactStats / exact_point with e = A give the pair-free part
-// of the density, exact_invert the inverse of the table.  -ffp-contract=off.
+// of the density, exact_invert the inverse of the table.  Also what both units need of an element: its drawing pairs, c8, the
+// loader of a (stats6, pairs) element and the workgroup's LDS layout.  -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,48 @@ struct ExactPairs {
   int il;
   const double *mm;
   int n;
+};
+
+// the drawing pairs of a resident event: its plain records (u16 f0, f1 per pair) in the batch's input pool
+__device__ __forceinline__ ExactPairs exact_pairs_resident(const unsigned char *in_pool, const DevEvent &E, const double *fp, int il) {
+  return ExactPairs{reinterpret_cast<const uint32_t *>(in_pool + E.off_draw), fp, il, nullptr, E.n_draw};
+}
+
+// (n + h0 + h1) / 32 from hyper - 1 (exact_paired_window's c8)
+__device__ __forceinline__ double exact_paired_c8(double n, double hm0, double hm1) {
+  return (n + ((hm0 + 1.0) + (hm1 + 1.0))) * 0.03125;
+}
+
+// Element i as the probe and compare kernels take it: statistics and c8 from row i of stats6 = {n10, n01, A0, A1, h0, h1} and
+// the number of its drawing pairs, which are EITHER caller-given probabilities (mm != null; offs[i], offs[i + 1] bound them) OR
+// the records of the resident event list[i] of a batch (in_pool, events, fp, il).  (The sampling kernel and the summaries' probe
+// take a resident event's statistics from the batch's pool instead: kernels_exact_paired.hip exact_paired_event.)
+// uni: what the caller makes of the statistics and of c8 before it keeps them -- nothing (ExactAsIs), or the comparison's move to
+// scalar registers (kernels_exact_paired_compare.hip exact_uni).  A parameter, applied to the expressions themselves: with the
+// move made afterwards by a wrapper the comparison kernel came out laid out differently and 0.5 % slower on a thousand pairs.
+struct ExactAsIs {
+  template <class T> __device__ __forceinline__ T operator()(const T &v) const { return v; }
+};
+template <class Uni = ExactAsIs>
+__device__ __forceinline__ void exact_paired_element(const double *stats6, const double *mm, const int64_t *offs, const unsigned char *in_pool,
+                                                     const DevEvent *events, const int32_t *list, const double *fp, int il, int i,
+                                                     ExactStats &st, double &c8, ExactPairs &pr, Uni uni = Uni()) {
+  const double *q = stats6 + 6 * static_cast<size_t>(i);
+  if (mm) {
+    pr.rec = nullptr; pr.fp = nullptr; pr.il = 0;
+    pr.mm = mm + 2 * static_cast<size_t>(offs[i]); pr.n = static_cast<int>(offs[i + 1] - offs[i]);
+  } else {
+    pr = exact_pairs_resident(in_pool, events[list[i]], fp, il);
+  }
+  const double nn = (q[0] + q[1]) + static_cast<double>(pr.n), hm0 = q[4] - 1.0, hm1 = q[5] - 1.0;
+  st = uni(exact_stats(q[0], q[1], nn, q[2], q[3], hm0, hm1));
+  c8 = uni(exact_paired_c8(nn, hm0, hm1));
+}
+
+// the workgroup's LDS: one F / f pair (37 KB), the reductions' and the staged pairs' buffers, f at the points -1 and G + 1
+struct ExactPairedLds {
+  double F[EXACT_PAD], f[EXACT_PAD], red[256], mbuf[2 * EXP_CHUNK], fext[2];
+  int redi[128];
 };
 
 // pairs [base, base + cnt) of the event -> mbuf[2 i], mbuf[2 i + 1]; lane i brings pair base + i

@@ -1,11 +1,15 @@
 // exact_posterior.hpp -- the exact-posterior mode's device functions: the density of psi of a single-end
 // two-isoform event in logit space, its mode and window, its table on 2049 points, the inverse of the tabulated CDF.
-// Shared by kernels_exact.hip (the mode itself; the scheme is described there) and kernels_exact_compare.hip (two such
-// posteriors compared).  Units that include it are built with -ffp-contract=off.
+// Shared by kernels_exact.hip (the mode itself; the scheme is described there), kernels_exact_compare.hip (two such
+// posteriors compared; exact_compare.hpp) and, through exact_paired.hpp, the paired-end mode, whose sampling
+// kernel draws its uniforms and fills its chain records with the two functions at the end.  Units that include it are built
+// with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "device.hpp"
 #include "miso_detmath.h"
+#include "miso_philox.h"
 
 namespace miso {
 
@@ -177,6 +181,21 @@ __device__ __forceinline__ ExactAt exact_at(const ExactStats &s, double t) {
   r.ly = pos ? naL : nL;
   r.ldx = p.ld - p.L;
   return r;
+}
+
+// the uniform of sample s: (word + 0.5) 2^-32, word 0 of Philox(key = seed (k0, k1), ctr = (s, 0, MISO_SITE_EXACT, event id))
+__device__ __forceinline__ double exact_uniform(int s, uint32_t event_id, uint32_t k0, uint32_t k1) {
+  const miso_u32x4 w = miso_philox4x32(static_cast<uint32_t>(s), 0u, MISO_SITE_EXACT, event_id, k0, k1);
+  return (static_cast<double>(w.v[0]) + 0.5) * (1.0 / 4294967296.0);
+}
+
+// no chain ran: every sample counts as accepted, dealt over the C chains' records so that they add up to S
+__device__ __forceinline__ void exact_chain_stats(ChainStats *cs, int C, int S, int lane) {
+  for (int c = lane; c < C; c += 64) {
+    cs[c].counts_hash = 0;
+    cs[c].accepted = (S + C - 1 - c) / C;
+    cs[c].hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);
+  }
 }
 
 }  // namespace miso

@@ -20,6 +20,7 @@
 
 #include "batch.hpp"
 #include "compare_column.hpp"
+#include "hip_host.hpp"
 
 namespace miso {
 
@@ -75,20 +76,13 @@ __global__ __launch_bounds__(256) void compare_groups_kernel(const DevEvent *con
 }
 
 // (a HIP runtime failure is MISO_ENODEVICE as everywhere in runtime.hip -- include/miso_amd.h: "no usable HIP device / HIP
-// runtime error" -- except memory: a chunk whose n1 * n2 results do not fit is MISO_ENOMEM, MemoryError in Python)
-#define GRP_HIP_OK(call)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(e_ == hipErrorOutOfMemory ? MISO_ENOMEM : MISO_ENODEVICE,                  \
-                std::string(#call) + ": " + hipGetErrorString(e_));                        \
-  } while (0)
-
+// runtime error" -- except memory: a chunk whose n1 * n2 results do not fit is MISO_ENOMEM, MemoryError in Python:
+// hip_host.hpp HIP_OK_OR_NOMEM)
 namespace {
 struct DevMem {
   void *p = nullptr;
   ~DevMem() { if (p) (void) hipFree(p); }
-  void alloc(size_t bytes) { GRP_HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
+  void alloc(size_t bytes) { HIP_OK_OR_NOMEM(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
 };
 }  // namespace
 
@@ -131,14 +125,14 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
   if (need_len && !out) MISO_FAIL(MISO_EINVAL, "out is NULL");
   if (kernel_ms) *kernel_ms = 0.f;
   if (n == 0) return;
-  GRP_HIP_OK(hipSetDevice(r.device));
-  for (miso_batch *b : all) GRP_HIP_OK(hipStreamSynchronize(b->stream));
+  HIP_OK_OR_NOMEM(hipSetDevice(r.device));
+  for (miso_batch *b : all) HIP_OK_OR_NOMEM(hipStreamSynchronize(b->stream));
 
   // the LDS a workgroup may have beside the kernel's own reduction buffers
   int lds_max = 0;
-  GRP_HIP_OK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, r.device));
+  HIP_OK_OR_NOMEM(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, r.device));
   hipDeviceProp_t prop{};
-  GRP_HIP_OK(hipGetDeviceProperties(&prop, r.device));
+  HIP_OK_OR_NOMEM(hipGetDeviceProperties(&prop, r.device));
   // (gfx950: 160 KiB per CU, all of it open to one workgroup, whatever the attribute says)
   if (std::string(prop.gcnArchName).rfind("gfx950", 0) == 0) lds_max = std::max(lds_max, 160 * 1024);
   using Kernel = void (*)(const DevEvent *const *, const unsigned char *const *, int, int, int, int, double, const uint64_t *,
@@ -146,7 +140,7 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
   const Kernel kernels[4] = {compare_groups_kernel<false, false>, compare_groups_kernel<true, true>,
                              compare_groups_kernel<true, false>, compare_groups_kernel<false, true>};
   hipFuncAttributes fa{};
-  GRP_HIP_OK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernels[1])));
+  HIP_OK_OR_NOMEM(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernels[1])));
   const size_t budget = static_cast<size_t>(lds_max) > fa.sharedSizeBytes ? lds_max - fa.sharedSizeBytes : 0;
   const size_t col = static_cast<size_t>(S) * 8;
   if (staging == MISO_STAGE_AUTO) staging = compare_groups_staging(n1, n2, S, budget);
@@ -154,7 +148,7 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
   if (dyn > budget) MISO_FAIL(MISO_EINVAL, "The requested staging does not fit the workgroup's LDS");
   const Kernel kernel = kernels[staging == MISO_STAGE_BOTH ? 1 : staging == MISO_STAGE_NONE ? 0 : (n1 <= n2 ? 2 : 3)];
   if (dyn > 0)
-    GRP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    HIP_OK_OR_NOMEM(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(dyn)));
 
   std::vector<const void *> ptrs(2 * static_cast<size_t>(nb));
@@ -164,18 +158,18 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
   d_off.alloc(n * sizeof(uint64_t));
   d_cmp.alloc(need_len * sizeof(double));
   hipStream_t st = r.stream;
-  GRP_HIP_OK(hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
-  GRP_HIP_OK(hipMemcpyAsync(d_off.p, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  GRP_HIP_OK(hipEventRecord(r.ev0, st));
+  HIP_OK_OR_NOMEM(hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
+  HIP_OK_OR_NOMEM(hipMemcpyAsync(d_off.p, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  HIP_OK_OR_NOMEM(hipEventRecord(r.ev0, st));
   hipLaunchKernelGGL(kernel, dim3(n, kmax), dim3(256), dyn, st,
                      static_cast<const DevEvent *const *>(d_ptrs.p),
                      static_cast<const unsigned char *const *>(d_ptrs.p) + nb, n1, n2, n, S, smoothing,
                      static_cast<const uint64_t *>(d_off.p), tot, static_cast<double *>(d_cmp.p));
-  GRP_HIP_OK(hipGetLastError());
-  GRP_HIP_OK(hipEventRecord(r.ev1, st));
-  GRP_HIP_OK(hipMemcpyAsync(out, d_cmp.p, need_len * sizeof(double), hipMemcpyDeviceToHost, st));
-  GRP_HIP_OK(hipStreamSynchronize(st));
-  if (kernel_ms) GRP_HIP_OK(hipEventElapsedTime(kernel_ms, r.ev0, r.ev1));
+  HIP_OK_OR_NOMEM(hipGetLastError());
+  HIP_OK_OR_NOMEM(hipEventRecord(r.ev1, st));
+  HIP_OK_OR_NOMEM(hipMemcpyAsync(out, d_cmp.p, need_len * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK_OR_NOMEM(hipStreamSynchronize(st));
+  if (kernel_ms) HIP_OK_OR_NOMEM(hipEventElapsedTime(kernel_ms, r.ev0, r.ev1));
 }
 
 }  // namespace miso

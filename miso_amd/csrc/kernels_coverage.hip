@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip_host.hpp"
 #include "host.hpp"
 #include "miso_alnio.h"
 
@@ -109,17 +110,6 @@ __global__ __launch_bounds__(kBlock) void coverage_record_kernel(const int32_t *
   wave_bin_add(hist_b, b);
 }
 
-#define COV_HIP_OK(call)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 template <class F> void parallel_for(int64_t n, int T, F &&body) {
   T = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(T, n / 65536 + 1)));
   std::vector<std::thread> th;
@@ -135,30 +125,30 @@ struct Scratch {
   std::vector<hipEvent_t> events;
   template <class T> T *alloc(size_t count) {
     void *p = nullptr;
-    COV_HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+    HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
     dev.push_back(p);
     return static_cast<T *>(p);
   }
   template <class T> T *upload(const std::vector<T> &v) {
     T *d = alloc<T>(v.size());
-    if (!v.empty()) COV_HIP_OK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (!v.empty()) HIP_OK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return d;
   }
   template <class T> T *host(size_t count) {
     void *p = nullptr;
-    COV_HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
     pinned.push_back(p);
     return static_cast<T *>(p);
   }
   hipStream_t stream() {
     hipStream_t s = nullptr;
-    COV_HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     streams.push_back(s);
     return s;
   }
   hipEvent_t event() {
     hipEvent_t e = nullptr;
-    COV_HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventCreate(&e));
     events.push_back(e);
     return e;
   }
@@ -250,7 +240,7 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
   const size_t n_bins = static_cast<size_t>(n_a + n_b + 1);
   unsigned long long *d_bins = s.alloc<unsigned long long>(n_bins);
   unsigned long long *d_ha = d_bins, *d_hb = d_bins + n_a, *d_kept = d_bins + n_a + n_b;
-  COV_HIP_OK(hipMemset(d_bins, 0, n_bins * 8));
+  HIP_OK(hipMemset(d_bins, 0, n_bins * 8));
 
   const int64_t slot_n = std::min<int64_t>(C, std::max<int64_t>(N, 1));
   struct Slot { int32_t *h_in, *d_in; hipStream_t st; hipEvent_t e0, e1; bool busy; };
@@ -261,9 +251,9 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
     q.st = s.stream(); q.e0 = s.event(); q.e1 = s.event(); q.busy = false;
   }
   auto drain = [&](Slot &q) {
-    COV_HIP_OK(hipStreamSynchronize(q.st));
+    HIP_OK(hipStreamSynchronize(q.st));
     float ms = 0.f;
-    COV_HIP_OK(hipEventElapsedTime(&ms, q.e0, q.e1));
+    HIP_OK(hipEventElapsedTime(&ms, q.e0, q.e1));
     st.records_ms += ms;
     q.busy = false;
   };
@@ -280,16 +270,16 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
       std::memcpy(h_end + lo, c.end + first + lo, static_cast<size_t>(hi - lo) * 4);
       for (int64_t k = lo; k < hi; k++) h_rid[k] = (c.flag[first + k] & 0x4) ? -1 : c.ref_id[first + k];
     });
-    COV_HIP_OK(hipEventRecord(q.e0, q.st));
+    HIP_OK(hipEventRecord(q.e0, q.st));
     for (int p = 0; p < 3; p++)
-      COV_HIP_OK(hipMemcpyAsync(q.d_in + p * slot_n, q.h_in + p * slot_n, static_cast<size_t>(cn) * 4,
+      HIP_OK(hipMemcpyAsync(q.d_in + p * slot_n, q.h_in + p * slot_n, static_cast<size_t>(cn) * 4,
                                 hipMemcpyHostToDevice, q.st));
     const int n = static_cast<int>(cn);
     coverage_record_kernel<<<dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, q.st>>>(
         q.d_in, q.d_in + slot_n, q.d_in + 2 * slot_n, n, d_off, nref, d_s0, d_pmax, d_ka, n_a, d_kb, n_b, d_ha, d_hb,
         d_kept);
-    COV_HIP_OK(hipGetLastError());
-    COV_HIP_OK(hipEventRecord(q.e1, q.st));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(q.e1, q.st));
     q.busy = true;
   }
   for (Slot &q : slot)
@@ -298,7 +288,7 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
   // rank step: the histograms back, prefix sums, one difference per interval
   t0 = std::chrono::steady_clock::now();
   std::vector<unsigned long long> bins(n_bins);
-  COV_HIP_OK(hipMemcpy(bins.data(), d_bins, n_bins * 8, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(bins.data(), d_bins, n_bins * 8, hipMemcpyDeviceToHost));
   std::partial_sum(bins.begin(), bins.begin() + n_a, bins.begin());
   std::partial_sum(bins.begin() + n_a, bins.begin() + n_a + n_b, bins.begin() + n_a);
   for (int i = 0; i < n_iv; i++)

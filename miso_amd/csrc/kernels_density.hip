@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip_host.hpp"
 #include "host.hpp"
 #include "miso_alnio.h"
 
@@ -228,17 +229,6 @@ __global__ __launch_bounds__(kBlock) void density_finish_kernel(const int64_t *r
   }
 }
 
-#define DEN_HIP_OK(call)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 template <class F> void parallel_for(int64_t n, int T, F &&body) {
   T = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(T, n / 65536 + 1)));
   std::vector<std::thread> th;
@@ -254,13 +244,13 @@ struct Scratch {
   std::vector<hipEvent_t> events;
   template <class T> T *alloc(size_t count) {
     void *p = nullptr;
-    DEN_HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+    HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
     dev.push_back(p);
     return static_cast<T *>(p);
   }
   template <class T> T *upload(const std::vector<T> &v) {
     T *d = alloc<T>(v.size());
-    if (!v.empty()) DEN_HIP_OK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (!v.empty()) HIP_OK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return d;
   }
   void release(void *p) {
@@ -269,19 +259,19 @@ struct Scratch {
   }
   template <class T> T *host(size_t count) {
     void *p = nullptr;
-    DEN_HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
     pinned.push_back(p);
     return static_cast<T *>(p);
   }
   hipStream_t stream() {
     hipStream_t s = nullptr;
-    DEN_HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     streams.push_back(s);
     return s;
   }
   hipEvent_t event() {
     hipEvent_t e = nullptr;
-    DEN_HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventCreate(&e));
     events.push_back(e);
     return e;
   }
@@ -405,9 +395,9 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
   }
   double device_ms = 0.0;
   auto drain = [&](Slot &q) {
-    DEN_HIP_OK(hipStreamSynchronize(q.st));
+    HIP_OK(hipStreamSynchronize(q.st));
     float ms = 0.f;
-    DEN_HIP_OK(hipEventElapsedTime(&ms, q.e0, q.e1));
+    HIP_OK(hipEventElapsedTime(&ms, q.e0, q.e1));
     device_ms += ms;
     q.busy = false;
   };
@@ -432,19 +422,19 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
         std::memcpy(h_cig + a, c.cigar + w0 + a, static_cast<size_t>(b - a) * 4);
       });
       h_off[cn] = static_cast<uint32_t>(wn);
-      DEN_HIP_OK(hipEventRecord(q.e0, q.st));
+      HIP_OK(hipEventRecord(q.e0, q.st));
       for (int p = 0; p < 3; p++)
-        DEN_HIP_OK(hipMemcpyAsync(q.d_in + p * slot_n, q.h_in + p * slot_n, static_cast<size_t>(cn) * 4,
+        HIP_OK(hipMemcpyAsync(q.d_in + p * slot_n, q.h_in + p * slot_n, static_cast<size_t>(cn) * 4,
                                   hipMemcpyHostToDevice, q.st));
-      DEN_HIP_OK(hipMemcpyAsync(q.d_in + 3 * slot_n, q.h_in + 3 * slot_n, static_cast<size_t>(cn + 1) * 4,
+      HIP_OK(hipMemcpyAsync(q.d_in + 3 * slot_n, q.h_in + 3 * slot_n, static_cast<size_t>(cn + 1) * 4,
                                 hipMemcpyHostToDevice, q.st));
       if (wn > 0)
-        DEN_HIP_OK(hipMemcpyAsync(q.d_in + 4 * slot_n + 1, q.h_in + 4 * slot_n + 1, static_cast<size_t>(wn) * 4,
+        HIP_OK(hipMemcpyAsync(q.d_in + 4 * slot_n + 1, q.h_in + 4 * slot_n + 1, static_cast<size_t>(wn) * 4,
                                   hipMemcpyHostToDevice, q.st));
       launch(q.d_in, q.d_in + slot_n, q.d_in + 2 * slot_n, reinterpret_cast<const uint32_t *>(q.d_in + 3 * slot_n),
              reinterpret_cast<const uint32_t *>(q.d_in + 4 * slot_n + 1), static_cast<int>(cn), q.st);
-      DEN_HIP_OK(hipGetLastError());
-      DEN_HIP_OK(hipEventRecord(q.e1, q.st));
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord(q.e1, q.st));
       q.busy = true;
     }
     for (Slot &q : slot)
@@ -459,13 +449,13 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
   int64_t *d_len = s.alloc<int64_t>(valid.size()), *d_out = s.alloc<int64_t>(valid.size());
   int32_t *d_index = s.alloc<int32_t>(valid.size());
   auto put = [&](auto *dst, const auto &v) {
-    if (!v.empty()) DEN_HIP_OK(hipMemcpy(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+    if (!v.empty()) HIP_OK(hipMemcpy(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
   };
   put(d_ref_off, all.ref_off); put(d_start, all.start); put(d_pmax, all.pmax);
   unsigned int *d_bits = s.alloc<unsigned int>(kMaxQlen / 32);
   unsigned long long *d_counters = s.alloc<unsigned long long>(kNCounters);
-  DEN_HIP_OK(hipMemset(d_bits, 0, kMaxQlen / 32 * sizeof(unsigned int)));
-  DEN_HIP_OK(hipMemset(d_counters, 0, kNCounters * sizeof(unsigned long long)));
+  HIP_OK(hipMemset(d_bits, 0, kMaxQlen / 32 * sizeof(unsigned int)));
+  HIP_OK(hipMemset(d_counters, 0, kNCounters * sizeof(unsigned long long)));
   stream_records([&](const int32_t *r, const int32_t *p, const int32_t *e, const uint32_t *off, const uint32_t *cg, int n,
                      hipStream_t q) {
     density_mark_kernel<<<blocks_of(n), dim3(kBlock), 0, q>>>(r, p, e, off, cg, n, d_ref_off, nref, d_start, d_pmax,
@@ -475,8 +465,8 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
   device_ms = 0.0;
   std::vector<unsigned int> bits(kMaxQlen / 32);
   unsigned long long counters[kNCounters];
-  DEN_HIP_OK(hipMemcpy(bits.data(), d_bits, bits.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
-  DEN_HIP_OK(hipMemcpy(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(bits.data(), d_bits, bits.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost));
   if (counters[kQlenOver])
     MISO_FAIL(MISO_EINVAL, "a fetched record has qlen " + std::to_string(counters[kQlenOver]) + ": the density pass holds qlen up to " + std::to_string(kMaxQlen - 1));
   st.fetched = static_cast<int64_t>(counters[kFetched]);
@@ -548,8 +538,8 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
     put(d_acc, acc); put(d_len, len); put(d_out, out); put(d_index, t.index);
     st.tables_ms += ms_since(t0);
     for (;;) {
-      DEN_HIP_OK(hipMemset(d_diff, 0, static_cast<size_t>(dn) * sizeof(int)));
-      DEN_HIP_OK(hipMemset(d_jx_count, 0, sizeof(unsigned long long)));
+      HIP_OK(hipMemset(d_diff, 0, static_cast<size_t>(dn) * sizeof(int)));
+      HIP_OK(hipMemset(d_jx_count, 0, sizeof(unsigned long long)));
       const unsigned long long cap = static_cast<unsigned long long>(jx_cap);
       stream_records([&](const int32_t *r, const int32_t *p, const int32_t *e, const uint32_t *off, const uint32_t *cg,
                          int n, hipStream_t q) {
@@ -560,13 +550,13 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
       st.records_ms += device_ms;
       device_ms = 0.0;
       unsigned long long found = 0;
-      DEN_HIP_OK(hipMemcpy(&found, d_jx_count, sizeof(found), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(&found, d_jx_count, sizeof(found), hipMemcpyDeviceToHost));
       if (found <= cap) {
         t0 = std::chrono::steady_clock::now();
         h_jx_region.resize(found); h_jx_sites.resize(found);
         if (found) {
-          DEN_HIP_OK(hipMemcpy(h_jx_region.data(), d_jx_region, found * sizeof(int32_t), hipMemcpyDeviceToHost));
-          DEN_HIP_OK(hipMemcpy(h_jx_sites.data(), d_jx_sites, found * sizeof(uint64_t), hipMemcpyDeviceToHost));
+          HIP_OK(hipMemcpy(h_jx_region.data(), d_jx_region, found * sizeof(int32_t), hipMemcpyDeviceToHost));
+          HIP_OK(hipMemcpy(h_jx_sites.data(), d_jx_sites, found * sizeof(uint64_t), hipMemcpyDeviceToHost));
         }
         for (size_t k = 0; k < found; k++) keys.push_back(Key{h_jx_region[k], h_jx_sites[k]});
         st.junction_ms += ms_since(t0);
@@ -582,22 +572,22 @@ void region_densities(const miso_alnfile_t *f, int device, int n_regions, const 
     // scan and finish
     hipEvent_t e0 = slot[0].e0, e1 = slot[0].e1;
     hipStream_t qs = slot[0].st;
-    DEN_HIP_OK(hipEventRecord(e0, qs));
+    HIP_OK(hipEventRecord(e0, qs));
     const int64_t rows = static_cast<int64_t>(members.size()) * n_classes;
     if (rows >= (int64_t{1} << 31)) MISO_FAIL(MISO_EINVAL, "too many (region, class) rows in one group: lower the budget");
     density_scan_kernel<<<dim3(static_cast<unsigned>(rows)), dim3(kBlock), 0, qs>>>(d_acc, d_len, n_classes, d_diff);
-    DEN_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     density_finish_kernel<<<dim3(static_cast<unsigned>(members.size())), dim3(kBlock), 0, qs>>>(
         d_acc, d_len, d_out, n_classes, d_qlen_of, d_diff, d_depth, d_wiggle);
-    DEN_HIP_OK(hipGetLastError());
-    DEN_HIP_OK(hipEventRecord(e1, qs));
-    DEN_HIP_OK(hipStreamSynchronize(qs));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(e1, qs));
+    HIP_OK(hipStreamSynchronize(qs));
     float ms = 0.f;
-    DEN_HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
     st.scan_ms += ms;
     t0 = std::chrono::steady_clock::now();
-    DEN_HIP_OK(hipMemcpy(h_depth.data(), d_depth, static_cast<size_t>(on) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    DEN_HIP_OK(hipMemcpy(h_wiggle.data(), d_wiggle, static_cast<size_t>(on) * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(h_depth.data(), d_depth, static_cast<size_t>(on) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(h_wiggle.data(), d_wiggle, static_cast<size_t>(on) * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t j = 0; j < members.size(); j++) {
       const int32_t i = t.index[j];
       std::memcpy(depth + out_off[i], h_depth.data() + out[j], static_cast<size_t>(len[j]) * sizeof(int32_t));

@@ -33,6 +33,11 @@
 // normaliser lgamma(h0 + h1) - lgamma(h0) - lgamma(h1), not a joint score with an assignment.  The returned assignment is
 // one per-read reassignment from the LAST sample's psi, drawn as algorithm = MARGINAL draws its one (kernels_marginal.hip:
 // Gibbs words of chain 0, MISO_ITER_INIT).
+//
+// WHERE THE PIECES LIVE.  The device functions of steps 1 - 4, the sample's uniform and the chain records of a mode without
+// a chain: exact_posterior.hpp (the paired-end mode, kernels_exact_paired.hip, uses them too).  The host driver's stream,
+// buffers and HIP_OK: hip_host.hpp.  Here: the two kernels, the driver of the posterior stage and the check of its
+// probabilities (exact_check_prob, which the paired driver calls as well).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +50,7 @@
 #include "miso_philox.h"
 
 #include "exact_posterior.hpp"
+#include "hip_host.hpp"
 
 namespace miso {
 
@@ -67,11 +73,7 @@ __global__ __launch_bounds__(64) void exact_sample(const KernelArgs a, const dou
   double *samples = reinterpret_cast<double *>(a.out_pool + E.off_samples);
   double *loglik = reinterpret_cast<double *>(a.out_pool + E.off_loglik);
   const uint32_t k0 = static_cast<uint32_t>(a.seed), k1 = static_cast<uint32_t>(a.seed >> 32);
-  auto sample = [&](int s) {
-    const miso_u32x4 w = miso_philox4x32(static_cast<uint32_t>(s), 0u, MISO_SITE_EXACT, event_id, k0, k1);
-    const double u = (static_cast<double>(w.v[0]) + 0.5) * (1.0 / 4294967296.0);
-    return exact_at(st, exact_invert(T, u * T.Z));
-  };
+  auto sample = [&](int s) { return exact_at(st, exact_invert(T, exact_uniform(s, event_id, k0, k1) * T.Z)); };
   for (int s = lane; s < S; s += 64) {   // consecutive lanes, consecutive rows of the K x S column-major sample matrix
     const ExactAt r = sample(s);
     reinterpret_cast<double2 *>(samples)[s] = make_double2(r.x, r.y);   // one 16-byte store per row (the pool's offsets are multiples of 16)
@@ -87,13 +89,7 @@ __global__ __launch_bounds__(64) void exact_sample(const KernelArgs a, const dou
       drawass[rd] = rnd < r.x ? 0 : 1;
     }
   }
-  // no chain ran: every sample counts as accepted, dealt over the chains' records so that they add up to S
-  ChainStats *cs = reinterpret_cast<ChainStats *>(a.out_pool + E.off_stats);
-  for (int c = lane; c < a.C; c += 64) {
-    cs[c].counts_hash = 0;
-    cs[c].accepted = (S + a.C - 1 - c) / a.C;
-    cs[c].hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-  }
+  exact_chain_stats(reinterpret_cast<ChainStats *>(a.out_pool + E.off_stats), a.C, S, lane);
 }
 
 // the posterior stage alone (miso_selftest_exact; the summaries of miso_batch_get_exact_summary)
@@ -117,38 +113,26 @@ __global__ __launch_bounds__(64) void exact_probe(const double *stats7, int n, c
   }
 }
 
-#define HIP_OK(call)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
+// the probabilities at which a posterior stage inverts its CDF
+void exact_check_prob(const double *prob, int n_prob) {
+  for (int j = 0; j < n_prob; j++) if (!(prob[j] > 0.0 && prob[j] < 1.0)) MISO_FAIL(MISO_EINVAL, "A probability must lie inside (0, 1)");
+}
 
 // (st: the stream to work on -- a batch's own; null: one of this call's, so that no other stream of the process waits)
 void exact_probe_run(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device");
   if (n < 0 || n_prob < 0) MISO_FAIL(MISO_EINVAL, "Negative element or probability count");
-  for (int j = 0; j < n_prob; j++) if (!(prob[j] > 0.0 && prob[j] < 1.0)) MISO_FAIL(MISO_EINVAL, "A probability must lie inside (0, 1)");
+  exact_check_prob(prob, n_prob);
   if (n == 0) return;
-  struct Held {   // freed on every way out, a failed call's included
-    double *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t own = nullptr;
-    ~Held() { for (double *q : p) if (q) (void) hipFree(q); if (own) (void) hipStreamDestroy(own); }
-  } held;
-  if (!st) { HIP_OK(hipStreamCreateWithFlags(&held.own, hipStreamNonBlocking)); st = held.own; }
-  double *&d_st = held.p[0], *&d_p = held.p[1], *&d_o = held.p[2], *&d_q = held.p[3];
-  const size_t nq = static_cast<size_t>(n) * std::max(n_prob, 1) * 2;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_st), static_cast<size_t>(n) * 7 * 8));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_p), std::max(n_prob, 1) * 8));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_o), static_cast<size_t>(n) * 8 * 8));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_q), nq * 8));
-  HIP_OK(hipMemcpyAsync(d_st, stats7, static_cast<size_t>(n) * 7 * 8, hipMemcpyHostToDevice, st));
-  if (n_prob) HIP_OK(hipMemcpyAsync(d_p, prob, static_cast<size_t>(n_prob) * 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(exact_probe, dim3(n), dim3(64), 0, st, d_st, n, d_p, n_prob, d_o, d_q);
+  HipCall call(st);
+  const size_t sb = static_cast<size_t>(n) * 7 * 8, ob = static_cast<size_t>(n) * 8 * 8, qb = static_cast<size_t>(n) * n_prob * 2 * 8;
+  const double *d_st = call.upload(stats7, sb), *d_p = call.upload(prob, static_cast<size_t>(n_prob) * 8);
+  double *d_o = call.alloc(ob), *d_q = call.alloc(qb);
+  hipLaunchKernelGGL(exact_probe, dim3(n), dim3(64), 0, call.st, d_st, n, d_p, n_prob, d_o, d_q);
   HIP_OK(hipGetLastError());
-  if (out8) HIP_OK(hipMemcpyAsync(out8, d_o, static_cast<size_t>(n) * 8 * 8, hipMemcpyDeviceToHost, st));
-  if (icdf && n_prob) HIP_OK(hipMemcpyAsync(icdf, d_q, static_cast<size_t>(n) * n_prob * 2 * 8, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
+  if (out8) HIP_OK(hipMemcpyAsync(out8, d_o, ob, hipMemcpyDeviceToHost, call.st));
+  if (icdf && n_prob) HIP_OK(hipMemcpyAsync(icdf, d_q, qb, hipMemcpyDeviceToHost, call.st));
+  HIP_OK(hipStreamSynchronize(call.st));
 }
 
 }  // namespace miso

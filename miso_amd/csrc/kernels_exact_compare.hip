@@ -22,10 +22,14 @@
 // posterior (Z12, gmax12), table of B, which stays for the n_z quadratures.  f64, no contraction, miso_det_exp /
 // miso_det_log, IEEE division; tests/_exact_compare_ref.py restates it operation by operation and the two agree bit for bit
 // (tests/test_gpu_exact_compare.py).
+//
+// WHERE THE PIECES LIVE.  What this comparison and the paired-end one (kernels_exact_paired_compare.hip) do alike -- B's CDF
+// at an argument, the lane-order sum, the verdict o[0 .. 4], the end of a quadrature, the host's prior term and check of z --
+// is exact_compare.hpp; the tables are exact_posterior.hpp's; the driver's stream, buffers and events hip_host.hpp's.  Here:
+// the order of the three tables, the quadrature loop (unrolled over z, A's f made again from scalars) and the driver.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -35,46 +39,10 @@
 #include "miso_amd.h"
 #include "miso_detmath.h"
 
-#include "exact_posterior.hpp"
+#include "exact_compare.hpp"
+#include "hip_host.hpp"
 
 namespace miso {
-
-constexpr int EXACT_MAX_Z = 8;
-constexpr double EXACT_BF_CAP = 1e12;
-constexpr double EXACT_LN10 = 2.302585092994046;
-
-// the tabulated, unnormalised CDF at psi = u; v = 1 - psi, computed on its own
-__device__ __forceinline__ double exact_cdf_at(const ExactTable &T, double u, double v) {
-  const bool uin = u > 0.0, vin = v > 0.0;
-  const double t = miso_det_log(uin ? u : 1.0) - miso_det_log(vin ? v : 1.0);
-  double s = (t - T.tL) / T.h;
-  s = s > 0.0 ? s : 0.0;
-  s = s < static_cast<double>(EXACT_G) ? s : static_cast<double>(EXACT_G);
-  int j = static_cast<int>(s);
-  j = j < EXACT_G - 1 ? j : EXACT_G - 1;   // 0 .. G - 1
-  const double fr = s - static_cast<double>(j);
-  const double F0 = T.F[exact_idx(j)], F1 = T.F[exact_idx(j + 1)];
-  const double m0 = T.h * T.f[exact_idx(j)], m1 = T.h * T.f[exact_idx(j + 1)];
-  const double dF = F1 - F0;
-  const double c2 = (3.0 * dF - 2.0 * m0) - m1, c3 = (m0 + m1) - 2.0 * dF;
-  double val = F0 + (m0 + fr * (c2 + fr * c3)) * fr;
-  val = val > T.Z ? T.Z : val;
-  val = val < 0.0 ? 0.0 : val;
-  val = t >= T.tR ? T.Z : val;
-  val = uin ? val : 0.0;
-  val = vin ? val : T.Z;
-  return val;
-}
-
-// the 64 lanes' values added in lane order (red: 64 doubles of LDS)
-__device__ __forceinline__ double exact_lanes_sum(double v, double *red, int lane) {
-  red[lane] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int m = 0; m < 64; m++) s = s + red[m];
-  __syncthreads();
-  return s;
-}
 
 // One workgroup = one wavefront = one pair.  stats7_i: {n10, n01, n, e0, e1, h0, h1} of sample i; out: 5 + n_z doubles per pair
 __global__ __launch_bounds__(64) void exact_compare(const double *stats7_1, const double *stats7_2, const double *log_prior0, int n,
@@ -98,17 +66,9 @@ __global__ __launch_bounds__(64) void exact_compare(const double *stats7_1, cons
   const ExactTable T12 = exact_tabulate(st12, F, f, red, lane);
   __syncthreads();
   const ExactTable TB = exact_table(stB, a2 ? W1 : W2, F, f, red, lane);
-  const double lzA = TA.gmax + miso_det_log(TA.Z), lzB = TB.gmax + miso_det_log(TB.Z), lz12 = T12.gmax + miso_det_log(T12.Z);
-  const double lz1 = a2 ? lzB : lzA, lz2 = a2 ? lzA : lzB;
-  const double log_d0 = (lz12 - lz1) - lz2;
-  const double log_bf = log_prior0[i] - log_d0;
-  double bf = miso_det_exp(log_bf);
-  bf = bf > EXACT_BF_CAP ? EXACT_BF_CAP : bf;
+  const ExactVerdict V = exact_verdict(TA, TB, T12, a2, log_prior0 + i);
   double *o = out + static_cast<size_t>(5 + n_z) * static_cast<size_t>(i);
-  if (lane == 0) {
-    o[0] = a2 ? TB.mean0 : TA.mean0; o[1] = a2 ? TA.mean0 : TB.mean0;
-    o[2] = log_d0; o[3] = bf; o[4] = log_bf / EXACT_LN10;
-  }
+  if (lane == 0) exact_verdict_store(V, TA, TB, a2, o);
   if (n_z <= 0) return;
   // the quadratures on A's grid, all n_z of them from one evaluation of A's points
   double acc[EXACT_MAX_Z];
@@ -131,26 +91,8 @@ __global__ __launch_bounds__(64) void exact_compare(const double *stats7_1, cons
   }
 #pragma unroll
   for (int k = 0; k < EXACT_MAX_Z; k++) {
-    if (k < n_z) {
-      const double s = exact_lanes_sum(acc[k], red, lane) / TA.sf;
-      if (lane == 0) o[5 + k] = a2 ? s : 1.0 - s;
-    }
+    if (k < n_z) exact_delta_cdf(acc[k], TA, a2, red, lane, o + 5 + k);
   }
-}
-
-#define HIP_OK(call)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
-// log of the prior density of psi_1 - psi_2 at 0: the Beta normalisers of the pooled hyperparameters over the two samples'
-static double exact_log_prior0(const double *q1, const double *q2) {
-  const double h0p = (q1[5] + q2[5]) - 1.0, h1p = (q1[6] + q2[6]) - 1.0;
-  double lp = (std::lgamma(h0p) + std::lgamma(h1p)) - std::lgamma(h0p + h1p);
-  for (const double *q : {q1, q2}) lp = lp - ((std::lgamma(q[5]) + std::lgamma(q[6])) - std::lgamma(q[5] + q[6]));
-  return lp;
 }
 
 // (st: the stream to work on -- a batch's own; null: one of this call's.  ms, may be null: the kernel's HIP-event time)
@@ -158,8 +100,7 @@ void exact_compare_run(const double *stats7_1, const double *stats7_2, int n, co
                        float *ms) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device");
   if (n < 0) MISO_FAIL(MISO_EINVAL, "Negative pair count");
-  if (n_z < 0 || n_z > EXACT_MAX_Z) MISO_FAIL(MISO_EINVAL, "The number of delta psi points must lie in [0, 8]");
-  for (int j = 0; j < n_z; j++) if (!(z[j] > -1.0 && z[j] < 1.0)) MISO_FAIL(MISO_EINVAL, "A delta psi point must lie inside (-1, 1)");
+  exact_check_z(z, n_z);
   std::vector<double> lp(std::max(n, 1));
   for (int i = 0; i < n; i++) {
     const double *q1 = stats7_1 + 7 * static_cast<size_t>(i), *q2 = stats7_2 + 7 * static_cast<size_t>(i);
@@ -167,42 +108,22 @@ void exact_compare_run(const double *stats7_1, const double *stats7_2, int n, co
       MISO_FAIL(MISO_EINVAL, "The effective lengths of a pair to compare differ between its samples");
     if (!exact_eligible(false, 2, q1 + 3, q1 + 5) || !exact_eligible(false, 2, q2 + 3, q2 + 5))
       MISO_FAIL(MISO_EINVAL, "A pair to compare is not eligible for the exact-posterior mode");
-    lp[i] = exact_log_prior0(q1, q2);
+    lp[i] = exact_log_prior0(q1 + 5, q2 + 5);
   }
   if (ms) *ms = 0.f;
   if (n == 0) return;
-  struct Held {   // freed on every way out, a failed call's included
-    double *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t own = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held() {
-      for (double *q : p) if (q) (void) hipFree(q);
-      if (e0) (void) hipEventDestroy(e0);
-      if (e1) (void) hipEventDestroy(e1);
-      if (own) (void) hipStreamDestroy(own);
-    }
-  } held;
-  if (!st) { HIP_OK(hipStreamCreateWithFlags(&held.own, hipStreamNonBlocking)); st = held.own; }
-  double *&d_1 = held.p[0], *&d_2 = held.p[1], *&d_lp = held.p[2], *&d_z = held.p[3], *&d_o = held.p[4];
+  HipCall call(st);
   const size_t sb = static_cast<size_t>(n) * 7 * 8, ob = static_cast<size_t>(n) * (5 + n_z) * 8;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_1), sb));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_2), sb));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_lp), static_cast<size_t>(n) * 8));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_z), EXACT_MAX_Z * 8));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_o), ob));
-  HIP_OK(hipMemcpyAsync(d_1, stats7_1, sb, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_2, stats7_2, sb, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_lp, lp.data(), static_cast<size_t>(n) * 8, hipMemcpyHostToDevice, st));
-  if (n_z) HIP_OK(hipMemcpyAsync(d_z, z, static_cast<size_t>(n_z) * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipEventCreate(&held.e0));
-  HIP_OK(hipEventCreate(&held.e1));
-  HIP_OK(hipEventRecord(held.e0, st));
-  hipLaunchKernelGGL(exact_compare, dim3(n), dim3(64), 0, st, d_1, d_2, d_lp, n, d_z, n_z, d_o);
+  const double *d_1 = call.upload(stats7_1, sb), *d_2 = call.upload(stats7_2, sb);
+  const double *d_lp = call.upload(lp.data(), static_cast<size_t>(n) * 8), *d_z = call.upload(z, static_cast<size_t>(n_z) * 8);
+  double *d_o = call.alloc(ob);
+  call.start();
+  hipLaunchKernelGGL(exact_compare, dim3(n), dim3(64), 0, call.st, d_1, d_2, d_lp, n, d_z, n_z, d_o);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(held.e1, st));
-  HIP_OK(hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (ms) HIP_OK(hipEventElapsedTime(ms, held.e0, held.e1));
+  call.stop();
+  HIP_OK(hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, call.st));
+  HIP_OK(hipStreamSynchronize(call.st));
+  if (ms) *ms = call.elapsed_ms();
 }
 
 }  // namespace miso

@@ -37,6 +37,12 @@
 // with the Dirichlet normaliser (P evaluated at the sample: the pairs are walked once per 512 rows); the assignment is one
 // reassignment of the pairs from the last row's psi by the paired pick rule, on the words of the paired sampler's initial
 // reassignment of chain 0.
+//
+// WHERE THE PIECES LIVE.  Steps P, 1, 2, the workgroup's LDS layout, c8 and the loader of a caller-given element:
+// exact_paired.hpp (kernels_exact_paired_compare.hip tabulates with them too).  Step 3, the sample's uniform and the chain
+// records of a mode without a chain: exact_posterior.hpp, shared with the single-end mode.  The host driver's stream, buffers
+// and HIP_OK: hip_host.hpp.  Here: the two kernels, the driver of the posterior stage and the check of caller-given elements
+// (exact_paired_check, which the comparison's driver calls as well).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,25 +56,17 @@
 #include "miso_philox.h"
 
 #include "exact_paired.hpp"
+#include "hip_host.hpp"
 
 namespace miso {
-
-struct ExactPairedLds {
-  double F[EXACT_PAD], f[EXACT_PAD], red[256], mbuf[2 * EXP_CHUNK], fext[2];
-  int redi[128];
-};
 
 __device__ __forceinline__ ExactTable exact_paired_tabulate(const ExactStats &st, double c8, const ExactPairs &pr, ExactPairedLds &L, int lane) {
   const ExactTable W = exact_paired_window(st, c8, pr, L.mbuf, L.red, L.redi, lane);
   return exact_paired_table(st, W, pr, L.mbuf, L.F, L.f, L.fext, L.red, lane);
 }
 
-// (n + h0 + h1) / 32 from the packed hyper - 1
-__device__ __forceinline__ double exact_paired_c8(double n, double hm0, double hm1) {
-  return (n + ((hm0 + 1.0) + (hm1 + 1.0))) * 0.03125;
-}
-
-// the event of slot `slot` of the launch's list: its statistics and pairs
+// the event of slot `slot` of the launch's list: its statistics from the batch's pool (integer counts, the packed hyper - 1)
+// and its pairs
 __device__ __forceinline__ void exact_paired_event(const KernelArgs &a, const double *A2, int slot, const DevEvent &E, ExactStats &st,
                                                    double &c8, ExactPairs &pr) {
   const double *consts = reinterpret_cast<const double *>(a.in_pool + E.off_consts);
@@ -77,8 +75,7 @@ __device__ __forceinline__ void exact_paired_event(const KernelArgs &a, const do
   const double n = static_cast<double>(n10 + n01 + E.n_draw);
   st = exact_stats(static_cast<double>(n10), static_cast<double>(n01), n, A2[2 * slot], A2[2 * slot + 1], consts[4], consts[5]);
   c8 = exact_paired_c8(n, consts[4], consts[5]);
-  pr.rec = reinterpret_cast<const uint32_t *>(a.in_pool + E.off_draw);   // plain records: u16 f0, f1 per pair
-  pr.fp = a.frag_prob; pr.il = a.il; pr.mm = nullptr; pr.n = E.n_draw;
+  pr = exact_pairs_resident(a.in_pool, E, a.frag_prob, a.il);
 }
 
 // One workgroup = one wavefront = one event of the launch's list.  A2: A0, A1 per event of the list.
@@ -98,11 +95,7 @@ __global__ __launch_bounds__(64) void exact_paired_sample(const KernelArgs a, co
   double *samples = reinterpret_cast<double *>(a.out_pool + E.off_samples);
   double *loglik = reinterpret_cast<double *>(a.out_pool + E.off_loglik);
   const uint32_t k0 = static_cast<uint32_t>(a.seed), k1 = static_cast<uint32_t>(a.seed >> 32);
-  auto sample = [&](int s) {
-    const miso_u32x4 w = miso_philox4x32(static_cast<uint32_t>(s), 0u, MISO_SITE_EXACT, event_id, k0, k1);
-    const double u = (static_cast<double>(w.v[0]) + 0.5) * (1.0 / 4294967296.0);
-    return exact_at(st, exact_invert(T, u * T.Z));
-  };
+  auto sample = [&](int s) { return exact_at(st, exact_invert(T, exact_uniform(s, event_id, k0, k1) * T.Z)); };
   // rows [s0, s0 + 512) per sweep over the pairs: lane l the rows s0 + l + 64 j
   for (int s0 = 0; s0 < S; s0 += 64 * EXP_ROW_PTS) {
     double x[EXP_ROW_PTS], y[EXP_ROW_PTS], base_ll[EXP_ROW_PTS], nld[EXP_ROW_PTS], P[EXP_ROW_PTS];
@@ -138,13 +131,7 @@ __global__ __launch_bounds__(64) void exact_paired_sample(const KernelArgs a, co
       drawass[rd] = miso_u01(word) * Tt < c0 ? 0 : 1;
     }
   }
-  // no chain ran: every sample counts as accepted, dealt over the chains' records so that they add up to S
-  ChainStats *cs = reinterpret_cast<ChainStats *>(a.out_pool + E.off_stats);
-  for (int c = lane; c < a.C; c += 64) {
-    cs[c].counts_hash = 0;
-    cs[c].accepted = (S + a.C - 1 - c) / a.C;
-    cs[c].hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-  }
+  exact_chain_stats(reinterpret_cast<ChainStats *>(a.out_pool + E.off_stats), a.C, S, lane);
 }
 
 // The posterior stage alone.  mm == null: element i is event i of the launch's list (the summaries of
@@ -157,16 +144,8 @@ __global__ __launch_bounds__(64) void exact_paired_probe(const KernelArgs a, con
   const int i = blockIdx.x;
   if (i >= n) return;
   ExactStats st; double c8; ExactPairs pr;
-  if (mm) {
-    const double *q = stats6 + 6 * static_cast<size_t>(i);
-    const int nd = static_cast<int>(offs[i + 1] - offs[i]);
-    const double nn = (q[0] + q[1]) + static_cast<double>(nd);
-    st = exact_stats(q[0], q[1], nn, q[2], q[3], q[4] - 1.0, q[5] - 1.0);
-    c8 = exact_paired_c8(nn, q[4] - 1.0, q[5] - 1.0);
-    pr.rec = nullptr; pr.fp = nullptr; pr.il = 0; pr.mm = mm + 2 * static_cast<size_t>(offs[i]); pr.n = nd;
-  } else {
-    exact_paired_event(a, A2, i, a.events[a.slot_event[i]], st, c8, pr);
-  }
+  if (mm) exact_paired_element(stats6, mm, offs, nullptr, nullptr, nullptr, nullptr, 0, i, st, c8, pr);
+  else exact_paired_event(a, A2, i, a.events[a.slot_event[i]], st, c8, pr);
   const ExactTable T = exact_paired_tabulate(st, c8, pr, L, lane);
   if (lane == 0) {
     double *o = out8 + 8 * static_cast<size_t>(i);
@@ -180,12 +159,23 @@ __global__ __launch_bounds__(64) void exact_paired_probe(const KernelArgs a, con
   }
 }
 
-#define HIP_OK(call)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
+// n elements as a paired driver takes them from its caller: every row of stats6 eligible; with caller-given pairs (offs !=
+// null: m, offs as miso_selftest_exact_paired's) offsets that start at 0 and ascend, probabilities in [2^-63, 1].  Returns the
+// number of caller-given pairs.
+int64_t exact_paired_check(const double *stats6, const double *m, const int64_t *offs, int n) {
+  for (int i = 0; i < n; i++) {
+    const double *q = stats6 + 6 * static_cast<size_t>(i);
+    if (!(q[0] >= 0 && q[1] >= 0) || !exact_paired_eligible(2, q + 2, q + 4, false))
+      MISO_FAIL(MISO_EINVAL, "An element is not eligible for the paired exact mode");
+  }
+  if (!offs || n <= 0) return 0;
+  if (offs[0] != 0) MISO_FAIL(MISO_EINVAL, "The pair offsets must start at 0");
+  for (int i = 0; i < n; i++)
+    if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] > INT32_MAX) MISO_FAIL(MISO_EINVAL, "The pair offsets must ascend");
+  for (int64_t r = 0; r < 2 * offs[n]; r++)
+    if (!(m[r] >= EXACT_PAIRED_MIN_PROB && m[r] <= 1.0)) MISO_FAIL(MISO_EINVAL, "A pair probability outside [2^-63, 1]");
+  return offs[n];
+}
 
 const void *exact_paired_sample_fn() { return reinterpret_cast<const void *>(&exact_paired_sample); }
 
@@ -194,49 +184,26 @@ void exact_paired_probe_run(const KernelArgs *ka, const double *A2, const double
                             int n, const double *prob, int n_prob, double *out8, double *icdf, hipStream_t st) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device");
   if (n < 0 || n_prob < 0) MISO_FAIL(MISO_EINVAL, "Negative element or probability count");
-  for (int j = 0; j < n_prob; j++) if (!(prob[j] > 0.0 && prob[j] < 1.0)) MISO_FAIL(MISO_EINVAL, "A probability must lie inside (0, 1)");
-  int64_t n_pairs = 0;
-  if (!ka && n > 0) {
-    if (offs[0] != 0) MISO_FAIL(MISO_EINVAL, "The pair offsets must start at 0");
-    for (int i = 0; i < n; i++) {
-      if (offs[i + 1] < offs[i] || offs[i + 1] - offs[i] > INT32_MAX) MISO_FAIL(MISO_EINVAL, "The pair offsets must ascend");
-      const double *q = stats6 + 6 * static_cast<size_t>(i);
-      const double A[2] = {q[2], q[3]}, h[2] = {q[4], q[5]};
-      if (!(q[0] >= 0 && q[1] >= 0) || !exact_paired_eligible(2, A, h, false)) MISO_FAIL(MISO_EINVAL, "An element is not eligible for the paired exact mode");
-    }
-    n_pairs = offs[n];
-    for (int64_t r = 0; r < 2 * n_pairs; r++)
-      if (!(m[r] >= EXACT_PAIRED_MIN_PROB && m[r] <= 1.0)) MISO_FAIL(MISO_EINVAL, "A pair probability outside [2^-63, 1]");
-  }
+  exact_check_prob(prob, n_prob);
+  const int64_t n_pairs = ka ? 0 : exact_paired_check(stats6, m, offs, n);
   if (n == 0) return;
-  struct Held {   // freed on every way out, a failed call's included
-    void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t own = nullptr;
-    ~Held() { for (void *q : p) if (q) (void) hipFree(q); if (own) (void) hipStreamDestroy(own); }
-  } held;
-  if (!st) { HIP_OK(hipStreamCreateWithFlags(&held.own, hipStreamNonBlocking)); st = held.own; }
-  double *d_st = nullptr, *d_m = nullptr, *d_p = nullptr, *d_o = nullptr, *d_q = nullptr;
-  int64_t *d_off = nullptr;
-  auto alloc = [&](int slot, size_t bytes) { HIP_OK(hipMalloc(&held.p[slot], std::max<size_t>(bytes, 16))); return held.p[slot]; };
-  const size_t np = static_cast<size_t>(std::max(n_prob, 1));
-  d_p = static_cast<double *>(alloc(0, np * 8));
-  d_o = static_cast<double *>(alloc(1, static_cast<size_t>(n) * 8 * 8));
-  d_q = static_cast<double *>(alloc(2, static_cast<size_t>(n) * np * 2 * 8));
+  HipCall call(st);
+  const size_t ob = static_cast<size_t>(n) * 8 * 8, qb = static_cast<size_t>(n) * n_prob * 2 * 8;
+  const double *d_p = call.upload(prob, static_cast<size_t>(n_prob) * 8);
+  double *d_o = call.alloc(ob), *d_q = call.alloc(qb);
+  const double *d_st = nullptr, *d_m = nullptr;
+  const int64_t *d_off = nullptr;
   if (!ka) {
-    d_st = static_cast<double *>(alloc(3, static_cast<size_t>(n) * 6 * 8));
-    d_m = static_cast<double *>(alloc(4, static_cast<size_t>(n_pairs) * 2 * 8));
-    d_off = static_cast<int64_t *>(alloc(5, static_cast<size_t>(n + 1) * 8));
-    HIP_OK(hipMemcpyAsync(d_st, stats6, static_cast<size_t>(n) * 6 * 8, hipMemcpyHostToDevice, st));
-    if (n_pairs) HIP_OK(hipMemcpyAsync(d_m, m, static_cast<size_t>(n_pairs) * 2 * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_off, offs, static_cast<size_t>(n + 1) * 8, hipMemcpyHostToDevice, st));
+    d_st = call.upload(stats6, static_cast<size_t>(n) * 6 * 8);
+    d_m = call.upload(m, static_cast<size_t>(n_pairs) * 2 * 8);   // (no pair at all: still a buffer, the kernel tells the routes by it)
+    d_off = call.upload(offs, static_cast<size_t>(n + 1) * 8);
   }
-  if (n_prob) HIP_OK(hipMemcpyAsync(d_p, prob, static_cast<size_t>(n_prob) * 8, hipMemcpyHostToDevice, st));
   KernelArgs none{};
-  hipLaunchKernelGGL(exact_paired_probe, dim3(n), dim3(64), 0, st, ka ? *ka : none, A2, d_st, d_m, d_off, n, d_p, n_prob, d_o, d_q);
+  hipLaunchKernelGGL(exact_paired_probe, dim3(n), dim3(64), 0, call.st, ka ? *ka : none, A2, d_st, d_m, d_off, n, d_p, n_prob, d_o, d_q);
   HIP_OK(hipGetLastError());
-  if (out8) HIP_OK(hipMemcpyAsync(out8, d_o, static_cast<size_t>(n) * 8 * 8, hipMemcpyDeviceToHost, st));
-  if (icdf && n_prob) HIP_OK(hipMemcpyAsync(icdf, d_q, static_cast<size_t>(n) * n_prob * 2 * 8, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
+  if (out8) HIP_OK(hipMemcpyAsync(out8, d_o, ob, hipMemcpyDeviceToHost, call.st));
+  if (icdf && n_prob) HIP_OK(hipMemcpyAsync(icdf, d_q, qb, hipMemcpyDeviceToHost, call.st));
+  HIP_OK(hipStreamSynchronize(call.st));
 }
 
 }  // namespace miso

@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip_host.hpp"
 #include "host.hpp"
 #include "miso_alnio.h"
 
@@ -113,17 +114,6 @@ __global__ __launch_bounds__(kBlock) void insert_pair_kernel(const int4 *in, int
   }
 }
 
-#define INS_HIP_OK(call)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 template <class F> void parallel_for(int64_t n, int T, F &&body) {
   T = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(T, n / 65536 + 1)));
   std::vector<std::thread> th;
@@ -138,19 +128,19 @@ struct DeviceScratch {
   std::vector<hipStream_t> streams;
   template <class T> T *alloc(size_t count) {
     void *p = nullptr;
-    INS_HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+    HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
     dev.push_back(p);
     return static_cast<T *>(p);
   }
   template <class T> T *host(size_t count) {
     void *p = nullptr;
-    INS_HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    HIP_OK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
     pinned.push_back(p);
     return static_cast<T *>(p);
   }
   hipStream_t stream() {
     hipStream_t s = nullptr;
-    INS_HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     streams.push_back(s);
     return s;
   }
@@ -223,12 +213,12 @@ void insert_tag_records(const miso_alnfile_t *f, int device, int filter, int n_i
   int64_t *d_off = s.alloc<int64_t>(iv.ref_off.size()), *d_max = s.alloc<int64_t>(iv.maxlen.size());
   int64_t *d_s0 = s.alloc<int64_t>(iv.s0.size()), *d_e = s.alloc<int64_t>(iv.e.size());
   int32_t *d_idx = s.alloc<int32_t>(iv.idx.size());
-  INS_HIP_OK(hipMemcpy(d_off, iv.ref_off.data(), iv.ref_off.size() * 8, hipMemcpyHostToDevice));
-  INS_HIP_OK(hipMemcpy(d_max, iv.maxlen.data(), iv.maxlen.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d_off, iv.ref_off.data(), iv.ref_off.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(d_max, iv.maxlen.data(), iv.maxlen.size() * 8, hipMemcpyHostToDevice));
   if (!iv.s0.empty()) {
-    INS_HIP_OK(hipMemcpy(d_s0, iv.s0.data(), iv.s0.size() * 8, hipMemcpyHostToDevice));
-    INS_HIP_OK(hipMemcpy(d_e, iv.e.data(), iv.e.size() * 8, hipMemcpyHostToDevice));
-    INS_HIP_OK(hipMemcpy(d_idx, iv.idx.data(), iv.idx.size() * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_s0, iv.s0.data(), iv.s0.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_e, iv.e.data(), iv.e.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_idx, iv.idx.data(), iv.idx.size() * 4, hipMemcpyHostToDevice));
   }
   const int64_t slot_n = std::min<int64_t>(C, std::max<int64_t>(N, 1));
   struct Slot { int32_t *h_in, *h_codes, *d_in, *d_codes; hipStream_t st; int64_t first, n; bool busy; };
@@ -240,7 +230,7 @@ void insert_tag_records(const miso_alnfile_t *f, int device, int filter, int n_i
   }
   const int T = std::min(miso_usable_threads(), 16);
   auto drain = [&](Slot &q) {
-    INS_HIP_OK(hipStreamSynchronize(q.st));
+    HIP_OK(hipStreamSynchronize(q.st));
     std::memcpy(codes + q.first, q.h_codes, static_cast<size_t>(q.n) * 4);
     q.busy = false;
   };
@@ -263,14 +253,14 @@ void insert_tag_records(const miso_alnfile_t *f, int device, int filter, int n_i
       }
     });
     for (int p = 0; p < 4; p++)
-      INS_HIP_OK(hipMemcpyAsync(q.d_in + p * slot_n, q.h_in + p * slot_n, static_cast<size_t>(q.n) * 4,
+      HIP_OK(hipMemcpyAsync(q.d_in + p * slot_n, q.h_in + p * slot_n, static_cast<size_t>(q.n) * 4,
                                 hipMemcpyHostToDevice, q.st));
     const int n = static_cast<int>(q.n);
     insert_record_kernel<<<dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, q.st>>>(
         q.d_in, q.d_in + slot_n, q.d_in + 2 * slot_n, q.d_in + 3 * slot_n, n, d_off, d_max, nref, d_s0, d_e, d_idx,
         filter ? 1 : 0, q.d_codes);
-    INS_HIP_OK(hipGetLastError());
-    INS_HIP_OK(hipMemcpyAsync(q.h_codes, q.d_codes, static_cast<size_t>(q.n) * 4, hipMemcpyDeviceToHost, q.st));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(q.h_codes, q.d_codes, static_cast<size_t>(q.n) * 4, hipMemcpyDeviceToHost, q.st));
     q.busy = true;
   }
   for (int k = 0; k < 2; k++) {
@@ -331,19 +321,19 @@ void insert_len(const miso_alnfile_t *f, int device, int filter, int n_iv, const
     int32_t *d_res = s.alloc<int32_t>(cn);
     unsigned long long *d_iv = s.alloc<unsigned long long>(per_iv.size()), *d_reasons = s.alloc<unsigned long long>(4);
     hipStream_t st_ = s.stream();
-    INS_HIP_OK(hipMemsetAsync(d_iv, 0, per_iv.size() * 8, st_));
-    INS_HIP_OK(hipMemsetAsync(d_reasons, 0, 4 * 8, st_));
+    HIP_OK(hipMemsetAsync(d_iv, 0, per_iv.size() * 8, st_));
+    HIP_OK(hipMemsetAsync(d_reasons, 0, 4 * 8, st_));
     for (int64_t first = 0; first < P; first += C) {
       const int n = static_cast<int>(std::min(C, P - first));
-      INS_HIP_OK(hipMemcpyAsync(d_in, in.data() + first, static_cast<size_t>(n) * sizeof(int4), hipMemcpyHostToDevice, st_));
+      HIP_OK(hipMemcpyAsync(d_in, in.data() + first, static_cast<size_t>(n) * sizeof(int4), hipMemcpyHostToDevice, st_));
       insert_pair_kernel<<<dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_>>>(
           d_in, n, d_res, d_iv, d_reasons);
-      INS_HIP_OK(hipGetLastError());
-      INS_HIP_OK(hipMemcpyAsync(result.data() + first, d_res, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st_));
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(result.data() + first, d_res, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st_));
     }
-    INS_HIP_OK(hipMemcpyAsync(per_iv.data(), d_iv, per_iv.size() * 8, hipMemcpyDeviceToHost, st_));
-    INS_HIP_OK(hipMemcpyAsync(reasons.data(), d_reasons, 4 * 8, hipMemcpyDeviceToHost, st_));
-    INS_HIP_OK(hipStreamSynchronize(st_));
+    HIP_OK(hipMemcpyAsync(per_iv.data(), d_iv, per_iv.size() * 8, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipMemcpyAsync(reasons.data(), d_reasons, 4 * 8, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
   }
   st.kept = static_cast<int64_t>(reasons[KEPT]);
   st.same_strand = static_cast<int64_t>(reasons[SAME_STRAND]);

@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "hip_host.hpp"
 #include "host.hpp"
 #include "text_digits.hpp"
 
@@ -257,13 +258,6 @@ __global__ void __launch_bounds__(256) selftest_binomial_kernel(uint64_t seed, u
   if (t / G < count && sub == 0) out[i] = y;
 }
 
-#define ST_HIP_OK(call)                                                                    \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
 namespace {
 
 // device copies of host arrays for one launch, freed on every way out
@@ -272,19 +266,19 @@ struct StBuffers {
   ~StBuffers() { for (void *p : ptrs) (void) hipFree(p); }
   template <class T> T *in(const T *host, size_t count) {
     T *d = out<T>(count);
-    if (count) ST_HIP_OK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    if (count) HIP_OK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
     return d;
   }
   template <class T> T *out(size_t count) {
     void *d = nullptr;
-    ST_HIP_OK(hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(T)));
+    HIP_OK(hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(T)));
     ptrs.push_back(d);
     return static_cast<T *>(d);
   }
   template <class T> void back(T *host, const T *dev, size_t count) {
-    ST_HIP_OK(hipGetLastError());
-    ST_HIP_OK(hipDeviceSynchronize());
-    if (count) ST_HIP_OK(hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    if (count) HIP_OK(hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost));
   }
 };
 

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "hip_host.hpp"
 
 extern "C" int miso_usable_threads(void);   // alnio.cpp
 
@@ -239,17 +240,6 @@ __global__ __launch_bounds__(kBlock) void text_decode_kernel(const unsigned char
   if (bad) atomicOr(status + w.e, bad);
 }
 
-#define TXT_HIP_OK(call)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // body(lo, hi) over [0, n) on up to T threads, at least `grain` items each
 template <class F> void parallel_for(int64_t n, int T, int64_t grain, F &&body) {
   T = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(T, n / grain + 1)));
@@ -266,25 +256,25 @@ struct Scratch {
   std::vector<hipEvent_t> events;
   void *alloc(size_t bytes) {
     void *p = nullptr;
-    TXT_HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+    HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
     dev.push_back(p);
     return p;
   }
   void *host(size_t bytes) {
     void *p = nullptr;
-    TXT_HIP_OK(hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault));
+    HIP_OK(hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault));
     pinned.push_back(p);
     return p;
   }
   hipStream_t stream() {
     hipStream_t s = nullptr;
-    TXT_HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     streams.push_back(s);
     return s;
   }
   hipEvent_t event() {
     hipEvent_t e = nullptr;
-    TXT_HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventCreate(&e));
     events.push_back(e);
     return e;
   }
@@ -368,10 +358,10 @@ void miso_batch::adopt_text(int n, const unsigned char *text, const int64_t *off
   Scratch s;
   int32_t *d_status = static_cast<int32_t *>(s.alloc(static_cast<size_t>(n) * 4));
   int64_t *d_offsets = static_cast<int64_t *>(s.alloc((static_cast<size_t>(n) + 1) * 8));
-  TXT_HIP_OK(hipMemcpy(d_offsets, offsets, (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice));
-  TXT_HIP_OK(hipMemset(d_status, 0, std::max<size_t>(static_cast<size_t>(n) * 4, 16)));
-  TXT_HIP_OK(hipMemset(d_out, 0, out_bytes));     // (the padding between regions, and what an undecoded event leaves)
-  TXT_HIP_OK(hipStreamSynchronize(nullptr));      // (the chunk streams do not wait for the null stream)
+  HIP_OK(hipMemcpy(d_offsets, offsets, (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(d_status, 0, std::max<size_t>(static_cast<size_t>(n) * 4, 16)));
+  HIP_OK(hipMemset(d_out, 0, out_bytes));     // (the padding between regions, and what an undecoded event leaves)
+  HIP_OK(hipStreamSynchronize(nullptr));      // (the chunk streams do not wait for the null stream)
 
   // a slot: the chunk's text, the first tile of each of its events, the rows per tile (then: before each tile)
   struct Slot { unsigned char *h, *d; int32_t *h_first, *d_first, *d_rows; hipStream_t st; hipEvent_t e0, ek, e1; bool busy; };
@@ -387,11 +377,11 @@ void miso_batch::adopt_text(int n, const unsigned char *text, const int64_t *off
     q.st = s.stream(); q.e0 = s.event(); q.ek = s.event(); q.e1 = s.event(); q.busy = false;
   }
   auto drain = [&](Slot &q) {
-    TXT_HIP_OK(hipStreamSynchronize(q.st));
+    HIP_OK(hipStreamSynchronize(q.st));
     float ms = 0.f;
-    TXT_HIP_OK(hipEventElapsedTime(&ms, q.ek, q.e1));
+    HIP_OK(hipEventElapsedTime(&ms, q.ek, q.e1));
     st.kernel_ms += ms;
-    TXT_HIP_OK(hipEventElapsedTime(&ms, q.e0, q.e1));
+    HIP_OK(hipEventElapsedTime(&ms, q.e0, q.e1));
     st.decode_ms += ms;
     q.busy = false;
   };
@@ -410,25 +400,25 @@ void miso_batch::adopt_text(int n, const unsigned char *text, const int64_t *off
     for (int i = 0; i < nc; i++)
       q.h_first[i + 1] = q.h_first[i] + static_cast<int32_t>(tiles_of(e0 + i, offsets[e0 + i] - base));
     const unsigned tiles = static_cast<unsigned>(q.h_first[nc]);
-    TXT_HIP_OK(hipEventRecord(q.e0, q.st));
-    TXT_HIP_OK(hipMemcpyAsync(q.d, q.h, static_cast<size_t>(bytes + kPad), hipMemcpyHostToDevice, q.st));
-    TXT_HIP_OK(hipMemcpyAsync(q.d_first, q.h_first, (static_cast<size_t>(nc) + 1) * 4, hipMemcpyHostToDevice, q.st));
-    TXT_HIP_OK(hipEventRecord(q.ek, q.st));
+    HIP_OK(hipEventRecord(q.e0, q.st));
+    HIP_OK(hipMemcpyAsync(q.d, q.h, static_cast<size_t>(bytes + kPad), hipMemcpyHostToDevice, q.st));
+    HIP_OK(hipMemcpyAsync(q.d_first, q.h_first, (static_cast<size_t>(nc) + 1) * 4, hipMemcpyHostToDevice, q.st));
+    HIP_OK(hipEventRecord(q.ek, q.st));
     text_count_kernel<<<dim3(tiles), dim3(kBlock), 0, q.st>>>(q.d, d_offsets, base, e0, nc, q.d_first, q.d_rows);
-    TXT_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     text_scan_kernel<<<dim3(static_cast<unsigned>((nc + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, q.st>>>(
         nc, q.d_first, q.d_rows);
-    TXT_HIP_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     text_decode_kernel<<<dim3(tiles), dim3(kBlock), 0, q.st>>>(q.d, d_offsets, base, e0, nc, q.d_first, q.d_rows, d_events,
                                                               d_out, Sn, d_status);
-    TXT_HIP_OK(hipGetLastError());
-    TXT_HIP_OK(hipEventRecord(q.e1, q.st));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(q.e1, q.st));
     q.busy = true;
     st.text_bytes += bytes;
   }
   for (size_t i = 0; i < n_slots; i++)
     if (slot[i].busy) drain(slot[i]);
-  if (n) TXT_HIP_OK(hipMemcpy(status, d_status, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost));
+  if (n) HIP_OK(hipMemcpy(status, d_status, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++) {
     if (status[i] == 0) { st.decoded++; st.sample_bytes += int64_t{8} * Sn * K[i]; }
     else st.not_decoded++;

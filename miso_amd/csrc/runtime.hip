@@ -18,6 +18,8 @@
 #include "batch.hpp"
 #include "compare_column.hpp"
 #include "coop.hpp"
+#include "exact_compare.hpp"
+#include "hip_host.hpp"
 #include "miso_binomial.h"
 
 namespace miso {
@@ -49,13 +51,6 @@ __global__ void sampler_grp_all(const KernelArgs a);   // kernels_grp_all.hip
 template <int KC, int KS, bool UNI> __global__ void sampler_flat(const KernelArgs a);   // KS: the launch's largest isoform count at compile time (0: at run time)
 __global__ void selftest_detmath_kernel(const double *, int, double *, double *, double *, double *);
 __global__ void selftest_philox_kernel(const uint32_t *, int, uint32_t *);
-
-#define HIP_OK(call)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      MISO_FAIL(MISO_ENODEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-  } while (0)
 
 // ---- the shader clock a launch ran at (miso_batch_set_clock_probe; bench.py's roofline prices its VALU peak with it) ----
 // ONE wavefront beside the sampler kernels, on a stream of its own: it sleeps, looks at a flag the batch's stream sets
@@ -2412,86 +2407,80 @@ void miso_batch::compare(miso_batch &other, double smoothing) {
   compared = true;
 }
 
-// The exact comparison of this batch (sample 1) with `other` (sample 2): the pairs both batches' exact mode took, with
-// bit-equal effective lengths, go to exact_compare (kernels_exact_compare.hip); every other pair is marked not comparable.
-void miso_batch::compare_exact(miso_batch &other, const double *z, int n_z) {
-  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
-  if (events.size() != other.events.size() || S() != other.S())
+// What the two exact comparisons of batch a (sample 1) with batch b (sample 2) share: the guards, the list of the events both
+// batches' exact mode took and that are `comparable`, their rows of `row_w` statistics from `gather`, the call of `run` (which
+// validates z, and fails with MISO_ENODEVICE without a device, also when no event is comparable), and the scatter of its rows
+// into a's h_exact_cmp / exact_cmp_ok; every other event is marked not comparable.
+template <class Comparable, class Gather, class Run>
+static void compare_exact_with(miso_batch &a, miso_batch &b, const double *z, int n_z, bool mode_ok, const char *mode_msg, int row_w,
+                               Comparable comparable, Gather gather, Run run, const char *kernel) {
+  if (!a.launched || !b.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (a.device != b.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
+  if (a.events.size() != b.events.size() || a.S() != b.S())
     MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
-  if (!exact || !other.exact || slots_exact != exact || other.slots_exact != other.exact)
-    MISO_FAIL(MISO_EINVAL, "Both batches to compare exactly must have run with the exact-posterior mode");
-  if (n_z < 0 || n_z > 8) MISO_FAIL(MISO_EINVAL, "The number of delta psi points must lie in [0, 8]");
-  const int n = static_cast<int>(events.size());
+  if (!mode_ok) MISO_FAIL(MISO_EINVAL, mode_msg);
+  exact_check_z(z, n_z);
+  const int n = static_cast<int>(a.events.size());
   for (int i = 0; i < n; i++)
-    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
-  std::vector<int> list;
+    if (a.events[i].K != b.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+  std::vector<int32_t> list;
   std::vector<double> s1, s2;
-  exact_cmp_ok.assign(n, 0);
+  a.exact_cmp_ok.assign(n, 0);
   for (int i = 0; i < n; i++) {
-    if (!event_exact(i) || !other.event_exact(i)) continue;
-    if (std::memcmp(events[i].eff.data(), other.events[i].eff.data(), 2 * sizeof(double)) != 0) continue;
+    if (!a.event_exact(i) || !b.event_exact(i) || !comparable(i)) continue;
     list.push_back(i);
-    s1.resize(s1.size() + 7); s2.resize(s2.size() + 7);
-    exact_stats7(i, &s1[s1.size() - 7]); other.exact_stats7(i, &s2[s2.size() - 7]);
+    s1.resize(s1.size() + row_w); s2.resize(s2.size() + row_w);
+    gather(a, i, &s1[s1.size() - row_w]); gather(b, i, &s2[s2.size() - row_w]);
   }
   const size_t w = 5 + static_cast<size_t>(n_z);
   std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
-  HIP_OK(hipSetDevice(device));
-  HIP_OK(hipStreamSynchronize(other.stream));
-  // (validates z, and fails with MISO_ENODEVICE without a device, also when no pair is comparable)
-  exact_compare_run(s1.data(), s2.data(), static_cast<int>(list.size()), z, n_z, got.data(), stream, &exact_compare_ms);
-  h_exact_cmp.assign(static_cast<size_t>(n) * w, 0.0);
+  HIP_OK(hipSetDevice(a.device));
+  HIP_OK(hipStreamSynchronize(b.stream));
+  run(s1.data(), s2.data(), list, got.data());
+  a.h_exact_cmp.assign(static_cast<size_t>(n) * w, 0.0);
   for (size_t j = 0; j < list.size(); j++) {
-    std::memcpy(&h_exact_cmp[list[j] * w], &got[j * w], w * sizeof(double));
-    exact_cmp_ok[list[j]] = 1;
+    std::memcpy(&a.h_exact_cmp[list[j] * w], &got[j * w], w * sizeof(double));
+    a.exact_cmp_ok[list[j]] = 1;
   }
-  exact_cmp_nz = n_z;
-  if (!list.empty()) note_kernel("exact_compare");
-  exact_compared = true;
+  a.exact_cmp_nz = n_z;
+  if (!list.empty()) a.note_kernel(kernel);
+  a.exact_compared = true;
+}
+
+// The exact comparison of this batch (sample 1) with `other` (sample 2): the pairs both batches' exact mode took, with
+// bit-equal effective lengths, go to exact_compare (kernels_exact_compare.hip).
+void miso_batch::compare_exact(miso_batch &other, const double *z, int n_z) {
+  compare_exact_with(
+      *this, other, z, n_z, exact && other.exact && slots_exact == exact && other.slots_exact == other.exact,
+      "Both batches to compare exactly must have run with the exact-posterior mode", 7,
+      [&](int i) { return std::memcmp(events[i].eff.data(), other.events[i].eff.data(), 2 * sizeof(double)) == 0; },
+      [](const miso_batch &b, int i, double *row) { b.exact_stats7(i, row); },
+      [&](const double *s1, const double *s2, const std::vector<int32_t> &list, double *got) {
+        exact_compare_run(s1, s2, static_cast<int>(list.size()), z, n_z, got, stream, &exact_compare_ms);
+      },
+      "exact_compare");
 }
 
 // The exact comparison of two paired-end batches (this one is sample 1): the events both batches' paired exact mode took go
-// to exact_paired_compare (kernels_exact_paired_compare.hip), which reads both batches' resident pair records; every other
-// event is marked not comparable.  The results take compare_exact's place (h_exact_cmp, read by the same getter).
+// to exact_paired_compare (kernels_exact_paired_compare.hip), which reads both batches' resident pair records.  The results
+// take compare_exact's place (h_exact_cmp, read by the same getter).
 void miso_batch::compare_exact_paired(miso_batch &other, const double *z, int n_z) {
-  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
-  if (events.size() != other.events.size() || S() != other.S())
-    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
-  if (!p.paired || !other.p.paired || !exact_paired || !other.exact_paired || slots_exact != exact_paired || other.slots_exact != other.exact_paired)
-    MISO_FAIL(MISO_EINVAL, "Both batches to compare exactly must be paired-end and have run with the paired exact-posterior mode");
-  if (n_z < 0 || n_z > 8) MISO_FAIL(MISO_EINVAL, "The number of delta psi points must lie in [0, 8]");
-  const int n = static_cast<int>(events.size());
-  for (int i = 0; i < n; i++)
-    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
-  std::vector<int32_t> list;
-  std::vector<double> s1, s2;
-  exact_cmp_ok.assign(n, 0);
-  auto stats6 = [](const PackedEvent &e, std::vector<double> &s) {
-    s.insert(s.end(), {static_cast<double>(e.base_count[0]), static_cast<double>(e.base_count[1]), e.eff[0], e.eff[1], e.hyper[0], e.hyper[1]});
-  };
-  for (int i = 0; i < n; i++) {
-    if (!event_exact(i) || !other.event_exact(i)) continue;
-    list.push_back(i);
-    stats6(events[i], s1); stats6(other.events[i], s2);
-  }
-  const size_t w = 5 + static_cast<size_t>(n_z);
-  std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
-  HIP_OK(hipSetDevice(device));
-  HIP_OK(hipStreamSynchronize(other.stream));
-  const ExactPairedCmpInput in1{s1.data(), nullptr, nullptr, d_events, d_in, d_fp, static_cast<int>(fd.prob.size())};
-  const ExactPairedCmpInput in2{s2.data(), nullptr, nullptr, other.d_events, other.d_in, other.d_fp, static_cast<int>(other.fd.prob.size())};
-  // (validates z, and fails with MISO_ENODEVICE without a device, also when no event is comparable)
-  exact_paired_compare_run(in1, in2, list.data(), static_cast<int>(list.size()), z, n_z, got.data(), stream, &exact_compare_ms);
-  h_exact_cmp.assign(static_cast<size_t>(n) * w, 0.0);
-  for (size_t j = 0; j < list.size(); j++) {
-    std::memcpy(&h_exact_cmp[list[j] * w], &got[j * w], w * sizeof(double));
-    exact_cmp_ok[list[j]] = 1;
-  }
-  exact_cmp_nz = n_z;
-  if (!list.empty()) note_kernel("exact_paired_compare");
-  exact_compared = true;
+  compare_exact_with(
+      *this, other, z, n_z,
+      p.paired && other.p.paired && exact_paired && other.exact_paired && slots_exact == exact_paired && other.slots_exact == other.exact_paired,
+      "Both batches to compare exactly must be paired-end and have run with the paired exact-posterior mode", 6,
+      [](int) { return true; },
+      [](const miso_batch &b, int i, double *row) {
+        const PackedEvent &e = b.events[i];
+        const double r[6] = {static_cast<double>(e.base_count[0]), static_cast<double>(e.base_count[1]), e.eff[0], e.eff[1], e.hyper[0], e.hyper[1]};
+        std::memcpy(row, r, sizeof r);
+      },
+      [&](const double *s1, const double *s2, const std::vector<int32_t> &list, double *got) {
+        const ExactPairedCmpInput in1{s1, nullptr, nullptr, d_events, d_in, d_fp, static_cast<int>(fd.prob.size())};
+        const ExactPairedCmpInput in2{s2, nullptr, nullptr, other.d_events, other.d_in, other.d_fp, static_cast<int>(other.fd.prob.size())};
+        exact_paired_compare_run(in1, in2, list.data(), static_cast<int>(list.size()), z, n_z, got, stream, &exact_compare_ms);
+      },
+      "exact_paired_compare");
 }
 
 // A batch that holds posterior samples produced elsewhere -- parsed `.miso` files (summarize_miso / compare_miso

@@ -83,6 +83,27 @@ def test_one_thousand_pairs_bit_exact(post):
     _check(post, [(big, small)], [0.1])
 
 
+def test_second_launch_slice_bit_equal():
+    """The driver launches in slices of 8192 pairs; a slice after the first indexes its rows of A's f by the workgroup and
+    its outputs by first + workgroup.  8192 + 3 elements, the case list's small elements (at most 40 drawing pairs) under
+    both hyperparameter settings tiled, one z so that the row buffer is used: every row equals, bit for bit, the row of
+    the same element in a call on the distinct elements alone (which test_case_list_bit_exact holds against the
+    restatement)."""
+    distinct = [(paired_stats(s1, h), paired_stats(s2, h)) for h in HYPERS for _, s1, s2 in cases()
+                if max(len(s1[4]), len(s2[4])) <= 40]
+    assert len(distinct) == 18 and 8192 % len(distinct) != 0     # the second slice starts inside the tiling
+
+    def run(pairs):
+        return capi.selftest_exact_paired_compare([stats6(a) for a, _ in pairs], [a.m for a, _ in pairs],
+                                                  [stats6(b) for _, b in pairs], [b.m for _, b in pairs], [0.05])
+    want = run(distinct)
+    n = 8192 + 3
+    got = run([distinct[j % len(distinct)] for j in range(n)])
+    assert got.shape == (n, 6)
+    assert np.array_equal(got, want[np.arange(n) % len(distinct)])
+    assert len({row.tobytes() for row in want}) == len(distinct)  # (no two elements share a row: a misplaced one shows)
+
+
 # ---- whole batches ----
 
 class Problem:
