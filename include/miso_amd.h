@@ -562,6 +562,24 @@ int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const doub
 /* kernels_k2.inl binomial_coop<G>, G = 1, 2, 4, 8 lanes per chain: `count` draws of Binomial(n, p) from the word streams
    (seed, event_id, chain 0, iteration i, MISO_SITE_COUNTS), i = 0 .. count - 1 */
 int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
+/* The law that miso_binomial.h's draws follow, by enumeration of the 32-bit words they are functions of, with the header's own
+   miso_binomial_btrs / miso_binomial_inversion compiled for the device (tests/test_gpu_binomial_law.py).  Every stride-th
+   first word U from stride / 2 (stride: a power of two): BTRS -- the number of second words V that trial 0 accepts (an
+   initial segment, its end by 32 steps of bisection) is added to bin k(U); inversion -- 1 is added to bin x(U).  r = min(p,
+   1 - p) and the routine are chosen as miso_binomial chooses them, so the bins are r's.  n: 1 .. 2^24, 0 < p < 1; hist:
+   n + 1 entries; info: MISO_SELFTEST_LAW_INFO_N entries; kernel_ms (may be NULL): the kernel's time by HIP events. */
+enum { MISO_SELFTEST_LAW_REGIME = 0,        /* MISO_SELFTEST_LAW_INVERSION / _BTRS */
+       MISO_SELFTEST_LAW_ENUMERATED,        /* words U enumerated: 2^32 / stride */
+       MISO_SELFTEST_LAW_TOTAL,             /* the sum of hist */
+       MISO_SELFTEST_LAW_RESTARTS,          /* inversion: words whose search ran past its bound (their x is another word's) */
+       MISO_SELFTEST_LAW_OUT_OF_RANGE,      /* BTRS: words whose k is outside 0 .. n (no V accepts) */
+       MISO_SELFTEST_LAW_NOT_MONOTONE,      /* enumerated words whose k is below the k of the word before */
+       MISO_SELFTEST_LAW_SEGMENT_CHECKED,   /* BTRS: words (one in 2^8) whose accepted V were probed around and away from V* */
+       MISO_SELFTEST_LAW_SEGMENT_BAD_NEAR,  /*   probes at V* - 2 .. V* + 3 that contradict "accepted = [0, V*]" */
+       MISO_SELFTEST_LAW_SEGMENT_BAD_FAR,   /*   the 16 + 16 probes spread over either side that do */
+       MISO_SELFTEST_LAW_INFO_N };
+enum { MISO_SELFTEST_LAW_INVERSION = 0, MISO_SELFTEST_LAW_BTRS = 1 };
+int miso_selftest_binomial_law(int32_t n, double p, uint32_t stride, uint64_t *hist, uint64_t *info, float *kernel_ms);
 /* kernels_exact.hip, the posterior stage alone, one wavefront per element: stats7[7 i ...] = {n10, n01, n, e0, e1, h0, h1}
    (n = all reads with a compatible isoform).  out8[8 i ...] = {mean of x, mean of 1 - x, window low, window high (logit
    space), the normalising sum F[G], the mode (logit space), the grid step, the log density at the mode as tabulated};

@@ -833,6 +833,21 @@ def selftest_binomial(G, n, p, count, seed=1, event_id=0):
     return out
 
 
+SELFTEST_LAW_INFO = ("regime", "enumerated", "total", "restarts", "out_of_range", "not_monotone", "segment_checked",
+                     "segment_bad_near", "segment_bad_far")
+SELFTEST_LAW_INVERSION, SELFTEST_LAW_BTRS = range(2)
+
+
+def selftest_binomial_law(n, p, stride):
+    """The law of include/miso_binomial.h's draws by enumeration of their 32-bit words on the device (include/miso_amd.h
+    miso_selftest_binomial_law): (hist[n + 1] uint64 in terms of r = min(p, 1 - p), info as a dict of ints, kernel ms)"""
+    hist = np.zeros(int(n) + 1, np.uint64)
+    info = np.zeros(len(SELFTEST_LAW_INFO), np.uint64)
+    ms = C.c_float(0.0)
+    check(lib().miso_selftest_binomial_law(C.c_int32(n), C.c_double(p), C.c_uint32(stride), _p(hist), _p(info), C.byref(ms)))
+    return hist, {k: int(v) for k, v in zip(SELFTEST_LAW_INFO, info)}, float(ms.value)
+
+
 def selftest_exact(stats7, probs):
     """csrc/kernels_exact.hip, the posterior stage alone: stats7[i] = (n10, n01, n, e0, e1, h0, h1) -> (out8 [n, 8] = mean of x,
     mean of 1 - x, window low / high, normalising sum, mode, grid step, log density at the mode; icdf [n, len(probs), 2] =

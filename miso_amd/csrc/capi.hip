@@ -1157,6 +1157,13 @@ int miso_selftest_pe_pick(int K, const uint8_t *f, const double *psi, const doub
 int miso_selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out) {
   return guarded([&] { selftest_binomial(G, seed, event_id, n, p, count, out); });
 }
+int miso_selftest_binomial_law(int32_t n, double p, uint32_t stride, uint64_t *hist, uint64_t *info, float *kernel_ms) {
+  return guarded([&] {
+    need(hist, "hist");
+    need(info, "info");
+    selftest_binomial_law(n, p, stride, hist, info, kernel_ms);
+  });
+}
 int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_prob, double *out8, double *icdf) {
   return guarded([&] {
     if (n > 0) need(stats7, "stats7");

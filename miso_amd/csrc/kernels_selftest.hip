@@ -258,6 +258,124 @@ __global__ void __launch_bounds__(256) selftest_binomial_kernel(uint64_t seed, u
   if (t / G < count && sub == 0) out[i] = y;
 }
 
+// ---- the law of miso_binomial.h's draws by enumeration of the 32-bit words they are functions of (miso_selftest_binomial_law) ----
+namespace {
+
+// a stream whose `next` is 1 takes its next words from w1, w2, w3 without a Philox block: ONE trial of the header's own routines
+// (a trial past the given words goes on with Philox words of stream (0, 0, 0, 0); its result is not used)
+__device__ __forceinline__ void law_stream(miso_ustream *s, uint32_t U, uint32_t V) {
+  miso_ustream_init(s, 0, 0, 0, 0, MISO_SITE_COUNTS);
+  s->next = 1; s->w1 = U; s->w2 = V;
+}
+// trial 0 of miso_binomial_btrs on the words (U, V): its k, acc = trial 0 accepted
+__device__ __forceinline__ int32_t law_btrs_trial(int32_t n, double r, const double *lf, uint32_t U, uint32_t V, bool &acc) {
+  miso_ustream s;
+  law_stream(&s, U, V);
+  const int32_t k = miso_binomial_btrs(&s, n, r, lf);
+  acc = s.next == 3;
+  return k;
+}
+// miso_binomial_inversion on the word U: its x, or -1 where the search ran past its bound and took another word
+__device__ __forceinline__ int32_t law_inversion_word(int32_t n, double r, uint32_t U, int32_t &x_any) {
+  miso_ustream s;
+  law_stream(&s, U, 0);
+  x_any = miso_binomial_inversion(&s, n, r);
+  return s.next == 2 ? x_any : -1;
+}
+// One word U of BTRS: count = #{V : trial 0 accepts (U, V)}, returns the trial's k, or -1 with count = 0 when k is outside
+// 0 .. n (V = 0 passes every acceptance test, so it is refused only there).  The accepted V are taken to be [0, V*], V* by 32
+// steps of bisection on the routine itself; check: the segment probed at V* - 2 .. V* + 3 (bad_near counts the words that
+// disagree) and at 16 further V spread over either side (bad_far).
+__device__ __forceinline__ int32_t law_btrs_word(int32_t n, double r, const double *lf, uint32_t U, bool check, uint64_t &count,
+                                                 uint32_t &bad_near, uint32_t &bad_far) {
+  bool acc;
+  const int32_t k = law_btrs_trial(n, r, lf, U, 0u, acc);
+  count = 0;
+  if (!acc) return -1;
+  uint64_t lo = 0, hi = 1ull << 32;
+  for (int step = 0; step < 32; step++) {
+    const uint64_t mid = (lo + hi) >> 1;
+    law_btrs_trial(n, r, lf, U, static_cast<uint32_t>(mid), acc);
+    if (acc) lo = mid; else hi = mid;
+  }
+  count = lo + 1;
+  if (check) {
+    for (int d = -2; d <= 3; d++) {
+      const int64_t v = static_cast<int64_t>(lo) + d;
+      if (v < 0 || v > 0xFFFFFFFFll) continue;
+      law_btrs_trial(n, r, lf, U, static_cast<uint32_t>(v), acc);
+      if (acc != (d <= 0)) bad_near++;
+    }
+    for (int j = 1; j <= 16; j++) {
+      const uint64_t below = lo * static_cast<uint64_t>(j) / 17, above = lo + 1 + (0xFFFFFFFFull - lo) * static_cast<uint64_t>(j) / 16;
+      law_btrs_trial(n, r, lf, U, static_cast<uint32_t>(below), acc);
+      if (!acc) bad_far++;
+      if (above <= 0xFFFFFFFFull) {
+        law_btrs_trial(n, r, lf, U, static_cast<uint32_t>(above), acc);
+        if (acc) bad_far++;
+      }
+    }
+  }
+  return k;
+}
+
+}  // namespace
+
+// Thread t takes the enumerated words run t .. run t + run - 1 (word i is U = stride / 2 + i stride).  k(U) does not decrease, so a
+// thread's bin changes rarely: counted in registers, added to hist (n + 1 entries) when k changes and at the end.  info:
+// MISO_SELFTEST_LAW_* sums (regime and enumerated are the host's).  Bounded: the run, 32 bisection steps and 38 probes per
+// word, the header's own trial caps.
+__global__ void __launch_bounds__(256) selftest_binomial_law_kernel(int32_t n, double r, int btrs, uint32_t stride, uint64_t enumerated,
+                                                                    uint32_t run, const double *lf, unsigned long long *hist,
+                                                                    unsigned long long *info) {
+  const uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const uint64_t i0 = t * run;
+  if (i0 >= enumerated) return;
+  const uint64_t i1 = min(i0 + run, enumerated);
+  auto word = [&](uint64_t i) { return static_cast<uint32_t>(stride / 2 + i * stride); };
+  int32_t prev = -1, any;
+  if (i0 > 0) {   // the k of the word before this run, for the order check
+    bool acc;
+    if (btrs) { prev = law_btrs_trial(n, r, lf, word(i0 - 1), 0u, acc); if (!acc) prev = -1; }
+    else prev = law_inversion_word(n, r, word(i0 - 1), any);
+  }
+  int32_t bin = -1;
+  uint64_t in_bin = 0, total = 0;
+  uint32_t restarts = 0, out_of_range = 0, not_monotone = 0, checked = 0, bad_near = 0, bad_far = 0;
+  auto flush = [&]() { if (bin >= 0 && bin <= n && in_bin != 0) atomicAdd(&hist[bin], static_cast<unsigned long long>(in_bin)); };
+  for (uint64_t i = i0; i < i1; i++) {
+    uint64_t count = 1;
+    int32_t x;
+    if (btrs) {
+      const bool check = (i & 255) == 128;
+      x = law_btrs_word(n, r, lf, word(i), check, count, bad_near, bad_far);
+      if (check && x >= 0) checked++;
+      if (x < 0) out_of_range++;
+    } else {
+      x = law_inversion_word(n, r, word(i), any);
+      if (x < 0) {   // a Philox word's x: counted, and told in info
+        restarts++; total++; count = 0;
+        if (any >= 0 && any <= n) atomicAdd(&hist[any], 1ull);
+      }
+    }
+    if (x >= 0) {
+      if (x != bin) { flush(); bin = x; in_bin = 0; }
+      in_bin += count;
+    }
+    total += count;
+    if (prev >= 0 && x >= 0 && x < prev) not_monotone++;
+    prev = x;
+  }
+  flush();
+  if (total) atomicAdd(&info[MISO_SELFTEST_LAW_TOTAL], static_cast<unsigned long long>(total));
+  if (restarts) atomicAdd(&info[MISO_SELFTEST_LAW_RESTARTS], static_cast<unsigned long long>(restarts));
+  if (out_of_range) atomicAdd(&info[MISO_SELFTEST_LAW_OUT_OF_RANGE], static_cast<unsigned long long>(out_of_range));
+  if (not_monotone) atomicAdd(&info[MISO_SELFTEST_LAW_NOT_MONOTONE], static_cast<unsigned long long>(not_monotone));
+  if (checked) atomicAdd(&info[MISO_SELFTEST_LAW_SEGMENT_CHECKED], static_cast<unsigned long long>(checked));
+  if (bad_near) atomicAdd(&info[MISO_SELFTEST_LAW_SEGMENT_BAD_NEAR], static_cast<unsigned long long>(bad_near));
+  if (bad_far) atomicAdd(&info[MISO_SELFTEST_LAW_SEGMENT_BAD_FAR], static_cast<unsigned long long>(bad_far));
+}
+
 namespace {
 
 // device copies of host arrays for one launch, freed on every way out
@@ -440,6 +558,38 @@ void selftest_binomial(int G, uint64_t seed, uint32_t event_id, int32_t n, doubl
   default: hipLaunchKernelGGL(selftest_binomial_kernel<8>, grid, dim3(256), 0, 0, seed, event_id, n, p, count, dlf, dout); break;
   }
   b.back(out, dout, static_cast<size_t>(count));
+}
+
+void selftest_binomial_law(int32_t n, double p, uint32_t stride, uint64_t *hist, uint64_t *info, float *kernel_ms) {
+  if (n < 1 || n > (1 << 24)) MISO_FAIL(MISO_EINVAL, "n: 1 .. 2^24");
+  if (!(p > 0.0) || p >= 1.0) MISO_FAIL(MISO_EINVAL, "p: inside (0, 1)");
+  if (stride == 0 || (stride & (stride - 1)) != 0) MISO_FAIL(MISO_EINVAL, "stride: a power of two");
+  st_need_device(0);
+  const double r = p > 0.5 ? 1.0 - p : p;                     // as miso_binomial reduces p and chooses the routine
+  const bool btrs = !(static_cast<double>(n) * r < 10.0);
+  const uint64_t enumerated = (1ull << 32) / stride;
+  // a run per thread: 2^18 threads where the words allow it, at most 4096 words each
+  const uint32_t run = static_cast<uint32_t>(std::min<uint64_t>(4096, std::max<uint64_t>(1, enumerated >> 18)));
+  const uint64_t threads = (enumerated + run - 1) / run;
+  std::vector<double> lf(static_cast<size_t>(n) + 2);
+  miso_logfact_fill(lf.data(), static_cast<int32_t>(lf.size()));   // as miso_batch::upload builds the batch's table
+  std::vector<uint64_t> zero(static_cast<size_t>(n) + 1, 0), info0(MISO_SELFTEST_LAW_INFO_N, 0);
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit atomics");
+  HipCall c(nullptr);
+  const double *dlf = c.upload(lf.data(), lf.size() * sizeof(double));
+  unsigned long long *dhist = c.upload(reinterpret_cast<const unsigned long long *>(zero.data()), zero.size() * sizeof(uint64_t));
+  unsigned long long *dinfo = c.upload(reinterpret_cast<const unsigned long long *>(info0.data()), info0.size() * sizeof(uint64_t));
+  c.start();
+  hipLaunchKernelGGL(selftest_binomial_law_kernel, st_grid(threads), dim3(256), 0, c.st, n, r, btrs ? 1 : 0, stride, enumerated, run, dlf,
+                     dhist, dinfo);
+  c.stop();
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(hist, dhist, zero.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c.st));
+  HIP_OK(hipMemcpyAsync(info, dinfo, info0.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c.st));
+  HIP_OK(hipStreamSynchronize(c.st));
+  info[MISO_SELFTEST_LAW_REGIME] = btrs ? MISO_SELFTEST_LAW_BTRS : MISO_SELFTEST_LAW_INVERSION;
+  info[MISO_SELFTEST_LAW_ENUMERATED] = enumerated;
+  if (kernel_ms) *kernel_ms = c.elapsed_ms();
 }
 
 }  // namespace miso

@@ -176,6 +176,117 @@ void orc_binomial(uint64_t seed, uint32_t event_id, int32_t n, double p, int cou
 }
 /* test hook: the first n entries of the log-factorial table (log 0! .. log (n-1)!) as miso_logfact_fill builds it */
 void orc_logfact(int n, double *out) { miso_logfact_fill(out, n); }
+
+/* ---- the law that miso_binomial's draws follow, by enumeration of the 32-bit words they are functions of ----
+   A miso_ustream whose `next` is 1 takes its next words from w1, w2, w3 without a Philox block: that reaches ONE trial of
+   the header's own routines.  A trial past the given words goes on with Philox words of stream (0, 0, 0, 0): its result is
+   not used. */
+static void law_stream(miso_ustream *s, uint32_t U, uint32_t V) {
+  miso_ustream_init(s, 0, 0, 0, 0, MISO_SITE_COUNTS);
+  s->next = 1; s->w1 = U; s->w2 = V;
+}
+/* trial 0 of miso_binomial_btrs on the words (U, V): its k, *acc = 1 iff trial 0 accepted */
+static int32_t law_btrs_trial(int32_t n, double r, const double *lf, uint32_t U, uint32_t V, int *acc) {
+  miso_ustream s;
+  int32_t k;
+  law_stream(&s, U, V);
+  k = miso_binomial_btrs(&s, n, r, lf);
+  *acc = s.next == 3;
+  return k;
+}
+/* miso_binomial_inversion on the word U: its x, *restarted = 1 iff the search ran past its bound and took another word */
+static int32_t law_inversion_word(int32_t n, double r, uint32_t U, int *restarted) {
+  miso_ustream s;
+  int32_t x;
+  law_stream(&s, U, 0);
+  x = miso_binomial_inversion(&s, n, r);
+  *restarted = s.next != 2;
+  return x;
+}
+/* One word U of BTRS: *count = #{V : trial 0 accepts (U, V)}, returns the trial's k, or -1 with *count = 0 when k is out
+   of range (V = 0 passes every acceptance test, so it is refused only there).  The accepted V are taken to be an initial
+   segment [0, V*] (squeeze: v <= vr; exact test: log(v const) <= rhs), V* found by 32 steps of bisection on the routine
+   itself.  check != 0: the segment is probed at V* - 2 .. V* + 3 (bad[0] counts the words that disagree) and at 16 further V
+   spread over either side (bad[1]). */
+static int32_t law_btrs_word(int32_t n, double r, const double *lf, uint32_t U, int check, uint64_t *count, uint64_t *bad) {
+  uint64_t lo = 0, hi = (uint64_t) 1 << 32;
+  int acc, step, d, j;
+  const int32_t k = law_btrs_trial(n, r, lf, U, 0, &acc);
+  *count = 0;
+  if (!acc) return -1;
+  for (step = 0; step < 32; step++) {
+    const uint64_t mid = (lo + hi) >> 1;
+    law_btrs_trial(n, r, lf, U, (uint32_t) mid, &acc);
+    if (acc) lo = mid; else hi = mid;
+  }
+  *count = lo + 1;
+  if (check) {
+    for (d = -2; d <= 3; d++) {
+      const int64_t v = (int64_t) lo + d;
+      if (v < 0 || v > (int64_t) 0xFFFFFFFFu) continue;
+      law_btrs_trial(n, r, lf, U, (uint32_t) v, &acc);
+      if (acc != (d <= 0)) bad[0]++;
+    }
+    for (j = 1; j <= 16; j++) {
+      const uint64_t below = lo * (uint64_t) j / 17, above = lo + 1 + (0xFFFFFFFFu - lo) * (uint64_t) j / 16;
+      law_btrs_trial(n, r, lf, U, (uint32_t) below, &acc);
+      if (!acc) bad[1]++;
+      if (above <= 0xFFFFFFFFu) {
+        law_btrs_trial(n, r, lf, U, (uint32_t) above, &acc);
+        if (acc) bad[1]++;
+      }
+    }
+  }
+  return k;
+}
+
+/* test hook: hist[k] = the number of word pairs (U, V) (BTRS) or words U (inversion) on which Binomial(n, r) draws k, over
+   U = stride / 2, stride / 2 + stride, ... < 2^32 (stride: a power of two); r = min(p, 1 - p) and the regime as miso_binomial
+   forms them, so the bins are r's (the caller reflects them for p > 1/2).  hist: n + 1 entries; info: ORC_LAW_INFO_N
+   entries (miso_oracle.h).  ORC_EINVAL unless n >= 1, 0 < p < 1 and stride is a power of two. */
+int orc_binomial_law(int32_t n, double p, uint32_t stride, uint64_t *hist, uint64_t *info) {
+  double r;
+  const double *lf;
+  uint64_t i, enumerated, bad[2] = { 0, 0 };
+  int32_t prev = -1;
+  int btrs, k;
+  if (n <= 0 || !(p > 0.0) || p >= 1.0 || stride == 0 || (stride & (stride - 1)) != 0) return ORC_EINVAL;
+  r = p > 0.5 ? 1.0 - p : p;
+  btrs = !((double) n * r < 10.0);
+  lf = logfact(n);
+  enumerated = ((uint64_t) 1 << 32) / stride;
+  for (k = 0; k <= n; k++) hist[k] = 0;
+  for (k = 0; k < ORC_LAW_INFO_N; k++) info[k] = 0;
+  info[ORC_LAW_REGIME] = btrs ? ORC_LAW_BTRS : ORC_LAW_INVERSION;
+  info[ORC_LAW_ENUMERATED] = enumerated;
+  for (i = 0; i < enumerated; i++) {
+    const uint32_t U = (uint32_t) (stride / 2 + i * stride);
+    uint64_t count = 1;
+    int32_t x;
+    if (btrs) {
+      const int check = (i & 255) == 128;
+      x = law_btrs_word(n, r, lf, U, check, &count, bad);
+      if (check && x >= 0) info[ORC_LAW_SEGMENT_CHECKED]++;
+      if (x < 0) info[ORC_LAW_OUT_OF_RANGE]++;   /* (count is 0) */
+    } else {
+      int restarted;
+      x = law_inversion_word(n, r, U, &restarted);
+      if (restarted) info[ORC_LAW_RESTARTS]++;
+      if (x < 0 || x > n) return ORC_FAILURE;
+      if (restarted) { hist[x] += 1; info[ORC_LAW_TOTAL] += 1; x = -1; count = 0; }   /* a Philox word's x: counted, and told in info */
+    }
+    if (x > n) return ORC_FAILURE;
+    if (x >= 0) hist[x] += count;
+    info[ORC_LAW_TOTAL] += count;
+    /* k(U) must not decrease from one enumerated word to the next (a word without a k of its own, and the one after it,
+       are left out) */
+    if (prev >= 0 && x >= 0 && x < prev) info[ORC_LAW_NOT_MONOTONE]++;
+    prev = x;
+  }
+  info[ORC_LAW_SEGMENT_BAD_NEAR] = bad[0];
+  info[ORC_LAW_SEGMENT_BAD_FAR] = bad[1];
+  return ORC_SUCCESS;
+}
 void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                 uint32_t *out4) {
   miso_u32x4 o = miso_philox4x32(c0, c1, c2, c3, k0, k1);

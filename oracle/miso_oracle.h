@@ -120,6 +120,21 @@ double orc_det_sqrt(double x);
 double orc_det_qnorm(double p);
 void orc_binomial(uint64_t seed, uint32_t event_id, int32_t n, double p, int count, int32_t *out);
 void orc_logfact(int n, double *out);
+/* The law of include/miso_binomial.h's draws by enumeration of the 32-bit words (tests/test_binomial_law.py): every
+   stride-th first word U from stride / 2, for BTRS the number of second words V that trial 0 accepts added to bin k(U), for
+   the inversion 1 added to bin x(U).  Bins of r = min(p, 1 - p); hist: n + 1 entries; info: the entries below. */
+enum { ORC_LAW_REGIME = 0,          /* ORC_LAW_INVERSION / ORC_LAW_BTRS, by miso_binomial's own comparison */
+       ORC_LAW_ENUMERATED,          /* words U enumerated: 2^32 / stride */
+       ORC_LAW_TOTAL,               /* the sum of hist */
+       ORC_LAW_RESTARTS,            /* inversion: words whose search ran past its bound (their x is another word's) */
+       ORC_LAW_OUT_OF_RANGE,        /* BTRS: words whose k is outside 0 .. n (no V accepts) */
+       ORC_LAW_NOT_MONOTONE,        /* enumerated words whose k is below the k of the word before */
+       ORC_LAW_SEGMENT_CHECKED,     /* BTRS: words (one in 2^8) whose accepted V were probed around and away from V* */
+       ORC_LAW_SEGMENT_BAD_NEAR,    /*   probes at V* - 2 .. V* + 3 that contradict "accepted = [0, V*]" */
+       ORC_LAW_SEGMENT_BAD_FAR,     /*   the 16 + 16 probes spread over either side that do */
+       ORC_LAW_INFO_N };
+enum { ORC_LAW_INVERSION = 0, ORC_LAW_BTRS = 1 };
+int orc_binomial_law(int32_t n, double p, uint32_t stride, uint64_t *hist, uint64_t *info);
 void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                 uint32_t *out4);
 void orc_philox_r(int rounds, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

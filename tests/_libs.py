@@ -45,7 +45,8 @@ def ensure_oracle_built():
     src = os.path.join(ROOT, "oracle", "miso_oracle.c")
     deps = [src, os.path.join(ROOT, "oracle", "miso_oracle.h"),
             os.path.join(ROOT, "include", "miso_detmath.h"),
-            os.path.join(ROOT, "include", "miso_philox.h")]
+            os.path.join(ROOT, "include", "miso_philox.h"),
+            os.path.join(ROOT, "include", "miso_binomial.h")]
     if (not os.path.exists(ORC_PATH)) or any(
             os.path.getmtime(d) > os.path.getmtime(ORC_PATH) for d in deps):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle"])
@@ -286,6 +287,19 @@ class OrcLib(_Base):
         out = np.zeros(count, np.int32)
         self.lib.orc_binomial(C.c_uint64(seed), C.c_uint32(event_id), C.c_int32(n), C.c_double(p), C.c_int(count), _p(out))
         return out
+
+    LAW_INFO = ("regime", "enumerated", "total", "restarts", "out_of_range", "not_monotone", "segment_checked",
+                "segment_bad_near", "segment_bad_far")
+    LAW_INVERSION, LAW_BTRS = 0, 1
+
+    def binomial_law(self, n, p, stride):
+        """oracle/miso_oracle.h orc_binomial_law: (hist[n + 1] uint64 in terms of r = min(p, 1 - p), info as a dict of ints)"""
+        hist = np.zeros(n + 1, np.uint64)
+        info = np.zeros(len(self.LAW_INFO), np.uint64)
+        rc = self.lib.orc_binomial_law(C.c_int32(n), C.c_double(p), C.c_uint32(stride), _p(hist), _p(info))
+        if rc != 0:
+            raise ValueError("orc_binomial_law(%r, %r, %r): error %d" % (n, p, stride, rc))
+        return hist, {k: int(v) for k, v in zip(self.LAW_INFO, info)}
 
     def logfact(self, n):
         """log 0! .. log (n-1)! as include/miso_binomial.h's miso_logfact_fill builds the binomial's table"""

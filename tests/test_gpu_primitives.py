@@ -16,6 +16,7 @@ test either: no input reaches it without a given starting psi."""
 import numpy as np
 import pytest
 
+import _binomial_law as L
 import _detmath_points as P
 from miso_amd import capi
 
@@ -374,3 +375,10 @@ def test_binomial_coop_equals_the_sequential_routine(orc, G):
             want = orc.binomial(n, float(p), 256, seed=5, event_id=n)
             got = capi.selftest_binomial(G, n, float(p), 256, seed=5, event_id=n)
             assert np.array_equal(got, want), (G, n, float(p).hex(), got[:8], want[:8])
+    # ... and at the points where the sequential routine is tied to the exact law (tests/test_binomial_law.py)
+    for n, p, _ in L.CASES:
+        if (n, p) in L.DEGENERATE:
+            continue
+        want = orc.binomial(n, p, 256, seed=5, event_id=n)
+        got = capi.selftest_binomial(G, n, p, 256, seed=5, event_id=n)
+        assert np.array_equal(got, want), (G, n, float(p).hex(), got[:8], want[:8])
