@@ -1,14 +1,16 @@
-// batch.hpp -- the batch object behind miso_batch_t (definition shared by runtime.hip / capi.hip)
+// batch.hpp -- the batch object behind miso_batch_t (definition shared by runtime.hip / launch.hip / capi.hip)
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "device.hpp"
+#include "hip_host.hpp"
 #include "host.hpp"
 #include "knobs.hpp"
 #include "plan.hpp"
@@ -89,7 +91,7 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
 template <class T> struct DevTable {
   T *d = nullptr;
   size_t cap = 0;                // elements allocated
-  std::vector<T> host;           // what d holds (runtime.hip put)
+  std::vector<T> host;           // what d holds (put, below)
   long key = -1;                 // the plan it was built for, -1 = none
   DevTable() = default;
   DevTable(const DevTable &) = delete;
@@ -100,6 +102,21 @@ template <class T> struct DevTable {
     d = nullptr; cap = 0; host.clear(); key = -1;
   }
 };
+// `t` holds `v` from now on, in an allocation of at least `min_n` elements; copied only when it holds something else
+template <class T> void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n = 1) {
+  const size_t n = std::max(v.size(), min_n);
+  if (t.d && n <= t.cap && v.size() == t.host.size() && (v.empty() || std::memcmp(v.data(), t.host.data(), v.size() * sizeof(T)) == 0)) return;
+  if (!t.d || n > t.cap) {
+    if (t.d) HIP_OK(hipFree(t.d));
+    t.d = nullptr; t.cap = 0;
+    HIP_OK(hipMalloc(reinterpret_cast<void **>(&t.d), n * sizeof(T)));
+    t.cap = n;
+  }
+  if (!v.empty()) HIP_OK(hipMemcpy(t.d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  t.host = v;
+}
+inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+template <class K> const void *fn(K *k) { return reinterpret_cast<const void *>(k); }   // a kernel's host stub as hipLaunchKernel takes it
 // chains on several workgroups (coop.hpp): which chain every workgroup works on, and the scratch they exchange through
 struct CoopTable {
   DevTable<int32_t> tab;         // four words per workgroup
@@ -108,6 +125,19 @@ struct CoopTable {
   void reset() { tab.reset(); mem.reset(); chains = 0; }
 };
 struct GrpShape { int qs = 0, ts = 0; };   // sampler_grp's slice: class thresholds (single-end), score table (paired-end)
+// A sampler kernel's host stub and its name as last_kernels and miso_batch_launch_stats report it (launch.hip: made side by
+// side, from the same template arguments)
+struct Kernel { const void *fn; std::string name; };
+// The kernel a general run is launched as.  The last six are a run's own kernels (launch.hip run_kernel: the one place that
+// tells them apart); the first three are what the plan puts a run into instead (plan_runs, group_runs).
+enum class RunKernel { LaneK, GrpAll, GrpMulti, GrpWide, GrpWave64, Big, Wave, Grp, Flat };
+// ... and a half of the two-isoform list (plan_k2)
+enum class K2Kernel { None, Lane, Multi, Mix, Single };
+// paired-end size bucket of a general run, in the launch list's order (build_slots: largest first): genes of few pairs in a
+// batch of several classes (eight lanes per chain); the class's normal launch; at least 32 lanes per chain (events several
+// times the class's mean size); one chain per wavefront (sampler_grp<64, true, KC>); one chain per workgroup (sampler_grp<64,
+// true, KC, true>)
+enum class Bucket { Small = -1, Normal = 0, Lanes32 = 1, Wavefront = 2, Workgroup = 3 };
 }  // namespace miso
 
 // diagnose(): chains at most (three doubles of LDS per split sequence)
@@ -150,7 +180,7 @@ struct miso_batch {
   bool coop_enabled() const;      // chains may use several workgroups (coop.hpp): not after a time-out, not with knobs.no_coop
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // the shader clock of a launch (miso_batch_set_clock_probe; runtime.hip clock_probe_kernel)
+  // the shader clock of a launch (miso_batch_set_clock_probe; launch.hip clock_probe_kernel)
   bool clock_probe = false, probe_armed = false, probe_failed = false;
   hipStream_t probe_stream = nullptr;
   unsigned long long *d_probe = nullptr;   // {t0 real, t0 cycles, t1 real, t1 cycles, gave up, -, -, flag}
@@ -195,13 +225,22 @@ struct miso_batch {
   float compare_ms = 0.f, exact_compare_ms = 0.f;   // kernel time of the last compare / compare_exact or compare_exact_paired
   void compare_exact(miso_batch &other, const double *z, int n_z);
   void compare_exact_paired(miso_batch &other, const double *z, int n_z);   // miso_batch_compare_exact_paired: the same stores
-  miso::LanePlan k2_plan;         // sampler_k2_multi: the runs of equal lanes per chain (runtime.hip), valid for k2_plan_key
-  long k2_plan_key = -1;
-  miso::CoopTable k2_coop_se, k2w_coop;   // the two plans' chains on several workgroups (key: the plan's wide run)
-  miso::LanePlan k2w_plan;        // the same for the paired-end MODE 2 events (sampler_k2_multi<2, 4>)
-  long k2w_plan_key = -1;
   int n_k2 = 0, n_gen = 0;
   int n_k2w = 0;                  // paired-end: the first n_k2w two-isoform slots take sampler_k2's MODE 2
+  // A half of the two-isoform list: k2[0] the paired-end MODE 2 events (no drawing read on a non-finite score), k2[1] the
+  // others (MODE 1; single-end: everything, MODE 0).  The slots and the mode are build_slots'; the lane plan, its key and the
+  // cooperative table are kept between launches; the rest is what the last launch() decided (plan_sizes, plan_k2).
+  struct K2Half {
+    int mode = 0;                 // sampler_k2's MODE
+    int first = 0, count = 0;     // slots [first, first + count) of d_slots
+    miso::K2Kernel kind = miso::K2Kernel::None;
+    int G = 0;                    // lanes per chain of the single-width launch (Mix: of its narrow part)
+    size_t fp = 0, tab = 0;       // LDS: the fragment-length probabilities, a chain's score table
+    miso::LanePlan plan;          // sampler_k2_multi: the runs of equal lanes per chain, valid for plan_key
+    long plan_key = -1;
+    miso::CoopTable coop;         // the plan's chains on several workgroups (key: the plan's wide run)
+  } k2[2];
+  bool k2_mode2(const miso::PackedEvent &e) const { return use_delta && e.pe_delta && !e.draw_dense.empty(); }   // k2[0] takes it
   // the other events, grouped by isoform-count class (sampler_grp<G, PE, KC> holds K in (KC_prev, KC])
   struct GenRun {
     int first = 0, count = 0;     // slice of d_slots (after the n_k2 two-isoform events)
@@ -211,15 +250,16 @@ struct miso_batch {
     int maxcls = 0;               // most drawing-read classes (single-end)
     bool nocls = false;           // some single-end event has no class table (> MAX_DRAW_CLASSES classes)
     bool dense = true;            // paired-end: every event has dense quad records (pe_dense)
-    bool small = false;           // paired-end size bucket: genes of few pairs in a batch of several classes -- eight lanes per chain (runtime.hip upload)
-    int force_G = 0;              // paired-end size bucket: at least this many lanes per chain (events several times the class's mean size)
-    bool wide = false;            // paired-end size bucket: one chain per workgroup (sampler_grp<64, true, KC, true>)
-    bool wave64 = false;          // paired-end size bucket: one chain per wavefront (sampler_grp<64, true, KC>)
-    // wide runs: which chain every workgroup works on, alone or as one of several (coop.hpp; runtime.hip wide_setup)
+    miso::Bucket bucket = miso::Bucket::Normal;   // paired-end size bucket (runtime.hip build_slots)
+    bool small() const { return bucket == miso::Bucket::Small; }
+    bool wave64() const { return bucket == miso::Bucket::Wavefront; }
+    bool wide() const { return bucket == miso::Bucket::Workgroup; }
+    int force_G() const { return bucket == miso::Bucket::Lanes32 ? 32 : (wave64() ? 64 : 0); }   // at least this many lanes per chain
+    // wide runs: which chain every workgroup works on, alone or as one of several (coop.hpp; launch.hip wide_setup)
     miso::CoopTable coop;
     int tuned_G = 0;              // lanes per chain picked by the first launch's trial runs
     int tuned_flat = -1;          // sampler_flat (1) or sampler_grp (0) by the first launch's trial runs, -1 = not tried
-    // sampler_flat: which chains every wavefront owns (runtime.hip flat_waves; two words per wavefront)
+    // sampler_flat: which chains every wavefront owns (launch.hip flat_waves; two words per wavefront)
     miso::DevTable<int32_t> wave_tab;
     int wave_nc = 0;              // most chains of any wavefront = slices per wavefront in LDS
     int wave_wide = 0;            // chains that own a whole workgroup
@@ -246,35 +286,35 @@ struct miso_batch {
   // sampler_k2_multi<0, 8>, one round: the launch's wavefronts paired by estimated duration across the runs (runtime.hip)
   miso::DevTable<int32_t> k2_pair_tab;
   int k2_pair_wide_blocks = 0, k2_pair_grid = 0;
-  // What launch() decided, kept until the next launch: the launches follow it, launch_stats() reads it (runtime.hip)
+  // What launch() decided, kept until the next launch: the launches follow it, launch_stats() reads it (launch.hip)
   struct LaunchPlan {
     bool sampled = false;         // the kernels below ran (not MARGINAL / CLASSES, not adopted samples)
     // this launch's sizes and switches (plan_sizes)
     size_t lds_max = 0;           // a workgroup's LDS budget
-    size_t k2_fp = 0, k2_tab = 0, k2w_fp = 0, k2w_tab = 0, fp_plain = 0;
+    size_t fp_plain = 0;
     bool dense_env = true;
     int il2 = 0;
     long total_chains = 0;
     size_t n_kernels = 0;
     bool tune_runs = false;
     int coop_max = 1;
-    // the two-isoform part (plan_k2)
-    int k2_G = 0, k2w_G = 0;      // sampler_k2's lanes per chain: MODE 0 / 1, MODE 2
+    // the two-isoform part (plan_k2; the halves' own figures are in k2[])
     bool k2_pair = false;         // single-end sampler_k2<G, 0, 8>
     int k2_mix = 0, k2_mix_blocks = 0;                 // sampler_k2_mix: events of the wide part, its workgroups
-    bool k2_multi = false, k2w_multi = false, k2_narrow = false;
-    size_t k2w_multi_lds = 0;
+    bool k2_narrow = false;       // sampler_k2_multi<0, 4, true>
     bool lane_route = false, lane_ilp = false;         // collapsed: sampler_lane, sampler_lane_ilp or sampler_k2c<lane_G>
     int lane_G = 1;
     // the general runs, one per gen_runs entry (plan_runs, group_runs)
     struct Run {
-      bool lane = false;          // sampler_lane_k
+      miso::RunKernel kind = miso::RunKernel::Grp;     // the kernel it is launched as
+      miso::RunKernel layout = miso::RunKernel::Grp;   // ... and, inside a launch of several runs, the run's own kernel: how its wavefronts are cut
+      bool lane() const { return kind == miso::RunKernel::LaneK; }
+      bool grouped() const { return kind == miso::RunKernel::GrpAll || kind == miso::RunKernel::GrpMulti; }
       int flat_nc = 0, flat_nc_max = 0;   // sampler_flat's chains per wavefront (0: not sampler_flat)
       int flat_ks = 0;            // ... its compile-time isoform count (0: the layout at run time)
       bool flat_uni = false;      // ... every event of the run has flat_ks isoforms
       int G = 64;                 // sampler_grp's lanes per chain
       miso::GrpShape sh;
-      int group = 0;              // launched as a segment of sampler_grp_multi (1) or sampler_grp_all (2)
       bool merge_next = false;    // one launch with the next run
     };
     std::vector<Run> runs;
@@ -324,7 +364,7 @@ struct miso_batch {
   void compare(miso_batch &other, double smoothing);
   std::vector<miso_kernel_stat_t> launch_stats() const;   // miso_batch_launch_stats: one record per two-isoform part and per run
 
-  // the parts of launch() (runtime.hip)
+  // the parts of launch(): the plan (runtime.hip), the launches that follow it (launch.hip)
   void plan_sizes();
   void plan_k2(const miso::KernelArgs &a);
   // a part of the two-isoform list as plan_lanes takes it: slots [first, first + count), the lanes per chain a run may have,
@@ -332,7 +372,7 @@ struct miso_batch {
   // wavefront the LDS allows, the part's share of the cooperative workgroups
   struct K2Part { int first, count; const int *widths; int n_widths; int wide_wpb = 0, wpb = 0, resident = 1, max_cpw = 64, coop_budget = 0; };
   miso::LanePlan k2_lanes(const K2Part &pt, const std::vector<int> &nd, const miso::LaneCost &cost) const;
-  bool plan_k2_lanes(const K2Part &pt, bool forced, miso::LaneCost &cost, std::vector<int> &nd, miso::LanePlan &pl, long &pl_key);
+  bool plan_k2_lanes(const K2Part &pt, bool forced, miso::LaneCost &cost, std::vector<int> &nd, K2Half &h);
   void k2_pair_table(const std::vector<int> &nd, const miso::LaneCost &cost);
   void plan_runs(const miso::KernelArgs &a);
   int flat_wgs(int kc) const;
@@ -343,18 +383,25 @@ struct miso_batch {
   template <class F> int fastest(const miso::KernelArgs &a, const std::vector<int> &cand, F &&trial);
   int slots_for(long chains) const;
   hipStream_t stream_for_next();
+  // launch.hip: every sampler launch goes through launch_kernel, which also records the kernel's name -- unless it is a
+  // trial launch (fastest)
+  bool trial_launch = false;
   void note_kernel(const std::string &name) { last_kernels += (last_kernels.empty() ? "" : ",") + name; }
-  std::string k2_part_name(bool wpart) const;
-  std::string run_name(size_t ri) const;
+  void launch_kernel(const miso::Kernel &k, unsigned grid, unsigned block, size_t lds, hipStream_t st, void **args);
+  void launch_kernel(const miso::Kernel &k, unsigned grid, unsigned block, size_t lds, hipStream_t st, const miso::KernelArgs &ka);
+  static miso::RunKernel run_kernel(const GenRun &run, int G, bool flat, bool dense_env, bool paired);
+  miso::Kernel k2_kernel_of(const K2Half &h) const;
+  miso::Kernel run_kernel_of(miso::RunKernel kind, int kc, const LaunchPlan::Run &r) const;
+  void launch_marginal(const miso::KernelArgs &a);
   int fp_rows(const GenRun &run) const;
   size_t fp_bytes_of(const GenRun &run) const;
   miso::GrpShape grp_shape(const GenRun &run) const;
   bool grp_fits(const GenRun &run, const miso::GrpShape &sh, int G) const;
   GenRun joined_run(size_t r0, size_t r1) const;
-  void launch_k2(miso::KernelArgs ka, int G, hipStream_t st, bool wpart = false);
+  void launch_k2(miso::KernelArgs ka, const K2Half &h, int G, hipStream_t st);
   void launch_k2_mix(miso::KernelArgs ka, hipStream_t st);
-  void k2_coop(miso::KernelArgs &ka, const miso::LanePlan &pl, miso::CoopTable &cc, hipStream_t st);
-  void launch_k2_multi(miso::KernelArgs ka, hipStream_t st, bool wpart = false);
+  void k2_coop(miso::KernelArgs &ka, K2Half &h, hipStream_t st);
+  void launch_k2_multi(miso::KernelArgs ka, K2Half &h, hipStream_t st);
   void launch_lane(miso::KernelArgs ka, hipStream_t st);
   unsigned wide_setup(GenRun &run, long chains, hipStream_t st);
   void launch_grp(miso::KernelArgs ka, GenRun &run, const miso::GrpShape &sh, int G, hipStream_t st);
@@ -363,7 +410,7 @@ struct miso_batch {
   void launch_run(const miso::KernelArgs &a, size_t ri);
   void launch_grp_all(const miso::KernelArgs &a);
   void launch_grp_multi(const miso::KernelArgs &a, size_t r0, size_t r1);
-  template <class F> void each_coop_table(F &&f) { for (GenRun &r : gen_runs) f(r.coop); f(k2_coop_se); f(k2w_coop); }
+  template <class F> void each_coop_table(F &&f) { for (GenRun &r : gen_runs) f(r.coop); f(k2[0].coop); f(k2[1].coop); }
   template <class F> void each_table(F &&f) {   // every device table above (release())
     f(grp_segs); f(round_tab); f(logfact); f(k2_pair_tab); f(exact_eff);
     for (GenRun &r : gen_runs) f(r.wave_tab);

@@ -1,4 +1,5 @@
-// runtime.hip -- batch object: host packing -> HBM pools -> kernel launches -> results.
+// runtime.hip -- batch object: host packing -> HBM pools -> the plan of a launch -> results (the launches themselves, which
+// follow that plan: launch.hip).
 //
 // One batch = the events one GPU samples in one go (the unit the reference hands to one worker
 // process, misopy/miso.py:165-187).  All events of a batch share the sampler parameters
@@ -20,61 +21,20 @@
 #include "coop.hpp"
 #include "exact_compare.hpp"
 #include "hip_host.hpp"
-#include "miso_binomial.h"
 
 namespace miso {
 
 extern int g_hw_queues_in_effect;   // capi.hip: the host's hardware queue count as the runtime read (or will read) it, 0 = unknown
 
-template <bool PE> __global__ void sampler_wave(const KernelArgs a);
-template <int G, int MODE, int WPB> __global__ void sampler_k2(const KernelArgs a);
-template <int GA, int GB> __global__ void sampler_k2_mix(const KernelArgs a);
-template <int MODE, int WPB, bool NARROW = false> __global__ void sampler_k2_multi(const KernelArgs a);
-template <bool PE> __global__ void sampler_big(const KernelArgs a);   // kernels_big.hip: 65 ... MISO_MAX_ISOFORMS isoforms
-__global__ void sampler_lane(const KernelArgs a);   // kernels_lane.hip: collapsed Gibbs step, one chain per lane
-__global__ void sampler_lane_ilp(const KernelArgs a);   // ... the form for at most two wavefronts per SIMD
-template <int G> __global__ void sampler_k2c(const KernelArgs a);   // ... G lanes per chain (k2_body COLLAPSED)
-__global__ void sampler_lane_k(const KernelArgs a); // ... three and more isoforms (vectors in LDS)
-__global__ void sampler_marginal(const KernelArgs a); // kernels_marginal.hip: algorithm = MARGINAL, one chain per lane
-__global__ void exact_sample(const KernelArgs a, const double *eff, int S);   // kernels_exact.hip: the exact-posterior mode, one wavefront per event
-constexpr int LANEK_VECTORS = 9;
-inline size_t lanek_lds_bytes(int ks) { return static_cast<size_t>(LANEK_VECTORS) * ks * 64 * 8 + static_cast<size_t>(ks) * 64 * 4; }
 __global__ void compare_kernel(const DevEvent *, const unsigned char *, const DevEvent *, const unsigned char *, int, int,
                                double, const uint64_t *, double *);
 __global__ void match_kernel(const MatchEvent *, const int2 *, const int *, const int *, const int *, const int *,
                              const int *, const int *, const int *, int, int, int, int, int, uint32_t *, uint16_t *);
 __global__ void summarize_kernel(const DevEvent *, const unsigned char *, int, int, int, int, const uint64_t *, double *, int);
 __global__ void diagnose_kernel(const DevEvent *, const unsigned char *, int, int, int, int, double, int, const uint64_t *, double *);
-template <int G, bool PE, int KC, bool WIDE = false> __global__ void sampler_grp(const KernelArgs a);
-template <int KC> __global__ void sampler_grp_multi(const KernelArgs a);
-__global__ void sampler_grp_all(const KernelArgs a);   // kernels_grp_all.hip
-template <int KC, int KS, bool UNI> __global__ void sampler_flat(const KernelArgs a);   // KS: the launch's largest isoform count at compile time (0: at run time)
 __global__ void selftest_detmath_kernel(const double *, int, double *, double *, double *, double *);
 __global__ void selftest_philox_kernel(const uint32_t *, int, uint32_t *);
 
-// ---- the shader clock a launch ran at (miso_batch_set_clock_probe; bench.py's roofline prices its VALU peak with it) ----
-// ONE wavefront beside the sampler kernels, on a stream of its own: it sleeps, looks at a flag the batch's stream sets
-// behind its last kernel, and leaves with the two counters' values at both ends -- s_memtime counts shader cycles,
-// wall_clock64() the constant reference clock (hipDeviceAttributeWallClockRate: 100 MHz here) -- so cycles / time over exactly the launch.  No VALU work, no LDS: it
-// takes one wave slot of one SIMD.  The flag carries the launch's number (nothing to reset between launches).  It gives up after `max_ticks` of the reference clock (a flag that never comes must
-// not hold the device).  out: {t0 real, t0 cycles, t1 real, t1 cycles, 1 = gave up}.
-__global__ void clock_probe_kernel(const uint32_t *flag, uint32_t want, unsigned long long *out, unsigned long long max_ticks) {
-  if (threadIdx.x != 0) return;
-  const unsigned long long r0 = static_cast<unsigned long long>(wall_clock64()), c0 = __builtin_readcyclecounter();
-  unsigned long long r1 = r0;
-  uint32_t f = 0;
-  do {
-    __builtin_amdgcn_s_sleep(127);
-    f = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    r1 = static_cast<unsigned long long>(wall_clock64());
-  } while (f != want && r1 - r0 < max_ticks);
-  const unsigned long long c1 = __builtin_readcyclecounter();
-  r1 = static_cast<unsigned long long>(wall_clock64());
-  out[0] = r0; out[1] = c0; out[2] = r1; out[3] = c1; out[4] = f != want;
-}
-__global__ void clock_probe_stop(uint32_t *flag, uint32_t value) {
-  if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 int device_count() {
   int n = 0;
@@ -84,7 +44,6 @@ int device_count() {
 
 void set_device(int d) { HIP_OK(hipSetDevice(d)); }
 
-static inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 // Lanes per chain for sampler_k2.  Measured on MI355X (profiles/r01_k2_phase_cycles.txt): the
 // kernel is VALU-issue bound at two resident wavefronts per SIMD; the per-iteration scalar MH
@@ -93,7 +52,6 @@ static inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a
 // mostly empty round starts.  Hence: the smallest supported G whose wavefront count still fills
 // the slots once, i.e. the largest G with ceil(chains / (64 / G)) <= slots; G = 1 for batches that
 // overflow anyway; never more lanes than a chain has pairs of draw quads to stride over.
-static inline int flat_wgs_for(int kc) { return kc <= 4 ? 3 : (kc == 12 ? 3 : 2); }
 
 int choose_lanes_per_chain(long chains, int max_quads, int wave_slots, int max_cpw) {
   static const int kG[] = {64, 32, 21, 16, 12, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1};
@@ -128,7 +86,7 @@ void miso_batch::release() {
   // (the next upload may be to another device: nothing may outlive its allocation as a stale pointer or a cached plan)
   each_table([](auto &t) { t.reset(); });
   k2_pair_grid = k2_pair_wide_blocks = 0;
-  k2_plan_key = k2w_plan_key = -1;
+  k2[0].plan_key = k2[1].plan_key = -1;
   if (probe_stream) { (void) hipStreamSynchronize(probe_stream); (void) hipStreamDestroy(probe_stream); probe_stream = nullptr; }
   if (d_probe) { (void) hipFree(d_probe); d_probe = nullptr; }
   probe_armed = false;
@@ -294,7 +252,6 @@ void miso_batch::resolve_pending() {
                  secs(T0, T1), match_ms, secs(T1, T2), nthreads, secs(T2, now()));
 }
 
-template <class T> static void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n = 1);
 
 void miso_batch::upload(int dev) {
   if (uploaded && dev == device) return;
@@ -440,7 +397,7 @@ void miso_batch::build_slots() {
   // reference, which takes any sd, miso_paired.c:299-308; or knobs.k2_general)
   k2_general = p.paired && (48 * fd.prob.size() + 64 > 150 * 1024 || knobs.k2_general);
   // (the exact-posterior mode, miso_batch_set_exact: its eligible events leave both lists for one of their own)
-  std::vector<int32_t> k2, gen, ex;
+  std::vector<int32_t> two, gen, ex;
   is_exact.assign(n, 0);
   if (exact && !p.paired && p.algorithm == MISO_ALGO_REASSIGN)
     for (int i = 0; i < n; i++) {
@@ -465,17 +422,17 @@ void miso_batch::build_slots() {
       is_exact[i] = exact_paired_eligible(2, events[i].eff.data(), events[i].hyper.data(), events[i].base_bad != 0 || !events[i].pe_delta);
     }
   }
-  for (int i = 0; i < n; i++) (is_exact[i] ? ex : (events[i].K == 2 && !k2_general) ? k2 : gen).push_back(i);
+  for (int i = 0; i < n; i++) (is_exact[i] ? ex : (events[i].K == 2 && !k2_general) ? two : gen).push_back(i);
   // (paired-end: the events sampler_k2's MODE 2 can take come first)
   use_delta = !knobs.no_pe_delta;   // fixed here: the slot order depends on it
   // (Round 5 tried ordering a collapsed batch's list by the binomial's likely regime -- inversion below n min(p, q) = 10, BTRS
   // above: a wavefront that holds chains of both runs both -- and measured nothing once the inversion had lost its division:
   // 50.3 - 50.8 ms against 50.1 - 50.6 ms, profiles/r05_sampler_lane_ilp.txt.)
-  std::stable_sort(k2.begin(), k2.end(), [&](int x, int y) {
-    const bool dx = use_delta && events[x].pe_delta && !events[x].draw_dense.empty(), dy = use_delta && events[y].pe_delta && !events[y].draw_dense.empty();
+  std::stable_sort(two.begin(), two.end(), [&](int x, int y) {
+    const bool dx = k2_mode2(events[x]), dy = k2_mode2(events[y]);
     return dx != dy ? dx : events[x].n_draw > events[y].n_draw; });
   n_k2w = 0;
-  for (int i : k2) n_k2w += (use_delta && events[i].pe_delta && !events[i].draw_dense.empty()) ? 1 : 0;
+  for (int i : two) n_k2w += k2_mode2(events[i]) ? 1 : 0;
   // the general kernel's wavefronts loop to their largest K and longest draw list: group alike.
   // Paired-end (sampler_grp gives every chain of a launch the same lanes): genes of very different sizes -- real
   // read counts, 20 ... 10^5 pairs per gene; the reference costs O(reads) per gene, miso_paired.c:393-552 -- are
@@ -490,7 +447,7 @@ void miso_batch::build_slots() {
   // (64: 33 ... MISO_MAX_ISOFORMS isoforms -- sampler_wave only, lane k = isoform k; the reference has no limit, miso.c:696)
   // (256: 65 ... MISO_MAX_ISOFORMS isoforms -- sampler_big, the chain's vectors in LDS, kernels_big.hip)
   auto kc_of = [](int K) { return K <= 4 ? 4 : (K <= 8 ? 8 : (K <= 12 ? 12 : (K <= 16 ? 16 : (K <= 32 ? 32 : (K <= 64 ? 64 : 256))))); };
-  std::vector<int> bucket(n, 0);   // 0 normal, 1 at least 32 lanes, 2 a wavefront, 3 workgroup-wide (coop_n[event] workgroups)
+  std::vector<Bucket> bucket(n, Bucket::Normal);   // (Workgroup: on coop_n[event] workgroups)
   coop_n.assign(n, 1);
   if (p.paired && !knobs.no_pe_buckets) {
     double W = 0;
@@ -512,11 +469,11 @@ void miso_batch::build_slots() {
       const double need = W > 0 ? share_factor * device_lanes * (static_cast<double>(nq) * e.K) / W : 0.0;
       const bool can_wide = dense_ok && !e.draw_dense.empty() && e.K >= 3 && e.K <= PE_DENSE_KMAX;
       if (can_wide && need > t_wide && nq >= 512) {
-        bucket[i] = 3;
+        bucket[i] = Bucket::Workgroup;
         if (coop_on && need > 384.0)
           coop_n[i] = std::max(1, std::min({COOP_MAX_N, static_cast<int>(std::ceil(need / 256.0)), nq / 512}));
-      } else if (can_wide && need > t_wave && nq >= 128) bucket[i] = 2;
-      else if (need > t_32 && nq >= 64) bucket[i] = 1;
+      } else if (can_wide && need > t_wave && nq >= 128) bucket[i] = Bucket::Wavefront;
+      else if (need > t_32 && nq >= 64) bucket[i] = Bucket::Lanes32;
     }
     // (round 6) ... and the SMALL genes of a batch of several classes: eight lanes per chain -- a gene of a hundred pairs is all
     // scalar step, which eight chains of a wavefront share instead of four (16 384 genes of 3 - 8 isoforms x 100 / 250 / 500 pairs:
@@ -527,7 +484,7 @@ void miso_batch::build_slots() {
     if (classes2 && t_small > 0 && dense_ok)
       for (int i : gen) {
         const PackedEvent &e = events[i];
-        if (bucket[i] == 0 && !e.draw_dense.empty() && e.K >= 3 && e.K <= PE_DENSE_KMAX && (e.n_draw + 3) / 4 <= t_small) bucket[i] = -1;
+        if (bucket[i] == Bucket::Normal && !e.draw_dense.empty() && e.K >= 3 && e.K <= PE_DENSE_KMAX && (e.n_draw + 3) / 4 <= t_small) bucket[i] = Bucket::Small;
       }
   }
   std::stable_sort(gen.begin(), gen.end(), [&](int x, int y) {
@@ -535,12 +492,12 @@ void miso_batch::build_slots() {
     if (kx != ky) return kx > ky;
     if (bucket[x] != bucket[y]) return bucket[x] > bucket[y];
     return events[x].K != events[y].K ? events[x].K > events[y].K : events[x].n_draw > events[y].n_draw; });
-  gen_runs.clear(); tuned_k2_G = 0; k2_plan_key = k2w_plan_key = -1;
+  gen_runs.clear(); tuned_k2_G = 0; k2[0].plan_key = k2[1].plan_key = -1;
   for (size_t j = 0; j < gen.size(); j++) {
     const PackedEvent &e = events[gen[j]];
-    const int kc = kc_of(e.K), bk = bucket[gen[j]];
-    if (gen_runs.empty() || gen_runs.back().kc != kc || (gen_runs.back().wide ? 3 : (gen_runs.back().wave64 ? 2 : (gen_runs.back().force_G ? 1 : (gen_runs.back().small ? -1 : 0)))) != bk) {
-      GenRun r; r.first = static_cast<int>(j); r.kc = kc; r.wide = bk == 3; r.wave64 = bk == 2; r.force_G = bk == 1 ? 32 : (bk == 2 ? 64 : 0); r.small = bk == -1;
+    const int kc = kc_of(e.K);
+    if (gen_runs.empty() || gen_runs.back().kc != kc || gen_runs.back().bucket != bucket[gen[j]]) {
+      GenRun r; r.first = static_cast<int>(j); r.kc = kc; r.bucket = bucket[gen[j]];
       gen_runs.push_back(std::move(r));
     }
     GenRun &r = gen_runs.back();
@@ -553,167 +510,21 @@ void miso_batch::build_slots() {
     if (!e.paired && e.n_draw > 0 && e.dcls_mask.empty()) r.nocls = true;
     if (!e.paired || e.draw_dense.empty() || e.K == 2) r.dense = false;   // (K = 2: draw_dense holds sampler_k2's records)
   }
-  n_k2 = static_cast<int>(k2.size()); n_gen = static_cast<int>(gen.size());
+  n_k2 = static_cast<int>(two.size()); n_gen = static_cast<int>(gen.size());
   n_exact = static_cast<int>(ex.size());
-  k2.insert(k2.end(), gen.begin(), gen.end());
-  k2.insert(k2.end(), ex.begin(), ex.end());
-  h_slots = k2;
+  k2[0].mode = 2; k2[0].first = 0; k2[0].count = n_k2w;
+  k2[1].mode = p.paired ? 1 : 0; k2[1].first = n_k2w; k2[1].count = n_k2 - n_k2w;
+  h_slots = two;
+  h_slots.insert(h_slots.end(), gen.begin(), gen.end());
+  h_slots.insert(h_slots.end(), ex.begin(), ex.end());
   std::vector<double> eff2;
   for (int i : ex) { eff2.push_back(events[i].eff[0]); eff2.push_back(events[i].eff[1]); }
   put(exact_eff, eff2);
   slots_exact = exact_any(); exact_sums.clear(); exact_sums_level = -1.0;
   if (!d_slots) HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_slots), std::max<size_t>(n, 1) * sizeof(int32_t)));
-  if (n) HIP_OK(hipMemcpy(d_slots, k2.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (n) HIP_OK(hipMemcpy(d_slots, h_slots.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
 }
 
-// ---- the sampler kernels' host stubs, picked by their template arguments ----
-// Only the instantiations the kernel units make (kernels_*.hip): a pointer to any other links into the library and fails
-// when it is loaded.
-template <class K> static const void *fn(K *k) { return reinterpret_cast<const void *>(k); }
-template <int MODE, int WPB> static const void *k2_kernel(int G) {
-  switch (G) {
-  case 1: return fn(&sampler_k2<1, MODE, WPB>);
-  case 2: return fn(&sampler_k2<2, MODE, WPB>);
-  case 3: return fn(&sampler_k2<3, MODE, WPB>);
-  case 4: return fn(&sampler_k2<4, MODE, WPB>);
-  case 5: return fn(&sampler_k2<5, MODE, WPB>);
-  case 6: return fn(&sampler_k2<6, MODE, WPB>);
-  case 7: return fn(&sampler_k2<7, MODE, WPB>);
-  case 8: return fn(&sampler_k2<8, MODE, WPB>);
-  case 9: return fn(&sampler_k2<9, MODE, WPB>);
-  case 10: return fn(&sampler_k2<10, MODE, WPB>);
-  case 12: return fn(&sampler_k2<12, MODE, WPB>);
-  case 16: return fn(&sampler_k2<16, MODE, WPB>);
-  case 21: return fn(&sampler_k2<21, MODE, WPB>);
-  case 32: return fn(&sampler_k2<32, MODE, WPB>);
-  case 64: return fn(&sampler_k2<64, MODE, WPB>);
-  default: MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
-  }
-}
-static const void *k2_mix_kernel(int G) {   // sampler_k2_mix<G + 1, G>
-  switch (G) {
-  case 1: return fn(&sampler_k2_mix<2, 1>);
-  case 2: return fn(&sampler_k2_mix<3, 2>);
-  case 3: return fn(&sampler_k2_mix<4, 3>);
-  case 4: return fn(&sampler_k2_mix<5, 4>);
-  case 5: return fn(&sampler_k2_mix<6, 5>);
-  case 6: return fn(&sampler_k2_mix<7, 6>);
-  default: return fn(&sampler_k2_mix<8, 7>);
-  }
-}
-static const void *k2_multi_kernel(int mode, int wpb, bool narrow) {
-  if (mode == 2) return wpb == 8 ? fn(&sampler_k2_multi<2, 8>) : fn(&sampler_k2_multi<2, 4>);
-  if (mode == 1) return fn(&sampler_k2_multi<1, 4>);
-  if (wpb == 8) return fn(&sampler_k2_multi<0, 8>);
-  if (wpb == 4) return narrow ? fn(&sampler_k2_multi<0, 4, true>) : fn(&sampler_k2_multi<0, 4>);
-  return fn(&sampler_k2_multi<0, 1>);
-}
-static const void *lane_kernel(int G, bool ilp) {   // the collapsed step: one lane per chain, or G (sampler_k2c)
-  switch (G) {
-  case 1: return ilp ? fn(&sampler_lane_ilp) : fn(&sampler_lane);
-  case 2: return fn(&sampler_k2c<2>);
-  case 4: return fn(&sampler_k2c<4>);
-  default: return fn(&sampler_k2c<8>);
-  }
-}
-template <int G, bool PE, bool WIDE = false> static const void *grp_kc(int kc) {
-  switch (kc) {
-  case 4: return fn(&sampler_grp<G, PE, 4, WIDE>);
-  case 8: return fn(&sampler_grp<G, PE, 8, WIDE>);
-  case 12: return fn(&sampler_grp<G, PE, 12, WIDE>);
-  case 16: return fn(&sampler_grp<G, PE, 16, WIDE>);
-  default: return fn(&sampler_grp<G, PE, 32, WIDE>);
-  }
-}
-static const void *grp_kernel(int G, bool pe, int kc) {   // G < 64
-  switch (G) {
-  case 2: return pe ? grp_kc<2, true>(kc) : grp_kc<2, false>(kc);
-  case 4: return pe ? grp_kc<4, true>(kc) : grp_kc<4, false>(kc);
-  case 8: return pe ? grp_kc<8, true>(kc) : grp_kc<8, false>(kc);
-  case 16: return pe ? grp_kc<16, true>(kc) : grp_kc<16, false>(kc);
-  case 32: return pe ? grp_kc<32, true>(kc) : grp_kc<32, false>(kc);
-  default: MISO_FAIL(MISO_EINVAL, "MISO_GENERAL_LANES must be 2, 4, 8, 16, 32 or 64");
-  }
-}
-static const void *grp_multi_kernel(int kc) {
-  switch (kc) {
-  case 4: return fn(&sampler_grp_multi<4>);
-  case 8: return fn(&sampler_grp_multi<8>);
-  case 12: return fn(&sampler_grp_multi<12>);
-  case 16: return fn(&sampler_grp_multi<16>);
-  default: return fn(&sampler_grp_multi<32>);
-  }
-}
-template <int KC, int KS> static const void *flat_ks_kernel(bool uni) {
-  return uni ? fn(&sampler_flat<KC, KS, true>) : fn(&sampler_flat<KC, KS, false>);
-}
-// ks: the run's largest isoform count at compile time (kc - 3 ... kc, 17 ... 20 for kc = 32), 0 = the layout at run time
-static const void *flat_kernel(int kc, int ks, bool uni) {
-  switch (kc) {
-  case 4:
-    return ks == 3 ? flat_ks_kernel<4, 3>(uni) : ks == 4 ? flat_ks_kernel<4, 4>(uni) : fn(&sampler_flat<4, 0, false>);
-  case 8:
-    return ks == 5 ? flat_ks_kernel<8, 5>(uni) : ks == 6 ? flat_ks_kernel<8, 6>(uni) : ks == 7 ? flat_ks_kernel<8, 7>(uni)
-         : ks == 8 ? flat_ks_kernel<8, 8>(uni) : fn(&sampler_flat<8, 0, false>);
-  case 12:
-    return ks == 9 ? flat_ks_kernel<12, 9>(uni) : ks == 10 ? flat_ks_kernel<12, 10>(uni) : ks == 11 ? flat_ks_kernel<12, 11>(uni)
-         : ks == 12 ? flat_ks_kernel<12, 12>(uni) : fn(&sampler_flat<12, 0, false>);
-  case 16:
-    return ks == 13 ? flat_ks_kernel<16, 13>(uni) : ks == 14 ? flat_ks_kernel<16, 14>(uni) : ks == 15 ? flat_ks_kernel<16, 15>(uni)
-         : ks == 16 ? flat_ks_kernel<16, 16>(uni) : fn(&sampler_flat<16, 0, false>);
-  default:
-    return ks == 17 ? flat_ks_kernel<32, 17>(uni) : ks == 18 ? flat_ks_kernel<32, 18>(uni) : ks == 19 ? flat_ks_kernel<32, 19>(uni)
-         : ks == 20 ? flat_ks_kernel<32, 20>(uni) : fn(&sampler_flat<32, 0, false>);
-  }
-}
-
-// Every sampler launch: the dynamic LDS the kernel may use, the launch (what the triple-chevron stub calls too), its check.
-static void launch_kernel(const void *f, unsigned grid, unsigned block, size_t lds, hipStream_t st, const KernelArgs &ka) {
-  if (lds) HIP_OK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  void *args[] = {const_cast<KernelArgs *>(&ka)};
-  (void) hipLaunchKernel(f, dim3(grid), dim3(block), args, lds, st);
-  HIP_OK(hipGetLastError());
-}
-
-// `t` holds `v` from now on, in an allocation of at least `min_n` elements; copied only when it holds something else
-template <class T> static void put(DevTable<T> &t, const std::vector<T> &v, size_t min_n) {
-  const size_t n = std::max(v.size(), min_n);
-  if (t.d && n <= t.cap && v.size() == t.host.size() && (v.empty() || std::memcmp(v.data(), t.host.data(), v.size() * sizeof(T)) == 0)) return;
-  if (!t.d || n > t.cap) {
-    if (t.d) HIP_OK(hipFree(t.d));
-    t.d = nullptr; t.cap = 0;
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&t.d), n * sizeof(T)));
-    t.cap = n;
-  }
-  if (!v.empty()) HIP_OK(hipMemcpy(t.d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  t.host = v;
-}
-
-// ---- names (last_kernels, launch_stats) ----
-static std::string k2_name(int G, bool paired, bool wpart, bool pair) {
-  return "sampler_k2<" + std::to_string(G) + (paired ? (wpart ? ", 2, 4>" : ", 1, 4>") : (pair ? ", 0, 8>" : ", 0, 4>"));
-}
-std::string miso_batch::k2_part_name(bool wpart) const {   // the kernel of the MODE 2 part (wpart) or of the other two-isoform events
-  const LaunchPlan &q = plan;
-  if (wpart) return q.k2w_multi ? "sampler_k2_multi<2, " + std::to_string(k2w_plan.wpb) + ">" : k2_name(q.k2w_G, p.paired, true, q.k2_pair);
-  if (q.lane_route) return q.lane_G == 1 ? std::string(q.lane_ilp ? "sampler_lane_ilp" : "sampler_lane") : "sampler_k2c<" + std::to_string(q.lane_G) + ">";
-  if (q.k2_multi)
-    return "sampler_k2_multi<" + std::string(p.paired ? "1, " : "0, ") + std::to_string(k2_plan.wpb) + (q.k2_narrow ? ", true>" : ">");
-  if (q.k2_mix > 0) return "sampler_k2_mix<" + std::to_string(q.k2_G + 1) + ", " + std::to_string(q.k2_G) + ">";
-  return k2_name(q.k2_G, p.paired, false, q.k2_pair);
-}
-std::string miso_batch::run_name(size_t ri) const {   // the kernel general run ri is part of
-  const GenRun &run = gen_runs[ri];
-  const LaunchPlan::Run &r = plan.runs[ri];
-  const std::string kc = std::to_string(run.kc), pe = p.paired ? "true" : "false";
-  if (r.lane) return "sampler_lane_k";
-  if (r.group == 2) return "sampler_grp_all";
-  if (r.group == 1) return "sampler_grp_multi<" + kc + ">";
-  if (run.wide) return "sampler_grp<64, true, " + kc + ", true>";
-  if (r.flat_nc > 0) return "sampler_flat<" + kc + ", " + std::to_string(r.flat_ks) + (r.flat_uni ? ", true>" : ">");
-  if (r.G == 64 && !(run.wave64 && p.paired && run.dense)) return std::string(run.kc > 64 ? "sampler_big<" : "sampler_wave<") + pe + ">";
-  return "sampler_grp<" + std::to_string(r.G) + ", " + pe + ", " + kc + ">";
-}
 
 // ---- launch(): plan the two-isoform part, plan the general runs, group them into launches, launch ----
 void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
@@ -757,7 +568,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
     pool_cleared = true;
   }
   lanes_per_chain = 0;
-  last_kernels.clear();
+  last_kernels.clear(); trial_launch = false;
   if (!launched_once) coop_wgs_used = 0;
   plan = LaunchPlan{};
   kernel_no = 0;
@@ -772,16 +583,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   }
   HIP_OK(hipEventRecord(ev0, stream));                  // events bracket the sampler kernels only
   if (marginal) {
-    // One chain per lane, every event of the batch in one launch (kernels_marginal.hip); its vectors live in LDS,
-    // [vector][isoform][lane], 64 lanes per workgroup up to 32 isoforms, 32 beyond.
-    int ks = 2;
-    for (const PackedEvent &e : events) ks = std::max(ks, e.K);
-    const int lanes = ks <= 32 ? 64 : 32;
-    KernelArgs ka = a;
-    ka.slot_event = d_slots; ka.n_slots = n; ka.kstride = ks;
-    const long chains = static_cast<long>(n) * p.noChains;
-    if (chains > 0) launch_kernel(fn(&sampler_marginal), static_cast<unsigned>((chains + lanes - 1) / lanes), lanes, marginal_lds_bytes(ks, lanes), stream, ka);
-    last_kernels = "sampler_marginal";
+    launch_marginal(a);
   } else {
     launch_planned(a, k2a);
     if (n_exact > 0) launch_exact(a);
@@ -803,13 +605,15 @@ void miso_batch::plan_sizes() {
   // (knobs.lds_max_kb: a larger cap lets one workgroup per CU hold more chains per wavefront)
   q.lds_max = knobs.lds_max_kb.v * 1024;
   const int il = static_cast<int>(fd.prob.size());
-  q.k2_fp = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
-  q.k2_tab = p.paired ? 2 * fd.prob.size() * 4 : 0;   // per chain: int32[2 x il]
+  K2Half &w = k2[0], &r = k2[1];
+  for (K2Half *h : {&w, &r}) { h->kind = K2Kernel::None; h->G = 0; }
+  r.fp = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
+  r.tab = p.paired ? 2 * fd.prob.size() * 4 : 0;   // per chain: int32[2 x il]
   // paired-end: the first n_k2w slots go to MODE 2 (no drawing read with a non-finite score), the rest to
   // MODE 1; single-end: everything is "the rest".  Both keep the event's score table (2 il int32) per chain in LDS.
   // MODE 2 reads the dense records (device.hpp pe_k2_entries): both tables with 2 il + 2 entries
-  q.k2w_fp = p.paired ? align_up(static_cast<size_t>(pe_k2_entries(il)) * 8, 16) : 0;
-  q.k2w_tab = p.paired ? static_cast<size_t>(pe_k2_entries(il)) * 4 : 0;
+  w.fp = p.paired ? align_up(static_cast<size_t>(pe_k2_entries(il)) * 8, 16) : 0;
+  w.tab = p.paired ? static_cast<size_t>(pe_k2_entries(il)) * 4 : 0;
   q.fp_plain = p.paired ? align_up(fd.prob.size() * 8, 16) : 0;
   // paired-end dense path (pe_dense): byte records, the probability table with its two extra entries, the
   // score table with rows of il + 2
@@ -821,7 +625,7 @@ void miso_batch::plan_sizes() {
   // a whole-gene batch -- a few thousand chains -- would be spread thin over 32 lanes per chain and
   // still leave the GPU half empty).
   q.total_chains = static_cast<long>(n_k2 + n_gen) * p.noChains;   // (the exact mode's events are not the samplers')
-  q.n_kernels = (n_k2 - n_k2w > 0 ? 1 : 0) + (n_k2w > 0 ? 1 : 0) + gen_runs.size();
+  q.n_kernels = (r.count > 0 ? 1 : 0) + (w.count > 0 ? 1 : 0) + gen_runs.size();
   // Lanes per chain, measured: the best split depends on how the batch's wavefronts fill the SIMDs
   // (chains, isoforms, reads, LDS per workgroup), so the first launch of a large single-end batch
   // with more than two isoforms times a few iterations of the rule of thumb's choice and of the next
@@ -846,7 +650,9 @@ template <class F> int miso_batch::fastest(const KernelArgs &a, const std::vecto
     t.M = iters; t.B = iters;
     float ms = 0;
     HIP_OK(hipEventRecord(ev0, stream));
+    trial_launch = true;   // (launch_kernel: not into last_kernels)
     trial(t, g);
+    trial_launch = false;
     HIP_OK(hipEventRecord(ev1, stream));
     HIP_OK(hipEventSynchronize(ev1));
     HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
@@ -873,66 +679,67 @@ LanePlan miso_batch::k2_lanes(const K2Part &pt, const std::vector<int> &nd, cons
                     knobs.k2_target.v, plan.coop_max, pt.coop_budget);
 }
 
-// The lane plan of one part into `pl`, unless `pl` still holds the one made for the same key: the resident workgroups, the
+// The lane plan of one half into `h.plan`, unless it still holds the one made for the same key: the resident workgroups, the
 // chains and the cooperative budget.  A knob the key does not carry (knobs.replan_k2(), the caller's `forced`) plans anew
 // at every launch.  `cost`: the part's cost model, here overridden by knobs.k2_cost and knobs.coop_min_quads.  True when
 // it planned: `nd` then holds the slots' drawing reads, for what the caller plans further.
-bool miso_batch::plan_k2_lanes(const K2Part &pt, bool forced, LaneCost &cost, std::vector<int> &nd, LanePlan &pl, long &pl_key) {
+bool miso_batch::plan_k2_lanes(const K2Part &pt, bool forced, LaneCost &cost, std::vector<int> &nd, K2Half &h) {
   const long key = (static_cast<long>(pt.resident) * 64 + p.noChains) * 256 + pt.coop_budget + (plan.coop_max > 1 ? 0 : 200);
-  if (pl_key == key && !forced && !knobs.replan_k2()) return false;
+  if (h.plan_key == key && !forced && !knobs.replan_k2()) return false;
   double *const c[5] = {&cost.block, &cost.step[1], &cost.step[2], &cost.step[3], &cost.step[4]};
   for (size_t i = 0; i < knobs.k2_cost.size(); i++) *c[i] = knobs.k2_cost[i];
   if (knobs.coop_min_quads.set) cost.coop_min_quads = knobs.coop_min_quads.v;
   nd.resize(pt.count);
   for (int i = 0; i < pt.count; i++) nd[i] = events[h_slots[pt.first + i]].n_draw;
-  pl = k2_lanes(pt, nd, cost);
-  pl_key = key;
+  h.plan = k2_lanes(pt, nd, cost);
+  h.plan_key = key;
   return true;
 }
 
 void miso_batch::plan_k2(const KernelArgs &a) {
   LaunchPlan &q = plan;
+  K2Half &w = k2[0], &r = k2[1];   // MODE 2; the others
   const size_t LDS_MAX = q.lds_max;
   // (only when the batch's wavefronts fit the resident slots once: with several rounds the hardware hands
   // out workgroups as slots free up, heaviest first, and the 4-wavefront workgroups balance better --
   // MISO defaults, 6 chains x 40 000 events at one lane per chain: 374 ms paired, 351 ms unpaired)
   q.k2_pair = !p.paired && !knobs.k2_pair.off();
-  if (n_k2 - n_k2w > 0) {
-    const long chains = static_cast<long>(n_k2 - n_k2w) * p.noChains;
+  if (r.count > 0) {
+    const long chains = static_cast<long>(r.count) * p.noChains;
     const int maxq = p.paired ? (events[k2_first_event()].n_draw + 3) / 4 : (events[k2_first_event()].n_draw + 7) / 8;   // Philox blocks
-    const int max_cpw = p.paired ? std::max<int>(1, static_cast<int>((60 * 1024 - q.k2_fp) / (4 * q.k2_tab))) : 64;
-    if (knobs.lanes_per_chain.set) q.k2_G = knobs.lanes_per_chain.v;
-    else if (tuned_k2_G) q.k2_G = tuned_k2_G;
+    const int max_cpw = p.paired ? std::max<int>(1, static_cast<int>((60 * 1024 - r.fp) / (4 * r.tab))) : 64;
+    if (knobs.lanes_per_chain.set) r.G = knobs.lanes_per_chain.v;
+    else if (tuned_k2_G) r.G = tuned_k2_G;
     else {
-      q.k2_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
+      r.G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
       if (q.tune_runs && chains >= 4096 && knobs.autotune_k2) {   // the rule is the measured optimum
         static const int kG[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32, 64};
-        std::vector<int> cand{q.k2_G};
+        std::vector<int> cand{r.G};
         for (int i = 0; i < 15; i++)
-          if (kG[i] == q.k2_G) {
+          if (kG[i] == r.G) {
             for (int j : {i - 1, i + 1, i + 2})
               if (j >= 0 && j < 15 && 64 / kG[j] <= max_cpw && !(p.paired && (kG[j] & (kG[j] - 1))) &&
                   kG[j] <= std::max(1, maxq))
                 cand.push_back(kG[j]);
           }
-        if (cand.size() > 1) q.k2_G = fastest(a, cand, [&](const KernelArgs &t, int g) { launch_k2(t, g, stream); });
-        tuned_k2_G = q.k2_G;
+        if (cand.size() > 1) r.G = fastest(a, cand, [&](const KernelArgs &t, int g) { launch_k2(t, r, g, stream); });
+        tuned_k2_G = r.G;
       }
     }
   }
-  if (n_k2w > 0) {   // MODE 2: two workgroups per CU may share the LDS (80 KB each)
-    const long chains = static_cast<long>(n_k2w) * p.noChains;
+  if (w.count > 0) {   // MODE 2: two workgroups per CU may share the LDS (80 KB each)
+    const long chains = static_cast<long>(w.count) * p.noChains;
     const int maxq = (events[k2_first_event()].n_draw + 3) / 4;
-    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp);
-    const int max_cpw = static_cast<int>(std::max<long>(1, lds_left / static_cast<long>(4 * q.k2w_tab)));
+    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(w.fp);
+    const int max_cpw = static_cast<int>(std::max<long>(1, lds_left / static_cast<long>(4 * w.tab)));
     if (knobs.lanes_per_chain.set) {
-      q.k2w_G = knobs.lanes_per_chain.v;
-      if (q.k2w_G < 1 || q.k2w_G > 64) MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
-    } else q.k2w_G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
-    while (q.k2w_G < 64 && static_cast<size_t>(64 / q.k2w_G) > static_cast<size_t>(max_cpw)) q.k2w_G *= 2;   // a forced choice never exceeds the LDS
+      w.G = knobs.lanes_per_chain.v;
+      if (w.G < 1 || w.G > 64) MISO_FAIL(MISO_EINVAL, "MISO_LANES_PER_CHAIN must be one of 1-10,12,16,21,32,64");
+    } else w.G = choose_lanes_per_chain(chains, maxq, slots_for(chains), max_cpw);
+    while (w.G < 64 && static_cast<size_t>(64 / w.G) > static_cast<size_t>(max_cpw)) w.G *= 2;   // a forced choice never exceeds the LDS
   }
-  if (q.k2_pair && q.k2_G > 0) {
-    const long waves = (static_cast<long>(n_k2 - n_k2w) * p.noChains + 64 / q.k2_G - 1) / (64 / q.k2_G);
+  if (q.k2_pair && r.G > 0) {
+    const long waves = (static_cast<long>(r.count) * p.noChains + 64 / r.G - 1) / (64 / r.G);
     q.k2_pair = waves <= wave_slots || knobs.k2_pair.set;
   }
   // ---- single-end two-isoform events in one launch with two lane widths (sampler_k2_mix, kernels_k2.hip) ----
@@ -940,7 +747,7 @@ void miso_batch::plan_k2(const KernelArgs &a) {
   // the heaviest events get G + 1 lanes per chain, as many of them as still leave one CU per workgroup.
   // (knobs.k2_mix switches it off, knobs.k2_split forces the number of events of the wide part.)
   {
-    const int count = n_k2 - n_k2w, C = p.noChains, G = q.k2_G;
+    const int count = r.count, C = p.noChains, G = r.G;
     if (!p.paired && q.k2_pair && count > 0 && G >= 1 && G <= 7 && q.n_kernels <= 1 && !knobs.k2_mix.off()) {
       const int cus = wave_slots / 8, cpwA = 64 / (G + 1), cpwB = 64 / G;
       auto blocks = [&](long chains, int cpw) { return static_cast<int>(((chains + cpw - 1) / cpw + 7) / 8); };
@@ -975,8 +782,8 @@ void miso_batch::plan_k2(const KernelArgs &a) {
     const long cap = n_k2 > 0 ? COOP_MAX_WGS * 5 / 8 : COOP_MAX_WGS;
     coop_gen_budget = coop_max > 1 ? static_cast<int>(std::min(want, cap)) : 0;
     const int left = COOP_MAX_WGS - coop_gen_budget;
-    coop_k2w_budget = (n_k2w > 0 && n_k2 - n_k2w > 0) ? left * 2 / 3 : left;
-    coop_k2_budget = n_k2w > 0 ? left - coop_k2w_budget : left;
+    coop_k2w_budget = (w.count > 0 && r.count > 0) ? left * 2 / 3 : left;
+    coop_k2_budget = w.count > 0 ? left - coop_k2w_budget : left;
     if (!p.paired) coop_k2_budget = left;
   }
   q.lane_route = collapsed && !p.paired && n_k2 > 0;   // miso_batch_set_collapsed
@@ -995,70 +802,56 @@ void miso_batch::plan_k2(const KernelArgs &a) {
     if (knobs.lane_ilp.set) q.lane_ilp = knobs.lane_ilp.v != 0;
   }
   const bool multi = !knobs.lanes_per_chain.set && !knobs.k2_multi.off();
+  bool r_multi = false, w_multi = false;   // sampler_k2_multi for the half
   std::vector<int> nd;
-  {
-    const int count = n_k2 - n_k2w;
-    // paired-end events that keep MODE 1 (a drawing read touches a non-finite score): the same, 4-wavefront workgroups,
-    // 4 ... 64 lanes as far as the chains' tables (2 il int32 each) fit the LDS, 256-lane chains
-    const long pe1_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2_fp) - K2_RED_BYTES;
-    const int pe1_cpw = p.paired ? static_cast<int>(std::max<long>(0, pe1_left / static_cast<long>(4 * std::max<size_t>(q.k2_tab, 1)))) : 64;
-    if (p.paired && count > 0 && pe1_cpw >= 1 && multi) {
-      K2Part pt{n_k2w, count, K2_WIDTHS_PE, 5};
-      pt.wide_wpb = pt.wpb = 4; pt.max_cpw = pe1_cpw; pt.coop_budget = coop_k2_budget;
-      pt.resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 4);
-      LaneCost cost = k2_cost_paired();
-      plan_k2_lanes(pt, false, cost, nd, k2_plan, k2_plan_key);
-      q.k2_multi = k2_plan.n_segs > 0;
-    }
-    if (!p.paired && count > 0 && multi) {
-      K2Part pt{n_k2w, count, K2_WIDTHS_SE, 12};
-      pt.wide_wpb = pt.wpb = 8; pt.max_cpw = 64; pt.coop_budget = coop_k2_budget;
-      pt.resident = std::max(1, slots_for(static_cast<long>(count) * p.noChains) / 8);
-      LaneCost cost = k2_cost_single();
-      if (knobs.k2_wpb.set && knobs.k2_wpb.v != 8 && knobs.k2_wpb.v != 4 && knobs.k2_wpb.v != 1) MISO_FAIL(MISO_EINVAL, "MISO_K2_WPB must be 8, 4 or 1");
-      if (plan_k2_lanes(pt, knobs.k2_wpb.set, cost, nd, k2_plan, k2_plan_key)) {
-        // several rounds: smaller workgroups (a workgroup starts when ALL its wavefronts' slots are free; with 8 the
-        // slots of early finishers idle: MISO defaults on 40 000 events 425 ms, with 4: see profiles/r03_k2_multi_ab.txt)
-        const int wpb = knobs.k2_wpb.set ? knobs.k2_wpb.v : (k2_plan.rounds == 1 ? 8 : 4);
-        if (wpb != 8) {
-          pt.wide_wpb = wpb >= 4 ? wpb : 0; pt.wpb = wpb; pt.resident = pt.resident * 8 / wpb;
-          k2_plan = k2_lanes(pt, nd, cost);
-        }
-        k2_pair_grid = 0; k2_pair_wide_blocks = 0;
-        if (wpb == 8) k2_pair_table(nd, cost);
-      }
-      q.k2_multi = k2_plan.n_segs > 0;
-    }
-  }
-  // ---- paired-end two-isoform events of MODE 2, likewise (sampler_k2_multi<2, 4>): 4, 8, ... 64 lanes per chain as far
-  // as the chains' score tables fit the workgroup's LDS, 256 lanes (the workgroup) for the largest events ----
-  if (p.paired && n_k2w > 0 && multi) {
-    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(q.k2w_fp) - K2_RED_BYTES;
-    const int max_cpw = static_cast<int>(std::max<long>(0, lds_left / static_cast<long>(4 * q.k2w_tab)));
-    K2Part pt{0, n_k2w, K2_WIDTHS_PE, 5};
-    pt.wide_wpb = pt.wpb = 4; pt.max_cpw = max_cpw; pt.coop_budget = coop_k2w_budget;
-    pt.resident = std::max(1, slots_for(static_cast<long>(n_k2w) * p.noChains) / 4);
+  // ---- paired-end: both halves likewise (sampler_k2_multi<1, 4>, <2, 4>), 4-wavefront workgroups, 4 ... 64 lanes per chain
+  // as far as the chains' score tables fit the workgroup's LDS, 256 lanes (the workgroup) for the largest events ----
+  for (K2Half *h : {&r, &w}) {
+    if (!p.paired || h->count <= 0 || !multi) continue;
+    const bool mode2 = h == &w;
+    const long lds_left = static_cast<long>(LDS_MAX) - static_cast<long>(h->fp) - K2_RED_BYTES;
+    const int max_cpw = static_cast<int>(std::max<long>(0, lds_left / static_cast<long>(4 * h->tab)));
+    if (max_cpw < 1) continue;
+    K2Part pt{h->first, h->count, K2_WIDTHS_PE, 5};
+    pt.wide_wpb = pt.wpb = 4; pt.max_cpw = max_cpw; pt.coop_budget = mode2 ? coop_k2w_budget : coop_k2_budget;
+    pt.resident = std::max(1, slots_for(static_cast<long>(h->count) * p.noChains) / 4);
     LaneCost cost = k2_cost_paired();
-    if (max_cpw >= 1 && plan_k2_lanes(pt, knobs.k2w_wpb.set, cost, nd, k2w_plan, k2w_plan_key)) {
+    if (plan_k2_lanes(pt, mode2 && knobs.k2w_wpb.set, cost, nd, *h) && mode2) {
       // The widest a chain can be is its workgroup: 256 lanes with 4 wavefronts, 512 with 8 (one workgroup per CU,
       // twice the LDS each: the same chains per CU).  8-wavefront workgroups lose ~19 % when the launch runs in
       // several rounds (a workgroup starts when ALL its slots are free), so they are taken only when the largest
       // events would otherwise outlast the launch (hg19-like read counts: 218 ms -> 175 ms; uniform: 217 ms -> 259 ms, not taken; profiles/r03_pe_k2_wpb.txt).
       pt.wide_wpb = pt.wpb = 8; pt.resident = std::max(1, pt.resident / 2);
       const LanePlan p8 = k2_lanes(pt, nd, cost);
-      if (knobs.k2w_wpb.set ? knobs.k2w_wpb.v == 8 : 1.2 * p8.est < k2w_plan.est) k2w_plan = p8;
+      if (knobs.k2w_wpb.set ? knobs.k2w_wpb.v == 8 : 1.2 * p8.est < w.plan.est) w.plan = p8;
     }
-    q.k2w_multi = max_cpw >= 1 && k2w_plan.n_segs > 0;
-    if (q.k2w_multi) {
-      int cpw = 1;
-      for (int i = 0; i < k2w_plan.n_segs; i++)
-        if (k2w_plan.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / k2w_plan.seg_lanes[i]);
-      q.k2w_multi_lds = align_up(q.k2w_fp + static_cast<size_t>(k2w_plan.wpb) * cpw * q.k2w_tab, 16);
+    (mode2 ? w_multi : r_multi) = h->plan.n_segs > 0;
+  }
+  if (!p.paired && r.count > 0 && multi) {
+    K2Part pt{r.first, r.count, K2_WIDTHS_SE, 12};
+    pt.wide_wpb = pt.wpb = 8; pt.max_cpw = 64; pt.coop_budget = coop_k2_budget;
+    pt.resident = std::max(1, slots_for(static_cast<long>(r.count) * p.noChains) / 8);
+    LaneCost cost = k2_cost_single();
+    if (knobs.k2_wpb.set && knobs.k2_wpb.v != 8 && knobs.k2_wpb.v != 4 && knobs.k2_wpb.v != 1) MISO_FAIL(MISO_EINVAL, "MISO_K2_WPB must be 8, 4 or 1");
+    if (plan_k2_lanes(pt, knobs.k2_wpb.set, cost, nd, r)) {
+      // several rounds: smaller workgroups (a workgroup starts when ALL its wavefronts' slots are free; with 8 the
+      // slots of early finishers idle: MISO defaults on 40 000 events 425 ms, with 4: see profiles/r03_k2_multi_ab.txt)
+      const int wpb = knobs.k2_wpb.set ? knobs.k2_wpb.v : (r.plan.rounds == 1 ? 8 : 4);
+      if (wpb != 8) {
+        pt.wide_wpb = wpb >= 4 ? wpb : 0; pt.wpb = wpb; pt.resident = pt.resident * 8 / wpb;
+        r.plan = k2_lanes(pt, nd, cost);
+      }
+      k2_pair_grid = 0; k2_pair_wide_blocks = 0;
+      if (wpb == 8) k2_pair_table(nd, cost);
     }
+    r_multi = r.plan.n_segs > 0;
   }
   // the several-rounds single-end plan has runs of one and two lanes per chain only: the kernel of three wavefronts per SIMD (kernels_k2m.inl)
-  q.k2_narrow = q.k2_multi && !p.paired && k2_plan.wpb == 4 && k2_plan.n_segs > 0 && !knobs.k2_no_narrow;
-  for (int i = 0; i < k2_plan.n_segs && q.k2_narrow; i++) q.k2_narrow = k2_plan.seg_lanes[i] <= 2;
+  q.k2_narrow = r_multi && !p.paired && r.plan.wpb == 4 && r.plan.n_segs > 0 && !knobs.k2_no_narrow;
+  for (int i = 0; i < r.plan.n_segs && q.k2_narrow; i++) q.k2_narrow = r.plan.seg_lanes[i] <= 2;
+  // the halves' kernels: decided here, read by the launch, the names and the statistics (launch.hip)
+  if (w.count > 0) w.kind = w_multi ? K2Kernel::Multi : K2Kernel::Single;
+  if (r.count > 0) r.kind = q.lane_route ? K2Kernel::Lane : r_multi ? K2Kernel::Multi : q.k2_mix > 0 ? K2Kernel::Mix : K2Kernel::Single;
 }
 
 // One round, 8 wavefronts per workgroup: wavefronts w and w + 4 of a workgroup share a SIMD.  Pair the launch's
@@ -1070,21 +863,22 @@ void miso_batch::plan_k2(const KernelArgs &a) {
 // 1000 reads each (4 runs) 99.7 -> 100.8 ms, 3000 reads 244.6 -> 250.0 ms (few runs: their sums are close already,
 // and the kernel with a body per run AND per wavefront is larger): used from seven runs on (knobs.k2_global_pair).
 void miso_batch::k2_pair_table(const std::vector<int> &nd, const LaneCost &cost) {
+  const LanePlan &pl = k2[1].plan;
   const Opt<int> &gp = knobs.k2_global_pair;
-  if (!(k2_plan.n_segs > 0 && k2_plan.rounds == 1 && (gp.set ? gp.v != 0 : k2_plan.n_segs >= 7))) return;
+  if (!(pl.n_segs > 0 && pl.rounds == 1 && (gp.set ? gp.v != 0 : pl.n_segs >= 7))) return;
   struct W { double cost; int32_t code; };
   std::vector<W> ws;
   bool ok = true, seen_narrow = false;
-  for (int sg = 0; sg < k2_plan.n_segs && ok; sg++) {
-    const int G = k2_plan.seg_lanes[sg];
-    if (G == K2_WIDE) { ok = !seen_narrow; k2_pair_wide_blocks = k2_plan.seg_block[sg + 1]; continue; }   // (wide runs come first)
+  for (int sg = 0; sg < pl.n_segs && ok; sg++) {
+    const int G = pl.seg_lanes[sg];
+    if (G == K2_WIDE) { ok = !seen_narrow; k2_pair_wide_blocks = pl.seg_block[sg + 1]; continue; }   // (wide runs come first)
     seen_narrow = true;
     const int cpw = 64 / G;
-    const long chains = static_cast<long>(k2_plan.seg_slot[sg + 1] - k2_plan.seg_slot[sg]) * p.noChains;
+    const long chains = static_cast<long>(pl.seg_slot[sg + 1] - pl.seg_slot[sg]) * p.noChains;
     const long waves = (chains + cpw - 1) / cpw;
     ok = waves < (1L << 20) && sg < 2048;
     for (long w = 0; w < waves && ok; w++) {
-      const int first = nd[k2_plan.seg_slot[sg] + static_cast<int>((w * cpw) / p.noChains)];   // the wavefront's longest chain
+      const int first = nd[pl.seg_slot[sg] + static_cast<int>((w * cpw) / p.noChains)];   // the wavefront's longest chain
       ws.push_back(W{cost.wave_step(G, first), static_cast<int32_t>(sg << 20 | static_cast<int32_t>(w))});
     }
   }
@@ -1100,115 +894,6 @@ void miso_batch::k2_pair_table(const std::vector<int> &nd, const LaneCost &cost)
   put(k2_pair_tab, tab);
 }
 
-void miso_batch::launch_k2(KernelArgs ka, int G, hipStream_t st, bool wpart) {
-  const int first = wpart ? 0 : n_k2w, count = wpart ? n_k2w : n_k2 - n_k2w;
-  const long chains = static_cast<long>(count) * p.noChains;
-  if (chains <= 0) return;
-  ka.slot_event = d_slots + first; ka.n_slots = count;
-  const int cpw = 64 / std::max(G, 1);
-  const long waves = (chains + cpw - 1) / cpw;
-  // single-end: workgroups of 8 wavefronts = one CU's resident slots; the two wavefronts of a SIMD
-  // take a heavy and a light group of chains (sampler_k2's WPB = 8); knobs.k2_pair off: the 4-wavefront
-  // workgroups in slot order (round-1 behaviour).
-  const bool pair = plan.k2_pair;
-  ka.pair_waves = pair ? 1 : 0;
-  const unsigned grid = static_cast<unsigned>(pair ? (waves + 7) / 8 : (waves + 3) / 4);
-  const size_t k2_lds = (wpart ? plan.k2w_fp : plan.k2_fp) + 4 * static_cast<size_t>(cpw) * (wpart ? plan.k2w_tab : plan.k2_tab);
-  if (k2_lds > 160 * 1024) MISO_FAIL(MISO_UNIMPLEMENTED, "Fragment-length distribution too wide for the two-isoform paired-end kernel");
-  const void *f = p.paired ? (wpart ? k2_kernel<2, 4>(G) : k2_kernel<1, 4>(G)) : (pair ? k2_kernel<0, 8>(G) : k2_kernel<0, 4>(G));
-  launch_kernel(f, grid, !p.paired && pair ? 512 : 256, k2_lds, st, ka);
-}
-
-void miso_batch::launch_k2_mix(KernelArgs ka, hipStream_t st) {
-  const int first = n_k2w, count = n_k2 - n_k2w, C = p.noChains, G = plan.k2_G, cpwB = 64 / G;
-  ka.slot_event = d_slots + first; ka.n_slots = count;
-  ka.pair_waves = 1; ka.mix_slots = plan.k2_mix; ka.mix_blocks = plan.k2_mix_blocks;
-  const long wavesB = (static_cast<long>(count - plan.k2_mix) * C + cpwB - 1) / cpwB;
-  launch_kernel(k2_mix_kernel(G), static_cast<unsigned>(plan.k2_mix_blocks + (wavesB + 7) / 8), 512, 0, st, ka);
-}
-
-// which chain every workgroup of a plan's workgroup-wide run works on (coop.hpp); nothing to do when every chain
-// has its workgroup to itself
-void miso_batch::k2_coop(KernelArgs &ka, const LanePlan &pl, CoopTable &cc, hipStream_t st) {
-  ka.coop_tab = nullptr; ka.coop_mem = nullptr;
-  if (pl.n_segs == 0 || pl.seg_lanes[0] != K2_WIDE) return;
-  bool any = false;
-  for (int m : pl.wide_wgs) any |= m > 1;
-  if (!any) return;
-  const long key = pl.seg_block[1] * 131 + static_cast<long>(pl.wide_wgs.size());
-  if (cc.tab.key != key || !cc.tab.d) {
-    std::vector<int32_t> tab;
-    cc.chains = 0;
-    for (size_t e = 0; e < pl.wide_wgs.size(); e++)
-      for (int c = 0; c < p.noChains; c++) {
-        const int m = pl.wide_wgs[e];
-        for (int r = 0; r < m; r++) { tab.push_back(static_cast<int32_t>(e * p.noChains + c)); tab.push_back(r); tab.push_back(m); tab.push_back(m > 1 ? cc.chains : 0); }
-        if (m > 1) cc.chains++;
-      }
-    if (static_cast<int>(tab.size() / 4) != pl.seg_block[1]) MISO_FAIL(MISO_EINTERNAL, "lane plan and cooperative table disagree");
-    put(cc.tab, tab);
-    put(cc.mem, {}, static_cast<size_t>(std::max(1, cc.chains)) * COOP_WORDS);
-    cc.tab.key = key;
-  }
-  HIP_OK(hipMemsetAsync(cc.mem.d, 0, std::max(1, cc.chains) * COOP_WORDS * sizeof(uint32_t), st));
-  ka.coop_tab = cc.tab.d; ka.coop_mem = cc.mem.d;
-}
-
-void miso_batch::launch_k2_multi(KernelArgs ka, hipStream_t st, bool wpart) {
-  const LanePlan &pl = wpart ? k2w_plan : k2_plan;
-  k2_coop(ka, pl, wpart ? k2w_coop : k2_coop_se, st);
-  ka.slot_event = d_slots + (wpart ? 0 : n_k2w); ka.n_slots = wpart ? n_k2w : n_k2 - n_k2w;
-  ka.n_segs = pl.n_segs;
-  for (int i = 0; i <= pl.n_segs; i++) { ka.seg_block[i] = pl.seg_block[i]; ka.seg_slot[i] = pl.seg_slot[i]; }
-  for (int i = 0; i < pl.n_segs; i++) ka.seg_lanes[i] = pl.seg_lanes[i];
-  unsigned grid = static_cast<unsigned>(pl.seg_block[pl.n_segs]);
-  if (wpart) {   // MODE 2
-    ka.pair_waves = 0;
-    ka.red_off = static_cast<int32_t>(plan.k2w_multi_lds);
-    launch_kernel(k2_multi_kernel(2, pl.wpb, false), grid, pl.wpb == 8 ? 512 : 256, plan.k2w_multi_lds + K2_RED_BYTES, st, ka);
-    return;
-  }
-  ka.pair_waves = (pl.rounds == 1 && pl.wpb == 8) ? 1 : 0;
-  ka.red_off = 0;
-  if (!p.paired && pl.wpb == 8 && k2_pair_grid > 0 && !k2_pair_tab.host.empty()) {   // wavefronts paired across the runs
-    ka.wave_tab = k2_pair_tab.d; ka.mix_blocks = k2_pair_wide_blocks; ka.pair_waves = 0;
-    grid = static_cast<unsigned>(k2_pair_grid);
-  }
-  if (p.paired) {   // MODE 1
-    int cpw = 1;
-    for (int i = 0; i < pl.n_segs; i++) if (pl.seg_lanes[i] != K2_WIDE) cpw = std::max(cpw, 64 / pl.seg_lanes[i]);
-    const size_t tabs = align_up(plan.k2_fp + 4 * static_cast<size_t>(cpw) * plan.k2_tab, 16);
-    ka.pair_waves = 0;
-    ka.red_off = static_cast<int32_t>(tabs);
-    launch_kernel(k2_multi_kernel(1, 4, false), grid, 256, tabs + K2_RED_BYTES, st, ka);
-    return;
-  }
-  // the whole launch resident at once: the two wavefronts of a SIMD keep step (kernels_k2.inl k2_balance)
-  if (pl.wpb == 8 && pl.rounds == 1) ka.balance = knobs.k2_balance.off() ? 0 : 1;
-  const int wpb = pl.wpb == 8 || pl.wpb == 4 ? pl.wpb : 1;
-  launch_kernel(k2_multi_kernel(0, wpb, plan.k2_narrow), grid, 64 * wpb, wpb == 1 ? 0 : K2_RED_BYTES, st, ka);
-}
-
-// collapsed single-end batch: one chain per lane, no read loop (kernels_lane.hip)
-void miso_batch::launch_lane(KernelArgs ka, hipStream_t st) {
-  ka.slot_event = d_slots; ka.n_slots = n_k2; ka.pair_waves = 0;
-  ka.logfact = logfact.d; ka.tstride = static_cast<int32_t>(logfact.host.size());   // (tstride: the table's entries, for sampler_lane_ilp's LDS copy)
-  const long chains = static_cast<long>(n_k2) * p.noChains;
-  const int G = plan.lane_G;
-  unsigned grid = static_cast<unsigned>(((chains + 64 / G - 1) / (64 / G) + 3) / 4);
-  if (G == 1) {
-    grid = static_cast<unsigned>((chains + 255) / 256);
-    // fewer wavefronts than SIMDs (or than two per SIMD): spread the chains over all of them (kernels_lane.hip lane_body)
-    const long simds = wave_slots / 2, waves = (chains + 63) / 64;
-    const int per_simd = knobs.lane_spread.v;
-    if (plan.lane_ilp && per_simd > 0 && waves < simds * per_simd && chains >= 64) {
-      const long target = simds * per_simd;
-      const int cpw = static_cast<int>((chains + target - 1) / target);
-      if (cpw >= 8 && cpw < 64) { ka.pair_waves = cpw; grid = static_cast<unsigned>(((chains + cpw - 1) / cpw + 3) / 4); }
-    }
-  }
-  launch_kernel(lane_kernel(G, plan.lane_ilp), grid, 256, 0, st, ka);
-}
 
 // ---- more than two isoforms: sampler_grp<G, PE, KC> per isoform-count class ----
 int miso_batch::fp_rows(const GenRun &run) const { return (p.paired && plan.dense_env && run.dense) ? 1 : 0; }
@@ -1242,237 +927,6 @@ miso_batch::GenRun miso_batch::joined_run(size_t r0, size_t r1) const {
   return m;
 }
 
-// Workgroup-wide chains of a run: which chain every workgroup works on (coop.hpp), built once per batch; returns the
-// number of workgroups.
-unsigned miso_batch::wide_setup(GenRun &run, long chains, hipStream_t st) {
-  // Workgroups per chain: what upload() derived from the gene's share of the batch's work (coop_n), at most
-  // COOP_MAX_N, all cooperative workgroups of the batch together at most COOP_MAX_WGS (coop.hpp: they must all be
-  // resident at once).  knobs.no_coop: one workgroup per chain; knobs.coop_draws: one per n drawing pairs.
-  CoopTable &cc = run.coop;
-  if (!cc.tab.d) {
-    std::vector<int32_t> tab;
-    cc.chains = 0;
-    const bool coop_on = coop_enabled();
-    const int per_wg = knobs.coop_draws.v;
-    for (long c = 0; c < chains; c++) {
-      const int ev_i = h_slots[n_k2 + run.first + c / p.noChains];
-      const int nd = events[ev_i].n_draw;
-      int nw = !coop_on ? 1 : (knobs.coop_draws.set ? std::min(COOP_MAX_N, std::max(1, (nd + per_wg - 1) / per_wg)) : coop_n[ev_i]);
-      if (nw > 1 && coop_wgs_used + nw > coop_gen_budget) nw = std::max(1, coop_gen_budget - coop_wgs_used);
-      if (nw > 1) coop_wgs_used += nw;
-      for (int r = 0; r < nw; r++) {
-        tab.push_back(static_cast<int32_t>(c)); tab.push_back(r); tab.push_back(nw);
-        tab.push_back(nw > 1 ? cc.chains : 0);
-      }
-      if (nw > 1) cc.chains++;
-    }
-    if (knobs.timing) {
-      std::fprintf(stderr, "[miso] wide run kc=%d: %ld chains on %zu workgroups (%d on several:", run.kc, chains, tab.size() / 4, cc.chains);
-      for (size_t i = 0; i < tab.size(); i += 4)
-        if (tab[i + 1] == 0 && tab[i + 2] > 1)
-          std::fprintf(stderr, " %d x %d draws K=%d", tab[i + 2], events[h_slots[n_k2 + run.first + tab[i] / p.noChains]].n_draw,
-                       events[h_slots[n_k2 + run.first + tab[i] / p.noChains]].K);
-      std::fprintf(stderr, ")\n");
-    }
-    put(cc.tab, tab);
-    put(cc.mem, {}, static_cast<size_t>(std::max(1, cc.chains)) * COOP_WORDS);
-  }
-  HIP_OK(hipMemsetAsync(cc.mem.d, 0, std::max(1, cc.chains) * COOP_WORDS * sizeof(uint32_t), st));
-  return static_cast<unsigned>(cc.tab.host.size() / 4);
-}
-
-void miso_batch::launch_grp(KernelArgs ka, GenRun &run, const GrpShape &sh, int G, hipStream_t st) {
-  const long chains = static_cast<long>(run.count) * p.noChains;
-  ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count;
-  ka.kstride = run.kmax; ka.cstride = sh.qs; ka.tstride = sh.ts;
-  const bool wave_kernel = G == 64 && !run.wide && !(run.wave64 && fp_rows(run));   // sampler_wave, not sampler_grp<64, ..>
-  ka.pe_dense = wave_kernel ? 0 : fp_rows(run);
-  const size_t fp_bytes = wave_kernel ? plan.fp_plain : fp_bytes_of(run);
-  if (run.wide) {   // one chain per workgroup: four slices (one per wavefront) + the reduction scratch behind them
-    ka.pe_dense = fp_rows(run);
-    if (!ka.pe_dense) MISO_FAIL(MISO_EINTERNAL, "workgroup-wide paired-end chains need the dense records");
-    const size_t lds0 = align_up(fp_bytes + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, sh.ts)), 16);
-    ka.red_off = static_cast<int32_t>(lds0);
-    const unsigned grid = wide_setup(run, chains, st);
-    ka.coop_tab = run.coop.tab.d; ka.coop_mem = run.coop.mem.d;
-    launch_kernel(grp_kc<64, true, true>(run.kc), grid, 256, lds0 + 96, st, ka);
-  } else if (G == 64 && !wave_kernel) {   // a wavefront per chain, dense records (size bucket between 32 lanes and a workgroup)
-    const size_t lds = fp_bytes + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, sh.qs, sh.ts));
-    launch_kernel(grp_kc<64, true>(run.kc), static_cast<unsigned>((chains + 3) / 4), 256, lds, st, ka);
-  } else if (G == 64 && run.kc > 64) {   // 65 ... MISO_MAX_ISOFORMS isoforms: one wavefront = one workgroup per chain, vectors in LDS (kernels_big.hip)
-    const size_t lds = fp_bytes + static_cast<size_t>(run.kmax) * (11 * sizeof(double) + 2 * sizeof(int));
-    launch_kernel(p.paired ? fn(&sampler_big<true>) : fn(&sampler_big<false>), static_cast<unsigned>(chains), 64, lds, st, ka);
-  } else if (G == 64) {
-    const size_t lds = fp_bytes + 4 * 64 * sizeof(int);
-    launch_kernel(p.paired ? fn(&sampler_wave<true>) : fn(&sampler_wave<false>), static_cast<unsigned>((chains + 3) / 4), 256, lds, st, ka);
-  } else {
-    const int cpw = 64 / G;
-    const unsigned grid = static_cast<unsigned>(((chains + cpw - 1) / cpw + 3) / 4);
-    const size_t lds = fp_bytes + 4 * static_cast<size_t>(cpw) * grp_slice_bytes(run.kmax, sh.qs, sh.ts);
-    launch_kernel(grp_kernel(G, p.paired, run.kc), grid, 256, lds, st, ka);
-  }
-}
-
-// Which chains a wavefront of sampler_flat owns (kernels_flat.inl: a.wave_tab).  Uniform batches: `nc` consecutive
-// chains each.  When the batch's events differ widely in size -- the heaviest wavefront of the uniform rule would
-// carry more than twice the average wavefront's work units -- the wavefronts are packed by UNITS instead: as many
-// consecutive chains (at most nc_max: the LDS) as make about the average wavefront's units, a chain of several
-// times that alone in a WORKGROUP (FLAT_WIDE: 256 lanes), workgroups ordered heaviest first (the hardware starts
-// them in index order); knobs.flat_pack: never / always.
-// How many units per wavefront: as many as nc_max average chains have -- the scalar step costs a wavefront the same
-// for 2 chains and for 13, so fewer, fuller wavefronts win (hg19-like read counts, 40 000 events, K = 5: 497 ms at 8
-// average chains per wavefront, 425 ms at 13+) -- unless that leaves the device part empty: fewer wavefronts than
-// resident slots, or a second round that is less than half full (K = 3: 3349 wavefronts on 3072 slots 286 ms,
-// 5704 wavefronts 270 ms); then the wavefront count goes to 0.95 x one or two rounds
-// (profiles/r03_flat_pack_sweep.txt).  A forced knobs.flat_nc sets the average chains per wavefront instead.
-void miso_batch::flat_waves(GenRun &run, int nc, int nc_max_u, long resident_u, int nc_max_p, long resident_p) {
-  const long chains = static_cast<long>(run.count) * p.noChains;
-  const int C = p.noChains;
-  const Opt<int> &fpack = knobs.flat_pack;
-  const long ov_pct = knobs.flat_pack_ov.v;   // (per cent of the rule below)
-  const long key = (((static_cast<long>(nc) * 4 + (fpack.set ? 1 + (fpack.v != 0) : 0)) * 128 + nc_max_u) * 128 + nc_max_p) * 1024 + (knobs.flat_pack_ov.set ? 1 + ov_pct % 1000 : 0);
-  if (run.wave_tab.key == key && run.wave_tab.d) return;
-  // (round 5) what a chain costs its wavefront, in work units: its units + the scalar step and thresholds, which do not
-  // depend on the reads.  Measured per chain-iteration at eight / five chains per wavefront (profiles/r05_flat_chunks.txt):
-  // K = 5 238 VALU against 1.33 per unit, K = 10 641 against 1.96, i.e. about 30 K + 25 units -- but the wavefronts this
-  // matters for carry 14 - 18 small chains, whose flat passes and leader sections are shared by twice as many chains:
-  // 16 K + 14.  Swept on hg19-like read counts at 25 ... 300 % of the first figure: K = 3 / 4 / 6 / 8 best at 50 % (208 /
-  // 152 / 107 / 80 k events/s against 153 / 144 / 97 / 74 k at 100 %), K = 5 / 12 at 100 % (122 / 45 k against 114 / 43 k);
-  // by units alone: 151 / 112 / 55 k at K = 3 / 5 / 10.
-  auto units_of = [&](long c) {
-    const PackedEvent &e = events[h_slots[n_k2 + run.first + c / C]];
-    return static_cast<long>(e.n_units) + (16L * e.K + 14) * ov_pct / 100;
-  };
-  long total = 0, head = 0;
-  for (long c = 0; c < chains; c++) { const long u = units_of(c); total += u; if (c < nc) head += u; }
-  long heaviest = head;   // the list is ordered by isoforms first: look at every wavefront of the uniform rule
-  for (long c = 0, sum = 0; c < chains; c++) {
-    sum += units_of(c);
-    if ((c + 1) % nc == 0 || c + 1 == chains) { heaviest = std::max(heaviest, sum); sum = 0; }
-  }
-  const double mean_wave = static_cast<double>(total) * nc / std::max<long>(1, chains);
-  const bool pack = fpack.set ? fpack.v != 0 : (chains > nc && static_cast<double>(heaviest) > 2.0 * mean_wave);
-  struct W { int32_t first, n; long units; };
-  std::vector<W> waves, wides;
-  if (!pack) {
-    for (long c = 0; c < chains; c += nc) waves.push_back(W{static_cast<int32_t>(c), static_cast<int32_t>(std::min<long>(nc, chains - c)), 0});
-    run.wave_nc = nc;
-  } else {
-    // (packed launches have their own sizing: launch_flat)
-    const int nc_max = nc_max_p; const long resident = resident_p;
-    const int cap = std::min(nc_max, 255);
-    int most = 1;
-    auto pack_with = [&](double U) {
-      waves.clear(); wides.clear(); most = 1;
-      const double wide_min = std::max(3.0 * U, 2048.0);
-      for (long c = 0; c < chains;) {
-        const long u = units_of(c);
-        if (static_cast<double>(u) >= wide_min) { wides.push_back(W{static_cast<int32_t>(c), 1, u}); c++; continue; }
-        W w{static_cast<int32_t>(c), 0, 0};
-        while (c < chains && w.n < cap) {
-          const long v = units_of(c);
-          if (static_cast<double>(v) >= wide_min || (w.n > 0 && static_cast<double>(w.units + v) > 1.05 * U)) break;
-          w.units += v; w.n++; c++;
-        }
-        most = std::max(most, static_cast<int>(w.n));
-        waves.push_back(w);
-      }
-      return static_cast<long>(waves.size() + 4 * wides.size());
-    };
-    const double per_chain = static_cast<double>(total) / std::max<long>(1, chains);
-    const bool forced = knobs.flat_nc.set;
-    const long n_waves = pack_with(std::max(64.0, per_chain * (forced ? nc : cap)));
-    if (!forced && n_waves < 3 * resident / 2) {
-      // (round 6) ... and TWO rounds are aimed at from further below than one: the second round's workgroups start as the
-      // first round's end, staggered, and a count within a few per cent of two full rounds runs into a third (hg19-like read
-      // counts, K = 5, 2048 resident wavefronts: 4029 wavefronts 71.7 ms, 3793 64.6 ms, 3541 66.2 ms, 2956 -- the fullest
-      // packing -- 67.7 ms; profiles/r06_flat_pack_rounds.txt): knobs.flat_rounds_frac.
-      const bool two = n_waves > resident;
-      const double frac2 = knobs.flat_rounds_frac.v;
-      const double want = (two ? frac2 : 0.95) * static_cast<double>(two ? 2 * resident : resident);
-      if (static_cast<double>(n_waves) < want) {
-        // (round 5) ... and not a few wavefronts MORE than the round(s): the packing's bound is a target, the count it
-        // makes lands some per cent off, and 3110 wavefronts on 3072 slots cost a second round for 38 of them
-        // (K = 3, hg19-like read counts: 154 k events/s there, 212 k at 2960; profiles/r05_flat_chunks.txt)
-        const long target = two ? static_cast<long>((frac2 + 0.04) * 2.0 * static_cast<double>(resident)) : resident;
-        double U2 = std::max(64.0, static_cast<double>(total) / want);
-        long n2 = pack_with(U2);
-        for (int it = 0; it < 8 && n2 > target; it++) {
-          const long before = n2;
-          U2 *= static_cast<double>(n2) / (0.97 * static_cast<double>(target));
-          n2 = pack_with(U2);
-          if (n2 >= before) break;   // the chains per wavefront are at the LDS's limit: fuller wavefronts are not to be had
-        }
-      }
-    }
-    if (knobs.timing)
-      std::fprintf(stderr, "[flat_waves] kc %d chains %ld cost/chain %.1f cap %d resident %ld first pack %ld waves -> %zu waves + %zu wide, most chains %d\n",
-                   run.kc, chains, per_chain, cap, resident, n_waves, waves.size(), wides.size(), most);
-    std::stable_sort(wides.begin(), wides.end(), [](const W &x, const W &y) { return x.units > y.units; });
-    std::stable_sort(waves.begin(), waves.end(), [](const W &x, const W &y) { return x.units > y.units; });
-    run.wave_nc = most;
-  }
-  std::vector<int32_t> tab;
-  for (const W &w : wides) for (int i = 0; i < 4; i++) { tab.push_back(w.first); tab.push_back(1 | FLAT_WIDE); }
-  for (const W &w : waves) { tab.push_back(w.first); tab.push_back(w.n); }
-  while ((tab.size() / 2) % 4) { tab.push_back(0); tab.push_back(0); }   // padding wavefronts
-  run.wave_wide = static_cast<int>(wides.size());
-  run.wave_packed = pack;
-  put(run.wave_tab, tab, 2);
-  run.wave_tab.key = key;
-}
-
-// Workgroups per CU a run of sampler_flat is sized for: kernels_flat.inl's register budgets -- 3 up to four isoforms and for
-// nine to twelve (measured round 4, profiles/r04_occupancy.txt), 2 otherwise (five to eight isoforms: the kernel allows 3,
-// sizing for 3 gained nothing) -- unless knobs.flat_wgs says otherwise.
-int miso_batch::flat_wgs(int kc) const { return knobs.flat_wgs.set ? knobs.flat_wgs.v : flat_wgs_for(kc); }
-
-void miso_batch::launch_flat(KernelArgs ka, size_t ri, hipStream_t st) {
-  GenRun &run = gen_runs[ri];
-  const int nc = plan.runs[ri].flat_nc, nc_max = plan.runs[ri].flat_nc_max;
-  {
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    const int wgs = flat_wgs(run.kc);
-    // Five to eight isoforms: the kernel's registers allow three workgroups per CU; launches of like-sized events are sized for
-    // two (fuller wavefronts: K = 6 312 against 333 ms, K = 7 347 / 366), launches packed by cost for three -- more, smaller
-    // wavefronts level the heavy tail better than fuller ones amortise the scalar step (hg19-like read counts, 40 000 events:
-    // K = 5 276 -> 252 ms, K = 6 332 -> 278, K = 7 379 -> 339, K = 8 415 -> 393; profiles/r06_flat_licm.txt)
-    int wgs_p = wgs, nc_max_p = nc_max;
-    if (run.kc == 8 && !knobs.flat_wgs.set && !knobs.lds_max_kb.set && !knobs.flat_pack_wgs2) {
-      wgs_p = 3;
-      const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
-      nc_max_p = std::max(1, std::min<int>(64, static_cast<int>(160 * 1024 / (4 * wgs_p) - 64) / slice));
-    }
-    flat_waves(run, nc, nc_max, std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs / 2),
-               nc_max_p, std::max<long>(1, static_cast<long>(slots_for(chains)) * wgs_p / 2));
-  }
-  ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count;
-  ka.kstride = run.kmax; ka.cstride = std::max(run.maxcls, 1); ka.tstride = 0; ka.nc = run.wave_nc;
-  ka.wave_tab = run.wave_tab.d;
-  // the descriptor read loop from four isoforms on (three: the walking loop is 2 % faster -- two thresholds per unit,
-  // little to save) and whenever a chain owns a whole workgroup
-  ka.flat_desc = ((!knobs.flat_no_desc && run.kmax >= 4) || run.wave_wide > 0) ? 1 : 0;
-  // Thresholds only for the chains whose psi changed (kernels_flat.inl): the pass is one lane per (chain, class) and the
-  // Metropolis-Hastings step rejects 45 - 65 % of the proposals, but numbering the chains that accepted costs every lane
-  // a few instructions -- it pays where the thresholds weigh enough: from six isoforms on (K = 6 ... 12: + 4.5 ... 6.4 %)
-  // and for small events (hg19-like read counts at K = 5: + 5.5 %; 1000 reads per event at K = 3 ... 5: - 1 ... 2 %,
-  // profiles/r04_occupancy.txt); knobs.flat_thr_skip: never / always.
-  {
-    double units = 0;
-    for (int j = 0; j < run.count; j++) units += events[h_slots[n_k2 + run.first + j]].n_units;
-    ka.flat_thr_skip = knobs.flat_thr_skip.set ? (knobs.flat_thr_skip.v != 0) : (run.kmax >= 6 || units < 150.0 * run.count);
-  }
-  const unsigned grid = static_cast<unsigned>(run.wave_tab.host.size() / 8);
-  const size_t lds = 4 * static_cast<size_t>(run.wave_nc) * flat_layout(ka.kstride, ka.cstride).bytes;
-  // Priority by progress (device.hpp prio_by_progress) when the launch takes several rounds of like-sized wavefronts:
-  // 40 000 events x 1000 reads, K = 5 348.0 -> 334.4 ms, K = 10 649.4 -> 631.4 ms, same box; wavefronts packed by cost
-  // (hg19-like read counts) lose 1 % and keep the arbiter's own order; so do the paired-end and the two-isoform kernels
-  // (+ 0.5 ... 4 %: profiles/r06_prio_by_progress.txt); knobs.prio_quartiles set: never here / everywhere (launch()).
-  if (!knobs.prio_quartiles.set && !run.wave_packed && run.wave_wide == 0 &&
-      static_cast<long>(grid) * 4 > static_cast<long>(slots_for(static_cast<long>(run.count) * p.noChains)) * flat_wgs_for(run.kc) / 2)
-    ka.balance = 2;
-  launch_kernel(flat_kernel(run.kc, plan.runs[ri].flat_ks, plan.runs[ri].flat_uni), grid, 256, lds, st, ka);
-}
 
 // ---- the general runs: sampler_lane_k, sampler_flat or sampler_grp, and the lanes per chain ----
 void miso_batch::plan_runs(const KernelArgs &a) {
@@ -1488,11 +942,18 @@ void miso_batch::plan_runs(const KernelArgs &a) {
   // (tests/test_gpu_collapsed.py).
   if (collapsed && collapsed_level >= 2 && !p.paired && n_gen > 0)
     for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-      q.runs[ri].lane = !(gen_runs[ri].nocls || gen_runs[ri].kc >= 64);
-      q.lane_gen |= q.runs[ri].lane;
+      if (gen_runs[ri].nocls || gen_runs[ri].kc >= 64) continue;
+      q.runs[ri].kind = q.runs[ri].layout = RunKernel::LaneK;
+      q.lane_gen = true;
     }
   for (size_t ri = 0; ri < gen_runs.size(); ri++) plan_flat(ri);
   for (size_t ri = 0; ri < gen_runs.size(); ri++) plan_grp(ri, a);
+  // the runs' own kernels: decided here, read by the launch, the names and the statistics (launch.hip); group_runs may
+  // still put a run into a launch of several
+  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
+    LaunchPlan::Run &r = q.runs[ri];
+    if (!r.lane()) r.kind = r.layout = run_kernel(gen_runs[ri], r.G, r.flat_nc > 0, q.dense_env, p.paired != 0);
+  }
 }
 
 // single-end runs whose events all have a class table go to sampler_flat (kernels_flat.inl): NC chains
@@ -1508,7 +969,7 @@ void miso_batch::plan_flat(size_t ri) {
   r.flat_ks = (run.kc <= 32 && run.kmax >= lo && run.kmax <= std::min(run.kc, 20) && !knobs.flat_no_ks) ? run.kmax : 0;
   // ... and, when every event of the launch has that count, the kernel that knows it (UNI: no per-chain `k < K` masks)
   r.flat_uni = r.flat_ks > 0 && run.kmin == run.kmax && !knobs.flat_no_uni;
-  if (r.lane) return;
+  if (r.lane()) return;
   if (p.paired || run.nocls || run.kc >= 64 || knobs.no_flat) return;
   const int slice = flat_layout(run.kmax, std::max(run.maxcls, 1)).bytes;
   const int wgs = flat_wgs(run.kc);
@@ -1535,7 +996,7 @@ void miso_batch::plan_flat(size_t ri) {
 void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
   GenRun &run = gen_runs[ri];
   LaunchPlan::Run &r = plan.runs[ri];
-  if (r.lane) return;
+  if (r.lane()) return;
   if (run.kc >= 64) { r.flat_nc = 0; r.G = 64; r.sh = GrpShape{0, 0}; return; }   // more than 32 isoforms: one wavefront per chain
   // sampler_flat or sampler_grp?  Measured on the batch's first launch like the lanes per chain below
   // (flat wins at every isoform count of profiles/r02_flat_vs_grp_sweep.txt but 5); a small or untuned
@@ -1547,7 +1008,7 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
   GrpShape &sh = r.sh = grp_shape(run);
   const long chains = static_cast<long>(run.count) * p.noChains;
   int G = 64;
-  if (run.wide) {   // one chain per workgroup (launch_grp): the score table joins the slice when four of them fit
+  if (run.wide()) {   // one chain per workgroup (launch_grp): the score table joins the slice when four of them fit
     GrpShape w{0, 0};
     w.ts = run.kmax * plan.il2;
     if (fp_bytes_of(run) + 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, w.ts)) + 64 > plan.lds_max) w.ts = 0;
@@ -1592,7 +1053,7 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
     // no longer fills the device with half-efficient wavefronts for the launch's first third while the other classes
     // wait; the bucket of "at least 32 lanes" from a need of 32 lanes instead of 24: a 20-isoform gene of 1000 pairs
     // needs 28 by the share rule; profiles/r05_pe_mix_lanes.txt)
-    const bool mix16 = run.kc <= 32 && !run.force_G && (knobs.pe_mix_lanes.set ? knobs.pe_mix_lanes.v == 16 : mean_q < 400.0);
+    const bool mix16 = run.kc <= 32 && !run.force_G() && (knobs.pe_mix_lanes.set ? knobs.pe_mix_lanes.v == 16 : mean_q < 400.0);
     const bool pe32 = p.paired && ((n_classes + (n_k2 > 0 ? 1 : 0) > 1 && !mix16) || (run.kc >= 12 && 2 * ((chains + 3) / 4) < 3 * static_cast<long>(slots_for(chains))) ||
                                    (chains + 3) / 4 < slots_for(chains));
     for (int g : {2, 4, 8, 16, 32}) {
@@ -1614,12 +1075,12 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
       const Opt<int> &l8 = knobs.pe_lanes8;
       const bool single = n_classes + (n_k2 > 0 ? 1 : 0) == 1;
       const bool want8 = l8.set && l8.v != 2 ? l8.v != 0 : ((single || l8.set) && chains >= 8L * 2 * slots_for(chains));   // (2: the rule in a mix of classes too)
-      if (p.paired && want8 && G == 16 && !run.force_G && run.kmin >= 5 && run.kmax <= 9 && grp_fits(run, sh, 8)) G = 8;
+      if (p.paired && want8 && G == 16 && !run.force_G() && run.kmin >= 5 && run.kmax <= 9 && grp_fits(run, sh, 8)) G = 8;
       // Three and four isoforms the same -- there the class keeps its score tables in LDS (grp_shape), which holds four
       // chains per wavefront and no more: eight chains with the tables in global memory (an L2 line per pick) instead,
       // K = 3 66.6 -> 78.9 k, K = 4 58.1 -> 68.0 k events/s; the tables alone are worth 2 % (16 lanes without them 65.3 /
       // 57.0 k), four lanes lose (55.9 / 37.6 k) (profiles/r05_lanes_sweep.txt).
-      if (p.paired && want8 && G == 16 && !run.force_G && run.kmax <= 4) {
+      if (p.paired && want8 && G == 16 && !run.force_G() && run.kmax <= 4) {
         GrpShape sh8 = sh;
         if (!grp_fits(run, sh8, 8)) sh8.ts = 0;
         if (grp_fits(run, sh8, 8)) { sh = sh8; G = 8; }
@@ -1635,8 +1096,8 @@ void miso_batch::plan_grp(size_t ri, const KernelArgs &a) {
       run.tuned_G = G;
     }
   }
-  if (run.force_G && G < run.force_G && !knobs.general_lanes.set) G = run.force_G;   // size bucket (upload)
-  if (run.small && p.paired && !knobs.general_lanes.set && !knobs.general_lanes_by_class_set) {   // the small genes' bucket: eight chains per wavefront, score tables in global memory
+  if (run.force_G() && G < run.force_G() && !knobs.general_lanes.set) G = run.force_G();   // size bucket (upload)
+  if (run.small() && p.paired && !knobs.general_lanes.set && !knobs.general_lanes_by_class_set) {   // the small genes' bucket: eight chains per wavefront, score tables in global memory
     GrpShape sh8 = sh;
     sh8.ts = 0;
     if (grp_fits(run, sh8, 8)) { sh = sh8; G = 8; }
@@ -1667,12 +1128,12 @@ void miso_batch::group_runs() {
     bool two_classes = false;
     for (size_t ri = 0; ri < gen_runs.size() && all_ok; ri++) {
       const GenRun &run = gen_runs[ri];
-      all_ok = !q.runs[ri].lane && q.runs[ri].flat_nc == 0 && fp_rows(run) && run.kc <= 32 && !run.wide && q.runs[ri].G == 16;
+      all_ok = !q.runs[ri].lane() && q.runs[ri].flat_nc == 0 && fp_rows(run) && run.kc <= 32 && !run.wide() && q.runs[ri].G == 16;
       two_classes |= run.kc != gen_runs[0].kc;
     }
     q.grp_all = all_ok && two_classes;
     if (q.grp_all)
-      for (LaunchPlan::Run &r : q.runs) r.group = 2;
+      for (LaunchPlan::Run &r : q.runs) r.kind = RunKernel::GrpAll;
   }
   // Paired-end: the size buckets of one isoform-count class in ONE launch (sampler_grp_multi<KC>, kernels_grp.inl):
   // segments = the class's runs in list order -- workgroup-wide chains (those on several workgroups in front), a
@@ -1684,7 +1145,7 @@ void miso_batch::group_runs() {
   bool any_mixed = false;
   for (size_t ri = 0; ri < gen_runs.size(); ri++) {
     const int G = q.runs[ri].G;
-    any_mixed |= p.paired && !gen_runs[ri].wide && (G == 16 || G == 32 || (G == 8 && gen_runs[ri].small)) && fp_rows(gen_runs[ri]) && q.runs[ri].flat_nc == 0 && gen_runs[ri].kmin != gen_runs[ri].kmax;
+    any_mixed |= p.paired && !gen_runs[ri].wide() && (G == 16 || G == 32 || (G == 8 && gen_runs[ri].small())) && fp_rows(gen_runs[ri]) && q.runs[ri].flat_nc == 0 && gen_runs[ri].kmin != gen_runs[ri].kmax;
   }
   const bool multi_on = p.paired && !q.lane_gen && !knobs.no_pe_multi && !knobs.general_lanes.set &&
                         (knobs.pe_multi || gen_runs.size() + (n_k2 > 0 ? 1 : 0) > 8 || any_mixed);
@@ -1692,23 +1153,23 @@ void miso_batch::group_runs() {
     size_t r1 = r0 + 1;
     while (r1 < gen_runs.size() && gen_runs[r1].kc == gen_runs[r0].kc) r1++;
     const int G0 = q.runs[r0].G;
-    bool ok = (r1 - r0 >= 2 || (r1 - r0 == 1 && gen_runs[r0].kmin != gen_runs[r0].kmax && (G0 == 16 || G0 == 32 || (G0 == 8 && gen_runs[r0].small)))) &&
+    bool ok = (r1 - r0 >= 2 || (r1 - r0 == 1 && gen_runs[r0].kmin != gen_runs[r0].kmax && (G0 == 16 || G0 == 32 || (G0 == 8 && gen_runs[r0].small())))) &&
               r1 - r0 <= static_cast<size_t>(K2_MAX_SEGS);
     for (size_t ri = r0; ri < r1 && ok; ri++) {
       const GenRun &run = gen_runs[ri];
       const int G = q.runs[ri].G;
       ok = q.runs[ri].flat_nc == 0 && fp_rows(run) && (ri == r0 || run.first == gen_runs[ri - 1].first + gen_runs[ri - 1].count) &&
-           (run.wide || G == 16 || G == 32 || (G == 64 && run.wave64) || (G == 8 && run.small));
+           (run.wide() || G == 16 || G == 32 || (G == 64 && run.wave64()) || (G == 8 && run.small()));
     }
     if (ok) {   // every segment's slices fit the workgroup's LDS
       const GenRun m = joined_run(r0, r1);
       const size_t fp_bytes = fp_bytes_of(m), slice = grp_slice_bytes(m.kmax, 0, grp_shape(m).ts), slice8 = grp_slice_bytes(m.kmax, 0, 0);
       for (size_t ri = r0; ri < r1 && ok; ri++)
-        if (!gen_runs[ri].wide) ok = fp_bytes + 4 * static_cast<size_t>(64 / q.runs[ri].G) * (q.runs[ri].G == 8 ? slice8 : slice) <= q.lds_max;
+        if (!gen_runs[ri].wide()) ok = fp_bytes + 4 * static_cast<size_t>(64 / q.runs[ri].G) * (q.runs[ri].G == 8 ? slice8 : slice) <= q.lds_max;
     }
     if (ok) {
       q.multi.emplace_back(r0, r1);
-      for (size_t ri = r0; ri < r1; ri++) q.runs[ri].group = 1;
+      for (size_t ri = r0; ri < r1; ri++) q.runs[ri].kind = RunKernel::GrpMulti;
     }
     r0 = r1;
   }
@@ -1724,8 +1185,8 @@ void miso_batch::group_runs() {
   for (size_t ri = 0; merge_on && ri + 1 < gen_runs.size(); ri++) {
     const GenRun &run = gen_runs[ri], &nx = gen_runs[ri + 1];
     const LaunchPlan::Run &r = q.runs[ri], &rx = q.runs[ri + 1];
-    if (r.lane || r.group || (ri > 0 && q.runs[ri - 1].merge_next)) continue;
-    if (!run.wide && run.force_G && r.G != 64 && r.flat_nc == 0 && !nx.wide && !nx.force_G && nx.kc == run.kc && rx.G == r.G &&
+    if (r.lane() || r.grouped() || (ri > 0 && q.runs[ri - 1].merge_next)) continue;
+    if (!run.wide() && run.force_G() && r.G != 64 && r.flat_nc == 0 && !nx.wide() && !nx.force_G() && nx.kc == run.kc && rx.G == r.G &&
         rx.flat_nc == 0 && nx.first == run.first + run.count) {
       const GenRun m = joined_run(ri, ri + 2);
       q.runs[ri].merge_next = grp_fits(m, grp_shape(m), r.G);
@@ -1733,83 +1194,6 @@ void miso_batch::group_runs() {
   }
 }
 
-// kernel i > 0 goes to its own stream, forked from and joined back into the batch's stream
-hipStream_t miso_batch::stream_for_next() {
-  const size_t i = kernel_no++;
-  if (i == 0 || knobs.serial_kernels) return stream;
-  while (aux_streams.size() < i) {
-    hipStream_t st; hipEvent_t e;
-    // (numerically lower = higher priority; the range has three levels on this device: the second and third kernel
-    // of a launch at the middle one, the rest at the lowest)
-    const int n_aux = static_cast<int>(aux_streams.size());
-    const int pr = prio_hi == prio_lo ? prio_lo : std::min(prio_lo, prio_hi + 1 + n_aux / 2);
-    if (prio_hi != prio_lo) HIP_OK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, pr));
-    else HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    aux_streams.push_back(st); aux_done.push_back(e);
-  }
-  HIP_OK(hipStreamWaitEvent(aux_streams[i - 1], ev0, 0));
-  return aux_streams[i - 1];
-}
-
-// The launches, in this order (the stream and priority every kernel gets follow from it): sampler_lane_k, the
-// workgroup-wide runs (chains on several workgroups first: their workgroups must all be resident at once, coop.hpp,
-// which the idle device guarantees; what is launched after them never waits for them) -- sampler_grp_all or the
-// classes' sampler_grp_multi, then the runs of their own --, MODE 2, the other two-isoform events, the other runs.
-void miso_batch::launch_planned(const KernelArgs &a, const KernelArgs &k2a) {
-  const LaunchPlan &q = plan;
-  if (q.lane_route || q.lane_gen) {   // log factorials (miso_binomial.h) up to the largest event's drawing reads
-    size_t need = 2;
-    for (int i = 0; i < n_k2 + n_gen; i++) need = std::max<size_t>(need, events[h_slots[i]].n_draw + 2);
-    if (need > logfact.host.size()) {
-      std::vector<double> lf(need);
-      miso_logfact_fill(lf.data(), static_cast<int>(need));
-      HIP_OK(hipStreamSynchronize(stream));   // (an earlier launch of this batch may still read the old table)
-      put(logfact, lf);
-    }
-  }
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-    if (!q.runs[ri].lane) continue;
-    const GenRun &run = gen_runs[ri];
-    const int ks = std::max(2, run.kmax);
-    KernelArgs ka = a;
-    ka.slot_event = d_slots + n_k2 + run.first; ka.n_slots = run.count; ka.kstride = ks; ka.logfact = logfact.d;
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    note_kernel(run_name(ri));
-    launch_kernel(fn(&sampler_lane_k), static_cast<unsigned>((chains + 63) / 64), 64, lanek_lds_bytes(ks), stream_for_next(), ka);
-  }
-  if (q.grp_all) launch_grp_all(a);
-  for (const auto &g : q.multi) launch_grp_multi(a, g.first, g.second);
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) if (gen_runs[ri].wide && !q.runs[ri].lane && !q.runs[ri].group) launch_run(a, ri);
-  if (n_k2w > 0) {
-    lanes_per_chain = q.k2w_multi ? k2w_plan.seg_lanes[k2w_plan.n_segs - 1] : q.k2w_G;
-    note_kernel(k2_part_name(true));
-    if (q.k2w_multi) launch_k2_multi(k2a, stream_for_next(), true);
-    else launch_k2(k2a, q.k2w_G, stream_for_next(), true);
-  }
-  if (n_k2 - n_k2w > 0) {
-    lanes_per_chain = q.lane_route ? q.lane_G : q.k2_multi ? k2_plan.seg_lanes[k2_plan.n_segs - 1] : q.k2_G;
-    note_kernel(k2_part_name(false));
-    if (q.lane_route) launch_lane(k2a, stream_for_next());
-    else if (q.k2_multi) launch_k2_multi(k2a, stream_for_next());
-    else if (q.k2_mix > 0) launch_k2_mix(k2a, stream_for_next());
-    else launch_k2(k2a, q.k2_G, stream_for_next());
-  }
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) if (!gen_runs[ri].wide && !q.runs[ri].lane && !q.runs[ri].group) launch_run(a, ri);
-}
-
-// The exact-posterior mode's events (kernels_exact.hip): one wavefront each, no chains; the launch's last kernel, on the
-// next of its streams (the batch's own when the samplers' plan is empty).
-void miso_batch::launch_exact(const KernelArgs &a) {
-  KernelArgs ka = a;
-  ka.slot_event = d_slots + n_k2 + n_gen; ka.n_slots = n_exact;
-  note_kernel(p.paired ? "exact_paired_sample" : "exact_sample");
-  const double *eff = exact_eff.d;
-  int Sn = S();
-  void *args[] = {&ka, &eff, &Sn};
-  (void) hipLaunchKernel(p.paired ? exact_paired_sample_fn() : fn(&exact_sample), dim3(static_cast<unsigned>(n_exact)), dim3(64), args, 0, stream_for_next());
-  HIP_OK(hipGetLastError());
-}
 
 // the statistics of an event of the exact list as exact_probe and exact_compare take them
 void miso_batch::exact_stats7(int event, double *r) const {
@@ -1849,297 +1233,6 @@ void miso_batch::exact_summaries(double confidence_level) {
   exact_sums_level = confidence_level;
 }
 
-// general run ri in a launch of its own, or with the next run (merge_next); nothing when the run before took it
-void miso_batch::launch_run(const KernelArgs &a, size_t ri) {
-  const LaunchPlan::Run &r = plan.runs[ri];
-  if (ri > 0 && plan.runs[ri - 1].merge_next) return;
-  note_kernel(run_name(ri));
-  if (r.merge_next) {
-    GenRun m = joined_run(ri, ri + 2);
-    launch_grp(a, m, grp_shape(m), r.G, stream_for_next());
-  } else if (r.flat_nc > 0) {
-    launch_flat(a, ri, stream_for_next());
-  } else {
-    launch_grp(a, gen_runs[ri], r.sh, r.G, stream_for_next());
-  }
-}
-
-void miso_batch::launch_grp_all(const KernelArgs &a) {
-  struct Seg { size_t ri; int e0, e1; double cost; };
-  std::vector<Seg> segs;
-  // (a segment per isoform count, so that no wavefront carries two -- see sampler_grp_multi below; knobs.pe_all_order: other orders)
-  const int order = knobs.pe_all_order.v;
-  for (size_t ri = 0; ri < gen_runs.size(); ri++) {
-    const GenRun &run = gen_runs[ri];
-    if (order == 0) { segs.push_back(Seg{ri, 0, run.count, (static_cast<double>(run.maxq) / 16.0 + 8.0) * (run.kmax + 2)}); continue; }
-    auto cost_at = [&](int e) {
-      const PackedEvent &ev = events[h_slots[n_k2 + run.first + e]];
-      return (static_cast<double>((ev.n_draw + 3) / 4) / 16.0 + 8.0) * (ev.K + 2);
-    };
-    int e0 = 0;   // pieces: one per isoform count
-    for (int e = 1; e <= run.count; e++)
-      if (e == run.count || events[h_slots[n_k2 + run.first + e]].K != events[h_slots[n_k2 + run.first + e0]].K) { segs.push_back(Seg{ri, e0, e, cost_at(e0)}); e0 = e; }
-  }
-  std::stable_sort(segs.begin(), segs.end(), [&](const Seg &x, const Seg &y) { return x.cost > y.cost; });
-  if (order == 2) {   // heaviest, lightest, second heaviest, second lightest, ...
-    std::vector<Seg> t;
-    for (size_t i = 0, j = segs.size(); i < j;) { t.push_back(segs[i++]); if (i < j) t.push_back(segs[--j]); }
-    segs = t;
-  }
-  if (order == 3) std::reverse(segs.begin(), segs.end());   // lightest first
-  KernelArgs ka = a;
-  hipStream_t st = stream_for_next();
-  ka.slot_event = d_slots + n_k2; ka.n_slots = n_gen;
-  ka.cstride = 0; ka.pe_dense = 1;
-  size_t lds = 0; int blocks = 0;
-  std::vector<GrpSeg> tab;
-  for (const Seg &sg : segs) {
-    const GenRun &run = gen_runs[sg.ri];
-    const GrpShape &sh = plan.runs[sg.ri].sh;
-    const long chains = static_cast<long>(sg.e1 - sg.e0) * p.noChains;
-    GrpSeg g{};
-    g.block0 = blocks; g.slot0 = run.first + sg.e0; g.n_slots = sg.e1 - sg.e0; g.kc = run.kc;
-    g.kstride = run.kmax; g.tstride = sh.ts;
-    lds = std::max(lds, fp_bytes_of(run) + 4 * 4 * static_cast<size_t>(grp_slice_bytes(run.kmax, 0, sh.ts)));
-    blocks += static_cast<int>(((chains + 3) / 4 + 3) / 4);
-    tab.push_back(g);
-  }
-  GrpSeg sentinel{}; sentinel.block0 = blocks;
-  tab.push_back(sentinel);
-  if (lds > plan.lds_max) MISO_FAIL(MISO_EINTERNAL, "sampler_grp_all: a segment's slices exceed the workgroup's LDS");
-  // (uploaded when it changed: the batch's first launch, or another upload's events; the launch that read the old one has
-  // been waited for by then)
-  constexpr size_t GRP_SEGS_CAP = 256;
-  if (tab.size() > GRP_SEGS_CAP) MISO_FAIL(MISO_EINTERNAL, "sampler_grp_all: too many segments");
-  put(grp_segs, tab, GRP_SEGS_CAP);
-  ka.grp_segs = grp_segs.d; ka.n_grp_segs = static_cast<int32_t>(segs.size());
-  note_kernel("sampler_grp_all");
-  launch_kernel(fn(&sampler_grp_all), static_cast<unsigned>(blocks), 256, lds, st, ka);
-}
-
-void miso_batch::launch_grp_multi(const KernelArgs &a, size_t r0, size_t r1) {
-  const GenRun m = joined_run(r0, r1);
-  const GrpShape msh = grp_shape(m);
-  const size_t fp_bytes = fp_bytes_of(m);
-  const size_t slice = grp_slice_bytes(m.kmax, 0, msh.ts);
-  // (the small genes' segment: eight chains per wavefront, their score tables in global memory -- a tstride of its own)
-  const size_t slice8 = grp_slice_bytes(m.kmax, 0, 0);
-  KernelArgs ka = a;
-  hipStream_t st = stream_for_next();
-  ka.slot_event = d_slots + n_k2 + m.first; ka.n_slots = m.count;
-  ka.kstride = m.kmax; ka.cstride = 0; ka.tstride = msh.ts;
-  ka.pe_dense = 1;
-  size_t lds = 0; int blocks = 0, segs = 0;
-  // A run on 16 or 32 lanes per chain is one segment PER ISOFORM COUNT (the run's events are ordered by it): every segment starts
-  // a new workgroup, so no wavefront carries chains of two isoform counts -- such a wavefront runs both counts' read loops one after
-  // the other (kernels_grp.inl pe_fast), twice a chain's own time, and with the class's longest chains that was the launch's length
-  // (round 6, profiles/r06_mix_timeline.txt).  As far as the segments suffice (knobs.pe_no_ksplit: a segment per run).
-  auto k_pieces = [&](const GenRun &run) {
-    std::vector<int> cuts{0};
-    for (int e = 1; e < run.count; e++)
-      if (events[h_slots[n_k2 + run.first + e]].K != events[h_slots[n_k2 + run.first + e - 1]].K) cuts.push_back(e);
-    cuts.push_back(run.count);
-    return cuts;
-  };
-  size_t want_segs = 0;
-  for (size_t ri = r0; ri < r1; ri++)
-    want_segs += (gen_runs[ri].wide || plan.runs[ri].G == 64) ? 1 : k_pieces(gen_runs[ri]).size() - 1;
-  const bool ksplit = want_segs <= static_cast<size_t>(K2_MAX_SEGS) && !knobs.pe_no_ksplit;
-  for (size_t ri = r0; ri < r1; ri++) {
-    GenRun &run = gen_runs[ri];
-    const long chains = static_cast<long>(run.count) * p.noChains;
-    if (run.wide) {
-      ka.seg_slot[segs] = run.first - m.first; ka.seg_block[segs] = blocks;
-      const size_t lds0 = align_up(fp_bytes + 4 * slice, 16);
-      ka.red_off = static_cast<int32_t>(lds0);
-      lds = std::max(lds, lds0 + 96);
-      blocks += static_cast<int>(wide_setup(run, chains, st));
-      ka.coop_tab = run.coop.tab.d; ka.coop_mem = run.coop.mem.d;
-      ka.seg_ts[segs] = msh.ts;
-      ka.seg_lanes[segs++] = K2_WIDE;
-    } else {
-      const int G = plan.runs[ri].G, cpw = 64 / G;
-      lds = std::max(lds, fp_bytes + 4 * static_cast<size_t>(cpw) * (G == 8 ? slice8 : slice));
-      const std::vector<int> cuts = (ksplit && G != 64) ? k_pieces(run) : std::vector<int>{0, run.count};
-      for (size_t c = 0; c + 1 < cuts.size(); c++) {
-        const long pc = static_cast<long>(cuts[c + 1] - cuts[c]) * p.noChains;
-        ka.seg_slot[segs] = run.first - m.first + cuts[c]; ka.seg_block[segs] = blocks;
-        blocks += static_cast<int>(((pc + cpw - 1) / cpw + 3) / 4);
-        ka.seg_ts[segs] = G == 8 ? 0 : msh.ts;
-        ka.seg_lanes[segs++] = G;
-      }
-    }
-  }
-  ka.seg_slot[segs] = m.count; ka.seg_block[segs] = blocks; ka.n_segs = segs;
-  note_kernel(run_name(r0));
-  launch_kernel(grp_multi_kernel(m.kc), static_cast<unsigned>(blocks), 256, lds, st, ka);
-}
-
-// ---- what the last launch put on the device, kernel by kernel (miso_batch_launch_stats): from its plan, on demand ----
-std::vector<miso_kernel_stat_t> miso_batch::launch_stats() const {
-  std::vector<miso_kernel_stat_t> out;
-  if (!plan.sampled) return out;
-  const LaunchPlan &q = plan;
-  auto add_stat = [&](const std::string &name, double waves, double trips, double chains, double words) {
-    miso_kernel_stat_t ks{};
-    std::snprintf(ks.name, sizeof ks.name, "%s", name.c_str());
-    ks.waves = waves; ks.trips = trips; ks.iterations = static_cast<double>(p.noIterations) + 1.0;
-    ks.chains = chains; ks.words = words;
-    out.push_back(ks);
-  };
-  for (int part = 0; part < 2; part++) {
-    const bool wpart = part == 0;
-    const int count = wpart ? n_k2w : n_k2 - n_k2w, k2G = wpart ? q.k2w_G : q.k2_G;
-    if (count <= 0) continue;
-    // slot order = events by drawing reads, descending, each with its noChains chains
-    std::vector<int> nd;
-    for (size_t i = 0; i < events.size(); i++) {
-      const PackedEvent &e = events[i];
-      if (e.K == 2 && !k2_general && !event_exact(static_cast<int>(i)) && (use_delta && e.pe_delta && !e.draw_dense.empty()) == wpart) nd.push_back(e.n_draw);
-    }
-    std::sort(nd.begin(), nd.end(), [](int x, int y) { return x > y; });
-    const int C = p.noChains;
-    const long chains = static_cast<long>(count) * C;
-    double trips = 0, words = 0;
-    long waves = 0;
-    const int bshift = p.paired ? 2 : 3;   // draws per Philox block: four, single-end eight (half-words, miso_philox.h)
-    auto slice = [&](long c0, long c1, int G) {   // chains [c0, c1) of the list with G lanes per chain
-      const int cpw = 64 / G;
-      for (long s0 = c0; s0 < c1; s0 += cpw, waves++) {
-        int mx = 0;   // blocks of the wavefront's largest chain (single-end: the partial block is one of the stride's)
-        for (long sl = s0; sl < std::min(c1, s0 + cpw); sl++) {
-          const int n = nd[sl / C];
-          mx = std::max(mx, (n >> bshift) + ((!p.paired && (n & ((1 << bshift) - 1))) ? 1 : 0));
-          words += n;
-        }
-        const int t = (mx + 2 * G - 1) / (2 * G);             // paired-end: trips of two Philox blocks per lane
-        trips += p.paired ? 2 * t + 1 : (mx + G - 1) / G;     // counted in blocks per lane (single-end: stride positions)
-      }
-    };
-    if (!wpart && q.lane_route) {
-      for (int n : nd) words += static_cast<double>(n) * C;
-      waves = (chains * q.lane_G + 63) / 64;
-    } else if (wpart ? q.k2w_multi : q.k2_multi) {
-      const LanePlan &pl = wpart ? k2w_plan : k2_plan;
-      for (int sg = 0; sg < pl.n_segs; sg++) {
-        const long c0 = static_cast<long>(pl.seg_slot[sg]) * C, c1 = static_cast<long>(pl.seg_slot[sg + 1]) * C;
-        if (pl.seg_lanes[sg] == K2_WIDE) {
-          for (long c = c0; c < c1; c++) {
-            const int n = nd[c / C];
-            const size_t we = static_cast<size_t>(c / C - pl.seg_slot[sg]);
-            const int m = we < pl.wide_wgs.size() ? pl.wide_wgs[we] : 1;     // workgroups of the chain (coop.hpp)
-            const int wl = 64 * pl.wpb * m;
-            const int t = ((n >> bshift) + ((!p.paired && (n & 7)) ? 1 : 0) + 2 * wl - 1) / (2 * wl);
-            const int nb = (n >> bshift) + ((!p.paired && (n & 7)) ? 1 : 0);
-            trips += pl.wpb * m * (p.paired ? 2 * t + 1 : (nb + wl - 1) / wl);
-            words += n; waves += pl.wpb * m;
-          }
-        } else slice(c0, c1, pl.seg_lanes[sg]);
-      }
-    } else if (!wpart && q.k2_mix > 0) {
-      slice(0, static_cast<long>(q.k2_mix) * C, k2G + 1);
-      slice(static_cast<long>(q.k2_mix) * C, chains, k2G);
-    } else {
-      slice(0, chains, k2G);
-    }
-    add_stat(k2_part_name(wpart), static_cast<double>(waves), trips, static_cast<double>(chains), words);
-  }
-  for (size_t ri = 0; ri < gen_runs.size() && ri < q.runs.size(); ri++) {
-    const GenRun &run = gen_runs[ri];
-    const LaunchPlan::Run &r = q.runs[ri];
-    const int C = p.noChains;
-    const long chains = static_cast<long>(run.count) * C;
-    std::vector<const PackedEvent *> evs;   // the run's events in slot order
-    for (int j = 0; j < run.count; j++) evs.push_back(&events[h_slots[n_k2 + run.first + j]]);   // the list upload made
-    double trips = 0, words = 0;
-    long waves = 0;
-    if (r.lane) {
-      for (const PackedEvent *e : evs) words += static_cast<double>(e->n_draw) * C;
-      add_stat(run_name(ri), static_cast<double>((chains + 63) / 64), 0.0, static_cast<double>(chains), words);
-      continue;
-    }
-    const bool flat = r.flat_nc > 0;
-    const int G = r.G, cpw = flat ? r.flat_nc : std::max(1, 64 / G);
-    const bool w64 = G == 64 && run.wave64 && p.paired && run.dense;
-    const bool cls = !p.paired && r.sh.qs > 0;
-    if (flat) {   // the wavefronts as flat_waves laid them out
-      const std::vector<int32_t> &tab = run.wave_tab.host;
-      for (size_t w = 0; w + 1 < tab.size(); w += 2) {
-        const int first = tab[w], n = tab[w + 1] & 0xFF;
-        const bool wide = (tab[w + 1] & FLAT_WIDE) != 0;
-        if (n == 0) continue;
-        long units = 0;
-        for (long sl = first; sl < first + n; sl++) { units += evs[sl / C]->n_units; if (!wide || (w / 2) % 4 == 0) words += evs[sl / C]->n_draw; }
-        trips += wide ? (units + 255) / 256 : (units + 63) / 64;
-        waves++;
-      }
-    } else
-    for (long s0 = 0; s0 < chains; s0 += cpw, waves++) {
-      int mx = 0, kmx = 0; long units = 0;
-      for (long sl = s0; sl < std::min(chains, s0 + cpw); sl++) {
-        const PackedEvent &e = *evs[sl / C];
-        mx = std::max(mx, cls ? e.n_units : (e.n_draw + 3) / 4);
-        units += e.n_units;
-        kmx = std::max(kmx, e.K);
-        words += e.n_draw;
-      }
-      const int nw = (cls && kmx - 1 <= 3) ? 2 : 1;         // Philox blocks in flight (class path, K <= 4)
-      trips += flat ? (units + 63) / 64 : ((G == 64 && !w64) ? mx : nw * ((mx + nw * G - 1) / (nw * G)));
-    }
-    if (run.wide) {   // four wavefronts per chain, the quads dealt over 256 lanes
-      trips = 0; waves = 0;
-      for (long sl = 0; sl < chains; sl++) { trips += 4 * ((((evs[sl / C]->n_draw + 3) / 4) + 255) / 256); waves += 4; }
-    }
-    add_stat(run_name(ri), static_cast<double>(waves), trips, static_cast<double>(chains), words);
-  }
-  if (n_exact > 0) {   // one wavefront per event, no chains: `chains` counts the events, `words` their sample uniforms
-    add_stat(p.paired ? "exact_paired_sample" : "exact_sample", static_cast<double>(n_exact), 0.0, static_cast<double>(n_exact), static_cast<double>(n_exact) * S());
-    out.back().iterations = 1.0;
-  }
-  return out;
-}
-
-// The clock probe of this launch (clock_probe_kernel above).  First the flag's store, behind the launch's last kernel on the
-// batch's stream; then the probe on a stream of its own: on a hardware queue of its own it starts at once, beside the
-// sampler kernels.  Should its stream share the batch's queue (or a profiler serialise the dispatches) it starts when
-// everything before it is done, finds the flag set and reports a window of no length, which sync() discards -- in no
-// order of execution does it wait for something queued behind it.  Give-up time: 1.5 x the last launch's kernel time + 20 ms.
-void miso_batch::start_clock_probe() {
-  probe_armed = false;
-  if (!clock_probe || probe_failed) return;
-  if (!probe_stream) {
-    HIP_OK(hipStreamCreateWithFlags(&probe_stream, hipStreamNonBlocking));
-    HIP_OK(hipMalloc(&d_probe, 8 * sizeof(unsigned long long)));
-    HIP_OK(hipMemset(d_probe, 0, 8 * sizeof(unsigned long long)));
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) wall_khz = khz;
-  }
-  probe_gen++;
-  uint32_t *flag = reinterpret_cast<uint32_t *>(d_probe + 7);
-  hipLaunchKernelGGL(clock_probe_stop, dim3(1), dim3(64), 0, stream, flag, probe_gen);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamWaitEvent(probe_stream, ev0, 0));
-  const double cap_ms = 1.5 * (last_ms > 0.f ? last_ms : 2000.0) + 20.0;
-  hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, probe_stream, flag, probe_gen, d_probe,
-                     static_cast<unsigned long long>(cap_ms * wall_khz));
-  HIP_OK(hipGetLastError());
-  probe_armed = true;
-}
-
-void miso_batch::read_clock_probe() {
-  last_clock_ghz = 0.0; last_probe_ms = 0.0;
-  if (!probe_armed) return;
-  probe_armed = false;
-  HIP_OK(hipStreamSynchronize(probe_stream));
-  unsigned long long h[5];
-  HIP_OK(hipMemcpy(h, d_probe, sizeof(h), hipMemcpyDeviceToHost));
-  if (h[4] != 0) { probe_failed = true; return; }   // it gave up: never again for this batch (each time would cost its give-up time)
-  const double ms = static_cast<double>(h[2] - h[0]) / wall_khz;
-  // a window much shorter than the launch: the probe ran behind the kernels, not beside them
-  if (ms < 0.5 * last_ms || ms <= 0.0) return;
-  last_probe_ms = ms;
-  last_clock_ghz = static_cast<double>(h[3] - h[1]) / (ms * 1e6);
-}
 
 void miso_batch::sync(float *ms) {
   if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
@@ -2166,7 +1259,7 @@ void miso_batch::sync(float *ms) {
   no_coop = true; coop_retries++;
   std::fill(coop_n.begin(), coop_n.end(), 1);
   each_coop_table([](CoopTable &c) { c.reset(); });
-  k2_plan_key = k2w_plan_key = -1; coop_wgs_used = 0;
+  k2[0].plan_key = k2[1].plan_key = -1; coop_wgs_used = 0;
   pool_cleared = false;   // (the abandoned chains left their sample columns half written)
   std::fprintf(stderr, "[miso] a chain on several workgroups gave up waiting for its workgroups after %.1f ms (busy device?): "
                        "re-running the launch with one workgroup per chain\n", first_ms);
@@ -2520,7 +1613,7 @@ void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_events), std::max<size_t>(n, 1) * sizeof(DevEvent)));
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
-  n_k2 = n_k2w = n_gen = 0; gen_runs.clear(); plan = LaunchPlan{};
+  n_k2 = n_k2w = n_gen = 0; k2[0].count = k2[1].count = 0; gen_runs.clear(); plan = LaunchPlan{};
   uploaded = launched = true; downloaded = false; summarized = compared = exact_compared = diagnosed = false; adopted = true;
 }
 

@@ -104,7 +104,7 @@ def test_mixed_read_counts_one_launch_bit_exact(orc, paired, chains):
 
 @pytest.mark.parametrize("K,chains", [(3, 1), (5, 2), (10, 1), (18, 1)])
 def test_mixed_read_counts_three_or_more_isoforms_bit_exact(orc, K, chains):
-    """sampler_flat: wavefronts packed by work units, the largest chains one per workgroup (runtime.hip flat_waves,
+    """sampler_flat: wavefronts packed by work units, the largest chains one per workgroup (launch.hip flat_waves,
     kernels_flat.inl FLAT_WIDE) against the uniform layout and the oracle."""
     sizes = [20, 40000, 300, 5, 0, 2500, 12000, 40, 1000, 150, 7000, 64, 3, 511, 90, 200, 35, 800]
     evs = []
