@@ -324,6 +324,24 @@ int miso_batch_get_diagnostics(const miso_batch_t *batch, int event_index, doubl
 /* Kernel time (HIP events) of the last miso_batch_summarize[_as_text] and miso_batch_diagnose of this batch, ms; 0 before. */
 int miso_batch_pass_ms(const miso_batch_t *batch, float *summarize_ms, float *diagnose_ms);
 
+/* Rank-normalised chain diagnostics on the device (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021),
+   same preconditions and the same split sequences as miso_batch_diagnose.  The N = 2 noChains (S div noChains div 2) used
+   draws of a column are replaced by the normal scores of their average ranks (bulk), by the normal scores of the ranks
+   of their distance from the median (folded), and by the indicators of lying at or below / at or above the bounds of
+   the `confidence_level` interval -- the order statistics of miso_batch_summarize, taken over the N used draws -- and
+   each goes through miso_batch_diagnose's computation:  rhat_bulk, rhat_fold, ess_bulk, ess_ci_low, ess_ci_high;
+   distinct: the number of distinct values among the used draws.  noiso doubles each.  A column that holds a NaN or an
+   infinity gets five NaN and distinct = 0, a constant one five NaN and distinct = 1; a column whose folded values are
+   all equal (a two-valued column) gets rhat_fold = NaN.  MISO_EINVAL before any launch, for the whole batch:  "Too few
+   samples per chain for diagnostics" as miso_batch_diagnose;  "Too few samples for a credible interval" as
+   miso_batch_summarize, with N for the sample count;  "Too many samples for rank diagnostics": N > 8192;  "Too many chains
+   for rank diagnostics": noChains > 512 (the column is sorted in the workgroup's local memory). */
+int miso_batch_diagnose_rank(miso_batch_t *batch, int noChains, double confidence_level);
+int miso_batch_get_rank_diagnostics(const miso_batch_t *batch, int event_index, double *rhat_bulk, double *rhat_fold,
+                                    double *ess_bulk, double *ess_ci_low, double *ess_ci_high, double *distinct);
+/* Kernel time (HIP events) of the last miso_batch_diagnose_rank of this batch, ms; 0 before. */
+int miso_batch_rank_pass_ms(const miso_batch_t *batch, float *ms);
+
 /* Samples that were produced elsewhere -- parsed `.miso` files: summarize_miso and compare_miso work on directories of
    them (misopy/samples_utils.py:263-329, hypothesis_test.py:186-345).  Event i has noiso[i] isoforms and n_samples
    samples in the file's layout (samples[i]: n_samples rows of noiso[i] values).  The batch lives on `device` and

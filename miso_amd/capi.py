@@ -361,6 +361,44 @@ class Batch:
         check(lib().miso_batch_pass_ms(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def diagnose_rank(self, chains=None, confidence_level=0.95):
+        """Device-side rank-normalised chain diagnostics of every event (miso_batch_diagnose_rank): bulk
+        and folded split R-hat, bulk effective sample size, and the effective sample size of the two bounds of the
+        `confidence_level` credible interval.  chains as in diagnose().  Refused for the whole batch when the used
+        draws of a column exceed 8192, the chains 512, or the draws are too few for the interval."""
+        check(lib().miso_batch_diagnose_rank(self.handle, C.c_int(0 if chains is None else int(chains)),
+                                             C.c_double(confidence_level)))
+
+    def rank_diagnostics(self, i):
+        """(rhat_bulk[K], rhat_fold[K], ess_bulk[K], ess_ci_low[K], ess_ci_high[K], distinct[K]) of event i after
+        diagnose_rank(); distinct as integers."""
+        K = C.c_int()
+        check(lib().miso_batch_event_info(self.handle, i, C.byref(K), None, None, None))
+        cols = [np.zeros(K.value) for _ in range(6)]
+        check(lib().miso_batch_get_rank_diagnostics(self.handle, i, *(_p(c) for c in cols)))
+        return tuple(cols[:5]) + (cols[5].astype(np.int64),)
+
+    def rank_diagnostics_many(self, indices, noiso):
+        """[(rhat_bulk[K], rhat_fold[K], ess_bulk[K], ess_ci_low[K], ess_ci_high[K], distinct[K])] of the given events after
+        diagnose_rank(): rank_diagnostics() for many events, as diagnostics_many() is diagnostics()'s."""
+        offs = np.concatenate([[0], np.cumsum(np.asarray(noiso, dtype=np.int64))])
+        buf = np.zeros((6, int(offs[-1])))
+        base = [buf[r].ctypes.data for r in range(6)]
+        f = lib().miso_batch_get_rank_diagnostics
+        h = self.handle
+        for j, i in enumerate(indices):
+            o = 8 * int(offs[j])
+            check(f(h, int(i), *(C.c_void_p(base[r] + o) for r in range(6))))
+        distinct = buf[5].astype(np.int64)
+        return [tuple(buf[r, offs[j]:offs[j + 1]] for r in range(5)) + (distinct[offs[j]:offs[j + 1]],)
+                for j in range(len(indices))]
+
+    def rank_pass_ms(self):
+        """Kernel time of the last diagnose_rank() of this batch (HIP events), ms."""
+        a = C.c_float(0)
+        check(lib().miso_batch_rank_pass_ms(self.handle, C.byref(a)))
+        return a.value
+
     def compare(self, other, smoothing=0.3):
         """Two-sample comparison with `other` (same events, same order) on the device."""
         check(lib().miso_batch_compare(self.handle, other.handle, C.c_double(smoothing)))
@@ -592,7 +630,8 @@ class Batch:
 class SamplesBatch(Batch):
     """Posterior samples produced elsewhere (parsed `.miso` files) on the device: summarize(), summary(i),
     compare(other), comparison(i), diagnose(chains), diagnostics(i), diagnostics_many() as on a sampled batch
-    (miso_batch_from_samples); diagnose() needs its `chains` here, the samples carry no chain count."""
+    (miso_batch_from_samples), and diagnose_rank(chains), rank_diagnostics(i), rank_diagnostics_many() likewise;
+    diagnose() and diagnose_rank() need their `chains` here, the samples carry no chain count."""
 
     def __init__(self, samples, device=0):
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in samples]     # each [S, K]

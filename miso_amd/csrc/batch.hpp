@@ -142,6 +142,10 @@ enum class Bucket { Small = -1, Normal = 0, Lanes32 = 1, Wavefront = 2, Workgrou
 
 // diagnose(): chains at most (three doubles of LDS per split sequence)
 constexpr int DIAG_MAX_CHAINS = 2048;
+// diagnose_rank(): used draws and chains at most (the column, its sorted copy and the per-sequence scratch stay in LDS:
+// (8192 + 8192 + 3 * 1024) * 8 bytes = 152 KB of a workgroup's 160 KiB)
+constexpr int RANK_MAX_DRAWS = 8192;
+constexpr int RANK_MAX_CHAINS = 512;
 
 struct miso_batch {
   miso_params_t p{};
@@ -334,7 +338,11 @@ struct miso_batch {
   std::vector<double> h_diag;           // per event: K x {rhat, ess, mcse, lag} (kernels_diagnose.hip)
   std::vector<uint64_t> h_diag_off;     // offsets (in doubles) into h_diag
   bool diagnosed = false;
+  std::vector<double> h_rank;           // per event: K x {rhat_bulk, rhat_fold, ess_bulk, ess_ci_low, ess_ci_high, distinct}
+  std::vector<uint64_t> h_rank_off;     // (kernels_diagnose_rank.hip) and the offsets (in doubles) into it
+  bool rank_diagnosed = false;
   float summarize_ms = 0.f, diagnose_ms = 0.f;   // kernel time of the last summarize / diagnose pass
+  float rank_ms = 0.f;                  // and of the last diagnose_rank pass
   hipEvent_t pass_ev0 = nullptr, pass_ev1 = nullptr;   // bracket that pass; made by the first one
   bool adopted = false;                 // samples produced elsewhere (adopt_pool): p.noChains says nothing about them
   uint64_t in_bytes = 0, out_bytes = 0;
@@ -356,6 +364,7 @@ struct miso_batch {
   void download();
   void summarize(double confidence_level, bool as_text = false);
   void diagnose(int noChains);
+  void diagnose_rank(int noChains, double confidence_level);
   void adopt_samples(int n, const int *K, int S, const double *const *samples, int dev);
   void adopt_pool(int n, const int *K, int S, int dev);
   // kernels_text.hip: the pool filled from `.miso` sample text by text_decode_kernel

@@ -830,6 +830,31 @@ int miso_batch_get_diagnostics(const miso_batch_t *b, int i, double *rhat, doubl
   });
 }
 
+int miso_batch_diagnose_rank(miso_batch_t *b, int noChains, double confidence_level) {
+  return guarded([&] { need(b, "batch"); b->diagnose_rank(noChains, confidence_level); });
+}
+
+int miso_batch_get_rank_diagnostics(const miso_batch_t *b, int i, double *rhat_bulk, double *rhat_fold, double *ess_bulk,
+                                    double *ess_ci_low, double *ess_ci_high, double *distinct) {
+  return guarded([&] {
+    need(b, "batch");
+    const PackedEvent &e = event_at(b, i);
+    if (!b->rank_diagnosed) MISO_FAIL(MISO_EINVAL, "miso_batch_diagnose_rank has not run");
+    const double *s = b->h_rank.data() + b->h_rank_off[i];
+    double *const dst[6] = {rhat_bulk, rhat_fold, ess_bulk, ess_ci_low, ess_ci_high, distinct};
+    for (int k = 0; k < e.K; k++)
+      for (int f = 0; f < 6; f++)
+        if (dst[f]) dst[f][k] = s[6 * k + f];
+  });
+}
+
+int miso_batch_rank_pass_ms(const miso_batch_t *b, float *ms) {
+  return guarded([&] {
+    need(b, "batch");
+    if (ms) *ms = b->rank_ms;
+  });
+}
+
 int miso_batch_pass_ms(const miso_batch_t *b, float *summarize_ms, float *diagnose_ms) {
   return guarded([&] {
     need(b, "batch");

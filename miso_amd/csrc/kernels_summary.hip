@@ -16,21 +16,10 @@
 #include "compare_column.hpp"
 #include "device.hpp"
 #include "miso_detmath.h"
+#include "order_key.hpp"
 #include "text_digits.hpp"
 
 namespace miso {
-
-// (every NaN gets the largest key, whatever its sign bit: numpy's sort -- the reference's, credible_intervals.py:53 --
-// puts NaN behind +inf; the bit pattern alone would put a sign-bit NaN in front of -inf)
-__device__ __forceinline__ uint64_t order_key(double x) {
-  const uint64_t u = __double_as_longlong(x);
-  if (x != x) return ~0ull;
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(uint64_t k) {
-  const uint64_t u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double(u);
-}
 
 // TEXT: summarise what summarize_miso READS, not what the sampler computed: every sample as "%.4f" prints it
 // (text_digits.hpp text_digits).

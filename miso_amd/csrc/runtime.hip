@@ -32,6 +32,8 @@ __global__ void match_kernel(const MatchEvent *, const int2 *, const int *, cons
                              const int *, const int *, const int *, int, int, int, int, int, uint32_t *, uint16_t *);
 __global__ void summarize_kernel(const DevEvent *, const unsigned char *, int, int, int, int, const uint64_t *, double *, int);
 __global__ void diagnose_kernel(const DevEvent *, const unsigned char *, int, int, int, int, double, int, const uint64_t *, double *);
+__global__ void diagnose_rank_kernel(const DevEvent *, const unsigned char *, int, int, int, int, int, int, int, double, const uint64_t *,
+                                     double *);
 __global__ void selftest_detmath_kernel(const double *, int, double *, double *, double *, double *);
 __global__ void selftest_philox_kernel(const uint32_t *, int, uint32_t *);
 
@@ -595,7 +597,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   }
   HIP_OK(hipEventRecord(ev1, stream));
   start_clock_probe();
-  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; exact_compared = false; diagnosed = false;
+  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; exact_compared = false; diagnosed = false; rank_diagnosed = false;
 }
 
 // The launch's sizes and switches, read once per launch.
@@ -1464,6 +1466,58 @@ void miso_batch::diagnose(int noChains) {
   diagnosed = true;
 }
 
+// Rank-normalised chain diagnostics of every (event, isoform) column (kernels_diagnose_rank.hip): bulk and
+// folded split R-hat, bulk effective sample size, and the effective sample size of the indicators of the two bounds of
+// the `confidence_level` interval, taken as summarize() takes them but over the N used draws.  Preconditions as diagnose().
+void miso_batch::diagnose_rank(int noChains, double confidence_level) {
+  if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (noChains < 0) MISO_FAIL(MISO_EINVAL, "Invalid number of chains");
+  if (noChains == 0 && adopted) MISO_FAIL(MISO_EINVAL, "Adopted samples have no chain count of their own: give noChains");
+  const int C = noChains ? noChains : p.noChains;
+  const int Sn = S();
+  const int n_draws = Sn / C, h = n_draws / 2;
+  if (h < 4) MISO_FAIL(MISO_EINVAL, "Too few samples per chain for diagnostics");
+  // (in 64 bits: C is the caller's)
+  const int64_t M64 = 2 * static_cast<int64_t>(C), N64 = M64 * h;
+  const double alpha = 1 - confidence_level;
+  const double lo_d = std::floor((alpha / 2) * static_cast<double>(N64) + 0.5) - 1;
+  const double hi_d = std::floor((1 - alpha / 2) * static_cast<double>(N64) + 0.5) - 1;
+  if (!(lo_d > 0 && hi_d > 0 && hi_d < static_cast<double>(N64)))
+    MISO_FAIL(MISO_EINVAL, "Too few samples for a credible interval");
+  if (N64 > RANK_MAX_DRAWS) MISO_FAIL(MISO_EINVAL, "Too many samples for rank diagnostics");
+  if (C > RANK_MAX_CHAINS) MISO_FAIL(MISO_EINVAL, "Too many chains for rank diagnostics");
+  const int M = static_cast<int>(M64), N = static_cast<int>(N64);
+  const int lo = static_cast<int>(lo_d), hi = static_cast<int>(hi_d);
+  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  HIP_OK(hipSetDevice(device));
+  const int n = static_cast<int>(events.size());
+  h_rank_off.assign(n, 0);
+  uint64_t off = 0; int kmax = 1;
+  for (int i = 0; i < n; i++) { h_rank_off[i] = off; off += 6 * events[i].K; kmax = std::max(kmax, events[i].K); }
+  h_rank.assign(off, 0.0);
+  if (n == 0) { rank_diagnosed = true; return; }
+  int P = 8;                                          // the sort's size: the power of two >= N
+  while (P < N) P <<= 1;
+  // the draws, the sort's keys, then the larger of the per-sequence scratch and the 16-bit ranks
+  const size_t dyn = (static_cast<size_t>(N) + P + std::max<size_t>(3 * static_cast<size_t>(M), (static_cast<size_t>(N) + 3) / 4)) * sizeof(double);
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(diagnose_rank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             static_cast<int>(dyn)));
+  uint64_t *d_off = nullptr; double *d_rank = nullptr;
+  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
+  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_rank), off * sizeof(double)));
+  HIP_OK(hipMemcpyAsync(d_off, h_rank_off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  PassTimer timer(stream, pass_ev0, pass_ev1);
+  hipLaunchKernelGGL(diagnose_rank_kernel, dim3(n, kmax), dim3(256), dyn, stream, d_events, d_out, n, C, n_draws, h, P, lo, hi,
+                     std::log10(static_cast<double>(N)), d_off, d_rank);
+  HIP_OK(hipGetLastError());
+  timer.stop();
+  HIP_OK(hipMemcpyAsync(h_rank.data(), d_rank, off * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  (void) hipFree(d_off); (void) hipFree(d_rank);
+  rank_ms = timer.ms();
+  rank_diagnosed = true;
+}
+
 // Two-sample comparison of this batch (sample 1) with `other` (sample 2), event by event and
 // index-paired (hypothesis_test.py:89-179): both must hold the same events in the same order.
 void miso_batch::compare(miso_batch &other, double smoothing) {
@@ -1614,7 +1668,7 @@ void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
   n_k2 = n_k2w = n_gen = 0; k2[0].count = k2[1].count = 0; gen_runs.clear(); plan = LaunchPlan{};
-  uploaded = launched = true; downloaded = false; summarized = compared = exact_compared = diagnosed = false; adopted = true;
+  uploaded = launched = true; downloaded = false; summarized = compared = exact_compared = diagnosed = rank_diagnosed = false; adopted = true;
 }
 
 void miso_batch::download() {

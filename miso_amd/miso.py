@@ -133,8 +133,9 @@ class GenesDispatcher(object):
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
-                 exact_compare=False, delta_thresholds=None, exact_paired=False):
+                 exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False):
         self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
+        self.rank_diagnostics = bool(rank_diagnostics)   # --rank-diagnostics: six more columns in every diagnostics table
         self.summary_only = bool(summary_only)
         self.exact = bool(exact)       # --exact: handed on to every worker
         # --exact-compare / --exact-paired-compare: beside the `.miso_bf` table the exact comparison's `.miso_bf_exact` (compare.py), merged like a
@@ -302,7 +303,7 @@ class GenesDispatcher(object):
                     dparts = ["%s.gpu%d" % (t, batch_num) for t, _ in self.diag_tables]
                     for (_, plist), dp in zip(self.diag_tables, dparts):
                         plist.append(dp)
-                    cmd += ["--diagnostics-files"] + dparts
+                    cmd += ["--diagnostics-files"] + dparts + (["--rank-diagnostics"] if self.rank_diagnostics else [])
             else:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compute-genes-from-file", fname,
                        self.bam_filename, self.output_dir]
@@ -312,7 +313,7 @@ class GenesDispatcher(object):
                         cmd += ["--no-miso-files"]
                 if self.diag_tables:
                     self.diag_tables[0][1].append("%s.gpu%d" % (self.diag_tables[0][0], batch_num))
-                    cmd += ["--diagnostics-file", self.diag_tables[0][1][-1]]
+                    cmd += ["--diagnostics-file", self.diag_tables[0][1][-1]] + (["--rank-diagnostics"] if self.rank_diagnostics else [])
             # more chunks than GPUs (-p above the GPU count) share the GPUs round robin
             cmd += ["--read-len", str(self.read_len), "--device", str(batch_num % self.n_gpus),
                     "--first-event-id", str(first)]
@@ -407,7 +408,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
-                          exact_compare=False, delta_thresholds=None, exact_paired=False):
+                          exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -420,7 +421,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
-                           delta_thresholds=delta_thresholds).run()
+                           delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics).run()
 
 
 def main(argv=None):
@@ -447,6 +448,10 @@ def main(argv=None):
                     help="also write OUT/summary/<OUT>.miso_diag: per event the split R-hat of its chains, the effective "
                          "sample size and the Monte-Carlo standard error of the Psi mean, computed on the GPU during the run; "
                          "with --compare one table per label: OUT/<label>/summary/<label>.miso_diag")
+    ap.add_argument("--rank-diagnostics", action="store_true",
+                    help="with --diagnostics: six more columns per event from the rank-normalised pass -- the larger of the bulk "
+                         "and the folded rank R-hat, the bulk effective sample size, the effective sample size of the 95 %% "
+                         "credible interval's two bounds and the smaller of them, and the number of distinct draws")
     ap.add_argument("--exact", action="store_true",
                     help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
                          "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
@@ -484,6 +489,8 @@ def main(argv=None):
     Settings.load(settings_filename)
     if a.exact_paired and a.paired_end is None:     # argument errors, before any work
         ap.error("--exact-paired goes with --paired-end")
+    if a.rank_diagnostics and not a.diagnostics:
+        ap.error("--rank-diagnostics goes with --diagnostics")
     if a.exact_compare:
         if a.compare is None:
             ap.error("--exact-compare goes with --compare")
@@ -529,7 +536,7 @@ def main(argv=None):
                                        labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics,
                                        exact=a.exact, exact_compare=a.exact_compare or a.exact_paired_compare,
                                        exact_paired=a.exact_paired,
-                                       delta_thresholds=a.delta_psi_thresholds)
+                                       delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

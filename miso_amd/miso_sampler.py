@@ -165,7 +165,8 @@ class MISOSampler:
     def run_sampler_batch(self, num_iters, events, num_chains=6, burn_in=1000, lag=2,
                           start_cond=pysplicing.MISO_START_AUTO,
                           stop_cond=pysplicing.MISO_STOP_FIXEDNO, seed=None, first_event_id=0,
-                          verbose=False, summary_file=None, confidence_level=0.95, threads=0, diagnostics_file=None):
+                          verbose=False, summary_file=None, confidence_level=0.95, threads=0, diagnostics_file=None,
+                          rank_diagnostics=False):
         """events: list of (reads, gene, output_file[, prior_params[, event_id]]); `reads` is the
         reference's (positions 0-based, cigars) pair or an AlnRegion; event_id pins the event's
         random stream (default: first_event_id + its position among the events actually sampled).  Same per-event skip rules as run_sampler
@@ -175,14 +176,15 @@ class MISOSampler:
         Returns the list of written file names (None for skipped events).
         summary_file: also write the `summarize_miso` table (samples_utils.py:263-329) for the
         events of this batch, from means / credible intervals computed on the device.
-        diagnostics_file: also write the chain diagnostics table (diagnostics.py) of these events.
+        diagnostics_file: also write the chain diagnostics table (diagnostics.py) of these events; rank_diagnostics: with
+        the six columns of the rank-normalised pass.
         = prepare_batch (host: skip rules, reads into the batch) + finish_batch (GPU + files); a caller
         with several batches can overlap one's finish with the next one's prepare (run_miso.py)."""
         state = self.prepare_batch(num_iters, events, num_chains=num_chains, burn_in=burn_in, lag=lag,
                                    start_cond=start_cond, stop_cond=stop_cond, verbose=verbose)
         return self.finish_batch(state, seed=seed, first_event_id=first_event_id, verbose=verbose,
                                  summary_file=summary_file, confidence_level=confidence_level,
-                                 threads=threads, diagnostics_file=diagnostics_file)
+                                 threads=threads, diagnostics_file=diagnostics_file, rank_diagnostics=rank_diagnostics)
 
     def exact_paired(self):
         """the paired-end exact-posterior mode is asked for: params["exact_paired"], else MISO_EXACT_PAIRED=1; never on a
@@ -324,7 +326,7 @@ class MISOSampler:
         return (batch, slots, written, int(num_iters), int(burn_in), int(lag))
 
     def finish_batch(self, state, seed=None, first_event_id=0, verbose=False, summary_file=None,
-                     confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None):
+                     confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None, rank_diagnostics=False):
         """Launch, then the event's outputs.  write_files=False (with a summary_file): no per-event `.miso` file --
         the posterior means and credible intervals that `summarize_miso` would compute from those files
         (samples_utils.py:263-329) come from the device, summarised from the four-decimal text the file WOULD hold.
@@ -332,7 +334,8 @@ class MISOSampler:
         launch beside this one's outputs."""
         self.launch_batch(state, seed=seed, first_event_id=first_event_id)
         return self.output_batch(state, verbose=verbose, summary_file=summary_file, confidence_level=confidence_level,
-                                 threads=threads, write_files=write_files, diagnostics_file=diagnostics_file)
+                                 threads=threads, write_files=write_files, diagnostics_file=diagnostics_file,
+                                 rank_diagnostics=rank_diagnostics)
 
     def launch_batch(self, state, seed=None, first_event_id=0):
         """Upload, sample, download (native code, the interpreter lock released throughout)."""
@@ -362,12 +365,13 @@ class MISOSampler:
                    ",".join(str(iso.genomic_end) for iso in gene.isoforms)))
 
     def output_batch(self, state, verbose=False, summary_file=None, confidence_level=0.95, threads=0,
-                     write_files=True, diagnostics_file=None):
+                     write_files=True, diagnostics_file=None, rank_diagnostics=False):
         """The `.miso` files and / or the summary table of a launched batch.  The header's run-dependent fields are
         formatted natively for the whole batch (miso_batch_header_fields); miso_header() below is the same line field
         by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte).
         diagnostics_file: the chain diagnostics table of the written events (diagnostics.py), from the full-precision
-        samples resident on the device; nothing else changes with it."""
+        samples resident on the device; nothing else changes with it.  rank_diagnostics: that table with the six columns
+        of the rank-normalised pass."""
         batch, slots, written, num_iters, burn_in, lag = state
         if not slots:
             return written
@@ -388,6 +392,14 @@ class MISOSampler:
             diags = batch.diagnostics_many([idx for _, idx, _, _ in slots], [len(gene.isoforms) for _, _, gene, _ in slots])
             n_chains = int(batch.params.noChains)
             n_samples = n_chains * (num_iters - burn_in) // lag
+            if rank_diagnostics:
+                ranks = [None] * len(slots)
+                try:
+                    batch.diagnose_rank(None, diagnostics.RANK_CONFIDENCE_LEVEL)
+                    ranks = batch.rank_diagnostics_many([idx for _, idx, _, _ in slots],
+                                                        [len(gene.isoforms) for _, _, gene, _ in slots])
+                except capi.InternalError as e:
+                    print(diagnostics.rank_notice("%d events of %d samples in %d chains" % (len(slots), n_samples, n_chains), e))
         for j, ((i, idx, gene, out), (unassigned, pa, counts, assigned)) in enumerate(zip(slots, fields)):
             if unassigned:                                                # miso_sampler.py:352-354
                 if verbose:
@@ -409,14 +421,15 @@ class MISOSampler:
                 hdr.update(kv.split("=", 1) for kv in tail.rstrip("\n").split("\t"))
                 rows.append((name,) + tuple(sums[j]) + (hdr,))
             if diagnostics_file is not None:
-                diag_rows.append((os.path.basename(out)[:-len(".miso")],) + tuple(diags[j]) + (n_samples, n_chains))
+                diag_rows.append((os.path.basename(out)[:-len(".miso")],) + tuple(diags[j]) + (n_samples, n_chains)
+                                 + ((ranks[j],) if rank_diagnostics else ()))
         t2 = time.time()
         if write_files:
             batch.write_miso_files(idxs, paths, headers, threads)
         if summary_file is not None:
             summary.write_summary(summary_file, rows)
         if diagnostics_file is not None:
-            diagnostics.write_diagnostics(diagnostics_file, diag_rows)
+            diagnostics.write_diagnostics(diagnostics_file, diag_rows, rank=rank_diagnostics)
         if timing:
             print("[miso] batch of %d events: headers %.2f s, .miso files / table %.2f s"
                   % (len(slots), t2 - t1, time.time() - t2))
@@ -426,7 +439,8 @@ class MISOSampler:
     def run_comparison_batch(self, num_iters, events1, events2, comparison_file, num_chains=6,
                              burn_in=1000, lag=2, seed=None, seed2=None, first_event_id=0,
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
-                             diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None):
+                             diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None,
+                             rank_diagnostics=False):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -436,7 +450,8 @@ class MISOSampler:
         full event list -- so that skipped events and chunking change nobody's random stream; default
         first_event_id + position among the events that are run.
         diagnostics_files (optional): (file1, file2), the chain diagnostics table (diagnostics.py) of each sample's
-        written events, from the samples resident on the device.
+        written events, from the samples resident on the device; rank_diagnostics: with the six columns of the
+        rank-normalised pass.
         exact_comparison_file (optional; the exact-posterior mode only): the `.miso_bf_exact` table of the exact comparison
         (compare.write_exact_comparison) with P(|delta psi| >= t) for every t of delta_thresholds (default 0.1, 0.2).  A
         paired-end sampler with the paired exact mode compares through MISOCompareBatch(exact_paired_compare=)."""
@@ -470,6 +485,8 @@ class MISOSampler:
                 kw["event_ids"] = tuple(int(event_ids[p[0]]) for p in keep)
             if diagnostics_files is not None:
                 kw["diagnostics"] = True
+                if rank_diagnostics:
+                    kw["rank_diagnostics"] = True
             if not self.paired_end and int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0):
                 kw["exact"] = True          # the exact-posterior mode, as in prepare_batch
             if self.exact_paired():
@@ -482,6 +499,11 @@ class MISOSampler:
                 int(self.params["overhang_len"]), int(num_chains), **kw)
             r1, r2, cmp = res[:3]
             n_samples = int(num_chains) * (int(num_iters) - int(burn_in)) // int(lag)
+            if diagnostics_files is not None and rank_diagnostics:
+                for which, refused in enumerate(res[3][2]):
+                    if refused is not None:
+                        print(diagnostics.rank_notice("sample %d's %d events of %d samples in %d chains"
+                                                      % (which + 1, len(keep), n_samples, int(num_chains)), refused))
             for j, ((i, gene, p1, p2), a, b, c) in enumerate(zip(keep, r1, r2, cmp)):
                 f1 = self._finish(a, gene, p1[4], num_iters, burn_in, lag, verbose)
                 f2 = self._finish(b, gene, p2[4], num_iters, burn_in, lag, verbose)
@@ -489,8 +511,10 @@ class MISOSampler:
                 if diagnostics_files is not None:
                     for which, f in enumerate((f1, f2)):
                         if f is not None:
-                            diag_rows[which].append((os.path.basename(f)[:-len(".miso")],) + tuple(res[3][which][j])
-                                                    + (n_samples, int(num_chains)))
+                            d = res[3][which][j]
+                            diag_rows[which].append((os.path.basename(f)[:-len(".miso")],) + tuple(d[:4])
+                                                    + (n_samples, int(num_chains))
+                                                    + (((d[4:] if len(d) == 10 else None),) if rank_diagnostics else ()))
                 if f1 is not None and f2 is not None:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
@@ -501,7 +525,7 @@ class MISOSampler:
             compare.write_exact_comparison(exact_comparison_file, xrows, xthr)
         if diagnostics_files is not None:
             for f, drows in zip(diagnostics_files, diag_rows):
-                diagnostics.write_diagnostics(f, drows)
+                diagnostics.write_diagnostics(f, drows, rank=rank_diagnostics)
         return written
 
     # -- shared pieces -------------------------------------------------------------------------

@@ -426,21 +426,43 @@ static PyObject *results_list(miso_batch_t *b, Py_ssize_t n, double conf) {
   return out;
 }
 
-/* chain diagnostics of a finished batch: per event (rhat, ess, mcse, lag), noiso values each */
-static PyObject *diagnostics_list(miso_batch_t *b, Py_ssize_t n) {
-  Py_ssize_t i; int rc;
+/* chain diagnostics of a finished batch: per event (rhat, ess, mcse, lag), noiso values each.  rank (may be NULL): also
+   the rank-normalised pass at the 95 % interval (miso_batch_diagnose_rank), whose (rhat_bulk, rhat_fold, ess_bulk,
+   ess_ci_low, ess_ci_high, distinct) follow the four; where that pass refuses the batch's shape (MISO_EINVAL) the tuples
+   keep their four elements and *rank becomes its message, else None */
+static PyObject *diagnostics_list(miso_batch_t *b, Py_ssize_t n, PyObject **rank) {
+  Py_ssize_t i; int rc, ranked = 0;
   PyObject *out;
   if (n > 0 && (rc = miso_batch_diagnose(b, 0))) return raise_miso(rc);
+  if (rank) {
+    *rank = NULL;
+    if (n > 0 && (rc = miso_batch_diagnose_rank(b, 0, 0.95))) {
+      if (rc != MISO_EINVAL) return raise_miso(rc);
+      if (!(*rank = PyUnicode_FromString(miso_last_error()))) return NULL;
+    } else {
+      ranked = n > 0;
+      *rank = Py_None; Py_INCREF(Py_None);
+    }
+  }
   out = PyList_New(n);
   for (i = 0; out && i < n; i++) {
     int K; double r[MISO_MAX_ISOFORMS], e[MISO_MAX_ISOFORMS], m[MISO_MAX_ISOFORMS], l[MISO_MAX_ISOFORMS];
     PyObject *t;
     if ((rc = miso_batch_event_info(b, (int) i, &K, NULL, NULL, NULL)) ||
         (rc = miso_batch_get_diagnostics(b, (int) i, r, e, m, l))) { raise_miso(rc); Py_CLEAR(out); break; }
-    t = Py_BuildValue("(NNNN)", from_doubles(r, K), from_doubles(e, K), from_doubles(m, K), from_doubles(l, K));
+    if (ranked) {
+      double q[6][MISO_MAX_ISOFORMS];
+      if ((rc = miso_batch_get_rank_diagnostics(b, (int) i, q[0], q[1], q[2], q[3], q[4], q[5]))) { raise_miso(rc); Py_CLEAR(out); break; }
+      t = Py_BuildValue("(NNNNNNNNNN)", from_doubles(r, K), from_doubles(e, K), from_doubles(m, K), from_doubles(l, K),
+                        from_doubles(q[0], K), from_doubles(q[1], K), from_doubles(q[2], K), from_doubles(q[3], K),
+                        from_doubles(q[4], K), from_doubles(q[5], K));
+    } else {
+      t = Py_BuildValue("(NNNN)", from_doubles(r, K), from_doubles(e, K), from_doubles(m, K), from_doubles(l, K));
+    }
     if (!t) { Py_CLEAR(out); break; }
     PyList_SET_ITEM(out, i, t);
   }
+  if (!out && rank) Py_CLEAR(*rank);
   return out;
 }
 
@@ -465,11 +487,12 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
                            "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired",
-                           "exact_paired_compare", NULL};
+                           "exact_paired_compare", "rank_diagnostics", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL, *xcobj = NULL, *xc = NULL;
   PyObject *xpobj = NULL;   /* exact_paired_compare=(z, ...): the same through miso_batch_compare_exact_paired */
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
+  int rank_diagnostics = 0;         /* with diagnostics=True: the rank-normalised pass too (diagnostics_list) */
   int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
   int exact_paired = 0;             /* exact_paired=True (with paired=): miso_batch_set_exact_paired */
   int readLength, iters = 5000, burn = 500, lag = 10, overhang = 1, chains = 6;
@@ -477,10 +500,11 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpO", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOp", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
                                    &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
-                                   &exact_paired, &xpobj)) return NULL;
+                                   &exact_paired, &xpobj, &rank_diagnostics)) return NULL;
+  if (rank_diagnostics && !diagnostics) { PyErr_SetString(PyExc_ValueError, "rank_diagnostics requires diagnostics=True"); return NULL; }
   if (xcobj == Py_None) xcobj = NULL;
   if (xpobj == Py_None) xpobj = NULL;
   if (xpobj) {
@@ -544,11 +568,15 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     if (!t) goto done;
     PyList_SET_ITEM(cmp, i, t);
   }
-  /* diagnostics=True: a fourth element, per sample the events' (rhat, ess, mcse, lag) (miso_batch_diagnose) */
+  /* diagnostics=True: a fourth element, per sample the events' (rhat, ess, mcse, lag) (miso_batch_diagnose); with
+     rank_diagnostics=True the six arrays of miso_batch_diagnose_rank after the four, and a third element: per sample
+     None or the message with which that pass refused the sample's shape (its events then keep four arrays) */
   if (diagnostics) {
-    PyObject *d1 = diagnostics_list(b1, n), *d2 = d1 ? diagnostics_list(b2, n) : NULL;
-    if (d2) dg = PyTuple_Pack(2, d1, d2);
-    Py_XDECREF(d1); Py_XDECREF(d2);
+    PyObject *k1 = NULL, *k2 = NULL;
+    PyObject *d1 = diagnostics_list(b1, n, rank_diagnostics ? &k1 : NULL);
+    PyObject *d2 = d1 ? diagnostics_list(b2, n, rank_diagnostics ? &k2 : NULL) : NULL;
+    if (d2) dg = rank_diagnostics ? Py_BuildValue("(OO(OO))", d1, d2, k1, k2) : PyTuple_Pack(2, d1, d2);
+    Py_XDECREF(d1); Py_XDECREF(d2); Py_XDECREF(k1); Py_XDECREF(k2);
     if (!dg) goto done;
     out = Py_BuildValue("(OOOO)", r1, r2, cmp, dg);
   } else {

@@ -147,11 +147,12 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
-                     diagnostics_file=None, exact=None, exact_paired=None):
+                     diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
-    diagnostics table of this run (diagnostics.py), per launch from the resident samples, merged like the summary parts.
+    diagnostics table of this run (diagnostics.py), per launch from the resident samples, merged like the summary parts;
+    rank_diagnostics: that table with the six columns of the rank-normalised pass.
     exact: single-end two-isoform events take the exact-posterior mode (None: the settings' `exact` key).
     exact_paired: the same switch for the paired-end two-isoform events of a --paired-end run (None: the settings'
     `exact_paired` key); nothing on a single-end run."""
@@ -274,7 +275,7 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart):
                 launched.result()
                 return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files,
-                                            diagnostics_file=dpart)
+                                            diagnostics_file=dpart, rank_diagnostics=rank_diagnostics)
             in_flight.append(out.submit(outputs))
         for f in in_flight:
             written += f.result()
@@ -323,7 +324,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
-                     exact_comparison_file=None, delta_thresholds=None, exact_paired=None):
+                     exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -332,7 +333,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     coverage filter entry k passes, "1", "2" or "1,2".  An entry is collected only in those samples; one that passes
     in one sample only is sampled there alone (with that sample's seed) and is not compared.
     diagnostics_files: (file1, file2), each sample's chain diagnostics table (diagnostics.py), parts merged like the
-    comparison's.
+    comparison's; rank_diagnostics: with the six columns of the rank-normalised pass.
     exact_comparison_file (the exact mode only): the `.miso_bf_exact` table of the exact comparison (compare.py
     write_exact_comparison), parts merged like the comparison's; delta_thresholds: its thresholds t of P(|delta psi| >= t)."""
     for d in (output_dir1, output_dir2):
@@ -394,7 +395,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                      first_event_id=first_event_id + lo, verbose=verbose,
                                      event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
                                      diagnostics_files=dparts, exact_comparison_file=xpart,
-                                     delta_thresholds=delta_thresholds)
+                                     delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics)
     merge_tables(parts, comparison_file)
     if exact_comparison_file is not None:
         merge_tables(xparts, exact_comparison_file)
@@ -420,7 +421,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                 dpart = "%s.alone" % diagnostics_files[int(which) - 1]
                 diag_parts[int(which) - 1].append(dpart)
             sampler.run_sampler_batch(p["num_iters"], alone, num_chains=p["num_chains"], burn_in=p["burn_in"],
-                                      lag=p["lag"], seed=s, verbose=verbose, diagnostics_file=dpart)
+                                      lag=p["lag"], seed=s, verbose=verbose, diagnostics_file=dpart,
+                                      rank_diagnostics=rank_diagnostics)
     if diagnostics_files is not None:
         for which in (0, 1):
             merge_tables(diag_parts[which], diagnostics_files[which])
@@ -469,6 +471,8 @@ def main(argv=None):
                     help="also write the chain diagnostics table of this run (split R-hat, ESS, MCSE; device-side)")
     ap.add_argument("--diagnostics-files", nargs=2, default=None, metavar=("FILE1", "FILE2"),
                     help="with --compare-genes-from-file: the chain diagnostics table of each sample")
+    ap.add_argument("--rank-diagnostics", action="store_true",
+                    help="with --diagnostics-file(s): six more columns from the rank-normalised pass")
     ap.add_argument("--no-miso-files", action="store_true",
                     help="with --summary-file: only the table, no per-event .miso files")
     ap.add_argument("--exact", action="store_true",
@@ -508,6 +512,9 @@ def main(argv=None):
     if a.diagnostics_files and not a.compare_genes_from_file:
         print("Error: --diagnostics-files goes with --compare-genes-from-file.")
         return 1
+    if a.rank_diagnostics and not (a.diagnostics_file or a.diagnostics_files):
+        print("Error: --rank-diagnostics goes with --diagnostics-file or --diagnostics-files.")
+        return 1
     if a.exact_comparison_file is not None:
         if paired_end and a.compare_genes_from_file:
             if not exact_paired:
@@ -532,7 +539,8 @@ def main(argv=None):
                              samples=samples, diagnostics_files=a.diagnostics_files, exact=exact,
                              exact_comparison_file=(os.path.abspath(os.path.expanduser(a.exact_comparison_file))
                                                     if a.exact_comparison_file else None),
-                             delta_thresholds=a.delta_psi_thresholds, exact_paired=exact_paired)
+                             delta_thresholds=a.delta_psi_thresholds, exact_paired=exact_paired,
+                             rank_diagnostics=a.rank_diagnostics)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -547,7 +555,8 @@ def main(argv=None):
                          seed=a.seed, first_event_id=a.first_event_id, device=a.device, event_ids=numbers,
                          summary_file=a.summary_file,
                          write_files=not (a.no_miso_files and a.summary_file),
-                         diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired)
+                         diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired,
+                         rank_diagnostics=a.rank_diagnostics)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")

@@ -346,33 +346,47 @@ def _diagnosable(S, num_chains, n_events):
     return False
 
 
-def _diagnose_rows(b, names, headers, Ks, S, num_chains, rows, status=None):
+def _rank_diagnostics(b, num_chains, Ks, what):
+    """Per event the six arrays of the rank pass, or None where the pass refuses the batch's shape (one notice line)."""
+    try:
+        b.diagnose_rank(num_chains, diagnostics.RANK_CONFIDENCE_LEVEL)
+    except capi.InternalError as e:
+        print(diagnostics.rank_notice(what, e))
+        return [None] * len(Ks)
+    return b.rank_diagnostics_many(range(len(Ks)), Ks)
+
+
+def _diagnose_rows(b, names, headers, Ks, S, num_chains, rows, status=None, rank=False):
     b.diagnose(num_chains)
     diags = b.diagnostics_many(range(len(names)), Ks)
+    if rank:
+        ranks = _rank_diagnostics(b, num_chains, Ks, "%d events of %d samples in %d chains" % (len(names), S, num_chains))
     for i, (name, hdr) in enumerate(zip(names, headers)):
         if status is not None and status[i]:
             continue
         warn = diagnostics.header_mismatch(name, hdr, S, num_chains)
         if warn:
             print(warn)
-        rows.append((name,) + tuple(diags[i]) + (S, num_chains))
+        rows.append((name,) + tuple(diags[i]) + (S, num_chains) + ((ranks[i],) if rank else ()))
 
 
-def _diagnose_parsed(events, num_chains, device, rows, stats):
+def _diagnose_parsed(events, num_chains, device, rows, stats, rank=False):
     """Diagnostics rows of host-parsed events (name, samples [S, K], header dict)."""
     for S, group in sorted(_by_sample_count(events).items()):
         if not _diagnosable(S, num_chains, len(group)):
             continue
         b = capi.SamplesBatch([g[1] for g in group], device=device)
         stats.stage("decode")
-        _diagnose_rows(b, [g[0] for g in group], [g[2] for g in group], [g[1].shape[1] for g in group], S, num_chains, rows)
+        _diagnose_rows(b, [g[0] for g in group], [g[2] for g in group], [g[1].shape[1] for g in group], S, num_chains, rows,
+                       rank=rank)
         stats.stage("diagnose")
 
 
-def diagnose_sampler_results(samples_dir, diag_filename, num_chains=None, device=0, decoder=None):
+def diagnose_sampler_results(samples_dir, diag_filename, num_chains=None, device=0, decoder=None, rank=False):
     """One diagnostics row per event of samples_dir (`.miso` files and `.miso_db` rows): what the files' four-decimal
     values say about their chains.  num_chains: the chains the rows interleave (row s is chain s % num_chains), default
-    the settings' num_chains; an event whose header disagrees with its row count is named and diagnosed all the same."""
+    the settings' num_chains; an event whose header disagrees with its row count is named and diagnosed all the same.
+    rank: also the six columns of the rank-normalised pass (diagnostics.py)."""
     if num_chains is None:
         num_chains = int(Settings.get_sampler_params()["num_chains"])
     num_chains = int(num_chains)
@@ -387,7 +401,7 @@ def diagnose_sampler_results(samples_dir, diag_filename, num_chains=None, device
         stats.stage("read")
         events = _load_all(files + evs)
         stats.stage("parse")
-        _diagnose_parsed(events, num_chains, device, rows, stats)
+        _diagnose_parsed(events, num_chains, device, rows, stats, rank)
     else:
         evs = _read_events(files, dbrows)
         stats.stage("read")
@@ -405,14 +419,14 @@ def diagnose_sampler_results(samples_dir, diag_filename, num_chains=None, device
                 b = _text_batch(run, S, device, stats)
                 stats.stage("decode")
                 _diagnose_rows(b, [e.name for e in run], [_header_fields(e.header) for e in run], [e.K for e in run], S,
-                               num_chains, rows, status=b.status)
+                               num_chains, rows, status=b.status, rank=rank)
                 left += [e for i, e in enumerate(run) if b.status[i]]
                 stats.stage("diagnose")
         stats.d["fallback_events"] += [e.name for e in left if e.name not in stats.d["fallback_events"]]
-        _diagnose_parsed(_load_all(left), num_chains, device, rows, stats)
+        _diagnose_parsed(_load_all(left), num_chains, device, rows, stats, rank)
     rows.sort(key=lambda r: r[0])
     os.makedirs(os.path.dirname(os.path.abspath(diag_filename)), exist_ok=True)
-    n = diagnostics.write_diagnostics(diag_filename, rows)
+    n = diagnostics.write_diagnostics(diag_filename, rows, rank=rank)
     stats.stage("write")
     stats.done()
     return n
@@ -775,6 +789,9 @@ def main(argv=None):
                     help="chain diagnostics (split R-hat, ESS, MCSE) of every event: OUTPUT_DIR/summary/<name>.miso_diag")
     ap.add_argument("--num-chains", type=int, default=None,
                     help="with --diagnose-samples: chains the sample rows interleave (default: the settings' num_chains, 6)")
+    ap.add_argument("--rank-diagnostics", action="store_true",
+                    help="with --diagnose-samples: six more columns from the rank-normalised pass (rank R-hat, bulk ESS, ESS of "
+                         "the 95 %% interval's bounds, distinct values)")
     ap.add_argument("--comparison-labels", nargs=2, default=None)
     ap.add_argument("--compare-groups", nargs=3, metavar=("DIR[,DIR...]", "DIR[,DIR...]", "OUTPUT_DIR"),
                     help="every pair of two groups of sample directories (replicates), one .miso_bf per pair")
@@ -791,10 +808,12 @@ def main(argv=None):
         samples_dir, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.diagnose_samples)
         label = os.path.basename(os.path.normpath(samples_dir))
         fname = os.path.join(out_dir, "summary", label + ".miso_diag")
-        n = diagnose_sampler_results(samples_dir, fname, num_chains=a.num_chains, device=a.device)
+        n = diagnose_sampler_results(samples_dir, fname, num_chains=a.num_chains, device=a.device, rank=a.rank_diagnostics)
         print("Diagnosed %d events into %s" % (n, fname))
     elif a.num_chains is not None:
         ap.error("--num-chains goes with --diagnose-samples")
+    elif a.rank_diagnostics:
+        ap.error("--rank-diagnostics goes with --diagnose-samples")
     if a.compare_samples:
         d1, d2, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.compare_samples)
         out, n = output_samples_comparison(d1, d2, out_dir, sample_labels=a.comparison_labels, device=a.device)
