@@ -428,6 +428,34 @@ int miso_batch_compare_exact_paired(miso_batch_t *sample1, miso_batch_t *sample2
    miso_batch_compare_exact_paired stored in this batch, ms; 0 before. */
 int miso_batch_compare_ms(const miso_batch_t *sample1, float *compare_ms, float *exact_compare_ms);
 
+/* The posterior of delta = psi_1 - psi_2 over ALL pairs of the two samples' draws (csrc/kernels_compare_pairs.hip, DESIGN.md
+   section 19): the samples are independent posteriors, so given the draws the law of delta is the empirical law of the
+   M = S1 * S2 differences, not of the index-paired ones.  Preconditions and errors as miso_batch_compare -- both launched
+   (a batch not yet synced is waited for), same device, the same events with the same isoform counts in the same order --
+   except that the two batches' n_samples may differ.
+   Per (event, isoform), with a[0..S1) and b[0..S2) the rows the summaries use and D the multiset of the IEEE doubles a_i - b_j:
+   ci_low / ci_high: the order statistics of D at ranks max(0, floor(alpha/2 M + 0.5) - 1) and floor((1 - alpha/2) M + 0.5) - 1,
+   alpha = 1 - confidence_level (the summaries' rule over M; the lower rank is clamped where they refuse);  median: the order
+   statistic at rank (M - 1) / 2 (the lower median);  a zero is +0.0;  n_gt0 = #{d > 0}, n_lt0 = #{d < 0}, and per threshold
+   n_abs_ge = #{d >= tau} + #{d <= -tau}, exact integers, compared as doubles compare (a decimal difference that equals tau may
+   be the double below it: 0.3 - 0.1 < 0.2).  A column pair with a NaN or an infinity in either column: three NaN, counts 0,
+   finite = 0; likewise every column of an event whose text miso_batch_from_miso_text did not decode (status != 0) in either
+   batch; other columns and events are unaffected.  tau: n_tau thresholds, 0 <= n_tau <= 4, each inside (0, 1);
+   confidence_level inside (0, 1).  MISO_EINVAL, nothing launched: any of these violated, or more than 8192 samples per event
+   in either batch (both sorted columns stay in the workgroup's local memory).  Results are stored in sample1 beside
+   miso_batch_compare's (which they leave as they are); the launch appears in miso_batch_last_kernels as compare_pairs.
+   miso_batch_get_pair_comparison: noiso values each, n_abs_ge noiso x n_tau (isoform-major), *n_pairs = M; any pointer may be
+   NULL. */
+int miso_batch_compare_pairs(miso_batch_t *sample1, miso_batch_t *sample2, double confidence_level, const double *tau, int n_tau);
+/* The same of the draws as the `.miso` files print them: every draw rounded to "%.4f" and read back first, as
+   miso_batch_summarize_as_text does -- what miso_batch_compare_pairs gives for batches made from the files a run writes. */
+int miso_batch_compare_pairs_as_text(miso_batch_t *sample1, miso_batch_t *sample2, double confidence_level, const double *tau,
+                                     int n_tau);
+int miso_batch_get_pair_comparison(const miso_batch_t *sample1, int event_index, double *median, double *ci_low, double *ci_high,
+                                   int64_t *n_gt0, int64_t *n_lt0, int64_t *n_abs_ge, int32_t *finite, int64_t *n_pairs);
+/* Kernel time (HIP events) of the last miso_batch_compare_pairs stored in this batch, ms; 0 before. */
+int miso_batch_compare_pairs_ms(const miso_batch_t *sample1, float *ms);
+
 /* Every pair of two groups of samples (biological replicates) in one device pass.  group1[i], group2[j]: batches that
    hold the SAME events in the same order with the same n_samples, on the same device (what miso_batch_compare requires of
    its two); n1, n2 >= 1.  out: n1 * n2 * tot doubles, tot = sum over events of 4 * noiso; pair (i, j), event e, isoform k

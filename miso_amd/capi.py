@@ -436,6 +436,39 @@ class Batch:
         check(lib().miso_batch_get_exact_comparison(self.handle, int(i), *[C.byref(x) for x in v], _p(cdf), C.byref(was)))
         return tuple(x.value for x in v) + (cdf,) if was.value else None
 
+    def compare_pairs(self, other, confidence_level=0.95, thresholds=(0.1, 0.2), as_text=False):
+        """The posterior of delta psi = psi_1 - psi_2 over ALL pairs of this batch's draws and `other`'s (same events, same
+        order; the sample counts may differ, 8192 per event at most) on the device: median, credible interval and exact
+        counts of the S1 * S2 differences (miso_batch_compare_pairs in include/miso_amd.h).  thresholds: at
+        most 4, each inside (0, 1).  The results stand beside compare()'s.  as_text: of the draws as the `.miso` files print
+        them, "%.4f" (miso_batch_compare_pairs_as_text)."""
+        tt = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        f = lib().miso_batch_compare_pairs_as_text if as_text else lib().miso_batch_compare_pairs
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]
+        check(f(self.handle, other.handle, C.c_double(confidence_level), _p(tt), C.c_int(len(tt))))
+        self._pairs_nt = len(tt)
+
+    def pair_comparison(self, i):
+        """(median[K], ci_low[K], ci_high[K], n_gt0[K], n_lt0[K], n_abs_ge[K, n_tau], finite[K], n_pairs) of event i after
+        compare_pairs(): the counts as int64, finite as bool; a probability is count / n_pairs."""
+        K = C.c_int()
+        check(lib().miso_batch_event_info(self.handle, i, C.byref(K), None, None, None))
+        nt = getattr(self, "_pairs_nt", 0)
+        med, lo, hi = (np.zeros(K.value) for _ in range(3))
+        gt, lt = np.zeros(K.value, np.int64), np.zeros(K.value, np.int64)
+        ge = np.zeros((K.value, nt), np.int64)
+        fin = np.zeros(K.value, np.int32)
+        M = C.c_int64(0)
+        check(lib().miso_batch_get_pair_comparison(self.handle, int(i), _p(med), _p(lo), _p(hi), _p(gt), _p(lt), _p(ge), _p(fin),
+                                                   C.byref(M)))
+        return med, lo, hi, gt, lt, ge, fin.astype(bool), int(M.value)
+
+    def compare_pairs_ms(self):
+        """Kernel time of the last compare_pairs() stored in this batch (HIP events), ms."""
+        a = C.c_float(0)
+        check(lib().miso_batch_compare_pairs_ms(self.handle, C.byref(a)))
+        return float(a.value)
+
     def compare_ms(self):
         """(kernel ms of the last compare(), of the last compare_exact() or compare_exact_paired()) stored in this batch"""
         a, b = C.c_float(0), C.c_float(0)

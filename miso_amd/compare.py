@@ -112,3 +112,48 @@ def write_exact_comparison(filename, rows, thresholds):
             f.write(exact_comparison_line(*row, thresholds=thresholds) + "\n")
             n += 1
     return n
+
+
+# ---- the all-pairs table, `<label1>_vs_<label2>.miso_dpsi` beside the `.miso_bf` ----
+DPSI_FIELDS = ["delta_psi_median", "delta_psi_ci_low", "delta_psi_ci_high", "prob_diff_gt_0", "prob_diff_lt_0"]
+
+
+def dpsi_header_fields(thresholds):
+    return HEADER_FIELDS + DPSI_FIELDS + ["prob_abs_diff_ge_%g" % t for t in thresholds]
+
+
+def dpsi_fields(pairs, n_thresholds):
+    """pairs = (median[K], ci_low[K], ci_high[K], n_gt0[K], n_lt0[K], n_abs_ge[K, n_tau], finite[K], n_pairs) as
+    capi.Batch.pair_comparison(i) returns it: the three doubles and the probabilities count / n_pairs as %.4f; two isoforms
+    -> isoform 0, more -> comma lists over the isoforms (as comparison_fields); a column that is not finite prints NA.
+    pairs = None (the pass did not take the event: too many draws): NA in every field."""
+    if pairs is None:
+        return ["NA"] * (len(DPSI_FIELDS) + n_thresholds)
+    med, lo, hi, gt, lt, ge, fin, M = pairs
+    ks = [0] if len(med) == 2 else range(len(med))
+    M = float(M)
+
+    def col(value):
+        return ",".join(("%.4f" % value(k)) if fin[k] else "NA" for k in ks)
+    f = [col(lambda k: med[k]), col(lambda k: lo[k]), col(lambda k: hi[k]), col(lambda k: gt[k] / M), col(lambda k: lt[k] / M)]
+    f += [col(lambda k, j=j: ge[k][j] / M) for j in range(n_thresholds)]
+    return f
+
+
+def dpsi_line(bf_line, pairs, n_thresholds):
+    """bf_line: the event's `.miso_bf` line, verbatim (comparison_line)"""
+    return "\t".join([bf_line] + dpsi_fields(pairs, n_thresholds))
+
+
+def write_dpsi(filename, rows, thresholds):
+    """rows: iterable of (event_name, summary1, summary2, bayes_factors, header1, header2, pairs) -- write_comparison's row
+    and the event's all-pairs results.  The quantities are those of the doubles the device holds: a pair of four-decimal
+    draws whose decimal difference equals a threshold exactly may fall on either side of it (0.3 - 0.1 < 0.2)."""
+    thresholds = check_delta_thresholds(thresholds)
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(dpsi_header_fields(thresholds)) + "\n")
+        for row in rows:
+            f.write(dpsi_line(comparison_line(*row[:6]), row[6], len(thresholds)) + "\n")
+            n += 1
+    return n

@@ -371,6 +371,16 @@ struct miso_batch {
   void adopt_text(int n, const unsigned char *text, const int64_t *offsets, const int *K, int S, int dev, int64_t chunk_bytes,
                   int32_t *status, miso_text_stats_t *stats);
   void compare(miso_batch &other, double smoothing);
+  // miso_batch_compare_pairs (this batch is sample 1; kernels_compare_pairs.hip): per (event, isoform) column
+  // pairs_words(pairs_ntau) 64-bit words (compare_pairs.hpp), event i's first column at h_pairs_off[i]
+  std::vector<uint64_t> h_pairs, h_pairs_off;
+  int pairs_ntau = 0;
+  int64_t pairs_M = 0;                  // S1 * S2
+  bool pairs_compared = false;
+  float pairs_ms = 0.f;                 // kernel time of the last compare_pairs
+  std::vector<int32_t> text_status;     // adopt_text: per event, non-zero = its text was not decoded, its pool region holds no samples
+  bool event_unread(int i) const { return i < static_cast<int>(text_status.size()) && text_status[i] != 0; }
+  void compare_pairs(miso_batch &other, double confidence_level, const double *tau, int n_tau, bool as_text = false);
   std::vector<miso_kernel_stat_t> launch_stats() const;   // miso_batch_launch_stats: one record per two-isoform part and per run
 
   // the parts of launch(): the plan (runtime.hip), the launches that follow it (launch.hip)

@@ -17,6 +17,7 @@
 #include "miso_philox.h"
 
 #include "batch.hpp"
+#include "compare_pairs.hpp"
 #include "coop.hpp"
 #include "miso_alnio.h"
 
@@ -924,6 +925,53 @@ int miso_batch_compare_ms(const miso_batch_t *b, float *compare_ms, float *exact
     need(b, "batch");
     if (compare_ms) *compare_ms = b->compare_ms;
     if (exact_compare_ms) *exact_compare_ms = b->exact_compare_ms;
+  });
+}
+
+int miso_batch_compare_pairs(miso_batch_t *a, miso_batch_t *b, double confidence_level, const double *tau, int n_tau) {
+  return guarded([&] {
+    need(a, "batch"); need(b, "batch");
+    if (n_tau > 0) need(tau, "tau");
+    a->compare_pairs(*b, confidence_level, tau, n_tau);
+  });
+}
+
+int miso_batch_compare_pairs_as_text(miso_batch_t *a, miso_batch_t *b, double confidence_level, const double *tau, int n_tau) {
+  return guarded([&] {
+    need(a, "batch"); need(b, "batch");
+    if (n_tau > 0) need(tau, "tau");
+    a->compare_pairs(*b, confidence_level, tau, n_tau, true);
+  });
+}
+
+int miso_batch_get_pair_comparison(const miso_batch_t *b, int i, double *median, double *ci_low, double *ci_high, int64_t *n_gt0,
+                                   int64_t *n_lt0, int64_t *n_abs_ge, int32_t *finite, int64_t *n_pairs) {
+  return guarded([&] {
+    need(b, "batch");
+    const PackedEvent &e = event_at(b, i);
+    if (!b->pairs_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_pairs has not run");
+    const int nt = b->pairs_ntau;
+    const size_t W = static_cast<size_t>(pairs_words(nt));
+    for (int k = 0; k < e.K; k++) {
+      const uint64_t *r = &b->h_pairs[(b->h_pairs_off[i] + k) * W];
+      double v[3];
+      std::memcpy(v, r, sizeof v);
+      if (median) median[k] = v[0];
+      if (ci_low) ci_low[k] = v[1];
+      if (ci_high) ci_high[k] = v[2];
+      if (n_gt0) n_gt0[k] = static_cast<int64_t>(r[3]);
+      if (n_lt0) n_lt0[k] = static_cast<int64_t>(r[4]);
+      if (finite) finite[k] = static_cast<int32_t>(r[5]);
+      if (n_abs_ge) for (int j = 0; j < nt; j++) n_abs_ge[static_cast<size_t>(k) * nt + j] = static_cast<int64_t>(r[PAIRS_FIXED_WORDS + j]);
+    }
+    if (n_pairs) *n_pairs = b->pairs_M;
+  });
+}
+
+int miso_batch_compare_pairs_ms(const miso_batch_t *b, float *ms) {
+  return guarded([&] {
+    need(b, "batch");
+    if (ms) *ms = b->pairs_ms;
   });
 }
 

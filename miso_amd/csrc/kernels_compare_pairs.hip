@@ -1,0 +1,229 @@
+// kernels_compare_pairs.hip -- the posterior of delta psi = psi_1 - psi_2 over ALL pairs of two samples' draws:
+// per (event, isoform) column pair a[0..S1) of sample 1 and b[0..S2) of sample 2, with D the multiset of the M = S1 S2 IEEE
+// doubles fl(a_i - b_j): three order statistics of D (lower median, the two bounds of a credible interval; the ranks are
+// the host's) and the exact counts #{d > 0}, #{d < 0} and, per threshold tau, #{d >= tau} + #{d <= -tau}.  No reference
+// counterpart (the reference pairs the draws by row index, hypothesis_test.py:89-179).
+//
+// D is never formed.  fl(a - b) is monotone in a and in -b, so with both columns ascending the pairs with fl(a_i - b_j) <= t
+// are, for every i, a suffix j >= p_i of b, and p_i does not fall as i grows: #{d <= t} is the sum of S2 - p_i.  The order
+// statistic of rank r is the value of the smallest order_key k with #{d <= key_value(k)} >= r + 1: a bisection over 64-bit
+// keys between the keys of the smallest and the largest difference, at most 64 counts.  The three bisections share their
+// passes over the columns.
+//
+// One 256-thread workgroup per column pair; dynamic LDS: the S1 + S2 draws, 8 bytes each -- as order_keys while they are
+// sorted, as doubles after.  The sort is the bitonic network in its all-ascending form (the first stage of every merge pairs
+// i with its mirror image in the block): a key past the end of the column would be the largest and stay where it is, so the
+// pairs that reach past the end are skipped and no padding to a power of two is stored -- two 5 000-draw columns take 80 KB,
+// two workgroups per CU, where kernels_diagnose_rank.hip's padded rank_sort would take 128 KB and leave one.
+// A count: every thread takes every 256th a_i and finds p_i by a binary search over b, four of them at a time (measured
+// against a chunk of consecutive a_i per thread with one search and a walk, which is seven times slower: DESIGN.md 19).
+// Plain C++, f64 subtraction and comparison only; every barrier in workgroup-uniform control flow
+// (the bisections' bounds are the same numbers in every thread).
+#include <hip/hip_runtime.h>
+
+#include "compare_pairs.hpp"
+#include "device.hpp"
+#include "order_key.hpp"
+#include "text_digits.hpp"
+
+namespace miso {
+
+// ascending, exact; B[0..N) published by a barrier, any N >= 1
+__device__ __forceinline__ void pairs_sort(uint64_t *B, int N) {
+  int P = 2;
+  while (P < N) P <<= 1;
+  for (int k = 2; k <= P; k <<= 1) {
+    const int hk = k >> 1;
+    for (int idx = threadIdx.x; idx < (P >> 1); idx += 256) {
+      const int r = idx & (hk - 1), base = (idx - r) << 1;   // the block of k keys, r its pair: (base + r, base + k - 1 - r)
+      const int i = base + r, l = base + k - 1 - r;
+      if (l < N) {
+        const uint64_t a = B[i], b = B[l];
+        if (a > b) { B[i] = b; B[l] = a; }
+      }
+    }
+    __syncthreads();
+    for (int j = hk >> 1; j > 0; j >>= 1) {
+      for (int idx = threadIdx.x; idx < (P >> 1); idx += 256) {
+        const int i = 2 * idx - (idx & (j - 1)), l = i + j;   // the pair (i, i + j), bit j of i clear
+        if (l < N) {
+          const uint64_t a = B[i], b = B[l];
+          if (a > b) { B[i] = b; B[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// d <= t, or d < t
+__device__ __forceinline__ bool pairs_below(double d, double t, bool strict) { return strict ? (d < t) : (d <= t); }
+
+// draws of a that a thread searches for at once: with the three thresholds twelve independent chains of LDS reads, which is
+// what hides their latency at the two wavefronts per SIMD the LDS leaves (the measurements)
+constexpr int PAIRS_E = 4;
+
+// cnt[q] = #{(i, j): fl(A[i] - B[j]) <= th[q]} (strict[q]: < th[q]) for three thresholds at once, the same numbers in every
+// thread.  A, B ascending doubles in LDS.  Thread t takes a[t], a[t + 256], ...: for each the start p of its suffix of b by a
+// binary search that applies the predicate to the difference itself (a wavefront's 64 draws are neighbours in a, so their
+// searches read the same few words of b).  part: four partial sums per query, which the caller alternates between two
+// buffers from call to call (one barrier per call: a buffer is written again two calls later, behind the barrier of the call
+// in between).
+__device__ __forceinline__ void pairs_count(const double *A, int S1, const double *B, int S2, const double (&th)[3],
+                                            const bool (&strict)[3], uint32_t (&cnt)[3], uint32_t (*part)[3]) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  cnt[0] = cnt[1] = cnt[2] = 0;
+  for (int i = t; i < S1; i += 256 * PAIRS_E) {
+    double a[PAIRS_E];
+    int p[PAIRS_E][3];
+#pragma unroll
+    for (int e = 0; e < PAIRS_E; e++) {
+      a[e] = A[min(i + 256 * e, S1 - 1)];               // (past the end: searched like the last draw, not counted)
+      p[e][0] = p[e][1] = p[e][2] = 0;
+    }
+    int len = S2;
+    while (len > 1) {                                 // the starts lie in [p, p + len]
+      const int half = len >> 1;
+#pragma unroll
+      for (int e = 0; e < PAIRS_E; e++)
+#pragma unroll
+        for (int q = 0; q < 3; q++)
+          if (!pairs_below(a[e] - B[p[e][q] + half - 1], th[q], strict[q])) p[e][q] += half;
+      len -= half;
+    }
+#pragma unroll
+    for (int e = 0; e < PAIRS_E; e++)
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        if (!pairs_below(a[e] - B[p[e][q]], th[q], strict[q])) p[e][q]++;
+        if (i + 256 * e < S1) cnt[q] += static_cast<uint32_t>(S2 - p[e][q]);
+      }
+  }
+#pragma unroll
+  for (int q = 0; q < 3; q++) {
+    uint32_t v = cnt[q];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    if (lane == 0) part[wave][q] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 3; q++) cnt[q] = part[0][q] + part[1][q] + part[2][q] + part[3][q];
+}
+
+// Grid (events, kmax), one workgroup per column pair; out: pairs_words(n_tau) 64-bit words per (event, isoform) at
+// (col_off[ev] + k) * pairs_words(n_tau) (compare_pairs.hpp; col_off[ev] with PAIRS_SKIP_EVENT set: not finite, nothing read).  The host refuses S1, S2 outside [1, 8192] and sizes the
+// dynamic LDS: (S1 + S2) * 8 bytes.
+__global__ __launch_bounds__(256) void compare_pairs_kernel(const DevEvent *events1, const unsigned char *pool1, int S1,
+                                                            const DevEvent *events2, const unsigned char *pool2, int S2,
+                                                            int n_events, PairsArgs pa, int as_text, const uint64_t *col_off,
+                                                            uint64_t *out) {
+  extern __shared__ uint64_t pairs_lds[];
+  __shared__ uint32_t s_part[2][4][3];
+  __shared__ uint32_t s_cnt[2 + 2 * PAIRS_MAX_TAU];   // thread 0's: the threshold counts until it puts them together
+  const int ev = blockIdx.x, kk = blockIdx.y;
+  if (ev >= n_events) return;
+  const DevEvent E1 = events1[ev], E2 = events2[ev];
+  if (kk >= E1.K) return;
+  const double *x1 = reinterpret_cast<const double *>(pool1 + E1.off_samples) + kk;
+  const double *x2 = reinterpret_cast<const double *>(pool2 + E2.off_samples) + kk;
+  const int W = PAIRS_FIXED_WORDS + pa.n_tau;
+  const uint64_t first_col = col_off[ev];
+  uint64_t *o = out + ((first_col & ~PAIRS_SKIP_EVENT) + kk) * W;
+  const int t = threadIdx.x;
+  const double inf = __longlong_as_double(0x7FF0000000000000ll);
+  const bool skip = (first_col & PAIRS_SKIP_EVENT) != 0;   // (the event's samples were never decoded: nothing of it is read)
+
+  uint64_t *KA = pairs_lds, *KB = KA + S1;
+  // as_text: a draw as its `.miso` file prints it and a reader parses it back (text_digits.hpp), so that a run's table is
+  // the table of the files it wrote.  (x + 0.0: -0.0 becomes +0.0; the differences compare the same)
+  int bad = skip ? 1 : 0;
+  for (int e = t; e < (skip ? 0 : S1); e += 256) {
+    double v = x1[static_cast<size_t>(e) * E1.K];
+    if (as_text && text_rounds(v)) v = static_cast<double>(text_digits(v)) / 10000.0;
+    bad |= !(fabs(v) < inf);
+    KA[e] = order_key(v + 0.0);
+  }
+  for (int e = t; e < (skip ? 0 : S2); e += 256) {
+    double v = x2[static_cast<size_t>(e) * E2.K];
+    if (as_text && text_rounds(v)) v = static_cast<double>(text_digits(v)) / 10000.0;
+    bad |= !(fabs(v) < inf);
+    KB[e] = order_key(v + 0.0);
+  }
+  if (__syncthreads_or(bad)) {                        // workgroup-uniform (a skipped event: bad in every thread, below)
+    if (t == 0) {
+      const uint64_t nan = 0x7FF8000000000000ull;
+      o[0] = nan; o[1] = nan; o[2] = nan;
+      for (int w = 3; w < W; w++) o[w] = 0;
+    }
+    return;
+  }
+  pairs_sort(KA, S1);
+  pairs_sort(KB, S2);
+  double *A = reinterpret_cast<double *>(KA), *B = reinterpret_cast<double *>(KB);
+  for (int e = t; e < S1; e += 256) A[e] = key_value(KA[e]);
+  for (int e = t; e < S2; e += 256) B[e] = key_value(KB[e]);
+  __syncthreads();
+
+  const uint32_t M = static_cast<uint32_t>(S1) * static_cast<uint32_t>(S2);   // <= 2^26
+  int buf = 0;
+
+  // the three order statistics: bisections over the keys of [smallest difference, largest difference]
+  uint64_t lo_k[3], hi_k[3];
+  {
+    const uint64_t kmin = order_key(A[0] - B[S2 - 1]), kmax = order_key(A[S1 - 1] - B[0]);
+#pragma unroll
+    for (int q = 0; q < 3; q++) { lo_k[q] = kmin; hi_k[q] = kmax; }
+  }
+  const bool not_strict[3] = {false, false, false};
+  while (lo_k[0] < hi_k[0] || lo_k[1] < hi_k[1] || lo_k[2] < hi_k[2]) {
+    uint64_t mid[3];
+    double th[3];
+    uint32_t cnt[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) { mid[q] = lo_k[q] + ((hi_k[q] - lo_k[q]) >> 1); th[q] = key_value(mid[q]); }
+    pairs_count(A, S1, B, S2, th, not_strict, cnt, s_part[buf]);
+    buf ^= 1;
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+      if (lo_k[q] < hi_k[q]) {
+        if (cnt[q] >= pa.rank[q] + 1u) hi_k[q] = mid[q]; else lo_k[q] = mid[q] + 1;
+      }
+  }
+
+  // the counts: query 0 is #{d <= 0}, 1 #{d < 0}, 2 + 2 j #{d < tau_j}, 3 + 2 j #{d <= -tau_j}; three to a pass
+  const int n_query = 2 + 2 * pa.n_tau;
+  for (int q0 = 0; q0 < n_query; q0 += 3) {
+    double th[3];
+    bool strict[3];
+    uint32_t cnt[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const int qi = q0 + q;
+      th[q] = 0.0; strict[q] = false;
+      if (qi == 1) strict[q] = true;
+      else if (qi >= 2 && qi < n_query) {
+        const double tau = pa.tau[(qi - 2) >> 1];
+        if (qi & 1) th[q] = -tau; else { th[q] = tau; strict[q] = true; }
+      }
+    }
+    pairs_count(A, S1, B, S2, th, strict, cnt, s_part[buf]);
+    buf ^= 1;
+    if (t == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; q++)
+        if (q0 + q < n_query) s_cnt[q0 + q] = cnt[q];
+    }
+  }
+  if (t == 0) {
+    // (+ 0.0: the smallest key whose count suffices is -0.0's when the order statistic is zero)
+#pragma unroll
+    for (int q = 0; q < 3; q++) o[q] = static_cast<uint64_t>(__double_as_longlong(key_value(lo_k[q]) + 0.0));
+    o[3] = M - s_cnt[0];
+    o[4] = s_cnt[1];
+    o[5] = 1;
+    for (int j = 0; j < pa.n_tau; j++) o[PAIRS_FIXED_WORDS + j] = static_cast<uint64_t>(M - s_cnt[2 + 2 * j]) + s_cnt[3 + 2 * j];
+  }
+}
+
+}  // namespace miso

@@ -419,6 +419,7 @@ void miso_batch::adopt_text(int n, const unsigned char *text, const int64_t *off
   for (size_t i = 0; i < n_slots; i++)
     if (slot[i].busy) drain(slot[i]);
   if (n) HIP_OK(hipMemcpy(status, d_status, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost));
+  text_status.assign(status, status + n);       // (compare_pairs: such an event's columns are not finite)
   for (int i = 0; i < n; i++) {
     if (status[i] == 0) { st.decoded++; st.sample_bytes += int64_t{8} * Sn * K[i]; }
     else st.not_decoded++;

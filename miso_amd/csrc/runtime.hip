@@ -18,6 +18,7 @@
 
 #include "batch.hpp"
 #include "compare_column.hpp"
+#include "compare_pairs.hpp"
 #include "coop.hpp"
 #include "exact_compare.hpp"
 #include "hip_host.hpp"
@@ -28,6 +29,8 @@ extern int g_hw_queues_in_effect;   // capi.hip: the host's hardware queue count
 
 __global__ void compare_kernel(const DevEvent *, const unsigned char *, const DevEvent *, const unsigned char *, int, int,
                                double, const uint64_t *, double *);
+__global__ void compare_pairs_kernel(const DevEvent *, const unsigned char *, int, const DevEvent *, const unsigned char *, int, int,
+                                     PairsArgs, int, const uint64_t *, uint64_t *);
 __global__ void match_kernel(const MatchEvent *, const int2 *, const int *, const int *, const int *, const int *,
                              const int *, const int *, const int *, int, int, int, int, int, uint32_t *, uint16_t *);
 __global__ void summarize_kernel(const DevEvent *, const unsigned char *, int, int, int, int, const uint64_t *, double *, int);
@@ -597,7 +600,7 @@ void miso_batch::launch(uint64_t seed, uint32_t first_event_id) {
   }
   HIP_OK(hipEventRecord(ev1, stream));
   start_clock_probe();
-  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; exact_compared = false; diagnosed = false; rank_diagnosed = false;
+  launched = true; launched_once = true; downloaded = false; summarized = false; compared = false; exact_compared = false; pairs_compared = false; diagnosed = false; rank_diagnosed = false;
 }
 
 // The launch's sizes and switches, read once per launch.
@@ -1554,6 +1557,84 @@ void miso_batch::compare(miso_batch &other, double smoothing) {
   compared = true;
 }
 
+// The posterior of delta psi over ALL S1 * S2 pairs of this batch's draws (sample 1) and `other`'s (sample 2), event by event
+// (kernels_compare_pairs.hip): the lower median and the bounds of the `confidence_level` interval of the
+// differences -- ranks as summarize() takes them but over S1 * S2, the lower one clamped at 0 --, the exact counts of the
+// differences above and below 0 and, per threshold, of those at least that far from 0.  The batches hold the same events
+// in the same order; their sample counts may differ.  The results stand beside compare()'s.  as_text: of the draws as the
+// `.miso` files print them ("%.4f"), as summarize()'s.
+void miso_batch::compare_pairs(miso_batch &other, double confidence_level, const double *tau, int n_tau, bool as_text) {
+  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
+  if (events.size() != other.events.size()) MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events");
+  if (!(confidence_level > 0 && confidence_level < 1)) MISO_FAIL(MISO_EINVAL, "Invalid confidence level: it must lie inside (0, 1)");
+  if (n_tau < 0 || n_tau > PAIRS_MAX_TAU) MISO_FAIL(MISO_EINVAL, "Invalid number of delta psi thresholds: 0 to 4");
+  for (int j = 0; j < n_tau; j++)
+    if (!(tau[j] > 0 && tau[j] < 1)) MISO_FAIL(MISO_EINVAL, "Invalid delta psi threshold: it must lie inside (0, 1)");
+  const int n = static_cast<int>(events.size()), S1 = S(), S2 = other.S();
+  if (S1 < 1 || S2 < 1) MISO_FAIL(MISO_EINVAL, "Too few samples to compare");
+  if (S1 > PAIRS_MAX_DRAWS || S2 > PAIRS_MAX_DRAWS)
+    MISO_FAIL(MISO_EINVAL, "Too many samples for the all-pairs comparison: 8192 per event and sample at most");
+  std::vector<uint64_t> off(n);
+  uint64_t cols = 0; int kmax = 1;
+  for (int i = 0; i < n; i++) {
+    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+    off[i] = cols; cols += events[i].K; kmax = std::max(kmax, events[i].K);
+  }
+  // the ranks in double, as summarize()'s: M <= 2^26, every product and sum below is far from 2^53
+  const int64_t M = static_cast<int64_t>(S1) * S2;
+  const double alpha = 1 - confidence_level;
+  const double lo_d = std::max(0.0, std::floor((alpha / 2) * static_cast<double>(M) + 0.5) - 1);
+  const double hi_d = std::min(static_cast<double>(M - 1), std::max(lo_d, std::floor((1 - alpha / 2) * static_cast<double>(M) + 0.5) - 1));
+  PairsArgs pa{};
+  pa.rank[0] = static_cast<uint32_t>((M - 1) / 2);
+  pa.rank[1] = static_cast<uint32_t>(lo_d);
+  pa.rank[2] = static_cast<uint32_t>(hi_d);
+  pa.n_tau = n_tau;
+  for (int j = 0; j < n_tau; j++) pa.tau[j] = tau[j];
+  // as summarize(): under CONVERGENT_MEAN a launch is finished once sync() has run its further rounds
+  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  if (other.p.stop == MISO_STOP_CONVERGENT_MEAN && !other.converged_done) other.sync(nullptr);
+  const size_t W = static_cast<size_t>(pairs_words(n_tau));
+  // an event whose sample text was not decoded in either batch (adopt_text): the kernel does not touch its columns, they
+  // come back not finite -- the top bit of the event's column offset says so
+  std::vector<uint64_t> off_flagged(off);
+  for (int i = 0; i < n; i++)
+    if (event_unread(i) || other.event_unread(i)) off_flagged[i] |= PAIRS_SKIP_EVENT;
+  // the results are made beside the stored ones and take their place at the end: a call that fails leaves what was there
+  std::vector<uint64_t> res(cols * W, 0);
+  float ms = 0.f;
+  if (n > 0) {
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipStreamSynchronize(other.stream));
+    const size_t dyn = (static_cast<size_t>(S1) + S2) * sizeof(uint64_t);   // both columns: what is live, not the limit
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(compare_pairs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(dyn)));
+    struct DeviceWords {               // freed however the block is left
+      uint64_t *d = nullptr;
+      ~DeviceWords() { if (d) (void) hipFree(d); }
+    } d_off, d_res;
+    HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off.d), n * sizeof(uint64_t)));
+    HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_res.d), cols * W * sizeof(uint64_t)));
+    HIP_OK(hipMemcpyAsync(d_off.d, off_flagged.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    PassTimer timer(stream, pass_ev0, pass_ev1);
+    hipLaunchKernelGGL(compare_pairs_kernel, dim3(n, kmax), dim3(256), dyn, stream, d_events, d_out, S1, other.d_events, other.d_out,
+                       S2, n, pa, as_text ? 1 : 0, d_off.d, d_res.d);
+    HIP_OK(hipGetLastError());
+    timer.stop();
+    HIP_OK(hipMemcpyAsync(res.data(), d_res.d, cols * W * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    ms = timer.ms();
+    if (last_kernels.find("compare_pairs") == std::string::npos) note_kernel("compare_pairs");   // (once, however often it is called)
+  }
+  h_pairs.swap(res);
+  h_pairs_off.swap(off);
+  pairs_ntau = n_tau;
+  pairs_M = M;
+  pairs_ms = ms;
+  pairs_compared = true;
+}
+
 // What the two exact comparisons of batch a (sample 1) with batch b (sample 2) share: the guards, the list of the events both
 // batches' exact mode took and that are `comparable`, their rows of `row_w` statistics from `gather`, the call of `run` (which
 // validates z, and fails with MISO_ENODEVICE without a device, also when no event is comparable), and the scatter of its rows
@@ -1668,7 +1749,8 @@ void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
   HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_out), out_bytes));
   if (n) HIP_OK(hipMemcpy(d_events, h_events.data(), n * sizeof(DevEvent), hipMemcpyHostToDevice));
   n_k2 = n_k2w = n_gen = 0; k2[0].count = k2[1].count = 0; gen_runs.clear(); plan = LaunchPlan{};
-  uploaded = launched = true; downloaded = false; summarized = compared = exact_compared = diagnosed = rank_diagnosed = false; adopted = true;
+  uploaded = launched = true; downloaded = false; summarized = compared = exact_compared = pairs_compared = diagnosed = rank_diagnosed = false; adopted = true;
+  text_status.clear();
 }
 
 void miso_batch::download() {

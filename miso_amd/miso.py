@@ -133,8 +133,12 @@ class GenesDispatcher(object):
                  settings_fname=None, paired_end=None, gene_ids=None, num_proc=None,
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
-                 exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False):
+                 exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
+                 delta_posterior=False):
         self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
+        # --delta-posterior: beside the `.miso_bf` table the all-pairs `.miso_dpsi` (compare.py), merged like a diagnostics
+        # table, with the same delta_thresholds
+        self.delta_posterior = bool(delta_posterior)
         self.rank_diagnostics = bool(rank_diagnostics)   # --rank-diagnostics: six more columns in every diagnostics table
         self.summary_only = bool(summary_only)
         self.exact = bool(exact)       # --exact: handed on to every worker
@@ -276,6 +280,7 @@ class GenesDispatcher(object):
             os.makedirs(os.path.dirname(table), exist_ok=True)
         self.diag_tables = []
         xtable = []                    # --exact-compare: [(table, its per-worker parts)], merged with the diagnostics tables
+        dtable = []                    # --delta-posterior: likewise
         if self.diagnostics:
             # one table per directory of `.miso` files: the output directory, or with --compare each label's
             for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
@@ -297,8 +302,13 @@ class GenesDispatcher(object):
                         xtable.append((table + "_exact", []))
                     xtable[0][1].append("%s.gpu%d" % (xtable[0][0], batch_num))
                     cmd += ["--exact-comparison-file", xtable[0][1][-1]]
-                    if self.delta_thresholds is not None:
-                        cmd += ["--delta-psi-thresholds"] + ["%r" % t for t in self.delta_thresholds]
+                if self.delta_posterior:
+                    if not dtable:
+                        dtable.append((table[:-len(".miso_bf")] + ".miso_dpsi", []))
+                    dtable[0][1].append("%s.gpu%d" % (dtable[0][0], batch_num))
+                    cmd += ["--delta-posterior-file", dtable[0][1][-1]]
+                if (self.exact_compare or self.delta_posterior) and self.delta_thresholds is not None:
+                    cmd += ["--delta-psi-thresholds"] + ["%r" % t for t in self.delta_thresholds]
                 if n_diag:
                     dparts = ["%s.gpu%d" % (t, batch_num) for t, _ in self.diag_tables]
                     for (_, plist), dp in zip(self.diag_tables, dparts):
@@ -336,7 +346,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
-        self.diag_tables += xtable
+        self.diag_tables += xtable + dtable
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -408,7 +418,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           paired_end=None, settings_fname=None, num_proc=None, event_type=None,
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
-                          exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False):
+                          exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
+                          delta_posterior=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -421,7 +432,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            event_type=event_type, seed=seed, summarize=summarize or summary_only,
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
-                           delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics).run()
+                           delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
+                           delta_posterior=delta_posterior).run()
 
 
 def main(argv=None):
@@ -470,8 +482,13 @@ def main(argv=None):
                          "--exact-compare for the events the paired exact mode took in both samples -- the product of the two "
                          "posteriors is tabulated over both samples' read pairs; the .miso files and the .miso_bf table are unchanged")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
-                    help="the thresholds T of --exact-compare / --exact-paired-compare, each in (0, 1), at most four "
-                         "(default 0.1 0.2)")
+                    help="the thresholds T of --exact-compare / --exact-paired-compare / --delta-posterior, each in (0, 1), at "
+                         "most four (default 0.1 0.2)")
+    ap.add_argument("--delta-posterior", action="store_true",
+                    help="with --compare, any mode and any number of isoforms: also write "
+                         "OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_dpsi -- median and 95 %% credible interval of delta Psi, "
+                         "P(delta Psi > 0), P(delta Psi < 0) and P(|delta Psi| >= T) over ALL pairs of the two samples' draws, "
+                         "computed on the GPU during the run; every other output is unchanged")
     ap.add_argument("--compare", metavar="BAM2", default=None,
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
@@ -506,9 +523,11 @@ def main(argv=None):
         if not (a.exact_paired or Settings.get_exact_paired()):
             ap.error("--exact-paired-compare needs the paired exact-posterior mode (--exact-paired, or `exact_paired = True` "
                      "in the settings)")
+    if a.delta_posterior and a.compare is None:
+        ap.error("--delta-posterior goes with --compare")
     if a.delta_psi_thresholds is not None:
-        if not (a.exact_compare or a.exact_paired_compare):
-            ap.error("--delta-psi-thresholds goes with --exact-compare")
+        if not (a.exact_compare or a.exact_paired_compare or a.delta_posterior):
+            ap.error("--delta-psi-thresholds goes with --exact-compare or --delta-posterior")
         from . import compare
         try:
             compare.check_delta_thresholds(a.delta_psi_thresholds)
@@ -536,7 +555,8 @@ def main(argv=None):
                                        labels=tuple(a.labels), prefilter=a.prefilter, diagnostics=a.diagnostics,
                                        exact=a.exact, exact_compare=a.exact_compare or a.exact_paired_compare,
                                        exact_paired=a.exact_paired,
-                                       delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics)
+                                       delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics,
+                                       delta_posterior=a.delta_posterior)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

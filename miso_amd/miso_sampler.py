@@ -440,7 +440,7 @@ class MISOSampler:
                              burn_in=1000, lag=2, seed=None, seed2=None, first_event_id=0,
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
                              diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None,
-                             rank_diagnostics=False):
+                             rank_diagnostics=False, delta_posterior_file=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -454,7 +454,14 @@ class MISOSampler:
         rank-normalised pass.
         exact_comparison_file (optional; the exact-posterior mode only): the `.miso_bf_exact` table of the exact comparison
         (compare.write_exact_comparison) with P(|delta psi| >= t) for every t of delta_thresholds (default 0.1, 0.2).  A
-        paired-end sampler with the paired exact mode compares through MISOCompareBatch(exact_paired_compare=)."""
+        paired-end sampler with the paired exact mode compares through MISOCompareBatch(exact_paired_compare=).
+        delta_posterior_file (optional; any mode): the `.miso_dpsi` table (compare.write_dpsi) of delta psi over all pairs
+        of the two samples' draws -- median, the confidence_level interval, P(delta > 0), P(delta < 0) and
+        P(|delta psi| >= t) for every t of delta_thresholds."""
+        dthr = None
+        if delta_posterior_file is not None:
+            dthr = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
+        drows = []
         xthr = None
         if exact_comparison_file is not None:
             if self.paired_end:
@@ -493,6 +500,8 @@ class MISOSampler:
                 kw["exact_paired"] = True   # ... and the paired-end one
             if xthr is not None:
                 kw["exact_paired_compare" if self.paired_end else "exact_compare"] = compare.delta_points(xthr)
+            if dthr is not None:
+                kw["delta_posterior"] = (float(confidence_level), tuple(dthr))
             res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),
@@ -519,8 +528,12 @@ class MISOSampler:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
                     if xthr is not None:
-                        xrows.append(rows[-1] + (res[-1][j],))
+                        xrows.append(rows[-1] + (res[-2 if dthr is not None else -1][j],))
+                    if dthr is not None:
+                        drows.append(rows[-1] + (res[-1][j],))
         compare.write_comparison(comparison_file, rows)
+        if dthr is not None:
+            compare.write_dpsi(delta_posterior_file, drows, dthr)
         if xthr is not None:
             compare.write_exact_comparison(exact_comparison_file, xrows, xthr)
         if diagnostics_files is not None:

@@ -36,6 +36,9 @@
  *                   miso_batch_compare_exact_paired, appended as the LAST element of the result.
  *   exact_compare=(z, ...)  MISOCompareBatch with exact=True: the exact comparison (miso_batch_compare_exact) at these
  *                   delta psi points, appended as the LAST element of the result.
+ *   delta_posterior=(level, (tau, ...))  MISOCompareBatch, any mode: delta psi over all pairs of the two samples' draws
+ *                   as their `.miso` files print them (miso_batch_compare_pairs_as_text), appended as the LAST element of the
+ *                   result, behind exact_compare's.
  * The functions of the module that are not on the sampler path raise NotImplementedError.
  * The reference's stdout side effect `printf("no chains: %d\n")` (miso.c:837) is not reproduced.
  */
@@ -487,8 +490,10 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
                            "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired",
-                           "exact_paired_compare", "rank_diagnostics", NULL};
+                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
+  PyObject *dpobj = NULL, *dp = NULL;   /* delta_posterior=(level, (tau, ...)): the all-pairs pass, miso_batch_compare_pairs */
+  double dp_level = 0.95, dp_tau[4]; int n_dp = 0;
   PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL, *xcobj = NULL, *xc = NULL;
   PyObject *xpobj = NULL;   /* exact_paired_compare=(z, ...): the same through miso_batch_compare_exact_paired */
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
@@ -500,10 +505,22 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOp", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpO", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
                                    &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
-                                   &exact_paired, &xpobj, &rank_diagnostics)) return NULL;
+                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj)) return NULL;
+  if (dpobj == Py_None) dpobj = NULL;
+  if (dpobj) {
+    PyObject *taus = NULL; Py_ssize_t nt;
+    if (!PyArg_ParseTuple(dpobj, "dO;delta_posterior must be (confidence_level, (threshold, ...))", &dp_level, &taus)) return NULL;
+    if (!PyTuple_Check(taus) || (nt = PyTuple_Size(taus)) > 4) {
+      PyErr_SetString(PyExc_ValueError, "delta_posterior takes a tuple of at most 4 delta psi thresholds"); return NULL;
+    }
+    for (n_dp = 0; n_dp < (int) nt; n_dp++) {
+      dp_tau[n_dp] = PyFloat_AsDouble(PyTuple_GET_ITEM(taus, n_dp));
+      if (PyErr_Occurred()) return NULL;
+    }
+  }
   if (rank_diagnostics && !diagnostics) { PyErr_SetString(PyExc_ValueError, "rank_diagnostics requires diagnostics=True"); return NULL; }
   if (xcobj == Py_None) xcobj = NULL;
   if (xpobj == Py_None) xpobj = NULL;
@@ -611,8 +628,40 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     all = one ? PySequence_Concat(out, one) : NULL;
     Py_XDECREF(one); Py_DECREF(out); out = all;
   }
+  /* delta_posterior=(level, (tau, ...)): a last element (behind exact_compare's), per event (median, ci_low, ci_high, n_gt0,
+     n_lt0, n_abs_ge -- per isoform a tuple over the thresholds --, finite, n_pairs) of the S1 * S2 differences */
+  if (out && dpobj) {
+    PyObject *one, *all;
+    if (n > 0 && (rc = miso_batch_compare_pairs_as_text(b1, b2, dp_level, dp_tau, n_dp))) { raise_miso(rc); Py_CLEAR(out); goto done; }
+    if (!(dp = PyList_New(n))) { Py_CLEAR(out); goto done; }
+    for (i = 0; i < n; i++) {
+      int K, k, j; double med[MISO_MAX_ISOFORMS], lo[MISO_MAX_ISOFORMS], hi[MISO_MAX_ISOFORMS];
+      int64_t gt[MISO_MAX_ISOFORMS], lt[MISO_MAX_ISOFORMS], ge[MISO_MAX_ISOFORMS * 4], M = 0; int32_t fin[MISO_MAX_ISOFORMS];
+      PyObject *t, *pgt, *plt, *pge, *pfin;
+      if ((rc = miso_batch_event_info(b1, (int) i, &K, NULL, NULL, NULL)) ||
+          (rc = miso_batch_get_pair_comparison(b1, (int) i, med, lo, hi, gt, lt, ge, fin, &M))) { raise_miso(rc); Py_CLEAR(out); goto done; }
+      pgt = PyTuple_New(K); plt = PyTuple_New(K); pge = PyTuple_New(K); pfin = PyTuple_New(K);
+      if (!pgt || !plt || !pge || !pfin) { Py_XDECREF(pgt); Py_XDECREF(plt); Py_XDECREF(pge); Py_XDECREF(pfin); Py_CLEAR(out); goto done; }
+      for (k = 0; k < K; k++) {
+        PyObject *row = PyTuple_New(n_dp);
+        if (!row) break;
+        for (j = 0; j < n_dp; j++) PyTuple_SET_ITEM(row, j, PyLong_FromLongLong((long long) ge[k * n_dp + j]));
+        PyTuple_SET_ITEM(pgt, k, PyLong_FromLongLong((long long) gt[k]));
+        PyTuple_SET_ITEM(plt, k, PyLong_FromLongLong((long long) lt[k]));
+        PyTuple_SET_ITEM(pge, k, row);
+        PyTuple_SET_ITEM(pfin, k, PyBool_FromLong(fin[k]));
+      }
+      if (k < K) { Py_DECREF(pgt); Py_DECREF(plt); Py_DECREF(pge); Py_DECREF(pfin); Py_CLEAR(out); goto done; }
+      t = Py_BuildValue("(NNNNNNNL)", from_doubles(med, K), from_doubles(lo, K), from_doubles(hi, K), pgt, plt, pge, pfin, (long long) M);
+      if (!t) { Py_CLEAR(out); goto done; }
+      PyList_SET_ITEM(dp, i, t);
+    }
+    one = PyTuple_Pack(1, dp);
+    all = one ? PySequence_Concat(out, one) : NULL;
+    Py_XDECREF(one); Py_DECREF(out); out = all;
+  }
 done:
-  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc);
+  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc); Py_XDECREF(dp);
   if (b1) miso_batch_destroy(b1);
   if (b2) miso_batch_destroy(b2);
   return out;

@@ -324,7 +324,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      comparison_file, read_len, overhang_len, paired_end=None, event_type=None,
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
-                     exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False):
+                     exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False,
+                     delta_posterior_file=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -335,7 +336,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     diagnostics_files: (file1, file2), each sample's chain diagnostics table (diagnostics.py), parts merged like the
     comparison's; rank_diagnostics: with the six columns of the rank-normalised pass.
     exact_comparison_file (the exact mode only): the `.miso_bf_exact` table of the exact comparison (compare.py
-    write_exact_comparison), parts merged like the comparison's; delta_thresholds: its thresholds t of P(|delta psi| >= t)."""
+    write_exact_comparison), parts merged like the comparison's; delta_thresholds: its thresholds t of P(|delta psi| >= t).
+    delta_posterior_file (any mode): the `.miso_dpsi` table of delta psi over all pairs of the two samples' draws (compare.py
+    write_dpsi), parts merged like the comparison's, with the same delta_thresholds."""
     for d in (output_dir1, output_dir2):
         os.makedirs(d, exist_ok=True)
     if device is not None:
@@ -362,6 +365,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     pairs = [(a, by_no2[a[4]]) for a in ev1 if a[4] in by_no2]
     parts = []
     xparts = []
+    dpsi_parts = []
     diag_parts = ([], [])
     if paired_end:
         mean_frag_len = int(paired_end[0])
@@ -389,14 +393,21 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         if exact_comparison_file is not None:
             xpart = "%s.part%06d" % (exact_comparison_file, lo)
             xparts.append(xpart)
+        dpsi_part = None
+        if delta_posterior_file is not None:
+            dpsi_part = "%s.part%06d" % (delta_posterior_file, lo)
+            dpsi_parts.append(dpsi_part)
         sampler.run_comparison_batch(p["num_iters"], [a[:3] for a, _ in chunk],
                                      [b[:3] for _, b in chunk], part, num_chains=p["num_chains"],
                                      burn_in=p["burn_in"], lag=p["lag"], seed=seed,
                                      first_event_id=first_event_id + lo, verbose=verbose,
                                      event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
                                      diagnostics_files=dparts, exact_comparison_file=xpart,
-                                     delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics)
+                                     delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
+                                     delta_posterior_file=dpsi_part)
     merge_tables(parts, comparison_file)
+    if delta_posterior_file is not None:
+        merge_tables(dpsi_parts, delta_posterior_file)
     if exact_comparison_file is not None:
         merge_tables(xparts, exact_comparison_file)
     if samples is not None:
@@ -485,7 +496,11 @@ def main(argv=None):
                     help="with --compare-genes-from-file and the exact mode: also write the exact comparison's table "
                          "(Bayes factors and P(|delta psi| >= T) from the posteriors' tables, no sampling error)")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
-                    help="the thresholds T of --exact-comparison-file, each in (0, 1), at most four (default 0.1 0.2)")
+                    help="the thresholds T of --exact-comparison-file and --delta-posterior-file, each in (0, 1), at most four "
+                         "(default 0.1 0.2)")
+    ap.add_argument("--delta-posterior-file", default=None, metavar="F",
+                    help="with --compare-genes-from-file, any mode: also write the table of delta psi over all pairs of the two "
+                         "samples' draws (median, credible interval, P(delta psi > 0), P(|delta psi| >= T))")
     ap.add_argument("--paired-end", nargs=2, type=float, metavar=("MEAN", "SD"))
     ap.add_argument("--read-len", type=int)
     ap.add_argument("--overhang-len", type=int)
@@ -523,6 +538,9 @@ def main(argv=None):
         elif not a.compare_genes_from_file or paired_end or not exact:
             print("Error: --exact-comparison-file goes with --compare-genes-from-file and the exact mode (single-end).")
             return 1
+    if a.delta_posterior_file is not None and not a.compare_genes_from_file:
+        print("Error: --delta-posterior-file goes with --compare-genes-from-file.")
+        return 1
     if a.delta_psi_thresholds is not None:
         try:
             miso.compare.check_delta_thresholds(a.delta_psi_thresholds)
@@ -540,7 +558,9 @@ def main(argv=None):
                              exact_comparison_file=(os.path.abspath(os.path.expanduser(a.exact_comparison_file))
                                                     if a.exact_comparison_file else None),
                              delta_thresholds=a.delta_psi_thresholds, exact_paired=exact_paired,
-                             rank_diagnostics=a.rank_diagnostics)
+                             rank_diagnostics=a.rank_diagnostics,
+                             delta_posterior_file=(os.path.abspath(os.path.expanduser(a.delta_posterior_file))
+                                                   if a.delta_posterior_file else None))
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))

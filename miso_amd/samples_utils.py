@@ -451,8 +451,29 @@ def _read_named(src, names):
     return files, dbrows
 
 
-def _compare_parsed(pairs, confidence_level, smoothing, device, rows):
-    """Comparison rows of host-parsed pairs ((name, samples, header), (name, samples, header))."""
+MAX_PAIR_DRAWS = 8192      # miso_batch_compare_pairs: draws per event and sample (both sorted columns stay in LDS)
+
+
+def _delta_posterior(b1, b2, n, names, S, confidence_level, delta):
+    """delta = (thresholds, results): results[name] = Batch.pair_comparison of every event of the two batches -- delta psi
+    over all pairs of their draws --, or None where the samples are too long for the pass (one notice per
+    call of output_samples_comparison: results[None] remembers it)."""
+    if delta is None:
+        return
+    thresholds, results = delta
+    if S > MAX_PAIR_DRAWS:
+        if None not in results:
+            print("No delta psi posterior for events of more than %d samples (%s has %d): their rows print NA"
+                  % (MAX_PAIR_DRAWS, names[0], S))
+            results[None] = None
+        results.update((name, None) for name in names)
+        return
+    b1.compare_pairs(b2, confidence_level, thresholds)
+    results.update((name, b1.pair_comparison(i)) for i, name in enumerate(names))
+
+
+def _compare_parsed(pairs, confidence_level, smoothing, device, rows, delta=None):
+    """Comparison rows of host-parsed pairs ((name, samples, header), (name, samples, header)); delta: _delta_posterior's."""
     groups = {}
     for a, b2 in pairs:
         if a[1].shape != b2[1].shape:
@@ -467,14 +488,18 @@ def _compare_parsed(pairs, confidence_level, smoothing, device, rows):
         b2 = capi.SamplesBatch([g[1][1] for g in group], device=device)
         b1.summarize(confidence_level); b2.summarize(confidence_level)
         b1.compare(b2, smoothing)
+        _delta_posterior(b1, b2, len(group), [g[0][0] for g in group], S, confidence_level, delta)
         for i, (a, c) in enumerate(group):
             _, _, bf, _ = b1.comparison(i)
             rows.append((a[0], tuple(b1.summary(i)), tuple(b2.summary(i)), bf, a[2], c[2]))
 
 
 def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_level=0.95, smoothing=0.3,
-                              sample_labels=None, device=0, decoder=None):
-    """hypothesis_test.py:186-345: events present in BOTH directories (262-264), `<l1>_vs_<l2>.miso_bf`."""
+                              sample_labels=None, device=0, decoder=None, delta_thresholds=None):
+    """hypothesis_test.py:186-345: events present in BOTH directories (262-264), `<l1>_vs_<l2>.miso_bf`.
+    delta_thresholds (--delta-posterior): also `<l1>_vs_<l2>.miso_dpsi` beside it, the table of delta psi over all pairs of
+    the two samples' draws (compare.write_dpsi) for the same events; the `.miso_bf` is what it is without."""
+    delta = None if delta_thresholds is None else (compare.check_delta_thresholds(delta_thresholds), {})
     decoder = _decoder(decoder)
     stats = _Stats(decoder)
     l1, l2 = sample_labels or (os.path.basename(os.path.normpath(sample1_dir)), os.path.basename(os.path.normpath(sample2_dir)))
@@ -490,7 +515,7 @@ def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_l
         ev1, ev2 = sides
         both = sorted(set(ev1) & set(ev2))                # (an event that could not be parsed drops out of the pairing)
         stats.stage("read+parse")
-        _compare_parsed([(ev1[n], ev2[n]) for n in both], confidence_level, smoothing, device, rows)
+        _compare_parsed([(ev1[n], ev2[n]) for n in both], confidence_level, smoothing, device, rows, delta)
     else:
         sides = []
         for src in (f1, f2):
@@ -518,6 +543,8 @@ def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_l
                 b2 = _text_batch([p[1] for p in run], S, device, stats)
                 b1.summarize(confidence_level); b2.summarize(confidence_level)
                 b1.compare(b2, smoothing)
+                # (an event the decoder did not take comes back not finite here; the host parser's pass below replaces it)
+                _delta_posterior(b1, b2, len(run), [p[0].name for p in run], S, confidence_level, delta)
                 for i, (a, c) in enumerate(run):
                     if b1.status[i] or b2.status[i]:
                         left.append((a, c))
@@ -533,12 +560,14 @@ def output_samples_comparison(sample1_dir, sample2_dir, output_dir, confidence_l
                     stats.d["fallback_events"].append(e.name)
         parsed = [(_parse_or_skip(a), _parse_or_skip(c)) for a, c in left]
         _compare_parsed([p for p in parsed if p[0] is not None and p[1] is not None], confidence_level, smoothing,
-                        device, rows)
+                        device, rows, delta)
     rows.sort(key=lambda r: r[0])
     name = "%s_vs_%s" % (l1, l2)
     out = os.path.join(output_dir, name, "bayes-factors", name + ".miso_bf")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     compare.write_comparison(out, rows)
+    if delta is not None:
+        compare.write_dpsi(out[:-len(".miso_bf")] + ".miso_dpsi", [r + (delta[1][r[0]],) for r in rows], delta[0])
     stats.stage("write")
     stats.done()
     return out, len(rows)
@@ -796,8 +825,23 @@ def main(argv=None):
     ap.add_argument("--compare-groups", nargs=3, metavar=("DIR[,DIR...]", "DIR[,DIR...]", "OUTPUT_DIR"),
                     help="every pair of two groups of sample directories (replicates), one .miso_bf per pair")
     ap.add_argument("--group-labels", nargs=2, default=None, metavar=("L[,L...]", "L[,L...]"))
+    ap.add_argument("--delta-posterior", action="store_true",
+                    help="with --compare-samples: also write <l1>_vs_<l2>.miso_dpsi beside the .miso_bf -- median and 95 %% "
+                         "credible interval of delta psi, P(delta psi > 0), P(delta psi < 0) and P(|delta psi| >= T) over ALL "
+                         "pairs of the two samples' draws, for events of any number of isoforms")
+    ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
+                    help="the thresholds T of --delta-posterior, each in (0, 1), at most four (default 0.1 0.2)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.delta_posterior and not a.compare_samples:      # argument errors, before any work
+        ap.error("--delta-posterior goes with --compare-samples")
+    if a.delta_psi_thresholds is not None:
+        if not a.delta_posterior:
+            ap.error("--delta-psi-thresholds goes with --delta-posterior")
+        try:
+            compare.check_delta_thresholds(a.delta_psi_thresholds)
+        except ValueError as err:
+            ap.error(str(err))
     if a.summarize_samples:
         samples_dir, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.summarize_samples)
         label = os.path.basename(os.path.normpath(samples_dir))          # summarize_miso.py: <dir name>.miso_summary
@@ -816,7 +860,11 @@ def main(argv=None):
         ap.error("--rank-diagnostics goes with --diagnose-samples")
     if a.compare_samples:
         d1, d2, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.compare_samples)
-        out, n = output_samples_comparison(d1, d2, out_dir, sample_labels=a.comparison_labels, device=a.device)
+        thr = None
+        if a.delta_posterior:
+            thr = compare.DEFAULT_DELTA_THRESHOLDS if a.delta_psi_thresholds is None else a.delta_psi_thresholds
+        out, n = output_samples_comparison(d1, d2, out_dir, sample_labels=a.comparison_labels, device=a.device,
+                                           delta_thresholds=thr)
         print("Compared %d events into %s" % (n, out))
     if a.compare_groups:
         try:
