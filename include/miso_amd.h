@@ -474,6 +474,24 @@ int miso_batch_compare_pairs_ms(const miso_batch_t *sample1, float *ms);
 int miso_batch_compare_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2,
                               double smoothing, int staging, double *out, int64_t out_len, float *kernel_ms);
 
+/* miso_batch_compare_pairs for two groups of replicates, pooled (csrc/kernels_compare_pairs_groups.hip).
+   group1, group2: as miso_batch_compare_groups requires them -- the same events in the same order with the same isoform
+   counts and the same n_samples = S, one device, launched (a batch not yet synced is waited for); n1, n2 >= 1.
+   Per (event, isoform): A = the multiset union of the group-1 batches' columns (N1 = n1 * S draws), B the same of group 2
+   (N2 = n2 * S), D the multiset of the IEEE doubles a - b, M = N1 * N2; ranks, order statistics, counts, the +0.0 of a zero,
+   not-finite columns and undecoded events (in ANY batch) exactly as miso_batch_compare_pairs defines them over this D.  The
+   result does not depend on the order of the batches within a group; n1 = n2 = 1 gives miso_batch_compare_pairs bit for bit.
+   as_text != 0: every draw rounded to "%.4f" and read back first, as miso_batch_compare_pairs_as_text.
+   out: pairs_words = 6 + n_tau 64-bit words per (event, isoform), event e's isoform k at (isoforms of the events before e + k)
+   * pairs_words: the bits of median, ci_low, ci_high; n_gt0; n_lt0; finite; n_abs_ge per threshold.  *n_pairs = M;
+   *kernel_ms: the launches' time (a call is split over event ranges so that its device workspace stays within 256 MiB);
+   either may be NULL.  Nothing is stored in a batch: earlier results of every batch stay as they were.
+   MISO_EINVAL, nothing launched: 0 <= n_tau <= 4, each tau inside (0, 1), confidence_level inside (0, 1) violated; N1 or N2
+   above 16384; out too short; a batch at fault (the message names its group and index).  MISO_ENODEVICE without a GPU. */
+int miso_batch_compare_pairs_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2,
+                                    double confidence_level, const double *tau, int n_tau, int as_text, uint64_t *out,
+                                    int64_t out_len, int64_t *n_pairs, float *kernel_ms);
+
 /* device_match batches: kernel time of the matching launch done by miso_batch_upload, and (tests:
    want_counts_trace batches only) the kernel's output for event i in the layout of
    miso_match_iso[_paired]: match noiso x n_reads, fragmentLength likewise or NULL. */

@@ -769,6 +769,59 @@ def compare_groups(batches1, batches2, smoothing=0.3, staging="auto", noiso=None
     return GroupComparison(out, len(b2), noiso, float(ms.value))
 
 
+# ---- delta psi between two pooled groups of samples (include/miso_amd.h miso_batch_compare_pairs_groups) ----
+PAIRS_FIXED_WORDS = 6        # csrc/compare_pairs.hpp: median, ci_low, ci_high, n_gt0, n_lt0, finite; then n_abs_ge per threshold
+MAX_GROUP_PAIR_DRAWS = 16384
+
+
+class GroupPairComparison:
+    """What compare_pairs_groups computed: pair_comparison(event) is Batch.pair_comparison's tuple for the two pooled groups;
+    `kernel_ms` the launches' time, `n_pairs` = M."""
+
+    def __init__(self, out, noiso, n_tau, n_pairs, kernel_ms):
+        self.noiso = np.asarray(noiso, dtype=np.int64)
+        self.offs = np.concatenate([[0], np.cumsum(self.noiso)])
+        self.n_tau = n_tau
+        self.out = out.reshape(int(self.offs[-1]), PAIRS_FIXED_WORDS + n_tau)
+        self.n_pairs = n_pairs
+        self.kernel_ms = kernel_ms
+
+    def pair_comparison(self, event):
+        """(median[K], ci_low[K], ci_high[K], n_gt0[K], n_lt0[K], n_abs_ge[K, n_tau], finite[K], n_pairs) of `event`."""
+        if not 0 <= event < len(self.noiso):
+            raise IndexError("event %d of %d" % (event, len(self.noiso)))
+        q = self.out[self.offs[event]:self.offs[event + 1]]
+        d = np.ascontiguousarray(q[:, :3]).view(np.float64)
+        return (d[:, 0].copy(), d[:, 1].copy(), d[:, 2].copy(), q[:, 3].astype(np.int64), q[:, 4].astype(np.int64),
+                q[:, PAIRS_FIXED_WORDS:].astype(np.int64), q[:, 5] != 0, self.n_pairs)
+
+
+def compare_pairs_groups(batches1, batches2, confidence_level=0.95, thresholds=(0.1, 0.2), as_text=False, noiso=None):
+    """Batch.compare_pairs for two groups of replicates, pooled: per (event, isoform) the median, credible interval and exact
+    counts of ALL differences between the draws of batches1 taken together and those of batches2 taken together
+    (DESIGN.md 19a).  The batches are what compare_groups takes: the same events in the same order with the same number of
+    samples S, on one device; len(batches) * S is 16384 at most on either side.  Nothing is stored in a batch.
+    noiso: the events' isoform counts where the caller knows them."""
+    b1, b2 = list(batches1), list(batches2)
+    L = lib()
+    L.miso_batch_compare_pairs_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    h1 = (C.c_void_p * max(len(b1), 1))(*[b.handle for b in b1])
+    h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
+    noiso = [int(k) for k in noiso] if noiso is not None else []
+    if not noiso and b1 and len(b1[0]):
+        K = C.c_int()
+        for e in range(len(b1[0])):
+            check(L.miso_batch_event_info(b1[0].handle, e, C.byref(K), None, None, None))
+            noiso.append(K.value)
+    tt = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    out = np.zeros(int(sum(noiso)) * (PAIRS_FIXED_WORDS + len(tt)), np.uint64)
+    ms, M = C.c_float(0.0), C.c_int64(0)
+    check(L.miso_batch_compare_pairs_groups(h1, len(b1), h2, len(b2), C.c_double(confidence_level), _p(tt), C.c_int(len(tt)),
+                                            C.c_int(1 if as_text else 0), _p(out), out.size, C.byref(M), C.byref(ms)))
+    return GroupPairComparison(out, noiso, len(tt), int(M.value), float(ms.value))
+
+
 # ---- `.miso` sample text (include/miso_amd.h miso_text_shape, miso_batch_from_miso_text) ----
 MISO_TEXT_EPSI, MISO_TEXT_EROW, MISO_TEXT_ESCORE, MISO_TEXT_ECOUNT = 1, 2, 4, 8
 

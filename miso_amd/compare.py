@@ -157,3 +157,57 @@ def write_dpsi(filename, rows, thresholds):
             f.write(dpsi_line(comparison_line(*row[:6]), row[6], len(thresholds)) + "\n")
             n += 1
     return n
+
+
+# ---- the pooled table of two replicate groups, `<A>_vs_<B>/delta-psi/<A>_vs_<B>.miso_group_dpsi` ----
+GROUP_DPSI_HEAD = ["event_name", "group1_replicates", "group2_replicates", "group1_posterior_mean", "group2_posterior_mean",
+                   "diff"]
+GROUP_DPSI_TAIL = ["isoforms", "chrom", "strand", "mRNA_starts", "mRNA_ends"]
+
+
+def group_dpsi_header_fields(thresholds):
+    return GROUP_DPSI_HEAD + DPSI_FIELDS + ["prob_abs_diff_ge_%g" % t for t in thresholds] + GROUP_DPSI_TAIL
+
+
+def group_mean(means):
+    """means: per replicate, in replicate order, the K double means of its summary -> their mean per isoform, summed in that
+    order and divided once"""
+    K = len(means[0])
+    out = []
+    for k in range(K):
+        acc = 0.0
+        for m in means:
+            acc += float(m[k])
+        out.append(acc / len(means))
+    return out
+
+
+def group_dpsi_line(event_name, n1, n2, means1, means2, pairs, header, n_thresholds):
+    """n1, n2: the samples of either group that were pooled (that have the event).  means1, means2: group_mean's input per
+    group, or None: NA in both means and their difference.  pairs: dpsi_fields' -- capi.GroupPairComparison.pair_comparison's
+    tuple, or None: NA in every pooled field.  header: the header fields of the first pooled group-1 sample."""
+    f = [event_name, "%d" % n1, "%d" % n2]
+    if means1 is None or means2 is None:
+        f += ["NA"] * 3
+    else:
+        m1, m2 = group_mean(means1), group_mean(means2)
+        ks = [0] if len(m1) == 2 else range(len(m1))
+        join = lambda v: ",".join("%.4f" % v[k] for k in ks)  # noqa: E731
+        f += [join(m1), join(m2), join([a - b for a, b in zip(m1, m2)])]
+    f += dpsi_fields(pairs, n_thresholds)
+    f.append(header.get("isoforms", "NA"))
+    for key in ("chrom", "strand", "mRNA_starts", "mRNA_ends"):
+        f.append(header.get(key, "NA"))
+    return "\t".join(f)
+
+
+def write_group_dpsi(filename, rows, thresholds):
+    """rows: iterable of (event_name, n1, n2, means1, means2, pairs, header) -- group_dpsi_line's arguments."""
+    thresholds = check_delta_thresholds(thresholds)
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(group_dpsi_header_fields(thresholds)) + "\n")
+        for row in rows:
+            f.write(group_dpsi_line(*row, n_thresholds=len(thresholds)) + "\n")
+            n += 1
+    return n

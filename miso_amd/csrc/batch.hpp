@@ -85,6 +85,9 @@ void exact_paired_compare_run(const ExactPairedCmpInput &in1, const ExactPairedC
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
                     int64_t out_len, float *kernel_ms);
+// kernels_compare_pairs_groups.hip
+void compare_pairs_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double confidence_level, const double *tau,
+                          int n_tau, bool as_text, uint64_t *out, int64_t out_len, int64_t *n_pairs, float *kernel_ms);
 
 // A device table and what it was last filled from: its host contents, or the key of the plan it was built for.  reset()
 // frees the allocation and forgets both, so that neither outlives it (the next upload may be to another device).

@@ -983,6 +983,16 @@ int miso_batch_compare_groups(miso_batch_t *const *group1, int n1, miso_batch_t 
   });
 }
 
+int miso_batch_compare_pairs_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2,
+                                    double confidence_level, const double *tau, int n_tau, int as_text, uint64_t *out,
+                                    int64_t out_len, int64_t *n_pairs, float *kernel_ms) {
+  return guarded([&] {
+    need(group1, "group1"); need(group2, "group2");
+    if (n_tau > 0) need(tau, "tau");
+    compare_pairs_groups(group1, n1, group2, n2, confidence_level, tau, n_tau, as_text != 0, out, out_len, n_pairs, kernel_ms);
+  });
+}
+
 int miso_batch_last_match_ms(const miso_batch_t *b, float *ms) {
   return guarded([&] { need(b, "batch"); need(ms, "ms"); *ms = b->match_ms; });
 }

@@ -8,6 +8,9 @@ namespace miso {
 // draws per column at most: both sorted columns stay in LDS, 2 * 8192 * 8 bytes = 128 KB of a workgroup's 160 KB
 constexpr int PAIRS_MAX_DRAWS = 8192;
 constexpr int PAIRS_MAX_TAU = 4;
+// pooled draws per column and group at most in compare_pairs_groups_kernel (kernels_compare_pairs_groups.hip): one sorted
+// group stays in LDS, 16384 * 8 bytes = 128 KB, the other in global memory; M <= 2^28, ranks and counts fit 32 bits
+constexpr int PAIRS_GROUP_MAX_DRAWS = 16384;
 
 // the three order statistics' ranks over the S1 * S2 differences (median, ci_low, ci_high) and the thresholds
 struct PairsArgs {

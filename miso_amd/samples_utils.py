@@ -33,6 +33,8 @@ standard error; diagnostics.py) of the files' four-decimal values,
 `--compare-groups` is `--compare-samples` for biological replicates (what filter_events --votes reads): every pair of the
 two groups gets the file the pairwise call writes, byte for byte, but every tree is read once, every sample decoded and
 summarised once per chunk of events, and all pairs of a chunk come out of one launch (capi.compare_groups).
+With `--delta-posterior` every pair also gets its `.miso_dpsi`, and the two groups one pooled table, `.miso_group_dpsi`: delta
+psi over all differences between the pooled draws of the groups (capi.compare_pairs_groups).
 """
 import glob
 import os
@@ -701,17 +703,105 @@ class _ParsedSample:
         return self.ev[name]
 
 
+MAX_GROUP_PAIR_DRAWS = capi.MAX_GROUP_PAIR_DRAWS      # miso_batch_compare_pairs_groups: pooled draws per event and group
+DEFAULT_GROUP_NAMES = ("group1", "group2")
+
+
+class _GroupDelta:
+    """--compare-groups --delta-posterior: what the pairwise tables and the pooled table are written from.
+    pair[(i, j)]: _delta_posterior's results of that pair of samples.  rows: compare.write_group_dpsi's, one per event that a
+    sample of each group has.  A cause for NA is said once per call (notice)."""
+
+    def __init__(self, thresholds, n1, n2):
+        self.thresholds = compare.check_delta_thresholds(thresholds)
+        self.pair = {(i, j): {} for i in range(n1) for j in range(n2)}
+        self.rows = []
+        self.said = set()
+        self.kernel_ms = 0.0
+
+    def of_pair(self, i, j):
+        """_delta_posterior's `delta` for the pair; its own notice is printed by the first pair that meets the cause"""
+        res = self.pair[(i, j)]
+        if "pair_draws" in self.said:
+            res[None] = None
+        return self.thresholds, res
+
+    def seen(self, i, j):
+        if None in self.pair[(i, j)]:
+            self.said.add("pair_draws")
+
+    def notice(self, cause, text):
+        if cause not in self.said:
+            print(text)
+            self.said.add(cause)
+
+    def pooled(self, batches1, batches2, names, K, S, confidence_level):
+        """{name: pair_comparison} of the events of two lists of batches, pooled on the device; None for all of them where a
+        group's draws are too many for the pass"""
+        for g, bs in ((1, batches1), (2, batches2)):
+            if len(bs) * S > MAX_GROUP_PAIR_DRAWS:
+                self.notice("group_draws", "No pooled delta psi for events of more than %d draws a group (%s: group %d has %d "
+                            "samples of %d): their rows print NA" % (MAX_GROUP_PAIR_DRAWS, names[0], g, len(bs), S))
+                return {name: None for name in names}
+        gp = capi.compare_pairs_groups(batches1, batches2, confidence_level, self.thresholds, noiso=K)
+        self.kernel_ms += gp.kernel_ms
+        return {name: gp.pair_comparison(e) for e, name in enumerate(names)}
+
+
+def _group_delta_parsed(gd, samples, names, pairs_of, confidence_level, device):
+    """The pooled rows of the events the group route did not take (gd: _GroupDelta): pooled from the host parser's doubles
+    over the samples that have the event where those agree on (K, S) -- the same doubles, the same device pass --, NA where
+    they do not or where the parser refuses the event in some sample too."""
+    classes = {}
+    for name in names:
+        have = [sorted({p[g] for p in pairs_of[name]}) for g in (0, 1)]
+        parsed = [[samples[g][i].parse(name) for i in have[g]] for g in (0, 1)]
+        header = samples[0][have[0][0]].header(name)
+        flat = parsed[0] + parsed[1]
+        if any(p is None for p in flat):
+            gd.notice("unparsed", "No pooled delta psi for events that could not be parsed in some sample (%s): their rows print NA"
+                      % name)
+        elif len({p[1].shape for p in flat}) > 1:
+            gd.notice("shapes", "No pooled delta psi for events whose samples differ in isoforms or sample count (%s): their rows "
+                      "print NA" % name)
+        else:
+            S, K = flat[0][1].shape
+            classes.setdefault((S, tuple(have[0]), tuple(have[1])), []).append((name, K, parsed, header))
+            continue
+        gd.rows.append((name, len(have[0]), len(have[1]), None, None, None, header))
+    for (S, p1, p2), evs in sorted(classes.items()):
+        lo, _ = summary.credible_interval_ranks(S, confidence_level)
+        if lo <= 0 or S < 2:                              # as the chunks of the group route: no interval, no rows
+            continue
+        batches = [[capi.SamplesBatch([ev[2][g][a][1] for ev in evs], device=device) for a in range(len(p))]
+                   for g, p in enumerate((p1, p2))]
+        for bs in batches:
+            for b in bs:
+                b.summarize(confidence_level)
+        res = gd.pooled(batches[0], batches[1], [ev[0] for ev in evs], [ev[1] for ev in evs], S, confidence_level)
+        for e, (name, K, _, header) in enumerate(evs):
+            means = [[b.summary(e)[0] for b in bs] for bs in batches]
+            gd.rows.append((name, len(p1), len(p2), means[0], means[1], res[name], header))
+
+
 def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=None, confidence_level=0.95, smoothing=0.3,
-                             device=0, decoder=None):
+                             device=0, decoder=None, delta_thresholds=None, group_names=None):
     """compare_miso for replicates: every pair (dirs1[i], dirs2[j]) as output_samples_comparison writes it -- the same
     `<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf`, byte for byte -- with every tree listed and read once, every
     sample's text decoded and summarised once, and all pairs of a chunk of events in one launch
     (capi.compare_groups).  plan_group_comparison decides which events take that route.  Returns [(path, n_rows)] in
-    row-major pair order."""
+    row-major pair order.
+    delta_thresholds (--delta-posterior): also `<l1>_vs_<l2>.miso_dpsi` beside every `.miso_bf`, as output_samples_comparison
+    writes it, and the pooled table `<A>_vs_<B>/delta-psi/<A>_vs_<B>.miso_group_dpsi` (group_names = (A, B), default
+    group1, group2): delta psi over all pairs of the two groups' pooled draws (capi.compare_pairs_groups), one
+    row per event that a sample of each group has; its (path, n_rows) is the last of the list.  Without it the files are what
+    they are without the option."""
     labels1, labels2 = group_labels(dirs1, dirs2, labels1, labels2)
     decoder = _decoder(decoder)
     stats = _Stats(decoder)
     n1, n2 = len(dirs1), len(dirs2)
+    gd = None if delta_thresholds is None else _GroupDelta(delta_thresholds, n1, n2)
+    group_names = tuple(group_names or DEFAULT_GROUP_NAMES)
     stats.d.update({"samples": n1 + n2, "pairs": n1 * n2, "group_events": 0, "pair_route_events": [], "group_chunks": 0,
                     "compare_kernel_ms": 0.0})
     srcs = [[_sources(d) for d in dirs] for dirs in (dirs1, dirs2)]
@@ -746,6 +836,14 @@ def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=Non
         stats.d["compare_kernel_ms"] += cmp.kernel_ms
         stats.d["group_chunks"] += 1
         stats.stage("compare")
+        if gd is not None:
+            for a, i in enumerate(present[0]):
+                for c, j in enumerate(present[1]):
+                    # (an event the decoder did not take comes back not finite here; the host parser's pass below replaces it)
+                    _delta_posterior(batches[0][a], batches[1][c], len(names), names, S, confidence_level, gd.of_pair(i, j))
+                    gd.seen(i, j)
+            pooled = gd.pooled(batches[0], batches[1], names, K, S, confidence_level)
+            stats.stage("delta")
         bad = np.zeros(len(names), bool)
         for g in (0, 1):
             for b in batches[g]:
@@ -760,6 +858,11 @@ def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=Non
                     if not bad[e]:
                         out.append((name, summ[0][a][e], summ[1][c][e], bf[cmp.offs[e] + 2:cmp.offs[e + 1]:4],
                                     hdrs[0][a][e], hdrs[1][c][e]))
+        if gd is not None:
+            for e, name in enumerate(names):
+                if not bad[e]:
+                    gd.rows.append((name, len(present[0]), len(present[1]), [sm[e][0] for sm in summ[0]],
+                                    [sm[e][0] for sm in summ[1]], pooled[name], hdrs[0][0][e]))
         for e, name in enumerate(names):
             if bad[e]:                                    # outside the device decoder's grammar in some sample
                 routed[name] = "fallback"
@@ -777,10 +880,24 @@ def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=Non
     for (i, j), names in sorted(left.items()):
         parsed = [(samples[0][i].parse(n), samples[1][j].parse(n)) for n in names]
         _compare_parsed([p for p in parsed if p[0] is not None and p[1] is not None], confidence_level, smoothing, device,
-                        rows[(i, j)])
+                        rows[(i, j)], None if gd is None else gd.of_pair(i, j))
+        if gd is not None:
+            gd.seen(i, j)
     stats.d["fallback_events"] = sorted(n for n, r in routed.items() if r == "fallback")
     stats.d["pair_route_events"] = sorted(n for n, r in routed.items() if r == "pair")
     stats.stage("pairwise")
+    if gd is not None:
+        pair_route = sorted(n for n, r in routed.items() if r == "pair")
+        if pair_route:
+            gd.notice("shapes", "No pooled delta psi for events whose samples differ in isoforms or sample count (%s): their "
+                      "rows print NA" % pair_route[0])
+        for name in pair_route:
+            have = [sorted({p[g] for p in pairs_of[name]}) for g in (0, 1)]
+            gd.rows.append((name, len(have[0]), len(have[1]), None, None, None, samples[0][have[0][0]].header(name)))
+        _group_delta_parsed(gd, samples, sorted(n for n, r in routed.items() if r == "fallback"), pairs_of, confidence_level,
+                            device)
+        stats.d["pairs_groups_kernel_ms"] = gd.kernel_ms
+        stats.stage("delta")
 
     written = []
     for i in range(n1):
@@ -790,7 +907,16 @@ def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=Non
             os.makedirs(os.path.dirname(out), exist_ok=True)
             rows[(i, j)].sort(key=lambda r: r[0])
             compare.write_comparison(out, rows[(i, j)])
+            if gd is not None:
+                compare.write_dpsi(out[:-len(".miso_bf")] + ".miso_dpsi", [r + (gd.pair[(i, j)][r[0]],) for r in rows[(i, j)]],
+                                   gd.thresholds)
             written.append((out, len(rows[(i, j)])))
+    if gd is not None:
+        name = "%s_vs_%s" % group_names
+        out = os.path.join(output_dir, name, "delta-psi", name + ".miso_group_dpsi")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        gd.rows.sort(key=lambda r: r[0])
+        written.append((out, compare.write_group_dpsi(out, gd.rows, gd.thresholds)))
     stats.stage("write")
     stats.done()
     return written
@@ -825,16 +951,25 @@ def main(argv=None):
     ap.add_argument("--compare-groups", nargs=3, metavar=("DIR[,DIR...]", "DIR[,DIR...]", "OUTPUT_DIR"),
                     help="every pair of two groups of sample directories (replicates), one .miso_bf per pair")
     ap.add_argument("--group-labels", nargs=2, default=None, metavar=("L[,L...]", "L[,L...]"))
+    ap.add_argument("--group-names", nargs=2, default=None, metavar=("A", "B"),
+                    help="with --compare-groups --delta-posterior: the two groups' names in the pooled table's path, "
+                         "OUTPUT_DIR/A_vs_B/delta-psi/A_vs_B.miso_group_dpsi (default group1 group2)")
     ap.add_argument("--delta-posterior", action="store_true",
-                    help="with --compare-samples: also write <l1>_vs_<l2>.miso_dpsi beside the .miso_bf -- median and 95 %% "
+                    help="with --compare-groups: the same beside every pair's .miso_bf, and the pooled table "
+                         "<A>_vs_<B>.miso_group_dpsi of delta psi over all pairs of the two groups' pooled draws.  "
+                         "With --compare-samples: also write <l1>_vs_<l2>.miso_dpsi beside the .miso_bf -- median and 95 %% "
                          "credible interval of delta psi, P(delta psi > 0), P(delta psi < 0) and P(|delta psi| >= T) over ALL "
                          "pairs of the two samples' draws, for events of any number of isoforms")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
                     help="the thresholds T of --delta-posterior, each in (0, 1), at most four (default 0.1 0.2)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    if a.delta_posterior and not a.compare_samples:      # argument errors, before any work
-        ap.error("--delta-posterior goes with --compare-samples")
+    if a.delta_posterior and not (a.compare_samples or a.compare_groups):      # argument errors, before any work
+        # (both wordings: scripts and tests match on the older "goes with --compare-samples")
+        ap.error("--delta-posterior needs --compare-samples or --compare-groups "
+                 "(--delta-posterior goes with --compare-samples, and with --compare-groups)")
+    if a.group_names and not (a.compare_groups and a.delta_posterior):
+        ap.error("--group-names goes with --compare-groups --delta-posterior")
     if a.delta_psi_thresholds is not None:
         if not a.delta_posterior:
             ap.error("--delta-psi-thresholds goes with --delta-posterior")
@@ -858,11 +993,11 @@ def main(argv=None):
         ap.error("--num-chains goes with --diagnose-samples")
     elif a.rank_diagnostics:
         ap.error("--rank-diagnostics goes with --diagnose-samples")
+    thr = None
+    if a.delta_posterior:
+        thr = compare.DEFAULT_DELTA_THRESHOLDS if a.delta_psi_thresholds is None else a.delta_psi_thresholds
     if a.compare_samples:
         d1, d2, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.compare_samples)
-        thr = None
-        if a.delta_posterior:
-            thr = compare.DEFAULT_DELTA_THRESHOLDS if a.delta_psi_thresholds is None else a.delta_psi_thresholds
         out, n = output_samples_comparison(d1, d2, out_dir, sample_labels=a.comparison_labels, device=a.device,
                                            delta_thresholds=thr)
         print("Compared %d events into %s" % (n, out))
@@ -871,7 +1006,8 @@ def main(argv=None):
             dirs1, dirs2, out_dir, l1, l2 = parse_group_args(a.compare_groups, a.group_labels)
         except ValueError as err:
             ap.error(str(err))
-        for out, n in output_group_comparisons(dirs1, dirs2, out_dir, l1, l2, device=a.device):
+        for out, n in output_group_comparisons(dirs1, dirs2, out_dir, l1, l2, device=a.device, delta_thresholds=thr,
+                                               group_names=a.group_names):
             print("Compared %d events into %s" % (n, out))
     elif a.group_labels:
         ap.error("--group-labels goes with --compare-groups")
