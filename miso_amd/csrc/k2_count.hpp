@@ -70,8 +70,12 @@ K2_FLAG_FN int k2_count_finish(int A, int E, int more) { return ((A - E) >> 1) +
 K2_FLAG_FN bool k2_count_top_clean(int A, uint32_t n_flagged, int N) { return n_flagged == 0u && A == 2 * N; }
 
 #if defined(__HIPCC__)
-// The device's fast form.  Two words per statement, interleaved so that no packed operation reads the result of the one
-// before it (inside a statement the hardware's interlocks apply; behind a statement of its own the compiler pads with s_nop).
+// The device's fast form.  Two words per statement: THREE operations per word -- sub, min, and half of a three-input add and
+// a three-input or that take both words' c at once (v_add3_u32: acc + c_a + c_b, the same 32-bit sum as two adds, the halves
+// carry no more than before; v_or3_b32: o | c_a | c_b).  The two subtracts and the two minima are interleaved so that no
+// packed operation reads the result of the one before it; the three-input add reads both minima and so follows one directly:
+// a dependent pair of these issues like an independent one (profiles/issue_costs_k2.txt).  Inside a statement the hardware's
+// interlocks apply; behind a statement of its own the compiler pads with s_nop.
 // FIRST: the trip's first pair starts o as c_a | c_b.
 // STEADY trips: classification and sums in one statement.
 template <bool FIRST>
@@ -80,12 +84,12 @@ __device__ __forceinline__ void k2_count_pair(uint32_t &acc, uint32_t &o, uint32
   if (FIRST)
     asm("v_pk_sub_u16 %0, %4, %5 clamp\n\tv_pk_sub_u16 %1, %4, %6 clamp\n\t"
         "v_pk_min_u16 %0, %0, %7\n\tv_pk_min_u16 %1, %1, %7\n\t"
-        "v_add_u32 %2, %2, %0\n\tv_or_b32 %3, %0, %1\n\tv_add_u32 %2, %2, %1"
+        "v_add3_u32 %2, %2, %0, %1\n\tv_or_b32 %3, %0, %1"
         : "=&v"(ca), "=&v"(cb), "+v"(acc), "=&v"(o) : "v"(P), "v"(ua), "v"(ub), "v"(two));
   else
     asm("v_pk_sub_u16 %0, %4, %5 clamp\n\tv_pk_sub_u16 %1, %4, %6 clamp\n\t"
         "v_pk_min_u16 %0, %0, %7\n\tv_pk_min_u16 %1, %1, %7\n\t"
-        "v_add_u32 %2, %2, %0\n\tv_or_b32 %3, %3, %0\n\tv_add_u32 %2, %2, %1\n\tv_or_b32 %3, %3, %1"
+        "v_add3_u32 %2, %2, %0, %1\n\tv_or3_b32 %3, %3, %0, %1"
         : "=&v"(ca), "=&v"(cb), "+v"(acc), "+v"(o) : "v"(P), "v"(ua), "v"(ub), "v"(two));
 }
 // MASKED trips and single steps: the masks go between the classification and the sums -- two statements, one `and` per word.
@@ -99,10 +103,10 @@ __device__ __forceinline__ void k2_count_pair_masked(uint32_t &acc, uint32_t &o,
   ca &= ~inva;
   cb &= ~invb;
   if (FIRST)
-    asm("v_add_u32 %0, %0, %2\n\tv_or_b32 %1, %2, %3\n\tv_add_u32 %0, %0, %3"
+    asm("v_add3_u32 %0, %0, %2, %3\n\tv_or_b32 %1, %2, %3"
         : "+v"(acc), "=&v"(o) : "v"(ca), "v"(cb));
   else
-    asm("v_add_u32 %0, %0, %2\n\tv_or_b32 %1, %1, %2\n\tv_add_u32 %0, %0, %3\n\tv_or_b32 %1, %1, %3"
+    asm("v_add3_u32 %0, %0, %2, %3\n\tv_or3_b32 %1, %1, %2, %3"
         : "+v"(acc), "+v"(o) : "v"(ca), "v"(cb));
 }
 #endif

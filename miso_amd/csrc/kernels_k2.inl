@@ -739,10 +739,11 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     int d0 = 0; K2Flag amb;
     PROF_T(g1);
     PROF_ADD(pf_thr, g0, g1);
-    // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask), FOUR
+    // Both half-words of a generator word at once (packed 16-bit arithmetic, no per-half compare into a lane mask), THREE
     // operations per word (k2_count.hpp): with P = th + 1 in both halves the saturating P - x is 0 iff x > th, 1 iff
-    // x == th and >= 2 iff x < th; c = min(.., 2) classifies the half three ways.  accv += c with a plain 32-bit add
-    // (per half 2 * below + on; the halves never carry: CHUNK below) and o |= c with a plain 32-bit or: bit 0 of a half of
+    // x == th and >= 2 iff x < th; c = min(.., 2) classifies the half three ways.  accv += c_a + c_b with ONE three-input
+    // 32-bit add per pair of words (per half 2 * below + on; the halves never carry: CHUNK below) and o |= c_a | c_b with
+    // ONE three-input or (the trip's first pair: o = c_a | c_b): bit 0 of a half of
     // o says that a read of the trip sits ON the threshold, tested once per trip (z = o & 0x00010001).  Behind the loop
     // the lane holds A = 2 below + E and d0 = (A - E) / 2 + more; E and more are 0 unless a trip was flagged.
     // th = 0xFFFF: P does not fit a half; the loop runs with P = 0xFFFF and the lane finishes by k2_count.hpp's rule.
@@ -753,7 +754,8 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // it assumes a destination-forwarding hazard it cannot see into -- and these operations have none: inside a statement
     // the hardware's ordinary interlocks apply.
     // Before the three-way form: five operations per word -- the count from min(sat(th - x), 1) with a packed add, the
-    // equal test as a running packed minimum of x ^ th: 96 `v_*` per steady trip against 87 now, docs/history.md.
+    // equal test as a running packed minimum of x ^ th: 96 `v_*` per steady trip; four -- a plain add and a plain or per
+    // word: 87; 80 now, docs/history.md.
     // Measured, same box, 40 000 events x 1000 reads: one SDWA compare per half into a lane mask + add-with-carry, 110
     // VALU per 16 reads, 74.6 ms; this form, 108 VALU but no lane masks, 71.0 ms; MISO defaults 235.9 -> 219.1 ms,
     // hg19-like read counts 66.4 -> 59.4 ms; the equal test once per trip instead of once per block: 70.9 -> 69.3 ms,
@@ -781,7 +783,7 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
       for (int i = 0; i < NB; i++) {
         const int q = sub + (k + i) * GE;
 #pragma unroll
-        for (int w = 0; w < 4; w += 2) {   // two words per statement, interleaved: no packed operation reads its predecessor's result
+        for (int w = 0; w < 4; w += 2) {   // two words per statement: their subtracts and minima interleaved, one add3 and one or3 for both
           const uint32_t ua = u[i].v[w], ub = u[i].v[w + 1];
           if (!MASKED) {
             if (i == 0 && w == 0) k2_count_pair<true>(accv, o, P2, two2, ua, ub);   // o = c_a | c_b instead of o | c_a | c_b

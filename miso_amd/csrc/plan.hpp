@@ -49,11 +49,12 @@ struct LaneCost {
 // (MODE 2, dense records): block = generator + four reads' weights, compares and score gathers.
 // (round 4: the generator has 7 rounds instead of 10, include/miso_philox.h: three rounds x four instructions fewer per block
 // than the 52 / 115 measured in round 3)
-// (single-end since the lazy low bits: a block is EIGHT reads -- 27 generator instructions + 4 per word for the packed
-// three-way count, k2_count.hpp (5 before: a packed add and a running packed minimum of x ^ th where a plain add and a plain
-// or now stand) + the loop's share: 87 `v_*` instructions per two blocks in the loop's steady part (no compare, no select,
-// no s_nop: the trip flag is two sums, k2_flag.hpp; 96 with five operations per word, 97 with a compare and a select on
-// VCC before that), 115 in its masked tail trips (124, 125 before; a masked step of one block per lane ends the loop where
+// (single-end since the lazy low bits: a block is EIGHT reads -- 27 generator instructions + 3 per word for the packed
+// three-way count, k2_count.hpp: sub, min, and per word PAIR one three-input add and one three-input or (4 with a plain add
+// and a plain or per word; 5 before that: a packed add and a running packed minimum of x ^ th) + the loop's share: 80 `v_*`
+// instructions per two blocks in the loop's steady part (no compare, no select, no s_nop: the trip flag is two sums,
+// k2_flag.hpp; 87 with four operations per word, 96 with five, 97 with a compare and a select on VCC before that), 108 in
+// its masked tail trips (115, 124, 125 before; a masked step of one block per lane ends the loop where
 // the stride positions are odd), 103 before the loop was split -- counted between the loop's header and its backward branch
 // (docs/history.md; round 4's "108" for that loop counted the trip's `s_nop`s and the chunk loop's share as well); the
 // launch time hardly moves between 44 and 96,

@@ -222,6 +222,20 @@ __global__ void k_ds_read_b64(uint32_t *out, int n, uint32_t seed, unsigned long
 #define M_OR(i) "v_or_b32 %" #i ", %" #i ", %10\n"
 #define M_AND(i) "v_and_b32 %" #i ", %" #i ", %10\n"
 #define M_COUNT_WORD(i) "v_pk_sub_u16 %" #i ", %10, %" #i " clamp\n v_pk_min_u16 %" #i ", %" #i ", %11\n v_add_u32 %" #i ", %" #i ", %10\n v_or_b32 %" #i ", %" #i ", %11\n"
+// the three-input add and or alone, and the word PAIR as the read loop now issues it (k2_count_pair<false>): two subtracts, two
+// minima, ONE v_add3_u32 and ONE v_or3_b32 over both words' classes -- six instructions for two words.  Two such pairs per
+// entry, on registers %0..%3 and %4..%7 (ca, cb, acc, o), each taking the other's ca and cb as its generator words: twelve
+// instructions per entry whichever chain index, per_trip counts all twelve.  As in the loop the add3 reads the minimum just
+// before it and the or3 reads both minima.
+#define M_ADD3(i) "v_add3_u32 %" #i ", %" #i ", %10, %11\n"
+#define M_OR3(i) "v_or3_b32 %" #i ", %" #i ", %10, %11\n"
+#define M_COUNT_PAIR3(i) "v_pk_sub_u16 %0, %10, %4 clamp\n v_pk_sub_u16 %1, %10, %5 clamp\n v_pk_min_u16 %0, %0, %11\n v_pk_min_u16 %1, %1, %11\n" \
+                         "v_add3_u32 %2, %2, %0, %1\n v_or3_b32 %3, %3, %0, %1\n"                                                             \
+                         "v_pk_sub_u16 %4, %10, %0 clamp\n v_pk_sub_u16 %5, %10, %1 clamp\n v_pk_min_u16 %4, %4, %11\n v_pk_min_u16 %5, %5, %11\n" \
+                         "v_add3_u32 %6, %6, %4, %5\n v_or3_b32 %7, %7, %4, %5\n"
+DEF_KERNEL_32M(k_add3, P_NONE, M_ADD3)
+DEF_KERNEL_32M(k_or3, P_NONE, M_OR3)
+DEF_KERNEL_32M(k_count_pair3, P_NONE, M_COUNT_PAIR3)
 DEF_KERNEL_32M(k_or, P_NONE, M_OR)
 DEF_KERNEL_32M(k_and, P_NONE, M_AND)
 DEF_KERNEL_32M(k_count_word, P_NONE, M_COUNT_WORD)
@@ -303,6 +317,7 @@ int main() {
     {"v_pk_add_u16", k_pk_add, 64}, {"v_readlane+s_nop+v_add", k_readlane_nop, 64},
     {"v_bcnt_u32_b32", k_bcnt, 64}, {"pk_sub, pk_min dependent", k_pk_dep, 128}, {"pk_sub, s_nop 0, pk_min", k_pk_dep_nop, 128},
     {"v_or_b32", k_or, 64}, {"v_and_b32", k_and, 64}, {"pk_sub, pk_min, add, or", k_count_word, 256},
+    {"v_add3_u32", k_add3, 64}, {"v_or3_b32", k_or3, 64}, {"2 sub, 2 min, add3, or3", k_count_pair3, 768},
     {"ds_bpermute (8 + wait)", k_ds_bpermute, 64}, {"ds_bpermute, one + wait", k_ds_bpermute_serial, 64},
   };
   const int n = 2000;
