@@ -427,6 +427,24 @@ int miso_batch_compare_exact_paired(miso_batch_t *sample1, miso_batch_t *sample2
 /* Kernel time (HIP events) of the last miso_batch_compare and of the last miso_batch_compare_exact or
    miso_batch_compare_exact_paired stored in this batch, ms; 0 before. */
 int miso_batch_compare_ms(const miso_batch_t *sample1, float *compare_ms, float *exact_compare_ms);
+/* Quantiles of delta = psi_1 - psi_2 from the exact CDF H(z) = P(psi_1 - psi_2 <= z), without a draw
+   (csrc/kernels_exact_delta.hip, csrc/kernels_exact_paired_delta.hip).  Preconditions and errors as
+   miso_batch_compare_exact (single-end batches) or miso_batch_compare_exact_paired (paired-end batches: the batch kind
+   chooses); in addition sample1 must hold an exact comparison of either kind -- MISO_EINVAL "has not run" otherwise, as
+   miso_batch_get_exact_comparison's --, and exactly the pairs whose was_exact is set there are taken, sample2 being the
+   batch that comparison was made with.  H is the comparison's own cdf (the same operations in the same order); the device
+   chooses the points itself: per probability five rounds of eight points inside the bracket, which starts as (-1, 1) with
+   H = 0 and 1 at its ends, then one linear interpolation inside the last bracket, 2 / 9^5 wide.  p: n_p probabilities,
+   1 <= n_p <= 4, each inside (0, 1), MISO_EINVAL otherwise.  No Monte-Carlo error, no dependence on the seed.  Results are
+   stored in sample1 beside the comparison's; a later miso_batch_compare_exact or miso_batch_compare_exact_paired on sample1
+   discards them.  The launch appears in miso_batch_last_kernels as exact_delta_quantiles or exact_paired_delta_quantiles.
+   miso_batch_get_exact_delta_quantiles: quantiles[k] of p[k], cdf_at_0 = H(0.0) = P(delta <= 0); was_exact = 0 and nothing
+   else for a pair that is not comparable.  miso_batch_exact_delta_ms: kernel time (HIP events) of the last such launch
+   stored in this batch, ms; 0 before. */
+int miso_batch_exact_delta_quantiles(miso_batch_t *sample1, miso_batch_t *sample2, const double *p, int n_p);
+int miso_batch_get_exact_delta_quantiles(const miso_batch_t *sample1, int event_index, double *quantiles /* n_p */,
+                                         double *cdf_at_0, int *was_exact);
+int miso_batch_exact_delta_ms(const miso_batch_t *sample1, float *ms);
 
 /* The posterior of delta = psi_1 - psi_2 over ALL pairs of the two samples' draws (csrc/kernels_compare_pairs.hip, DESIGN.md
    section 19): the samples are independent posteriors, so given the draws the law of delta is the empirical law of the
@@ -667,6 +685,14 @@ int miso_selftest_exact_compare(const double *stats7_1, const double *stats7_2, 
    mode, a probability lies outside [2^-63, 1], n_z is outside [0, 8] or a z outside (-1, 1). */
 int miso_selftest_exact_paired_compare(const double *stats6_1, const double *m_1, const int64_t *offs_1, const double *stats6_2,
                                        const double *m_2, const int64_t *offs_2, int n, const double *z, int n_z, double *out);
+/* kernels_exact_delta.hip on caller-given statistics, one wavefront per pair: the pairs, their eligibility and the e0, e1
+   error as miso_selftest_exact_compare's.  out[(n_p + 1) i ...] = {quantile of psi_1 - psi_2 at p[0 .. n_p), cdf at 0} as
+   miso_batch_get_exact_delta_quantiles returns them.  MISO_EINVAL also when n_p is outside [1, 4] or a p outside (0, 1). */
+int miso_selftest_exact_delta_quantiles(const double *stats7_1, const double *stats7_2, int n, const double *p, int n_p, double *out);
+/* kernels_exact_paired_delta.hip on caller-given elements, one wavefront per pair: the elements and their errors as
+   miso_selftest_exact_paired_compare's, p and out as miso_selftest_exact_delta_quantiles'. */
+int miso_selftest_exact_paired_delta_quantiles(const double *stats6_1, const double *m_1, const int64_t *offs_1, const double *stats6_2,
+                                               const double *m_2, const int64_t *offs_2, int n, const double *p, int n_p, double *out);
 /* csrc/text_digits.hpp text_digits, the rounding of summarize_as_text: out[i] = x[i] x 10^4 rounded to the nearest integer,
    ties to even, on the exact product -- the digits of "%.4f" of x[i], sign included.  Finite |x[i]| < 2^38. */
 int miso_selftest_text_digits(const double *x, int n, int64_t *out);

@@ -436,6 +436,29 @@ class Batch:
         check(lib().miso_batch_get_exact_comparison(self.handle, int(i), *[C.byref(x) for x in v], _p(cdf), C.byref(was)))
         return tuple(x.value for x in v) + (cdf,) if was.value else None
 
+    def exact_delta_quantiles(self, other, probs=(0.5, 0.025, 0.975)):
+        """The quantiles of delta psi = psi_1 - psi_2 at `probs` (at most 4, each inside (0, 1)) from the exact CDF, on the
+        device and without a draw, of the pairs the stored compare_exact() / compare_exact_paired() with `other` found
+        comparable (miso_batch_exact_delta_quantiles in include/miso_amd.h).  The next exact comparison
+        discards them."""
+        pp = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        check(lib().miso_batch_exact_delta_quantiles(self.handle, other.handle, _p(pp), C.c_int(len(pp))))
+        self._exact_np = len(pp)
+
+    def exact_delta(self, i):
+        """(quantiles[n_p], cdf_at_0) of event i after exact_delta_quantiles(): the quantiles of psi_1 - psi_2 and
+        P(psi_1 - psi_2 <= 0); None when the pair is not exact-comparable (miso_batch_get_exact_delta_quantiles)."""
+        q = np.zeros(getattr(self, "_exact_np", 0))
+        h0, was = C.c_double(0.0), C.c_int(0)
+        check(lib().miso_batch_get_exact_delta_quantiles(self.handle, int(i), _p(q), C.byref(h0), C.byref(was)))
+        return (q, h0.value) if was.value else None
+
+    def exact_delta_ms(self):
+        """Kernel time of the last exact_delta_quantiles() stored in this batch (HIP events), ms."""
+        a = C.c_float(0)
+        check(lib().miso_batch_exact_delta_ms(self.handle, C.byref(a)))
+        return float(a.value)
+
     def compare_pairs(self, other, confidence_level=0.95, thresholds=(0.1, 0.2), as_text=False):
         """The posterior of delta psi = psi_1 - psi_2 over ALL pairs of this batch's draws and `other`'s (same events, same
         order; the sample counts may differ, 8192 per event at most) on the device: median, credible interval and exact
@@ -1045,6 +1068,34 @@ def selftest_exact_compare(stats7_1, stats7_2, z=()):
     zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
     out = np.zeros((len(s1), 5 + len(zz)))
     check(lib().miso_selftest_exact_compare(_p(s1), _p(s2), C.c_int(len(s1)), _p(zz), C.c_int(len(zz)), _p(out)))
+    return out
+
+
+def selftest_exact_delta_quantiles(stats7_1, stats7_2, probs=(0.5, 0.025, 0.975)):
+    """csrc/kernels_exact_delta.hip on caller-given statistics: the pairs as selftest_exact_compare's -> out [n, len(probs) + 1]
+    = the quantiles of psi_1 - psi_2 at probs, then P(psi_1 - psi_2 <= 0) -- include/miso_amd.h
+    miso_selftest_exact_delta_quantiles"""
+    s1 = np.ascontiguousarray(stats7_1, dtype=np.float64).reshape(-1, 7)
+    s2 = np.ascontiguousarray(stats7_2, dtype=np.float64).reshape(-1, 7)
+    if len(s1) != len(s2):
+        raise ValueError("stats7_1, stats7_2: one row per pair each")
+    pp = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    out = np.zeros((len(s1), len(pp) + 1))
+    check(lib().miso_selftest_exact_delta_quantiles(_p(s1), _p(s2), C.c_int(len(s1)), _p(pp), C.c_int(len(pp)), _p(out)))
+    return out
+
+
+def selftest_exact_paired_delta_quantiles(stats6_1, pairs_1, stats6_2, pairs_2, probs=(0.5, 0.025, 0.975)):
+    """csrc/kernels_exact_paired_delta.hip on caller-given elements: the pairs as selftest_exact_paired_compare's -> out
+    [n, len(probs) + 1] as selftest_exact_delta_quantiles' -- include/miso_amd.h miso_selftest_exact_paired_delta_quantiles"""
+    s1, m1, o1 = _pair_lists(stats6_1, pairs_1)
+    s2, m2, o2 = _pair_lists(stats6_2, pairs_2)
+    if len(s1) != len(s2):
+        raise ValueError("stats6_1, stats6_2: one row per pair each")
+    pp = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    out = np.zeros((len(s1), len(pp) + 1))
+    check(lib().miso_selftest_exact_paired_delta_quantiles(_p(s1), _p(m1), _p(o1), _p(s2), _p(m2), _p(o2), C.c_int(len(s1)),
+                                                          _p(pp), C.c_int(len(pp)), _p(out)))
     return out
 
 

@@ -90,15 +90,24 @@ def exact_comparison_line(event_name, summary1, summary2, bayes_factors, header1
     if exact is None:
         return "\t".join([comparison_line(event_name, summary1, summary2, bayes_factors, header1, header2), "0", "NA"]
                          + ["NA"] * len(thresholds))
-    mean1, mean2, _, bf, log10_bf, cdf, (m1, lo1, hi1), (m2, lo2, hi2) = exact
+    return "\t".join(exact_head_fields(event_name, header1, header2, exact) + ["1", "%.4f" % exact[4]]
+                     + exact_prob_fields(exact[5], thresholds))
+
+
+def exact_head_fields(event_name, header1, header2, exact):
+    """the HEADER_FIELDS part of an exact-comparable event's row: the summaries from the grid"""
+    mean1, mean2, _, bf, _, _, (m1, lo1, hi1), (m2, lo2, hi2) = exact
     f = [event_name, "%.4f" % m1[0], "%.4f" % lo1[0], "%.4f" % hi1[0], "%.4f" % m2[0], "%.4f" % lo2[0], "%.4f" % hi2[0],
          "%.4f" % (mean1 - mean2), "%.2f" % min(bf, MAX_BF), header1["isoforms"],
          header1["counts"], header1["assigned_counts"], header2["counts"], header2["assigned_counts"]]
     for key in ("chrom", "strand", "mRNA_starts", "mRNA_ends"):
         f.append(header1.get(key, "NA"))
-    f += ["1", "%.4f" % log10_bf]
-    f += ["%.4f" % ((1.0 - cdf[2 * j]) + cdf[2 * j + 1]) for j in range(len(thresholds))]
-    return "\t".join(f)
+    return f
+
+
+def exact_prob_fields(cdf, thresholds):
+    """P(|psi_1 - psi_2| >= t) = 1 - H(t) + H(-t) per threshold, cdf at delta_points(thresholds)"""
+    return ["%.4f" % ((1.0 - cdf[2 * j]) + cdf[2 * j + 1]) for j in range(len(thresholds))]
 
 
 def write_exact_comparison(filename, rows, thresholds):
@@ -155,6 +164,41 @@ def write_dpsi(filename, rows, thresholds):
         f.write("\t".join(dpsi_header_fields(thresholds)) + "\n")
         for row in rows:
             f.write(dpsi_line(comparison_line(*row[:6]), row[6], len(thresholds)) + "\n")
+            n += 1
+    return n
+
+
+# ---- the exact comparison's delta psi table, `<label1>_vs_<label2>.miso_dpsi_exact` ----
+EXACT_DPSI_PROBS = (0.5, 0.025, 0.975)      # median and the 95 % credible interval, as `.miso_dpsi`'s confidence level
+
+
+def exact_dpsi_header_fields(thresholds):
+    return HEADER_FIELDS + ["exact"] + DPSI_FIELDS + ["prob_abs_diff_ge_%g" % t for t in thresholds]
+
+
+def exact_dpsi_line(event_name, summary1, summary2, bayes_factors, header1, header2, exact, delta, thresholds):
+    """exact: as exact_comparison_line's; delta = (quantiles of psi_1 - psi_2 at EXACT_DPSI_PROBS, H(0)) as
+    capi.Batch.exact_delta(i) returns it.  Either None: the event's `.miso_bf` line, then exact = 0 and NA.  Otherwise the
+    `.miso_bf_exact` row's leading fields, 1, median and interval as %.4f, P(diff > 0) = 1 - H(0) and P(diff < 0) = H(0) (the
+    law has no atom at 0), and `.miso_bf_exact`'s P(|psi_1 - psi_2| >= t)."""
+    if exact is None or delta is None:
+        return "\t".join([comparison_line(event_name, summary1, summary2, bayes_factors, header1, header2), "0"]
+                         + ["NA"] * (len(DPSI_FIELDS) + len(thresholds)))
+    q, h0 = delta
+    f = exact_head_fields(event_name, header1, header2, exact) + ["1"]
+    f += ["%.4f" % q[0], "%.4f" % q[1], "%.4f" % q[2], "%.4f" % (1.0 - h0), "%.4f" % h0]
+    return "\t".join(f + exact_prob_fields(exact[5], thresholds))
+
+
+def write_exact_dpsi(filename, rows, thresholds):
+    """rows: iterable of (event_name, summary1, summary2, bayes_factors, header1, header2, exact, delta) --
+    write_exact_comparison's row and the event's exact quantiles of delta psi."""
+    thresholds = check_delta_thresholds(thresholds)
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(exact_dpsi_header_fields(thresholds)) + "\n")
+        for row in rows:
+            f.write(exact_dpsi_line(*row, thresholds=thresholds) + "\n")
             n += 1
     return n
 

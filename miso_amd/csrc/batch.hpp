@@ -81,6 +81,14 @@ struct ExactPairedCmpSide {
 // out: 5 + n_z doubles per pair, as exact_compare_run's
 void exact_paired_compare_run(const ExactPairedCmpInput &in1, const ExactPairedCmpInput &in2, const int32_t *list, int n, const double *z,
                               int n_z, double *out, hipStream_t st = nullptr, float *ms = nullptr);
+// kernels_exact_delta.hip, kernels_exact_paired_delta.hip: the quantiles of psi_1 - psi_2 of such pairs at the probabilities
+// p[0 .. n_p) from the exact CDF (miso_batch_exact_delta_quantiles, miso_selftest_exact_delta_quantiles,
+// miso_selftest_exact_paired_delta_quantiles); pairs and errors as the comparisons' drivers'.  out: n_p + 1 doubles per pair,
+// the quantiles and then P(psi_1 - psi_2 <= 0)
+void exact_delta_run(const double *stats7_1, const double *stats7_2, int n, const double *p, int n_p, double *out,
+                     hipStream_t st = nullptr, float *ms = nullptr);
+void exact_paired_delta_run(const ExactPairedCmpInput &in1, const ExactPairedCmpInput &in2, const int32_t *list, int n, const double *p,
+                            int n_p, double *out, hipStream_t st = nullptr, float *ms = nullptr);
 // kernels_compare_groups.hip
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
@@ -232,6 +240,13 @@ struct miso_batch {
   float compare_ms = 0.f, exact_compare_ms = 0.f;   // kernel time of the last compare / compare_exact or compare_exact_paired
   void compare_exact(miso_batch &other, const double *z, int n_z);
   void compare_exact_paired(miso_batch &other, const double *z, int n_z);   // miso_batch_compare_exact_paired: the same stores
+  // miso_batch_exact_delta_quantiles, of the pairs the stored exact comparison found comparable: per event exact_delta_np + 1
+  // doubles (the quantiles, then the CDF at 0).  The next exact comparison discards them.
+  std::vector<double> h_exact_delta;
+  int exact_delta_np = 0;
+  bool exact_delta_done = false;
+  float exact_delta_ms = 0.f;   // kernel time of the last such launch
+  void exact_delta_quantiles(miso_batch &other, const double *p, int n_p);
   int n_k2 = 0, n_gen = 0;
   int n_k2w = 0;                  // paired-end: the first n_k2w two-isoform slots take sampler_k2's MODE 2
   // A half of the two-isoform list: k2[0] the paired-end MODE 2 events (no drawing read on a non-finite score), k2[1] the

@@ -920,6 +920,35 @@ int miso_batch_get_exact_comparison(const miso_batch_t *b, int i, double *mean1,
   });
 }
 
+int miso_batch_exact_delta_quantiles(miso_batch_t *a, miso_batch_t *b, const double *p, int n_p) {
+  return guarded([&] {
+    need(a, "batch"); need(b, "batch");
+    if (n_p > 0) need(p, "p");
+    a->exact_delta_quantiles(*b, p, n_p);
+  });
+}
+
+int miso_batch_get_exact_delta_quantiles(const miso_batch_t *b, int i, double *quantiles, double *cdf_at_0, int *was_exact) {
+  return guarded([&] {
+    need(b, "batch"); need(was_exact, "was_exact");
+    (void) event_at(b, i);
+    if (!b->exact_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_exact / miso_batch_compare_exact_paired has not run");
+    if (!b->exact_delta_done) MISO_FAIL(MISO_EINVAL, "miso_batch_exact_delta_quantiles has not run");
+    *was_exact = b->exact_cmp_ok[i] ? 1 : 0;
+    if (!*was_exact) return;
+    const double *r = &b->h_exact_delta[static_cast<size_t>(i) * (b->exact_delta_np + 1)];
+    if (quantiles) for (int k = 0; k < b->exact_delta_np; k++) quantiles[k] = r[k];
+    if (cdf_at_0) *cdf_at_0 = r[b->exact_delta_np];
+  });
+}
+
+int miso_batch_exact_delta_ms(const miso_batch_t *b, float *ms) {
+  return guarded([&] {
+    need(b, "batch"); need(ms, "ms");
+    *ms = b->exact_delta_ms;
+  });
+}
+
 int miso_batch_compare_ms(const miso_batch_t *b, float *compare_ms, float *exact_compare_ms) {
   return guarded([&] {
     need(b, "batch");
@@ -1273,6 +1302,27 @@ int miso_selftest_exact_paired_compare(const double *stats6_1, const double *m_1
     const ExactPairedCmpInput in1{stats6_1, m_1 ? m_1 : none, offs_1, nullptr, nullptr, nullptr, 0};
     const ExactPairedCmpInput in2{stats6_2, m_2 ? m_2 : none, offs_2, nullptr, nullptr, nullptr, 0};
     exact_paired_compare_run(in1, in2, nullptr, n, z, n_z, out);
+  });
+}
+int miso_selftest_exact_delta_quantiles(const double *stats7_1, const double *stats7_2, int n, const double *p, int n_p, double *out) {
+  return guarded([&] {
+    if (n > 0) { need(stats7_1, "stats7_1"); need(stats7_2, "stats7_2"); need(out, "out"); }
+    if (n_p > 0) need(p, "p");
+    exact_delta_run(stats7_1, stats7_2, n, p, n_p, out);
+  });
+}
+int miso_selftest_exact_paired_delta_quantiles(const double *stats6_1, const double *m_1, const int64_t *offs_1, const double *stats6_2,
+                                               const double *m_2, const int64_t *offs_2, int n, const double *p, int n_p, double *out) {
+  return guarded([&] {
+    if (n > 0) { need(stats6_1, "stats6_1"); need(stats6_2, "stats6_2"); need(offs_1, "offs_1"); need(offs_2, "offs_2"); need(out, "out"); }
+    if (n > 0 && offs_1[0] == 0 && offs_1[n] > 0) need(m_1, "m_1");
+    if (n > 0 && offs_2[0] == 0 && offs_2[n] > 0) need(m_2, "m_2");
+    if (n_p > 0) need(p, "p");
+    // (an element without a pair still takes the caller-given route: a placeholder stands for the empty list)
+    static const double none[2] = {1.0, 1.0};
+    const ExactPairedCmpInput in1{stats6_1, m_1 ? m_1 : none, offs_1, nullptr, nullptr, nullptr, 0};
+    const ExactPairedCmpInput in2{stats6_2, m_2 ? m_2 : none, offs_2, nullptr, nullptr, nullptr, 0};
+    exact_paired_delta_run(in1, in2, nullptr, n, p, n_p, out);
   });
 }
 int miso_selftest_exact_paired(const double *stats6, const double *m, const int64_t *offs, int n, const double *prob, int n_prob,

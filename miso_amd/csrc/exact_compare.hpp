@@ -4,7 +4,8 @@
 // of delta psi at 0, Bayes factor) and the end of one delta psi quadrature.  Host part: the prior term and the check of the
 // delta psi points.  The quadrature loops themselves differ and stay in their units.  -ffp-contract=off; every operation in
 // a fixed order: tests/_exact_compare_ref.py restates these functions, tests/_exact_paired_compare_ref.py imports them from
-// there.
+// there.  exact_delta.hpp (the quantiles of delta psi) builds its sweeps on exact_cdf_at and on exact_lanes_sum's
+// order.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -24,8 +24,9 @@
 // WHERE THE PIECES LIVE.  B's CDF at an argument, the lane-order sum, the verdict o[0 .. 4], the end of a quadrature, the
 // host's prior term and check of z: exact_compare.hpp, shared with kernels_exact_compare.hip.  Windows, tables, the LDS
 // layout, c8 and the loader of an element: exact_paired.hpp.  The check of caller-given elements: kernels_exact_paired.hip
-// (exact_paired_check).  The driver's stream, buffers and events: hip_host.hpp.  Here: exact_uni, the pooled density's
-// statistics, the order of the tables, the quadrature loop (one z at a time, A's f read from its global row) and the driver.
+// (exact_paired_check).  The driver's stream, buffers and events: hip_host.hpp.  exact_uni, a pair's side and the rows' sizes:
+// exact_paired_pair.hpp, shared with kernels_exact_paired_delta.hip.  Here: the pooled density's statistics, the order of the
+// tables, the quadrature loop (one z at a time, A's f read from its global row) and the driver.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,36 +40,10 @@
 
 #include "exact_compare.hpp"
 #include "exact_paired.hpp"
+#include "exact_paired_pair.hpp"
 #include "hip_host.hpp"
 
 namespace miso {
-
-constexpr int EXPC_ROW = EXACT_G + 64;      // doubles of a workgroup's row of A's f: 64 j + l, the grid's last point at 2048; 512-byte rows
-constexpr int EXPC_LAUNCH = 8192;           // pairs per launch: bounds the rows' buffer (138 MB)
-
-// A value every lane holds alike, moved to scalar registers (the same bits).  The statistics, windows and table scalars of
-// three densities live across five sweeps over the pairs; as vector registers they would not fit beside a sweep's points.
-__device__ __forceinline__ double exact_uni(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ ExactStats exact_uni(const ExactStats &s) {
-  return ExactStats{exact_uni(s.am1), exact_uni(s.bm1), exact_uni(s.a), exact_uni(s.b), exact_uni(s.c), exact_uni(s.n), exact_uni(s.e0), exact_uni(s.e1)};
-}
-__device__ __forceinline__ ExactTable exact_uni(const ExactTable &T) {
-  return ExactTable{exact_uni(T.tm), exact_uni(T.gmax), exact_uni(T.tL), exact_uni(T.tR), exact_uni(T.h), exact_uni(T.Z), exact_uni(T.mean0),
-                    exact_uni(T.mean1), exact_uni(T.sf), T.F, T.f};
-}
-
-struct ExactUni {
-  template <class T> __device__ __forceinline__ T operator()(const T &v) const { return exact_uni(v); }
-};
-
-// pair i of one sample: its statistics and c8, in scalar registers, and its drawing pairs
-__device__ __forceinline__ void exact_paired_cmp_side(const ExactPairedCmpSide &sd, const int32_t *list, int i, ExactStats &st, double &c8,
-                                                      ExactPairs &pr) {
-  exact_paired_element(sd.stats6, sd.mm, sd.offs, sd.in_pool, sd.events, list, sd.frag_prob, sd.il, i, st, c8, pr, ExactUni());
-}
 
 // One workgroup = one wavefront = pair first + blockIdx.x.  out: 5 + n_z doubles per pair; frow: EXPC_ROW doubles per
 // workgroup of the launch (unused, and may be null, when n_z = 0).
@@ -152,17 +127,7 @@ void exact_paired_compare_run(const ExactPairedCmpInput &in1, const ExactPairedC
   if (n == 0) return;
   HipCall call(st);
   ExactPairedCmpSide side[2];
-  for (int s = 0; s < 2; s++) {
-    const ExactPairedCmpInput &I = *in[s];
-    side[s] = ExactPairedCmpSide{};
-    side[s].stats6 = call.upload(I.stats6, static_cast<size_t>(n) * 6 * 8);
-    if (I.m) {
-      side[s].mm = call.upload(I.m, static_cast<size_t>(n_pairs[s]) * 2 * 8);
-      side[s].offs = call.upload(I.offs, static_cast<size_t>(n + 1) * 8);
-    } else {
-      side[s].events = I.events; side[s].in_pool = I.in_pool; side[s].frag_prob = I.frag_prob; side[s].il = I.il;
-    }
-  }
+  for (int s = 0; s < 2; s++) side[s] = exact_paired_cmp_upload(call, *in[s], n, n_pairs[s]);
   const int32_t *d_list = (in1.m && in2.m) ? nullptr : call.upload(list, static_cast<size_t>(n) * 4);
   const double *d_lp = call.upload(lp.data(), static_cast<size_t>(n) * 8), *d_z = call.upload(z, static_cast<size_t>(n_z) * 8);
   const size_t ob = static_cast<size_t>(n) * (5 + n_z) * 8;

@@ -21,6 +21,7 @@
 #include "compare_pairs.hpp"
 #include "coop.hpp"
 #include "exact_compare.hpp"
+#include "exact_delta.hpp"
 #include "hip_host.hpp"
 
 namespace miso {
@@ -1635,6 +1636,38 @@ void miso_batch::compare_pairs(miso_batch &other, double confidence_level, const
   pairs_compared = true;
 }
 
+// The two kinds of exact pair, as the comparison and the quantiles of delta psi take them: whether both batches ran the
+// kind's mode, and an event's row of statistics in the kind's selftest layout.
+static bool exact_single_ok(const miso_batch &a, const miso_batch &b) {
+  return a.exact && b.exact && a.slots_exact == a.exact && b.slots_exact == b.exact;
+}
+static bool exact_paired_ok(const miso_batch &a, const miso_batch &b) {
+  return a.p.paired && b.p.paired && a.exact_paired && b.exact_paired && a.slots_exact == a.exact_paired && b.slots_exact == b.exact_paired;
+}
+static const char *const EXACT_SINGLE_MSG = "Both batches to compare exactly must have run with the exact-posterior mode";
+static const char *const EXACT_PAIRED_MSG = "Both batches to compare exactly must be paired-end and have run with the paired exact-posterior mode";
+static void exact_paired_stats6(const miso_batch &b, int i, double *row) {
+  const PackedEvent &e = b.events[i];
+  const double r[6] = {static_cast<double>(e.base_count[0]), static_cast<double>(e.base_count[1]), e.eff[0], e.eff[1], e.hyper[0], e.hyper[1]};
+  std::memcpy(row, r, sizeof r);
+}
+static ExactPairedCmpInput exact_paired_resident(const miso_batch &b, const double *stats6) {
+  return ExactPairedCmpInput{stats6, nullptr, nullptr, b.d_events, b.d_in, b.d_fp, static_cast<int>(b.fd.prob.size())};
+}
+
+// the guards of every exact pass over the pairs of batch a (sample 1) and batch b (sample 2)
+static void exact_pair_guards(const miso_batch &a, const miso_batch &b, bool mode_ok, const char *mode_msg) {
+  if (!a.launched || !b.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (a.device != b.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
+  if (a.events.size() != b.events.size() || a.S() != b.S())
+    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
+  if (!mode_ok) MISO_FAIL(MISO_EINVAL, mode_msg);
+}
+static void exact_pair_same_isoforms(const miso_batch &a, const miso_batch &b) {
+  for (size_t i = 0; i < a.events.size(); i++)
+    if (a.events[i].K != b.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+}
+
 // What the two exact comparisons of batch a (sample 1) with batch b (sample 2) share: the guards, the list of the events both
 // batches' exact mode took and that are `comparable`, their rows of `row_w` statistics from `gather`, the call of `run` (which
 // validates z, and fails with MISO_ENODEVICE without a device, also when no event is comparable), and the scatter of its rows
@@ -1642,18 +1675,14 @@ void miso_batch::compare_pairs(miso_batch &other, double confidence_level, const
 template <class Comparable, class Gather, class Run>
 static void compare_exact_with(miso_batch &a, miso_batch &b, const double *z, int n_z, bool mode_ok, const char *mode_msg, int row_w,
                                Comparable comparable, Gather gather, Run run, const char *kernel) {
-  if (!a.launched || !b.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (a.device != b.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
-  if (a.events.size() != b.events.size() || a.S() != b.S())
-    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
-  if (!mode_ok) MISO_FAIL(MISO_EINVAL, mode_msg);
+  exact_pair_guards(a, b, mode_ok, mode_msg);
   exact_check_z(z, n_z);
   const int n = static_cast<int>(a.events.size());
-  for (int i = 0; i < n; i++)
-    if (a.events[i].K != b.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+  exact_pair_same_isoforms(a, b);
   std::vector<int32_t> list;
   std::vector<double> s1, s2;
   a.exact_cmp_ok.assign(n, 0);
+  a.exact_delta_done = false;   // (the quantiles of delta psi belong to the comparison this one replaces)
   for (int i = 0; i < n; i++) {
     if (!a.event_exact(i) || !b.event_exact(i) || !comparable(i)) continue;
     list.push_back(i);
@@ -1679,8 +1708,7 @@ static void compare_exact_with(miso_batch &a, miso_batch &b, const double *z, in
 // bit-equal effective lengths, go to exact_compare (kernels_exact_compare.hip).
 void miso_batch::compare_exact(miso_batch &other, const double *z, int n_z) {
   compare_exact_with(
-      *this, other, z, n_z, exact && other.exact && slots_exact == exact && other.slots_exact == other.exact,
-      "Both batches to compare exactly must have run with the exact-posterior mode", 7,
+      *this, other, z, n_z, exact_single_ok(*this, other), EXACT_SINGLE_MSG, 7,
       [&](int i) { return std::memcmp(events[i].eff.data(), other.events[i].eff.data(), 2 * sizeof(double)) == 0; },
       [](const miso_batch &b, int i, double *row) { b.exact_stats7(i, row); },
       [&](const double *s1, const double *s2, const std::vector<int32_t> &list, double *got) {
@@ -1694,21 +1722,57 @@ void miso_batch::compare_exact(miso_batch &other, const double *z, int n_z) {
 // take compare_exact's place (h_exact_cmp, read by the same getter).
 void miso_batch::compare_exact_paired(miso_batch &other, const double *z, int n_z) {
   compare_exact_with(
-      *this, other, z, n_z,
-      p.paired && other.p.paired && exact_paired && other.exact_paired && slots_exact == exact_paired && other.slots_exact == other.exact_paired,
-      "Both batches to compare exactly must be paired-end and have run with the paired exact-posterior mode", 6,
+      *this, other, z, n_z, exact_paired_ok(*this, other), EXACT_PAIRED_MSG, 6,
       [](int) { return true; },
-      [](const miso_batch &b, int i, double *row) {
-        const PackedEvent &e = b.events[i];
-        const double r[6] = {static_cast<double>(e.base_count[0]), static_cast<double>(e.base_count[1]), e.eff[0], e.eff[1], e.hyper[0], e.hyper[1]};
-        std::memcpy(row, r, sizeof r);
-      },
+      exact_paired_stats6,
       [&](const double *s1, const double *s2, const std::vector<int32_t> &list, double *got) {
-        const ExactPairedCmpInput in1{s1, nullptr, nullptr, d_events, d_in, d_fp, static_cast<int>(fd.prob.size())};
-        const ExactPairedCmpInput in2{s2, nullptr, nullptr, other.d_events, other.d_in, other.d_fp, static_cast<int>(other.fd.prob.size())};
-        exact_paired_compare_run(in1, in2, list.data(), static_cast<int>(list.size()), z, n_z, got, stream, &exact_compare_ms);
+        exact_paired_compare_run(exact_paired_resident(*this, s1), exact_paired_resident(other, s2), list.data(),
+                                 static_cast<int>(list.size()), z, n_z, got, stream, &exact_compare_ms);
       },
       "exact_paired_compare");
+}
+
+// The quantiles of delta psi = psi_1 - psi_2 at prob[0 .. n_p) of exactly the pairs the stored exact comparison of this batch
+// (sample 1) found comparable, `other` being sample 2 again: exact_delta_quantiles (kernels_exact_delta.hip) for single-end
+// batches, exact_paired_delta_quantiles (kernels_exact_paired_delta.hip) for paired-end ones.  The results are made beside
+// the stored ones and take their place at the end: a call that fails leaves what was there.
+void miso_batch::exact_delta_quantiles(miso_batch &other, const double *prob, int n_p) {
+  const bool paired = p.paired;
+  if (paired) exact_pair_guards(*this, other, exact_paired_ok(*this, other), EXACT_PAIRED_MSG);
+  else exact_pair_guards(*this, other, exact_single_ok(*this, other), EXACT_SINGLE_MSG);
+  if (!exact_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_exact / miso_batch_compare_exact_paired has not run");
+  exact_delta_check_p(prob, n_p);
+  exact_pair_same_isoforms(*this, other);
+  const int n = static_cast<int>(events.size()), row_w = paired ? 6 : 7;
+  std::vector<int32_t> list;
+  std::vector<double> s1, s2;
+  for (int i = 0; i < n; i++) {
+    if (!exact_cmp_ok[i]) continue;
+    if (!other.event_exact(i)) MISO_FAIL(MISO_EINVAL, "The second batch is not the one the stored exact comparison was made with");
+    list.push_back(i);
+    s1.resize(s1.size() + row_w); s2.resize(s2.size() + row_w);
+    double *r1 = &s1[s1.size() - row_w], *r2 = &s2[s2.size() - row_w];
+    if (paired) { exact_paired_stats6(*this, i, r1); exact_paired_stats6(other, i, r2); }
+    else { exact_stats7(i, r1); other.exact_stats7(i, r2); }
+  }
+  const size_t w = static_cast<size_t>(n_p) + 1;
+  const int m = static_cast<int>(list.size());
+  std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
+  HIP_OK(hipSetDevice(device));
+  HIP_OK(hipStreamSynchronize(other.stream));
+  float ms = 0.f;
+  if (paired)
+    exact_paired_delta_run(exact_paired_resident(*this, s1.data()), exact_paired_resident(other, s2.data()), list.data(), m, prob, n_p,
+                           got.data(), stream, &ms);
+  else
+    exact_delta_run(s1.data(), s2.data(), m, prob, n_p, got.data(), stream, &ms);
+  std::vector<double> res(static_cast<size_t>(n) * w, 0.0);
+  for (size_t j = 0; j < list.size(); j++) std::memcpy(&res[list[j] * w], &got[j * w], w * sizeof(double));
+  h_exact_delta.swap(res);
+  exact_delta_np = n_p;
+  exact_delta_ms = ms;
+  if (!list.empty()) note_kernel(paired ? "exact_paired_delta_quantiles" : "exact_delta_quantiles");
+  exact_delta_done = true;
 }
 
 // A batch that holds posterior samples produced elsewhere -- parsed `.miso` files (summarize_miso / compare_miso

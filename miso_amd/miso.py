@@ -134,8 +134,10 @@ class GenesDispatcher(object):
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                  exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                 delta_posterior=False):
+                 delta_posterior=False, exact_delta_posterior=False):
         self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
+        # --exact-delta-posterior: beside the `.miso_bf_exact` table the `.miso_dpsi_exact` (compare.py), merged like it
+        self.exact_delta_posterior = bool(exact_delta_posterior)
         # --delta-posterior: beside the `.miso_bf` table the all-pairs `.miso_dpsi` (compare.py), merged like a diagnostics
         # table, with the same delta_thresholds
         self.delta_posterior = bool(delta_posterior)
@@ -281,6 +283,7 @@ class GenesDispatcher(object):
         self.diag_tables = []
         xtable = []                    # --exact-compare: [(table, its per-worker parts)], merged with the diagnostics tables
         dtable = []                    # --delta-posterior: likewise
+        etable = []                    # --exact-delta-posterior: likewise
         if self.diagnostics:
             # one table per directory of `.miso` files: the output directory, or with --compare each label's
             for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
@@ -302,6 +305,11 @@ class GenesDispatcher(object):
                         xtable.append((table + "_exact", []))
                     xtable[0][1].append("%s.gpu%d" % (xtable[0][0], batch_num))
                     cmd += ["--exact-comparison-file", xtable[0][1][-1]]
+                    if self.exact_delta_posterior:
+                        if not etable:
+                            etable.append((table[:-len(".miso_bf")] + ".miso_dpsi_exact", []))
+                        etable[0][1].append("%s.gpu%d" % (etable[0][0], batch_num))
+                        cmd += ["--exact-delta-file", etable[0][1][-1]]
                 if self.delta_posterior:
                     if not dtable:
                         dtable.append((table[:-len(".miso_bf")] + ".miso_dpsi", []))
@@ -346,7 +354,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
-        self.diag_tables += xtable + dtable
+        self.diag_tables += xtable + dtable + etable
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -419,7 +427,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                           exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                          delta_posterior=False):
+                          delta_posterior=False, exact_delta_posterior=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -433,7 +441,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
                            delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
-                           delta_posterior=delta_posterior).run()
+                           delta_posterior=delta_posterior, exact_delta_posterior=exact_delta_posterior).run()
 
 
 def main(argv=None):
@@ -489,6 +497,11 @@ def main(argv=None):
                          "OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_dpsi -- median and 95 %% credible interval of delta Psi, "
                          "P(delta Psi > 0), P(delta Psi < 0) and P(|delta Psi| >= T) over ALL pairs of the two samples' draws, "
                          "computed on the GPU during the run; every other output is unchanged")
+    ap.add_argument("--exact-delta-posterior", action="store_true",
+                    help="with --exact-compare or --exact-paired-compare: also write "
+                         "OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_dpsi_exact -- median and 95 %% credible interval of delta "
+                         "Psi, P(delta Psi > 0), P(delta Psi < 0) and P(|delta Psi| >= T) from the exact CDF of delta Psi, without "
+                         "sampling error and whatever the seed; every other output is unchanged")
     ap.add_argument("--compare", metavar="BAM2", default=None,
                     help="second RNA-seq sample: sample both, write OUT/<label1>/, OUT/<label2>/ and the "
                          "compare_miso table OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf")
@@ -525,6 +538,8 @@ def main(argv=None):
                      "in the settings)")
     if a.delta_posterior and a.compare is None:
         ap.error("--delta-posterior goes with --compare")
+    if a.exact_delta_posterior and not (a.exact_compare or a.exact_paired_compare):
+        ap.error("--exact-delta-posterior goes with --exact-compare or --exact-paired-compare")
     if a.delta_psi_thresholds is not None:
         if not (a.exact_compare or a.exact_paired_compare or a.delta_posterior):
             ap.error("--delta-psi-thresholds goes with --exact-compare or --delta-posterior")
@@ -556,7 +571,7 @@ def main(argv=None):
                                        exact=a.exact, exact_compare=a.exact_compare or a.exact_paired_compare,
                                        exact_paired=a.exact_paired,
                                        delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics,
-                                       delta_posterior=a.delta_posterior)
+                                       delta_posterior=a.delta_posterior, exact_delta_posterior=a.exact_delta_posterior)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

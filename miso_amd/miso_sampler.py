@@ -440,7 +440,7 @@ class MISOSampler:
                              burn_in=1000, lag=2, seed=None, seed2=None, first_event_id=0,
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
                              diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None,
-                             rank_diagnostics=False, delta_posterior_file=None):
+                             rank_diagnostics=False, delta_posterior_file=None, exact_delta_file=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -457,7 +457,12 @@ class MISOSampler:
         paired-end sampler with the paired exact mode compares through MISOCompareBatch(exact_paired_compare=).
         delta_posterior_file (optional; any mode): the `.miso_dpsi` table (compare.write_dpsi) of delta psi over all pairs
         of the two samples' draws -- median, the confidence_level interval, P(delta > 0), P(delta < 0) and
-        P(|delta psi| >= t) for every t of delta_thresholds."""
+        P(|delta psi| >= t) for every t of delta_thresholds.
+        exact_delta_file (optional; with exact_comparison_file only): the `.miso_dpsi_exact` table (compare.write_exact_dpsi)
+        -- median and 95 % credible interval of delta psi, P(delta > 0), P(delta < 0) from the exact CDF
+        (MISOCompareBatch(exact_delta=)) and the exact comparison's P(|delta psi| >= t)."""
+        if exact_delta_file is not None and exact_comparison_file is None:
+            raise ValueError("the exact delta psi table goes with the exact comparison")
         dthr = None
         if delta_posterior_file is not None:
             dthr = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
@@ -471,6 +476,7 @@ class MISOSampler:
                 raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
             xthr = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
         xrows = []
+        erows = []
         if len(events1) != len(events2):
             raise ValueError("the two samples must list the same events")
         keep = []
@@ -500,6 +506,8 @@ class MISOSampler:
                 kw["exact_paired"] = True   # ... and the paired-end one
             if xthr is not None:
                 kw["exact_paired_compare" if self.paired_end else "exact_compare"] = compare.delta_points(xthr)
+            if exact_delta_file is not None:
+                kw["exact_delta"] = compare.EXACT_DPSI_PROBS
             if dthr is not None:
                 kw["delta_posterior"] = (float(confidence_level), tuple(dthr))
             res = pysplicing.MISOCompareBatch(
@@ -507,6 +515,10 @@ class MISOSampler:
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),
                 int(self.params["overhang_len"]), int(num_chains), **kw)
             r1, r2, cmp = res[:3]
+            # the optional elements behind them, in this order: diagnostics, exact comparison, exact delta psi, all pairs
+            at = 3 + (diagnostics_files is not None)
+            xres = res[at] if xthr is not None else None
+            eres = res[at + 1] if exact_delta_file is not None else None
             n_samples = int(num_chains) * (int(num_iters) - int(burn_in)) // int(lag)
             if diagnostics_files is not None and rank_diagnostics:
                 for which, refused in enumerate(res[3][2]):
@@ -528,7 +540,9 @@ class MISOSampler:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
                     if xthr is not None:
-                        xrows.append(rows[-1] + (res[-2 if dthr is not None else -1][j],))
+                        xrows.append(rows[-1] + (xres[j],))
+                    if eres is not None:
+                        erows.append(xrows[-1] + (eres[j],))
                     if dthr is not None:
                         drows.append(rows[-1] + (res[-1][j],))
         compare.write_comparison(comparison_file, rows)
@@ -536,6 +550,8 @@ class MISOSampler:
             compare.write_dpsi(delta_posterior_file, drows, dthr)
         if xthr is not None:
             compare.write_exact_comparison(exact_comparison_file, xrows, xthr)
+        if exact_delta_file is not None:
+            compare.write_exact_dpsi(exact_delta_file, erows, xthr)
         if diagnostics_files is not None:
             for f, drows in zip(diagnostics_files, diag_rows):
                 diagnostics.write_diagnostics(f, drows, rank=rank_diagnostics)

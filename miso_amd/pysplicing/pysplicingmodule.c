@@ -38,7 +38,10 @@
  *                   delta psi points, appended as the LAST element of the result.
  *   delta_posterior=(level, (tau, ...))  MISOCompareBatch, any mode: delta psi over all pairs of the two samples' draws
  *                   as their `.miso` files print them (miso_batch_compare_pairs_as_text), appended as the LAST element of the
- *                   result, behind exact_compare's.
+ *                   result, behind exact_compare's and exact_delta's.
+ *   exact_delta=(p, ...)  MISOCompareBatch with exact_compare= or exact_paired_compare=: the quantiles of psi_1 - psi_2 at
+ *                   these probabilities (1 to 4) from the exact CDF (miso_batch_exact_delta_quantiles), one more element of the
+ *                   result, behind exact_compare's: per event None or ((quantile, ...), P(psi_1 - psi_2 <= 0)).
  * The functions of the module that are not on the sampler path raise NotImplementedError.
  * The reference's stdout side effect `printf("no chains: %d\n")` (miso.c:837) is not reproduced.
  */
@@ -490,13 +493,15 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
                            "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired",
-                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", NULL};
+                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", "exact_delta", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *dpobj = NULL, *dp = NULL;   /* delta_posterior=(level, (tau, ...)): the all-pairs pass, miso_batch_compare_pairs */
   double dp_level = 0.95, dp_tau[4]; int n_dp = 0;
   PyObject *r1 = NULL, *r2 = NULL, *cmp = NULL, *out = NULL, *dg = NULL, *xcobj = NULL, *xc = NULL;
   PyObject *xpobj = NULL;   /* exact_paired_compare=(z, ...): the same through miso_batch_compare_exact_paired */
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
+  PyObject *edobj = NULL, *ed = NULL;   /* exact_delta=(p, ...): the quantiles of delta psi from the exact CDF, miso_batch_exact_delta_quantiles */
+  double ep[4]; int n_ep = 0;
   int rank_diagnostics = 0;         /* with diagnostics=True: the rank-normalised pass too (diagnostics_list) */
   int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
   int exact_paired = 0;             /* exact_paired=True (with paired=): miso_batch_set_exact_paired */
@@ -505,10 +510,10 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpO", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpOO", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
                                    &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
-                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj)) return NULL;
+                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj, &edobj)) return NULL;
   if (dpobj == Py_None) dpobj = NULL;
   if (dpobj) {
     PyObject *taus = NULL; Py_ssize_t nt;
@@ -539,6 +544,18 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     }
     for (n_xz = 0; n_xz < (int) nz; n_xz++) {
       xz[n_xz] = PyFloat_AsDouble(PyTuple_GET_ITEM(xcobj, n_xz));
+      if (PyErr_Occurred()) return NULL;
+    }
+  }
+  if (edobj == Py_None) edobj = NULL;
+  if (edobj) {
+    Py_ssize_t np;
+    if (!xcobj) { PyErr_SetString(PyExc_ValueError, "exact_delta requires exact_compare or exact_paired_compare"); return NULL; }
+    if (!PyTuple_Check(edobj) || (np = PyTuple_Size(edobj)) < 1 || np > 4) {
+      PyErr_SetString(PyExc_ValueError, "exact_delta must be a tuple of 1 to 4 probabilities"); return NULL;
+    }
+    for (n_ep = 0; n_ep < (int) np; n_ep++) {
+      ep[n_ep] = PyFloat_AsDouble(PyTuple_GET_ITEM(edobj, n_ep));
       if (PyErr_Occurred()) return NULL;
     }
   }
@@ -628,7 +645,26 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     all = one ? PySequence_Concat(out, one) : NULL;
     Py_XDECREF(one); Py_DECREF(out); out = all;
   }
-  /* delta_posterior=(level, (tau, ...)): a last element (behind exact_compare's), per event (median, ci_low, ci_high, n_gt0,
+  /* exact_delta=(p, ...): a last element (behind exact_compare's), per event None (not exact-comparable) or ((the quantile
+     of psi_1 - psi_2 at every p), P(psi_1 - psi_2 <= 0)) */
+  if (out && edobj) {
+    PyObject *one, *all;
+    if (n > 0 && (rc = miso_batch_exact_delta_quantiles(b1, b2, ep, n_ep))) { raise_miso(rc); Py_CLEAR(out); goto done; }
+    if (!(ed = PyList_New(n))) { Py_CLEAR(out); goto done; }
+    for (i = 0; i < n; i++) {
+      double q[4], h0 = 0.0; int was = 0;
+      PyObject *t;
+      if ((rc = miso_batch_get_exact_delta_quantiles(b1, (int) i, q, &h0, &was))) { raise_miso(rc); Py_CLEAR(out); goto done; }
+      if (!was) { Py_INCREF(Py_None); PyList_SET_ITEM(ed, i, Py_None); continue; }
+      t = Py_BuildValue("(Nd)", from_doubles(q, n_ep), h0);
+      if (!t) { Py_CLEAR(out); goto done; }
+      PyList_SET_ITEM(ed, i, t);
+    }
+    one = PyTuple_Pack(1, ed);
+    all = one ? PySequence_Concat(out, one) : NULL;
+    Py_XDECREF(one); Py_DECREF(out); out = all;
+  }
+  /* delta_posterior=(level, (tau, ...)): a last element (behind exact_compare's and exact_delta's), per event (median, ci_low, ci_high, n_gt0,
      n_lt0, n_abs_ge -- per isoform a tuple over the thresholds --, finite, n_pairs) of the S1 * S2 differences */
   if (out && dpobj) {
     PyObject *one, *all;
@@ -661,7 +697,7 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     Py_XDECREF(one); Py_DECREF(out); out = all;
   }
 done:
-  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc); Py_XDECREF(dp);
+  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc); Py_XDECREF(ed); Py_XDECREF(dp);
   if (b1) miso_batch_destroy(b1);
   if (b2) miso_batch_destroy(b2);
   return out;

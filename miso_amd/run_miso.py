@@ -325,7 +325,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
                      exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False,
-                     delta_posterior_file=None):
+                     delta_posterior_file=None, exact_delta_file=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -338,7 +338,11 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     exact_comparison_file (the exact mode only): the `.miso_bf_exact` table of the exact comparison (compare.py
     write_exact_comparison), parts merged like the comparison's; delta_thresholds: its thresholds t of P(|delta psi| >= t).
     delta_posterior_file (any mode): the `.miso_dpsi` table of delta psi over all pairs of the two samples' draws (compare.py
-    write_dpsi), parts merged like the comparison's, with the same delta_thresholds."""
+    write_dpsi), parts merged like the comparison's, with the same delta_thresholds.
+    exact_delta_file (with exact_comparison_file only): the `.miso_dpsi_exact` table of delta psi's median and credible
+    interval from the exact CDF (compare.py write_exact_dpsi), parts merged like the exact comparison's."""
+    if exact_delta_file is not None and exact_comparison_file is None:
+        raise ValueError("the exact delta psi table goes with the exact comparison")
     for d in (output_dir1, output_dir2):
         os.makedirs(d, exist_ok=True)
     if device is not None:
@@ -365,6 +369,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     pairs = [(a, by_no2[a[4]]) for a in ev1 if a[4] in by_no2]
     parts = []
     xparts = []
+    eparts = []
     dpsi_parts = []
     diag_parts = ([], [])
     if paired_end:
@@ -393,6 +398,10 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         if exact_comparison_file is not None:
             xpart = "%s.part%06d" % (exact_comparison_file, lo)
             xparts.append(xpart)
+        epart = None
+        if exact_delta_file is not None:
+            epart = "%s.part%06d" % (exact_delta_file, lo)
+            eparts.append(epart)
         dpsi_part = None
         if delta_posterior_file is not None:
             dpsi_part = "%s.part%06d" % (delta_posterior_file, lo)
@@ -404,12 +413,14 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                      event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
                                      diagnostics_files=dparts, exact_comparison_file=xpart,
                                      delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
-                                     delta_posterior_file=dpsi_part)
+                                     delta_posterior_file=dpsi_part, exact_delta_file=epart)
     merge_tables(parts, comparison_file)
     if delta_posterior_file is not None:
         merge_tables(dpsi_parts, delta_posterior_file)
     if exact_comparison_file is not None:
         merge_tables(xparts, exact_comparison_file)
+    if exact_delta_file is not None:
+        merge_tables(eparts, exact_delta_file)
     if samples is not None:
         # sample 2's stream: the seed MISOCompareBatch derives for it (pysplicingmodule.c)
         seed2 = None if seed is None else (int(seed) ^ 0x5851F42D4C957F2D) & 0xFFFFFFFFFFFFFFFF
@@ -495,6 +506,9 @@ def main(argv=None):
     ap.add_argument("--exact-comparison-file", default=None, metavar="F",
                     help="with --compare-genes-from-file and the exact mode: also write the exact comparison's table "
                          "(Bayes factors and P(|delta psi| >= T) from the posteriors' tables, no sampling error)")
+    ap.add_argument("--exact-delta-file", default=None, metavar="F",
+                    help="with --exact-comparison-file: also write the table of delta psi's median and 95 %% credible interval, "
+                         "P(delta psi > 0) and P(|delta psi| >= T) from the exact CDF of delta psi (no sampling error)")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
                     help="the thresholds T of --exact-comparison-file and --delta-posterior-file, each in (0, 1), at most four "
                          "(default 0.1 0.2)")
@@ -538,6 +552,9 @@ def main(argv=None):
         elif not a.compare_genes_from_file or paired_end or not exact:
             print("Error: --exact-comparison-file goes with --compare-genes-from-file and the exact mode (single-end).")
             return 1
+    if a.exact_delta_file is not None and a.exact_comparison_file is None:
+        print("Error: --exact-delta-file goes with --exact-comparison-file.")
+        return 1
     if a.delta_posterior_file is not None and not a.compare_genes_from_file:
         print("Error: --delta-posterior-file goes with --compare-genes-from-file.")
         return 1
@@ -560,7 +577,9 @@ def main(argv=None):
                              delta_thresholds=a.delta_psi_thresholds, exact_paired=exact_paired,
                              rank_diagnostics=a.rank_diagnostics,
                              delta_posterior_file=(os.path.abspath(os.path.expanduser(a.delta_posterior_file))
-                                                   if a.delta_posterior_file else None))
+                                                   if a.delta_posterior_file else None),
+                             exact_delta_file=(os.path.abspath(os.path.expanduser(a.exact_delta_file))
+                                               if a.exact_delta_file else None))
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
