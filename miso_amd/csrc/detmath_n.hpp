@@ -198,23 +198,37 @@ __device__ __forceinline__ double det_log_fast(double x, const double (&tl)[12])
 }
 
 // The route, per wavefront: the fast routine when EVERY active lane's argument is in its domain (one compare; its lane mask
-// is tested on the scalar side), the full routine for the whole wavefront otherwise.  force_full (0 or 1, wave-uniform:
-// KernelArgs::k2_full_math, tests) sends every call down the full route.  Call in wave-uniform control flow only.
+// is tested on the scalar side), the full routine for the whole wavefront otherwise.  Call in wave-uniform control flow only.
 // full: whether the wavefront took the full route (tests, MISO_K2_ROUTE_COUNT).
-__device__ __forceinline__ double det_exp_r(double x, const double (&te)[12], uint64_t force_full, bool &full) {
-  const uint64_t outside = __builtin_amdgcn_ballot_w64(!(__builtin_fabs(x) <= 700.0));
-  full = (outside | force_full) != 0;
+// force_full (KernelArgs::k2_full_math, tests: every call down the full route) is not a mask of its own OR-ed into the
+// test -- a 64-bit scalar that a kernel short of scalar registers fetched back with two v_readlane before every call -- but
+// folded into the operand the compare reads anyway, made once per kernel (DetRoute) and held in vector registers: exp's
+// bound, which under the hook is negative, so that every |x| fails it; log's class mask, which under the hook names
+// every class.
+struct DetRoute {
+  double exp_bound;     // |x| <= exp_bound: det_exp_fast
+  uint32_t log_outside; // classes (v_cmp_class) that send det_log_r down the full route
+};
+__device__ __forceinline__ DetRoute det_route(bool force_full) {
+  DetRoute r;
+  r.exp_bound = force_full ? -1.0 : 700.0;
+  r.log_outside = force_full ? 0x3FFu : (0x3FFu & ~0x100u);   // every class but "positive normal" (0x100)
+  asm volatile("" : "+v"(r.exp_bound), "+v"(r.log_outside));  // vector registers, not rebuilt from the scalar flag at the calls
+  return r;
+}
+__device__ __forceinline__ double det_exp_r(double x, const double (&te)[12], const DetRoute &rt, bool &full) {
+  full = __builtin_amdgcn_ballot_w64(!(__builtin_fabs(x) <= rt.exp_bound)) != 0;
   if (!full) return det_exp_fast(x, te);
   return det_exp_t(x, te);
 }
-__device__ __forceinline__ double det_log_r(double x, const double (&tl)[12], uint64_t force_full, bool &full) {
-  // every class but "positive normal" (0x100): NaNs, infinities, negatives, zeros, subnormals.  Written as the one
+__device__ __forceinline__ double det_log_r(double x, const double (&tl)[12], const DetRoute &rt, bool &full) {
+  // every class but "positive normal": NaNs, infinities, negatives, zeros, subnormals.  Written as the one
   // instruction it is: the ballot of __builtin_amdgcn_class compiles to three (compare, select 0 / 1, compare).
   // The compare reads EXEC implicitly: an inactive lane's bit is 0, so it counts as inside the domain, as in a ballot.
   // (Not volatile: device inline assembly is convergent, and every caller is in wave-uniform control flow.)
   uint64_t outside;
-  asm("v_cmp_class_f64_e64 %0, %1, %2" : "=s"(outside) : "v"(x), "s"(0x3FF & ~0x100));
-  full = (outside | force_full) != 0;
+  asm("v_cmp_class_f64_e64 %0, %1, %2" : "=s"(outside) : "v"(x), "v"(rt.log_outside));
+  full = outside != 0;
   if (!full) return det_log_fast(x, tl);
   return det_log_t(x, tl);
 }

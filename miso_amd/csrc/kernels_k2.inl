@@ -392,6 +392,33 @@ __device__ __forceinline__ void k2_balance(int wv, int m) {
   else __builtin_amdgcn_s_setprio(1);
 }
 
+// A wave-uniform constant of the iteration loop, kept in a VECTOR register and fetched with one v_readfirstlane where it is
+// used.  The kernels with many bodies are short of scalar registers: what the loop reads from a scalar that was set in front
+// of it -- a by-value kernel argument, a trip count, a uniform condition hoisted as a 64-bit lane mask -- the allocator parks
+// in a lane of a spill VGPR and fetches back in every iteration with one v_readlane per dword: four for one field of a
+// 4-dword argument tuple, two for a mask.  The empty asm makes the register's content opaque and loop-variant, so the
+// fetch (and every compare of its result) stays where it is written instead of being hoisted into a spilled scalar again.
+#ifndef MISO_K2_LANE_CONST
+#define MISO_K2_LANE_CONST 1   // 0: plain scalars, the compiler's choice of where they live
+#endif
+__device__ __forceinline__ int k2_lane_const(int &v) {
+#if MISO_K2_LANE_CONST
+  asm volatile("" : "+v"(v));
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
+}
+// RoundOpen (device.hpp) with its table index in a vector register: as a scalar it was written to its spill lane in every
+// iteration of the two-isoform kernels, changed or not, and read back behind the read loop.  It changes on a round's first
+// iteration only, where it indexes a table in global memory.
+// (The compiler now takes `i`, `next` and what at() returns for divergent values though every lane holds the same: use
+// at()'s result in selects only, never as a branch around k2_exp / k2_log -- their route is a wave-wide vote, and a branch
+// the compiler sees as divergent would run it under a partial EXEC mask.)
+struct K2RoundOpen : RoundOpen {
+  __device__ explicit K2RoundOpen(const KernelArgs &a) : RoundOpen(a) { asm volatile("" : "+v"(i)); }
+};
+
 typedef const __attribute__((address_space(3))) double *k2_lds_cdp;
 typedef const __attribute__((address_space(3))) int32_t *k2_lds_cip;
 __device__ __forceinline__ double k2_lds_f64(uint32_t addr) { return *reinterpret_cast<k2_lds_cdp>(static_cast<uintptr_t>(addr)); }
@@ -507,6 +534,8 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   // single-end: behind the steady trips, masked trips of UQ positions while UQ remain, then masked steps of ONE position:
   // uq_trips = steady and masked trips together; positions UQ uq_trips .. npos - 1 are single steps
   const int uq_trips = npos / UQ;
+  // (the single-end step reads these through k2_lane_const, the forced rescan's flag -- KernelArgs::pe_force_exact -- too)
+  int full_trips_v = full_trips, uq_trips_v = uq_trips, npos_v = npos, settle_v = a.pe_force_exact;
   // the halves of the partial block's word w that are NOT reads of the chain (rem = 0: all of them)
   uint32_t part_inv[4];
 #pragma unroll
@@ -728,6 +757,9 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
       }
     }
     PROF_T(g0);
+    // the wavefront's trip counts and the tests' rescan flag: set in front of the iteration loop, one v_readfirstlane each here
+    const int full_trips_s = k2_lane_const(full_trips_v), uq_trips_s = k2_lane_const(uq_trips_v), npos_s = k2_lane_const(npos_v);
+    const bool settle_all = k2_lane_const(settle_v) != 0;
     // u < t with u = hi 2^16 + lo:  hi < t >> 16, or hi == t >> 16 and lo < (t & 0xFFFF).  The loop looks at the high
     // halves only -- eight reads per Philox block -- and notes the trip in which one of them EQUALS t >> 16 (one read
     // in 65 536); that trip's blocks' low halves (site MISO_SITE_GIBBS_LOW) are drawn behind the loop, by the lane that owns them.
@@ -806,25 +838,25 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // reaches.  d0 is A, the sum of c, until the loop is through.)
     constexpr int CHUNK = 8000 / UQ;
     static_assert(CHUNK * UQ <= K2_COUNT_MAX_BLOCKS, "the packed counters would carry");
-    for (int j0 = 0; j0 < full_trips; j0 += CHUNK) {
-      const int j1 = min(full_trips, j0 + CHUNK);
+    for (int j0 = 0; j0 < full_trips_s; j0 += CHUNK) {
+      const int j1 = min(full_trips_s, j0 + CHUNK);
       for (int j = j0; j < j1; j++) trip(UQ * j, std::false_type{}, whole);
       d0 += k2_count_sum(accv);
       accv = 0;
     }
-    for (int j0 = full_trips; j0 < uq_trips; j0 += CHUNK) {
-      const int j1 = min(uq_trips, j0 + CHUNK);
+    for (int j0 = full_trips_s; j0 < uq_trips_s; j0 += CHUNK) {
+      const int j1 = min(uq_trips_s, j0 + CHUNK);
       for (int j = j0; j < j1; j++) trip(UQ * j, std::true_type{}, whole);
       d0 += k2_count_sum(accv);
       accv = 0;
     }
-    if (UQ * uq_trips < npos) {   // fewer than UQ positions left: one block per lane at a time (fewer than UQ: no chunks)
-      for (int k = UQ * uq_trips; k < npos; k++) trip(k, std::true_type{}, single);
+    if (UQ * uq_trips_s < npos_s) {   // fewer than UQ positions left: one block per lane at a time (fewer than UQ: no chunks)
+      for (int k = UQ * uq_trips_s; k < npos_s; k++) trip(k, std::true_type{}, single);
       d0 += k2_count_sum(accv);
       accv = 0;
     }
     // behind the loop: the lane's reads on isoform 0 from its sum and its flag (k2_finish_lane above)
-    d0 = k2_finish_lane<UQ>(d0, amb, th, tl, sub, GE, nfq, rem, nblk, npos, uq_trips, lane_used, a.pe_force_exact != 0,
+    d0 = k2_finish_lane<UQ>(d0, amb, th, tl, sub, GE, nfq, rem, nblk, npos_s, uq_trips_s, lane_used, settle_all,
                             [&](int q, bool low) {
                               return miso_philox4x32(static_cast<uint32_t>(q), iter, low ? (MISO_SITE_GIBBS_LOW | (chain << 8)) : c2_gibbs,
                                                      event_id, k0, k1);
@@ -886,10 +918,11 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   double TE[12], TL[12];
   det_tables_to_registers(TE, TL);
   // the routines without their special cases where no active lane's argument needs one (detmath_n.hpp det_exp_r / det_log_r:
-  // a wave-uniform choice, every call site is in wave-uniform control flow); MISO_K2_FULL_MATH: the full routines always
-  const uint64_t full_math = a.k2_full_math != 0;
-  auto k2_exp = [&](double v) { bool full; const double y = det_exp_r(v, TE, full_math, full); ROUTE_COUNT(full); return y; };
-  auto k2_log = [&](double v) { bool full; const double y = det_log_r(v, TL, full_math, full); ROUTE_COUNT(full); return y; };
+  // a wave-uniform choice, every call site is in wave-uniform control flow); MISO_K2_FULL_MATH: the full routines always,
+  // through the compares' own operands (DetRoute: three vector registers, nothing fetched per call)
+  const DetRoute route = det_route(a.k2_full_math != 0);
+  auto k2_exp = [&](double v) { bool full; const double y = det_exp_r(v, TE, route, full); ROUTE_COUNT(full); return y; };
+  auto k2_log = [&](double v) { bool full; const double y = det_log_r(v, TL, route, full); ROUTE_COUNT(full); return y; };
 #else
   auto k2_exp = [](double v) { return miso_det_exp(v); };
   auto k2_log = [](double v) { return miso_det_log(v); };
@@ -914,8 +947,24 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
   if (a.M == 0 && live && chain == 0) gibbs_write(MISO_ITER_INIT);
 
   uint64_t hash = 0xCBF29CE484222325ull;
-  int accepted = 0, lagCounter = 0, noS = 0;
+  int accepted = 0;
   const bool writer = live && sub == 0;
+  // Recording (miso.c:882-893: from iteration B on, every lag-th iteration's state is a sample; the chains' samples
+  // interleave, column noS + chain with noS += C per sample).  The reference's two counters are wave-uniform, so they were
+  // scalars -- spilled ones, read, updated and written back through v_readlane / v_writelane in every iteration together
+  // with a.B, a.lag and a.C.  The same schedule held by the writing lane in vector registers: the next iteration it records
+  // (B + lag - 1, then every lag-th; -1: never -- every lane but the chain's first, and lag < 1, where the reference's
+  // counter never meets lag - 1) and where that sample goes; the steps in registers of their own, read once here.
+  int next_rec = -1;
+  {
+    const long first = static_cast<long>(max(a.B, 0)) + a.lag - 1;
+    if (writer && a.lag >= 1 && first <= 0x7FFFFFFFl) next_rec = static_cast<int>(first);
+  }
+  double *rec_s = samples + 2 * static_cast<size_t>(chain), *rec_l = loglik + chain;
+  uint32_t lag_v = static_cast<uint32_t>(a.lag);
+  size_t c_v = static_cast<size_t>(a.C);
+  int trace_on = (trace && writer) ? 1 : 0, M_v = a.M, balance_v = a.balance;
+  asm volatile("" : "+v"(lag_v), "+v"(c_v));
   // WIDE, eight wavefronts: wavefronts w and w + 4 of the workgroup share a SIMD and belong to the SAME chain.  Both used to run
   // the Metropolis-Hastings step (same inputs, same bits) -- on a SIMD whose two wavefronts are one chain's that is the step
   // twice per iteration, and the launch's largest event (80 000 drawing reads on one workgroup) set the launch's duration: 1.33
@@ -940,17 +989,25 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     e_p = k2_exp(alphaN_p);
   }
   const double E0 = k2_exp(0.0);   // exp(maxv - maxv) of the log-sum-exp below
-  RoundOpen ro(a);
-  for (int m = 0; m < a.M; m++) {
+  K2RoundOpen ro(a);
+  // (a.M and a.balance through k2_lane_const: one v_readfirstlane each per iteration instead of the four v_readlane of
+  // the argument tuple a.M sits in and a.balance's two.  The bound is fetched in the loop's increment, not in its test: a
+  // test that holds a convergent operation is not rotated to the loop's end, and the loop then copies half a dozen
+  // loop-carried registers at its head and back.)
+  for (int m = 0, m_end = k2_lane_const(M_v); m < m_end; m++, m_end = k2_lane_const(M_v)) {
     const bool opens = ro.at(a, m);   // a round's first iteration: no proposal terms (miso.c:866)
-    prio_by_progress(a, m);
-    if (MODE == 0 && WPB == 8 && !WIDE && !COLLAPSED && a.balance == 1) k2_balance(threadIdx.x >> 6, m);
+    const int balance = k2_lane_const(balance_v);
+    if (balance == 2) prio_by_progress(a, m);
+    if (MODE == 0 && WPB == 8 && !WIDE && !COLLAPSED && balance == 1) k2_balance(threadIdx.x >> 6, m);
     if (WIDE && !coop_ok) return;   // the chain's workgroups gave up waiting for each other (coop.hpp): the host reports it
     if (!helper) {
     hash = (hash ^ static_cast<uint32_t>(cnt0)) * 0x100000001B3ull;
     hash = (hash ^ static_cast<uint32_t>(cnt1)) * 0x100000001B3ull;
-    if (trace && writer) {
-      int32_t *row = trace + (static_cast<size_t>(m) * a.C + chain) * 2;
+    // (the writer's test on a register that is opaque here: as the loop-invariant lane mask of `trace && writer` it was
+    // hoisted, spilled and fetched with two v_readlane)
+    asm volatile("" : "+v"(trace_on));
+    if (trace_on != 0) {
+      int32_t *row = trace + (static_cast<size_t>(m) * c_v + chain) * 2;
       row[0] = cnt0; row[1] = cnt1;
     }
     PROF_T(m0);
@@ -1036,18 +1093,13 @@ __device__ __forceinline__ void k2_body(const KernelArgs &a, unsigned block_x, u
     // miso.c:882-893.  (Round 5 tried issuing these stores BEHIND the Gibbs step -- vmcnt counts loads and stores in order,
     // so a load issued after a store is only "there" once the store has been acknowledged: no gain paired-end (198.4 vs
     // 199.4 ms), 4 % slower at MISO's default settings, profiles/r05_store_after.txt.)
-    if (m >= a.B) {
-      if (lagCounter == a.lag - 1) {
-        if (writer) {
-          const size_t col = static_cast<size_t>(noS) + chain;
-          *reinterpret_cast<double2 *>(samples + col * 2) = make_double2(cur.x0, cur.x1);
-          loglik[col] = cJS;
-        }
-        noS += a.C;
-        lagCounter = 0;
-      } else {
-        lagCounter++;
-      }
+    // One compare of the iteration number with the lane's own register decides; nothing is written back unchanged.
+    if (m == next_rec) {
+      *reinterpret_cast<double2 *>(rec_s) = make_double2(cur.x0, cur.x1);
+      *rec_l = cJS;
+      rec_s += 2 * c_v;
+      rec_l += c_v;
+      next_rec = static_cast<int>(static_cast<uint32_t>(next_rec) + lag_v);   // (past 2^31 - 1: negative, never met)
     }
     PROF_T(m2);
     PROF_ADD(pf_rec, m1, m2);

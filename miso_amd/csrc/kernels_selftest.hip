@@ -63,11 +63,11 @@ __global__ void __launch_bounds__(256) selftest_detmath_routed_kernel(int fn, in
   det_tables_to_registers(te, tl);
   const bool on = i < n;
   const double v = on ? x[i] : 1.0;
-  const uint64_t force = force_full != 0;
+  const DetRoute rt = det_route(force_full != 0);
   bool full = false;
   double y;
-  if (fn == MISO_SELFTEST_LOG_R) y = det_log_r(v, tl, force, full);
-  else y = det_exp_r(v, te, force, full);
+  if (fn == MISO_SELFTEST_LOG_R) y = det_log_r(v, tl, rt, full);
+  else y = det_exp_r(v, te, rt, full);
   if (on) { out[i] = y; route[i] = full ? MISO_SELFTEST_ROUTE_FULL : MISO_SELFTEST_ROUTE_FAST; }
 }
 

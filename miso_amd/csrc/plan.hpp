@@ -59,6 +59,10 @@ struct LaneCost {
 // (docs/history.md; round 4's "108" for that loop counted the trip's `s_nop`s and the chunk loop's share as well); the
 // launch time hardly moves between 44 and 96,
 // profiles/r04_lazy_low_bits.txt: `block` stays as fitted)
+// (the step around the loop no longer fetches spilled scalars back -- 53 v_readlane and 6 v_writelane per iteration in the
+// four-lane body of the one-round kernel, six v_readfirstlane and two compares in their place, kernels_k2.inl
+// k2_lane_const and the recording block: about 3 % of a wavefront's VALU instructions, the same for every width, so the
+// widths compare as before and `step[]` stays as fitted: profiles/k2_step_scalars.txt)
 inline LaneCost k2_cost_single() {
   LaneCost c; c.step[1] = 1750; c.step[2] = 1170; c.step[3] = 840; c.step[4] = 720; c.block = 54; c.uq = 2; c.paired = false;
   c.draws = 8;

@@ -1,14 +1,11 @@
 #!/bin/bash
-# Profile build of the library (-DMISO_K2_PROFILE: s_memtime phase counters written into loglik[0..]).
+# Profile build of the library (-DMISO_K2_PROFILE: per-phase cycle counters of the two-isoform step, written into
+# loglik[0..4] of every event's first chain; read them with tools/k2_phase_cycles.py).  Every unit that instantiates
+# k2_body is recompiled with the define and linked with the in-tree objects of everything else (tools/build_variant.sh:
+# build the library first), so the unit list is the Makefile's kernels_k2* objects and nothing else.
+#   tools/build_prof.sh   -> tools/_build/libmiso_prof.so   (OUTNAME=x: libmiso_x.so; PROFDEF / EXTRA: other defines)
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p tools/_build
-F="$EXTRA ${PROFDEF--DMISO_K2_PROFILE} -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Iinclude -Imiso_amd/csrc -Wno-unused-result"
-for f in runtime kernels kernels_k2 kernels_grp_c4 kernels_grp_c8 kernels_grp_c12 kernels_grp_c16 kernels_grp_c32 kernels_flat_c4 kernels_flat_c8 kernels_flat_c12 kernels_flat_c16 kernels_flat_c32 kernels_summary kernels_match capi; do
-  /opt/rocm/bin/hipcc $F -c miso_amd/csrc/$f.hip -o tools/_build/$f.o &
-done
-/opt/rocm/bin/hipcc $F -x hip -c miso_amd/csrc/host.cpp -o tools/_build/host.o &
-g++ -O2 -std=c++17 -fPIC -Iinclude -Imiso_amd/csrc -c miso_amd/csrc/alnio.cpp -o tools/_build/alnio.o &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC tools/_build/*.o -o tools/_build/${OUTLIB:-libmiso_prof.so} -lz -lpthread
-rm -f tools/_build/*.o
+units=$(sed -n 's/^OBJS *= *//p' miso_amd/csrc/Makefile | tr ' ' '\n' | sed -n 's/^\(kernels_k2[a-z0-9_]*\)\.o$/\1/p')
+[ -n "$units" ] || { echo "no kernels_k2* units in miso_amd/csrc/Makefile" >&2; exit 1; }
+exec tools/build_variant.sh "${OUTNAME:-prof}" "${PROFDEF--DMISO_K2_PROFILE} $EXTRA" $units

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""VALU instructions, selects by encoding, compares and f64 reciprocals in line ranges of a kept assembly file (CPU tool).
+"""VALU instructions, selects by encoding, compares, f64 reciprocals and division scalings, spilled-scalar traffic
+(v_readlane_b32 / v_writelane_b32, v_readfirstlane_b32), s_nop and cross-lane operations (DPP, ds_bpermute) in line ranges
+of a kept assembly file (CPU tool).
 
     python tools/isa_range_count.py miso_amd/csrc/.isa/kernels_k2m_m0w8.s 5200-5700 [FIRST-LAST ...]
     python tools/isa_range_count.py miso_amd/csrc/.isa/kernels_k2m_m0w8.s --label .LBB0_236 [--label ...]
@@ -33,6 +35,20 @@ def count(lines):
             c["compare"] += 1
         if op.startswith("v_rcp_f64"):
             c["rcp f64"] += 1
+        if op.startswith("v_div_scale"):
+            c["div_scale"] += 1
+        if op == "v_readlane_b32":
+            c["readlane"] += 1
+        if op == "v_writelane_b32":
+            c["writelane"] += 1
+        if op == "v_readfirstlane_b32":
+            c["readfirstlane"] += 1
+        if op == "s_nop":
+            c["s_nop"] += 1
+        if op.endswith("_dpp") or re.search(r"\b(quad_perm|row_shl|row_shr|row_ror|row_bcast|row_share|row_xmask|row_mirror|row_half_mirror|wave_sh[lr]|wave_ro[lr]):?", l):
+            c["dpp"] += 1
+        if op.startswith("ds_bpermute") or op.startswith("ds_permute"):
+            c["bpermute"] += 1
         if op.startswith(("s_cbranch", "s_branch")):
             c["branch"] += 1
     return c
@@ -56,7 +72,8 @@ def main():
         end = next(i for i in range(starts[0] + 1, len(lines)) if re.match(r"^\.L\w+:", lines[i]))
         spans.append((lab, starts[0], end))
     total = collections.Counter()
-    keys = ("VALU", "select e32", "select e64", "of which vcc", "compare", "rcp f64", "branch")
+    keys = ("VALU", "select e32", "select e64", "of which vcc", "compare", "rcp f64", "div_scale", "readlane", "writelane",
+            "readfirstlane", "s_nop", "dpp", "bpermute", "branch")
     for name, lo, hi in spans:
         c = count(lines[lo:hi])
         total += c
