@@ -1,4 +1,7 @@
-// batch.hpp -- the batch object behind miso_batch_t (definition shared by runtime.hip / launch.hip / capi.hip)
+// batch.hpp -- the batch object behind miso_batch_t (definition shared by runtime.hip / launch.hip / capi.hip and the passes
+// that are its methods or take batches).  What the batch owns on the device is its pools, tables, streams and the two events
+// around its sampler kernels; a pass over the resident samples holds its buffers and events for the call only
+// (hip_host.hpp HipCall, column_pass.hpp) and stores its results here when it has succeeded.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -352,6 +355,7 @@ struct miso_batch {
   std::vector<uint64_t> h_sum_off;      // offsets (in doubles) into h_summary
   bool summarized = false;
   std::vector<double> h_compare;        // per event: K x {mean1, mean2, bayes factor, posterior density at 0}
+  std::vector<uint64_t> h_cmp_off;      // offsets (in doubles) into h_compare
   bool compared = false;
   std::vector<double> h_diag;           // per event: K x {rhat, ess, mcse, lag} (kernels_diagnose.hip)
   std::vector<uint64_t> h_diag_off;     // offsets (in doubles) into h_diag
@@ -360,8 +364,7 @@ struct miso_batch {
   std::vector<uint64_t> h_rank_off;     // (kernels_diagnose_rank.hip) and the offsets (in doubles) into it
   bool rank_diagnosed = false;
   float summarize_ms = 0.f, diagnose_ms = 0.f;   // kernel time of the last summarize / diagnose pass
-  float rank_ms = 0.f;                  // and of the last diagnose_rank pass
-  hipEvent_t pass_ev0 = nullptr, pass_ev1 = nullptr;   // bracket that pass; made by the first one
+  float rank_ms = 0.f;                  // and of the last diagnose_rank pass (each timed by its own HipCall's events)
   bool adopted = false;                 // samples produced elsewhere (adopt_pool): p.noChains says nothing about them
   uint64_t in_bytes = 0, out_bytes = 0;
   float last_ms = 0.f;

@@ -874,9 +874,7 @@ int miso_batch_get_comparison(const miso_batch_t *b, int i, double *mean1, doubl
     need(b, "batch");
     const PackedEvent &e = event_at(b, i);
     if (!b->compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare has not run");
-    size_t off = 0;
-    for (int j = 0; j < i; j++) off += 4 * static_cast<size_t>(b->events[j].K);
-    const double *s = b->h_compare.data() + off;
+    const double *s = b->h_compare.data() + b->h_cmp_off[i];
     for (int k = 0; k < e.K; k++) {
       if (mean1) mean1[k] = s[4 * k];
       if (mean2) mean2[k] = s[4 * k + 1];

@@ -1,6 +1,7 @@
 // hip_host.hpp -- host-side launch glue shared by the units under csrc/: the check of a HIP call, a wall clock, and what one
-// one-shot call holds on the device.  (The pooled, multi-stream Scratch objects of the coverage, density, text and insert
-// passes are their own.)
+// one-shot call holds on the device: the exact-posterior units' and every pass over the resident sample pool
+// (column_pass.hpp).  (The pooled, multi-stream Scratch objects of the coverage, density, text and insert passes are their
+// own.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,10 +50,10 @@ struct HipCall {
     if (e1) (void) hipEventDestroy(e1);
     if (own) (void) hipStreamDestroy(own);
   }
-  // `bytes` of device memory, rounded up to 16 (and 16 at least)
+  // `bytes` of device memory, rounded up to 16 (and 16 at least); none left: MISO_ENOMEM
   template <class T = double> T *alloc(size_t bytes) {
     bufs.push_back(nullptr);
-    HIP_OK(hipMalloc(&bufs.back(), (std::max<size_t>(bytes, 1) + 15) & ~size_t{15}));
+    HIP_OK_OR_NOMEM(hipMalloc(&bufs.back(), (std::max<size_t>(bytes, 1) + 15) & ~size_t{15}));
     return static_cast<T *>(bufs.back());
   }
   // a device copy of a host array, queued on the stream

@@ -19,8 +19,8 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "column_pass.hpp"
 #include "compare_column.hpp"
-#include "hip_host.hpp"
 
 namespace miso {
 
@@ -75,17 +75,6 @@ __global__ __launch_bounds__(256) void compare_groups_kernel(const DevEvent *con
   }
 }
 
-// (a HIP runtime failure is MISO_ENODEVICE as everywhere in runtime.hip -- include/miso_amd.h: "no usable HIP device / HIP
-// runtime error" -- except memory: a chunk whose n1 * n2 results do not fit is MISO_ENOMEM, MemoryError in Python:
-// hip_host.hpp HIP_OK_OR_NOMEM)
-namespace {
-struct DevMem {
-  void *p = nullptr;
-  ~DevMem() { if (p) (void) hipFree(p); }
-  void alloc(size_t bytes) { HIP_OK_OR_NOMEM(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
-};
-}  // namespace
-
 // Which columns a workgroup of compare_groups_kernel can keep in LDS: `budget` bytes of dynamic LDS, S doubles a column.
 int compare_groups_staging(int n1, int n2, int S, size_t budget) {
   const size_t col = static_cast<size_t>(S) * 8;
@@ -94,45 +83,31 @@ int compare_groups_staging(int n1, int n2, int S, size_t budget) {
   return MISO_STAGE_NONE;
 }
 
+// (a HIP runtime failure is MISO_ENODEVICE as everywhere in runtime.hip -- include/miso_amd.h: "no usable HIP device / HIP
+// runtime error" -- except memory: a call whose n1 * n2 results do not fit is MISO_ENOMEM, MemoryError in Python: HipCall::alloc)
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging,
                     double *out, int64_t out_len, float *kernel_ms) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the comparison has no CPU path");
-  if (n1 < 1 || n2 < 1) MISO_FAIL(MISO_EINVAL, "Each group needs at least one batch");
   if (!(smoothing > 0)) MISO_FAIL(MISO_EINVAL, "Invalid smoothing parameter");
   if (staging < MISO_STAGE_AUTO || staging > MISO_STAGE_NONE) MISO_FAIL(MISO_EINVAL, "Invalid staging");
-  std::vector<miso_batch *> all;
-  for (int i = 0; i < n1 + n2; i++) {
-    miso_batch *b = i < n1 ? g1[i] : g2[i - n1];
-    const std::string who = "group " + std::to_string(i < n1 ? 1 : 2) + " batch " + std::to_string(i < n1 ? i : i - n1) + ": ";
-    if (!b) MISO_FAIL(MISO_EINVAL, who + "batch is NULL");
-    if (!b->launched) MISO_FAIL(MISO_EINVAL, who + "batch not launched");
-    all.push_back(b);
-    const miso_batch &r = *all[0];
-    if (b->device != r.device) MISO_FAIL(MISO_EINVAL, who + "Batches to compare live on different devices");
-    if (b->events.size() != r.events.size() || b->S() != r.S())
-      MISO_FAIL(MISO_EINVAL, who + "Batches to compare differ in events or samples per event");
-    for (size_t e = 0; e < r.events.size(); e++)
-      if (b->events[e].K != r.events[e].K) MISO_FAIL(MISO_EINVAL, who + "Events to compare differ in isoforms");
-  }
+  const std::vector<miso_batch *> all = same_events_groups(g1, n1, g2, n2);
   miso_batch &r = *all[0];
   const int n = static_cast<int>(r.events.size()), S = r.S(), nb = n1 + n2;
   if (S < 2) MISO_FAIL(MISO_EINVAL, "Too few samples to compare");
-  std::vector<uint64_t> off(std::max(n, 1));
-  uint64_t tot = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) { off[i] = tot; tot += 4 * r.events[i].K; kmax = std::max(kmax, r.events[i].K); }
-  const uint64_t need_len = static_cast<uint64_t>(n1) * n2 * tot;
+  const ColumnLayout l = column_layout(r, 4);
+  const uint64_t tot = l.total, need_len = static_cast<uint64_t>(n1) * n2 * tot;
   if (out_len < 0 || static_cast<uint64_t>(out_len) < need_len) MISO_FAIL(MISO_EINVAL, "out is too short for n1 * n2 * tot doubles");
   if (need_len && !out) MISO_FAIL(MISO_EINVAL, "out is NULL");
   if (kernel_ms) *kernel_ms = 0.f;
   if (n == 0) return;
-  HIP_OK_OR_NOMEM(hipSetDevice(r.device));
-  for (miso_batch *b : all) HIP_OK_OR_NOMEM(hipStreamSynchronize(b->stream));
+  HIP_OK(hipSetDevice(r.device));
+  for (miso_batch *b : all) { finish_rounds(*b); HIP_OK(hipStreamSynchronize(b->stream)); }
 
   // the LDS a workgroup may have beside the kernel's own reduction buffers
   int lds_max = 0;
-  HIP_OK_OR_NOMEM(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, r.device));
+  HIP_OK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, r.device));
   hipDeviceProp_t prop{};
-  HIP_OK_OR_NOMEM(hipGetDeviceProperties(&prop, r.device));
+  HIP_OK(hipGetDeviceProperties(&prop, r.device));
   // (gfx950: 160 KiB per CU, all of it open to one workgroup, whatever the attribute says)
   if (std::string(prop.gcnArchName).rfind("gfx950", 0) == 0) lds_max = std::max(lds_max, 160 * 1024);
   using Kernel = void (*)(const DevEvent *const *, const unsigned char *const *, int, int, int, int, double, const uint64_t *,
@@ -140,36 +115,24 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
   const Kernel kernels[4] = {compare_groups_kernel<false, false>, compare_groups_kernel<true, true>,
                              compare_groups_kernel<true, false>, compare_groups_kernel<false, true>};
   hipFuncAttributes fa{};
-  HIP_OK_OR_NOMEM(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernels[1])));
+  HIP_OK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernels[1])));
   const size_t budget = static_cast<size_t>(lds_max) > fa.sharedSizeBytes ? lds_max - fa.sharedSizeBytes : 0;
   const size_t col = static_cast<size_t>(S) * 8;
   if (staging == MISO_STAGE_AUTO) staging = compare_groups_staging(n1, n2, S, budget);
   const size_t dyn = staging == MISO_STAGE_BOTH ? nb * col : staging == MISO_STAGE_SMALLER ? std::min(n1, n2) * col : 0;
   if (dyn > budget) MISO_FAIL(MISO_EINVAL, "The requested staging does not fit the workgroup's LDS");
   const Kernel kernel = kernels[staging == MISO_STAGE_BOTH ? 1 : staging == MISO_STAGE_NONE ? 0 : (n1 <= n2 ? 2 : 3)];
-  if (dyn > 0)
-    HIP_OK_OR_NOMEM(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   static_cast<int>(dyn)));
 
-  std::vector<const void *> ptrs(2 * static_cast<size_t>(nb));
-  for (int i = 0; i < nb; i++) { ptrs[i] = all[i]->d_events; ptrs[nb + i] = all[i]->d_out; }
-  DevMem d_ptrs, d_off, d_cmp;
-  d_ptrs.alloc(ptrs.size() * sizeof(void *));
-  d_off.alloc(n * sizeof(uint64_t));
-  d_cmp.alloc(need_len * sizeof(double));
-  hipStream_t st = r.stream;
-  HIP_OK_OR_NOMEM(hipMemcpyAsync(d_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
-  HIP_OK_OR_NOMEM(hipMemcpyAsync(d_off.p, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  HIP_OK_OR_NOMEM(hipEventRecord(r.ev0, st));
-  hipLaunchKernelGGL(kernel, dim3(n, kmax), dim3(256), dyn, st,
-                     static_cast<const DevEvent *const *>(d_ptrs.p),
-                     static_cast<const unsigned char *const *>(d_ptrs.p) + nb, n1, n2, n, S, smoothing,
-                     static_cast<const uint64_t *>(d_off.p), tot, static_cast<double *>(d_cmp.p));
-  HIP_OK_OR_NOMEM(hipGetLastError());
-  HIP_OK_OR_NOMEM(hipEventRecord(r.ev1, st));
-  HIP_OK_OR_NOMEM(hipMemcpyAsync(out, d_cmp.p, need_len * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK_OR_NOMEM(hipStreamSynchronize(st));
-  if (kernel_ms) HIP_OK_OR_NOMEM(hipEventElapsedTime(kernel_ms, r.ev0, r.ev1));
+  const std::vector<const void *> ptrs = group_pointers(all);
+  HipCall call(r.stream);
+  const void *const *d_ptrs = call.upload(ptrs.data(), ptrs.size() * sizeof(void *));
+  const float ms = column_pass(call, fn(kernel), dim3(n, l.kmax), dyn, l.off, need_len, out,
+                               [&](dim3 grid, const uint64_t *d_off, double *d_cmp) {
+                                 hipLaunchKernelGGL(kernel, grid, dim3(256), dyn, call.st, reinterpret_cast<const DevEvent *const *>(d_ptrs),
+                                                    reinterpret_cast<const unsigned char *const *>(d_ptrs) + nb, n1, n2, n, S, smoothing,
+                                                    d_off, tot, d_cmp);
+                               });
+  if (kernel_ms) *kernel_ms = ms;
 }
 
 }  // namespace miso

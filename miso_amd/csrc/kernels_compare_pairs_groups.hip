@@ -23,9 +23,9 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "column_pass.hpp"
 #include "compare_pairs.hpp"
 #include "compare_pairs_device.hpp"
-#include "hip_host.hpp"
 #include "order_key.hpp"
 #include "text_digits.hpp"
 
@@ -169,25 +169,7 @@ constexpr size_t PAIRS_GROUP_WORK_BYTES = size_t{256} << 20;
 void compare_pairs_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double confidence_level, const double *tau,
                           int n_tau, bool as_text, uint64_t *out, int64_t out_len, int64_t *n_pairs, float *kernel_ms) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the comparison has no CPU path");
-  if (n1 < 1 || n2 < 1) MISO_FAIL(MISO_EINVAL, "Each group needs at least one batch");
-  if (!(confidence_level > 0 && confidence_level < 1)) MISO_FAIL(MISO_EINVAL, "Invalid confidence level: it must lie inside (0, 1)");
-  if (n_tau < 0 || n_tau > PAIRS_MAX_TAU) MISO_FAIL(MISO_EINVAL, "Invalid number of delta psi thresholds: 0 to 4");
-  for (int j = 0; j < n_tau; j++)
-    if (!(tau[j] > 0 && tau[j] < 1)) MISO_FAIL(MISO_EINVAL, "Invalid delta psi threshold: it must lie inside (0, 1)");
-  std::vector<miso_batch *> all;
-  for (int i = 0; i < n1 + n2; i++) {
-    miso_batch *b = i < n1 ? g1[i] : g2[i - n1];
-    const std::string who = "group " + std::to_string(i < n1 ? 1 : 2) + " batch " + std::to_string(i < n1 ? i : i - n1) + ": ";
-    if (!b) MISO_FAIL(MISO_EINVAL, who + "batch is NULL");
-    if (!b->launched) MISO_FAIL(MISO_EINVAL, who + "batch not launched");
-    all.push_back(b);
-    const miso_batch &r = *all[0];
-    if (b->device != r.device) MISO_FAIL(MISO_EINVAL, who + "Batches to compare live on different devices");
-    if (b->events.size() != r.events.size() || b->S() != r.S())
-      MISO_FAIL(MISO_EINVAL, who + "Batches to compare differ in events or samples per event");
-    for (size_t e = 0; e < r.events.size(); e++)
-      if (b->events[e].K != r.events[e].K) MISO_FAIL(MISO_EINVAL, who + "Events to compare differ in isoforms");
-  }
+  const std::vector<miso_batch *> all = same_events_groups(g1, n1, g2, n2);
   miso_batch &r = *all[0];
   const int n = static_cast<int>(r.events.size()), S = r.S(), nb = n1 + n2;
   if (S < 1) MISO_FAIL(MISO_EINVAL, "Too few samples to compare");
@@ -199,75 +181,45 @@ void compare_pairs_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, 
                                  " draws, 16384 per event and group at most");
   }
   const int N1 = n1 * S, N2 = n2 * S;
-  std::vector<uint64_t> off(std::max(n, 1));
-  uint64_t cols = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) { off[i] = cols; cols += r.events[i].K; kmax = std::max(kmax, r.events[i].K); }
+  const int64_t M = static_cast<int64_t>(N1) * N2;
+  const PairsArgs pa = pairs_args(M, confidence_level, tau, n_tau);
+  ColumnLayout l = column_layout(r, 1);
+  const int kmax = l.kmax;
   const size_t W = static_cast<size_t>(pairs_words(n_tau));
-  const uint64_t need_len = cols * W;
+  const uint64_t need_len = l.total * W;
   if (out_len < 0 || static_cast<uint64_t>(out_len) < need_len) MISO_FAIL(MISO_EINVAL, "out is too short for pairs_words(n_tau) words per column");
   if (need_len && !out) MISO_FAIL(MISO_EINVAL, "out is NULL");
-  // the ranks in double, as miso_batch::compare_pairs takes them: M <= 2^28, every product and sum below is far from 2^53
-  const int64_t M = static_cast<int64_t>(N1) * N2;
-  const double alpha = 1 - confidence_level;
-  const double lo_d = std::max(0.0, std::floor((alpha / 2) * static_cast<double>(M) + 0.5) - 1);
-  const double hi_d = std::min(static_cast<double>(M - 1), std::max(lo_d, std::floor((1 - alpha / 2) * static_cast<double>(M) + 0.5) - 1));
-  PairsArgs pa{};
-  pa.rank[0] = static_cast<uint32_t>((M - 1) / 2);
-  pa.rank[1] = static_cast<uint32_t>(lo_d);
-  pa.rank[2] = static_cast<uint32_t>(hi_d);
-  pa.n_tau = n_tau;
-  for (int j = 0; j < n_tau; j++) pa.tau[j] = tau[j];
   if (n_pairs) *n_pairs = M;
   if (kernel_ms) *kernel_ms = 0.f;
   if (n == 0) return;
-  HIP_OK_OR_NOMEM(hipSetDevice(r.device));
-  for (miso_batch *b : all) {
-    // under CONVERGENT_MEAN a launch is finished once sync() has run its further rounds
-    if (b->p.stop == MISO_STOP_CONVERGENT_MEAN && !b->converged_done) b->sync(nullptr);
-    HIP_OK_OR_NOMEM(hipStreamSynchronize(b->stream));
-  }
+  HIP_OK(hipSetDevice(r.device));
+  for (miso_batch *b : all) { finish_rounds(*b); HIP_OK(hipStreamSynchronize(b->stream)); }
   // an event whose sample text some batch did not decode (adopt_text): the kernel does not touch its columns
   for (int i = 0; i < n; i++)
     for (miso_batch *b : all)
-      if (b->event_unread(i)) off[i] |= PAIRS_SKIP_EVENT;
+      if (b->event_unread(i)) l.off[i] |= PAIRS_SKIP_EVENT;
 
   const size_t dyn = static_cast<size_t>(std::max(N1, N2)) * sizeof(uint64_t);   // what is live, not the limit
-  HIP_OK_OR_NOMEM(hipFuncSetAttribute(reinterpret_cast<const void *>(compare_pairs_groups_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(dyn)));
   const size_t row = static_cast<size_t>(kmax) * N1 * sizeof(double);           // an event's rows of the workspace
   const int per_launch = static_cast<int>(std::min<size_t>(n, std::max<size_t>(1, PAIRS_GROUP_WORK_BYTES / row)));
 
-  std::vector<const void *> ptrs(2 * static_cast<size_t>(nb));
-  for (int i = 0; i < nb; i++) { ptrs[i] = all[i]->d_events; ptrs[nb + i] = all[i]->d_out; }
-  struct Bufs {                        // freed however the call is left: nothing of it outlives the call
-    std::vector<void *> p;
-    ~Bufs() { for (void *q : p) (void) hipFree(q); }
-    void *alloc(size_t bytes) {
-      p.push_back(nullptr);
-      HIP_OK_OR_NOMEM(hipMalloc(&p.back(), std::max<size_t>(bytes, 16)));
-      return p.back();
-    }
-  } bufs;
-  void *d_ptrs = bufs.alloc(ptrs.size() * sizeof(void *));
-  uint64_t *d_off = static_cast<uint64_t *>(bufs.alloc(n * sizeof(uint64_t)));
-  uint64_t *d_res = static_cast<uint64_t *>(bufs.alloc(need_len * sizeof(uint64_t)));
-  double *d_work = static_cast<double *>(bufs.alloc(row * per_launch));
-  hipStream_t st = r.stream;
-  HIP_OK_OR_NOMEM(hipMemcpyAsync(d_ptrs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, st));
-  HIP_OK_OR_NOMEM(hipMemcpyAsync(d_off, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  const std::vector<const void *> ptrs = group_pointers(all);
+  HipCall call(r.stream);
+  const void *const *d_ptrs = call.upload(ptrs.data(), ptrs.size() * sizeof(void *));
+  double *d_work = call.alloc(row * per_launch);
   // (the launches follow one another in the stream, each with the whole workspace: one pair of events times their sum)
-  HIP_OK_OR_NOMEM(hipEventRecord(r.ev0, st));
-  for (int e0 = 0; e0 < n; e0 += per_launch) {
-    const int ne = std::min(per_launch, n - e0);
-    hipLaunchKernelGGL(compare_pairs_groups_kernel, dim3(ne, kmax), dim3(256), dyn, st,
-                       static_cast<const DevEvent *const *>(d_ptrs), static_cast<const unsigned char *const *>(d_ptrs) + nb, n1,
-                       n2, S, e0, ne, kmax, pa, as_text ? 1 : 0, d_off, d_res, d_work);
-    HIP_OK_OR_NOMEM(hipGetLastError());
-  }
-  HIP_OK_OR_NOMEM(hipEventRecord(r.ev1, st));
-  HIP_OK_OR_NOMEM(hipMemcpyAsync(out, d_res, need_len * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIP_OK_OR_NOMEM(hipStreamSynchronize(st));
-  if (kernel_ms) HIP_OK_OR_NOMEM(hipEventElapsedTime(kernel_ms, r.ev0, r.ev1));
+  const float ms = column_pass(call, fn(compare_pairs_groups_kernel), dim3(n, kmax), dyn, l.off, need_len, out,
+                               [&](dim3 grid, const uint64_t *d_off, uint64_t *d_res) {
+                                 for (int e0 = 0; e0 < n; e0 += per_launch) {
+                                   const int ne = std::min(per_launch, n - e0);
+                                   hipLaunchKernelGGL(compare_pairs_groups_kernel, dim3(ne, grid.y), dim3(256), dyn, call.st,
+                                                      reinterpret_cast<const DevEvent *const *>(d_ptrs),
+                                                      reinterpret_cast<const unsigned char *const *>(d_ptrs) + nb, n1, n2, S, e0, ne, kmax,
+                                                      pa, as_text ? 1 : 0, d_off, d_res, d_work);
+                                   HIP_OK(hipGetLastError());
+                                 }
+                               });
+  if (kernel_ms) *kernel_ms = ms;
 }
 
 }  // namespace miso

@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "batch.hpp"
+#include "column_pass.hpp"
 #include "compare_column.hpp"
 #include "compare_pairs.hpp"
 #include "coop.hpp"
@@ -98,13 +99,11 @@ void miso_batch::release() {
   probe_armed = false;
   if (ev0) (void) hipEventDestroy(ev0);
   if (ev1) (void) hipEventDestroy(ev1);
-  if (pass_ev0) (void) hipEventDestroy(pass_ev0);
-  if (pass_ev1) (void) hipEventDestroy(pass_ev1);
   for (hipStream_t st : aux_streams) (void) hipStreamDestroy(st);
   for (hipEvent_t e : aux_done) (void) hipEventDestroy(e);
   aux_streams.clear(); aux_done.clear();
   if (stream) (void) hipStreamDestroy(stream);
-  d_events = nullptr; d_in = d_out = nullptr; d_fp = nullptr; ev0 = ev1 = pass_ev0 = pass_ev1 = nullptr; stream = nullptr;
+  d_events = nullptr; d_in = d_out = nullptr; d_fp = nullptr; ev0 = ev1 = nullptr; stream = nullptr;
   uploaded = launched = downloaded = false;
 }
 
@@ -1371,102 +1370,74 @@ void miso_batch::converge_rounds(float *ms) {
   last_kernels += "," + next->last_kernels;
 }
 
-// The kernel time of a reduction pass over the resident samples (miso_batch_pass_ms), on the batch's pass_ev0 / pass_ev1,
-// made by its first pass: ev0 / ev1 bracket the sampler kernels and sync() reads them later.
-namespace {
-struct PassTimer {
-  hipStream_t st;
-  hipEvent_t &a, &b;
-  PassTimer(hipStream_t s, hipEvent_t &e0, hipEvent_t &e1) : st(s), a(e0), b(e1) {
-    if (!a) HIP_OK(hipEventCreate(&a));
-    if (!b) HIP_OK(hipEventCreate(&b));
-    HIP_OK(hipEventRecord(a, st));
-  }
-  void stop() { HIP_OK(hipEventRecord(b, st)); }
-  float ms() {   // after the stream has been synchronised
-    float v = 0.f;
-    HIP_OK(hipEventElapsedTime(&v, a, b));
-    return v;
-  }
-};
-}  // namespace
+// The reduction passes over the resident samples, one workgroup per (event, isoform) column (column_pass.hpp).  Each makes its
+// results beside the stored ones and puts them in their place at the end, with the flag and the kernel time: a call that
+// fails frees what it held on the device (HipCall) and leaves what was there.
 
-// Posterior mean and Chen-Shao credible interval of every isoform, computed where the samples are
-// (credible_intervals.py:31-55: order statistics int(round(alpha/2 n)) - 1 and
-// int(round((1 - alpha/2) n)) - 1, Python-2 rounding = half away from zero).
+// Posterior mean and Chen-Shao credible interval of every isoform, computed where the samples are (the interval's order
+// statistics: column_pass.hpp ci_ranks).
 void miso_batch::summarize(double confidence_level, bool as_text) {
   if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  // stop = CONVERGENT_MEAN: the launch is only finished once sync() has run its further rounds; without them the pool holds
-  // the unconverged first round
-  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  finish_rounds(*this);
   HIP_OK(hipSetDevice(device));
   const int n = static_cast<int>(events.size()), Sn = S();
-  const double alpha = 1 - confidence_level;
-  const int lo = static_cast<int>(std::floor((alpha / 2) * Sn + 0.5)) - 1;
-  const int hi = static_cast<int>(std::floor((1 - alpha / 2) * Sn + 0.5)) - 1;
-  if (!(lo > 0 && hi > 0 && hi < Sn))   // the reference asserts both indices > 0
-    MISO_FAIL(MISO_EINVAL, "Too few samples for a credible interval");
-  h_sum_off.assign(n, 0);
-  uint64_t off = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) { h_sum_off[i] = off; off += 3 * events[i].K; kmax = std::max(kmax, events[i].K); }
-  h_summary.assign(off, 0.0);
-  if (n == 0) { summarized = true; return; }
-  uint64_t *d_off = nullptr; double *d_sum = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_sum), off * sizeof(double)));
-  HIP_OK(hipMemcpyAsync(d_off, h_sum_off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  PassTimer timer(stream, pass_ev0, pass_ev1);
-  hipLaunchKernelGGL(summarize_kernel, dim3(n, kmax), dim3(256), 0, stream, d_events, d_out, n, Sn, lo, hi,
-                     d_off, d_sum, as_text ? 1 : 0);
-  HIP_OK(hipGetLastError());
-  timer.stop();
-  HIP_OK(hipMemcpyAsync(h_summary.data(), d_sum, off * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_OK(hipStreamSynchronize(stream));
-  (void) hipFree(d_off); (void) hipFree(d_sum);
-  summarize_ms = timer.ms();
+  const CiRanks r = ci_ranks_strict(Sn, confidence_level);
+  const int lo = static_cast<int>(r.lo), hi = static_cast<int>(r.hi);
+  ColumnLayout l = column_layout(*this, 3);
+  std::vector<double> res(l.total, 0.0);
+  float ms = summarize_ms;
+  if (n > 0) {
+    HipCall call(stream);
+    ms = column_pass(call, fn(summarize_kernel), dim3(n, l.kmax), 0, l.off, res.size(), res.data(),
+                     [&](dim3 grid, const uint64_t *d_off, double *d_sum) {
+                       hipLaunchKernelGGL(summarize_kernel, grid, dim3(256), 0, call.st, d_events, d_out, n, Sn, lo, hi, d_off, d_sum,
+                                          as_text ? 1 : 0);
+                     });
+  }
+  h_summary.swap(res);
+  h_sum_off.swap(l.off);
+  summarize_ms = ms;
   summarized = true;
+}
+
+// the guards diagnose() and diagnose_rank() share; returns the chains the samples are split by
+static int diagnose_chains(const miso_batch &b, int noChains) {
+  if (!b.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+  if (noChains < 0) MISO_FAIL(MISO_EINVAL, "Invalid number of chains");
+  if (noChains == 0 && b.adopted) MISO_FAIL(MISO_EINVAL, "Adopted samples have no chain count of their own: give noChains");
+  const int C = noChains ? noChains : b.p.noChains;
+  if (b.S() / C / 2 < 4) MISO_FAIL(MISO_EINVAL, "Too few samples per chain for diagnostics");
+  return C;
 }
 
 // Chain diagnostics of every (event, isoform) column, computed where the samples are (kernels_diagnose.hip):
 // split R-hat, effective sample size, Monte-Carlo standard error of the mean and the lag at which Geyer's sequence was cut.
 // noChains = 0: the batch's own chains; an adopted batch has none to offer.
 void miso_batch::diagnose(int noChains) {
-  if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (noChains < 0) MISO_FAIL(MISO_EINVAL, "Invalid number of chains");
-  if (noChains == 0 && adopted) MISO_FAIL(MISO_EINVAL, "Adopted samples have no chain count of their own: give noChains");
-  const int C = noChains ? noChains : p.noChains;
-  const int Sn = S();
-  const int n_draws = Sn / C, h = n_draws / 2;
-  if (h < 4) MISO_FAIL(MISO_EINVAL, "Too few samples per chain for diagnostics");
+  const int C = diagnose_chains(*this, noChains);
+  const int n_draws = S() / C, h = n_draws / 2;
   // (the per-sequence scratch of a workgroup: three doubles per sequence in LDS)
   if (C > DIAG_MAX_CHAINS) MISO_FAIL(MISO_EINVAL, "Too many chains for diagnostics");
-  // as summarize(): under CONVERGENT_MEAN the launch is finished once sync() has run its further rounds
-  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  finish_rounds(*this);
   HIP_OK(hipSetDevice(device));
   const int n = static_cast<int>(events.size());
   const int M = 2 * C, N = M * h;
-  h_diag_off.assign(n, 0);
-  uint64_t off = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) { h_diag_off[i] = off; off += 4 * events[i].K; kmax = std::max(kmax, events[i].K); }
-  h_diag.assign(off, 0.0);
-  if (n == 0) { diagnosed = true; return; }
-  const bool cached = N <= 256 * miso::SUMMARY_CACHE;
-  const size_t dyn = (static_cast<size_t>(cached ? N : 0) + 3 * static_cast<size_t>(M)) * sizeof(double);
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(diagnose_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(dyn)));
-  uint64_t *d_off = nullptr; double *d_diag = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_diag), off * sizeof(double)));
-  HIP_OK(hipMemcpyAsync(d_off, h_diag_off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  PassTimer timer(stream, pass_ev0, pass_ev1);
-  hipLaunchKernelGGL(diagnose_kernel, dim3(n, kmax), dim3(256), dyn, stream, d_events, d_out, n, C, n_draws, h,
-                     std::log10(static_cast<double>(N)), cached ? 1 : 0, d_off, d_diag);
-  HIP_OK(hipGetLastError());
-  timer.stop();
-  HIP_OK(hipMemcpyAsync(h_diag.data(), d_diag, off * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_OK(hipStreamSynchronize(stream));
-  (void) hipFree(d_off); (void) hipFree(d_diag);
-  diagnose_ms = timer.ms();
+  ColumnLayout l = column_layout(*this, 4);
+  std::vector<double> res(l.total, 0.0);
+  float ms = diagnose_ms;
+  if (n > 0) {
+    const bool cached = N <= 256 * miso::SUMMARY_CACHE;
+    const size_t dyn = (static_cast<size_t>(cached ? N : 0) + 3 * static_cast<size_t>(M)) * sizeof(double);
+    HipCall call(stream);
+    ms = column_pass(call, fn(diagnose_kernel), dim3(n, l.kmax), dyn, l.off, res.size(), res.data(),
+                     [&](dim3 grid, const uint64_t *d_off, double *d_diag) {
+                       hipLaunchKernelGGL(diagnose_kernel, grid, dim3(256), dyn, call.st, d_events, d_out, n, C, n_draws, h,
+                                          std::log10(static_cast<double>(N)), cached ? 1 : 0, d_off, d_diag);
+                     });
+  }
+  h_diag.swap(res);
+  h_diag_off.swap(l.off);
+  diagnose_ms = ms;
   diagnosed = true;
 }
 
@@ -1474,162 +1445,106 @@ void miso_batch::diagnose(int noChains) {
 // folded split R-hat, bulk effective sample size, and the effective sample size of the indicators of the two bounds of
 // the `confidence_level` interval, taken as summarize() takes them but over the N used draws.  Preconditions as diagnose().
 void miso_batch::diagnose_rank(int noChains, double confidence_level) {
-  if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (noChains < 0) MISO_FAIL(MISO_EINVAL, "Invalid number of chains");
-  if (noChains == 0 && adopted) MISO_FAIL(MISO_EINVAL, "Adopted samples have no chain count of their own: give noChains");
-  const int C = noChains ? noChains : p.noChains;
-  const int Sn = S();
-  const int n_draws = Sn / C, h = n_draws / 2;
-  if (h < 4) MISO_FAIL(MISO_EINVAL, "Too few samples per chain for diagnostics");
+  const int C = diagnose_chains(*this, noChains);
+  const int n_draws = S() / C, h = n_draws / 2;
   // (in 64 bits: C is the caller's)
   const int64_t M64 = 2 * static_cast<int64_t>(C), N64 = M64 * h;
-  const double alpha = 1 - confidence_level;
-  const double lo_d = std::floor((alpha / 2) * static_cast<double>(N64) + 0.5) - 1;
-  const double hi_d = std::floor((1 - alpha / 2) * static_cast<double>(N64) + 0.5) - 1;
-  if (!(lo_d > 0 && hi_d > 0 && hi_d < static_cast<double>(N64)))
-    MISO_FAIL(MISO_EINVAL, "Too few samples for a credible interval");
+  const CiRanks r = ci_ranks_strict(static_cast<double>(N64), confidence_level);
   if (N64 > RANK_MAX_DRAWS) MISO_FAIL(MISO_EINVAL, "Too many samples for rank diagnostics");
   if (C > RANK_MAX_CHAINS) MISO_FAIL(MISO_EINVAL, "Too many chains for rank diagnostics");
   const int M = static_cast<int>(M64), N = static_cast<int>(N64);
-  const int lo = static_cast<int>(lo_d), hi = static_cast<int>(hi_d);
-  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  const int lo = static_cast<int>(r.lo), hi = static_cast<int>(r.hi);
+  finish_rounds(*this);
   HIP_OK(hipSetDevice(device));
   const int n = static_cast<int>(events.size());
-  h_rank_off.assign(n, 0);
-  uint64_t off = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) { h_rank_off[i] = off; off += 6 * events[i].K; kmax = std::max(kmax, events[i].K); }
-  h_rank.assign(off, 0.0);
-  if (n == 0) { rank_diagnosed = true; return; }
-  int P = 8;                                          // the sort's size: the power of two >= N
-  while (P < N) P <<= 1;
-  // the draws, the sort's keys, then the larger of the per-sequence scratch and the 16-bit ranks
-  const size_t dyn = (static_cast<size_t>(N) + P + std::max<size_t>(3 * static_cast<size_t>(M), (static_cast<size_t>(N) + 3) / 4)) * sizeof(double);
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(diagnose_rank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(dyn)));
-  uint64_t *d_off = nullptr; double *d_rank = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_rank), off * sizeof(double)));
-  HIP_OK(hipMemcpyAsync(d_off, h_rank_off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  PassTimer timer(stream, pass_ev0, pass_ev1);
-  hipLaunchKernelGGL(diagnose_rank_kernel, dim3(n, kmax), dim3(256), dyn, stream, d_events, d_out, n, C, n_draws, h, P, lo, hi,
-                     std::log10(static_cast<double>(N)), d_off, d_rank);
-  HIP_OK(hipGetLastError());
-  timer.stop();
-  HIP_OK(hipMemcpyAsync(h_rank.data(), d_rank, off * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_OK(hipStreamSynchronize(stream));
-  (void) hipFree(d_off); (void) hipFree(d_rank);
-  rank_ms = timer.ms();
+  ColumnLayout l = column_layout(*this, 6);
+  std::vector<double> res(l.total, 0.0);
+  float ms = rank_ms;
+  if (n > 0) {
+    int P = 8;                                          // the sort's size: the power of two >= N
+    while (P < N) P <<= 1;
+    // the draws, the sort's keys, then the larger of the per-sequence scratch and the 16-bit ranks
+    const size_t dyn = (static_cast<size_t>(N) + P + std::max<size_t>(3 * static_cast<size_t>(M), (static_cast<size_t>(N) + 3) / 4)) * sizeof(double);
+    HipCall call(stream);
+    ms = column_pass(call, fn(diagnose_rank_kernel), dim3(n, l.kmax), dyn, l.off, res.size(), res.data(),
+                     [&](dim3 grid, const uint64_t *d_off, double *d_rank) {
+                       hipLaunchKernelGGL(diagnose_rank_kernel, grid, dim3(256), dyn, call.st, d_events, d_out, n, C, n_draws, h, P, lo,
+                                          hi, std::log10(static_cast<double>(N)), d_off, d_rank);
+                     });
+  }
+  h_rank.swap(res);
+  h_rank_off.swap(l.off);
+  rank_ms = ms;
   rank_diagnosed = true;
 }
 
 // Two-sample comparison of this batch (sample 1) with `other` (sample 2), event by event and
 // index-paired (hypothesis_test.py:89-179): both must hold the same events in the same order.
 void miso_batch::compare(miso_batch &other, double smoothing) {
-  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
-  if (events.size() != other.events.size() || S() != other.S())
-    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
+  same_events(*this, other, true);
   if (!(smoothing > 0)) MISO_FAIL(MISO_EINVAL, "Invalid smoothing parameter");
   const int n = static_cast<int>(events.size()), Sn = S();
   if (Sn < 2) MISO_FAIL(MISO_EINVAL, "Too few samples to compare");
-  std::vector<uint64_t> off(n);
-  uint64_t tot = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) {
-    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
-    off[i] = tot; tot += 4 * events[i].K; kmax = std::max(kmax, events[i].K);
+  finish_rounds(*this);
+  finish_rounds(other);
+  ColumnLayout l = column_layout(*this, 4);
+  std::vector<double> res(l.total, 0.0);
+  float ms = compare_ms;
+  if (n > 0) {
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipStreamSynchronize(other.stream));
+    HipCall call(stream);
+    ms = column_pass(call, fn(compare_kernel), dim3(n, l.kmax), 0, l.off, res.size(), res.data(),
+                     [&](dim3 grid, const uint64_t *d_off, double *d_cmp) {
+                       hipLaunchKernelGGL(compare_kernel, grid, dim3(256), 0, call.st, d_events, d_out, other.d_events, other.d_out, n,
+                                          Sn, smoothing, d_off, d_cmp);
+                     });
   }
-  h_compare.assign(tot, 0.0);
-  if (n == 0) { compared = true; return; }
-  HIP_OK(hipSetDevice(device));
-  HIP_OK(hipStreamSynchronize(other.stream));
-  uint64_t *d_off = nullptr; double *d_cmp = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off), n * sizeof(uint64_t)));
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_cmp), tot * sizeof(double)));
-  HIP_OK(hipMemcpyAsync(d_off, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  PassTimer timer(stream, pass_ev0, pass_ev1);
-  hipLaunchKernelGGL(compare_kernel, dim3(n, kmax), dim3(256), 0, stream, d_events, d_out, other.d_events,
-                     other.d_out, n, Sn, smoothing, d_off, d_cmp);
-  HIP_OK(hipGetLastError());
-  timer.stop();
-  HIP_OK(hipMemcpyAsync(h_compare.data(), d_cmp, tot * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_OK(hipStreamSynchronize(stream));
-  (void) hipFree(d_off); (void) hipFree(d_cmp);
-  compare_ms = timer.ms();
+  h_compare.swap(res);
+  h_cmp_off.swap(l.off);
+  compare_ms = ms;
   compared = true;
 }
 
 // The posterior of delta psi over ALL S1 * S2 pairs of this batch's draws (sample 1) and `other`'s (sample 2), event by event
 // (kernels_compare_pairs.hip): the lower median and the bounds of the `confidence_level` interval of the
-// differences -- ranks as summarize() takes them but over S1 * S2, the lower one clamped at 0 --, the exact counts of the
-// differences above and below 0 and, per threshold, of those at least that far from 0.  The batches hold the same events
-// in the same order; their sample counts may differ.  The results stand beside compare()'s.  as_text: of the draws as the
-// `.miso` files print them ("%.4f"), as summarize()'s.
+// differences -- ranks as summarize() takes them but over S1 * S2, clamped --, the exact counts of the differences above and
+// below 0 and, per threshold, of those at least that far from 0.  The batches hold the same events in the same order; their
+// sample counts may differ.  The results stand beside compare()'s.  as_text: of the draws as the `.miso` files print them
+// ("%.4f"), as summarize()'s.
 void miso_batch::compare_pairs(miso_batch &other, double confidence_level, const double *tau, int n_tau, bool as_text) {
-  if (!launched || !other.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (device != other.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
-  if (events.size() != other.events.size()) MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events");
-  if (!(confidence_level > 0 && confidence_level < 1)) MISO_FAIL(MISO_EINVAL, "Invalid confidence level: it must lie inside (0, 1)");
-  if (n_tau < 0 || n_tau > PAIRS_MAX_TAU) MISO_FAIL(MISO_EINVAL, "Invalid number of delta psi thresholds: 0 to 4");
-  for (int j = 0; j < n_tau; j++)
-    if (!(tau[j] > 0 && tau[j] < 1)) MISO_FAIL(MISO_EINVAL, "Invalid delta psi threshold: it must lie inside (0, 1)");
+  same_events(*this, other, false);
   const int n = static_cast<int>(events.size()), S1 = S(), S2 = other.S();
   if (S1 < 1 || S2 < 1) MISO_FAIL(MISO_EINVAL, "Too few samples to compare");
   if (S1 > PAIRS_MAX_DRAWS || S2 > PAIRS_MAX_DRAWS)
     MISO_FAIL(MISO_EINVAL, "Too many samples for the all-pairs comparison: 8192 per event and sample at most");
-  std::vector<uint64_t> off(n);
-  uint64_t cols = 0; int kmax = 1;
-  for (int i = 0; i < n; i++) {
-    if (events[i].K != other.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
-    off[i] = cols; cols += events[i].K; kmax = std::max(kmax, events[i].K);
-  }
-  // the ranks in double, as summarize()'s: M <= 2^26, every product and sum below is far from 2^53
   const int64_t M = static_cast<int64_t>(S1) * S2;
-  const double alpha = 1 - confidence_level;
-  const double lo_d = std::max(0.0, std::floor((alpha / 2) * static_cast<double>(M) + 0.5) - 1);
-  const double hi_d = std::min(static_cast<double>(M - 1), std::max(lo_d, std::floor((1 - alpha / 2) * static_cast<double>(M) + 0.5) - 1));
-  PairsArgs pa{};
-  pa.rank[0] = static_cast<uint32_t>((M - 1) / 2);
-  pa.rank[1] = static_cast<uint32_t>(lo_d);
-  pa.rank[2] = static_cast<uint32_t>(hi_d);
-  pa.n_tau = n_tau;
-  for (int j = 0; j < n_tau; j++) pa.tau[j] = tau[j];
-  // as summarize(): under CONVERGENT_MEAN a launch is finished once sync() has run its further rounds
-  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
-  if (other.p.stop == MISO_STOP_CONVERGENT_MEAN && !other.converged_done) other.sync(nullptr);
+  const PairsArgs pa = pairs_args(M, confidence_level, tau, n_tau);
+  finish_rounds(*this);
+  finish_rounds(other);
   const size_t W = static_cast<size_t>(pairs_words(n_tau));
+  ColumnLayout l = column_layout(*this, 1);
   // an event whose sample text was not decoded in either batch (adopt_text): the kernel does not touch its columns, they
   // come back not finite -- the top bit of the event's column offset says so
-  std::vector<uint64_t> off_flagged(off);
+  std::vector<uint64_t> off_flagged(l.off);
   for (int i = 0; i < n; i++)
     if (event_unread(i) || other.event_unread(i)) off_flagged[i] |= PAIRS_SKIP_EVENT;
-  // the results are made beside the stored ones and take their place at the end: a call that fails leaves what was there
-  std::vector<uint64_t> res(cols * W, 0);
+  std::vector<uint64_t> res(l.total * W, 0);
   float ms = 0.f;
   if (n > 0) {
     HIP_OK(hipSetDevice(device));
     HIP_OK(hipStreamSynchronize(other.stream));
     const size_t dyn = (static_cast<size_t>(S1) + S2) * sizeof(uint64_t);   // both columns: what is live, not the limit
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(compare_pairs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(dyn)));
-    struct DeviceWords {               // freed however the block is left
-      uint64_t *d = nullptr;
-      ~DeviceWords() { if (d) (void) hipFree(d); }
-    } d_off, d_res;
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_off.d), n * sizeof(uint64_t)));
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_res.d), cols * W * sizeof(uint64_t)));
-    HIP_OK(hipMemcpyAsync(d_off.d, off_flagged.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    PassTimer timer(stream, pass_ev0, pass_ev1);
-    hipLaunchKernelGGL(compare_pairs_kernel, dim3(n, kmax), dim3(256), dyn, stream, d_events, d_out, S1, other.d_events, other.d_out,
-                       S2, n, pa, as_text ? 1 : 0, d_off.d, d_res.d);
-    HIP_OK(hipGetLastError());
-    timer.stop();
-    HIP_OK(hipMemcpyAsync(res.data(), d_res.d, cols * W * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    ms = timer.ms();
+    HipCall call(stream);
+    ms = column_pass(call, fn(compare_pairs_kernel), dim3(n, l.kmax), dyn, off_flagged, res.size(), res.data(),
+                     [&](dim3 grid, const uint64_t *d_off, uint64_t *d_res) {
+                       hipLaunchKernelGGL(compare_pairs_kernel, grid, dim3(256), dyn, call.st, d_events, d_out, S1, other.d_events,
+                                          other.d_out, S2, n, pa, as_text ? 1 : 0, d_off, d_res);
+                     });
     if (last_kernels.find("compare_pairs") == std::string::npos) note_kernel("compare_pairs");   // (once, however often it is called)
   }
   h_pairs.swap(res);
-  h_pairs_off.swap(off);
+  h_pairs_off.swap(l.off);
   pairs_ntau = n_tau;
   pairs_M = M;
   pairs_ms = ms;
@@ -1657,19 +1572,30 @@ static ExactPairedCmpInput exact_paired_resident(const miso_batch &b, const doub
 
 // the guards of every exact pass over the pairs of batch a (sample 1) and batch b (sample 2)
 static void exact_pair_guards(const miso_batch &a, const miso_batch &b, bool mode_ok, const char *mode_msg) {
-  if (!a.launched || !b.launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  if (a.device != b.device) MISO_FAIL(MISO_EINVAL, "Batches to compare live on different devices");
-  if (a.events.size() != b.events.size() || a.S() != b.S())
-    MISO_FAIL(MISO_EINVAL, "Batches to compare differ in events or samples per event");
+  same_events(a, b, true);
   if (!mode_ok) MISO_FAIL(MISO_EINVAL, mode_msg);
 }
-static void exact_pair_same_isoforms(const miso_batch &a, const miso_batch &b) {
-  for (size_t i = 0; i < a.events.size(); i++)
-    if (a.events[i].K != b.events[i].K) MISO_FAIL(MISO_EINVAL, "Events to compare differ in isoforms");
+
+// The pairs of an exact pass: the events `take` admits, in order, and their rows of `row_w` statistics from `gather`, batch
+// a's in s1 and batch b's in s2.
+struct ExactPairs {
+  std::vector<int32_t> list;
+  std::vector<double> s1, s2;
+};
+template <class Take, class Gather>
+static ExactPairs exact_pairs(const miso_batch &a, const miso_batch &b, int row_w, Take take, Gather gather) {
+  ExactPairs x;
+  for (int i = 0; i < static_cast<int>(a.events.size()); i++) {
+    if (!take(i)) continue;
+    x.list.push_back(i);
+    x.s1.resize(x.s1.size() + row_w); x.s2.resize(x.s2.size() + row_w);
+    gather(a, i, &x.s1[x.s1.size() - row_w]); gather(b, i, &x.s2[x.s2.size() - row_w]);
+  }
+  return x;
 }
 
-// What the two exact comparisons of batch a (sample 1) with batch b (sample 2) share: the guards, the list of the events both
-// batches' exact mode took and that are `comparable`, their rows of `row_w` statistics from `gather`, the call of `run` (which
+// What the two exact comparisons of batch a (sample 1) with batch b (sample 2) share: the guards, the pairs (exact_pairs) of the
+// events both batches' exact mode took and that are `comparable`, the call of `run` (which
 // validates z, and fails with MISO_ENODEVICE without a device, also when no event is comparable), and the scatter of its rows
 // into a's h_exact_cmp / exact_cmp_ok; every other event is marked not comparable.
 template <class Comparable, class Gather, class Run>
@@ -1678,22 +1604,15 @@ static void compare_exact_with(miso_batch &a, miso_batch &b, const double *z, in
   exact_pair_guards(a, b, mode_ok, mode_msg);
   exact_check_z(z, n_z);
   const int n = static_cast<int>(a.events.size());
-  exact_pair_same_isoforms(a, b);
-  std::vector<int32_t> list;
-  std::vector<double> s1, s2;
   a.exact_cmp_ok.assign(n, 0);
   a.exact_delta_done = false;   // (the quantiles of delta psi belong to the comparison this one replaces)
-  for (int i = 0; i < n; i++) {
-    if (!a.event_exact(i) || !b.event_exact(i) || !comparable(i)) continue;
-    list.push_back(i);
-    s1.resize(s1.size() + row_w); s2.resize(s2.size() + row_w);
-    gather(a, i, &s1[s1.size() - row_w]); gather(b, i, &s2[s2.size() - row_w]);
-  }
+  const ExactPairs x = exact_pairs(a, b, row_w, [&](int i) { return a.event_exact(i) && b.event_exact(i) && comparable(i); }, gather);
+  const std::vector<int32_t> &list = x.list;
   const size_t w = 5 + static_cast<size_t>(n_z);
   std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
   HIP_OK(hipSetDevice(a.device));
   HIP_OK(hipStreamSynchronize(b.stream));
-  run(s1.data(), s2.data(), list, got.data());
+  run(x.s1.data(), x.s2.data(), list, got.data());
   a.h_exact_cmp.assign(static_cast<size_t>(n) * w, 0.0);
   for (size_t j = 0; j < list.size(); j++) {
     std::memcpy(&a.h_exact_cmp[list[j] * w], &got[j * w], w * sizeof(double));
@@ -1742,19 +1661,16 @@ void miso_batch::exact_delta_quantiles(miso_batch &other, const double *prob, in
   else exact_pair_guards(*this, other, exact_single_ok(*this, other), EXACT_SINGLE_MSG);
   if (!exact_compared) MISO_FAIL(MISO_EINVAL, "miso_batch_compare_exact / miso_batch_compare_exact_paired has not run");
   exact_delta_check_p(prob, n_p);
-  exact_pair_same_isoforms(*this, other);
-  const int n = static_cast<int>(events.size()), row_w = paired ? 6 : 7;
-  std::vector<int32_t> list;
-  std::vector<double> s1, s2;
-  for (int i = 0; i < n; i++) {
-    if (!exact_cmp_ok[i]) continue;
-    if (!other.event_exact(i)) MISO_FAIL(MISO_EINVAL, "The second batch is not the one the stored exact comparison was made with");
-    list.push_back(i);
-    s1.resize(s1.size() + row_w); s2.resize(s2.size() + row_w);
-    double *r1 = &s1[s1.size() - row_w], *r2 = &s2[s2.size() - row_w];
-    if (paired) { exact_paired_stats6(*this, i, r1); exact_paired_stats6(other, i, r2); }
-    else { exact_stats7(i, r1); other.exact_stats7(i, r2); }
-  }
+  const int n = static_cast<int>(events.size());
+  const ExactPairs x = exact_pairs(
+      *this, other, paired ? 6 : 7,
+      [&](int i) {
+        if (!exact_cmp_ok[i]) return false;
+        if (!other.event_exact(i)) MISO_FAIL(MISO_EINVAL, "The second batch is not the one the stored exact comparison was made with");
+        return true;
+      },
+      [&](const miso_batch &b, int i, double *row) { if (paired) exact_paired_stats6(b, i, row); else b.exact_stats7(i, row); });
+  const std::vector<int32_t> &list = x.list;
   const size_t w = static_cast<size_t>(n_p) + 1;
   const int m = static_cast<int>(list.size());
   std::vector<double> got(std::max<size_t>(list.size(), 1) * w);
@@ -1762,10 +1678,10 @@ void miso_batch::exact_delta_quantiles(miso_batch &other, const double *prob, in
   HIP_OK(hipStreamSynchronize(other.stream));
   float ms = 0.f;
   if (paired)
-    exact_paired_delta_run(exact_paired_resident(*this, s1.data()), exact_paired_resident(other, s2.data()), list.data(), m, prob, n_p,
-                           got.data(), stream, &ms);
+    exact_paired_delta_run(exact_paired_resident(*this, x.s1.data()), exact_paired_resident(other, x.s2.data()), list.data(), m, prob,
+                           n_p, got.data(), stream, &ms);
   else
-    exact_delta_run(s1.data(), s2.data(), m, prob, n_p, got.data(), stream, &ms);
+    exact_delta_run(x.s1.data(), x.s2.data(), m, prob, n_p, got.data(), stream, &ms);
   std::vector<double> res(static_cast<size_t>(n) * w, 0.0);
   for (size_t j = 0; j < list.size(); j++) std::memcpy(&res[list[j] * w], &got[j * w], w * sizeof(double));
   h_exact_delta.swap(res);
@@ -1819,9 +1735,7 @@ void miso_batch::adopt_pool(int n, const int *K, int Sn, int dev) {
 
 void miso_batch::download() {
   if (!launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
-  // stop = CONVERGENT_MEAN: the launch is only finished once sync() has run its further rounds; without them the pool holds
-  // the unconverged first round
-  if (p.stop == MISO_STOP_CONVERGENT_MEAN && !converged_done) sync(nullptr);
+  finish_rounds(*this);
   HIP_OK(hipSetDevice(device));
   h_out.resize(out_bytes);
   HIP_OK(hipMemcpy(h_out.data(), d_out, out_bytes, hipMemcpyDeviceToHost));

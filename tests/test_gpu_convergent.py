@@ -73,11 +73,9 @@ def test_one_round_when_the_schedule_is_already_at_max_iterations(orc):
     assert b.rounds() == 1
 
 
-@pytest.mark.parametrize("paired", [False, True])
-def test_batch_where_some_events_converge_and_some_do_not(orc, paired):
-    """Twelve events of 2..6 isoforms in one batch, short and long enough schedules mixed by event size: every event
-    equals the checker's run of it alone (its random stream is addressed by its id, not by the round's batch), the
-    summaries are those of the returned samples, and a second launch of the same batch repeats the rounds."""
+def _mixed_batch(orc, paired):
+    """The batch of test_batch_where_some_events_converge_and_some_do_not, filled but not yet on the device: (batch, its
+    events as the checker takes them, the schedule); it runs with seed 5 and first event id 1000."""
     rng = np.random.default_rng(3)
     iters, burn, lag, chains, max_iters = 200, 50, 2, 3, 3000
     kw = dict(iters=iters, burn=burn, lag=lag, chains=chains, stop=1, max_iters=max_iters)
@@ -99,6 +97,15 @@ def test_batch_where_some_events_converge_and_some_do_not(orc, paired):
         assert rc == 0
         b.add_event(miso_amd.Gene(exons, isoforms), pos, cig)
         cases.append((og, pos, cig))
+    return b, cases, kw
+
+
+@pytest.mark.parametrize("paired", [False, True])
+def test_batch_where_some_events_converge_and_some_do_not(orc, paired):
+    """Twelve events of 2..6 isoforms in one batch, short and long enough schedules mixed by event size: every event
+    equals the checker's run of it alone (its random stream is addressed by its id, not by the round's batch), the
+    summaries are those of the returned samples, and a second launch of the same batch repeats the rounds."""
+    b, cases, kw = _mixed_batch(orc, paired)
     b.run(seed=5, first_event_id=1000)
     rounds = b.rounds()
     assert rounds > 1
