@@ -446,6 +446,34 @@ int miso_batch_get_exact_delta_quantiles(const miso_batch_t *sample1, int event_
                                          double *cdf_at_0, int *was_exact);
 int miso_batch_exact_delta_ms(const miso_batch_t *sample1, float *ms);
 
+/* The same quantiles between two GROUPS of replicates, pooled, from the exact posteriors and without a draw
+   (csrc/kernels_exact_delta_groups.hip).  Single-end two-isoform events only.  The law of "psi of a
+   replicate of group 1 minus psi of a replicate of group 2", equal weights, is the mixture of the n1 * n2 pairwise laws:
+   H(z) = (sum_a sum_b H_ab(z)) / (double) (n1 * n2), summed from 0.0 with a outer and b inner, H_ab being
+   miso_batch_exact_delta_quantiles' CDF of the pair (a, b) bit for bit; the search is that function's on this H.
+   miso_exact_delta_groups works on caller-given statistics: stats7_g holds n_events * n_g rows {n10, n01, n, e0, e1, h0, h1},
+   [event][replicate][7], 1 <= n1, n2 <= 8; p: 1 <= n_p <= 4 probabilities inside (0, 1); z: 0 <= n_z <= 8 points inside
+   (-1, 1); MISO_EINVAL otherwise, MISO_ENODEVICE without a device, in either case before anything is allocated.  An event is
+   comparable when every one of its rows is eligible for the exact mode and all carry bit-equal (e0, e1): it gets
+   was_exact[event] = 1 and the row out[event * (2 + n_p + 1 + n_z)] = {m1, m2, q[0 .. n_p), H(0.0), H(z[0 .. n_z))}, m_g the
+   mean over the group's replicates of their posterior means of psi.  Any other event gets was_exact = 0 and its row is left
+   untouched; that is no error.  A call is split into launches over event ranges so that what it holds on the device stays
+   within 256 MiB; max_events_per_launch > 0 lowers the range further, 0 derives it.  kernel_ms (may be NULL): the HIP-event
+   time of the launches.
+   miso_batch_get_exact_stats: the seven statistics of an event of a launched single-end batch as the functions above take
+   them; was_exact = 0 (and the statistics as they are) for an event the exact mode did not take and for every event of a
+   paired-end batch.
+   miso_batch_exact_delta_groups: the same pass over launched batches, preconditions as miso_batch_compare_pairs_groups (the
+   same events in the same order, one device); a paired-end batch or one that did not run with the exact mode is MISO_EINVAL
+   naming the group and the index of the batch.  The rows come from miso_batch_get_exact_stats; an event that some batch's
+   exact mode did not take is not comparable.  out_len: doubles available in out, n_events * (2 + n_p + 1 + n_z) at least;
+   was_exact: n_events ints.  Nothing is stored in any batch. */
+int miso_exact_delta_groups(const double *stats7_1, int n1, const double *stats7_2, int n2, int n_events, const double *p, int n_p,
+                            const double *z, int n_z, int max_events_per_launch, double *out, int *was_exact, float *kernel_ms);
+int miso_batch_get_exact_stats(const miso_batch_t *batch, int event_index, double *stats7, int *was_exact);
+int miso_batch_exact_delta_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, const double *p, int n_p,
+                                  const double *z, int n_z, double *out, int64_t out_len, int *was_exact, float *kernel_ms);
+
 /* The posterior of delta = psi_1 - psi_2 over ALL pairs of the two samples' draws (csrc/kernels_compare_pairs.hip, DESIGN.md
    section 19): the samples are independent posteriors, so given the draws the law of delta is the empirical law of the
    M = S1 * S2 differences, not of the index-paired ones.  Preconditions and errors as miso_batch_compare -- both launched

@@ -459,6 +459,15 @@ class Batch:
         check(lib().miso_batch_exact_delta_ms(self.handle, C.byref(a)))
         return float(a.value)
 
+    def exact_stats(self, i):
+        """(stats7, was_exact) of event i of a launched batch: (n10, n01, n, e0, e1, h0, h1), what the exact posterior of a
+        single-end two-isoform event is made of and exact_delta_groups takes; was_exact False for an event the exact mode did
+        not take and for every event of a paired-end batch (miso_batch_get_exact_stats)."""
+        r = np.zeros(7)
+        was = C.c_int(0)
+        check(lib().miso_batch_get_exact_stats(self.handle, int(i), _p(r), C.byref(was)))
+        return r, bool(was.value)
+
     def compare_pairs(self, other, confidence_level=0.95, thresholds=(0.1, 0.2), as_text=False):
         """The posterior of delta psi = psi_1 - psi_2 over ALL pairs of this batch's draws and `other`'s (same events, same
         order; the sample counts may differ, 8192 per event at most) on the device: median, credible interval and exact
@@ -843,6 +852,69 @@ def compare_pairs_groups(batches1, batches2, confidence_level=0.95, thresholds=(
     check(L.miso_batch_compare_pairs_groups(h1, len(b1), h2, len(b2), C.c_double(confidence_level), _p(tt), C.c_int(len(tt)),
                                             C.c_int(1 if as_text else 0), _p(out), out.size, C.byref(M), C.byref(ms)))
     return GroupPairComparison(out, noiso, len(tt), int(M.value), float(ms.value))
+
+
+class ExactGroupDelta:
+    """What exact_delta_groups / exact_delta_groups_batches computed: `out` [n_events, 2 + n_p + 1 + n_z] (a row the device did
+    not write stays NaN), `was_exact` [n_events], `kernel_ms` the launches' time."""
+
+    def __init__(self, out, was_exact, n_p, n_z, kernel_ms):
+        self.out, self.was_exact, self.n_p, self.n_z, self.kernel_ms = out, was_exact, n_p, n_z, kernel_ms
+
+    def row(self, event):
+        """(mean1, mean2, quantiles[n_p], cdf_at_0, cdf[n_z]) of `event`: the groups' mean posterior means, the quantiles of
+        psi_1 - psi_2 pooled over all pairs of replicates, P(delta <= 0) and P(delta <= z); None when the event is not
+        comparable."""
+        if not 0 <= event < len(self.was_exact):
+            raise IndexError("event %d of %d" % (event, len(self.was_exact)))
+        if not self.was_exact[event]:
+            return None
+        r = self.out[event]
+        return float(r[0]), float(r[1]), r[2:2 + self.n_p].copy(), float(r[2 + self.n_p]), r[3 + self.n_p:].copy()
+
+
+def _exact_group_args(probs, z, n_events):
+    pp = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+    out = np.full((n_events, 2 + len(pp) + 1 + len(zz)), np.nan)
+    return pp, zz, out, np.zeros(n_events, np.int32)
+
+
+def exact_delta_groups(stats1, stats2, probs=(0.5, 0.025, 0.975), z=(), max_events_per_launch=0):
+    """Quantiles of delta psi between two groups of replicates from their exact posteriors, pooled over all pairs of
+    replicates with equal weights, on the device and without a draw (miso_exact_delta_groups in include/miso_amd.h, DESIGN.md
+    20a).  stats_g: [n_events, n_g, 7] rows (n10, n01, n, e0, e1, h0, h1), 1 <= n_g <= 8 -- what Batch.exact_stats returns and
+    a `.miso_exact_stats` table holds.  probs: at most 4, inside (0, 1); z: at most 8 points inside (-1, 1)."""
+    s1 = np.ascontiguousarray(stats1, dtype=np.float64)
+    s2 = np.ascontiguousarray(stats2, dtype=np.float64)
+    if s1.ndim != 3 or s2.ndim != 3 or s1.shape[2] != 7 or s2.shape[2] != 7 or s1.shape[0] != s2.shape[0]:
+        raise ValueError("stats1, stats2: [n_events, n_replicates, 7] each, with as many events")
+    n = s1.shape[0]
+    pp, zz, out, was = _exact_group_args(probs, z, n)
+    ms = C.c_float(0.0)
+    L = lib()
+    L.miso_exact_delta_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    check(L.miso_exact_delta_groups(_p(s1), s1.shape[1], _p(s2), s2.shape[1], n, _p(pp), len(pp), _p(zz), len(zz),
+                                    int(max_events_per_launch), _p(out), _p(was), C.byref(ms)))
+    return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
+
+
+def exact_delta_groups_batches(batches1, batches2, probs=(0.5, 0.025, 0.975), z=()):
+    """exact_delta_groups over launched single-end Batch(exact=True) objects that hold the same events in the same order on
+    one device (miso_batch_exact_delta_groups): the rows are the batches' exact_stats.  Nothing is stored in a batch."""
+    b1, b2 = list(batches1), list(batches2)
+    n = len(b1[0]) if b1 else (len(b2[0]) if b2 else 0)
+    pp, zz, out, was = _exact_group_args(probs, z, n)
+    ms = C.c_float(0.0)
+    L = lib()
+    L.miso_batch_exact_delta_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+    h1 = (C.c_void_p * max(len(b1), 1))(*[b.handle for b in b1])
+    h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
+    check(L.miso_batch_exact_delta_groups(h1, len(b1), h2, len(b2), _p(pp), len(pp), _p(zz), len(zz), _p(out), out.size, _p(was),
+                                          C.byref(ms)))
+    return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
 
 
 # ---- `.miso` sample text (include/miso_amd.h miso_text_shape, miso_batch_from_miso_text) ----

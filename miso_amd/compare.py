@@ -255,3 +255,71 @@ def write_group_dpsi(filename, rows, thresholds):
             f.write(group_dpsi_line(*row, n_thresholds=len(thresholds)) + "\n")
             n += 1
     return n
+
+
+# ---- the pooled table from the exact posteriors, `<A>_vs_<B>.miso_group_dpsi_exact` beside it ----
+def group_dpsi_exact_header_fields(thresholds):
+    return (GROUP_DPSI_HEAD + ["exact"] + DPSI_FIELDS + ["prob_abs_diff_ge_%g" % t for t in thresholds] + GROUP_DPSI_TAIL)
+
+
+def group_dpsi_exact_line(event_name, n1, n2, result, header, thresholds):
+    """n1, n2: the replicates of either group that were pooled (that have the event with exact = 1).  result = (mean1, mean2,
+    quantiles at EXACT_DPSI_PROBS, H(0), cdf at delta_points(thresholds)) as capi.ExactGroupDelta.row returns it, or None (the
+    event is not comparable): the replicate counts, exact = 0 and NA.  Otherwise exact = 1, the means, the median and bounds as
+    %.4f, P(diff > 0) = 1 - H(0) and P(diff < 0) = H(0), and `.miso_bf_exact`'s P(|diff| >= t) = 1 - H(t) + H(-t).  header:
+    whatever of isoforms, chrom, strand, mRNA_starts, mRNA_ends the caller knows."""
+    f = [event_name, "%d" % n1, "%d" % n2]
+    if result is None:
+        f += ["NA"] * 3 + ["0"] + ["NA"] * (len(DPSI_FIELDS) + len(thresholds))
+    else:
+        m1, m2, q, h0, cdf = result
+        f += ["%.4f" % m1, "%.4f" % m2, "%.4f" % (m1 - m2), "1"]
+        f += ["%.4f" % q[0], "%.4f" % q[1], "%.4f" % q[2], "%.4f" % (1.0 - h0), "%.4f" % h0]
+        f += exact_prob_fields(cdf, thresholds)
+    f.append(header.get("isoforms", "NA"))
+    for key in ("chrom", "strand", "mRNA_starts", "mRNA_ends"):
+        f.append(header.get(key, "NA"))
+    return "\t".join(f)
+
+
+def write_group_dpsi_exact(filename, rows, thresholds):
+    """rows: iterable of (event_name, n1, n2, result, header) -- group_dpsi_exact_line's arguments."""
+    thresholds = check_delta_thresholds(thresholds)
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(group_dpsi_exact_header_fields(thresholds)) + "\n")
+        for row in rows:
+            f.write(group_dpsi_exact_line(*row, thresholds=thresholds) + "\n")
+            n += 1
+    return n
+
+
+# ---- the statistics an exact posterior is made of, `<sample>.miso_exact_stats` (DESIGN.md section 20a) ----
+EXACT_STATS_FIELDS = ["event_name", "exact", "n10", "n01", "n", "e0", "e1", "h0", "h1"]
+
+
+def write_exact_stats(filename, rows):
+    """rows: iterable of (event_name, was_exact, stats7).  The statistics are printed with repr, so that they read back to
+    the same doubles."""
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(EXACT_STATS_FIELDS) + "\n")
+        for name, was, st in rows:
+            f.write("\t".join([name, "1" if was else "0"] + [repr(float(v)) for v in st]) + "\n")
+            n += 1
+    return n
+
+
+def read_exact_stats(filename):
+    """{event_name: (was_exact, [7 floats])} of a `.miso_exact_stats` table, in the file's order"""
+    out = {}
+    with open(filename) as f:
+        head = f.readline().rstrip("\n").split("\t")
+        if head != EXACT_STATS_FIELDS:
+            raise ValueError("Error: %s is no .miso_exact_stats table" % filename)
+        for line in f:
+            v = line.rstrip("\n").split("\t")
+            if len(v) != len(EXACT_STATS_FIELDS):
+                raise ValueError("Error: %s: malformed line %r" % (filename, line))
+            out[v[0]] = (v[1] == "1", [float(x) for x in v[2:]])
+    return out

@@ -92,6 +92,15 @@ void exact_delta_run(const double *stats7_1, const double *stats7_2, int n, cons
                      hipStream_t st = nullptr, float *ms = nullptr);
 void exact_paired_delta_run(const ExactPairedCmpInput &in1, const ExactPairedCmpInput &in2, const int32_t *list, int n, const double *p,
                             int n_p, double *out, hipStream_t st = nullptr, float *ms = nullptr);
+// kernels_exact_delta_groups.hip: the same quantiles between two groups of replicates, from the equal-weight mixture of the
+// n1 n2 pairwise CDFs (miso_exact_delta_groups, miso_batch_exact_delta_groups).  Rows [event][replicate][7];
+// take (may be null): per event, 0 = not to be compared; out: 2 + n_p + 1 + n_z doubles per event (m1, m2, q, H(0.0), H(z)),
+// untouched and was_exact = 0 where the event is not comparable
+void exact_delta_groups_run(const double *stats7_1, int n1, const double *stats7_2, int n2, int n_events, const unsigned char *take,
+                            const double *p, int n_p, const double *z, int n_z, int max_events_per_launch, double *out,
+                            int *was_exact, float *ms, hipStream_t st = nullptr);
+void exact_delta_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, const double *p, int n_p, const double *z, int n_z,
+                        double *out, int64_t out_len, int *was_exact, float *kernel_ms);
 // kernels_compare_groups.hip
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,

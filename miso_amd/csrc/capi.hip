@@ -947,6 +947,37 @@ int miso_batch_exact_delta_ms(const miso_batch_t *b, float *ms) {
   });
 }
 
+int miso_exact_delta_groups(const double *stats7_1, int n1, const double *stats7_2, int n2, int n_events, const double *p, int n_p,
+                            const double *z, int n_z, int max_events_per_launch, double *out, int *was_exact, float *kernel_ms) {
+  return guarded([&] {
+    if (n_events > 0) { need(stats7_1, "stats7_1"); need(stats7_2, "stats7_2"); need(out, "out"); need(was_exact, "was_exact"); }
+    if (n_p > 0) need(p, "p");
+    if (n_z > 0) need(z, "z");
+    exact_delta_groups_run(stats7_1, n1, stats7_2, n2, n_events, nullptr, p, n_p, z, n_z, max_events_per_launch, out, was_exact, kernel_ms);
+  });
+}
+
+int miso_batch_get_exact_stats(const miso_batch_t *b, int i, double *stats7, int *was_exact) {
+  return guarded([&] {
+    need(b, "batch"); need(stats7, "stats7"); need(was_exact, "was_exact");
+    (void) event_at(b, i);
+    if (!b->launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+    b->exact_stats7(i, stats7);
+    *was_exact = !b->p.paired && b->event_exact(i) ? 1 : 0;
+  });
+}
+
+int miso_batch_exact_delta_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, const double *p, int n_p,
+                                  const double *z, int n_z, double *out, int64_t out_len, int *was_exact, float *kernel_ms) {
+  return guarded([&] {
+    need(group1, "group1"); need(group2, "group2"); need(was_exact, "was_exact");
+    if (n_p > 0) need(p, "p");
+    if (n_z > 0) need(z, "z");
+    if (out_len > 0) need(out, "out");
+    exact_delta_groups(group1, n1, group2, n2, p, n_p, z, n_z, out, out_len, was_exact, kernel_ms);
+  });
+}
+
 int miso_batch_compare_ms(const miso_batch_t *b, float *compare_ms, float *exact_compare_ms) {
   return guarded([&] {
     need(b, "batch");

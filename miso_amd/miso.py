@@ -134,7 +134,10 @@ class GenesDispatcher(object):
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                  exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                 delta_posterior=False, exact_delta_posterior=False):
+                 delta_posterior=False, exact_delta_posterior=False, exact_stats=False):
+        # --exact-stats: beside the outputs the `.miso_exact_stats` table (compare.py) of every directory of `.miso` files,
+        # merged like a diagnostics table
+        self.exact_stats = bool(exact_stats)
         self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
         # --exact-delta-posterior: beside the `.miso_bf_exact` table the `.miso_dpsi_exact` (compare.py), merged like it
         self.exact_delta_posterior = bool(exact_delta_posterior)
@@ -291,6 +294,12 @@ class GenesDispatcher(object):
                 self.diag_tables.append((os.path.join(d, "summary", label + ".miso_diag"), []))
                 os.makedirs(os.path.dirname(self.diag_tables[-1][0]), exist_ok=True)
         n_diag = len(self.diag_tables)
+        stables = []                   # --exact-stats: [(table, its per-worker parts)], one per directory of `.miso` files
+        if self.exact_stats:
+            for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
+                label = os.path.basename(os.path.normpath(d))
+                stables.append((os.path.join(d, "summary", label + ".miso_exact_stats"), []))
+                os.makedirs(os.path.dirname(stables[-1][0]), exist_ok=True)
         for batch_num, (fname, size, first) in enumerate(batches):
             if size == 0:
                 continue
@@ -322,6 +331,11 @@ class GenesDispatcher(object):
                     for (_, plist), dp in zip(self.diag_tables, dparts):
                         plist.append(dp)
                     cmd += ["--diagnostics-files"] + dparts + (["--rank-diagnostics"] if self.rank_diagnostics else [])
+                if stables:
+                    sparts = ["%s.gpu%d" % (t, batch_num) for t, _ in stables]
+                    for (_, plist), sp in zip(stables, sparts):
+                        plist.append(sp)
+                    cmd += ["--exact-stats-files"] + sparts
             else:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compute-genes-from-file", fname,
                        self.bam_filename, self.output_dir]
@@ -332,6 +346,9 @@ class GenesDispatcher(object):
                 if self.diag_tables:
                     self.diag_tables[0][1].append("%s.gpu%d" % (self.diag_tables[0][0], batch_num))
                     cmd += ["--diagnostics-file", self.diag_tables[0][1][-1]] + (["--rank-diagnostics"] if self.rank_diagnostics else [])
+                if stables:
+                    stables[0][1].append("%s.gpu%d" % (stables[0][0], batch_num))
+                    cmd += ["--exact-stats-file", stables[0][1][-1]]
             # more chunks than GPUs (-p above the GPU count) share the GPUs round robin
             cmd += ["--read-len", str(self.read_len), "--device", str(batch_num % self.n_gpus),
                     "--first-event-id", str(first)]
@@ -354,7 +371,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
-        self.diag_tables += xtable + dtable + etable
+        self.diag_tables += xtable + dtable + etable + stables
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -427,7 +444,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                           exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                          delta_posterior=False, exact_delta_posterior=False):
+                          delta_posterior=False, exact_delta_posterior=False, exact_stats=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -441,7 +458,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            compare_bam=compare_bam, labels=labels, summary_only=summary_only,
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
                            delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
-                           delta_posterior=delta_posterior, exact_delta_posterior=exact_delta_posterior).run()
+                           delta_posterior=delta_posterior, exact_delta_posterior=exact_delta_posterior,
+                           exact_stats=exact_stats).run()
 
 
 def main(argv=None):
@@ -476,6 +494,10 @@ def main(argv=None):
                     help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
                          "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
                          "other events are sampled as always.  Also the settings key `exact` under [sampler].")
+    ap.add_argument("--exact-stats", action="store_true",
+                    help="with --exact: also write OUT/summary/<OUT>.miso_exact_stats (with --compare one table per label): per "
+                         "event the seven statistics its exact posterior is made of, what `samples_utils --compare-groups "
+                         "--exact-delta-posterior` pools replicates of separate runs from; every other output is unchanged")
     ap.add_argument("--exact-paired", action="store_true",
                     help="with --paired-end: paired-end two-isoform events run no chains -- the posterior of Psi, a product over "
                          "the event's read pairs, is tabulated once per event on the GPU and the .miso file's samples are "
@@ -521,6 +543,8 @@ def main(argv=None):
         ap.error("--exact-paired goes with --paired-end")
     if a.rank_diagnostics and not a.diagnostics:
         ap.error("--rank-diagnostics goes with --diagnostics")
+    if a.exact_stats and (a.paired_end or not (a.exact or Settings.get_exact())):
+        ap.error("--exact-stats needs the exact-posterior mode of single-end runs (--exact, or `exact = True` in the settings)")
     if a.exact_compare:
         if a.compare is None:
             ap.error("--exact-compare goes with --compare")
@@ -571,7 +595,8 @@ def main(argv=None):
                                        exact=a.exact, exact_compare=a.exact_compare or a.exact_paired_compare,
                                        exact_paired=a.exact_paired,
                                        delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics,
-                                       delta_posterior=a.delta_posterior, exact_delta_posterior=a.exact_delta_posterior)
+                                       delta_posterior=a.delta_posterior, exact_delta_posterior=a.exact_delta_posterior,
+                                       exact_stats=a.exact_stats)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

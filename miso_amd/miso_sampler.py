@@ -166,7 +166,7 @@ class MISOSampler:
                           start_cond=pysplicing.MISO_START_AUTO,
                           stop_cond=pysplicing.MISO_STOP_FIXEDNO, seed=None, first_event_id=0,
                           verbose=False, summary_file=None, confidence_level=0.95, threads=0, diagnostics_file=None,
-                          rank_diagnostics=False):
+                          rank_diagnostics=False, exact_stats_file=None):
         """events: list of (reads, gene, output_file[, prior_params[, event_id]]); `reads` is the
         reference's (positions 0-based, cigars) pair or an AlnRegion; event_id pins the event's
         random stream (default: first_event_id + its position among the events actually sampled).  Same per-event skip rules as run_sampler
@@ -177,14 +177,15 @@ class MISOSampler:
         summary_file: also write the `summarize_miso` table (samples_utils.py:263-329) for the
         events of this batch, from means / credible intervals computed on the device.
         diagnostics_file: also write the chain diagnostics table (diagnostics.py) of these events; rank_diagnostics: with
-        the six columns of the rank-normalised pass.
+        the six columns of the rank-normalised pass.  exact_stats_file: output_batch's.
         = prepare_batch (host: skip rules, reads into the batch) + finish_batch (GPU + files); a caller
         with several batches can overlap one's finish with the next one's prepare (run_miso.py)."""
         state = self.prepare_batch(num_iters, events, num_chains=num_chains, burn_in=burn_in, lag=lag,
                                    start_cond=start_cond, stop_cond=stop_cond, verbose=verbose)
         return self.finish_batch(state, seed=seed, first_event_id=first_event_id, verbose=verbose,
                                  summary_file=summary_file, confidence_level=confidence_level,
-                                 threads=threads, diagnostics_file=diagnostics_file, rank_diagnostics=rank_diagnostics)
+                                 threads=threads, diagnostics_file=diagnostics_file, rank_diagnostics=rank_diagnostics,
+                                 exact_stats_file=exact_stats_file)
 
     def exact_paired(self):
         """the paired-end exact-posterior mode is asked for: params["exact_paired"], else MISO_EXACT_PAIRED=1; never on a
@@ -326,7 +327,8 @@ class MISOSampler:
         return (batch, slots, written, int(num_iters), int(burn_in), int(lag))
 
     def finish_batch(self, state, seed=None, first_event_id=0, verbose=False, summary_file=None,
-                     confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None, rank_diagnostics=False):
+                     confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None, rank_diagnostics=False,
+                     exact_stats_file=None):
         """Launch, then the event's outputs.  write_files=False (with a summary_file): no per-event `.miso` file --
         the posterior means and credible intervals that `summarize_miso` would compute from those files
         (samples_utils.py:263-329) come from the device, summarised from the four-decimal text the file WOULD hold.
@@ -335,7 +337,7 @@ class MISOSampler:
         self.launch_batch(state, seed=seed, first_event_id=first_event_id)
         return self.output_batch(state, verbose=verbose, summary_file=summary_file, confidence_level=confidence_level,
                                  threads=threads, write_files=write_files, diagnostics_file=diagnostics_file,
-                                 rank_diagnostics=rank_diagnostics)
+                                 rank_diagnostics=rank_diagnostics, exact_stats_file=exact_stats_file)
 
     def launch_batch(self, state, seed=None, first_event_id=0):
         """Upload, sample, download (native code, the interpreter lock released throughout)."""
@@ -365,15 +367,20 @@ class MISOSampler:
                    ",".join(str(iso.genomic_end) for iso in gene.isoforms)))
 
     def output_batch(self, state, verbose=False, summary_file=None, confidence_level=0.95, threads=0,
-                     write_files=True, diagnostics_file=None, rank_diagnostics=False):
+                     write_files=True, diagnostics_file=None, rank_diagnostics=False, exact_stats_file=None):
         """The `.miso` files and / or the summary table of a launched batch.  The header's run-dependent fields are
         formatted natively for the whole batch (miso_batch_header_fields); miso_header() below is the same line field
         by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte).
         diagnostics_file: the chain diagnostics table of the written events (diagnostics.py), from the full-precision
         samples resident on the device; nothing else changes with it.  rank_diagnostics: that table with the six columns
-        of the rank-normalised pass."""
+        of the rank-normalised pass.  exact_stats_file: the `.miso_exact_stats` table of the written events
+        (compare.write_exact_stats): the seven statistics an exact posterior is made of, as the batch holds them
+        (Batch.exact_stats), and whether the exact mode took the event; nothing else changes with it."""
         batch, slots, written, num_iters, burn_in, lag = state
+        stat_rows = []
         if not slots:
+            if exact_stats_file is not None:
+                compare.write_exact_stats(exact_stats_file, stat_rows)
             return written
         timing = os.environ.get("MISO_TIMING")
         t1 = time.time()
@@ -423,6 +430,9 @@ class MISOSampler:
             if diagnostics_file is not None:
                 diag_rows.append((os.path.basename(out)[:-len(".miso")],) + tuple(diags[j]) + (n_samples, n_chains)
                                  + ((ranks[j],) if rank_diagnostics else ()))
+            if exact_stats_file is not None:
+                st, was = batch.exact_stats(idx)
+                stat_rows.append((os.path.basename(out)[:-len(".miso")], was, st))
         t2 = time.time()
         if write_files:
             batch.write_miso_files(idxs, paths, headers, threads)
@@ -430,6 +440,8 @@ class MISOSampler:
             summary.write_summary(summary_file, rows)
         if diagnostics_file is not None:
             diagnostics.write_diagnostics(diagnostics_file, diag_rows, rank=rank_diagnostics)
+        if exact_stats_file is not None:
+            compare.write_exact_stats(exact_stats_file, stat_rows)
         if timing:
             print("[miso] batch of %d events: headers %.2f s, .miso files / table %.2f s"
                   % (len(slots), t2 - t1, time.time() - t2))
@@ -440,7 +452,8 @@ class MISOSampler:
                              burn_in=1000, lag=2, seed=None, seed2=None, first_event_id=0,
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
                              diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None,
-                             rank_diagnostics=False, delta_posterior_file=None, exact_delta_file=None):
+                             rank_diagnostics=False, delta_posterior_file=None, exact_delta_file=None,
+                             exact_stats_files=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -460,7 +473,12 @@ class MISOSampler:
         P(|delta psi| >= t) for every t of delta_thresholds.
         exact_delta_file (optional; with exact_comparison_file only): the `.miso_dpsi_exact` table (compare.write_exact_dpsi)
         -- median and 95 % credible interval of delta psi, P(delta > 0), P(delta < 0) from the exact CDF
-        (MISOCompareBatch(exact_delta=)) and the exact comparison's P(|delta psi| >= t)."""
+        (MISOCompareBatch(exact_delta=)) and the exact comparison's P(|delta psi| >= t).
+        exact_stats_files (optional; the single-end exact mode only): (file1, file2), each sample's `.miso_exact_stats` table
+        (compare.write_exact_stats) of its written events (MISOCompareBatch(exact_stats=))."""
+        if exact_stats_files is not None and (self.paired_end or not int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0)):
+            raise ValueError("the exact statistics tables need the exact-posterior mode (single-end)")
+        stat_rows = ([], [])
         if exact_delta_file is not None and exact_comparison_file is None:
             raise ValueError("the exact delta psi table goes with the exact comparison")
         dthr = None
@@ -510,6 +528,8 @@ class MISOSampler:
                 kw["exact_delta"] = compare.EXACT_DPSI_PROBS
             if dthr is not None:
                 kw["delta_posterior"] = (float(confidence_level), tuple(dthr))
+            if exact_stats_files is not None:
+                kw["exact_stats"] = True
             res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),
@@ -519,6 +539,8 @@ class MISOSampler:
             at = 3 + (diagnostics_files is not None)
             xres = res[at] if xthr is not None else None
             eres = res[at + 1] if exact_delta_file is not None else None
+            # (the statistics stand behind the exact comparison's elements and before the all-pairs one)
+            sres = res[at + (xthr is not None) + (exact_delta_file is not None)] if exact_stats_files is not None else None
             n_samples = int(num_chains) * (int(num_iters) - int(burn_in)) // int(lag)
             if diagnostics_files is not None and rank_diagnostics:
                 for which, refused in enumerate(res[3][2]):
@@ -536,6 +558,11 @@ class MISOSampler:
                             diag_rows[which].append((os.path.basename(f)[:-len(".miso")],) + tuple(d[:4])
                                                     + (n_samples, int(num_chains))
                                                     + (((d[4:] if len(d) == 10 else None),) if rank_diagnostics else ()))
+                if sres is not None:
+                    for which, f in enumerate((f1, f2)):
+                        if f is not None:
+                            was, st = sres[which][j]
+                            stat_rows[which].append((os.path.basename(f)[:-len(".miso")], was, st))
                 if f1 is not None and f2 is not None:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
@@ -555,6 +582,9 @@ class MISOSampler:
         if diagnostics_files is not None:
             for f, drows in zip(diagnostics_files, diag_rows):
                 diagnostics.write_diagnostics(f, drows, rank=rank_diagnostics)
+        if exact_stats_files is not None:
+            for f, srows in zip(exact_stats_files, stat_rows):
+                compare.write_exact_stats(f, srows)
         return written
 
     # -- shared pieces -------------------------------------------------------------------------

@@ -42,6 +42,8 @@
  *   exact_delta=(p, ...)  MISOCompareBatch with exact_compare= or exact_paired_compare=: the quantiles of psi_1 - psi_2 at
  *                   these probabilities (1 to 4) from the exact CDF (miso_batch_exact_delta_quantiles), one more element of the
  *                   result, behind exact_compare's: per event None or ((quantile, ...), P(psi_1 - psi_2 <= 0)).
+ *   exact_stats=True  MISOCompareBatch with exact=True: one more element, behind exact_delta's and before delta_posterior's:
+ *                   per sample the events' (was_exact, (n10, n01, n, e0, e1, h0, h1)) (miso_batch_get_exact_stats).
  * The functions of the module that are not on the sampler path raise NotImplementedError.
  * The reference's stdout side effect `printf("no chains: %d\n")` (miso.c:837) is not reproduced.
  */
@@ -493,7 +495,7 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
                            "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired",
-                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", "exact_delta", NULL};
+                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", "exact_delta", "exact_stats", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *dpobj = NULL, *dp = NULL;   /* delta_posterior=(level, (tau, ...)): the all-pairs pass, miso_batch_compare_pairs */
   double dp_level = 0.95, dp_tau[4]; int n_dp = 0;
@@ -502,6 +504,8 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
   PyObject *edobj = NULL, *ed = NULL;   /* exact_delta=(p, ...): the quantiles of delta psi from the exact CDF, miso_batch_exact_delta_quantiles */
   double ep[4]; int n_ep = 0;
+  int exact_stats = 0;              /* exact_stats=True (with exact=True): the seven statistics of every event, miso_batch_get_exact_stats */
+  PyObject *es = NULL;
   int rank_diagnostics = 0;         /* with diagnostics=True: the rank-normalised pass too (diagnostics_list) */
   int diagnostics = 0, exact = 0;   /* exact=True (single-end): the exact-posterior mode, miso_batch_set_exact */
   int exact_paired = 0;             /* exact_paired=True (with paired=): miso_batch_set_exact_paired */
@@ -510,10 +514,11 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpOO", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpOOp", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
                                    &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
-                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj, &edobj)) return NULL;
+                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj, &edobj, &exact_stats)) return NULL;
+  if (exact_stats && !exact) { PyErr_SetString(PyExc_ValueError, "exact_stats requires exact=True"); return NULL; }
   if (dpobj == Py_None) dpobj = NULL;
   if (dpobj) {
     PyObject *taus = NULL; Py_ssize_t nt;
@@ -664,7 +669,30 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     all = one ? PySequence_Concat(out, one) : NULL;
     Py_XDECREF(one); Py_DECREF(out); out = all;
   }
-  /* delta_posterior=(level, (tau, ...)): a last element (behind exact_compare's and exact_delta's), per event (median, ci_low, ci_high, n_gt0,
+  /* exact_stats=True: a last element (behind exact_compare's and exact_delta's), per sample the events' (was_exact, (n10, n01,
+     n, e0, e1, h0, h1)) */
+  if (out && exact_stats) {
+    PyObject *one, *all, *per[2] = {NULL, NULL};
+    int w;
+    for (w = 0; w < 2; w++) {
+      if (!(per[w] = PyList_New(n))) break;
+      for (i = 0; i < n; i++) {
+        double st[7]; int was = 0;
+        PyObject *t;
+        if ((rc = miso_batch_get_exact_stats(w ? b2 : b1, (int) i, st, &was))) { raise_miso(rc); break; }
+        if (!(t = Py_BuildValue("(NN)", PyBool_FromLong(was), from_doubles(st, 7)))) break;
+        PyList_SET_ITEM(per[w], i, t);
+      }
+      if (i < n) break;
+    }
+    if (w < 2) { Py_XDECREF(per[0]); Py_XDECREF(per[1]); Py_CLEAR(out); goto done; }
+    es = PyTuple_Pack(2, per[0], per[1]);
+    Py_DECREF(per[0]); Py_DECREF(per[1]);
+    one = es ? PyTuple_Pack(1, es) : NULL;
+    all = one ? PySequence_Concat(out, one) : NULL;
+    Py_XDECREF(one); Py_DECREF(out); out = all;
+  }
+  /* delta_posterior=(level, (tau, ...)): a last element (behind exact_compare's, exact_delta's and exact_stats'), per event (median, ci_low, ci_high, n_gt0,
      n_lt0, n_abs_ge -- per isoform a tuple over the thresholds --, finite, n_pairs) of the S1 * S2 differences */
   if (out && dpobj) {
     PyObject *one, *all;
@@ -697,7 +725,7 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     Py_XDECREF(one); Py_DECREF(out); out = all;
   }
 done:
-  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc); Py_XDECREF(ed); Py_XDECREF(dp);
+  Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc); Py_XDECREF(ed); Py_XDECREF(es); Py_XDECREF(dp);
   if (b1) miso_batch_destroy(b1);
   if (b2) miso_batch_destroy(b2);
   return out;

@@ -147,7 +147,7 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
-                     diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False):
+                     diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False, exact_stats_file=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
@@ -155,8 +155,13 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     rank_diagnostics: that table with the six columns of the rank-normalised pass.
     exact: single-end two-isoform events take the exact-posterior mode (None: the settings' `exact` key).
     exact_paired: the same switch for the paired-end two-isoform events of a --paired-end run (None: the settings'
-    `exact_paired` key); nothing on a single-end run."""
+    `exact_paired` key); nothing on a single-end run.
+    exact_stats_file (the single-end exact mode only): also write the `.miso_exact_stats` table of the written events
+    (compare.write_exact_stats), parts merged like the diagnostics table's."""
     exact = Settings.get_exact() if exact is None else bool(exact)
+    if exact_stats_file is not None and (paired_end or not exact):
+        raise ValueError("the exact statistics table needs the exact-posterior mode (single-end)")
+    stat_parts = []
     exact_paired = Settings.get_exact_paired() if exact_paired is None else bool(exact_paired)
     os.makedirs(output_dir, exist_ok=True)
     if gene_entries is None:
@@ -270,12 +275,15 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             dpart = None if diagnostics_file is None else "%s.part%06d" % (diagnostics_file, lo)
             if dpart:
                 diag_parts.append(dpart)
+            spart = None if exact_stats_file is None else "%s.part%06d" % (exact_stats_file, lo)
+            if spart:
+                stat_parts.append(spart)
             launched = gpu.submit(sampler.launch_batch, state, seed=seed, first_event_id=first_event_id + lo)
 
-            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart):
+            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart, spart=spart):
                 launched.result()
                 return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files,
-                                            diagnostics_file=dpart, rank_diagnostics=rank_diagnostics)
+                                            diagnostics_file=dpart, rank_diagnostics=rank_diagnostics, exact_stats_file=spart)
             in_flight.append(out.submit(outputs))
         for f in in_flight:
             written += f.result()
@@ -286,6 +294,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
         merge_tables(summary_parts, summary_file)
     if diagnostics_file is not None:
         merge_tables(diag_parts, diagnostics_file)
+    if exact_stats_file is not None:
+        merge_tables(stat_parts, exact_stats_file)
     t2 = time.time()
     if verbose:
         print("Collected %d events in %.2f s (beside the decoding / sampling), batches prepared in %.2f s, whole run %.2f s"
@@ -325,7 +335,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
                      exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False,
-                     delta_posterior_file=None, exact_delta_file=None):
+                     delta_posterior_file=None, exact_delta_file=None, exact_stats_files=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -340,7 +350,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     delta_posterior_file (any mode): the `.miso_dpsi` table of delta psi over all pairs of the two samples' draws (compare.py
     write_dpsi), parts merged like the comparison's, with the same delta_thresholds.
     exact_delta_file (with exact_comparison_file only): the `.miso_dpsi_exact` table of delta psi's median and credible
-    interval from the exact CDF (compare.py write_exact_dpsi), parts merged like the exact comparison's."""
+    interval from the exact CDF (compare.py write_exact_dpsi), parts merged like the exact comparison's.
+    exact_stats_files (the single-end exact mode only): (file1, file2), each sample's `.miso_exact_stats` table
+    (compare.py write_exact_stats), parts merged like the diagnostics tables'."""
     if exact_delta_file is not None and exact_comparison_file is None:
         raise ValueError("the exact delta psi table goes with the exact comparison")
     for d in (output_dir1, output_dir2):
@@ -354,6 +366,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
         raise ValueError("the exact comparison of paired-end samples needs the paired exact-posterior mode")
     if exact_comparison_file is not None and not paired_end and not exact:
         raise ValueError("the exact comparison needs the exact-posterior mode (single-end)")
+    if exact_stats_files is not None and (paired_end or not exact):
+        raise ValueError("the exact statistics tables need the exact-posterior mode (single-end)")
+    stat_parts = ([], [])
     p = Settings.get_sampler_params()
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
     evs = []
@@ -394,6 +409,11 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             dparts = tuple("%s.part%06d" % (f, lo) for f in diagnostics_files)
             for which in (0, 1):
                 diag_parts[which].append(dparts[which])
+        sparts = None
+        if exact_stats_files is not None:
+            sparts = tuple("%s.part%06d" % (f, lo) for f in exact_stats_files)
+            for which in (0, 1):
+                stat_parts[which].append(sparts[which])
         xpart = None
         if exact_comparison_file is not None:
             xpart = "%s.part%06d" % (exact_comparison_file, lo)
@@ -413,7 +433,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                      event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
                                      diagnostics_files=dparts, exact_comparison_file=xpart,
                                      delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
-                                     delta_posterior_file=dpsi_part, exact_delta_file=epart)
+                                     delta_posterior_file=dpsi_part, exact_delta_file=epart, exact_stats_files=sparts)
     merge_tables(parts, comparison_file)
     if delta_posterior_file is not None:
         merge_tables(dpsi_parts, delta_posterior_file)
@@ -442,12 +462,19 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             if diagnostics_files is not None:
                 dpart = "%s.alone" % diagnostics_files[int(which) - 1]
                 diag_parts[int(which) - 1].append(dpart)
+            spart = None
+            if exact_stats_files is not None:
+                spart = "%s.alone" % exact_stats_files[int(which) - 1]
+                stat_parts[int(which) - 1].append(spart)
             sampler.run_sampler_batch(p["num_iters"], alone, num_chains=p["num_chains"], burn_in=p["burn_in"],
                                       lag=p["lag"], seed=s, verbose=verbose, diagnostics_file=dpart,
-                                      rank_diagnostics=rank_diagnostics)
+                                      rank_diagnostics=rank_diagnostics, exact_stats_file=spart)
     if diagnostics_files is not None:
         for which in (0, 1):
             merge_tables(diag_parts[which], diagnostics_files[which])
+    if exact_stats_files is not None:
+        for which in (0, 1):
+            merge_tables(stat_parts[which], exact_stats_files[which])
     return len(pairs)
 
 
@@ -503,6 +530,11 @@ def main(argv=None):
     ap.add_argument("--exact-paired", action="store_true",
                     help="with --paired-end: paired-end two-isoform events draw independently from the exact posterior of Psi "
                          "instead of running chains (also the settings key `exact_paired`)")
+    ap.add_argument("--exact-stats-file", default=None, metavar="F",
+                    help="with --compute-genes-from-file and the exact mode (single-end): also write the `.miso_exact_stats` "
+                         "table, per event the seven statistics its exact posterior is made of")
+    ap.add_argument("--exact-stats-files", nargs=2, default=None, metavar=("FILE1", "FILE2"),
+                    help="with --compare-genes-from-file and the exact mode (single-end): that table of each sample")
     ap.add_argument("--exact-comparison-file", default=None, metavar="F",
                     help="with --compare-genes-from-file and the exact mode: also write the exact comparison's table "
                          "(Bayes factors and P(|delta psi| >= T) from the posteriors' tables, no sampling error)")
@@ -555,6 +587,12 @@ def main(argv=None):
     if a.exact_delta_file is not None and a.exact_comparison_file is None:
         print("Error: --exact-delta-file goes with --exact-comparison-file.")
         return 1
+    if a.exact_stats_file is not None and (not a.compute_genes_from_file or paired_end or not exact):
+        print("Error: --exact-stats-file goes with --compute-genes-from-file and the exact mode (single-end).")
+        return 1
+    if a.exact_stats_files is not None and (not a.compare_genes_from_file or paired_end or not exact):
+        print("Error: --exact-stats-files goes with --compare-genes-from-file and the exact mode (single-end).")
+        return 1
     if a.delta_posterior_file is not None and not a.compare_genes_from_file:
         print("Error: --delta-posterior-file goes with --compare-genes-from-file.")
         return 1
@@ -579,7 +617,8 @@ def main(argv=None):
                              delta_posterior_file=(os.path.abspath(os.path.expanduser(a.delta_posterior_file))
                                                    if a.delta_posterior_file else None),
                              exact_delta_file=(os.path.abspath(os.path.expanduser(a.exact_delta_file))
-                                               if a.exact_delta_file else None))
+                                               if a.exact_delta_file else None),
+                             exact_stats_files=a.exact_stats_files)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -595,7 +634,7 @@ def main(argv=None):
                          summary_file=a.summary_file,
                          write_files=not (a.no_miso_files and a.summary_file),
                          diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired,
-                         rank_diagnostics=a.rank_diagnostics)
+                         rank_diagnostics=a.rank_diagnostics, exact_stats_file=a.exact_stats_file)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")

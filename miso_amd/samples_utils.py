@@ -33,6 +33,8 @@ standard error; diagnostics.py) of the files' four-decimal values,
 `--compare-groups` is `--compare-samples` for biological replicates (what filter_events --votes reads): every pair of the
 two groups gets the file the pairwise call writes, byte for byte, but every tree is read once, every sample decoded and
 summarised once per chunk of events, and all pairs of a chunk come out of one launch (capi.compare_groups).
+With `--exact-delta-posterior` the two groups also get `<A>_vs_<B>.miso_group_dpsi_exact`: delta psi pooled over all pairs of
+replicates from their exact posteriors, without a draw, from each directory's `summary/<name>.miso_exact_stats`.
 With `--delta-posterior` every pair also gets its `.miso_dpsi`, and the two groups one pooled table, `.miso_group_dpsi`: delta
 psi over all differences between the pooled draws of the groups (capi.compare_pairs_groups).
 """
@@ -922,6 +924,67 @@ def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=Non
     return written
 
 
+MAX_EXACT_GROUP = 8     # replicates a group in the exact pooled pass (include/miso_amd.h miso_exact_delta_groups)
+
+
+def exact_stats_path(sample_dir):
+    """where `miso --run ... --exact --exact-stats` leaves a sample directory's table"""
+    return os.path.join(sample_dir, "summary", os.path.basename(os.path.normpath(sample_dir)) + ".miso_exact_stats")
+
+
+def check_exact_stats_tables(dirs1, dirs2):
+    """ValueError, before any work, unless both groups have 1 .. 8 directories and each holds its `.miso_exact_stats` table"""
+    for which, dirs in enumerate((dirs1, dirs2)):
+        if not 1 <= len(dirs) <= MAX_EXACT_GROUP:
+            raise ValueError("Error: --exact-delta-posterior pools between 1 and %d replicates a group, group %d has %d"
+                             % (MAX_EXACT_GROUP, which + 1, len(dirs)))
+    for d in list(dirs1) + list(dirs2):
+        if not os.path.isfile(exact_stats_path(d)):
+            raise ValueError("Error: %s has no %s (written by miso --run ... --exact --exact-stats)"
+                             % (d, os.path.relpath(exact_stats_path(d), d)))
+
+
+def output_group_exact_delta(dirs1, dirs2, output_dir, delta_thresholds=None, group_names=None):
+    """--compare-groups --exact-delta-posterior: `<A>_vs_<B>/delta-psi/<A>_vs_<B>.miso_group_dpsi_exact`, delta psi of the two
+    groups pooled over all pairs of replicates from their exact posteriors, without a draw (capi.exact_delta_groups, DESIGN.md
+    20a), from each sample directory's `.miso_exact_stats` table.  An event is pooled over the replicates that have it with
+    exact = 1: the events are grouped by which replicates those are, one device call per such pattern.  An event without such
+    a replicate on a side, or with unequal effective lengths among its replicates, prints NA; one notice per cause.
+    Returns (path, n_rows)."""
+    check_exact_stats_tables(dirs1, dirs2)
+    thresholds = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
+    group_names = tuple(group_names or DEFAULT_GROUP_NAMES)
+    tables = [[compare.read_exact_stats(exact_stats_path(d)) for d in dirs] for dirs in (dirs1, dirs2)]
+    names = sorted(set().union(*[t.keys() for g in tables for t in g]))
+    patterns = {}
+    for name in names:
+        have = tuple(tuple(r for r, t in enumerate(g) if name in t and t[name][0]) for g in tables)
+        patterns.setdefault(have, []).append(name)
+    rows = {}
+    n_none = n_unequal = 0
+    for (have1, have2), evs in patterns.items():
+        if not have1 or not have2:
+            n_none += len(evs)
+            for name in evs:
+                rows[name] = (name, len(have1), len(have2), None, {})
+            continue
+        s1 = [[tables[0][r][name][1] for r in have1] for name in evs]
+        s2 = [[tables[1][r][name][1] for r in have2] for name in evs]
+        res = capi.exact_delta_groups(s1, s2, compare.EXACT_DPSI_PROBS, compare.delta_points(thresholds))
+        for j, name in enumerate(evs):
+            row = res.row(j)
+            n_unequal += row is None
+            rows[name] = (name, len(have1), len(have2), row, {})
+    if n_none:
+        print("Notice: %d event(s) have no replicate with an exact posterior in one of the groups: NA in the pooled table" % n_none)
+    if n_unequal:
+        print("Notice: %d event(s) differ in effective lengths among their replicates: NA in the pooled table" % n_unequal)
+    name = "%s_vs_%s" % group_names
+    out = os.path.join(output_dir, name, "delta-psi", name + ".miso_group_dpsi_exact")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    return out, compare.write_group_dpsi_exact(out, [rows[n] for n in names], thresholds)
+
+
 def parse_group_args(compare_groups, group_labels_arg=None):
     """`--compare-groups DIR[,DIR...] DIR[,DIR...] OUTPUT_DIR [--group-labels L[,L...] L[,L...]]` ->
     (dirs1, dirs2, output_dir, labels1, labels2); the labels are checked (group_labels) before anything is read."""
@@ -960,18 +1023,25 @@ def main(argv=None):
                          "With --compare-samples: also write <l1>_vs_<l2>.miso_dpsi beside the .miso_bf -- median and 95 %% "
                          "credible interval of delta psi, P(delta psi > 0), P(delta psi < 0) and P(|delta psi| >= T) over ALL "
                          "pairs of the two samples' draws, for events of any number of isoforms")
+    ap.add_argument("--exact-delta-posterior", action="store_true",
+                    help="with --compare-groups: also the pooled table <A>_vs_<B>.miso_group_dpsi_exact of delta psi over all "
+                         "pairs of replicates from their exact posteriors, without a draw -- from every sample directory's "
+                         "summary/<name>.miso_exact_stats, which miso --run ... --exact --exact-stats writes")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
-                    help="the thresholds T of --delta-posterior, each in (0, 1), at most four (default 0.1 0.2)")
+                    help="the thresholds T of --delta-posterior and --exact-delta-posterior, each in (0, 1), at most four "
+                         "(default 0.1 0.2)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.delta_posterior and not (a.compare_samples or a.compare_groups):      # argument errors, before any work
         # (both wordings: scripts and tests match on the older "goes with --compare-samples")
         ap.error("--delta-posterior needs --compare-samples or --compare-groups "
                  "(--delta-posterior goes with --compare-samples, and with --compare-groups)")
-    if a.group_names and not (a.compare_groups and a.delta_posterior):
-        ap.error("--group-names goes with --compare-groups --delta-posterior")
+    if a.exact_delta_posterior and not a.compare_groups:
+        ap.error("--exact-delta-posterior goes with --compare-groups")
+    if a.group_names and not (a.compare_groups and (a.delta_posterior or a.exact_delta_posterior)):
+        ap.error("--group-names goes with --compare-groups --delta-posterior (or --exact-delta-posterior)")
     if a.delta_psi_thresholds is not None:
-        if not a.delta_posterior:
+        if not (a.delta_posterior or a.exact_delta_posterior):
             ap.error("--delta-psi-thresholds goes with --delta-posterior")
         try:
             compare.check_delta_thresholds(a.delta_psi_thresholds)
@@ -1004,11 +1074,16 @@ def main(argv=None):
     if a.compare_groups:
         try:
             dirs1, dirs2, out_dir, l1, l2 = parse_group_args(a.compare_groups, a.group_labels)
+            if a.exact_delta_posterior:
+                check_exact_stats_tables(dirs1, dirs2)
         except ValueError as err:
             ap.error(str(err))
         for out, n in output_group_comparisons(dirs1, dirs2, out_dir, l1, l2, device=a.device, delta_thresholds=thr,
                                                group_names=a.group_names):
             print("Compared %d events into %s" % (n, out))
+        if a.exact_delta_posterior:
+            print("Pooled %d events into %s" % output_group_exact_delta(
+                dirs1, dirs2, out_dir, delta_thresholds=a.delta_psi_thresholds, group_names=a.group_names)[::-1])
     elif a.group_labels:
         ap.error("--group-labels goes with --compare-groups")
     if not a.summarize_samples and not a.compare_samples and not a.compare_groups and not a.diagnose_samples:
