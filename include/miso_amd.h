@@ -474,6 +474,36 @@ int miso_batch_get_exact_stats(const miso_batch_t *batch, int event_index, doubl
 int miso_batch_exact_delta_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, const double *p, int n_p,
                                   const double *z, int n_z, double *out, int64_t out_len, int *was_exact, float *kernel_ms);
 
+/* The same for PAIRED-END replicates (csrc/kernels_exact_paired_delta_groups.hip): the mixture, the
+   search, p, z, the output row, was_exact, the launch ranges and kernel_ms are as above; H_ab is
+   miso_batch_exact_delta_quantiles' CDF of two paired-end posteriors bit for bit (A, the replicate with the narrower window in
+   psi, contributes its own tabulated density; a tie goes to the group-1 replicate).  No equality of A0, A1 between replicates
+   is needed.
+   miso_exact_paired_delta_groups works on caller-given elements: stats6, m, offs are arrays of n1 + n2 pointers, group 1's
+   replicates first, each replicate's elements in miso_selftest_exact_paired's layout over the same n_events (stats6[r]:
+   n_events rows {n10, n01, A0, A1, h0, h1}; offs[r]: n_events + 1 offsets from 0, ascending; m[r]: offs[r][n_events] pairs
+   (m0, m1), NULL allowed when there is none).  An event is comparable when every replicate's row passes
+   miso_exact_paired_eligible; any other event gets was_exact = 0 and an untouched row.  MISO_EINVAL, before anything is
+   allocated: counts outside their ranges, p, z, offsets that do not start at 0 or descend, a negative count or a pair
+   probability outside [2^-63, 1] in a comparable event.
+   miso_batch_exact_paired_delta_groups: the same pass over launched batches, preconditions as
+   miso_batch_compare_pairs_groups; every batch must be paired-end and have run with miso_batch_set_exact_paired, otherwise
+   MISO_EINVAL naming the group and the index of the batch.  An event that some batch's mode did not take is not comparable.
+   The kernels read the batches' resident pair records, on the first batch's stream after all have been waited for.  Nothing
+   is stored in any batch.
+   miso_batch_get_exact_paired_element: event_index of a launched batch as the first function takes it: the six statistics,
+   n_pairs, and -- m != NULL, m_cap pairs of room, MISO_EINVAL when too few -- the drawing pairs' probabilities (m0, m1) in
+   record order, the doubles the kernels multiply.  was_exact = 0, n_pairs = 0 and nothing else for an event the paired exact
+   mode did not take and for every event of a single-end batch. */
+int miso_exact_paired_delta_groups(const double *const *stats6, const double *const *m, const int64_t *const *offs, int n1, int n2,
+                                   int n_events, const double *p, int n_p, const double *z, int n_z, int max_events_per_launch,
+                                   double *out, int *was_exact, float *kernel_ms);
+int miso_batch_exact_paired_delta_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, const double *p,
+                                         int n_p, const double *z, int n_z, double *out, int64_t out_len, int *was_exact,
+                                         float *kernel_ms);
+int miso_batch_get_exact_paired_element(const miso_batch_t *batch, int event_index, double *stats6, double *m, int64_t m_cap,
+                                        int64_t *n_pairs, int *was_exact);
+
 /* The posterior of delta = psi_1 - psi_2 over ALL pairs of the two samples' draws (csrc/kernels_compare_pairs.hip, DESIGN.md
    section 19): the samples are independent posteriors, so given the draws the law of delta is the empirical law of the
    M = S1 * S2 differences, not of the index-paired ones.  Preconditions and errors as miso_batch_compare -- both launched

@@ -468,6 +468,22 @@ class Batch:
         check(lib().miso_batch_get_exact_stats(self.handle, int(i), _p(r), C.byref(was)))
         return r, bool(was.value)
 
+    def exact_paired_element(self, i):
+        """(stats6, m [n_pairs, 2], was_exact) of event i of a launched batch: (n10, n01, A0, A1, h0, h1) and the drawing
+        pairs' probabilities in record order, what the exact posterior of a paired-end two-isoform event is made of and
+        exact_paired_delta_groups takes; was_exact False (and nothing else filled) for an event the paired exact mode did
+        not take and for every event of a single-end batch (miso_batch_get_exact_paired_element)."""
+        r = np.zeros(6)
+        n, was = C.c_int64(0), C.c_int(0)
+        L = lib()
+        L.miso_batch_get_exact_paired_element.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                                          C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        check(L.miso_batch_get_exact_paired_element(self.handle, int(i), _p(r), None, 0, C.byref(n), C.byref(was)))
+        m = np.zeros((n.value, 2))
+        if was.value and n.value:
+            check(L.miso_batch_get_exact_paired_element(self.handle, int(i), _p(r), _p(m), n.value, C.byref(n), C.byref(was)))
+        return r, m, bool(was.value)
+
     def compare_pairs(self, other, confidence_level=0.95, thresholds=(0.1, 0.2), as_text=False):
         """The posterior of delta psi = psi_1 - psi_2 over ALL pairs of this batch's draws and `other`'s (same events, same
         order; the sample counts may differ, 8192 per event at most) on the device: median, credible interval and exact
@@ -914,6 +930,49 @@ def exact_delta_groups_batches(batches1, batches2, probs=(0.5, 0.025, 0.975), z=
     h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
     check(L.miso_batch_exact_delta_groups(h1, len(b1), h2, len(b2), _p(pp), len(pp), _p(zz), len(zz), _p(out), out.size, _p(was),
                                           C.byref(ms)))
+    return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
+
+
+def exact_paired_delta_groups(group1, group2, probs=(0.5, 0.025, 0.975), z=(), max_events_per_launch=0):
+    """exact_delta_groups for PAIRED-END replicates (miso_exact_paired_delta_groups in include/miso_amd.h).
+    Each group is a list of 1 .. 8 replicates (stats6 [n_events, 6], pairs), stats6 rows (n10, n01, A0, A1, h0, h1) and
+    pairs[i] = the drawing pairs [(m0, m1), ...] of event i, as selftest_exact_paired_delta_quantiles takes one sample --
+    what Batch.exact_paired_element returns and a `.miso_exact_pairs` table holds.  All replicates hold the same events in
+    the same order."""
+    reps = [_pair_lists(st, pairs) for st, pairs in list(group1) + list(group2)]
+    n1, n2 = len(group1), len(group2)
+    n = len(reps[0][0]) if reps else 0
+    if any(len(r[0]) != n for r in reps):
+        raise ValueError("every replicate: one row of stats6 and one list of pairs per event, as many events each")
+    pp, zz, out, was = _exact_group_args(probs, z, n)
+    ms = C.c_float(0.0)
+    nb = max(len(reps), 1)
+    st = (C.c_void_p * nb)(*[r[0].ctypes.data for r in reps])
+    mm = (C.c_void_p * nb)(*[r[1].ctypes.data for r in reps])
+    oo = (C.c_void_p * nb)(*[r[2].ctypes.data for r in reps])
+    L = lib()
+    L.miso_exact_paired_delta_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    check(L.miso_exact_paired_delta_groups(st, mm, oo, n1, n2, n, _p(pp), len(pp), _p(zz), len(zz), int(max_events_per_launch),
+                                           _p(out), _p(was), C.byref(ms)))
+    return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
+
+
+def exact_paired_delta_groups_batches(batches1, batches2, probs=(0.5, 0.025, 0.975), z=()):
+    """exact_paired_delta_groups over launched paired-end Batch(exact_paired=True) objects that hold the same events in the
+    same order on one device (miso_batch_exact_paired_delta_groups): the kernels read the batches' resident pair records.
+    Nothing is stored in a batch."""
+    b1, b2 = list(batches1), list(batches2)
+    n = len(b1[0]) if b1 else (len(b2[0]) if b2 else 0)
+    pp, zz, out, was = _exact_group_args(probs, z, n)
+    ms = C.c_float(0.0)
+    L = lib()
+    L.miso_batch_exact_paired_delta_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                       C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+    h1 = (C.c_void_p * max(len(b1), 1))(*[b.handle for b in b1])
+    h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
+    check(L.miso_batch_exact_paired_delta_groups(h1, len(b1), h2, len(b2), _p(pp), len(pp), _p(zz), len(zz), _p(out), out.size,
+                                                 _p(was), C.byref(ms)))
     return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
 
 

@@ -4,6 +4,8 @@ device computes (`miso_batch_compare`, `miso_batch_summarize`).
 """
 from decimal import Decimal
 
+import numpy as np
+
 HEADER_FIELDS = ["event_name", "sample1_posterior_mean", "sample1_ci_low", "sample1_ci_high",
                  "sample2_posterior_mean", "sample2_ci_low", "sample2_ci_high", "diff",
                  "bayes_factor", "isoforms", "sample1_counts", "sample1_assigned_counts",
@@ -322,4 +324,45 @@ def read_exact_stats(filename):
             if len(v) != len(EXACT_STATS_FIELDS):
                 raise ValueError("Error: %s: malformed line %r" % (filename, line))
             out[v[0]] = (v[1] == "1", [float(x) for x in v[2:]])
+    return out
+
+
+# ---- what a paired-end exact posterior is made of, `<sample>.miso_exact_pairs` ----
+EXACT_PAIRS_FIELDS = ["event_name", "exact", "n10", "n01", "A0", "A1", "h0", "h1", "n_pairs", "pair_probs", "pairs"]
+
+
+def write_exact_pairs(filename, rows):
+    """rows: iterable of (event_name, was_exact, stats6, m [n_pairs, 2]).  One header line; every row stands alone: the six
+    statistics as repr, the number of drawing pairs, the event's distinct pair probabilities as repr in order of first use
+    (comma-separated), and the pairs in record order as `i:j` index pairs into that list -- so the table reads back to the
+    same doubles in the same order.  It grows with the drawing pairs, in the order of 10 bytes a pair."""
+    n = 0
+    with open(filename, "w") as f:
+        f.write("\t".join(EXACT_PAIRS_FIELDS) + "\n")
+        for name, was, st, m in rows:
+            index, pairs = {}, []
+            for m0, m1 in np.asarray(m, np.float64).reshape(-1, 2).tolist():
+                pairs.append("%d:%d" % (index.setdefault(m0, len(index)), index.setdefault(m1, len(index))))
+            f.write("\t".join([name, "1" if was else "0"] + [repr(float(v)) for v in st] +
+                              [str(len(pairs)), ",".join(repr(v) for v in index) or "NA", ",".join(pairs) or "NA"]) + "\n")
+            n += 1
+    return n
+
+
+def read_exact_pairs(filename):
+    """{event_name: (was_exact, [6 floats], m [n_pairs, 2])} of a `.miso_exact_pairs` table, in the file's order"""
+    out = {}
+    with open(filename) as f:
+        head = f.readline().rstrip("\n").split("\t")
+        if head != EXACT_PAIRS_FIELDS:
+            raise ValueError("Error: %s is no .miso_exact_pairs table" % filename)
+        for line in f:
+            v = line.rstrip("\n").split("\t")
+            if len(v) != len(EXACT_PAIRS_FIELDS):
+                raise ValueError("Error: %s: malformed line %r" % (filename, line))
+            probs = np.array([float(x) for x in v[9].split(",")] if v[9] != "NA" else [], np.float64)
+            idx = np.array([[int(i) for i in p.split(":")] for p in v[10].split(",")] if v[10] != "NA" else [], np.int64).reshape(-1, 2)
+            if len(idx) != int(v[8]):
+                raise ValueError("Error: %s: event %s has %d pairs, not %s" % (filename, v[0], len(idx), v[8]))
+            out[v[0]] = (v[1] == "1", [float(x) for x in v[2:8]], probs[idx].reshape(-1, 2))
     return out

@@ -101,6 +101,15 @@ void exact_delta_groups_run(const double *stats7_1, int n1, const double *stats7
                             int *was_exact, float *ms, hipStream_t st = nullptr);
 void exact_delta_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, const double *p, int n_p, const double *z, int n_z,
                         double *out, int64_t out_len, int *was_exact, float *kernel_ms);
+// kernels_exact_paired_delta_groups.hip: the same for paired-end replicates (miso_exact_paired_delta_groups,
+// miso_batch_exact_paired_delta_groups).  stats6, m, offs: n1 + n2 pointers, group 1's first, each replicate's
+// elements in miso_selftest_exact_paired's layout over the same n_events; an event is comparable when every replicate's row
+// is eligible for the paired exact mode.  out, was_exact: as above
+void exact_paired_delta_groups_given(const double *const *stats6, const double *const *m, const int64_t *const *offs, int n1, int n2,
+                                     int n_events, const double *p, int n_p, const double *z, int n_z, int max_events_per_launch,
+                                     double *out, int *was_exact, float *ms);
+void exact_paired_delta_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, const double *p, int n_p, const double *z,
+                               int n_z, double *out, int64_t out_len, int *was_exact, float *kernel_ms);
 // kernels_compare_groups.hip
 int compare_groups_staging(int n1, int n2, int S, size_t budget);
 void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double smoothing, int staging, double *out,
@@ -466,3 +475,8 @@ struct miso_batch {
     each_coop_table(f);
   }
 };
+
+// runtime.hip: an event's row {n10, n01, A0, A1, h0, h1} as the paired exact passes take it, and a launched paired-end batch's
+// side of such a pass (its resident pair records; stats6: the rows of the pass's events, on the host)
+void exact_paired_stats6(const miso_batch &b, int i, double *row);
+miso::ExactPairedCmpInput exact_paired_resident(const miso_batch &b, const double *stats6);

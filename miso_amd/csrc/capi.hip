@@ -978,6 +978,49 @@ int miso_batch_exact_delta_groups(miso_batch_t *const *group1, int n1, miso_batc
   });
 }
 
+int miso_exact_paired_delta_groups(const double *const *stats6, const double *const *m, const int64_t *const *offs, int n1, int n2,
+                                   int n_events, const double *p, int n_p, const double *z, int n_z, int max_events_per_launch,
+                                   double *out, int *was_exact, float *kernel_ms) {
+  return guarded([&] {
+    need(stats6, "stats6"); need(m, "m"); need(offs, "offs");
+    if (n_events > 0) { need(out, "out"); need(was_exact, "was_exact"); }
+    if (n_p > 0) need(p, "p");
+    if (n_z > 0) need(z, "z");
+    exact_paired_delta_groups_given(stats6, m, offs, n1, n2, n_events, p, n_p, z, n_z, max_events_per_launch, out, was_exact, kernel_ms);
+  });
+}
+
+int miso_batch_exact_paired_delta_groups(miso_batch_t *const *group1, int n1, miso_batch_t *const *group2, int n2, const double *p,
+                                         int n_p, const double *z, int n_z, double *out, int64_t out_len, int *was_exact,
+                                         float *kernel_ms) {
+  return guarded([&] {
+    need(group1, "group1"); need(group2, "group2"); need(was_exact, "was_exact");
+    if (n_p > 0) need(p, "p");
+    if (n_z > 0) need(z, "z");
+    if (out_len > 0) need(out, "out");
+    exact_paired_delta_groups(group1, n1, group2, n2, p, n_p, z, n_z, out, out_len, was_exact, kernel_ms);
+  });
+}
+
+int miso_batch_get_exact_paired_element(const miso_batch_t *b, int i, double *stats6, double *m, int64_t m_cap, int64_t *n_pairs,
+                                        int *was_exact) {
+  return guarded([&] {
+    need(b, "batch"); need(stats6, "stats6"); need(n_pairs, "n_pairs"); need(was_exact, "was_exact");
+    const PackedEvent &e = event_at(b, i);
+    if (!b->launched) MISO_FAIL(MISO_EINVAL, "batch not launched");
+    *was_exact = b->p.paired && b->exact_paired && b->event_exact(i) ? 1 : 0;
+    *n_pairs = 0;
+    if (!*was_exact) return;
+    exact_paired_stats6(*b, i, stats6);
+    *n_pairs = e.n_draw;
+    if (!m) return;
+    if (m_cap < e.n_draw) MISO_FAIL(MISO_EINVAL, "m is too short for the event's drawing pairs");
+    // (what exact_pairs_stage multiplies: the fragment-length probability at the record's index, the index clamped as there)
+    const int top = static_cast<int>(b->fd.prob.size()) - 1;
+    for (size_t r = 0; r < 2 * static_cast<size_t>(e.n_draw); r++) m[r] = b->fd.prob[std::min<int>(e.draw_frag[r], top)];
+  });
+}
+
 int miso_batch_compare_ms(const miso_batch_t *b, float *compare_ms, float *exact_compare_ms) {
   return guarded([&] {
     need(b, "batch");

@@ -20,7 +20,8 @@
 // interpolation; thread 0 of an event also writes the group means, H(0.0) and H(z_j) after the first launch.
 // No workgroup has more than one wavefront: no barrier in divergent control flow, no cooperative launch, no atomics.  f64, no
 // contraction, miso_det_exp / miso_det_log, IEEE division, no inline assembly.  tests/_exact_delta_groups_ref.py restates it
-// and the two agree bit for bit (tests/test_gpu_exact_delta_groups.py).
+// and the two agree bit for bit (tests/test_gpu_exact_delta_groups.py).  The limits, the row's layout and the launch of
+// exact_groups_update are in exact_delta_groups.hpp, shared with the paired-end unit (kernels_exact_paired_delta_groups.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,36 +36,10 @@
 #include "miso_detmath.h"
 
 #include "exact_delta.hpp"
+#include "exact_delta_groups.hpp"
 #include "hip_host.hpp"
 
 namespace miso {
-
-constexpr int EXACT_GROUP_MAX = 8;                                  // replicates a group
-// a replicate's row of the workspace, in doubles: F, f, then {tm, gmax, tL, tR, h, Z, mean0, mean1, sf}, the window's width in
-// psi, {am1, bm1, a, b, c, n, e0, e1}
-constexpr int EXACT_GROUPS_SCALARS = 18;
-constexpr int EXACT_GROUPS_ROW = 2 * EXACT_PAD + EXACT_GROUPS_SCALARS;
-// the sweeps of the first launch: slot 0 H(0.0), slot 1 round 1, slot 2 the caller's points; later slot k = probability k
-constexpr int EXACT_GROUPS_FIRST_SLOTS = 3;
-// what one launch range holds on the device at most (workspace, the pairs' H and the brackets)
-constexpr size_t EXACT_GROUPS_WORK_BYTES = size_t{256} << 20;
-
-__device__ __forceinline__ void exact_groups_store_scalars(double *s, const ExactTable &T, double w, const ExactStats &st) {
-  s[0] = T.tm; s[1] = T.gmax; s[2] = T.tL; s[3] = T.tR; s[4] = T.h; s[5] = T.Z; s[6] = T.mean0; s[7] = T.mean1; s[8] = T.sf;
-  s[9] = w;
-  s[10] = st.am1; s[11] = st.bm1; s[12] = st.a; s[13] = st.b; s[14] = st.c; s[15] = st.n; s[16] = st.e0; s[17] = st.e1;
-}
-__device__ __forceinline__ ExactTable exact_groups_load_table(const double *s, const double *F, const double *f) {
-  ExactTable T;
-  T.tm = s[0]; T.gmax = s[1]; T.tL = s[2]; T.tR = s[3]; T.h = s[4]; T.Z = s[5]; T.mean0 = s[6]; T.mean1 = s[7]; T.sf = s[8];
-  T.F = F; T.f = f;
-  return T;
-}
-__device__ __forceinline__ ExactStats exact_groups_load_stats(const double *s) {
-  ExactStats st;
-  st.am1 = s[10]; st.bm1 = s[11]; st.a = s[12]; st.b = s[13]; st.c = s[14]; st.n = s[15]; st.e0 = s[16]; st.e1 = s[17];
-  return st;
-}
 
 // One workgroup = one wavefront = one (event, replicate) of the launch's ne events.  stats7: nb rows of {n10, n01, n, e0, e1,
 // h0, h1} per event, group 1's first; ws: nb rows of EXACT_GROUPS_ROW doubles per event
@@ -185,6 +160,13 @@ __global__ __launch_bounds__(64) void exact_groups_update(const double *ws, cons
   }
 }
 
+void exact_groups_update_launch(hipStream_t st, const double *ws, const double *Hp, const double *prob, int n_p, int n_z, int n1, int n2,
+                                int ne, int n_slots, int round, ExactBracket *br, double *out) {
+  hipLaunchKernelGGL(exact_groups_update, dim3((ne * n_p + 63) / 64), dim3(64), 0, st, ws, Hp, prob, n_p, n_z, n1, n2, ne, n_slots, round,
+                     br, out);
+  HIP_OK(hipGetLastError());
+}
+
 // Rows [event][replicate][7] of the two groups; take (may be null): per event, whether the caller lets it be compared at all.
 // An event is comparable when every row is eligible and all rows carry bit-equal (e0, e1); every other event keeps its row of
 // out and gets was_exact = 0.  The comparable ones go to the device in ranges of at most `per_launch` events.
@@ -245,9 +227,7 @@ void exact_delta_groups_run(const double *stats7_1, int n1, const double *stats7
       hipLaunchKernelGGL(exact_groups_sweep, dim3(ne * np_pairs * (first ? 1 : n_p)), dim3(64), 0, call.st, d_ws, d_br, d_z, n_z, n1,
                          n2, ne, n_p, n_slots, first, d_hp);
       HIP_OK(hipGetLastError());
-      hipLaunchKernelGGL(exact_groups_update, dim3((ne * n_p + 63) / 64), dim3(64), 0, call.st, d_ws, d_hp, d_p, n_p, n_z, n1, n2, ne,
-                         n_slots, round, d_br, d_o);
-      HIP_OK(hipGetLastError());
+      exact_groups_update_launch(call.st, d_ws, d_hp, d_p, n_p, n_z, n1, n2, ne, n_slots, round, d_br, d_o);
     }
   }
   call.stop();

@@ -1561,12 +1561,12 @@ static bool exact_paired_ok(const miso_batch &a, const miso_batch &b) {
 }
 static const char *const EXACT_SINGLE_MSG = "Both batches to compare exactly must have run with the exact-posterior mode";
 static const char *const EXACT_PAIRED_MSG = "Both batches to compare exactly must be paired-end and have run with the paired exact-posterior mode";
-static void exact_paired_stats6(const miso_batch &b, int i, double *row) {
+void exact_paired_stats6(const miso_batch &b, int i, double *row) {
   const PackedEvent &e = b.events[i];
   const double r[6] = {static_cast<double>(e.base_count[0]), static_cast<double>(e.base_count[1]), e.eff[0], e.eff[1], e.hyper[0], e.hyper[1]};
   std::memcpy(row, r, sizeof r);
 }
-static ExactPairedCmpInput exact_paired_resident(const miso_batch &b, const double *stats6) {
+ExactPairedCmpInput exact_paired_resident(const miso_batch &b, const double *stats6) {
   return ExactPairedCmpInput{stats6, nullptr, nullptr, b.d_events, b.d_in, b.d_fp, static_cast<int>(b.fd.prob.size())};
 }
 

@@ -134,10 +134,12 @@ class GenesDispatcher(object):
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                  exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                 delta_posterior=False, exact_delta_posterior=False, exact_stats=False):
+                 delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False):
         # --exact-stats: beside the outputs the `.miso_exact_stats` table (compare.py) of every directory of `.miso` files,
         # merged like a diagnostics table
         self.exact_stats = bool(exact_stats)
+        # --exact-paired-stats: the same for the paired exact mode, the `.miso_exact_pairs` table (no --compare)
+        self.exact_paired_stats = bool(exact_paired_stats)
         self.exact_paired = bool(exact_paired)     # --exact-paired: handed on to every worker
         # --exact-delta-posterior: beside the `.miso_bf_exact` table the `.miso_dpsi_exact` (compare.py), merged like it
         self.exact_delta_posterior = bool(exact_delta_posterior)
@@ -300,6 +302,10 @@ class GenesDispatcher(object):
                 label = os.path.basename(os.path.normpath(d))
                 stables.append((os.path.join(d, "summary", label + ".miso_exact_stats"), []))
                 os.makedirs(os.path.dirname(stables[-1][0]), exist_ok=True)
+        if self.exact_paired_stats:    # --exact-paired-stats: (the `.miso_exact_pairs` table, its per-worker parts); no --compare
+            label = os.path.basename(os.path.normpath(self.output_dir))
+            ptable = (os.path.join(self.output_dir, "summary", label + ".miso_exact_pairs"), [])
+            os.makedirs(os.path.dirname(ptable[0]), exist_ok=True)
         for batch_num, (fname, size, first) in enumerate(batches):
             if size == 0:
                 continue
@@ -349,6 +355,9 @@ class GenesDispatcher(object):
                 if stables:
                     stables[0][1].append("%s.gpu%d" % (stables[0][0], batch_num))
                     cmd += ["--exact-stats-file", stables[0][1][-1]]
+                if self.exact_paired_stats:
+                    ptable[1].append("%s.gpu%d" % (ptable[0], batch_num))
+                    cmd += ["--exact-pairs-file", ptable[1][-1]]
             # more chunks than GPUs (-p above the GPU count) share the GPUs round robin
             cmd += ["--read-len", str(self.read_len), "--device", str(batch_num % self.n_gpus),
                     "--first-event-id", str(first)]
@@ -371,7 +380,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
-        self.diag_tables += xtable + dtable + etable + stables
+        self.diag_tables += xtable + dtable + etable + stables + ([ptable] if self.exact_paired_stats else [])
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -444,7 +453,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                           exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                          delta_posterior=False, exact_delta_posterior=False, exact_stats=False):
+                          delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -459,7 +468,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
                            delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
                            delta_posterior=delta_posterior, exact_delta_posterior=exact_delta_posterior,
-                           exact_stats=exact_stats).run()
+                           exact_stats=exact_stats, exact_paired_stats=exact_paired_stats).run()
 
 
 def main(argv=None):
@@ -503,6 +512,11 @@ def main(argv=None):
                          "the event's read pairs, is tabulated once per event on the GPU and the .miso file's samples are "
                          "independent draws from it (percent_accept=100); other events are sampled as always.  Also the "
                          "settings key `exact_paired` under [sampler].")
+    ap.add_argument("--exact-paired-stats", action="store_true",
+                    help="with --exact-paired (and without --compare): also write OUT/summary/<OUT>.miso_exact_pairs: per event the "
+                         "six statistics and the drawing pairs' probabilities its exact posterior is made of, what `samples_utils "
+                         "--compare-groups --exact-paired-delta-posterior` pools replicates of separate runs from.  The table "
+                         "grows with the drawing pairs, in the order of 10 bytes a pair; every other output is unchanged")
     ap.add_argument("--exact-compare", action="store_true",
                     help="with --compare and the exact mode: also write OUT/<l1>_vs_<l2>/bayes-factors/<l1>_vs_<l2>.miso_bf_exact -- "
                          "for the events the exact mode took in both samples the Bayes factor and P(|delta Psi| >= T) come from the "
@@ -545,6 +559,12 @@ def main(argv=None):
         ap.error("--rank-diagnostics goes with --diagnostics")
     if a.exact_stats and (a.paired_end or not (a.exact or Settings.get_exact())):
         ap.error("--exact-stats needs the exact-posterior mode of single-end runs (--exact, or `exact = True` in the settings)")
+    if a.exact_paired_stats:
+        if a.paired_end is None or not (a.exact_paired or Settings.get_exact_paired()):
+            ap.error("--exact-paired-stats needs the paired exact-posterior mode (--paired-end with --exact-paired, or "
+                     "`exact_paired = True` in the settings)")
+        if a.compare is not None:
+            ap.error("--exact-paired-stats does not go with --compare")
     if a.exact_compare:
         if a.compare is None:
             ap.error("--exact-compare goes with --compare")
@@ -596,7 +616,7 @@ def main(argv=None):
                                        exact_paired=a.exact_paired,
                                        delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics,
                                        delta_posterior=a.delta_posterior, exact_delta_posterior=a.exact_delta_posterior,
-                                       exact_stats=a.exact_stats)
+                                       exact_stats=a.exact_stats, exact_paired_stats=a.exact_paired_stats)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

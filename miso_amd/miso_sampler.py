@@ -367,7 +367,8 @@ class MISOSampler:
                    ",".join(str(iso.genomic_end) for iso in gene.isoforms)))
 
     def output_batch(self, state, verbose=False, summary_file=None, confidence_level=0.95, threads=0,
-                     write_files=True, diagnostics_file=None, rank_diagnostics=False, exact_stats_file=None):
+                     write_files=True, diagnostics_file=None, rank_diagnostics=False, exact_stats_file=None,
+                     exact_pairs_file=None):
         """The `.miso` files and / or the summary table of a launched batch.  The header's run-dependent fields are
         formatted natively for the whole batch (miso_batch_header_fields); miso_header() below is the same line field
         by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte).
@@ -375,12 +376,16 @@ class MISOSampler:
         samples resident on the device; nothing else changes with it.  rank_diagnostics: that table with the six columns
         of the rank-normalised pass.  exact_stats_file: the `.miso_exact_stats` table of the written events
         (compare.write_exact_stats): the seven statistics an exact posterior is made of, as the batch holds them
-        (Batch.exact_stats), and whether the exact mode took the event; nothing else changes with it."""
+        (Batch.exact_stats), and whether the exact mode took the event; nothing else changes with it.
+        exact_pairs_file: the `.miso_exact_pairs` table of the written events (compare.write_exact_pairs), the same for the
+        paired exact mode: the six statistics and the drawing pairs' probabilities (Batch.exact_paired_element)."""
         batch, slots, written, num_iters, burn_in, lag = state
-        stat_rows = []
+        stat_rows, pair_rows = [], []
         if not slots:
             if exact_stats_file is not None:
                 compare.write_exact_stats(exact_stats_file, stat_rows)
+            if exact_pairs_file is not None:
+                compare.write_exact_pairs(exact_pairs_file, pair_rows)
             return written
         timing = os.environ.get("MISO_TIMING")
         t1 = time.time()
@@ -433,6 +438,9 @@ class MISOSampler:
             if exact_stats_file is not None:
                 st, was = batch.exact_stats(idx)
                 stat_rows.append((os.path.basename(out)[:-len(".miso")], was, st))
+            if exact_pairs_file is not None:
+                st, m, was = batch.exact_paired_element(idx)
+                pair_rows.append((os.path.basename(out)[:-len(".miso")], was, st, m))
         t2 = time.time()
         if write_files:
             batch.write_miso_files(idxs, paths, headers, threads)
@@ -442,6 +450,8 @@ class MISOSampler:
             diagnostics.write_diagnostics(diagnostics_file, diag_rows, rank=rank_diagnostics)
         if exact_stats_file is not None:
             compare.write_exact_stats(exact_stats_file, stat_rows)
+        if exact_pairs_file is not None:
+            compare.write_exact_pairs(exact_pairs_file, pair_rows)
         if timing:
             print("[miso] batch of %d events: headers %.2f s, .miso files / table %.2f s"
                   % (len(slots), t2 - t1, time.time() - t2))

@@ -147,7 +147,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      overhang_len, paired_end=None, event_type=None, verbose=True, bamfile=None,
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
-                     diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False, exact_stats_file=None):
+                     diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False, exact_stats_file=None,
+                     exact_pairs_file=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
@@ -157,12 +158,17 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     exact_paired: the same switch for the paired-end two-isoform events of a --paired-end run (None: the settings'
     `exact_paired` key); nothing on a single-end run.
     exact_stats_file (the single-end exact mode only): also write the `.miso_exact_stats` table of the written events
-    (compare.write_exact_stats), parts merged like the diagnostics table's."""
+    (compare.write_exact_stats), parts merged like the diagnostics table's.
+    exact_pairs_file (the paired exact mode only): also write the `.miso_exact_pairs` table of the written events
+    (compare.write_exact_pairs), parts merged the same way."""
     exact = Settings.get_exact() if exact is None else bool(exact)
     if exact_stats_file is not None and (paired_end or not exact):
         raise ValueError("the exact statistics table needs the exact-posterior mode (single-end)")
     stat_parts = []
     exact_paired = Settings.get_exact_paired() if exact_paired is None else bool(exact_paired)
+    if exact_pairs_file is not None and not (paired_end and exact_paired):
+        raise ValueError("the exact pairs table needs the paired exact-posterior mode (paired-end)")
+    pair_parts = []
     os.makedirs(output_dir, exist_ok=True)
     if gene_entries is None:
         gene_entries = [(g, gff_index_filename) for g in gene_ids]
@@ -278,12 +284,16 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             spart = None if exact_stats_file is None else "%s.part%06d" % (exact_stats_file, lo)
             if spart:
                 stat_parts.append(spart)
+            ppart = None if exact_pairs_file is None else "%s.part%06d" % (exact_pairs_file, lo)
+            if ppart:
+                pair_parts.append(ppart)
             launched = gpu.submit(sampler.launch_batch, state, seed=seed, first_event_id=first_event_id + lo)
 
-            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart, spart=spart):
+            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart, spart=spart, ppart=ppart):
                 launched.result()
                 return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files,
-                                            diagnostics_file=dpart, rank_diagnostics=rank_diagnostics, exact_stats_file=spart)
+                                            diagnostics_file=dpart, rank_diagnostics=rank_diagnostics, exact_stats_file=spart,
+                                            exact_pairs_file=ppart)
             in_flight.append(out.submit(outputs))
         for f in in_flight:
             written += f.result()
@@ -296,6 +306,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
         merge_tables(diag_parts, diagnostics_file)
     if exact_stats_file is not None:
         merge_tables(stat_parts, exact_stats_file)
+    if exact_pairs_file is not None:
+        merge_tables(pair_parts, exact_pairs_file)
     t2 = time.time()
     if verbose:
         print("Collected %d events in %.2f s (beside the decoding / sampling), batches prepared in %.2f s, whole run %.2f s"
@@ -535,6 +547,10 @@ def main(argv=None):
                          "table, per event the seven statistics its exact posterior is made of")
     ap.add_argument("--exact-stats-files", nargs=2, default=None, metavar=("FILE1", "FILE2"),
                     help="with --compare-genes-from-file and the exact mode (single-end): that table of each sample")
+    ap.add_argument("--exact-pairs-file", default=None, metavar="F",
+                    help="with --compute-genes-from-file and the paired exact mode (--paired-end, --exact-paired): also write the "
+                         "`.miso_exact_pairs` table, per event the six statistics and the drawing pairs' probabilities its exact "
+                         "posterior is made of (in the order of 10 bytes a pair)")
     ap.add_argument("--exact-comparison-file", default=None, metavar="F",
                     help="with --compare-genes-from-file and the exact mode: also write the exact comparison's table "
                          "(Bayes factors and P(|delta psi| >= T) from the posteriors' tables, no sampling error)")
@@ -593,6 +609,9 @@ def main(argv=None):
     if a.exact_stats_files is not None and (not a.compare_genes_from_file or paired_end or not exact):
         print("Error: --exact-stats-files goes with --compare-genes-from-file and the exact mode (single-end).")
         return 1
+    if a.exact_pairs_file is not None and (not a.compute_genes_from_file or not exact_paired):
+        print("Error: --exact-pairs-file goes with --compute-genes-from-file and the paired exact mode (--paired-end, --exact-paired).")
+        return 1
     if a.delta_posterior_file is not None and not a.compare_genes_from_file:
         print("Error: --delta-posterior-file goes with --compare-genes-from-file.")
         return 1
@@ -634,7 +653,8 @@ def main(argv=None):
                          summary_file=a.summary_file,
                          write_files=not (a.no_miso_files and a.summary_file),
                          diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired,
-                         rank_diagnostics=a.rank_diagnostics, exact_stats_file=a.exact_stats_file)
+                         rank_diagnostics=a.rank_diagnostics, exact_stats_file=a.exact_stats_file,
+                         exact_pairs_file=a.exact_pairs_file)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")

@@ -35,6 +35,7 @@ two groups gets the file the pairwise call writes, byte for byte, but every tree
 summarised once per chunk of events, and all pairs of a chunk come out of one launch (capi.compare_groups).
 With `--exact-delta-posterior` the two groups also get `<A>_vs_<B>.miso_group_dpsi_exact`: delta psi pooled over all pairs of
 replicates from their exact posteriors, without a draw, from each directory's `summary/<name>.miso_exact_stats`.
+`--exact-paired-delta-posterior` is the same for paired-end replicates, from `summary/<name>.miso_exact_pairs`.
 With `--delta-posterior` every pair also gets its `.miso_dpsi`, and the two groups one pooled table, `.miso_group_dpsi`: delta
 psi over all differences between the pooled draws of the groups (capi.compare_pairs_groups).
 """
@@ -985,6 +986,57 @@ def output_group_exact_delta(dirs1, dirs2, output_dir, delta_thresholds=None, gr
     return out, compare.write_group_dpsi_exact(out, [rows[n] for n in names], thresholds)
 
 
+def exact_pairs_path(sample_dir):
+    """where `miso --run ... --paired-end M SD --exact-paired --exact-paired-stats` leaves a sample directory's table"""
+    return os.path.join(sample_dir, "summary", os.path.basename(os.path.normpath(sample_dir)) + ".miso_exact_pairs")
+
+
+def check_exact_pairs_tables(dirs1, dirs2):
+    """ValueError, before any work, unless both groups have 1 .. 8 directories and each holds its `.miso_exact_pairs` table"""
+    for which, dirs in enumerate((dirs1, dirs2)):
+        if not 1 <= len(dirs) <= MAX_EXACT_GROUP:
+            raise ValueError("Error: --exact-paired-delta-posterior pools between 1 and %d replicates a group, group %d has %d"
+                             % (MAX_EXACT_GROUP, which + 1, len(dirs)))
+    for d in list(dirs1) + list(dirs2):
+        if not os.path.isfile(exact_pairs_path(d)):
+            raise ValueError("Error: %s has no %s (written by miso --run ... --paired-end M SD --exact-paired --exact-paired-stats)"
+                             % (d, os.path.relpath(exact_pairs_path(d), d)))
+
+
+def output_group_exact_paired_delta(dirs1, dirs2, output_dir, delta_thresholds=None, group_names=None):
+    """--compare-groups --exact-paired-delta-posterior: output_group_exact_delta for paired-end replicates
+    (capi.exact_paired_delta_groups), from each sample directory's `.miso_exact_pairs` table: the same pooled
+    table, the events grouped by which replicates have them with exact = 1, one device call per such pattern.  An event without
+    such a replicate on a side prints NA.  Returns (path, n_rows)."""
+    check_exact_pairs_tables(dirs1, dirs2)
+    thresholds = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
+    group_names = tuple(group_names or DEFAULT_GROUP_NAMES)
+    tables = [[compare.read_exact_pairs(exact_pairs_path(d)) for d in dirs] for dirs in (dirs1, dirs2)]
+    names = sorted(set().union(*[t.keys() for g in tables for t in g]))
+    patterns = {}
+    for name in names:
+        have = tuple(tuple(r for r, t in enumerate(g) if name in t and t[name][0]) for g in tables)
+        patterns.setdefault(have, []).append(name)
+    rows = {}
+    n_none = 0
+    for have, evs in patterns.items():
+        if not have[0] or not have[1]:
+            n_none += len(evs)
+            for name in evs:
+                rows[name] = (name, len(have[0]), len(have[1]), None, {})
+            continue
+        groups = [[([tables[g][r][name][1] for name in evs], [tables[g][r][name][2] for name in evs]) for r in have[g]] for g in (0, 1)]
+        res = capi.exact_paired_delta_groups(groups[0], groups[1], compare.EXACT_DPSI_PROBS, compare.delta_points(thresholds))
+        for j, name in enumerate(evs):
+            rows[name] = (name, len(have[0]), len(have[1]), res.row(j), {})
+    if n_none:
+        print("Notice: %d event(s) have no replicate with an exact posterior in one of the groups: NA in the pooled table" % n_none)
+    name = "%s_vs_%s" % group_names
+    out = os.path.join(output_dir, name, "delta-psi", name + ".miso_group_dpsi_exact")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    return out, compare.write_group_dpsi_exact(out, [rows[n] for n in names], thresholds)
+
+
 def parse_group_args(compare_groups, group_labels_arg=None):
     """`--compare-groups DIR[,DIR...] DIR[,DIR...] OUTPUT_DIR [--group-labels L[,L...] L[,L...]]` ->
     (dirs1, dirs2, output_dir, labels1, labels2); the labels are checked (group_labels) before anything is read."""
@@ -1027,9 +1079,13 @@ def main(argv=None):
                     help="with --compare-groups: also the pooled table <A>_vs_<B>.miso_group_dpsi_exact of delta psi over all "
                          "pairs of replicates from their exact posteriors, without a draw -- from every sample directory's "
                          "summary/<name>.miso_exact_stats, which miso --run ... --exact --exact-stats writes")
+    ap.add_argument("--exact-paired-delta-posterior", action="store_true",
+                    help="with --compare-groups, for paired-end replicates: the same pooled table from every sample directory's "
+                         "summary/<name>.miso_exact_pairs, which miso --run ... --paired-end M SD --exact-paired "
+                         "--exact-paired-stats writes (not together with --exact-delta-posterior)")
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
-                    help="the thresholds T of --delta-posterior and --exact-delta-posterior, each in (0, 1), at most four "
-                         "(default 0.1 0.2)")
+                    help="the thresholds T of --delta-posterior, --exact-delta-posterior and --exact-paired-delta-posterior, each "
+                         "in (0, 1), at most four (default 0.1 0.2)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.delta_posterior and not (a.compare_samples or a.compare_groups):      # argument errors, before any work
@@ -1038,10 +1094,14 @@ def main(argv=None):
                  "(--delta-posterior goes with --compare-samples, and with --compare-groups)")
     if a.exact_delta_posterior and not a.compare_groups:
         ap.error("--exact-delta-posterior goes with --compare-groups")
-    if a.group_names and not (a.compare_groups and (a.delta_posterior or a.exact_delta_posterior)):
+    if a.exact_paired_delta_posterior and not a.compare_groups:
+        ap.error("--exact-paired-delta-posterior goes with --compare-groups")
+    if a.exact_paired_delta_posterior and a.exact_delta_posterior:
+        ap.error("one of --exact-delta-posterior (single-end replicates) and --exact-paired-delta-posterior (paired-end), not both")
+    if a.group_names and not (a.compare_groups and (a.delta_posterior or a.exact_delta_posterior or a.exact_paired_delta_posterior)):
         ap.error("--group-names goes with --compare-groups --delta-posterior (or --exact-delta-posterior)")
     if a.delta_psi_thresholds is not None:
-        if not (a.delta_posterior or a.exact_delta_posterior):
+        if not (a.delta_posterior or a.exact_delta_posterior or a.exact_paired_delta_posterior):
             ap.error("--delta-psi-thresholds goes with --delta-posterior")
         try:
             compare.check_delta_thresholds(a.delta_psi_thresholds)
@@ -1076,6 +1136,8 @@ def main(argv=None):
             dirs1, dirs2, out_dir, l1, l2 = parse_group_args(a.compare_groups, a.group_labels)
             if a.exact_delta_posterior:
                 check_exact_stats_tables(dirs1, dirs2)
+            if a.exact_paired_delta_posterior:
+                check_exact_pairs_tables(dirs1, dirs2)
         except ValueError as err:
             ap.error(str(err))
         for out, n in output_group_comparisons(dirs1, dirs2, out_dir, l1, l2, device=a.device, delta_thresholds=thr,
@@ -1083,6 +1145,9 @@ def main(argv=None):
             print("Compared %d events into %s" % (n, out))
         if a.exact_delta_posterior:
             print("Pooled %d events into %s" % output_group_exact_delta(
+                dirs1, dirs2, out_dir, delta_thresholds=a.delta_psi_thresholds, group_names=a.group_names)[::-1])
+        if a.exact_paired_delta_posterior:
+            print("Pooled %d events into %s" % output_group_exact_paired_delta(
                 dirs1, dirs2, out_dir, delta_thresholds=a.delta_psi_thresholds, group_names=a.group_names)[::-1])
     elif a.group_labels:
         ap.error("--group-labels goes with --compare-groups")
