@@ -209,8 +209,10 @@ int miso_batch_set_collapsed(miso_batch_t *batch, int on);
    over the reads' assignments is a density of one variable,
        log p(x) = (n10 + h0 - 1) log x + (n01 + h1 - 1) log(1 - x) - n log(x e0 + (1 - x) e1) + const
    (n10 / n01 reads compatible with isoform 0 / 1 only, n all reads with a compatible isoform, e the effective lengths,
-   h the Dirichlet hyperparameters).  An eligible event -- two isoforms, both effective lengths > 0, both
-   hyperparameters >= 1 (miso_exact_eligible) -- runs no chain: the density is tabulated once on a grid in logit space
+   h the Dirichlet hyperparameters).  An eligible event -- two isoforms, both hyperparameters in [1, 2^20], both effective
+   lengths in [2^-40, 2^40] and within a factor 2^20 of each other (the fence of DESIGN.md section 15: inside it the scheme
+   keeps its stated accuracy at any counts; an infinity or a NaN is outside; miso_exact_eligible) -- runs no chain: the
+   density is tabulated once on a grid in logit space
    and the event's noSamples rows are INDEPENDENT draws from it, row s by inverting the CDF at the uniform of
    (seed, event id, sample s, MISO_SITE_EXACT).  What such an event returns: samples as ever (row order = sample
    index); logLik[s] = the MARGINAL score log p at the sample with the Dirichlet normaliser, not a joint score with an
@@ -221,7 +223,9 @@ int miso_batch_set_collapsed(miso_batch_t *batch, int on);
    takes the eligible events, collapsed the rest it would have taken.  Before miso_batch_launch; MISO_EINVAL for
    paired-end batches and for algorithm != MISO_ALGO_REASSIGN. */
 int miso_batch_set_exact(miso_batch_t *batch, int on);
-/* the eligibility rule on its own (host arithmetic, no device): eff_len / hyper: noiso doubles each */
+/* the eligibility rule on its own (host arithmetic, no device): eff_len / hyper: noiso doubles each.  Every entry point that
+   takes raw statistics (the miso_selftest_exact* calls, the exact comparisons) answers an element outside it with
+   MISO_EINVAL; a batch in the mode leaves such an event to the sampler; the replicate-group calls report was_exact = 0. */
 int miso_exact_eligible(int paired, int noiso, const double *eff_len, const double *hyper, int *eligible);
 /* After miso_batch_sync: posterior mean and the quantiles (1 - confidence_level) / 2 and 1 - (1 - confidence_level) / 2
    of an event the exact mode took, from the grid itself: no Monte-Carlo error.  mean / ci_low / ci_high: two doubles
@@ -237,8 +241,9 @@ int miso_batch_get_exact_summary(miso_batch_t *batch, int event_index, double *m
                   - n log(x A0 + (1 - x) A1) + const
    (n10 / n01 pairs compatible with isoform 0 / 1 only; the sum over the pairs compatible with both, m their
    fragment-length probabilities under the two isoforms; n all pairs with a compatible isoform; A_k = exp(assscores_k),
-   miso_paired.c:403-419).  An eligible event -- two isoforms, A0, A1 > 0, both hyperparameters >= 1, no pair on a
-   non-finite score entry (miso_exact_paired_eligible) -- runs no chain: one wavefront tabulates the density (which may
+   miso_paired.c:403-419).  An eligible event -- two isoforms, both hyperparameters in [1, 2^20], A0 and A1 in
+   [2^-40, 2^40] and within a factor 2^20 of each other (the single-end mode's fence), no pair on a non-finite score
+   entry (miso_exact_paired_eligible) -- runs no chain: one wavefront tabulates the density (which may
    have SEVERAL modes) and row s of the samples inverts the CDF at the uniform of (seed, event id, sample s,
    MISO_SITE_EXACT).  logLik[s] = log p at the sample with the Dirichlet normaliser and without psi-free constants: the
    MARGINAL log density, not the reference's joint score -- the additive terms of quirk C5 are absent by construction;

@@ -47,9 +47,22 @@ void exact_check_prob(const double *prob, int n_prob);   // MISO_EINVAL unless e
 // out: 5 + n_z doubles per pair
 void exact_compare_run(const double *stats7_1, const double *stats7_2, int n, const double *z, int n_z, double *out,
                        hipStream_t st = nullptr, float *ms = nullptr);
+// The fence of both exact-posterior modes (DESIGN.md 15 "The fence"): a hyperparameter counts like reads of its isoform and is
+// bounded like few of them; an effective length (paired: A) and the ratio of the two are bounded so that the mode stays within
+// +-36.6 in logit space and no term of the log density rounds by more than the counts' own terms do.  Every comparison is
+// false for a NaN, and the upper bounds refuse an infinity.
+constexpr double EXACT_HYPER_MAX = 1048576.0;                       // 2^20
+constexpr double EXACT_LEN_MAX = 1099511627776.0;                   // 2^40
+constexpr double EXACT_LEN_MIN = 1.0 / 1099511627776.0;             // 2^-40
+constexpr double EXACT_LEN_RATIO_MAX = 1048576.0;                   // 2^20
+inline bool exact_fence(const double *len, const double *hyper) {
+  for (int k = 0; k < 2; k++)
+    if (!(hyper[k] >= 1 && hyper[k] <= EXACT_HYPER_MAX && len[k] >= EXACT_LEN_MIN && len[k] <= EXACT_LEN_MAX)) return false;
+  return len[0] <= EXACT_LEN_RATIO_MAX * len[1] && len[1] <= EXACT_LEN_RATIO_MAX * len[0];
+}
 // the exact-posterior mode takes such an event (include/miso_amd.h miso_exact_eligible)
 inline bool exact_eligible(bool paired, int K, const double *eff, const double *hyper) {
-  return !paired && K == 2 && eff[0] > 0 && eff[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1;
+  return !paired && K == 2 && exact_fence(eff, hyper);
 }
 // kernels_exact_paired.hip: the paired-end exact-posterior mode (miso_batch_set_exact_paired).  Its posterior stage on its
 // own: ka != null -- the events of ka's list, A2 their A0, A1 on the device (exact summaries); otherwise caller-given
@@ -61,7 +74,7 @@ const void *exact_paired_sample_fn();   // the kernel exact_paired_sample(Kernel
 constexpr double EXACT_PAIRED_MIN_PROB = 1.0 / 9223372036854775808.0;   // 2^-63
 // the paired mode takes such an event (include/miso_amd.h miso_exact_paired_eligible); A = exp(assscores)
 inline bool exact_paired_eligible(int K, const double *A, const double *hyper, bool any_bad) {
-  return K == 2 && A[0] > 0 && A[1] > 0 && hyper[0] >= 1 && hyper[1] >= 1 && !any_bad;
+  return K == 2 && exact_fence(A, hyper) && !any_bad;
 }
 // n elements given by a caller: MISO_EINVAL unless every row of stats6 is eligible and -- offs != null: caller-given pairs --
 // the offsets start at 0 and ascend and the probabilities m lie in [2^-63, 1]; returns the number of caller-given pairs

@@ -1352,6 +1352,9 @@ int miso_selftest_exact(const double *stats7, int n, const double *prob, int n_p
   return guarded([&] {
     if (n > 0) need(stats7, "stats7");
     if (n_prob > 0) need(prob, "prob");
+    for (int i = 0; i < n; i++)
+      if (!exact_eligible(false, 2, stats7 + 7 * static_cast<size_t>(i) + 3, stats7 + 7 * static_cast<size_t>(i) + 5))
+        MISO_FAIL(MISO_EINVAL, "An element is not eligible for the exact-posterior mode");
     exact_probe_run(stats7, n, prob, n_prob, out8, icdf);
   });
 }

@@ -9,7 +9,7 @@ are then added in block order, as the kernel adds them.  Test infrastructure onl
 """
 import numpy as np
 
-from _exact_ref import DROP, G, LANES, CELLS, T_MODE, SITE_GIBBS, ITER_INIT, Posterior, Stats
+from _exact_ref import DROP, G, LANES, CELLS, T_MODE, SITE_GIBBS, ITER_INIT, Posterior, Stats, fence
 
 BLOCK = 16          # exact_paired.hpp EXP_BLOCK
 PASSES = 2          # EXP_PASSES
@@ -19,7 +19,7 @@ MIN_PROB = 2.0 ** -63
 
 def eligible(K, A, hyper, any_bad=False):
     """include/miso_amd.h miso_exact_paired_eligible"""
-    return K == 2 and all(a > 0 for a in A[:2]) and all(h >= 1 for h in hyper[:2]) and not any_bad
+    return K == 2 and fence(A, hyper) and not any_bad
 
 
 class PairedStats:

@@ -46,9 +46,21 @@ def lgamma(x):
     return float(_libm.lgamma(float(x)))
 
 
+HYPER_MAX = 2.0 ** 20                      # csrc/batch.hpp EXACT_HYPER_MAX
+LEN_MIN, LEN_MAX = 2.0 ** -40, 2.0 ** 40    # EXACT_LEN_MIN, EXACT_LEN_MAX
+LEN_RATIO_MAX = 2.0 ** 20                   # EXACT_LEN_RATIO_MAX
+
+
+def fence(length, hyper):
+    """csrc/batch.hpp exact_fence: both hyperparameters in [1, 2^20], both lengths in [2^-40, 2^40] and within a factor 2^20
+    of each other (false for a NaN, an infinity)"""
+    return (all(1 <= h <= HYPER_MAX for h in hyper[:2]) and all(LEN_MIN <= e <= LEN_MAX for e in length[:2])
+            and length[0] <= LEN_RATIO_MAX * length[1] and length[1] <= LEN_RATIO_MAX * length[0])
+
+
 def eligible(paired, K, eff, hyper):
-    """include/miso_amd.h miso_exact_eligible: single-end, two isoforms, both effective lengths > 0, both hyperparameters >= 1"""
-    return (not paired) and K == 2 and all(e > 0 for e in eff[:2]) and all(h >= 1 for h in hyper[:2])
+    """include/miso_amd.h miso_exact_eligible: single-end, two isoforms, effective lengths and hyperparameters inside the fence"""
+    return (not paired) and K == 2 and fence(eff, hyper)
 
 
 class Stats:

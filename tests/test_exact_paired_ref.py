@@ -13,6 +13,7 @@ import pytest
 from _exact_paired_ref import (PairedPosterior, PairedStats, eligible, simulated_case, synthetic_cases)
 from _exact_ref import Posterior, Stats
 from _libs import OrcLib
+from miso_amd import capi
 
 PROBS = [0.001, 0.025, 0.5, 0.975, 0.999]
 MEAN_TOL = 1e-9      # posterior mean (tests/test_exact_ref.py)
@@ -151,6 +152,25 @@ def test_restated_mean_against_counter_mode_paired_sampler(orc, post, sims, n_pa
     (2, (60000.0, 0.0), (1.0, 1.0), False, False),
     (2, (60000.0, 43000.0), (1.0, 1.0), True, False),      # a pair on a non-finite score entry
     (3, (60000.0, 43000.0, 100.0), (1.0, 1.0, 1.0), False, False),
+    # the fence (DESIGN.md sections 15, 17): just inside and just beyond each bound, and what is not finite
+    (2, (60000.0, 43000.0), (2.0 ** 20, 2.0 ** 20), False, True),
+    (2, (60000.0, 43000.0), (1.0, 2.0 ** 20 + 1.0), False, False),
+    (2, (60000.0, 43000.0), (2.0 ** 20 + 1.0, 1.0), False, False),
+    (2, (60000.0, 43000.0), (1.0, 1e20), False, False),
+    (2, (60000.0, 43000.0), (float("inf"), 1.0), False, False),
+    (2, (60000.0, 43000.0), (1.0, float("nan")), False, False),
+    (2, (2.0 ** 40, 2.0 ** 20), (1.0, 1.0), False, True),
+    (2, (2.0 ** 21, 2.0 ** 40 * (1 + 2.0 ** -52)), (1.0, 1.0), False, False),
+    (2, (2.0 ** -40, 2.0 ** -20), (1.0, 1.0), False, True),
+    (2, (2.0 ** -40 * (1 - 2.0 ** -53), 2.0 ** -21), (1.0, 1.0), False, False),
+    (2, (1.0, 2.0 ** 20), (1.0, 1.0), False, True),
+    (2, (2.0 ** 20 + 1.0, 1.0), (1.0, 1.0), False, False),
+    (2, (1.0, 2.0 ** 20 + 1.0), (1.0, 1.0), False, False),
+    (2, (float("inf"), 43000.0), (1.0, 1.0), False, False),
+    (2, (60000.0, float("nan")), (1.0, 1.0), False, False),
 ])
 def test_eligibility_table(K, A, hyper, any_bad, want):
     assert eligible(K, A, hyper, any_bad) == want
+    el = capi.C.c_int(-1)       # ... and the library's own rule (host code: no device is needed)
+    assert capi.lib().miso_exact_paired_eligible(K, capi._p(np.array(A)), capi._p(np.array(hyper)), int(any_bad), capi.C.byref(el)) == 0
+    assert el.value == int(want)

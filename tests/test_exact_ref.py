@@ -13,6 +13,7 @@ import pytest
 from _exact_ref import CASES, HYPERS, Posterior, Stats, case_stats, eligible
 from _libs import OrcLib
 from _problems import simulate_se
+from miso_amd import capi
 
 PROBS = [0.001, 0.025, 0.5, 0.975, 0.999]
 MEAN_TOL = 1e-9      # posterior mean
@@ -102,6 +103,29 @@ def test_restated_mean_against_counter_mode_sampler(orc, post):
     (False, 2, (100.0, 0.0), (1.0, 1.0), False),
     (False, 3, (100.0, 60.0, 50.0), (1.0, 1.0, 1.0), False),
     (True, 2, (100.0, 60.0), (1.0, 1.0), False),
+    # the fence: just inside and just beyond each bound, and what is not finite
+    (False, 2, (100.0, 60.0), (1.0, 2.0 ** 20), True),
+    (False, 2, (100.0, 60.0), (2.0 ** 20, 1.0), True),
+    (False, 2, (100.0, 60.0), (1.0, 2.0 ** 20 + 1.0), False),
+    (False, 2, (100.0, 60.0), (2.0 ** 20 + 1.0, 1.0), False),
+    (False, 2, (100.0, 60.0), (1.0, 1e20), False),
+    (False, 2, (100.0, 60.0), (1e30, 1.0), False),
+    (False, 2, (100.0, 60.0), (1.0, float("inf")), False),
+    (False, 2, (100.0, 60.0), (float("nan"), 1.0), False),
+    (False, 2, (2.0 ** 40, 2.0 ** 20), (1.0, 1.0), True),
+    (False, 2, (2.0 ** 40 * (1 + 2.0 ** -52), 2.0 ** 21), (1.0, 1.0), False),
+    (False, 2, (2.0 ** -20, 2.0 ** -40), (1.0, 1.0), True),
+    (False, 2, (2.0 ** -21, 2.0 ** -40 * (1 - 2.0 ** -53)), (1.0, 1.0), False),
+    (False, 2, (1.0, 2.0 ** 20), (1.0, 1.0), True),
+    (False, 2, (2.0 ** 20, 1.0), (1.0, 1.0), True),
+    (False, 2, (1.0, 2.0 ** 20 + 1.0), (1.0, 1.0), False),
+    (False, 2, (2.0 ** 20 + 1.0, 1.0), (1.0, 1.0), False),
+    (False, 2, (float("inf"), 60.0), (1.0, 1.0), False),
+    (False, 2, (float("inf"), float("inf")), (1.0, 1.0), False),
+    (False, 2, (100.0, float("nan")), (1.0, 1.0), False),
 ])
 def test_eligibility_table(paired, K, eff, hyper, want):
     assert eligible(paired, K, eff, hyper) == want
+    el = capi.C.c_int(-1)       # ... and the library's own rule (host code: no device is needed)
+    assert capi.lib().miso_exact_eligible(int(paired), K, capi._p(np.array(eff)), capi._p(np.array(hyper)), capi.C.byref(el)) == 0
+    assert el.value == int(want)
