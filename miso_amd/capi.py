@@ -916,21 +916,25 @@ def exact_delta_groups(stats1, stats2, probs=(0.5, 0.025, 0.975), z=(), max_even
     return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
 
 
-def exact_delta_groups_batches(batches1, batches2, probs=(0.5, 0.025, 0.975), z=()):
-    """exact_delta_groups over launched single-end Batch(exact=True) objects that hold the same events in the same order on
-    one device (miso_batch_exact_delta_groups): the rows are the batches' exact_stats.  Nothing is stored in a batch."""
+def _exact_groups_batches(symbol, batches1, batches2, probs, z):
+    """the batches' route of either family: the handles of both groups to `symbol` of the library"""
     b1, b2 = list(batches1), list(batches2)
     n = len(b1[0]) if b1 else (len(b2[0]) if b2 else 0)
     pp, zz, out, was = _exact_group_args(probs, z, n)
     ms = C.c_float(0.0)
-    L = lib()
-    L.miso_batch_exact_delta_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                                C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+    fn = getattr(lib(), symbol)
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                   C.c_void_p, C.POINTER(C.c_float)]
     h1 = (C.c_void_p * max(len(b1), 1))(*[b.handle for b in b1])
     h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
-    check(L.miso_batch_exact_delta_groups(h1, len(b1), h2, len(b2), _p(pp), len(pp), _p(zz), len(zz), _p(out), out.size, _p(was),
-                                          C.byref(ms)))
+    check(fn(h1, len(b1), h2, len(b2), _p(pp), len(pp), _p(zz), len(zz), _p(out), out.size, _p(was), C.byref(ms)))
     return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
+
+
+def exact_delta_groups_batches(batches1, batches2, probs=(0.5, 0.025, 0.975), z=()):
+    """exact_delta_groups over launched single-end Batch(exact=True) objects that hold the same events in the same order on
+    one device (miso_batch_exact_delta_groups): the rows are the batches' exact_stats.  Nothing is stored in a batch."""
+    return _exact_groups_batches("miso_batch_exact_delta_groups", batches1, batches2, probs, z)
 
 
 def exact_paired_delta_groups(group1, group2, probs=(0.5, 0.025, 0.975), z=(), max_events_per_launch=0):
@@ -962,18 +966,7 @@ def exact_paired_delta_groups_batches(batches1, batches2, probs=(0.5, 0.025, 0.9
     """exact_paired_delta_groups over launched paired-end Batch(exact_paired=True) objects that hold the same events in the
     same order on one device (miso_batch_exact_paired_delta_groups): the kernels read the batches' resident pair records.
     Nothing is stored in a batch."""
-    b1, b2 = list(batches1), list(batches2)
-    n = len(b1[0]) if b1 else (len(b2[0]) if b2 else 0)
-    pp, zz, out, was = _exact_group_args(probs, z, n)
-    ms = C.c_float(0.0)
-    L = lib()
-    L.miso_batch_exact_paired_delta_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                                       C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
-    h1 = (C.c_void_p * max(len(b1), 1))(*[b.handle for b in b1])
-    h2 = (C.c_void_p * max(len(b2), 1))(*[b.handle for b in b2])
-    check(L.miso_batch_exact_paired_delta_groups(h1, len(b1), h2, len(b2), _p(pp), len(pp), _p(zz), len(zz), _p(out), out.size,
-                                                 _p(was), C.byref(ms)))
-    return ExactGroupDelta(out, was, len(pp), len(zz), float(ms.value))
+    return _exact_groups_batches("miso_batch_exact_paired_delta_groups", batches1, batches2, probs, z)
 
 
 # ---- `.miso` sample text (include/miso_amd.h miso_text_shape, miso_batch_from_miso_text) ----

@@ -20,8 +20,11 @@
 // interpolation; thread 0 of an event also writes the group means, H(0.0) and H(z_j) after the first launch.
 // No workgroup has more than one wavefront: no barrier in divergent control flow, no cooperative launch, no atomics.  f64, no
 // contraction, miso_det_exp / miso_det_log, IEEE division, no inline assembly.  tests/_exact_delta_groups_ref.py restates it
-// and the two agree bit for bit (tests/test_gpu_exact_delta_groups.py).  The limits, the row's layout and the launch of
-// exact_groups_update are in exact_delta_groups.hpp, shared with the paired-end unit (kernels_exact_paired_delta_groups.hip).
+// and the two agree bit for bit (tests/test_gpu_exact_delta_groups.py).  This unit holds exact_groups_tables,
+// exact_groups_update and the two entry points; the limits, the row's layout, the exact_groups_sweep template (here
+// exact_groups_sweep<false>: f made again from scalars), the argument checks, the guards of the batches' route, the driver of
+// the launch ranges and the scatter are in exact_delta_groups.hpp, shared with the paired-end unit
+// (kernels_exact_paired_delta_groups.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,73 +55,7 @@ __global__ __launch_bounds__(64) void exact_groups_tables(const double *stats7, 
   const ExactTable W = exact_window(st, lane);
   const double w = exact_point(st, W.tR).x - exact_point(st, W.tL).x;
   const ExactTable T = exact_table(st, W, F, f, red, lane);
-  double *row = ws + static_cast<size_t>(blockIdx.x) * EXACT_GROUPS_ROW;
-  // (all EXACT_PAD words, the exact_idx image's unused padding words included: exact_table never writes those, nothing reads
-  // them, and they travel LDS -> workspace -> LDS as they are)
-  for (int i = lane; i < EXACT_PAD; i += 64) { row[i] = F[i]; row[EXACT_PAD + i] = f[i]; }
-  if (lane == 0) exact_groups_store_scalars(row + 2 * EXACT_PAD, T, w, st);
-}
-
-// One workgroup = one wavefront.  first != 0: one per (event, pair), H_ab at 0.0 (slot 0), at round 1's points (slot 1) and,
-// n_z > 0, at z[0 .. n_z) (slot 2).  first == 0: one per (event, pair, probability k), H_ab at the points of bracket br[event][k]
-// (slot k).  Hp: n_slots rows of eight doubles per (event, pair), the pairs a-major.
-__global__ __launch_bounds__(64) void exact_groups_sweep(const double *ws, const ExactBracket *br, const double *zc, int n_z, int n1,
-                                                         int n2, int ne, int n_p, int n_slots, int first, double *Hp) {
-  __shared__ double F[EXACT_PAD], f[EXACT_PAD], red[256];
-  const int lane = threadIdx.x;
-  const int np_pairs = n1 * n2, nb = n1 + n2;
-  const int per_event = first ? np_pairs : np_pairs * n_p;
-  if (static_cast<int>(blockIdx.x) >= ne * per_event) return;   // (uniform: the whole workgroup)
-  const int e = static_cast<int>(blockIdx.x) / per_event, in_e = static_cast<int>(blockIdx.x) % per_event;
-  const int pair = first ? in_e : in_e / n_p, k = first ? 0 : in_e % n_p;
-  const int a = pair / n2, b = pair % n2;
-  const double *row1 = ws + (static_cast<size_t>(e) * nb + a) * EXACT_GROUPS_ROW;
-  const double *row2 = ws + (static_cast<size_t>(e) * nb + n1 + b) * EXACT_GROUPS_ROW;
-  const bool a2 = row2[2 * EXACT_PAD + 9] < row1[2 * EXACT_PAD + 9];   // A = the group-2 replicate
-  const double *rowA = a2 ? row2 : row1, *rowB = a2 ? row1 : row2;
-  for (int i = lane; i < EXACT_PAD; i += 64) { F[i] = rowB[i]; f[i] = rowB[EXACT_PAD + i]; }
-  const ExactStats stA = exact_groups_load_stats(rowA + 2 * EXACT_PAD);
-  const ExactTable TA = exact_groups_load_table(rowA + 2 * EXACT_PAD, nullptr, nullptr);   // (only its scalars are used)
-  const ExactTable TB = exact_groups_load_table(rowB + 2 * EXACT_PAD, F, f);
-  __syncthreads();
-  const auto weight = [&](int, int, const ExactPoint &p) __attribute__((always_inline)) { return miso_det_exp(p.g - TA.gmax); };
-  double *o = Hp + (static_cast<size_t>(e) * np_pairs + pair) * n_slots * EXACT_DELTA_PTS;
-  if (first) {
-    const double z0[1] = {0.0};
-    double H0[1];
-    exact_delta_sweep<1>(stA, TA, TB, a2, z0, H0, red, lane, weight);
-    if (lane == 0) o[0] = H0[0];
-  }
-  // (the caller's points: five to eight of them take a second eight-wide sweep, one to four a four-wide one below)
-  const int n_sweeps = first && n_z > EXACT_DELTA_PTS / 2 ? 2 : 1;
-#pragma unroll 1
-  for (int s = 0; s < n_sweeps; s++) {
-    double z[EXACT_DELTA_PTS], H[EXACT_DELTA_PTS];
-    if (first && s == 1) {
-#pragma unroll
-      for (int j = 0; j < EXACT_DELTA_PTS; j++) z[j] = j < n_z ? zc[j] : 0.0;
-    } else {
-      const ExactBracket all{-1.0, 0.0, 1.0, 1.0};
-      exact_delta_points(first ? all : br[static_cast<size_t>(e) * n_p + k], z);
-    }
-    exact_delta_sweep<EXACT_DELTA_PTS>(stA, TA, TB, a2, z, H, red, lane, weight);
-    if (lane == 0) {
-      double *os = o + static_cast<size_t>(first ? 1 + s : k) * EXACT_DELTA_PTS;
-#pragma unroll
-      for (int j = 0; j < EXACT_DELTA_PTS; j++) os[j] = H[j];
-    }
-  }
-  if (first && n_z > 0 && n_z <= EXACT_DELTA_PTS / 2) {
-    constexpr int HALF = EXACT_DELTA_PTS / 2;
-    double z[HALF], H[HALF];
-#pragma unroll
-    for (int j = 0; j < HALF; j++) z[j] = j < n_z ? zc[j] : 0.0;
-    exact_delta_sweep<HALF>(stA, TA, TB, a2, z, H, red, lane, weight);
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < HALF; j++) o[2 * EXACT_DELTA_PTS + j] = H[j];
-    }
-  }
+  exact_groups_store_row(ws + static_cast<size_t>(blockIdx.x) * EXACT_GROUPS_ROW, F, f, T, w, st, lane);
 }
 
 // the mixture's value from the pairs' column j of slot `slot`: from 0.0, a outer and b inner, divided once
@@ -169,19 +106,18 @@ void exact_groups_update_launch(hipStream_t st, const double *ws, const double *
 
 // Rows [event][replicate][7] of the two groups; take (may be null): per event, whether the caller lets it be compared at all.
 // An event is comparable when every row is eligible and all rows carry bit-equal (e0, e1); every other event keeps its row of
-// out and gets was_exact = 0.  The comparable ones go to the device in ranges of at most `per_launch` events.
+// out and gets was_exact = 0.  The comparable ones' rows go up and exact_groups_ranges takes them through the device.
 void exact_delta_groups_run(const double *stats7_1, int n1, const double *stats7_2, int n2, int n_events, const unsigned char *take,
                             const double *p, int n_p, const double *z, int n_z, int max_events_per_launch, double *out,
                             int *was_exact, float *ms, hipStream_t st) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device");
-  if (n1 < 1 || n2 < 1 || n1 > EXACT_GROUP_MAX || n2 > EXACT_GROUP_MAX)
-    MISO_FAIL(MISO_EINVAL, "The number of replicates of a group must lie in [1, 8]");
+  exact_groups_check_sizes(n1, n2);
   if (n_events < 0) MISO_FAIL(MISO_EINVAL, "Negative event count");
   if (max_events_per_launch < 0) MISO_FAIL(MISO_EINVAL, "Negative max_events_per_launch");
   exact_delta_check_p(p, n_p);
   exact_check_z(z, n_z);
   if (ms) *ms = 0.f;
-  const int nb = n1 + n2, np_pairs = n1 * n2;
+  const int nb = n1 + n2;
   const size_t ncol = 2 + static_cast<size_t>(n_p) + 1 + static_cast<size_t>(n_z);
   std::vector<int32_t> list;
   std::vector<double> rows;
@@ -192,74 +128,32 @@ void exact_delta_groups_run(const double *stats7_1, int n1, const double *stats7
       const double *q = r < n1 ? g1 + 7 * r : g2 + 7 * (r - n1);
       ok = exact_eligible(false, 2, q + 3, q + 5) && std::memcmp(q + 3, g1 + 3, 2 * sizeof(double)) == 0;
     }
-    was_exact[i] = ok ? 1 : 0;
     if (!ok) continue;
     list.push_back(i);
     rows.insert(rows.end(), g1, g1 + static_cast<size_t>(n1) * 7);
     rows.insert(rows.end(), g2, g2 + static_cast<size_t>(n2) * 7);
   }
   const int m = static_cast<int>(list.size());
-  if (m == 0) return;
-
-  const int n_slots = std::max(n_p, EXACT_GROUPS_FIRST_SLOTS);
-  const size_t ws_ev = static_cast<size_t>(nb) * EXACT_GROUPS_ROW, hp_ev = static_cast<size_t>(np_pairs) * n_slots * EXACT_DELTA_PTS;
-  const size_t bytes_ev = (ws_ev + hp_ev) * sizeof(double) + static_cast<size_t>(n_p) * sizeof(ExactBracket);
-  int per_launch = static_cast<int>(std::min<size_t>(m, std::max<size_t>(1, EXACT_GROUPS_WORK_BYTES / bytes_ev)));
-  if (max_events_per_launch > 0) per_launch = std::min(per_launch, max_events_per_launch);
-
-  HipCall call(st);
-  const double *d_rows = call.upload(rows.data(), rows.size() * sizeof(double));
-  const double *d_p = call.upload(p, static_cast<size_t>(n_p) * sizeof(double));
-  const double *d_z = call.upload(z, static_cast<size_t>(n_z) * sizeof(double));
-  double *d_ws = call.alloc(ws_ev * per_launch * sizeof(double));
-  double *d_hp = call.alloc(hp_ev * per_launch * sizeof(double));
-  ExactBracket *d_br = call.alloc<ExactBracket>(static_cast<size_t>(per_launch) * n_p * sizeof(ExactBracket));
-  double *d_out = call.alloc(static_cast<size_t>(m) * ncol * sizeof(double));
-  call.start();
-  // (the ranges follow one another in the stream, each with the whole workspace: one pair of events times their sum)
-  for (int e0 = 0; e0 < m; e0 += per_launch) {
-    const int ne = std::min(per_launch, m - e0);
-    double *d_o = d_out + static_cast<size_t>(e0) * ncol;
-    hipLaunchKernelGGL(exact_groups_tables, dim3(ne * nb), dim3(64), 0, call.st, d_rows + static_cast<size_t>(e0) * nb * 7, nb, ne, d_ws);
-    HIP_OK(hipGetLastError());
-    for (int round = 0; round < EXACT_DELTA_ROUNDS; round++) {
-      const int first = round == 0 ? 1 : 0;
-      hipLaunchKernelGGL(exact_groups_sweep, dim3(ne * np_pairs * (first ? 1 : n_p)), dim3(64), 0, call.st, d_ws, d_br, d_z, n_z, n1,
-                         n2, ne, n_p, n_slots, first, d_hp);
-      HIP_OK(hipGetLastError());
-      exact_groups_update_launch(call.st, d_ws, d_hp, d_p, n_p, n_z, n1, n2, ne, n_slots, round, d_br, d_o);
-    }
-  }
-  call.stop();
   std::vector<double> got(static_cast<size_t>(m) * ncol);
-  HIP_OK(hipMemcpyAsync(got.data(), d_out, got.size() * sizeof(double), hipMemcpyDeviceToHost, call.st));
-  HIP_OK(hipStreamSynchronize(call.st));
-  for (int j = 0; j < m; j++) std::memcpy(out + static_cast<size_t>(list[j]) * ncol, &got[static_cast<size_t>(j) * ncol], ncol * sizeof(double));
-  if (ms) *ms = call.elapsed_ms();
+  if (m > 0) {
+    HipCall call(st);
+    const double *d_rows = call.upload(rows.data(), rows.size() * sizeof(double));
+    exact_groups_ranges<false>(call, m, n1, n2, p, n_p, z, n_z, max_events_per_launch, [&](int e0, int ne, double *d_ws) {
+      hipLaunchKernelGGL(exact_groups_tables, dim3(ne * nb), dim3(64), 0, call.st, d_rows + static_cast<size_t>(e0) * nb * 7, nb, ne, d_ws);
+    }, got.data());
+    if (ms) *ms = call.elapsed_ms();
+  }
+  exact_groups_scatter(list, got, ncol, n_events, out, was_exact);
 }
 
-// The batches' route: the guards of a group pass, every batch single-end with the exact mode, the rows from exact_stats7 (an
-// event some batch's exact mode did not take is not comparable), then the pass above on the first batch's stream.  Nothing is
-// stored in any batch.
+// The batches' route: exact_groups_guard's guards for single-end batches, the rows from exact_stats7 (an event some batch's
+// exact mode did not take is not comparable), then the pass above on the first batch's stream.  Nothing is stored in any
+// batch.
 void exact_delta_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, const double *p, int n_p, const double *z, int n_z,
                         double *out, int64_t out_len, int *was_exact, float *kernel_ms) {
-  if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the comparison has no CPU path");
-  if (n1 > EXACT_GROUP_MAX || n2 > EXACT_GROUP_MAX) MISO_FAIL(MISO_EINVAL, "The number of replicates of a group must lie in [1, 8]");
-  const std::vector<miso_batch *> all = same_events_groups(g1, n1, g2, n2);
-  for (int i = 0; i < n1 + n2; i++) {
-    const miso_batch &b = *all[i];
-    const std::string who = "group " + std::to_string(i < n1 ? 1 : 2) + " batch " + std::to_string(i < n1 ? i : i - n1) + ": ";
-    if (b.p.paired) MISO_FAIL(MISO_EINVAL, who + "a paired-end batch cannot take part in the exact group comparison");
-    if (!b.exact || b.slots_exact != b.exact) MISO_FAIL(MISO_EINVAL, who + "the batch has not run with the exact-posterior mode");
-  }
-  exact_delta_check_p(p, n_p);
-  exact_check_z(z, n_z);
+  const std::vector<miso_batch *> all = exact_groups_guard(g1, n1, g2, n2, false, p, n_p, z, n_z, out_len, kernel_ms);
   miso_batch &r = *all[0];
   const int n = static_cast<int>(r.events.size());
-  const size_t ncol = 2 + static_cast<size_t>(n_p) + 1 + static_cast<size_t>(n_z);
-  if (out_len < 0 || static_cast<uint64_t>(out_len) < static_cast<uint64_t>(n) * ncol)
-    MISO_FAIL(MISO_EINVAL, "out is too short for 2 + n_p + 1 + n_z doubles per event");
-  if (kernel_ms) *kernel_ms = 0.f;
   if (n == 0) return;
   std::vector<double> s1(static_cast<size_t>(n) * n1 * 7), s2(static_cast<size_t>(n) * n2 * 7);
   std::vector<unsigned char> take(n, 1);
@@ -269,8 +163,7 @@ void exact_delta_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, in
       if (!b.event_exact(i)) take[i] = 0;
       b.exact_stats7(i, c < n1 ? &s1[(static_cast<size_t>(i) * n1 + c) * 7] : &s2[(static_cast<size_t>(i) * n2 + (c - n1)) * 7]);
     }
-  HIP_OK(hipSetDevice(r.device));
-  for (miso_batch *b : all) HIP_OK(hipStreamSynchronize(b->stream));
+  exact_groups_wait(all);
   exact_delta_groups_run(s1.data(), n1, s2.data(), n2, n, take.data(), p, n_p, z, n_z, 0, out, was_exact, kernel_ms, r.stream);
 }
 

@@ -3,9 +3,11 @@
 // and host driver.
 //
 // The mixture, the rounds-as-launches shape, the workspace rows and exact_groups_update are kernels_exact_delta_groups.hip's
-// (exact_delta_groups.hpp).  H_ab is kernels_exact_paired_delta.hip's, operation for operation: A is the
-// replicate with the narrower window in psi (a tie: the group-1 replicate), decided per pair; exact_delta_sweep over A's 2049
-// points with A's own tabulated f as the weight, exact_cdf_at on B's table.
+// (DESIGN.md 20a), and what the two units do alike is in exact_delta_groups.hpp: the exact_groups_sweep template, the argument
+// checks, the guards of the batches' route, the driver of the launch ranges and the scatter.  This unit holds
+// exact_paired_groups_tables and the two entry points.  H_ab is kernels_exact_paired_delta.hip's, operation for operation: A
+// is the replicate with the narrower window in psi (a tie: the group-1 replicate), decided per pair; exact_delta_sweep over
+// A's 2049 points with A's own tabulated f as the weight, exact_cdf_at on B's table.
 //
 // TABLES ONCE.  exact_paired_groups_tables, one wavefront per (event, replicate): the replicate's side of the event loaded
 // with exact_paired_element (caller-given probabilities or the resident records of the replicate's batch), exact_paired_window
@@ -16,7 +18,7 @@
 // ExactPairedCmpSide travel as ONE kernel argument (896 bytes of the 4 KiB a launch may pass), indexed by the wavefront's
 // replicate -- a uniform index into the kernel-argument segment, scalar loads, no scratch; no buffer to upload and one launch
 // a range where a launch per replicate would make up to sixteen.
-// THE SWEEP.  exact_paired_groups_sweep is exact_groups_sweep with one change: the weight is read from the f image of A's row
+// THE SWEEP.  exact_groups_sweep<true>, the one template of exact_delta_groups.hpp: the weight is read from the f image of A's row
 // (rowA[EXACT_PAD + exact_idx(point)]) -- the paired posterior's f needs the pair sum and cannot be made again from scalars.
 // The lanes' loads lie 33 doubles apart; a second copy of f laid out [64 j + l] as kernels_exact_paired_delta.hip's row, each
 // load one 512-byte line, was built first and read no faster (187.1 against 186.5 ms on DESIGN.md 20b's workload); without
@@ -63,83 +65,18 @@ __global__ __launch_bounds__(64) void exact_paired_groups_tables(const ExactPair
   const ExactTable W = exact_uni(exact_paired_window(st, c8, pr, L.mbuf, L.red, L.redi, lane));
   const double w = exact_point(st, W.tR).x - exact_point(st, W.tL).x;
   const ExactTable T = exact_paired_table(st, W, pr, L.mbuf, L.F, L.f, L.fext, L.red, lane);
-  double *row = ws + static_cast<size_t>(blockIdx.x) * EXACT_GROUPS_ROW;
-  // (all EXACT_PAD words, the exact_idx image's unused padding words included: nothing reads them)
-  for (int i = lane; i < EXACT_PAD; i += 64) { row[i] = L.F[i]; row[EXACT_PAD + i] = L.f[i]; }
-  if (lane == 0) exact_groups_store_scalars(row + 2 * EXACT_PAD, T, w, st);
-}
-
-// exact_groups_sweep (kernels_exact_delta_groups.hip) with A's f read from its row: the same workgroups, slots and
-// stores.  first != 0: one workgroup per (event, pair), H_ab at 0.0 (slot 0), at round 1's points (slot 1) and, n_z > 0, at
-// z[0 .. n_z) (slot 2).  first == 0: one per (event, pair, probability k), H_ab at the points of bracket br[event][k] (slot k).
-__global__ __launch_bounds__(64) void exact_paired_groups_sweep(const double *ws, const ExactBracket *br, const double *zc, int n_z, int n1,
-                                                                int n2, int ne, int n_p, int n_slots, int first, double *Hp) {
-  __shared__ double F[EXACT_PAD], f[EXACT_PAD], red[256];
-  const int lane = threadIdx.x;
-  const int np_pairs = n1 * n2, nb = n1 + n2;
-  const int per_event = first ? np_pairs : np_pairs * n_p;
-  if (static_cast<int>(blockIdx.x) >= ne * per_event) return;   // (uniform: the whole workgroup)
-  const int e = static_cast<int>(blockIdx.x) / per_event, in_e = static_cast<int>(blockIdx.x) % per_event;
-  const int pair = first ? in_e : in_e / n_p, k = first ? 0 : in_e % n_p;
-  const int a = pair / n2, b = pair % n2;
-  const double *row1 = ws + (static_cast<size_t>(e) * nb + a) * EXACT_GROUPS_ROW;
-  const double *row2 = ws + (static_cast<size_t>(e) * nb + n1 + b) * EXACT_GROUPS_ROW;
-  const bool a2 = row2[2 * EXACT_PAD + 9] < row1[2 * EXACT_PAD + 9];   // A = the group-2 replicate
-  const double *rowA = a2 ? row2 : row1, *rowB = a2 ? row1 : row2;
-  for (int i = lane; i < EXACT_PAD; i += 64) { F[i] = rowB[i]; f[i] = rowB[EXACT_PAD + i]; }
-  const ExactStats stA = exact_groups_load_stats(rowA + 2 * EXACT_PAD);
-  const ExactTable TA = exact_groups_load_table(rowA + 2 * EXACT_PAD, nullptr, nullptr);   // (only its scalars are used)
-  const ExactTable TB = exact_groups_load_table(rowB + 2 * EXACT_PAD, F, f);
-  __syncthreads();
-  const auto weight = [&](int, int pt, const ExactPoint &) __attribute__((always_inline)) { return rowA[EXACT_PAD + exact_idx(pt)]; };
-  double *o = Hp + (static_cast<size_t>(e) * np_pairs + pair) * n_slots * EXACT_DELTA_PTS;
-  if (first) {
-    const double z0[1] = {0.0};
-    double H0[1];
-    exact_delta_sweep<1>(stA, TA, TB, a2, z0, H0, red, lane, weight);
-    if (lane == 0) o[0] = H0[0];
-  }
-  // (the caller's points: five to eight of them take a second eight-wide sweep, one to four a four-wide one below)
-  const int n_sweeps = first && n_z > EXACT_DELTA_PTS / 2 ? 2 : 1;
-#pragma unroll 1
-  for (int s = 0; s < n_sweeps; s++) {
-    double z[EXACT_DELTA_PTS], H[EXACT_DELTA_PTS];
-    if (first && s == 1) {
-#pragma unroll
-      for (int j = 0; j < EXACT_DELTA_PTS; j++) z[j] = j < n_z ? zc[j] : 0.0;
-    } else {
-      const ExactBracket all{-1.0, 0.0, 1.0, 1.0};
-      exact_delta_points(first ? all : br[static_cast<size_t>(e) * n_p + k], z);
-    }
-    exact_delta_sweep<EXACT_DELTA_PTS>(stA, TA, TB, a2, z, H, red, lane, weight);
-    if (lane == 0) {
-      double *os = o + static_cast<size_t>(first ? 1 + s : k) * EXACT_DELTA_PTS;
-#pragma unroll
-      for (int j = 0; j < EXACT_DELTA_PTS; j++) os[j] = H[j];
-    }
-  }
-  if (first && n_z > 0 && n_z <= EXACT_DELTA_PTS / 2) {
-    constexpr int HALF = EXACT_DELTA_PTS / 2;
-    double z[HALF], H[HALF];
-#pragma unroll
-    for (int j = 0; j < HALF; j++) z[j] = j < n_z ? zc[j] : 0.0;
-    exact_delta_sweep<HALF>(stA, TA, TB, a2, z, H, red, lane, weight);
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < HALF; j++) o[2 * EXACT_DELTA_PTS + j] = H[j];
-    }
-  }
+  exact_groups_store_row(ws + static_cast<size_t>(blockIdx.x) * EXACT_GROUPS_ROW, L.F, L.f, T, w, st, lane);
 }
 
 // The pass over m comparable events.  in[r]: replicate r's side of them, group 1's first (exact_paired_compare_run's form:
 // caller-given m / offs, or a batch's device pointers with event j being list[j]); list may be null when no side is resident.
-// rows: 2 + n_p + 1 + n_z doubles per event.  Everything is checked before anything is allocated; the events go to the device
-// in ranges of at most `per_launch`, eleven launches a range in one stream, one pair of HIP events around them all.
+// rows: 2 + n_p + 1 + n_z doubles per event.  Everything is checked before anything is allocated; the sides go up and
+// exact_groups_ranges takes the events through the device.
 static void exact_paired_delta_groups_run(const ExactPairedCmpInput *in, int n1, int n2, const int32_t *list, int m, const double *p,
                                           int n_p, const double *z, int n_z, int max_events_per_launch, double *rows, float *ms,
                                           hipStream_t st) {
   if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device");
-  const int nb = n1 + n2, np_pairs = n1 * n2;
+  const int nb = n1 + n2;
   int64_t n_pairs[2 * EXACT_GROUP_MAX];
   bool resident = false;
   for (int r = 0; r < nb; r++) {
@@ -148,58 +85,14 @@ static void exact_paired_delta_groups_run(const ExactPairedCmpInput *in, int n1,
   }
   if (ms) *ms = 0.f;
   if (m == 0) return;
-  const size_t ncol = 2 + static_cast<size_t>(n_p) + 1 + static_cast<size_t>(n_z);
-  const int n_slots = std::max(n_p, EXACT_GROUPS_FIRST_SLOTS);
-  const size_t ws_ev = static_cast<size_t>(nb) * EXACT_GROUPS_ROW, hp_ev = static_cast<size_t>(np_pairs) * n_slots * EXACT_DELTA_PTS;
-  const size_t bytes_ev = (ws_ev + hp_ev) * sizeof(double) + static_cast<size_t>(n_p) * sizeof(ExactBracket);
-  int per_launch = static_cast<int>(std::min<size_t>(m, std::max<size_t>(1, EXACT_GROUPS_WORK_BYTES / bytes_ev)));
-  if (max_events_per_launch > 0) per_launch = std::min(per_launch, max_events_per_launch);
-
   HipCall call(st);
   ExactPairedGroupSides sides{};
   for (int r = 0; r < nb; r++) sides.s[r] = exact_paired_cmp_upload(call, in[r], m, n_pairs[r]);
   const int32_t *d_list = resident ? call.upload(list, static_cast<size_t>(m) * sizeof(int32_t)) : nullptr;
-  const double *d_p = call.upload(p, static_cast<size_t>(n_p) * sizeof(double));
-  const double *d_z = call.upload(z, static_cast<size_t>(n_z) * sizeof(double));
-  double *d_ws = call.alloc(ws_ev * per_launch * sizeof(double));
-  double *d_hp = call.alloc(hp_ev * per_launch * sizeof(double));
-  ExactBracket *d_br = call.alloc<ExactBracket>(static_cast<size_t>(per_launch) * n_p * sizeof(ExactBracket));
-  double *d_out = call.alloc(static_cast<size_t>(m) * ncol * sizeof(double));
-  call.start();
-  // (the ranges follow one another in the stream, each with the whole workspace: one pair of events times their sum)
-  for (int e0 = 0; e0 < m; e0 += per_launch) {
-    const int ne = std::min(per_launch, m - e0);
-    double *d_o = d_out + static_cast<size_t>(e0) * ncol;
+  exact_groups_ranges<true>(call, m, n1, n2, p, n_p, z, n_z, max_events_per_launch, [&](int e0, int ne, double *d_ws) {
     hipLaunchKernelGGL(exact_paired_groups_tables, dim3(ne * nb), dim3(64), 0, call.st, sides, d_list, e0, nb, ne, d_ws);
-    HIP_OK(hipGetLastError());
-    for (int round = 0; round < EXACT_DELTA_ROUNDS; round++) {
-      const int first = round == 0 ? 1 : 0;
-      hipLaunchKernelGGL(exact_paired_groups_sweep, dim3(ne * np_pairs * (first ? 1 : n_p)), dim3(64), 0, call.st, d_ws, d_br, d_z, n_z,
-                         n1, n2, ne, n_p, n_slots, first, d_hp);
-      HIP_OK(hipGetLastError());
-      exact_groups_update_launch(call.st, d_ws, d_hp, d_p, n_p, n_z, n1, n2, ne, n_slots, round, d_br, d_o);
-    }
-  }
-  call.stop();
-  HIP_OK(hipMemcpyAsync(rows, d_out, static_cast<size_t>(m) * ncol * sizeof(double), hipMemcpyDeviceToHost, call.st));
-  HIP_OK(hipStreamSynchronize(call.st));
+  }, rows);
   if (ms) *ms = call.elapsed_ms();
-}
-
-// what both routes check first, and the rows' scatter: event list[j] gets row j and was_exact = 1, every other event 0
-static void exact_paired_groups_check(int n1, int n2, const double *p, int n_p, const double *z, int n_z) {
-  if (n1 < 1 || n2 < 1 || n1 > EXACT_GROUP_MAX || n2 > EXACT_GROUP_MAX)
-    MISO_FAIL(MISO_EINVAL, "The number of replicates of a group must lie in [1, 8]");
-  exact_delta_check_p(p, n_p);
-  exact_check_z(z, n_z);
-}
-static void exact_paired_groups_scatter(const std::vector<int32_t> &list, const std::vector<double> &rows, size_t ncol, int n_events,
-                                        double *out, int *was_exact) {
-  for (int i = 0; i < n_events; i++) was_exact[i] = 0;
-  for (size_t j = 0; j < list.size(); j++) {
-    std::memcpy(out + static_cast<size_t>(list[j]) * ncol, &rows[j * ncol], ncol * sizeof(double));
-    was_exact[list[j]] = 1;
-  }
 }
 
 // Caller-given elements.  The comparable events' elements are gathered into the selftest's layout again (statistics, offsets
@@ -207,7 +100,7 @@ static void exact_paired_groups_scatter(const std::vector<int32_t> &list, const 
 void exact_paired_delta_groups_given(const double *const *stats6, const double *const *mm, const int64_t *const *offs, int n1, int n2,
                                      int n_events, const double *p, int n_p, const double *z, int n_z, int max_events_per_launch,
                                      double *out, int *was_exact, float *ms) {
-  exact_paired_groups_check(n1, n2, p, n_p, z, n_z);
+  exact_groups_check(n1, n2, p, n_p, z, n_z);
   if (n_events < 0) MISO_FAIL(MISO_EINVAL, "Negative event count");
   if (max_events_per_launch < 0) MISO_FAIL(MISO_EINVAL, "Negative max_events_per_launch");
   const int nb = n1 + n2;
@@ -246,32 +139,19 @@ void exact_paired_delta_groups_given(const double *const *stats6, const double *
   const size_t ncol = 2 + static_cast<size_t>(n_p) + 1 + static_cast<size_t>(n_z);
   std::vector<double> rows(static_cast<size_t>(m) * ncol);
   exact_paired_delta_groups_run(in.data(), n1, n2, nullptr, m, p, n_p, z, n_z, max_events_per_launch, rows.data(), ms, nullptr);
-  exact_paired_groups_scatter(list, rows, ncol, n_events, out, was_exact);
+  exact_groups_scatter(list, rows, ncol, n_events, out, was_exact);
 }
 
-// The batches' route: the guards of a group pass, every batch paired-end with the paired exact mode, an event comparable when
-// every batch's mode took it; the kernels read the batches' resident pair records, on the first batch's stream after all have
-// been waited for.  Nothing is stored in any batch.
+// The batches' route: exact_groups_guard's guards for paired-end batches, an event comparable when every batch's mode took it;
+// the kernels read the batches' resident pair records, on the first batch's stream after all have been waited for.  Nothing
+// is stored in any batch.
 void exact_paired_delta_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, const double *p, int n_p, const double *z,
                                int n_z, double *out, int64_t out_len, int *was_exact, float *kernel_ms) {
-  if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the comparison has no CPU path");
-  if (n1 > EXACT_GROUP_MAX || n2 > EXACT_GROUP_MAX) MISO_FAIL(MISO_EINVAL, "The number of replicates of a group must lie in [1, 8]");
-  const std::vector<miso_batch *> all = same_events_groups(g1, n1, g2, n2);
+  const std::vector<miso_batch *> all = exact_groups_guard(g1, n1, g2, n2, true, p, n_p, z, n_z, out_len, kernel_ms);
   const int nb = n1 + n2;
-  for (int i = 0; i < nb; i++) {
-    const miso_batch &b = *all[i];
-    const std::string who = "group " + std::to_string(i < n1 ? 1 : 2) + " batch " + std::to_string(i < n1 ? i : i - n1) + ": ";
-    if (!b.p.paired) MISO_FAIL(MISO_EINVAL, who + "a single-end batch cannot take part in the paired exact group comparison");
-    if (!b.exact_paired || b.slots_exact != b.exact_paired)
-      MISO_FAIL(MISO_EINVAL, who + "the batch has not run with the paired exact-posterior mode");
-  }
-  exact_paired_groups_check(n1, n2, p, n_p, z, n_z);
   miso_batch &first = *all[0];
   const int n = static_cast<int>(first.events.size());
   const size_t ncol = 2 + static_cast<size_t>(n_p) + 1 + static_cast<size_t>(n_z);
-  if (out_len < 0 || static_cast<uint64_t>(out_len) < static_cast<uint64_t>(n) * ncol)
-    MISO_FAIL(MISO_EINVAL, "out is too short for 2 + n_p + 1 + n_z doubles per event");
-  if (kernel_ms) *kernel_ms = 0.f;
   if (n == 0) return;
   std::vector<int32_t> list;
   for (int i = 0; i < n; i++) {
@@ -287,10 +167,9 @@ void exact_paired_delta_groups(miso_batch *const *g1, int n1, miso_batch *const 
     in.push_back(exact_paired_resident(*all[r], cs[r].data()));
   }
   std::vector<double> rows(static_cast<size_t>(m) * ncol);
-  HIP_OK(hipSetDevice(first.device));
-  for (miso_batch *b : all) HIP_OK(hipStreamSynchronize(b->stream));
+  exact_groups_wait(all);
   exact_paired_delta_groups_run(in.data(), n1, n2, list.data(), m, p, n_p, z, n_z, 0, rows.data(), kernel_ms, first.stream);
-  exact_paired_groups_scatter(list, rows, ncol, n, out, was_exact);
+  exact_groups_scatter(list, rows, ncol, n, out, was_exact);
 }
 
 }  // namespace miso

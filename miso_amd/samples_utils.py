@@ -928,34 +928,55 @@ def output_group_comparisons(dirs1, dirs2, output_dir, labels1=None, labels2=Non
 MAX_EXACT_GROUP = 8     # replicates a group in the exact pooled pass (include/miso_amd.h miso_exact_delta_groups)
 
 
-def exact_stats_path(sample_dir):
-    """where `miso --run ... --exact --exact-stats` leaves a sample directory's table"""
-    return os.path.join(sample_dir, "summary", os.path.basename(os.path.normpath(sample_dir)) + ".miso_exact_stats")
+class _ExactKind:
+    """What the two pooled exact tables differ in.  flag: as the messages name it; suffix, read: a sample directory's table;
+    written_by: the run that leaves it; call(tables, have, evs): the capi call for the events `evs`, which the replicates
+    have[g] of group g hold with exact = 1."""
+
+    def __init__(self, flag, suffix, read, written_by, call):
+        self.flag, self.suffix, self.read, self.written_by, self.call = flag, suffix, read, written_by, call
+
+    def path(self, sample_dir):
+        return os.path.join(sample_dir, "summary", os.path.basename(os.path.normpath(sample_dir)) + self.suffix)
 
 
-def check_exact_stats_tables(dirs1, dirs2):
-    """ValueError, before any work, unless both groups have 1 .. 8 directories and each holds its `.miso_exact_stats` table"""
+def _exact_stats_call(tables, have, evs, probs, z):
+    s1, s2 = ([[tables[g][r][name][1] for r in have[g]] for name in evs] for g in (0, 1))
+    return capi.exact_delta_groups(s1, s2, probs, z)
+
+
+def _exact_pairs_call(tables, have, evs, probs, z):
+    groups = [[([tables[g][r][name][1] for name in evs], [tables[g][r][name][2] for name in evs]) for r in have[g]] for g in (0, 1)]
+    return capi.exact_paired_delta_groups(groups[0], groups[1], probs, z)
+
+
+_EXACT_STATS = _ExactKind("--exact-delta-posterior", ".miso_exact_stats", compare.read_exact_stats,
+                          "miso --run ... --exact --exact-stats", _exact_stats_call)
+_EXACT_PAIRS = _ExactKind("--exact-paired-delta-posterior", ".miso_exact_pairs", compare.read_exact_pairs,
+                          "miso --run ... --paired-end M SD --exact-paired --exact-paired-stats", _exact_pairs_call)
+
+
+def _check_exact_tables(kind, dirs1, dirs2):
+    """ValueError, before any work, unless both groups have 1 .. 8 directories and each holds the kind's table"""
     for which, dirs in enumerate((dirs1, dirs2)):
         if not 1 <= len(dirs) <= MAX_EXACT_GROUP:
-            raise ValueError("Error: --exact-delta-posterior pools between 1 and %d replicates a group, group %d has %d"
-                             % (MAX_EXACT_GROUP, which + 1, len(dirs)))
+            raise ValueError("Error: %s pools between 1 and %d replicates a group, group %d has %d"
+                             % (kind.flag, MAX_EXACT_GROUP, which + 1, len(dirs)))
     for d in list(dirs1) + list(dirs2):
-        if not os.path.isfile(exact_stats_path(d)):
-            raise ValueError("Error: %s has no %s (written by miso --run ... --exact --exact-stats)"
-                             % (d, os.path.relpath(exact_stats_path(d), d)))
+        if not os.path.isfile(kind.path(d)):
+            raise ValueError("Error: %s has no %s (written by %s)" % (d, os.path.relpath(kind.path(d), d), kind.written_by))
 
 
-def output_group_exact_delta(dirs1, dirs2, output_dir, delta_thresholds=None, group_names=None):
-    """--compare-groups --exact-delta-posterior: `<A>_vs_<B>/delta-psi/<A>_vs_<B>.miso_group_dpsi_exact`, delta psi of the two
-    groups pooled over all pairs of replicates from their exact posteriors, without a draw (capi.exact_delta_groups, DESIGN.md
-    20a), from each sample directory's `.miso_exact_stats` table.  An event is pooled over the replicates that have it with
-    exact = 1: the events are grouped by which replicates those are, one device call per such pattern.  An event without such
-    a replicate on a side, or with unequal effective lengths among its replicates, prints NA; one notice per cause.
-    Returns (path, n_rows)."""
-    check_exact_stats_tables(dirs1, dirs2)
+def _output_group_exact(kind, dirs1, dirs2, output_dir, delta_thresholds, group_names):
+    """`<A>_vs_<B>/delta-psi/<A>_vs_<B>.miso_group_dpsi_exact`, delta psi of the two groups pooled over all pairs of replicates
+    from their exact posteriors, without a draw, from each sample directory's table of the kind.  An event is pooled over the
+    replicates that have it with exact = 1: the events are grouped by which replicates those are, one device call per such
+    pattern.  An event without such a replicate on a side, or one the device call does not take, prints NA; one notice per
+    cause.  Returns (path, n_rows)."""
+    _check_exact_tables(kind, dirs1, dirs2)
     thresholds = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
     group_names = tuple(group_names or DEFAULT_GROUP_NAMES)
-    tables = [[compare.read_exact_stats(exact_stats_path(d)) for d in dirs] for dirs in (dirs1, dirs2)]
+    tables = [[kind.read(kind.path(d)) for d in dirs] for dirs in (dirs1, dirs2)]
     names = sorted(set().union(*[t.keys() for g in tables for t in g]))
     patterns = {}
     for name in names:
@@ -963,22 +984,21 @@ def output_group_exact_delta(dirs1, dirs2, output_dir, delta_thresholds=None, gr
         patterns.setdefault(have, []).append(name)
     rows = {}
     n_none = n_unequal = 0
-    for (have1, have2), evs in patterns.items():
-        if not have1 or not have2:
+    for have, evs in patterns.items():
+        if not have[0] or not have[1]:
             n_none += len(evs)
             for name in evs:
-                rows[name] = (name, len(have1), len(have2), None, {})
+                rows[name] = (name, len(have[0]), len(have[1]), None, {})
             continue
-        s1 = [[tables[0][r][name][1] for r in have1] for name in evs]
-        s2 = [[tables[1][r][name][1] for r in have2] for name in evs]
-        res = capi.exact_delta_groups(s1, s2, compare.EXACT_DPSI_PROBS, compare.delta_points(thresholds))
+        res = kind.call(tables, have, evs, compare.EXACT_DPSI_PROBS, compare.delta_points(thresholds))
         for j, name in enumerate(evs):
             row = res.row(j)
             n_unequal += row is None
-            rows[name] = (name, len(have1), len(have2), row, {})
+            rows[name] = (name, len(have[0]), len(have[1]), row, {})
     if n_none:
         print("Notice: %d event(s) have no replicate with an exact posterior in one of the groups: NA in the pooled table" % n_none)
-    if n_unequal:
+    # (single-end only: the paired-end pass takes every event whose replicates' tables say exact = 1)
+    if n_unequal and kind is _EXACT_STATS:
         print("Notice: %d event(s) differ in effective lengths among their replicates: NA in the pooled table" % n_unequal)
     name = "%s_vs_%s" % group_names
     out = os.path.join(output_dir, name, "delta-psi", name + ".miso_group_dpsi_exact")
@@ -986,55 +1006,37 @@ def output_group_exact_delta(dirs1, dirs2, output_dir, delta_thresholds=None, gr
     return out, compare.write_group_dpsi_exact(out, [rows[n] for n in names], thresholds)
 
 
+def exact_stats_path(sample_dir):
+    """where `miso --run ... --exact --exact-stats` leaves a sample directory's table"""
+    return _EXACT_STATS.path(sample_dir)
+
+
+def check_exact_stats_tables(dirs1, dirs2):
+    """ValueError, before any work, unless both groups have 1 .. 8 directories and each holds its `.miso_exact_stats` table"""
+    _check_exact_tables(_EXACT_STATS, dirs1, dirs2)
+
+
+def output_group_exact_delta(dirs1, dirs2, output_dir, delta_thresholds=None, group_names=None):
+    """--compare-groups --exact-delta-posterior: the pooled exact table (_output_group_exact; capi.exact_delta_groups, DESIGN.md
+    20a) from each sample directory's `.miso_exact_stats` table.  An event with unequal effective lengths among its replicates
+    prints NA too."""
+    return _output_group_exact(_EXACT_STATS, dirs1, dirs2, output_dir, delta_thresholds, group_names)
+
+
 def exact_pairs_path(sample_dir):
     """where `miso --run ... --paired-end M SD --exact-paired --exact-paired-stats` leaves a sample directory's table"""
-    return os.path.join(sample_dir, "summary", os.path.basename(os.path.normpath(sample_dir)) + ".miso_exact_pairs")
+    return _EXACT_PAIRS.path(sample_dir)
 
 
 def check_exact_pairs_tables(dirs1, dirs2):
     """ValueError, before any work, unless both groups have 1 .. 8 directories and each holds its `.miso_exact_pairs` table"""
-    for which, dirs in enumerate((dirs1, dirs2)):
-        if not 1 <= len(dirs) <= MAX_EXACT_GROUP:
-            raise ValueError("Error: --exact-paired-delta-posterior pools between 1 and %d replicates a group, group %d has %d"
-                             % (MAX_EXACT_GROUP, which + 1, len(dirs)))
-    for d in list(dirs1) + list(dirs2):
-        if not os.path.isfile(exact_pairs_path(d)):
-            raise ValueError("Error: %s has no %s (written by miso --run ... --paired-end M SD --exact-paired --exact-paired-stats)"
-                             % (d, os.path.relpath(exact_pairs_path(d), d)))
+    _check_exact_tables(_EXACT_PAIRS, dirs1, dirs2)
 
 
 def output_group_exact_paired_delta(dirs1, dirs2, output_dir, delta_thresholds=None, group_names=None):
-    """--compare-groups --exact-paired-delta-posterior: output_group_exact_delta for paired-end replicates
-    (capi.exact_paired_delta_groups), from each sample directory's `.miso_exact_pairs` table: the same pooled
-    table, the events grouped by which replicates have them with exact = 1, one device call per such pattern.  An event without
-    such a replicate on a side prints NA.  Returns (path, n_rows)."""
-    check_exact_pairs_tables(dirs1, dirs2)
-    thresholds = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
-    group_names = tuple(group_names or DEFAULT_GROUP_NAMES)
-    tables = [[compare.read_exact_pairs(exact_pairs_path(d)) for d in dirs] for dirs in (dirs1, dirs2)]
-    names = sorted(set().union(*[t.keys() for g in tables for t in g]))
-    patterns = {}
-    for name in names:
-        have = tuple(tuple(r for r, t in enumerate(g) if name in t and t[name][0]) for g in tables)
-        patterns.setdefault(have, []).append(name)
-    rows = {}
-    n_none = 0
-    for have, evs in patterns.items():
-        if not have[0] or not have[1]:
-            n_none += len(evs)
-            for name in evs:
-                rows[name] = (name, len(have[0]), len(have[1]), None, {})
-            continue
-        groups = [[([tables[g][r][name][1] for name in evs], [tables[g][r][name][2] for name in evs]) for r in have[g]] for g in (0, 1)]
-        res = capi.exact_paired_delta_groups(groups[0], groups[1], compare.EXACT_DPSI_PROBS, compare.delta_points(thresholds))
-        for j, name in enumerate(evs):
-            rows[name] = (name, len(have[0]), len(have[1]), res.row(j), {})
-    if n_none:
-        print("Notice: %d event(s) have no replicate with an exact posterior in one of the groups: NA in the pooled table" % n_none)
-    name = "%s_vs_%s" % group_names
-    out = os.path.join(output_dir, name, "delta-psi", name + ".miso_group_dpsi_exact")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    return out, compare.write_group_dpsi_exact(out, [rows[n] for n in names], thresholds)
+    """--compare-groups --exact-paired-delta-posterior: the same for paired-end replicates (capi.exact_paired_delta_groups,
+    DESIGN.md 20b), from each sample directory's `.miso_exact_pairs` table."""
+    return _output_group_exact(_EXACT_PAIRS, dirs1, dirs2, output_dir, delta_thresholds, group_names)
 
 
 def parse_group_args(compare_groups, group_labels_arg=None):
