@@ -178,6 +178,21 @@ int miso_region_counts(const miso_alnfile_t *f, int device, int n_intervals, con
                        const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
                        miso_region_stats_t *stats);
 
+/* ---- fetch counts of many intervals (`sam_rpkm --compute-rpkm`, misopy/sam_rpkm.py:138-154) ----
+ * counts[i] = the number miso_aln_fetch(f, miso_aln_ref_id(f, seqid[i]), start[i], end[i], NULL, 0, &n) puts in n: the
+ * records whose reference is named exactly seqid[i] with pos < end[i] && bam_endpos > start[i] (pos 0-based, bam_endpos
+ * as above).  No flag matters; a record without a reference counts nowhere.  The numbers are used as given, as
+ * bamfile.fetch(chrom, exon.start, exon.end) uses them in the reference: a caller that hands over GFF numbers (1-based,
+ * inclusive) puts them in pysam's 0-based half-open slot, the mix miso_region_densities documents below.  A seqid the
+ * file does not name, or start[i] > end[i], counts 0; intervals may nest, overlap and repeat.  One pass over the record
+ * columns on the device, whatever n_intervals is.  chunk_records: records per device chunk (<= 0: the default, 4 M);
+ * device memory is bounded by it and by n_intervals.  The counts do not depend on it or on the record order.  Fails
+ * with MISO_ENODEVICE without a GPU: there is no CPU path.  stats may be NULL; its fields as for miso_region_counts,
+ * `kept` = the records of the file (nothing is filtered). */
+int miso_fetch_counts(const miso_alnfile_t *f, int device, int n_intervals, const char *const *seqid,
+                      const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
+                      miso_region_stats_t *stats);
+
 /* ---- per-base read density and junction counts of many regions (sashimi_plot, misopy/sashimi_plot/plot_utils/
  * plot_gene.py:48-57, 398-444 readsToWiggle_pysam) ----
  * Regions: n_regions triples (seqid[i], tx_start[i], tx_end[i]) in the numbers a GFF gives (1-based, inclusive); seqid[i]

@@ -1324,7 +1324,14 @@ class InsertStats(C.Structure):
 
 def _intervals(seqids, starts, ends):
     n = len(seqids)
-    names = (C.c_char_p * max(n, 1))(*[s.encode() if isinstance(s, str) else s for s in seqids])
+    # one C string per distinct name and an array of their addresses (an annotation has 10^5 - 10^6 intervals on a few
+    # dozen names: setting a c_char_p array entry by entry costs more than the device pass it feeds)
+    held = {s: C.create_string_buffer(s.encode() if isinstance(s, str) else s) for s in set(seqids)}
+    addr = {s: C.addressof(b) for s, b in held.items()}
+    ptrs = np.zeros(max(n, 1), np.uint64)
+    ptrs[:n] = [addr[s] for s in seqids]
+    names = (C.c_char_p * max(n, 1)).from_buffer(ptrs)      # shares ptrs' memory and keeps it alive
+    names.held = held
     st = np.ascontiguousarray(starts, dtype=np.int64)
     en = np.ascontiguousarray(ends, dtype=np.int64)
     if len(st) != n or len(en) != n:
@@ -1386,6 +1393,22 @@ def region_counts(alnfile, seqids, starts, ends, device=0, chunk_records=0):
                                      C.c_void_p, C.POINTER(RegionStats)]
     check(L.miso_region_counts(alnfile._h, int(device), n, names, _p(st), _p(en), int(chunk_records), _p(counts),
                                C.byref(stats)))
+    return counts[:n].copy(), stats.as_dict()
+
+
+# ---- fetch counts of many intervals (include/miso_alnio.h miso_fetch_counts) ----
+def fetch_counts(alnfile, seqids, starts, ends, device=0, chunk_records=0):
+    """len(bamfile.fetch(seqid, start, end)) for every interval of an open alignment file (sam_utils.Samfile) in one
+    device pass: the records on the reference named seqid with pos < end and bam_endpos > start, the numbers used as
+    given, seqids spelled as the file spells them.  Returns (int64 counts per interval, stats dict)."""
+    n, names, st, en = _intervals(seqids, starts, ends)
+    counts = np.zeros(max(n, 1), np.int64)
+    stats = RegionStats()
+    L = lib()
+    L.miso_fetch_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.POINTER(RegionStats)]
+    check(L.miso_fetch_counts(alnfile._h, int(device), n, names, _p(st), _p(en), int(chunk_records), _p(counts),
+                              C.byref(stats)))
     return counts[:n].copy(), stats.as_dict()
 
 

@@ -68,6 +68,11 @@ void region_counts(const miso_alnfile_t *f, int device, int n_iv, const char *co
                    const int64_t *end, int64_t chunk, int64_t *counts, miso_region_stats_t *stats);
 }  // namespace miso
 
+namespace miso {   // kernels_rpkm.hip
+void fetch_counts(const miso_alnfile_t *f, int device, int n_iv, const char *const *seqid, const int64_t *start,
+                  const int64_t *end, int64_t chunk, int64_t *counts, miso_region_stats_t *stats);
+}  // namespace miso
+
 namespace miso {   // kernels_density.hip
 void region_densities(const miso_alnfile_t *f, int device, int n_regions, const char *const *seqid, const int64_t *start,
                       const int64_t *end, int64_t chunk, int64_t accum_bytes, int32_t *depth, double *wiggle,
@@ -547,6 +552,12 @@ int miso_region_counts(const miso_alnfile_t *f, int device, int n_intervals, con
                        const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
                        miso_region_stats_t *stats) {
   return guarded([&] { region_counts(f, device, n_intervals, seqid, start, end, chunk_records, counts, stats); });
+}
+
+int miso_fetch_counts(const miso_alnfile_t *f, int device, int n_intervals, const char *const *seqid,
+                      const int64_t *start, const int64_t *end, int64_t chunk_records, int64_t *counts,
+                      miso_region_stats_t *stats) {
+  return guarded([&] { fetch_counts(f, device, n_intervals, seqid, start, end, chunk_records, counts, stats); });
 }
 
 int miso_region_densities(const miso_alnfile_t *f, int device, int n_regions, const char *const *seqid,

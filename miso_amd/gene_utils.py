@@ -88,6 +88,16 @@ class Gene(object):
                                          label=None if transcript_ids is None else transcript_ids[n]))
         self.iso_lens = [iso.len for iso in self.isoforms]
 
+    def isoform_has_part(self, isoform, part):
+        """Does the isoform hold a part with the same start and end? (Gene.py:155-163)"""
+        return any(p.start == part.start and p.end == part.end for p in isoform.parts)
+
+    def get_const_parts(self):
+        """The constitutive parts: every element of `parts` that every isoform holds (Gene.py:165-181).  `parts` has
+        one object per GFF record, so an exon all T transcripts share comes back T times; sam_rpkm counts each copy."""
+        return [part for part in self.parts
+                if all(self.isoform_has_part(iso, part) for iso in self.isoforms)]
+
     def get_part_by_label(self, part_label):
         return next((p for p in self.parts if p.label == part_label), None)
 
