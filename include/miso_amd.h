@@ -347,6 +347,59 @@ int miso_batch_get_rank_diagnostics(const miso_batch_t *batch, int event_index, 
 /* Kernel time (HIP events) of the last miso_batch_diagnose_rank of this batch, ms; 0 before. */
 int miso_batch_rank_pass_ms(const miso_batch_t *batch, float *ms);
 
+/* Posterior predictive model check of single-end events (csrc/kernels_model_check.hip; the arithmetic
+   contract is include/miso_model_check.h).  The model draws a read uniformly from the start positions of its isoform, so a
+   read falls into class c of the gene's assignment matrix (pattern_c = its set of isoforms, m_c > 0 its start positions,
+   columns in miso_gene_assignment_matrix's order) with probability p_c = w_c / T_0, w_c = m_c sum_{k in pattern_c} psi_k.
+   For every posterior row s the kernel draws a replicate n_rep ~ Multinomial(N, p(psi_s)) and compares the Freeman-Tukey
+   discrepancy D(n, p) = sum_c (sqrt n_c - sqrt(N p_c))^2 of the replicate with the observed counts'.  A row whose T_0 is
+   zero, negative or not finite is a bad row: counted, skipped.
+     status      MISO_FIT_OK; MISO_FIT_NO_GENE (added without a gene structure); MISO_FIT_NO_READS (N = 0);
+                 MISO_FIT_TOO_MANY_CLASSES (more than 64 classes or isoforms); MISO_FIT_NO_ROWS (every row bad).
+                 Every other result of an event whose status is not MISO_FIT_OK is 0.
+     rows, bad_rows, exceed = #{s : D(n_rep_s, p_s) >= D(n, p_s)}: the posterior predictive p-value is exceed / rows
+     sum_obs, sum_rep = the sums of the two discrepancies over the rows
+     per class: expected = N (sum_s p_c) / rows;  ge = #{n_rep_c >= n_c},  le = #{n_rep_c <= n_c}
+   The integers are exact; the double sums are made in one fixed order (every thread its own rows ascending, then the 256
+   partial sums folded in halves): two runs give the same bits.
+   miso_model_check, the raw call: n_events events; event i has noiso[i] isoforms, n_classes[i] classes at
+   class_off[i] .. class_off[i + 1] of pattern / m / n (class_off: n_events + 1 entries from 0), n_samples[i] rows of
+   noiso[i] doubles at samples + sample_off[i] (row s = psi of draw s; n_sample_doubles = the extent of `samples`), and
+   the Philox event id event_id[i]: the replicate of row s draws from the word stream (seed, event_id, chain 0, iteration
+   s, site 6).  Results per event, and per class in class_off's layout.  MISO_EINVAL for tables that do not fit together
+   (offsets, a pattern naming an isoform >= noiso or none, m < 1, n < 0, N > 2^24, rows outside `samples`);
+   MISO_ENODEVICE without a GPU: there is no CPU path.  A failed call leaves the result arrays as they were. */
+#define MISO_FIT_OK 0
+#define MISO_FIT_NO_GENE 1
+#define MISO_FIT_NO_READS 2
+#define MISO_FIT_TOO_MANY_CLASSES 3
+#define MISO_FIT_NO_ROWS 4
+int miso_model_check(int device, int n_events, const int32_t *noiso, const int32_t *n_classes, const int64_t *class_off,
+                     const uint64_t *pattern, const int64_t *m, const int32_t *n, const uint64_t *sample_off,
+                     const int32_t *n_samples, const uint32_t *event_id, const double *samples, uint64_t n_sample_doubles,
+                     uint64_t seed, int32_t *status, int32_t *rows, int32_t *bad_rows, int32_t *exceed, double *sum_obs,
+                     double *sum_rep, double *expected, int32_t *ge, int32_t *le, float *kernel_ms);
+/* The same for a batch.  miso_batch_set_model_check, before any event is added: MISO_EINVAL for a paired-end batch (its
+   classes are compatibility x fragment length), MISO_UNIMPLEMENTED with overHang > 1 (the assignment matrix's own
+   limit).  With the switch on, miso_batch_add_event and miso_batch_add_simulated keep the gene's class table; an event
+   added any other way has status MISO_FIT_NO_GENE.  With it off nothing is computed and nothing changes.
+   miso_batch_model_check_table (host only, no device): the event's table -- status (MISO_FIT_OK, _NO_GENE or
+   _TOO_MANY_CLASSES), n_classes, and up to max_classes entries of pattern / m / n; n_reads = N = sum n; n_off = the
+   reads with a non-empty compatibility pattern that is no column (clipped reads, indels, a template the positions cannot
+   produce); reads compatible with no isoform are in neither.  Any output may be NULL.
+   miso_batch_model_check, after the batch was launched (stop = CONVERGENT_MEAN: its further rounds are finished first):
+   the raw call's kernel over the resident samples, event ids as the launch's; it only reads.  Results are stored in the
+   batch; a refused or failed call leaves the earlier ones in place.  miso_batch_get_model_check: one event's results,
+   the per-class ones up to max_classes entries.  miso_batch_model_check_ms: kernel time (HIP events) of the last pass. */
+int miso_batch_set_model_check(miso_batch_t *batch, int on);
+int miso_batch_model_check_table(const miso_batch_t *batch, int event_index, int max_classes, int *status, int *n_classes,
+                                 uint64_t *pattern, int64_t *m, int32_t *n, int64_t *n_reads, int64_t *n_off);
+int miso_batch_model_check(miso_batch_t *batch, uint64_t seed);
+int miso_batch_get_model_check(const miso_batch_t *batch, int event_index, int max_classes, int *status, int32_t *rows,
+                               int32_t *bad_rows, int32_t *exceed, double *sum_obs, double *sum_rep, double *expected,
+                               int32_t *ge, int32_t *le);
+int miso_batch_model_check_ms(const miso_batch_t *batch, float *ms);
+
 /* Samples that were produced elsewhere -- parsed `.miso` files: summarize_miso and compare_miso work on directories of
    them (misopy/samples_utils.py:263-329, hypothesis_test.py:186-345).  Event i has noiso[i] isoforms and n_samples
    samples in the file's layout (samples[i]: n_samples rows of noiso[i] values).  The batch lives on `device` and

@@ -192,19 +192,78 @@ class EventResult:
                 (rd.noIso, rd.noIters, rd.noBurnIn, rd.noLag, rd.noAccepted, rd.noRejected))
 
 
+# ---- the posterior predictive model check (include/miso_amd.h miso_model_check) ----
+FIT_STATUS = ("ok", "no_gene", "no_reads", "too_many_classes", "no_rows")
+
+
+class ModelFit:
+    """One event's model check: status (a FIT_STATUS name); the class table pattern / m / n (class order = the assignment
+    matrix's columns), num_reads = sum n, num_off_model; rows, bad_rows, exceed, sum_obs, sum_rep; per class expected, ge, le.
+    pvalue = exceed / rows.  Everything but the table is zero unless status == "ok"."""
+
+    def __init__(self, status, pattern, m, n, num_reads, num_off_model, rows, bad_rows, exceed, sum_obs, sum_rep, expected,
+                 ge, le):
+        self.status, self.pattern, self.m, self.n = status, pattern, m, n
+        self.num_reads, self.num_off_model = int(num_reads), int(num_off_model)
+        self.rows, self.bad_rows, self.exceed = int(rows), int(bad_rows), int(exceed)
+        self.sum_obs, self.sum_rep = float(sum_obs), float(sum_rep)
+        self.expected, self.ge, self.le = expected, ge, le
+
+    @property
+    def ok(self):
+        return self.status == "ok"
+
+    @property
+    def pvalue(self):
+        return self.exceed / self.rows if self.ok else float("nan")
+
+
+def model_check(K, pattern, m, n, samples, event_id=None, seed=0, device=0):
+    """miso_model_check on caller-given tables: per event e, K[e] isoforms, the classes pattern[e] / m[e] / n[e] (sequences of
+    equal length) and samples[e], an array [S, K[e]] of posterior rows.  Returns ([ModelFit], kernel_ms)."""
+    L = lib()
+    ne = len(K)
+    Ks = np.asarray(K, dtype=np.int32)
+    Cs = np.asarray([len(x) for x in pattern], dtype=np.int32)
+    coff = np.concatenate([[0], np.cumsum(Cs, dtype=np.int64)]).astype(np.int64)
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt).reshape(-1) for x in xs] + [np.zeros(1, dt)]))
+    pat, mm, nn = cat(pattern, np.uint64), cat(m, np.int64), cat(n, np.int32)
+    rows = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, int(k)) for x, k in zip(samples, Ks)]
+    Ss = np.asarray([r.shape[0] for r in rows], dtype=np.int32)
+    soff = np.concatenate([[0], np.cumsum([r.size for r in rows], dtype=np.int64)]).astype(np.uint64)
+    flat = cat(rows, np.float64)
+    ids = np.arange(ne, dtype=np.uint32) if event_id is None else np.asarray(event_id, dtype=np.uint32)
+    nc = int(coff[-1]) + 1
+    st, ro, ba, ex = (np.zeros(max(ne, 1), np.int32) for _ in range(4))
+    so, sr = np.zeros(max(ne, 1)), np.zeros(max(ne, 1))
+    exp, ge, le = np.zeros(nc), np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+    ms = C.c_float(0)
+    check(L.miso_model_check(int(device), ne, _p(Ks), _p(Cs), _p(coff), _p(pat), _p(mm), _p(nn), _p(soff[:-1].copy()), _p(Ss),
+                             _p(ids), _p(flat), C.c_uint64(int(soff[-1])), C.c_uint64(int(seed)), _p(st), _p(ro), _p(ba), _p(ex),
+                             _p(so), _p(sr), _p(exp), _p(ge), _p(le), C.byref(ms)))
+    out = []
+    for e in range(ne):
+        a, b = int(coff[e]), int(coff[e + 1])
+        out.append(ModelFit(FIT_STATUS[st[e]], pat[a:b], mm[a:b], nn[a:b], int(nn[a:b].sum()), 0, ro[e], ba[e], ex[e], so[e],
+                            sr[e], exp[a:b], ge[a:b], le[a:b]))
+    return out, ms.value
+
+
 class Batch:
     """Many events, one launch (miso_batch_* in include/miso_amd.h)."""
 
     def __init__(self, read_len, iters=5000, burn=500, lag=10, chains=6, overhang=1, paired=False,
                  mean=0.0, var=0.0, num_devs=4.0, start=MISO_START_AUTO, stop=MISO_STOP_FIXEDNO,
                  algo=MISO_ALGO_REASSIGN, max_iters=100000, counts_trace=False, device_match=False,
-                 collapsed=False, exact=False, exact_paired=False):
+                 collapsed=False, exact=False, exact_paired=False, model_check=False):
         """collapsed (single-end): the two-isoform events draw their assignment COUNTS directly (one exact binomial
         per iteration instead of one uniform per read; miso_batch_set_collapsed in include/miso_amd.h).
         exact (single-end, algo = REASSIGN): the eligible two-isoform events run no chain, their samples are independent
         draws from the posterior of psi itself, tabulated once per event (miso_batch_set_exact in include/miso_amd.h).
         exact_paired (paired-end, algo = REASSIGN): the same for the eligible paired-end two-isoform events, a switch of its
-        own (miso_batch_set_exact_paired in include/miso_amd.h)."""
+        own (miso_batch_set_exact_paired in include/miso_amd.h).
+        model_check (single-end, overhang <= 1): every event added with its gene keeps the gene's class table for the
+        posterior predictive check, model_check() (miso_batch_set_model_check in include/miso_amd.h)."""
         self.params = Params(int(paired), read_len, overhang, chains, iters, max_iters, burn, lag,
                              algo, start, stop, mean, var, num_devs, int(counts_trace),
                              int(device_match))
@@ -219,6 +278,9 @@ class Batch:
         self.exact_paired = bool(exact_paired)
         if exact_paired:
             check(lib().miso_batch_set_exact_paired(self.handle, 1))
+        self.model_check_on = bool(model_check)
+        if model_check:
+            check(lib().miso_batch_set_model_check(self.handle, 1))
 
     def set_exact_paired(self, on=True):
         """Switch the paired-end exact-posterior mode on or off, also after the upload: the next launch makes its lists anew
@@ -354,6 +416,50 @@ class Batch:
         lag = buf[3].astype(np.int64)
         return [(buf[0, offs[j]:offs[j + 1]], buf[1, offs[j]:offs[j + 1]], buf[2, offs[j]:offs[j + 1]], lag[offs[j]:offs[j + 1]])
                 for j in range(len(indices))]
+
+    def model_check_table(self, i):
+        """The class table of event i of a Batch(model_check=True), on the host (miso_batch_model_check_table): a dict of
+        status (FIT_STATUS name), pattern (uint64[C], bit k = isoform k), m (int64[C] start positions), n (int32[C] reads),
+        num_reads (their sum) and num_off_model (reads whose non-empty pattern is no class)."""
+        L = lib()
+        st, nc, nr, no = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+        check(L.miso_batch_model_check_table(self.handle, int(i), 0, C.byref(st), C.byref(nc), None, None, None, C.byref(nr),
+                                             C.byref(no)))
+        pat, m, n = np.zeros(nc.value, np.uint64), np.zeros(nc.value, np.int64), np.zeros(nc.value, np.int32)
+        check(L.miso_batch_model_check_table(self.handle, int(i), nc.value, None, None, _p(pat), _p(m), _p(n), None, None))
+        return {"status": FIT_STATUS[st.value], "pattern": pat, "m": m, "n": n, "num_reads": nr.value, "num_off_model": no.value}
+
+    def model_check(self, seed=0):
+        """The posterior predictive model check of every event over the resident samples (miso_batch_model_check, DESIGN.md
+        22); it only reads.  Results: model_fit(i) / model_fit_many(indices)."""
+        check(lib().miso_batch_model_check(self.handle, C.c_uint64(int(seed))))
+
+    def model_fit(self, i):
+        """ModelFit of event i after model_check(), its class table included."""
+        return self.model_fit_many([i])[0]
+
+    def model_fit_many(self, indices):
+        """[ModelFit] of the given events after model_check(): model_fit() for many events."""
+        L = lib()
+        h = self.handle
+        out = []
+        st, rows, bad, exc = C.c_int(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        so, sr = C.c_double(0), C.c_double(0)
+        for i in indices:
+            t = self.model_check_table(int(i))
+            nc = len(t["n"])
+            exp, ge, le = np.zeros(nc), np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+            check(L.miso_batch_get_model_check(h, int(i), nc, C.byref(st), C.byref(rows), C.byref(bad), C.byref(exc),
+                                               C.byref(so), C.byref(sr), _p(exp), _p(ge), _p(le)))
+            out.append(ModelFit(FIT_STATUS[st.value], t["pattern"], t["m"], t["n"], t["num_reads"], t["num_off_model"],
+                                rows.value, bad.value, exc.value, so.value, sr.value, exp, ge, le))
+        return out
+
+    def model_check_ms(self):
+        """Kernel time of the last model_check() of this batch (HIP events), ms."""
+        a = C.c_float(0)
+        check(lib().miso_batch_model_check_ms(self.handle, C.byref(a)))
+        return a.value
 
     def pass_ms(self):
         """(summarize_ms, diagnose_ms): kernel time of the last summarize() and diagnose() of this batch (HIP events)."""

@@ -396,6 +396,23 @@ struct miso_batch {
   bool rank_diagnosed = false;
   float summarize_ms = 0.f, diagnose_ms = 0.f;   // kernel time of the last summarize / diagnose pass
   float rank_ms = 0.f;                  // and of the last diagnose_rank pass (each timed by its own HipCall's events)
+  // the posterior predictive model check (miso_batch_set_model_check; kernels_model_check.hip): per event
+  // added with a gene its class table (pattern, m); the observed counts are read from the event's own read classes when
+  // asked for (fit_counts), so that an event matched on the device has them once it is resolved
+  bool model_check_on = false;
+  struct FitTable { int status = MISO_FIT_NO_GENE; std::vector<uint64_t> pattern; std::vector<int64_t> m; };
+  std::vector<FitTable> fit_tables;     // one per event while the switch is on (an event beyond it: no gene)
+  const FitTable &fit_table(int i) const { static const FitTable none; return i < static_cast<int>(fit_tables.size()) ? fit_tables[i] : none; }
+  void fit_add(const miso::Gene *g);    // the table of the event added last (null: added without a gene)
+  void fit_counts(int i, std::vector<int32_t> &n, int64_t *n_reads, int64_t *n_off) const;
+  struct FitResults {                   // per event, per class at class_off[i] + c
+    std::vector<int64_t> class_off;
+    std::vector<int32_t> status, rows, bad_rows, exceed, ge, le;
+    std::vector<double> sum_obs, sum_rep, expected;
+  } fit;
+  bool model_checked = false;
+  float model_check_ms = 0.f;
+  void model_check(uint64_t seed);
   bool adopted = false;                 // samples produced elsewhere (adopt_pool): p.noChains says nothing about them
   uint64_t in_bytes = 0, out_bytes = 0;
   float last_ms = 0.f;

@@ -19,6 +19,7 @@
 #include "batch.hpp"
 #include "compare_pairs.hpp"
 #include "coop.hpp"
+#include "model_check.hpp"
 #include "miso_alnio.h"
 
 extern "C" int miso_usable_threads(void);   // alnio.cpp: affinity mask capped by the cgroup quota
@@ -265,6 +266,7 @@ int miso_batch_add_event(miso_batch_t *b, const miso_gene_t *gene, const int *po
       PackedEvent ph;
       ph.K = g.K; ph.N = N; ph.paired = b->p.paired != 0;
       b->events.push_back(std::move(ph));
+      if (b->model_check_on) b->fit_add(&g);
       if (event_index) *event_index = static_cast<int>(b->events.size()) - 1;
       return;
     }
@@ -281,6 +283,7 @@ int miso_batch_add_event(miso_batch_t *b, const miso_gene_t *gene, const int *po
                                    b->p.paired ? fraglen.data() : nullptr, g.isolen.data(),
                                    g.noexons.data(), hyperp));
     attach_gene_classes(b->events.back(), b->p, g);   // algorithm = CLASSES only
+    if (b->model_check_on) b->fit_add(&g);
     if (event_index) *event_index = static_cast<int>(b->events.size()) - 1;
   });
 }
@@ -298,6 +301,7 @@ int miso_batch_add_problem(miso_batch_t *b, int noiso, int n_reads, const double
       MISO_FAIL(MISO_UNIMPLEMENTED, "The CLASSES algorithm needs the gene's structure (miso_batch_add_event)");
     b->events.push_back(pack_event(b->p, b->p.paired ? &b->fd : nullptr, noiso, n_reads, match,
                                    fragmentLength, isolength, noexons, hyperp));
+    if (b->model_check_on) b->fit_add(nullptr);
     if (event_index) *event_index = static_cast<int>(b->events.size()) - 1;
   });
 }
@@ -525,6 +529,7 @@ int miso_batch_add_events_aln(miso_batch_t *b, int n, const miso_gene_t *const *
       ph.K = pe.gene.K; ph.N = N; ph.paired = paired != 0;
       b->pending.push_back(std::move(pe));
       b->events.push_back(std::move(ph));
+      if (b->model_check_on) b->fit_add(&b->pending.back().gene);
       event_index[i] = static_cast<int>(b->events.size()) - 1;
     }
   });
@@ -864,6 +869,91 @@ int miso_batch_rank_pass_ms(const miso_batch_t *b, float *ms) {
   return guarded([&] {
     need(b, "batch");
     if (ms) *ms = b->rank_ms;
+  });
+}
+
+// ---- the posterior predictive model check (kernels_model_check.hip) ----
+int miso_model_check(int device, int n_events, const int32_t *noiso, const int32_t *n_classes, const int64_t *class_off,
+                     const uint64_t *pattern, const int64_t *m, const int32_t *n, const uint64_t *sample_off,
+                     const int32_t *n_samples, const uint32_t *event_id, const double *samples, uint64_t n_sample_doubles,
+                     uint64_t seed, int32_t *status, int32_t *rows, int32_t *bad_rows, int32_t *exceed, double *sum_obs,
+                     double *sum_rep, double *expected, int32_t *ge, int32_t *le, float *kernel_ms) {
+  return guarded([&] {
+    if (n_events > 0) {
+      need(status, "status"); need(rows, "rows"); need(bad_rows, "bad_rows"); need(exceed, "exceed"); need(sum_obs, "sum_obs");
+      need(sum_rep, "sum_rep"); need(expected, "expected"); need(ge, "ge"); need(le, "le");
+    }
+    if (device_count() <= 0) MISO_FAIL(MISO_ENODEVICE, "no HIP device: the model check has no CPU path");
+    set_device(device);
+    ModelCheckInput in;
+    in.n = n_events; in.K = noiso; in.C = n_classes; in.class_off = class_off; in.pattern = pattern; in.m = m; in.counts = n;
+    in.sample_off = sample_off; in.S = n_samples; in.event_id = event_id; in.h_samples = samples;
+    in.n_sample_doubles = n_sample_doubles; in.seed = seed;
+    const float ms = model_check_run(in, ModelCheckOutput{status, rows, bad_rows, exceed, sum_obs, sum_rep, expected, ge, le}, nullptr);
+    if (kernel_ms) *kernel_ms = ms;
+  });
+}
+
+int miso_batch_set_model_check(miso_batch_t *b, int on) {
+  return guarded([&] {
+    need(b, "batch");
+    if (on && b->p.paired) MISO_FAIL(MISO_EINVAL, "the model check takes single-end events only: a paired-end read's class is compatibility x fragment length");
+    if (on && b->p.overHang > 1) MISO_FAIL(MISO_UNIMPLEMENTED, "Overhang is not implemented in assignment matrix yet.");
+    if (!b->events.empty() && (on != 0) != b->model_check_on) MISO_FAIL(MISO_EINVAL, "the model check is switched before the first event is added");
+    b->model_check_on = on != 0;
+  });
+}
+
+int miso_batch_model_check_table(const miso_batch_t *b, int i, int max_classes, int *status, int *n_classes, uint64_t *pattern,
+                                 int64_t *m, int32_t *n, int64_t *n_reads, int64_t *n_off) {
+  return guarded([&] {
+    need(b, "batch");
+    (void) event_at(b, i);
+    if (!b->model_check_on) MISO_FAIL(MISO_EINVAL, "the model check is not switched on (miso_batch_set_model_check)");
+    for (const miso_batch::Pending &pe : b->pending)
+      if (pe.event == i) MISO_FAIL(MISO_EINVAL, "event still to be matched on the device: its reads are not known before the upload");
+    const miso_batch::FitTable &t = b->fit_table(i);
+    std::vector<int32_t> counts;
+    b->fit_counts(i, counts, n_reads, n_off);
+    if (status) *status = t.status;
+    if (n_classes) *n_classes = static_cast<int>(t.pattern.size());
+    for (int c = 0; c < static_cast<int>(t.pattern.size()) && c < max_classes; c++) {
+      if (pattern) pattern[c] = t.pattern[c];
+      if (m) m[c] = t.m[c];
+      if (n) n[c] = counts[c];
+    }
+  });
+}
+
+int miso_batch_model_check(miso_batch_t *b, uint64_t seed) {
+  return guarded([&] { need(b, "batch"); b->model_check(seed); });
+}
+
+int miso_batch_get_model_check(const miso_batch_t *b, int i, int max_classes, int *status, int32_t *rows, int32_t *bad_rows,
+                               int32_t *exceed, double *sum_obs, double *sum_rep, double *expected, int32_t *ge, int32_t *le) {
+  return guarded([&] {
+    need(b, "batch");
+    (void) event_at(b, i);
+    if (!b->model_checked) MISO_FAIL(MISO_EINVAL, "miso_batch_model_check has not run");
+    const miso_batch::FitResults &r = b->fit;
+    if (status) *status = r.status[i];
+    if (rows) *rows = r.rows[i];
+    if (bad_rows) *bad_rows = r.bad_rows[i];
+    if (exceed) *exceed = r.exceed[i];
+    if (sum_obs) *sum_obs = r.sum_obs[i];
+    if (sum_rep) *sum_rep = r.sum_rep[i];
+    for (int64_t c = r.class_off[i]; c < r.class_off[i + 1] && c - r.class_off[i] < max_classes; c++) {
+      if (expected) expected[c - r.class_off[i]] = r.expected[c];
+      if (ge) ge[c - r.class_off[i]] = r.ge[c];
+      if (le) le[c - r.class_off[i]] = r.le[c];
+    }
+  });
+}
+
+int miso_batch_model_check_ms(const miso_batch_t *b, float *ms) {
+  return guarded([&] {
+    need(b, "batch");
+    if (ms) *ms = b->model_check_ms;
   });
 }
 

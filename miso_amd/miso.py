@@ -134,7 +134,13 @@ class GenesDispatcher(object):
                  event_type=None, seed=None, summarize=False, compare_bam=None,
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                  exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                 delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False):
+                 delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False,
+                 model_check=False):
+        # --model-check: beside the outputs the `.miso_fit` table (model_check.py) of every directory of `.miso` files, merged
+        # like a diagnostics table; single-end only
+        self.model_check = bool(model_check)
+        if self.model_check and paired_end is not None:
+            raise ValueError("--model-check is single-end only")
         # --exact-stats: beside the outputs the `.miso_exact_stats` table (compare.py) of every directory of `.miso` files,
         # merged like a diagnostics table
         self.exact_stats = bool(exact_stats)
@@ -302,6 +308,12 @@ class GenesDispatcher(object):
                 label = os.path.basename(os.path.normpath(d))
                 stables.append((os.path.join(d, "summary", label + ".miso_exact_stats"), []))
                 os.makedirs(os.path.dirname(stables[-1][0]), exist_ok=True)
+        ftables = []                   # --model-check: [(table, its per-worker parts)], one per directory of `.miso` files
+        if self.model_check:
+            for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
+                label = os.path.basename(os.path.normpath(d))
+                ftables.append((os.path.join(d, "summary", label + ".miso_fit"), []))
+                os.makedirs(os.path.dirname(ftables[-1][0]), exist_ok=True)
         if self.exact_paired_stats:    # --exact-paired-stats: (the `.miso_exact_pairs` table, its per-worker parts); no --compare
             label = os.path.basename(os.path.normpath(self.output_dir))
             ptable = (os.path.join(self.output_dir, "summary", label + ".miso_exact_pairs"), [])
@@ -342,6 +354,11 @@ class GenesDispatcher(object):
                     for (_, plist), sp in zip(stables, sparts):
                         plist.append(sp)
                     cmd += ["--exact-stats-files"] + sparts
+                if ftables:
+                    fparts = ["%s.gpu%d" % (t, batch_num) for t, _ in ftables]
+                    for (_, plist), fp in zip(ftables, fparts):
+                        plist.append(fp)
+                    cmd += ["--model-check-files"] + fparts
             else:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compute-genes-from-file", fname,
                        self.bam_filename, self.output_dir]
@@ -355,6 +372,9 @@ class GenesDispatcher(object):
                 if stables:
                     stables[0][1].append("%s.gpu%d" % (stables[0][0], batch_num))
                     cmd += ["--exact-stats-file", stables[0][1][-1]]
+                if ftables:
+                    ftables[0][1].append("%s.gpu%d" % (ftables[0][0], batch_num))
+                    cmd += ["--model-check-file", ftables[0][1][-1]]
                 if self.exact_paired_stats:
                     ptable[1].append("%s.gpu%d" % (ptable[0], batch_num))
                     cmd += ["--exact-pairs-file", ptable[1][-1]]
@@ -380,7 +400,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
-        self.diag_tables += xtable + dtable + etable + stables + ([ptable] if self.exact_paired_stats else [])
+        self.diag_tables += xtable + dtable + etable + stables + ftables + ([ptable] if self.exact_paired_stats else [])
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -453,7 +473,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           seed=None, summarize=False, compare_bam=None,
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                           exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
-                          delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False):
+                          delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False,
+                          model_check=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -468,7 +489,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
                            delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
                            delta_posterior=delta_posterior, exact_delta_posterior=exact_delta_posterior,
-                           exact_stats=exact_stats, exact_paired_stats=exact_paired_stats).run()
+                           exact_stats=exact_stats, exact_paired_stats=exact_paired_stats, model_check=model_check).run()
 
 
 def main(argv=None):
@@ -499,6 +520,11 @@ def main(argv=None):
                     help="with --diagnostics: six more columns per event from the rank-normalised pass -- the larger of the bulk "
                          "and the folded rank R-hat, the bulk effective sample size, the effective sample size of the 95 %% "
                          "credible interval's two bounds and the smaller of them, and the number of distinct draws")
+    ap.add_argument("--model-check", action="store_true",
+                    help="single-end runs: also write OUT/summary/<OUT>.miso_fit (with --compare one table per label, where "
+                         ".miso_diag goes): per event a posterior predictive check of its reads against the read classes the "
+                         "model expects -- a p-value, observed and expected reads per class and which class is short or in "
+                         "excess --, computed on the GPU during the run with the run's seed; every other output is unchanged")
     ap.add_argument("--exact", action="store_true",
                     help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
                          "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
@@ -555,6 +581,8 @@ def main(argv=None):
     Settings.load(settings_filename)
     if a.exact_paired and a.paired_end is None:     # argument errors, before any work
         ap.error("--exact-paired goes with --paired-end")
+    if a.model_check and a.paired_end is not None:
+        ap.error("--model-check is single-end only: a paired-end read's class is compatibility x fragment length")
     if a.rank_diagnostics and not a.diagnostics:
         ap.error("--rank-diagnostics goes with --diagnostics")
     if a.exact_stats and (a.paired_end or not (a.exact or Settings.get_exact())):
@@ -616,7 +644,8 @@ def main(argv=None):
                                        exact_paired=a.exact_paired,
                                        delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics,
                                        delta_posterior=a.delta_posterior, exact_delta_posterior=a.exact_delta_posterior,
-                                       exact_stats=a.exact_stats, exact_paired_stats=a.exact_paired_stats)
+                                       exact_stats=a.exact_stats, exact_paired_stats=a.exact_paired_stats,
+                                       model_check=a.model_check)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

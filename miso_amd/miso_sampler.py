@@ -30,6 +30,7 @@ EXACT_PAIRED_ENV = "MISO_EXACT_PAIRED"
 import summary  # noqa: E402  (miso_amd/summary.py)
 import diagnostics  # noqa: E402  (miso_amd/diagnostics.py)
 import compare  # noqa: E402  (miso_amd/compare.py)
+import model_check  # noqa: E402  (miso_amd/model_check.py)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -166,7 +167,7 @@ class MISOSampler:
                           start_cond=pysplicing.MISO_START_AUTO,
                           stop_cond=pysplicing.MISO_STOP_FIXEDNO, seed=None, first_event_id=0,
                           verbose=False, summary_file=None, confidence_level=0.95, threads=0, diagnostics_file=None,
-                          rank_diagnostics=False, exact_stats_file=None):
+                          rank_diagnostics=False, exact_stats_file=None, model_fit_file=None):
         """events: list of (reads, gene, output_file[, prior_params[, event_id]]); `reads` is the
         reference's (positions 0-based, cigars) pair or an AlnRegion; event_id pins the event's
         random stream (default: first_event_id + its position among the events actually sampled).  Same per-event skip rules as run_sampler
@@ -185,7 +186,7 @@ class MISOSampler:
         return self.finish_batch(state, seed=seed, first_event_id=first_event_id, verbose=verbose,
                                  summary_file=summary_file, confidence_level=confidence_level,
                                  threads=threads, diagnostics_file=diagnostics_file, rank_diagnostics=rank_diagnostics,
-                                 exact_stats_file=exact_stats_file)
+                                 exact_stats_file=exact_stats_file, model_fit_file=model_fit_file)
 
     def exact_paired(self):
         """the paired-end exact-posterior mode is asked for: params["exact_paired"], else MISO_EXACT_PAIRED=1; never on a
@@ -214,7 +215,10 @@ class MISOSampler:
                            exact=False if self.paired_end else bool(int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0)),
                            # opt-in, paired-end: the exact-posterior mode of the eligible paired-end two-isoform events, a switch
                            # of its own (miso_batch_set_exact_paired); params["exact_paired"] or MISO_EXACT_PAIRED=1
-                           exact_paired=self.exact_paired())
+                           exact_paired=self.exact_paired(),
+                           # opt-in, single-end: every event keeps its gene's class table for the posterior predictive model
+                           # check (include/miso_amd.h miso_batch_set_model_check); params["model_check"]
+                           model_check=False if self.paired_end else bool(int(self.params.get("model_check", 0) or 0)))
         written = [None] * len(events)
         slots = []
         from sam_utils import STRAND_RULES
@@ -328,7 +332,7 @@ class MISOSampler:
 
     def finish_batch(self, state, seed=None, first_event_id=0, verbose=False, summary_file=None,
                      confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None, rank_diagnostics=False,
-                     exact_stats_file=None):
+                     exact_stats_file=None, model_fit_file=None):
         """Launch, then the event's outputs.  write_files=False (with a summary_file): no per-event `.miso` file --
         the posterior means and credible intervals that `summarize_miso` would compute from those files
         (samples_utils.py:263-329) come from the device, summarised from the four-decimal text the file WOULD hold.
@@ -337,7 +341,7 @@ class MISOSampler:
         self.launch_batch(state, seed=seed, first_event_id=first_event_id)
         return self.output_batch(state, verbose=verbose, summary_file=summary_file, confidence_level=confidence_level,
                                  threads=threads, write_files=write_files, diagnostics_file=diagnostics_file,
-                                 rank_diagnostics=rank_diagnostics, exact_stats_file=exact_stats_file)
+                                 rank_diagnostics=rank_diagnostics, exact_stats_file=exact_stats_file, model_fit_file=model_fit_file)
 
     def launch_batch(self, state, seed=None, first_event_id=0):
         """Upload, sample, download (native code, the interpreter lock released throughout)."""
@@ -346,8 +350,8 @@ class MISOSampler:
             return
         dev = int(os.environ.get("MISO_DEVICE", os.environ.get("LOCAL_RANK", "0")))
         t0 = time.time()
-        batch.run(device=dev, seed=seed if seed is not None else random.getrandbits(64),
-                  first_event_id=first_event_id)
+        batch.run_seed = seed if seed is not None else random.getrandbits(64)     # the model check draws with the run's seed
+        batch.run(device=dev, seed=batch.run_seed, first_event_id=first_event_id)
         if os.environ.get("MISO_TIMING"):
             print("[miso] batch of %d events: upload + sample + download %.2f s" % (len(slots), time.time() - t0))
 
@@ -368,7 +372,7 @@ class MISOSampler:
 
     def output_batch(self, state, verbose=False, summary_file=None, confidence_level=0.95, threads=0,
                      write_files=True, diagnostics_file=None, rank_diagnostics=False, exact_stats_file=None,
-                     exact_pairs_file=None):
+                     exact_pairs_file=None, model_fit_file=None):
         """The `.miso` files and / or the summary table of a launched batch.  The header's run-dependent fields are
         formatted natively for the whole batch (miso_batch_header_fields); miso_header() below is the same line field
         by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte).
@@ -378,10 +382,15 @@ class MISOSampler:
         (compare.write_exact_stats): the seven statistics an exact posterior is made of, as the batch holds them
         (Batch.exact_stats), and whether the exact mode took the event; nothing else changes with it.
         exact_pairs_file: the `.miso_exact_pairs` table of the written events (compare.write_exact_pairs), the same for the
-        paired exact mode: the six statistics and the drawing pairs' probabilities (Batch.exact_paired_element)."""
+        paired exact mode: the six statistics and the drawing pairs' probabilities (Batch.exact_paired_element).
+        model_fit_file (a batch prepared with params["model_check"]): the `.miso_fit` table of the written events
+        (model_check.write_model_fit), from the samples resident on the device, drawn with the run's seed; the pass only
+        reads, nothing else changes with it."""
         batch, slots, written, num_iters, burn_in, lag = state
-        stat_rows, pair_rows = [], []
+        stat_rows, pair_rows, fit_rows = [], [], []
         if not slots:
+            if model_fit_file is not None:
+                model_check.write_model_fit(model_fit_file, fit_rows)
             if exact_stats_file is not None:
                 compare.write_exact_stats(exact_stats_file, stat_rows)
             if exact_pairs_file is not None:
@@ -412,6 +421,10 @@ class MISOSampler:
                                                         [len(gene.isoforms) for _, _, gene, _ in slots])
                 except capi.InternalError as e:
                     print(diagnostics.rank_notice("%d events of %d samples in %d chains" % (len(slots), n_samples, n_chains), e))
+        fits = None
+        if model_fit_file is not None:
+            batch.model_check(batch.run_seed)
+            fits = batch.model_fit_many([idx for _, idx, _, _ in slots])
         for j, ((i, idx, gene, out), (unassigned, pa, counts, assigned)) in enumerate(zip(slots, fields)):
             if unassigned:                                                # miso_sampler.py:352-354
                 if verbose:
@@ -435,6 +448,8 @@ class MISOSampler:
             if diagnostics_file is not None:
                 diag_rows.append((os.path.basename(out)[:-len(".miso")],) + tuple(diags[j]) + (n_samples, n_chains)
                                  + ((ranks[j],) if rank_diagnostics else ()))
+            if model_fit_file is not None:
+                fit_rows.append((os.path.basename(out)[:-len(".miso")], fits[j], len(gene.isoforms)))
             if exact_stats_file is not None:
                 st, was = batch.exact_stats(idx)
                 stat_rows.append((os.path.basename(out)[:-len(".miso")], was, st))
@@ -452,6 +467,8 @@ class MISOSampler:
             compare.write_exact_stats(exact_stats_file, stat_rows)
         if exact_pairs_file is not None:
             compare.write_exact_pairs(exact_pairs_file, pair_rows)
+        if model_fit_file is not None:
+            model_check.write_model_fit(model_fit_file, fit_rows)
         if timing:
             print("[miso] batch of %d events: headers %.2f s, .miso files / table %.2f s"
                   % (len(slots), t2 - t1, time.time() - t2))
@@ -463,7 +480,7 @@ class MISOSampler:
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
                              diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None,
                              rank_diagnostics=False, delta_posterior_file=None, exact_delta_file=None,
-                             exact_stats_files=None):
+                             exact_stats_files=None, model_fit_files=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -485,7 +502,12 @@ class MISOSampler:
         -- median and 95 % credible interval of delta psi, P(delta > 0), P(delta < 0) from the exact CDF
         (MISOCompareBatch(exact_delta=)) and the exact comparison's P(|delta psi| >= t).
         exact_stats_files (optional; the single-end exact mode only): (file1, file2), each sample's `.miso_exact_stats` table
-        (compare.write_exact_stats) of its written events (MISOCompareBatch(exact_stats=))."""
+        (compare.write_exact_stats) of its written events (MISOCompareBatch(exact_stats=)).
+        model_fit_files (optional; single-end only): (file1, file2), each sample's `.miso_fit` table (model_check.py) of its
+        written events, each drawn with its sample's seed (MISOCompareBatch(model_check=))."""
+        if model_fit_files is not None and self.paired_end:
+            raise ValueError("the model check takes single-end events only")
+        fit_rows = ([], [])
         if exact_stats_files is not None and (self.paired_end or not int(self.params.get("exact", os.environ.get("MISO_EXACT", 0)) or 0)):
             raise ValueError("the exact statistics tables need the exact-posterior mode (single-end)")
         stat_rows = ([], [])
@@ -540,10 +562,15 @@ class MISOSampler:
                 kw["delta_posterior"] = (float(confidence_level), tuple(dthr))
             if exact_stats_files is not None:
                 kw["exact_stats"] = True
+            if model_fit_files is not None:
+                kw["model_check"] = True
             res = pysplicing.MISOCompareBatch(
                 tuple(p[2][:4] for p in keep), tuple(p[3][:4] for p in keep),
                 int(self.params["read_len"]), int(num_iters), int(burn_in), int(lag),
                 int(self.params["overhang_len"]), int(num_chains), **kw)
+            fres = None
+            if model_fit_files is not None:      # the model check's element stands behind every other
+                fres, res = res[-1], res[:-1]
             r1, r2, cmp = res[:3]
             # the optional elements behind them, in this order: diagnostics, exact comparison, exact delta psi, all pairs
             at = 3 + (diagnostics_files is not None)
@@ -568,6 +595,12 @@ class MISOSampler:
                             diag_rows[which].append((os.path.basename(f)[:-len(".miso")],) + tuple(d[:4])
                                                     + (n_samples, int(num_chains))
                                                     + (((d[4:] if len(d) == 10 else None),) if rank_diagnostics else ()))
+                if fres is not None:
+                    for which, f in enumerate((f1, f2)):
+                        if f is not None:
+                            t = fres[which][j]
+                            fit = capi.ModelFit(capi.FIT_STATUS[t[0]], t[8], t[9], t[10], t[1], t[2], *t[3:8], t[11], t[12], t[13])
+                            fit_rows[which].append((os.path.basename(f)[:-len(".miso")], fit, len(gene.isoforms)))
                 if sres is not None:
                     for which, f in enumerate((f1, f2)):
                         if f is not None:
@@ -595,6 +628,9 @@ class MISOSampler:
         if exact_stats_files is not None:
             for f, srows in zip(exact_stats_files, stat_rows):
                 compare.write_exact_stats(f, srows)
+        if model_fit_files is not None:
+            for f, frows in zip(model_fit_files, fit_rows):
+                model_check.write_model_fit(f, frows)
         return written
 
     # -- shared pieces -------------------------------------------------------------------------

@@ -42,6 +42,10 @@
  *   exact_delta=(p, ...)  MISOCompareBatch with exact_compare= or exact_paired_compare=: the quantiles of psi_1 - psi_2 at
  *                   these probabilities (1 to 4) from the exact CDF (miso_batch_exact_delta_quantiles), one more element of the
  *                   result, behind exact_compare's: per event None or ((quantile, ...), P(psi_1 - psi_2 <= 0)).
+ *   model_check=True  MISOCompareBatch, single-end: the posterior predictive model check of both samples
+ *                   (miso_batch_set_model_check, miso_batch_model_check, each sample with its own seed), appended as the LAST
+ *                   element of the result, behind every other: per sample the events' (status, num_reads, num_off_model,
+ *                   rows, bad_rows, exceed, sum_obs, sum_rep, pattern, m, n, expected, ge, le).
  *   exact_stats=True  MISOCompareBatch with exact=True: one more element, behind exact_delta's and before delta_posterior's:
  *                   per sample the events' (was_exact, (n10, n01, n, e0, e1, h0, h1)) (miso_batch_get_exact_stats).
  * The functions of the module that are not on the sampler path raise NotImplementedError.
@@ -394,10 +398,11 @@ static int parse_level(PyObject *obj, double *conf) {
 
 /* a new batch holding `events` = ((gff, readpos, readcigar[, hyperp]), ...); exact: 1 miso_batch_set_exact, 2
    miso_batch_set_exact_paired */
-static miso_batch_t *fill_batch(PyObject *events, miso_params_t *p, int exact) {
+static miso_batch_t *fill_batch_fit(PyObject *events, miso_params_t *p, int exact, int model_check) {
   miso_batch_t *b = NULL; Py_ssize_t i, n; int rc;
   if (!PyTuple_Check(events)) { PyErr_SetString(PyExc_TypeError, "Need a tuple"); return NULL; }
   if ((rc = miso_batch_create(p, &b))) { raise_miso(rc); return NULL; }
+  if (model_check && (rc = miso_batch_set_model_check(b, 1))) { raise_miso(rc); miso_batch_destroy(b); return NULL; }
   if (exact && (rc = exact == 2 ? miso_batch_set_exact_paired(b, 1) : miso_batch_set_exact(b, 1))) {
     raise_miso(rc); miso_batch_destroy(b); return NULL;
   }
@@ -412,6 +417,44 @@ static miso_batch_t *fill_batch(PyObject *events, miso_params_t *p, int exact) {
                   PyTuple_Size(ev) == 4 ? PyTuple_GET_ITEM(ev, 3) : NULL)) { miso_batch_destroy(b); return NULL; }
   }
   return b;
+}
+
+static miso_batch_t *fill_batch(PyObject *events, miso_params_t *p, int exact) { return fill_batch_fit(events, p, exact, 0); }
+
+static PyObject *from_int32s(const int32_t *v, Py_ssize_t n) {
+  PyObject *t = PyTuple_New(n); Py_ssize_t i;
+  for (i = 0; t && i < n; i++) PyTuple_SET_ITEM(t, i, PyLong_FromLong((long) v[i]));
+  return t;
+}
+
+/* the posterior predictive model check of a finished batch (miso_batch_model_check with `seed`): per event (status, num_reads,
+   num_off_model, rows, bad_rows, exceed, sum_obs, sum_rep, pattern, m, n, expected, ge, le), the last six one value per class */
+static PyObject *model_fit_list(miso_batch_t *b, Py_ssize_t n, unsigned long long seed) {
+  Py_ssize_t i; int rc;
+  PyObject *out;
+  if (n > 0 && (rc = miso_batch_model_check(b, (uint64_t) seed))) return raise_miso(rc);
+  out = PyList_New(n);
+  for (i = 0; out && i < n; i++) {
+    int st = 0, st2 = 0, nc = 0, c; int64_t nr = 0, no = 0; int32_t rows = 0, bad = 0, exc = 0; double so = 0, sr = 0;
+    uint64_t pat[64]; int64_t m[64]; int32_t cnt[64], ge[64], le[64]; double ex[64];
+    PyObject *t, *pp, *pm;
+    if ((rc = miso_batch_model_check_table(b, (int) i, 64, &st, &nc, pat, m, cnt, &nr, &no)) ||
+        (rc = miso_batch_get_model_check(b, (int) i, 64, &st2, &rows, &bad, &exc, &so, &sr, ex, ge, le))) {
+      raise_miso(rc); Py_CLEAR(out); break;
+    }
+    if (nc > 64) nc = 0;   /* too many classes: the status says so, no per-class values */
+    pp = PyTuple_New(nc); pm = PyTuple_New(nc);
+    for (c = 0; pp && pm && c < nc; c++) {
+      PyTuple_SET_ITEM(pp, c, PyLong_FromUnsignedLongLong((unsigned long long) pat[c]));
+      PyTuple_SET_ITEM(pm, c, PyLong_FromLongLong((long long) m[c]));
+    }
+    t = (pp && pm) ? Py_BuildValue("(iLLiiiddOONNNN)", st2, (long long) nr, (long long) no, (int) rows, (int) bad, (int) exc, so, sr,
+                                   pp, pm, from_int32s(cnt, nc), from_doubles(ex, nc), from_int32s(ge, nc), from_int32s(le, nc)) : NULL;
+    Py_XDECREF(pp); Py_XDECREF(pm);
+    if (!t) { Py_CLEAR(out); break; }
+    PyList_SET_ITEM(out, i, t);
+  }
+  return out;
 }
 
 /* list of the 6-tuples of a finished batch; 7-tuples with the summary when conf > 0 */
@@ -495,7 +538,7 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   static char *kwlist[] = {"events1", "events2", "readLength", "noIterations", "noBurnIn", "noLag",
                            "overhang", "no_chains", "start", "stop", "seed", "seed2", "first_event_id",
                            "summary", "smoothing", "paired", "event_ids", "diagnostics", "exact", "exact_compare", "exact_paired",
-                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", "exact_delta", "exact_stats", NULL};
+                           "exact_paired_compare", "rank_diagnostics", "delta_posterior", "exact_delta", "exact_stats", "model_check", NULL};
   PyObject *ev1, *ev2, *seedobj = NULL, *seed2obj = NULL, *summaryobj = NULL, *pairedobj = NULL, *idsobj = NULL;
   PyObject *dpobj = NULL, *dp = NULL;   /* delta_posterior=(level, (tau, ...)): the all-pairs pass, miso_batch_compare_pairs */
   double dp_level = 0.95, dp_tau[4]; int n_dp = 0;
@@ -504,6 +547,7 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   double xz[8]; int n_xz = 0;   /* exact_compare=(z, ...): the exact comparison's delta psi points, miso_batch_compare_exact */
   PyObject *edobj = NULL, *ed = NULL;   /* exact_delta=(p, ...): the quantiles of delta psi from the exact CDF, miso_batch_exact_delta_quantiles */
   double ep[4]; int n_ep = 0;
+  int model_check = 0;              /* model_check=True (single-end): the posterior predictive model check of both samples, miso_batch_model_check */
   int exact_stats = 0;              /* exact_stats=True (with exact=True): the seven statistics of every event, miso_batch_get_exact_stats */
   PyObject *es = NULL;
   int rank_diagnostics = 0;         /* with diagnostics=True: the rank-normalised pass too (diagnostics_list) */
@@ -514,10 +558,10 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   unsigned int first = 0; double smoothing = 0.3, conf = 0.95, mean = 0, var = 0, devs = 0;
   unsigned long long seed, seed2; Py_ssize_t i, n;
   miso_params_t p; miso_batch_t *b1 = NULL, *b2 = NULL;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpOOp", kwlist, &ev1, &ev2, &readLength, &iters,
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OOi|iiiiiii$OOIOdOOppOpOpOOpp", kwlist, &ev1, &ev2, &readLength, &iters,
                                    &burn, &lag, &overhang, &chains, &start, &stop, &seedobj, &seed2obj,
                                    &first, &summaryobj, &smoothing, &pairedobj, &idsobj, &diagnostics, &exact, &xcobj,
-                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj, &edobj, &exact_stats)) return NULL;
+                                   &exact_paired, &xpobj, &rank_diagnostics, &dpobj, &edobj, &exact_stats, &model_check)) return NULL;
   if (exact_stats && !exact) { PyErr_SetString(PyExc_ValueError, "exact_stats requires exact=True"); return NULL; }
   if (dpobj == Py_None) dpobj = NULL;
   if (dpobj) {
@@ -578,8 +622,8 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
   if (!PyTuple_Check(ev1) || !PyTuple_Check(ev2)) { PyErr_SetString(PyExc_TypeError, "Need a tuple"); return NULL; }
   n = PyTuple_Size(ev1);
   if (PyTuple_Size(ev2) != n) { PyErr_SetString(PyExc_ValueError, "the two samples must list the same events"); return NULL; }
-  if (!(b1 = fill_batch(ev1, &p, exact_paired ? 2 : exact))) goto done;
-  if (!(b2 = fill_batch(ev2, &p, exact_paired ? 2 : exact))) goto done;
+  if (!(b1 = fill_batch_fit(ev1, &p, exact_paired ? 2 : exact, model_check))) goto done;
+  if (!(b2 = fill_batch_fit(ev2, &p, exact_paired ? 2 : exact, model_check))) goto done;
   /* event_ids: every event's id in the Philox counter (its number in the caller's full event list), so
      that events dropped by the caller's skip rules, the chunking and the number of GPUs change nobody's
      random stream -- as miso_batch_set_event_id does for MISOBatch's callers */
@@ -723,6 +767,18 @@ static PyObject *py_miso_compare_batch(PyObject *self, PyObject *args, PyObject 
     one = PyTuple_Pack(1, dp);
     all = one ? PySequence_Concat(out, one) : NULL;
     Py_XDECREF(one); Py_DECREF(out); out = all;
+  }
+  /* model_check=True: a last element (behind every other), per sample the events' model_fit_list tuples, each sample with its
+     own seed */
+  if (out && model_check) {
+    PyObject *one, *all, *both = NULL;
+    PyObject *f1 = model_fit_list(b1, n, seed);
+    PyObject *f2 = f1 ? model_fit_list(b2, n, seed2) : NULL;
+    if (f2) both = PyTuple_Pack(2, f1, f2);
+    Py_XDECREF(f1); Py_XDECREF(f2);
+    one = both ? PyTuple_Pack(1, both) : NULL;
+    all = one ? PySequence_Concat(out, one) : NULL;
+    Py_XDECREF(one); Py_XDECREF(both); Py_DECREF(out); out = all;
   }
 done:
   Py_XDECREF(r1); Py_XDECREF(r2); Py_XDECREF(cmp); Py_XDECREF(dg); Py_XDECREF(xc); Py_XDECREF(ed); Py_XDECREF(es); Py_XDECREF(dp);

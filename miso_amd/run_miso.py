@@ -148,7 +148,7 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
                      diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False, exact_stats_file=None,
-                     exact_pairs_file=None):
+                     exact_pairs_file=None, model_check_file=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
@@ -160,7 +160,13 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     exact_stats_file (the single-end exact mode only): also write the `.miso_exact_stats` table of the written events
     (compare.write_exact_stats), parts merged like the diagnostics table's.
     exact_pairs_file (the paired exact mode only): also write the `.miso_exact_pairs` table of the written events
-    (compare.write_exact_pairs), parts merged the same way."""
+    (compare.write_exact_pairs), parts merged the same way.
+    model_check_file (single-end only): also write the `.miso_fit` table of this run, the posterior predictive model check
+    of every written event (model_check.py), per launch from the resident samples with the run's seed, parts merged the
+    same way; nothing else changes with it."""
+    if model_check_file is not None and paired_end:
+        raise ValueError("the model check takes single-end events only")
+    fit_parts = []
     exact = Settings.get_exact() if exact is None else bool(exact)
     if exact_stats_file is not None and (paired_end or not exact):
         raise ValueError("the exact statistics table needs the exact-posterior mode (single-end)")
@@ -265,6 +271,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
                 if exact:
                     params["exact"] = 1     # miso_sampler.py prepare_batch
+                if model_check_file is not None:
+                    params["model_check"] = 1
             sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=output_dir)
             # every event keeps the number it has in the caller's gene list: skipped genes, chunking
             # and the number of GPUs do not change anybody's random stream
@@ -287,13 +295,17 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             ppart = None if exact_pairs_file is None else "%s.part%06d" % (exact_pairs_file, lo)
             if ppart:
                 pair_parts.append(ppart)
+            fpart = None if model_check_file is None else "%s.part%06d" % (model_check_file, lo)
+            if fpart:
+                fit_parts.append(fpart)
             launched = gpu.submit(sampler.launch_batch, state, seed=seed, first_event_id=first_event_id + lo)
 
-            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart, spart=spart, ppart=ppart):
+            def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart, spart=spart, ppart=ppart,
+                        fpart=fpart):
                 launched.result()
                 return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files,
                                             diagnostics_file=dpart, rank_diagnostics=rank_diagnostics, exact_stats_file=spart,
-                                            exact_pairs_file=ppart)
+                                            exact_pairs_file=ppart, model_fit_file=fpart)
             in_flight.append(out.submit(outputs))
         for f in in_flight:
             written += f.result()
@@ -308,6 +320,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
         merge_tables(stat_parts, exact_stats_file)
     if exact_pairs_file is not None:
         merge_tables(pair_parts, exact_pairs_file)
+    if model_check_file is not None:
+        merge_tables(fit_parts, model_check_file)
     t2 = time.time()
     if verbose:
         print("Collected %d events in %.2f s (beside the decoding / sampling), batches prepared in %.2f s, whole run %.2f s"
@@ -347,7 +361,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
                      exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False,
-                     delta_posterior_file=None, exact_delta_file=None, exact_stats_files=None):
+                     delta_posterior_file=None, exact_delta_file=None, exact_stats_files=None, model_check_files=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -364,7 +378,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     exact_delta_file (with exact_comparison_file only): the `.miso_dpsi_exact` table of delta psi's median and credible
     interval from the exact CDF (compare.py write_exact_dpsi), parts merged like the exact comparison's.
     exact_stats_files (the single-end exact mode only): (file1, file2), each sample's `.miso_exact_stats` table
-    (compare.py write_exact_stats), parts merged like the diagnostics tables'."""
+    (compare.py write_exact_stats), parts merged like the diagnostics tables'.
+    model_check_files (single-end only): (file1, file2), each sample's `.miso_fit` table (model_check.py), each drawn with its
+    sample's seed, parts merged like the diagnostics tables'."""
     if exact_delta_file is not None and exact_comparison_file is None:
         raise ValueError("the exact delta psi table goes with the exact comparison")
     for d in (output_dir1, output_dir2):
@@ -381,6 +397,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     if exact_stats_files is not None and (paired_end or not exact):
         raise ValueError("the exact statistics tables need the exact-posterior mode (single-end)")
     stat_parts = ([], [])
+    if model_check_files is not None and paired_end:
+        raise ValueError("the model check takes single-end events only")
+    fit_parts = ([], [])
     p = Settings.get_sampler_params()
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
     evs = []
@@ -421,6 +440,11 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             dparts = tuple("%s.part%06d" % (f, lo) for f in diagnostics_files)
             for which in (0, 1):
                 diag_parts[which].append(dparts[which])
+        fparts = None
+        if model_check_files is not None:
+            fparts = tuple("%s.part%06d" % (f, lo) for f in model_check_files)
+            for which in (0, 1):
+                fit_parts[which].append(fparts[which])
         sparts = None
         if exact_stats_files is not None:
             sparts = tuple("%s.part%06d" % (f, lo) for f in exact_stats_files)
@@ -445,7 +469,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                      event_ids=[_event_number(a[4], first_event_id, event_ids) for a, _ in chunk],
                                      diagnostics_files=dparts, exact_comparison_file=xpart,
                                      delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
-                                     delta_posterior_file=dpsi_part, exact_delta_file=epart, exact_stats_files=sparts)
+                                     delta_posterior_file=dpsi_part, exact_delta_file=epart, exact_stats_files=sparts,
+                                     model_fit_files=fparts)
     merge_tables(parts, comparison_file)
     if delta_posterior_file is not None:
         merge_tables(dpsi_parts, delta_posterior_file)
@@ -469,6 +494,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                 params = miso.get_single_end_sampler_params(2, read_len, overhang_len)
                 if exact:
                     params["exact"] = 1     # miso_sampler.py prepare_batch
+                if model_check_files is not None:
+                    params["model_check"] = 1
             sampler = miso.MISOSampler(params, paired_end=bool(paired_end), log_dir=out)
             dpart = None
             if diagnostics_files is not None:
@@ -478,15 +505,22 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             if exact_stats_files is not None:
                 spart = "%s.alone" % exact_stats_files[int(which) - 1]
                 stat_parts[int(which) - 1].append(spart)
+            fpart = None
+            if model_check_files is not None:
+                fpart = "%s.alone" % model_check_files[int(which) - 1]
+                fit_parts[int(which) - 1].append(fpart)
             sampler.run_sampler_batch(p["num_iters"], alone, num_chains=p["num_chains"], burn_in=p["burn_in"],
                                       lag=p["lag"], seed=s, verbose=verbose, diagnostics_file=dpart,
-                                      rank_diagnostics=rank_diagnostics, exact_stats_file=spart)
+                                      rank_diagnostics=rank_diagnostics, exact_stats_file=spart, model_fit_file=fpart)
     if diagnostics_files is not None:
         for which in (0, 1):
             merge_tables(diag_parts[which], diagnostics_files[which])
     if exact_stats_files is not None:
         for which in (0, 1):
             merge_tables(stat_parts[which], exact_stats_files[which])
+    if model_check_files is not None:
+        for which in (0, 1):
+            merge_tables(fit_parts[which], model_check_files[which])
     return len(pairs)
 
 
@@ -534,6 +568,11 @@ def main(argv=None):
                     help="with --compare-genes-from-file: the chain diagnostics table of each sample")
     ap.add_argument("--rank-diagnostics", action="store_true",
                     help="with --diagnostics-file(s): six more columns from the rank-normalised pass")
+    ap.add_argument("--model-check-file", default=None, metavar="F",
+                    help="with --compute-genes-from-file, single-end: also write the `.miso_fit` table of this run, per event the "
+                         "posterior predictive check of its reads against the model's read classes (device-side)")
+    ap.add_argument("--model-check-files", nargs=2, default=None, metavar=("FILE1", "FILE2"),
+                    help="with --compare-genes-from-file, single-end: that table of each sample")
     ap.add_argument("--no-miso-files", action="store_true",
                     help="with --summary-file: only the table, no per-event .miso files")
     ap.add_argument("--exact", action="store_true",
@@ -579,6 +618,13 @@ def main(argv=None):
         return 1
     overhang_len = a.overhang_len if a.overhang_len is not None else 1
     paired_end = tuple(a.paired_end) if a.paired_end else None
+    if (a.model_check_file or a.model_check_files) and paired_end:
+        ap.error("--model-check-file(s): the model check is single-end only (a paired-end read's class is compatibility x "
+                 "fragment length)")
+    if a.model_check_file and not a.compute_genes_from_file:
+        ap.error("--model-check-file goes with --compute-genes-from-file")
+    if a.model_check_files and not a.compare_genes_from_file:
+        ap.error("--model-check-files goes with --compare-genes-from-file")
     exact = bool(a.exact) or Settings.get_exact()       # the flag, or `exact = True` under [sampler] of the settings file
     if a.exact_paired and not paired_end:
         ap.error("--exact-paired goes with --paired-end")
@@ -637,7 +683,7 @@ def main(argv=None):
                                                    if a.delta_posterior_file else None),
                              exact_delta_file=(os.path.abspath(os.path.expanduser(a.exact_delta_file))
                                                if a.exact_delta_file else None),
-                             exact_stats_files=a.exact_stats_files)
+                             exact_stats_files=a.exact_stats_files, model_check_files=a.model_check_files)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -654,7 +700,7 @@ def main(argv=None):
                          write_files=not (a.no_miso_files and a.summary_file),
                          diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired,
                          rank_diagnostics=a.rank_diagnostics, exact_stats_file=a.exact_stats_file,
-                         exact_pairs_file=a.exact_pairs_file)
+                         exact_pairs_file=a.exact_pairs_file, model_check_file=a.model_check_file)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")
