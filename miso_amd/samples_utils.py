@@ -101,6 +101,13 @@ def _header_fields(header):
 
 
 def _parse_rows(body):
+    """The rows "psi_1,...,psi_K<TAB>log_score" as samples [S, K], parsed by numpy's C reader in one go.  Empty lines
+    are ignored and the last LF may be missing, as for the device decoder (include/miso_amd.h) and the reference's
+    load_samples; K comes from the first non-empty line."""
+    if body.startswith("\n") or "\n\n" in body:
+        body = "\n".join(ln for ln in body.split("\n") if ln)
+    if not body:
+        raise ValueError("no sample rows")
     first = body.split("\n", 1)[0]
     K = first.split("\t")[0].count(",") + 1
     flat = np.array(body.replace("\t", ",").replace("\n", ",").strip(",").split(","), dtype=np.float64)
@@ -109,18 +116,13 @@ def _parse_rows(body):
 
 
 def parse_miso_file(path):
-    """samples_utils.py:130-180 load_samples: (event name, samples [S, K], header dict).  The rows
-    "psi_1,...,psi_K<TAB>log_score" are parsed by numpy's C reader in one go."""
+    """samples_utils.py:130-180 load_samples: (event name, samples [S, K], header dict)."""
     with open(path) as f:
         header = f.readline().rstrip("\n")
         f.readline()                                      # sampled_psi<TAB>log_score
         body = f.read()
     fields = dict(kv.split("=", 1) for kv in header[1:].split("\t") if "=" in kv)
-    first = body.split("\n", 1)[0]
-    K = first.split("\t")[0].count(",") + 1
-    flat = np.array(body.replace("\t", ",").replace("\n", ",").strip(",").split(","), dtype=np.float64)
-    rows = flat.reshape(-1, K + 1)
-    return os.path.basename(path)[:-len(".miso")], np.ascontiguousarray(rows[:, :K]), fields
+    return os.path.basename(path)[:-len(".miso")], _parse_rows(body), fields
 
 
 def parse_miso_text(name, header, rows):
