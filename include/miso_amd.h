@@ -626,6 +626,34 @@ int miso_batch_compare_pairs_groups(miso_batch_t *const *group1, int n1, miso_ba
                                     double confidence_level, const double *tau, int n_tau, int as_text, uint64_t *out,
                                     int64_t out_len, int64_t *n_pairs, float *kernel_ms);
 
+/* Part-level psi: isoform-group columns (csrc/kernels_groups.hip).  A group is (group_event[g],
+   group_mask[g]): an event index of the batch and a set of that event's isoform indices, bit k = isoform k; the mask must be
+   non-empty and set no bit at or above the event's isoform count, and the event may have 64 isoforms at most.  The group's
+   draw of pool row s is v_s = ((0.0 + psi[s][k1]) + psi[s][k2]) + ... over the mask's k ascending, plain IEEE adds; with
+   as_text != 0 every member is first rounded to "%.4f" and read back as miso_batch_compare_pairs_as_text does it.  v_s + 0.0
+   is the column's value.  A NaN or an infinity among the v_s makes the group not finite (values of isoforms outside the mask
+   are never read).
+   miso_batch_summarize_isoform_groups: out[3 g ..] = mean, ci_low, ci_high of group g's column, by miso_batch_summarize's
+   rules: the mean as 256 strided partial sums folded in halves, over n_samples; the bounds the order statistics of the
+   strict ranks (too few samples: MISO_EINVAL).  Not finite: three NaN.
+   miso_batch_compare_pairs_isoform_groups: per group what miso_batch_compare_pairs defines for a column pair, a = the
+   group's column of sample1 (S1 draws), b = that of sample2 (S2 draws, S1 != S2 allowed), M = S1 * S2: out[(6 + n_tau) g ..]
+   = the bits of median, ci_low, ci_high; n_gt0; n_lt0; finite; n_abs_ge per threshold.  The batches as
+   miso_batch_compare_pairs requires them; an event either batch did not decode is not finite.  *n_pairs = M.
+   Both: n_samples <= 8192 per batch; n_groups = 0 is valid and launches nothing; a batch not yet synced is waited for;
+   *kernel_ms (may be NULL) the launches' time (a call is split over group ranges so that its result buffer stays within
+   256 MiB).  Nothing is stored in a batch.  MISO_EINVAL before any launch (the message names the group at fault);
+   MISO_ENODEVICE without a GPU.  The launches appear in miso_batch_last_kernels as summarize_groups and
+   compare_pairs_groups_iso. */
+int miso_batch_summarize_isoform_groups(miso_batch_t *batch, const int32_t *group_event, const uint64_t *group_mask,
+                                        int64_t n_groups, double confidence_level, int as_text,
+                                        double *out /* 3 per group */, int64_t out_len, float *kernel_ms);
+int miso_batch_compare_pairs_isoform_groups(miso_batch_t *sample1, miso_batch_t *sample2, const int32_t *group_event,
+                                            const uint64_t *group_mask, int64_t n_groups, double confidence_level,
+                                            const double *tau, int n_tau, int as_text,
+                                            uint64_t *out /* 6 + n_tau words per group */, int64_t out_len,
+                                            int64_t *n_pairs, float *kernel_ms);
+
 /* device_match batches: kernel time of the matching launch done by miso_batch_upload, and (tests:
    want_counts_trace batches only) the kernel's output for event i in the layout of
    miso_match_iso[_paired]: match noiso x n_reads, fragmentLength likewise or NULL. */

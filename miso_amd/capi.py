@@ -365,6 +365,20 @@ class Batch:
         check(lib().miso_batch_get_summary(self.handle, i, _p(m), _p(lo), _p(hi)))
         return m, lo, hi
 
+    def summarize_isoform_groups(self, groups, confidence_level=0.95, as_text=False):
+        """Mean and credible interval of isoform-group columns (miso_batch_summarize_isoform_groups): groups is
+        a sequence of (event index, mask), the mask a set of the event's isoform indices as an integer (bit k = isoform k);
+        a group's draw is the sum of its isoforms' psi, row by row of the sample pool.  Nothing is stored in the batch."""
+        ev, mask = _group_arrays(groups)
+        out = np.zeros((len(ev), 3))
+        ms = C.c_float(0.0)
+        L = lib()
+        L.miso_batch_summarize_isoform_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int,
+                                                          C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
+        check(L.miso_batch_summarize_isoform_groups(self.handle, _p(ev), _p(mask), len(ev), C.c_double(confidence_level),
+                                                    C.c_int(1 if as_text else 0), _p(out), out.size, C.byref(ms)))
+        return IsoformGroupSummary(out, float(ms.value))
+
     def exact_summary(self, i, confidence_level=0.95):
         """(mean[2], ci_low[2], ci_high[2]) of event i from the exact mode's grid -- no Monte-Carlo error -- after sync();
         None for an event that ran the sampler (miso_batch_get_exact_summary)."""
@@ -974,6 +988,73 @@ def compare_pairs_groups(batches1, batches2, confidence_level=0.95, thresholds=(
     check(L.miso_batch_compare_pairs_groups(h1, len(b1), h2, len(b2), C.c_double(confidence_level), _p(tt), C.c_int(len(tt)),
                                             C.c_int(1 if as_text else 0), _p(out), out.size, C.byref(M), C.byref(ms)))
     return GroupPairComparison(out, noiso, len(tt), int(M.value), float(ms.value))
+
+
+# ---- part-level psi: isoform-group columns (include/miso_amd.h miso_batch_summarize_isoform_groups) ----
+MAX_ISOFORM_GROUP_DRAWS = 8192      # csrc/compare_pairs.hpp PAIRS_MAX_DRAWS: the derived columns live sorted in LDS
+
+
+def _group_arrays(groups):
+    """(event index, mask) pairs as the two arrays the C ABI takes"""
+    gs = [(int(e), int(m)) for e, m in groups]
+    if any(not 0 <= m < 1 << 64 for _, m in gs):
+        raise ValueError("an isoform mask holds 64 bits")
+    return (np.asarray([e for e, _ in gs], dtype=np.int32).reshape(-1),
+            np.asarray([m for _, m in gs], dtype=np.uint64).reshape(-1))
+
+
+class IsoformGroupSummary:
+    """What Batch.summarize_isoform_groups computed: mean, ci_low, ci_high [n_groups] (three NaN for a group that is not
+    finite); summary(g) is one group's triple; `kernel_ms` the launches' time."""
+
+    def __init__(self, out, kernel_ms):
+        self.out = out
+        self.mean, self.ci_low, self.ci_high = out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+        self.kernel_ms = kernel_ms
+
+    def __len__(self):
+        return len(self.out)
+
+    def summary(self, g):
+        return float(self.mean[g]), float(self.ci_low[g]), float(self.ci_high[g])
+
+
+class IsoformGroupPairComparison:
+    """What compare_pairs_isoform_groups computed: pair_comparison(g) is group g's (median, ci_low, ci_high, n_gt0, n_lt0,
+    n_abs_ge[n_tau], finite, n_pairs), a probability being count / n_pairs; `kernel_ms` the launches' time."""
+
+    def __init__(self, out, n_tau, n_pairs, kernel_ms):
+        self.n_tau = n_tau
+        self.out = out.reshape(-1, PAIRS_FIXED_WORDS + n_tau)
+        self.n_pairs = n_pairs
+        self.kernel_ms = kernel_ms
+
+    def __len__(self):
+        return len(self.out)
+
+    def pair_comparison(self, g):
+        q = self.out[g]
+        d = np.ascontiguousarray(q[:3]).view(np.float64)
+        return (float(d[0]), float(d[1]), float(d[2]), int(q[3]), int(q[4]), [int(v) for v in q[PAIRS_FIXED_WORDS:]],
+                bool(q[5] != 0), self.n_pairs)
+
+
+def compare_pairs_isoform_groups(batch1, batch2, groups, confidence_level=0.95, thresholds=(0.1, 0.2), as_text=False):
+    """Batch.compare_pairs for isoform-group columns: per group (event index, mask) the median, credible interval and exact
+    counts of ALL differences between the group's draws in batch1 and in batch2.  The batches as
+    Batch.compare_pairs takes them.  Nothing is stored in a batch."""
+    ev, mask = _group_arrays(groups)
+    tt = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    out = np.zeros(len(ev) * (PAIRS_FIXED_WORDS + len(tt)), np.uint64)
+    ms, M = C.c_float(0.0), C.c_int64(0)
+    L = lib()
+    L.miso_batch_compare_pairs_isoform_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double,
+                                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                                          C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    check(L.miso_batch_compare_pairs_isoform_groups(batch1.handle, batch2.handle, _p(ev), _p(mask), len(ev),
+                                                    C.c_double(confidence_level), _p(tt), C.c_int(len(tt)),
+                                                    C.c_int(1 if as_text else 0), _p(out), out.size, C.byref(M), C.byref(ms)))
+    return IsoformGroupPairComparison(out, len(tt), int(M.value), float(ms.value))
 
 
 class ExactGroupDelta:

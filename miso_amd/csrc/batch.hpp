@@ -130,6 +130,13 @@ void compare_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2
 // kernels_compare_pairs_groups.hip
 void compare_pairs_groups(miso_batch *const *g1, int n1, miso_batch *const *g2, int n2, double confidence_level, const double *tau,
                           int n_tau, bool as_text, uint64_t *out, int64_t out_len, int64_t *n_pairs, float *kernel_ms);
+// kernels_groups.hip: isoform-group columns (miso_batch_summarize_isoform_groups, miso_batch_compare_pairs_isoform_groups;
+// DESIGN.md 23).  Group g is (group_event[g], group_mask[g]); out: 3 doubles, or pairs_words(n_tau) words, per group
+void summarize_isoform_groups(miso_batch &b, const int32_t *group_event, const uint64_t *group_mask, int64_t n_groups,
+                              double confidence_level, bool as_text, double *out, int64_t out_len, float *kernel_ms);
+void compare_pairs_isoform_groups(miso_batch &a, miso_batch &b, const int32_t *group_event, const uint64_t *group_mask,
+                                  int64_t n_groups, double confidence_level, const double *tau, int n_tau, bool as_text,
+                                  uint64_t *out, int64_t out_len, int64_t *n_pairs, float *kernel_ms);
 
 // A device table and what it was last filled from: its host contents, or the key of the plan it was built for.  reset()
 // frees the allocation and forgets both, so that neither outlives it (the next upload may be to another device).
@@ -475,6 +482,11 @@ struct miso_batch {
   // trial launch (fastest)
   bool trial_launch = false;
   void note_kernel(const std::string &name) { last_kernels += (last_kernels.empty() ? "" : ",") + name; }
+  // ... a pass over the launch's samples, named once however often it is called (a whole name: compare_pairs is not
+  // compare_pairs_groups_iso)
+  void note_pass(const std::string &name) {
+    if (("," + last_kernels + ",").find("," + name + ",") == std::string::npos) note_kernel(name);
+  }
   void launch_kernel(const miso::Kernel &k, unsigned grid, unsigned block, size_t lds, hipStream_t st, void **args);
   void launch_kernel(const miso::Kernel &k, unsigned grid, unsigned block, size_t lds, hipStream_t st, const miso::KernelArgs &ka);
   static miso::RunKernel run_kernel(const GenRun &run, int G, bool flat, bool dense_env, bool paired);

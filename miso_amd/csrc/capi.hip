@@ -1195,6 +1195,26 @@ int miso_batch_compare_pairs_groups(miso_batch_t *const *group1, int n1, miso_ba
   });
 }
 
+int miso_batch_summarize_isoform_groups(miso_batch_t *b, const int32_t *group_event, const uint64_t *group_mask, int64_t n_groups,
+                                        double confidence_level, int as_text, double *out, int64_t out_len, float *kernel_ms) {
+  return guarded([&] {
+    need(b, "batch");
+    summarize_isoform_groups(*b, group_event, group_mask, n_groups, confidence_level, as_text != 0, out, out_len, kernel_ms);
+  });
+}
+
+int miso_batch_compare_pairs_isoform_groups(miso_batch_t *s1, miso_batch_t *s2, const int32_t *group_event,
+                                            const uint64_t *group_mask, int64_t n_groups, double confidence_level,
+                                            const double *tau, int n_tau, int as_text, uint64_t *out, int64_t out_len,
+                                            int64_t *n_pairs, float *kernel_ms) {
+  return guarded([&] {
+    need(s1, "batch"); need(s2, "batch");
+    if (n_tau > 0) need(tau, "tau");
+    compare_pairs_isoform_groups(*s1, *s2, group_event, group_mask, n_groups, confidence_level, tau, n_tau, as_text != 0, out,
+                                 out_len, n_pairs, kernel_ms);
+  });
+}
+
 int miso_batch_last_match_ms(const miso_batch_t *b, float *ms) {
   return guarded([&] { need(b, "batch"); need(ms, "ms"); *ms = b->match_ms; });
 }

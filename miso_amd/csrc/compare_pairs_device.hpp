@@ -1,10 +1,14 @@
-// compare_pairs_device.hpp -- the device routines compare_pairs_kernel (kernels_compare_pairs.hip) and
-// compare_pairs_groups_kernel (kernels_compare_pairs_groups.hip) share: the sort of a column of order_keys in LDS and the
-// count of the differences at or below three thresholds.  One text, so that a group of one sample against a group of one
-// gives the pairwise pass's bits.  Workgroups of 256 threads.
+// compare_pairs_device.hpp -- the device routines compare_pairs_kernel (kernels_compare_pairs.hip),
+// compare_pairs_groups_kernel (kernels_compare_pairs_groups.hip) and the isoform-group kernels (kernels_groups.hip) share:
+// the sort of a column of order_keys in LDS, the count of the differences at or below three thresholds and, once both
+// columns stand sorted, the statistics themselves.  One text, so that a group of one sample against a group of one, and a
+// group of one isoform, give the pairwise pass's bits.  Workgroups of 256 threads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "compare_pairs.hpp"
+#include "order_key.hpp"
 
 namespace miso {
 
@@ -90,6 +94,86 @@ __device__ __forceinline__ void pairs_count(const double *A, int S1, const doubl
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < 3; q++) cnt[q] = part[0][q] + part[1][q] + part[2][q] + part[3][q];
+}
+
+// What an all-pairs kernel's workgroup holds beside its columns
+struct PairsScratch {
+  uint32_t part[2][4][3];
+  uint32_t cnt[2 + 2 * PAIRS_MAX_TAU];   // thread 0's: the threshold counts until it puts them together
+};
+
+// A column pair's statistics (compare_pairs.hpp: pairs_words(pa.n_tau) words at o) once A[0..S1) and B[0..S2) stand
+// ascending and published, A in LDS or global memory, B in LDS: the three order statistics by bisections over the keys of
+// [smallest difference, largest difference] that share their passes, then the threshold counts, three to a pass.  Every
+// barrier in workgroup-uniform control flow (the bisections' bounds are the same numbers in every thread).
+__device__ __forceinline__ void pairs_statistics(const double *A, int S1, const double *B, int S2, const PairsArgs &pa, uint64_t *o,
+                                                 PairsScratch &sc) {
+  const int t = threadIdx.x;
+  const uint32_t M = static_cast<uint32_t>(S1) * static_cast<uint32_t>(S2);   // <= 2^28
+  int buf = 0;
+
+  uint64_t lo_k[3], hi_k[3];
+  {
+    const uint64_t kmin = order_key(A[0] - B[S2 - 1]), kmax = order_key(A[S1 - 1] - B[0]);
+#pragma unroll
+    for (int q = 0; q < 3; q++) { lo_k[q] = kmin; hi_k[q] = kmax; }
+  }
+  const bool not_strict[3] = {false, false, false};
+  while (lo_k[0] < hi_k[0] || lo_k[1] < hi_k[1] || lo_k[2] < hi_k[2]) {
+    uint64_t mid[3];
+    double th[3];
+    uint32_t cnt[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) { mid[q] = lo_k[q] + ((hi_k[q] - lo_k[q]) >> 1); th[q] = key_value(mid[q]); }
+    pairs_count(A, S1, B, S2, th, not_strict, cnt, sc.part[buf]);
+    buf ^= 1;
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+      if (lo_k[q] < hi_k[q]) {
+        if (cnt[q] >= pa.rank[q] + 1u) hi_k[q] = mid[q]; else lo_k[q] = mid[q] + 1;
+      }
+  }
+
+  // the counts: query 0 is #{d <= 0}, 1 #{d < 0}, 2 + 2 j #{d < tau_j}, 3 + 2 j #{d <= -tau_j}; three to a pass
+  const int n_query = 2 + 2 * pa.n_tau;
+  for (int q0 = 0; q0 < n_query; q0 += 3) {
+    double th[3];
+    bool strict[3];
+    uint32_t cnt[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const int qi = q0 + q;
+      th[q] = 0.0; strict[q] = false;
+      if (qi == 1) strict[q] = true;
+      else if (qi >= 2 && qi < n_query) {
+        const double tau = pa.tau[(qi - 2) >> 1];
+        if (qi & 1) th[q] = -tau; else { th[q] = tau; strict[q] = true; }
+      }
+    }
+    pairs_count(A, S1, B, S2, th, strict, cnt, sc.part[buf]);
+    buf ^= 1;
+    if (t == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; q++)
+        if (q0 + q < n_query) sc.cnt[q0 + q] = cnt[q];
+    }
+  }
+  if (t == 0) {
+    // (+ 0.0: the smallest key whose count suffices is -0.0's when the order statistic is zero)
+#pragma unroll
+    for (int q = 0; q < 3; q++) o[q] = static_cast<uint64_t>(__double_as_longlong(key_value(lo_k[q]) + 0.0));
+    o[3] = M - sc.cnt[0];
+    o[4] = sc.cnt[1];
+    o[5] = 1;
+    for (int j = 0; j < pa.n_tau; j++) o[PAIRS_FIXED_WORDS + j] = static_cast<uint64_t>(M - sc.cnt[2 + 2 * j]) + sc.cnt[3 + 2 * j];
+  }
+}
+
+// ... and of a pair that is not finite, or whose event was never decoded: three NaN, no counts, finite = 0
+__device__ __forceinline__ void pairs_not_finite(uint64_t *o, int n_tau) {
+  const uint64_t nan = 0x7FF8000000000000ull;
+  o[0] = nan; o[1] = nan; o[2] = nan;
+  for (int w = 3; w < PAIRS_FIXED_WORDS + n_tau; w++) o[w] = 0;
 }
 
 }  // namespace miso

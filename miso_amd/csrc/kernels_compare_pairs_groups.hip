@@ -64,8 +64,7 @@ __global__ __launch_bounds__(256) void compare_pairs_groups_kernel(const DevEven
                                                                    PairsArgs pa, int as_text, const uint64_t *col_off,
                                                                    uint64_t *out, double *work) {
   extern __shared__ uint64_t pairs_lds[];
-  __shared__ uint32_t s_part[2][4][3];
-  __shared__ uint32_t s_cnt[2 + 2 * PAIRS_MAX_TAU];   // thread 0's: the threshold counts until it puts them together
+  __shared__ PairsScratch sc;
   const int kk = blockIdx.y, t = threadIdx.x;
   if (static_cast<int>(blockIdx.x) >= n_events) return;
   const int ev = ev0 + static_cast<int>(blockIdx.x);
@@ -87,11 +86,7 @@ __global__ __launch_bounds__(256) void compare_pairs_groups_kernel(const DevEven
     bad = __syncthreads_or(pairs_gather(evs + n1, pools + n1, n2, ev, kk, K, S, as_text, pairs_lds)) != 0;
   }
   if (bad) {
-    if (t == 0) {
-      const uint64_t nan = 0x7FF8000000000000ull;
-      o[0] = nan; o[1] = nan; o[2] = nan;
-      for (int w = 3; w < W; w++) o[w] = 0;
-    }
+    if (t == 0) pairs_not_finite(o, pa.n_tau);
     return;
   }
   pairs_sort(pairs_lds, N2);
@@ -99,65 +94,7 @@ __global__ __launch_bounds__(256) void compare_pairs_groups_kernel(const DevEven
   for (int e = t; e < N2; e += 256) B[e] = key_value(pairs_lds[e]);   // (each thread its own words, in place)
   __syncthreads();
 
-  const uint32_t M = static_cast<uint32_t>(N1) * static_cast<uint32_t>(N2);   // <= 2^28
-  int buf = 0;
-
-  // the three order statistics: bisections over the keys of [smallest difference, largest difference]
-  uint64_t lo_k[3], hi_k[3];
-  {
-    const uint64_t kmin = order_key(A[0] - B[N2 - 1]), kmax_d = order_key(A[N1 - 1] - B[0]);
-#pragma unroll
-    for (int q = 0; q < 3; q++) { lo_k[q] = kmin; hi_k[q] = kmax_d; }
-  }
-  const bool not_strict[3] = {false, false, false};
-  while (lo_k[0] < hi_k[0] || lo_k[1] < hi_k[1] || lo_k[2] < hi_k[2]) {
-    uint64_t mid[3];
-    double th[3];
-    uint32_t cnt[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) { mid[q] = lo_k[q] + ((hi_k[q] - lo_k[q]) >> 1); th[q] = key_value(mid[q]); }
-    pairs_count(A, N1, B, N2, th, not_strict, cnt, s_part[buf]);
-    buf ^= 1;
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-      if (lo_k[q] < hi_k[q]) {
-        if (cnt[q] >= pa.rank[q] + 1u) hi_k[q] = mid[q]; else lo_k[q] = mid[q] + 1;
-      }
-  }
-
-  // the counts: query 0 is #{d <= 0}, 1 #{d < 0}, 2 + 2 j #{d < tau_j}, 3 + 2 j #{d <= -tau_j}; three to a pass
-  const int n_query = 2 + 2 * pa.n_tau;
-  for (int q0 = 0; q0 < n_query; q0 += 3) {
-    double th[3];
-    bool strict[3];
-    uint32_t cnt[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      const int qi = q0 + q;
-      th[q] = 0.0; strict[q] = false;
-      if (qi == 1) strict[q] = true;
-      else if (qi >= 2 && qi < n_query) {
-        const double tau = pa.tau[(qi - 2) >> 1];
-        if (qi & 1) th[q] = -tau; else { th[q] = tau; strict[q] = true; }
-      }
-    }
-    pairs_count(A, N1, B, N2, th, strict, cnt, s_part[buf]);
-    buf ^= 1;
-    if (t == 0) {
-#pragma unroll
-      for (int q = 0; q < 3; q++)
-        if (q0 + q < n_query) s_cnt[q0 + q] = cnt[q];
-    }
-  }
-  if (t == 0) {
-    // (+ 0.0: the smallest key whose count suffices is -0.0's when the order statistic is zero)
-#pragma unroll
-    for (int q = 0; q < 3; q++) o[q] = static_cast<uint64_t>(__double_as_longlong(key_value(lo_k[q]) + 0.0));
-    o[3] = M - s_cnt[0];
-    o[4] = s_cnt[1];
-    o[5] = 1;
-    for (int j = 0; j < pa.n_tau; j++) o[PAIRS_FIXED_WORDS + j] = static_cast<uint64_t>(M - s_cnt[2 + 2 * j]) + s_cnt[3 + 2 * j];
-  }
+  pairs_statistics(A, N1, B, N2, pa, o, sc);
 }
 
 // The workspace of one launch, bytes at most: a launch covers as many events as fit (one at least), so what a call holds

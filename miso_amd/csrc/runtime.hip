@@ -1541,7 +1541,7 @@ void miso_batch::compare_pairs(miso_batch &other, double confidence_level, const
                        hipLaunchKernelGGL(compare_pairs_kernel, grid, dim3(256), dyn, call.st, d_events, d_out, S1, other.d_events,
                                           other.d_out, S2, n, pa, as_text ? 1 : 0, d_off, d_res);
                      });
-    if (last_kernels.find("compare_pairs") == std::string::npos) note_kernel("compare_pairs");   // (once, however often it is called)
+    note_pass("compare_pairs");
   }
   h_pairs.swap(res);
   h_pairs_off.swap(l.off);

@@ -135,7 +135,10 @@ class GenesDispatcher(object):
                  labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                  exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
                  delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False,
-                 model_check=False):
+                 model_check=False, part_psi=False):
+        # --part-psi: beside the outputs the `.miso_part_summary` table (part_psi.py) of every directory of `.miso` files and,
+        # with --compare, `<l1>_vs_<l2>.miso_part_dpsi` beside the `.miso_bf`; merged like a diagnostics table, then sorted
+        self.part_psi = bool(part_psi)
         # --model-check: beside the outputs the `.miso_fit` table (model_check.py) of every directory of `.miso` files, merged
         # like a diagnostics table; single-end only
         self.model_check = bool(model_check)
@@ -314,6 +317,15 @@ class GenesDispatcher(object):
                 label = os.path.basename(os.path.normpath(d))
                 ftables.append((os.path.join(d, "summary", label + ".miso_fit"), []))
                 os.makedirs(os.path.dirname(ftables[-1][0]), exist_ok=True)
+        qtables = []                   # --part-psi: [(table, its per-worker parts)]: one per directory, then the comparison's
+        if self.part_psi:
+            for d in ([self.output_dir] if self.compare_bam is None else [out1, out2]):
+                label = os.path.basename(os.path.normpath(d))
+                qtables.append((os.path.join(d, "summary", label + ".miso_part_summary"), []))
+                os.makedirs(os.path.dirname(qtables[-1][0]), exist_ok=True)
+            if self.compare_bam is not None:
+                qtables.append((table[:-len(".miso_bf")] + ".miso_part_dpsi", []))
+        self.part_tables = [t for t, _ in qtables]
         if self.exact_paired_stats:    # --exact-paired-stats: (the `.miso_exact_pairs` table, its per-worker parts); no --compare
             label = os.path.basename(os.path.normpath(self.output_dir))
             ptable = (os.path.join(self.output_dir, "summary", label + ".miso_exact_pairs"), [])
@@ -359,6 +371,13 @@ class GenesDispatcher(object):
                     for (_, plist), fp in zip(ftables, fparts):
                         plist.append(fp)
                     cmd += ["--model-check-files"] + fparts
+                if qtables:
+                    qparts = ["%s.gpu%d" % (t, batch_num) for t, _ in qtables]
+                    for (_, plist), qp in zip(qtables, qparts):
+                        plist.append(qp)
+                    cmd += ["--part-psi-files"] + qparts
+                    if self.delta_thresholds is not None and not (self.exact_compare or self.delta_posterior):
+                        cmd += ["--delta-psi-thresholds"] + ["%r" % t for t in self.delta_thresholds]
             else:
                 cmd = [sys.executable, "-m", "miso_amd.run_miso", "--compute-genes-from-file", fname,
                        self.bam_filename, self.output_dir]
@@ -375,6 +394,9 @@ class GenesDispatcher(object):
                 if ftables:
                     ftables[0][1].append("%s.gpu%d" % (ftables[0][0], batch_num))
                     cmd += ["--model-check-file", ftables[0][1][-1]]
+                if qtables:
+                    qtables[0][1].append("%s.gpu%d" % (qtables[0][0], batch_num))
+                    cmd += ["--part-psi-file", qtables[0][1][-1]]
                 if self.exact_paired_stats:
                     ptable[1].append("%s.gpu%d" % (ptable[0], batch_num))
                     cmd += ["--exact-pairs-file", ptable[1][-1]]
@@ -400,7 +422,7 @@ class GenesDispatcher(object):
                                % (batch_num, time.strftime("%m-%d-%y_%H:%M:%S")))
             print("Running batch of %d genes on GPU %d.." % (size, batch_num % self.n_gpus))
             jobs.append((batch_num, cmd, log))
-        self.diag_tables += xtable + dtable + etable + stables + ftables + ([ptable] if self.exact_paired_stats else [])
+        self.diag_tables += xtable + dtable + etable + stables + ftables + qtables + ([ptable] if self.exact_paired_stats else [])
         # One decode per node: this process reads the alignment file(s) ONCE through the HIP-free reader
         # library and forks the workers, which inherit the decoded columns (copy-on-write, nothing copied);
         # each worker then initialises its own GPU.  The reference re-opens the BAM per event through an
@@ -464,6 +486,9 @@ class GenesDispatcher(object):
         for diag_table, diag_parts in self.diag_tables:
             from .run_miso import merge_tables
             merge_tables(diag_parts, diag_table)
+            if diag_table in getattr(self, "part_tables", ()):      # one order whatever the workers and launches were
+                from . import part_psi
+                part_psi.sort_table(diag_table)
             print("Wrote %s" % diag_table)
         return failed
 
@@ -474,7 +499,7 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                           labels=("sample1", "sample2"), summary_only=False, prefilter=False, diagnostics=False, exact=False,
                           exact_compare=False, delta_thresholds=None, exact_paired=False, rank_diagnostics=False,
                           delta_posterior=False, exact_delta_posterior=False, exact_stats=False, exact_paired_stats=False,
-                          model_check=False):
+                          model_check=False, part_psi=False):
     """miso.py:340-420."""
     print("Computing Psi values...")
     print("  - GFF index: %s" % gff_dir)
@@ -489,7 +514,8 @@ def compute_all_genes_psi(gff_dir, bam_filename, read_len, output_dir, overhang_
                            prefilter=prefilter, diagnostics=diagnostics, exact=exact, exact_compare=exact_compare, exact_paired=exact_paired,
                            delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
                            delta_posterior=delta_posterior, exact_delta_posterior=exact_delta_posterior,
-                           exact_stats=exact_stats, exact_paired_stats=exact_paired_stats, model_check=model_check).run()
+                           exact_stats=exact_stats, exact_paired_stats=exact_paired_stats, model_check=model_check,
+                           part_psi=part_psi).run()
 
 
 def main(argv=None):
@@ -525,6 +551,12 @@ def main(argv=None):
                          ".miso_diag goes): per event a posterior predictive check of its reads against the read classes the "
                          "model expects -- a p-value, observed and expected reads per class and which class is short or in "
                          "excess --, computed on the GPU during the run with the run's seed; every other output is unchanged")
+    ap.add_argument("--part-psi", action="store_true",
+                    help="also write OUT/summary/<OUT>.miso_part_summary: per part (exon) of every multi-isoform event how often "
+                         "it is included -- the sum of the psi of the isoforms that hold it --, posterior mean and credible "
+                         "interval from the joint draws, computed on the GPU during the run; with --compare one table per label "
+                         "and <l1>_vs_<l2>.miso_part_dpsi beside the .miso_bf: each exon's delta psi over all pairs of the two "
+                         "samples' draws (thresholds: --delta-psi-thresholds, default 0.1 0.2); every other output is unchanged")
     ap.add_argument("--exact", action="store_true",
                     help="single-end two-isoform events (SE, A3SS, A5SS, RI, MXE): no chains -- the posterior of Psi is tabulated "
                          "once per event on the GPU and the .miso file's samples are independent draws from it (percent_accept=100); "
@@ -583,6 +615,12 @@ def main(argv=None):
         ap.error("--exact-paired goes with --paired-end")
     if a.model_check and a.paired_end is not None:
         ap.error("--model-check is single-end only: a paired-end read's class is compatibility x fragment length")
+    if a.part_psi:
+        from . import part_psi
+        p = Settings.get_sampler_params()
+        why = part_psi.samples_refusal(p["num_chains"] * (p["num_iters"] - p["burn_in"]) // p["lag"])
+        if why:
+            ap.error("--part-psi: %s" % why)
     if a.rank_diagnostics and not a.diagnostics:
         ap.error("--rank-diagnostics goes with --diagnostics")
     if a.exact_stats and (a.paired_end or not (a.exact or Settings.get_exact())):
@@ -613,7 +651,7 @@ def main(argv=None):
     if a.exact_delta_posterior and not (a.exact_compare or a.exact_paired_compare):
         ap.error("--exact-delta-posterior goes with --exact-compare or --exact-paired-compare")
     if a.delta_psi_thresholds is not None:
-        if not (a.exact_compare or a.exact_paired_compare or a.delta_posterior):
+        if not (a.exact_compare or a.exact_paired_compare or a.delta_posterior or (a.part_psi and a.compare is not None)):
             ap.error("--delta-psi-thresholds goes with --exact-compare or --delta-posterior")
         from . import compare
         try:
@@ -645,7 +683,7 @@ def main(argv=None):
                                        delta_thresholds=a.delta_psi_thresholds, rank_diagnostics=a.rank_diagnostics,
                                        delta_posterior=a.delta_posterior, exact_delta_posterior=a.exact_delta_posterior,
                                        exact_stats=a.exact_stats, exact_paired_stats=a.exact_paired_stats,
-                                       model_check=a.model_check)
+                                       model_check=a.model_check, part_psi=a.part_psi)
     except PrefilterError as err:
         print("Error: %s" % err)
         return 1

@@ -167,7 +167,7 @@ class MISOSampler:
                           start_cond=pysplicing.MISO_START_AUTO,
                           stop_cond=pysplicing.MISO_STOP_FIXEDNO, seed=None, first_event_id=0,
                           verbose=False, summary_file=None, confidence_level=0.95, threads=0, diagnostics_file=None,
-                          rank_diagnostics=False, exact_stats_file=None, model_fit_file=None):
+                          rank_diagnostics=False, exact_stats_file=None, model_fit_file=None, part_psi_file=None):
         """events: list of (reads, gene, output_file[, prior_params[, event_id]]); `reads` is the
         reference's (positions 0-based, cigars) pair or an AlnRegion; event_id pins the event's
         random stream (default: first_event_id + its position among the events actually sampled).  Same per-event skip rules as run_sampler
@@ -178,7 +178,7 @@ class MISOSampler:
         summary_file: also write the `summarize_miso` table (samples_utils.py:263-329) for the
         events of this batch, from means / credible intervals computed on the device.
         diagnostics_file: also write the chain diagnostics table (diagnostics.py) of these events; rank_diagnostics: with
-        the six columns of the rank-normalised pass.  exact_stats_file: output_batch's.
+        the six columns of the rank-normalised pass.  exact_stats_file, part_psi_file: output_batch's.
         = prepare_batch (host: skip rules, reads into the batch) + finish_batch (GPU + files); a caller
         with several batches can overlap one's finish with the next one's prepare (run_miso.py)."""
         state = self.prepare_batch(num_iters, events, num_chains=num_chains, burn_in=burn_in, lag=lag,
@@ -186,7 +186,7 @@ class MISOSampler:
         return self.finish_batch(state, seed=seed, first_event_id=first_event_id, verbose=verbose,
                                  summary_file=summary_file, confidence_level=confidence_level,
                                  threads=threads, diagnostics_file=diagnostics_file, rank_diagnostics=rank_diagnostics,
-                                 exact_stats_file=exact_stats_file, model_fit_file=model_fit_file)
+                                 exact_stats_file=exact_stats_file, model_fit_file=model_fit_file, part_psi_file=part_psi_file)
 
     def exact_paired(self):
         """the paired-end exact-posterior mode is asked for: params["exact_paired"], else MISO_EXACT_PAIRED=1; never on a
@@ -332,7 +332,7 @@ class MISOSampler:
 
     def finish_batch(self, state, seed=None, first_event_id=0, verbose=False, summary_file=None,
                      confidence_level=0.95, threads=0, write_files=True, diagnostics_file=None, rank_diagnostics=False,
-                     exact_stats_file=None, model_fit_file=None):
+                     exact_stats_file=None, model_fit_file=None, part_psi_file=None):
         """Launch, then the event's outputs.  write_files=False (with a summary_file): no per-event `.miso` file --
         the posterior means and credible intervals that `summarize_miso` would compute from those files
         (samples_utils.py:263-329) come from the device, summarised from the four-decimal text the file WOULD hold.
@@ -341,7 +341,8 @@ class MISOSampler:
         self.launch_batch(state, seed=seed, first_event_id=first_event_id)
         return self.output_batch(state, verbose=verbose, summary_file=summary_file, confidence_level=confidence_level,
                                  threads=threads, write_files=write_files, diagnostics_file=diagnostics_file,
-                                 rank_diagnostics=rank_diagnostics, exact_stats_file=exact_stats_file, model_fit_file=model_fit_file)
+                                 rank_diagnostics=rank_diagnostics, exact_stats_file=exact_stats_file, model_fit_file=model_fit_file,
+                                 part_psi_file=part_psi_file)
 
     def launch_batch(self, state, seed=None, first_event_id=0):
         """Upload, sample, download (native code, the interpreter lock released throughout)."""
@@ -372,7 +373,7 @@ class MISOSampler:
 
     def output_batch(self, state, verbose=False, summary_file=None, confidence_level=0.95, threads=0,
                      write_files=True, diagnostics_file=None, rank_diagnostics=False, exact_stats_file=None,
-                     exact_pairs_file=None, model_fit_file=None):
+                     exact_pairs_file=None, model_fit_file=None, part_psi_file=None):
         """The `.miso` files and / or the summary table of a launched batch.  The header's run-dependent fields are
         formatted natively for the whole batch (miso_batch_header_fields); miso_header() below is the same line field
         by field in Python (the one-event path; tests/test_gpu_frontend.py compares the files byte for byte).
@@ -385,10 +386,17 @@ class MISOSampler:
         paired exact mode: the six statistics and the drawing pairs' probabilities (Batch.exact_paired_element).
         model_fit_file (a batch prepared with params["model_check"]): the `.miso_fit` table of the written events
         (model_check.write_model_fit), from the samples resident on the device, drawn with the run's seed; the pass only
+        reads, nothing else changes with it.
+        part_psi_file: the `.miso_part_summary` table of the written events (miso_amd/part_psi.py), the inclusion of every
+        part of a multi-isoform gene from the samples resident on the device, as the `.miso` files print them; the pass only
         reads, nothing else changes with it."""
         batch, slots, written, num_iters, burn_in, lag = state
         stat_rows, pair_rows, fit_rows = [], [], []
+        if part_psi_file is not None:
+            from miso_amd import part_psi
         if not slots:
+            if part_psi_file is not None:
+                part_psi.write_part_summary(part_psi_file, [])
             if model_fit_file is not None:
                 model_check.write_model_fit(model_fit_file, fit_rows)
             if exact_stats_file is not None:
@@ -425,11 +433,15 @@ class MISOSampler:
         if model_fit_file is not None:
             batch.model_check(batch.run_seed)
             fits = batch.model_fit_many([idx for _, idx, _, _ in slots])
+        if part_psi_file is not None:     # the written events, by batch index
+            part_names, part_genes = [None] * len(batch), [None] * len(batch)
         for j, ((i, idx, gene, out), (unassigned, pa, counts, assigned)) in enumerate(zip(slots, fields)):
             if unassigned:                                                # miso_sampler.py:352-354
                 if verbose:
                     print("All reads incompatible with annotation, skipping...")
                 continue
+            if part_psi_file is not None:
+                part_names[idx], part_genes[idx] = os.path.basename(out)[:-len(".miso")], gene
             head, tail = self._static_header(gene)
             header = "%s%s%s\tproposal_type=drift\tcounts=%s\tassigned_counts=%s\t%s" % (head, middle, pa, counts, assigned, tail)
             if write_files:
@@ -469,6 +481,9 @@ class MISOSampler:
             compare.write_exact_pairs(exact_pairs_file, pair_rows)
         if model_fit_file is not None:
             model_check.write_model_fit(model_fit_file, fit_rows)
+        if part_psi_file is not None:
+            part_psi.write_part_summary(part_psi_file, part_psi.summary_rows(batch, part_names, part_genes, confidence_level,
+                                                                             as_text=True))
         if timing:
             print("[miso] batch of %d events: headers %.2f s, .miso files / table %.2f s"
                   % (len(slots), t2 - t1, time.time() - t2))
@@ -480,7 +495,7 @@ class MISOSampler:
                              confidence_level=0.95, smoothing=0.3, verbose=False, event_ids=None,
                              diagnostics_files=None, exact_comparison_file=None, delta_thresholds=None,
                              rank_diagnostics=False, delta_posterior_file=None, exact_delta_file=None,
-                             exact_stats_files=None, model_fit_files=None):
+                             exact_stats_files=None, model_fit_files=None, part_psi_files=None):
         """events1[i] and events2[i] = (reads, gene, output_file[, prior_params]) describe the SAME
         event in sample 1 and sample 2.  Samples both on the GPU, writes every .miso file and the
         `.miso_bf` table of hypothesis_test.py:186-345 with Bayes factors computed on the device.
@@ -504,7 +519,12 @@ class MISOSampler:
         exact_stats_files (optional; the single-end exact mode only): (file1, file2), each sample's `.miso_exact_stats` table
         (compare.write_exact_stats) of its written events (MISOCompareBatch(exact_stats=)).
         model_fit_files (optional; single-end only): (file1, file2), each sample's `.miso_fit` table (model_check.py) of its
-        written events, each drawn with its sample's seed (MISOCompareBatch(model_check=))."""
+        written events, each drawn with its sample's seed (MISOCompareBatch(model_check=)).
+        part_psi_files (optional; any mode): (file1, file2, file_d): each sample's `.miso_part_summary` table of its written
+        events and the `.miso_part_dpsi` table of the events written in both (miso_amd/part_psi.py), with delta_thresholds.
+        The draws the call returns go back to the device as adopted samples and the isoform-group passes run on them as the
+        `.miso` files print them, so the tables are those of the files."""
+        part_samples = ([], [])          # per sample: (name, gene, samples [S, K]) of its written events
         if model_fit_files is not None and self.paired_end:
             raise ValueError("the model check takes single-end events only")
         fit_rows = ([], [])
@@ -606,6 +626,10 @@ class MISOSampler:
                         if f is not None:
                             was, st = sres[which][j]
                             stat_rows[which].append((os.path.basename(f)[:-len(".miso")], was, st))
+                if part_psi_files is not None:
+                    for which, (f, r) in enumerate(((f1, a), (f2, b))):
+                        if f is not None:
+                            part_samples[which].append((os.path.basename(f)[:-len(".miso")], gene, np.transpose(np.array(r[0]))))
                 if f1 is not None and f2 is not None:
                     name = os.path.basename(f1)[:-len(".miso")]
                     rows.append((name, a[6], b[6], c[2], read_header(f1), read_header(f2)))
@@ -631,7 +655,33 @@ class MISOSampler:
         if model_fit_files is not None:
             for f, frows in zip(model_fit_files, fit_rows):
                 model_check.write_model_fit(f, frows)
+        if part_psi_files is not None:
+            self._write_part_tables(part_psi_files, part_samples, confidence_level, delta_thresholds)
         return written
+
+    @staticmethod
+    def _write_part_tables(part_psi_files, part_samples, confidence_level, delta_thresholds):
+        """run_comparison_batch's part-level tables from each sample's (name, gene, samples) of its written events"""
+        from miso_amd import part_psi
+        device = int(os.environ.get("MISO_DEVICE", 0) or 0)
+        thr = compare.check_delta_thresholds(compare.DEFAULT_DELTA_THRESHOLDS if delta_thresholds is None else delta_thresholds)
+
+        def adopted(evs):
+            return capi.SamplesBatch([e[2] for e in evs], device=device) if evs else None
+        batches = [adopted(evs) for evs in part_samples]
+        for f, evs, b in zip(part_psi_files[:2], part_samples, batches):
+            rows = part_psi.summary_rows(b, [e[0] for e in evs], [e[1] for e in evs], confidence_level, as_text=True) if evs else []
+            part_psi.write_part_summary(f, rows)
+        in2 = {e[0] for e in part_samples[1]}
+        both = [e[0] for e in part_samples[0] if e[0] in in2]
+        drows = []
+        if both:
+            pair = batches
+            if not (len(both) == len(part_samples[0]) == len(part_samples[1])):     # (an event one sample did not write)
+                pair = [adopted([e for e in evs if e[0] in set(both)]) for evs in part_samples]
+            genes = [e[1] for e in part_samples[0] if e[0] in set(both)]
+            drows = part_psi.dpsi_rows(pair[0], pair[1], both, genes, confidence_level, thr, as_text=True)
+        part_psi.write_part_dpsi(part_psi_files[2], drows, thr)
 
     # -- shared pieces -------------------------------------------------------------------------
     def _prepare(self, reads, gene, output_file, prior_params, verbose):

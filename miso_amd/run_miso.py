@@ -148,7 +148,7 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
                      seed=None, first_event_id=0, device=None, gene_entries=None,
                      max_events_per_launch=8192, summary_file=None, write_files=True, event_ids=None,
                      diagnostics_file=None, exact=None, exact_paired=None, rank_diagnostics=False, exact_stats_file=None,
-                     exact_pairs_file=None, model_check_file=None):
+                     exact_pairs_file=None, model_check_file=None, part_psi_file=None):
     """run_miso.py:34-206.  `gene_entries` (list of (gene_id, index file)) generalises the
     reference's (gene_ids, one index file) so a whole batch file is one GPU batch.  event_ids[k] (optional): entry k's
     number in the random-number counter (default first_event_id + k).  diagnostics_file: also write the chain
@@ -163,10 +163,14 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     (compare.write_exact_pairs), parts merged the same way.
     model_check_file (single-end only): also write the `.miso_fit` table of this run, the posterior predictive model check
     of every written event (model_check.py), per launch from the resident samples with the run's seed, parts merged the
-    same way; nothing else changes with it."""
+    same way; nothing else changes with it.
+    part_psi_file: also write the `.miso_part_summary` table of this run, the inclusion of every part of the written
+    multi-isoform events (part_psi.py), per launch from the resident samples, parts merged the same way; nothing else changes
+    with it."""
     if model_check_file is not None and paired_end:
         raise ValueError("the model check takes single-end events only")
     fit_parts = []
+    part_parts = []
     exact = Settings.get_exact() if exact is None else bool(exact)
     if exact_stats_file is not None and (paired_end or not exact):
         raise ValueError("the exact statistics table needs the exact-posterior mode (single-end)")
@@ -186,6 +190,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     settings_params = Settings.get_sampler_params()
     burn_in, lag = settings_params["burn_in"], settings_params["lag"]
     num_iters, num_chains = settings_params["num_iters"], settings_params["num_chains"]
+    if part_psi_file is not None:
+        _check_part_psi(settings_params)
     if device is not None:
         _check_device(device)
         os.environ["MISO_DEVICE"] = str(int(device))               # read by pysplicing per launch
@@ -298,14 +304,17 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
             fpart = None if model_check_file is None else "%s.part%06d" % (model_check_file, lo)
             if fpart:
                 fit_parts.append(fpart)
+            qpart = None if part_psi_file is None else "%s.part%06d" % (part_psi_file, lo)
+            if qpart:
+                part_parts.append(qpart)
             launched = gpu.submit(sampler.launch_batch, state, seed=seed, first_event_id=first_event_id + lo)
 
             def outputs(sampler=sampler, state=state, launched=launched, part=part, dpart=dpart, spart=spart, ppart=ppart,
-                        fpart=fpart):
+                        fpart=fpart, qpart=qpart):
                 launched.result()
                 return sampler.output_batch(state, verbose=verbose, summary_file=part, write_files=write_files,
                                             diagnostics_file=dpart, rank_diagnostics=rank_diagnostics, exact_stats_file=spart,
-                                            exact_pairs_file=ppart, model_fit_file=fpart)
+                                            exact_pairs_file=ppart, model_fit_file=fpart, part_psi_file=qpart)
             in_flight.append(out.submit(outputs))
         for f in in_flight:
             written += f.result()
@@ -322,6 +331,8 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
         merge_tables(pair_parts, exact_pairs_file)
     if model_check_file is not None:
         merge_tables(fit_parts, model_check_file)
+    if part_psi_file is not None:
+        _merge_part_tables(part_parts, part_psi_file)
     t2 = time.time()
     if verbose:
         print("Collected %d events in %.2f s (beside the decoding / sampling), batches prepared in %.2f s, whole run %.2f s"
@@ -329,6 +340,20 @@ def compute_gene_psi(gene_ids, gff_index_filename, bam_filename, output_dir, rea
     if own:
         bamfile.close()
     return written, info
+
+
+def _merge_part_tables(parts, filename):
+    """merge_tables for a part-level table (part_psi.py), then the one order such a table has: by event name"""
+    from . import part_psi
+    return part_psi.sort_table(merge_tables(parts, filename))
+
+
+def _check_part_psi(p):
+    """The sampler settings' samples per event must suit the isoform-group passes: refused before anything is sampled"""
+    from . import part_psi
+    why = part_psi.samples_refusal(p["num_chains"] * (p["num_iters"] - p["burn_in"]) // p["lag"])
+    if why:
+        raise ValueError(why)
 
 
 def _event_number(k, first_event_id, event_ids):
@@ -361,7 +386,8 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                      verbose=True, seed=None, first_event_id=0, device=None,
                      max_events_per_launch=4096, event_ids=None, samples=None, diagnostics_files=None, exact=None,
                      exact_comparison_file=None, delta_thresholds=None, exact_paired=None, rank_diagnostics=False,
-                     delta_posterior_file=None, exact_delta_file=None, exact_stats_files=None, model_check_files=None):
+                     delta_posterior_file=None, exact_delta_file=None, exact_stats_files=None, model_check_files=None,
+                     part_psi_files=None):
     """Two RNA-seq samples over the same genes in one go (BASELINE configs[4]): both samples are
     sampled on this GPU, their `.miso` files written like two `miso --run`s would, and the
     `.miso_bf` table of `compare_miso` (hypothesis_test.py:186-345) comes from Bayes factors
@@ -380,7 +406,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     exact_stats_files (the single-end exact mode only): (file1, file2), each sample's `.miso_exact_stats` table
     (compare.py write_exact_stats), parts merged like the diagnostics tables'.
     model_check_files (single-end only): (file1, file2), each sample's `.miso_fit` table (model_check.py), each drawn with its
-    sample's seed, parts merged like the diagnostics tables'."""
+    sample's seed, parts merged like the diagnostics tables'.
+    part_psi_files (any mode): (file1, file2, file_d), each sample's `.miso_part_summary` table and the `.miso_part_dpsi` table
+    of the compared events (part_psi.py), with the same delta_thresholds; parts merged, then in event-name order."""
     if exact_delta_file is not None and exact_comparison_file is None:
         raise ValueError("the exact delta psi table goes with the exact comparison")
     for d in (output_dir1, output_dir2):
@@ -400,7 +428,10 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     if model_check_files is not None and paired_end:
         raise ValueError("the model check takes single-end events only")
     fit_parts = ([], [])
+    part_parts = ([], [], [])
     p = Settings.get_sampler_params()
+    if part_psi_files is not None:
+        _check_part_psi(p)
     bam1, bam2 = sam_utils.load_bam_reads(bam1_filename), sam_utils.load_bam_reads(bam2_filename)
     evs = []
     for which, bam, out in (("1", bam1, output_dir1), ("2", bam2, output_dir2)):
@@ -450,6 +481,11 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             sparts = tuple("%s.part%06d" % (f, lo) for f in exact_stats_files)
             for which in (0, 1):
                 stat_parts[which].append(sparts[which])
+        qparts = None
+        if part_psi_files is not None:
+            qparts = tuple("%s.part%06d" % (f, lo) for f in part_psi_files)
+            for which in (0, 1, 2):
+                part_parts[which].append(qparts[which])
         xpart = None
         if exact_comparison_file is not None:
             xpart = "%s.part%06d" % (exact_comparison_file, lo)
@@ -470,7 +506,7 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
                                      diagnostics_files=dparts, exact_comparison_file=xpart,
                                      delta_thresholds=delta_thresholds, rank_diagnostics=rank_diagnostics,
                                      delta_posterior_file=dpsi_part, exact_delta_file=epart, exact_stats_files=sparts,
-                                     model_fit_files=fparts)
+                                     model_fit_files=fparts, part_psi_files=qparts)
     merge_tables(parts, comparison_file)
     if delta_posterior_file is not None:
         merge_tables(dpsi_parts, delta_posterior_file)
@@ -509,9 +545,14 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
             if model_check_files is not None:
                 fpart = "%s.alone" % model_check_files[int(which) - 1]
                 fit_parts[int(which) - 1].append(fpart)
+            qpart = None
+            if part_psi_files is not None:
+                qpart = "%s.alone" % part_psi_files[int(which) - 1]
+                part_parts[int(which) - 1].append(qpart)
             sampler.run_sampler_batch(p["num_iters"], alone, num_chains=p["num_chains"], burn_in=p["burn_in"],
                                       lag=p["lag"], seed=s, verbose=verbose, diagnostics_file=dpart,
-                                      rank_diagnostics=rank_diagnostics, exact_stats_file=spart, model_fit_file=fpart)
+                                      rank_diagnostics=rank_diagnostics, exact_stats_file=spart, model_fit_file=fpart,
+                                      part_psi_file=qpart)
     if diagnostics_files is not None:
         for which in (0, 1):
             merge_tables(diag_parts[which], diagnostics_files[which])
@@ -521,6 +562,9 @@ def compare_gene_psi(gene_entries, bam1_filename, bam2_filename, output_dir1, ou
     if model_check_files is not None:
         for which in (0, 1):
             merge_tables(fit_parts[which], model_check_files[which])
+    if part_psi_files is not None:
+        for which in (0, 1, 2):
+            _merge_part_tables(part_parts[which], part_psi_files[which])
     return len(pairs)
 
 
@@ -573,6 +617,12 @@ def main(argv=None):
                          "posterior predictive check of its reads against the model's read classes (device-side)")
     ap.add_argument("--model-check-files", nargs=2, default=None, metavar=("FILE1", "FILE2"),
                     help="with --compare-genes-from-file, single-end: that table of each sample")
+    ap.add_argument("--part-psi-file", default=None, metavar="F",
+                    help="with --compute-genes-from-file: also write the `.miso_part_summary` table of this run, per part (exon) "
+                         "of every multi-isoform event the mean and credible interval of its inclusion (device-side)")
+    ap.add_argument("--part-psi-files", nargs=3, default=None, metavar=("FILE1", "FILE2", "FILE_D"),
+                    help="with --compare-genes-from-file: that table of each sample, and the `.miso_part_dpsi` table of the parts' "
+                         "delta psi over all pairs of the two samples' draws (thresholds: --delta-psi-thresholds)")
     ap.add_argument("--no-miso-files", action="store_true",
                     help="with --summary-file: only the table, no per-event .miso files")
     ap.add_argument("--exact", action="store_true",
@@ -625,6 +675,15 @@ def main(argv=None):
         ap.error("--model-check-file goes with --compute-genes-from-file")
     if a.model_check_files and not a.compare_genes_from_file:
         ap.error("--model-check-files goes with --compare-genes-from-file")
+    if a.part_psi_file and not a.compute_genes_from_file:
+        ap.error("--part-psi-file goes with --compute-genes-from-file")
+    if a.part_psi_files and not a.compare_genes_from_file:
+        ap.error("--part-psi-files goes with --compare-genes-from-file")
+    if a.part_psi_file or a.part_psi_files:
+        try:
+            _check_part_psi(Settings.get_sampler_params())
+        except ValueError as err:
+            ap.error("--part-psi-file(s): %s" % err)
     exact = bool(a.exact) or Settings.get_exact()       # the flag, or `exact = True` under [sampler] of the settings file
     if a.exact_paired and not paired_end:
         ap.error("--exact-paired goes with --paired-end")
@@ -683,7 +742,8 @@ def main(argv=None):
                                                    if a.delta_posterior_file else None),
                              exact_delta_file=(os.path.abspath(os.path.expanduser(a.exact_delta_file))
                                                if a.exact_delta_file else None),
-                             exact_stats_files=a.exact_stats_files, model_check_files=a.model_check_files)
+                             exact_stats_files=a.exact_stats_files, model_check_files=a.model_check_files,
+                             part_psi_files=a.part_psi_files)
         print("Compared %d genes" % n)
     elif a.compute_genes_from_file:
         genes_filename, bam_filename, output_dir = (os.path.abspath(os.path.expanduser(p))
@@ -700,7 +760,8 @@ def main(argv=None):
                          write_files=not (a.no_miso_files and a.summary_file),
                          diagnostics_file=a.diagnostics_file, exact=exact, exact_paired=exact_paired,
                          rank_diagnostics=a.rank_diagnostics, exact_stats_file=a.exact_stats_file,
-                         exact_pairs_file=a.exact_pairs_file, model_check_file=a.model_check_file)
+                         exact_pairs_file=a.exact_pairs_file, model_check_file=a.model_check_file,
+                         part_psi_file=a.part_psi_file)
         print("Processed %d genes" % len(entries))
     elif a.compute_gene_psi:
         gene_ids = a.compute_gene_psi[0].split(",")

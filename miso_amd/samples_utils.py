@@ -5,6 +5,8 @@
     python -m miso_amd.samples_utils --compare-samples SAMPLES_DIR1 SAMPLES_DIR2 OUTPUT_DIR
     python -m miso_amd.samples_utils --diagnose-samples SAMPLES_DIR OUTPUT_DIR [--num-chains C]
     python -m miso_amd.samples_utils --compare-groups DIR[,DIR...] DIR[,DIR...] OUTPUT_DIR [--group-labels L[,L...] L[,L...]]
+    python -m miso_amd.samples_utils --summarize-parts SAMPLES_DIR INDEX_DIR OUTPUT_DIR
+    python -m miso_amd.samples_utils --compare-parts SAMPLES_DIR1 SAMPLES_DIR2 INDEX_DIR OUTPUT_DIR
 
 The reference walks the samples directory (chromosome sub-directories of `<event>.miso`, or their packed form
 `<chrom>.miso_db`, samples_utils.py:263-411), parses every event's "%.4f" rows and computes per event the posterior
@@ -38,6 +40,10 @@ replicates from their exact posteriors, without a draw, from each directory's `s
 `--exact-paired-delta-posterior` is the same for paired-end replicates, from `summary/<name>.miso_exact_pairs`.
 With `--delta-posterior` every pair also gets its `.miso_dpsi`, and the two groups one pooled table, `.miso_group_dpsi`: delta
 psi over all differences between the pooled draws of the groups (capi.compare_pairs_groups).
+
+`--summarize-parts` and `--compare-parts` give part-level psi: the inclusion of every exon of a multi-isoform gene, the sum of
+the psi of the isoforms that hold it, with its credible interval, and its delta psi between two samples (part_psi.py;
+DESIGN.md 23).
 """
 import glob
 import os
@@ -46,7 +52,7 @@ import time
 
 import numpy as np
 
-from . import capi, compare, diagnostics, miso_db, summary
+from . import capi, compare, diagnostics, miso_db, part_psi, summary
 from .settings import Settings
 
 # The default decoder: `device`, because it is the faster one end to end (profiles/miso_text.txt: a tree of
@@ -1090,8 +1096,17 @@ def main(argv=None):
     ap.add_argument("--delta-psi-thresholds", nargs="+", type=float, default=None, metavar="T",
                     help="the thresholds T of --delta-posterior, --exact-delta-posterior and --exact-paired-delta-posterior, each "
                          "in (0, 1), at most four (default 0.1 0.2)")
+    ap.add_argument("--summarize-parts", nargs=3, metavar=("SAMPLES_DIR", "INDEX_DIR", "OUTPUT_DIR"),
+                    help="part-level psi (part_psi.py): mean and credible interval of every exon's inclusion, "
+                         "OUTPUT_DIR/summary/<name>.miso_part_summary; the gene models come from the index directory")
+    ap.add_argument("--compare-parts", nargs=4, metavar=("SAMPLES_DIR1", "SAMPLES_DIR2", "INDEX_DIR", "OUTPUT_DIR"),
+                    help="the same of either sample and delta psi over all pairs of their draws, per exon: "
+                         "<l1>_vs_<l2>.miso_part_dpsi (labels: --comparison-labels, thresholds: --delta-psi-thresholds)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    for opt, given in (("--summarize-parts", a.summarize_parts), ("--compare-parts", a.compare_parts)):
+        if given and not os.path.isdir(given[-2]):
+            ap.error("%s: no index directory %s" % (opt, given[-2]))
     if a.delta_posterior and not (a.compare_samples or a.compare_groups):      # argument errors, before any work
         # (both wordings: scripts and tests match on the older "goes with --compare-samples")
         ap.error("--delta-posterior needs --compare-samples or --compare-groups "
@@ -1105,7 +1120,7 @@ def main(argv=None):
     if a.group_names and not (a.compare_groups and (a.delta_posterior or a.exact_delta_posterior or a.exact_paired_delta_posterior)):
         ap.error("--group-names goes with --compare-groups --delta-posterior (or --exact-delta-posterior)")
     if a.delta_psi_thresholds is not None:
-        if not (a.delta_posterior or a.exact_delta_posterior or a.exact_paired_delta_posterior):
+        if not (a.delta_posterior or a.exact_delta_posterior or a.exact_paired_delta_posterior or a.compare_parts):
             ap.error("--delta-psi-thresholds goes with --delta-posterior")
         try:
             compare.check_delta_thresholds(a.delta_psi_thresholds)
@@ -1155,7 +1170,15 @@ def main(argv=None):
                 dirs1, dirs2, out_dir, delta_thresholds=a.delta_psi_thresholds, group_names=a.group_names)[::-1])
     elif a.group_labels:
         ap.error("--group-labels goes with --compare-groups")
-    if not a.summarize_samples and not a.compare_samples and not a.compare_groups and not a.diagnose_samples:
+    if a.summarize_parts:
+        samples_dir, index_dir, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.summarize_parts)
+        print("Summarized %d parts into %s" % part_psi.summarize_parts(samples_dir, index_dir, out_dir, device=a.device)[::-1])
+    if a.compare_parts:
+        d1, d2, index_dir, out_dir = (os.path.abspath(os.path.expanduser(p)) for p in a.compare_parts)
+        print("Compared %d parts into %s" % part_psi.compare_parts(d1, d2, index_dir, out_dir, sample_labels=a.comparison_labels,
+                                                                   delta_thresholds=a.delta_psi_thresholds, device=a.device)[::-1])
+    if not (a.summarize_samples or a.compare_samples or a.compare_groups or a.diagnose_samples or a.summarize_parts
+            or a.compare_parts):
         ap.print_help()
     return 0
 
